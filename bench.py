@@ -5,7 +5,10 @@ Metric (BASELINE.json): Mrays/s (primary+secondary) and ms/frame on scenes/cover
 1920x1080, recursion depth 5.  One "step" = one frame: Camera.render of the whole image with the
 flat scene already resident in HBM and the canvas left in HBM.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--scene cover.json] [--width 1920] [--height 1080]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--scene cover.json] [--width 1920] [--height 1080] [--dump-outputs DIR]
+
+--dump-outputs DIR writes the canvas of the last timed step to DIR/canvas.npy (f64; a seeded pixel sample above 64 MB).
+The inputs are a committed scene file and a fixed camera: the same arguments give the same inputs in every run.
 
 N == 1: one rtc_render_device launch per step.
 N  > 1: (launched by torch.distributed.run, one rank per GPU, backend nccl == RCCL)  the image is cut
@@ -344,6 +347,28 @@ def cpu_baseline(rtc, hs, cam, depth, target_seconds=12.0):
     }
 
 
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, name, image):
+    """Writes what the timed path computed (`image`: H x W x C on the host, float32 or float64) as out_dir/<name>.npy, so
+    that two builds can be compared output for output.  An image larger than DUMP_LIMIT_BYTES is written as a fixed,
+    seeded sample of its pixels instead: <name>_sample.npy (n x C) and <name>_sample_pixels.npy (the row-major pixel
+    indices of the sample, as float64), the same pixels for the same image size in every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if image.nbytes <= DUMP_LIMIT_BYTES - 4096:
+        np.save(os.path.join(out_dir, name + ".npy"), image)
+        return [name + ".npy"]
+    pixels = image.reshape(-1, image.shape[-1])
+    n = (DUMP_LIMIT_BYTES - 4096) // (pixels.itemsize * pixels.shape[1] + 8)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(pixels.shape[0], size=n, replace=False))
+    np.save(os.path.join(out_dir, name + "_sample.npy"), pixels[idx])
+    np.save(os.path.join(out_dir, name + "_sample_pixels.npy"), idx.astype(np.float64))
+    return [name + "_sample.npy", name + "_sample_pixels.npy"]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -374,7 +399,13 @@ def main():
     ap.add_argument("--rehearse", action="store_true",
                     help="N ranks on ONE GPU over gloo (tiles staged through host memory): exercises the N > 1 code "
                          "path where only one GPU exists; the numbers mean nothing")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (the f64 canvas; the RGBA8 "
+                         "framebuffer as float32 with --output rgba8), at most 64 MB: a larger image is a fixed, seeded sample "
+                         "of its pixels")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # stdout carries exactly ONE line (the JSON): libraries that chat on fd 1 (RCCL prints a version banner
     # there at communicator creation) are sent to stderr for the duration of the run.
@@ -582,6 +613,17 @@ def main():
                 "gather_unpermute_ms": float(np.mean([a.elapsed_time(b) for a, b in comm_ev])) if comm_ev else None}
         per_rank = [None] * world
         dist.all_gather_object(per_rank, mine)
+
+    if args.dump_outputs and rank == 0:
+        # the last timed step's output, as its caller receives it (finish() + barrier() above: the frame is complete)
+        if world == 1 and not args.tile_path:
+            name, image = "canvas", canvases[(args.steps - 1) % M].cpu().numpy()
+        elif args.output == "rgba8":
+            name, image = "framebuffer_rgba8", framebuffer.cpu().numpy().view(np.uint8).reshape(H, W, 4).astype(np.float32)
+        else:
+            name, image = "canvas", canvas.cpu().numpy()
+        written = dump_outputs(args.dump_outputs, name, image)
+        print("dumped %s to %s" % (", ".join(written), args.dump_outputs), file=sys.stderr)
 
     if args.check and rank == 0:
         ref = torch.empty((H, W, 3), dtype=torch.float64, device="cuda")

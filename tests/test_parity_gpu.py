@@ -1793,16 +1793,17 @@ def test_moving_view_measured_every_nth_frame(rtc):
         rtc.set_option("measure_every", 1)
 
 
-def test_bench_multi_rank_path_rehearsal():
+def test_bench_multi_rank_path_rehearsal(rtc, tmp_path):
     """bench.py's N > 1 code path (tile split, gather, rtc_assemble_tiles_device, stats reduction, the JSON line) with
-    two ranks on the ONE GPU of this box over gloo (--rehearse); real RCCL runs over N GPUs are the driver's."""
+    two ranks on the ONE GPU of this box over gloo (--rehearse); real RCCL runs over N GPUs are the driver's.  Rank 0's
+    --dump-outputs: the assembled canvas, then the RGBA8 framebuffer (as float32) of the same frame."""
     import json
     import subprocess
     import sys
     repo = _os.path.dirname(_os.path.dirname(_os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29541", _os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--width", "480", "--height", "270", "--rehearse", "--check"]
+           "--width", "480", "--height", "270", "--dump-outputs", str(tmp_path), "--rehearse", "--check"]
     out = subprocess.run(cmd, cwd=repo, capture_output=True, text=True, timeout=200)
     assert out.returncode == 0, out.stderr[-2000:]
     assert "check ok" in out.stderr
@@ -1820,22 +1821,33 @@ def test_bench_multi_rank_path_rehearsal():
     assert out.returncode == 0, out.stderr[-2000:]
     assert "check ok: assembled RGBA8 framebuffer" in out.stderr
     assert json.loads([l for l in out.stdout.splitlines() if l.strip()][0])["config"]["output"].startswith("RGBA8")
+    canvas = np.load(tmp_path / "canvas.npy")
+    rgba = np.load(tmp_path / "framebuffer_rgba8.npy")
+    assert canvas.dtype == np.float64 and canvas.shape == (270, 480, 3) and np.isfinite(canvas).all()
+    assert rgba.dtype == np.float32 and rgba.shape == (270, 480, 4)
+    assert np.abs(rgba - rtc.canvas_rgba8(canvas).astype(np.float32)).max() <= 1
 
 
-def test_bench_frames_in_flight():
+def test_bench_frames_in_flight(rtc, tmp_path):
     """bench.py --inflight 2 on one GPU: two handles, streams and canvases, frames dealt round-robin; the last frame is
-    checked against a plain render."""
+    checked against a plain render.  --dump-outputs writes that frame: it is the render of the same camera here."""
     import json
     import subprocess
     import sys
     repo = _os.path.dirname(_os.path.dirname(_os.path.abspath(__file__)))
     cmd = [sys.executable, _os.path.join(repo, "bench.py"), "--steps", "5", "--warmup", "1", "--settle-frames", "4", "--width", "320",
-           "--height", "180", "--inflight", "2", "--no-cpu-baseline", "--no-extras", "--check"]
+           "--height", "180", "--inflight", "2", "--no-cpu-baseline", "--no-extras", "--check", "--dump-outputs", str(tmp_path)]
     out = subprocess.run(cmd, cwd=repo, capture_output=True, text=True, timeout=200)
     assert out.returncode == 0, out.stderr[-2000:]
     assert "check ok" in out.stderr
     line = json.loads([l for l in out.stdout.splitlines() if l.strip()][0])
     assert line["config"]["frames_in_flight"] == 2 and line["n_gpus"] == 1 and line["value"] > 0
+    assert line["steps"] == 5 and line["ms_per_step"] > 0
+    dumped = np.load(tmp_path / "canvas.npy")
+    hs = rtc.HostScene.from_file("cover.json")
+    want = rtc.GpuScene(hs.desc).render(hs.camera(320, 180), 5)
+    assert dumped.dtype == np.float64 and dumped.shape == want.shape == (180, 320, 3)
+    assert np.abs(dumped - want).max() < REPEAT_TOL
 
 
 def _json_scene(objects, lights, w=24, h=16):
