@@ -64,7 +64,11 @@ extern "C" __global__ void rtc_render_kernel_bigworld_ext(const DevScene S, cons
                                                           DevStats* __restrict__ stats, DevStats* __restrict__ next_stats);
 extern "C" __global__ void rtc_estimate_kernel(const DevScene S, const DevCamera cam, const DevPixelMap map,
                                                uint32_t* __restrict__ chunk_cost, uint32_t* __restrict__ chunk_time,
-                                               DevChunkShape* __restrict__ chunk_shape, DevPackState* __restrict__ state);
+                                               DevChunkShape* __restrict__ chunk_shape, DevPackState* __restrict__ state
+#ifdef RTC_PROFILE
+                                               , unsigned long long* __restrict__ oob
+#endif
+                                               );
 extern "C" __global__ void rtc_chunk_cost_kernel(const uint32_t* __restrict__ cost, const DevPixelMap map, const uint32_t max_depth,
                                                  uint32_t* __restrict__ chunk_cost, uint32_t* __restrict__ chunk_time,
                                                  DevChunkShape* __restrict__ chunk_shape, DevPackState* __restrict__ state);
@@ -492,6 +496,17 @@ int updateSchedule(rtc_scene* s, const rtc_camera& cam, DevPixelMap& map, uint32
 // pinned host memory behind an event (see updateSchedule).  Nothing here waits.
 enum class PackFrom { Measurement, Estimate };
 
+#ifdef RTC_PROFILE
+// The handle's count of rtc_estimate_kernel's root-table indices outside their allocation, over all its estimates (the
+// launch counters are cleared after that kernel has run).
+hipError_t ensureEstimateOob(rtc_scene* s, hipStream_t stream) {
+  if (s->d_estimate_oob) return hipSuccess;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->d_estimate_oob), sizeof(unsigned long long));
+  if (e == hipSuccess) e = hipMemsetAsync(s->d_estimate_oob, 0, sizeof(unsigned long long), stream);
+  return e;
+}
+#endif
+
 int packNextSchedule(rtc_scene* s, const rtc_camera& cam, const DevPixelMap& map, uint32_t max_depth, hipStream_t stream,
                      PackFrom from) {
   const bool unmeasured = from != PackFrom::Measurement;  // (no frame has been measured: nothing to read back)
@@ -503,8 +518,14 @@ int packNextSchedule(rtc_scene* s, const rtc_camera& cam, const DevPixelMap& map
   const uint32_t prev_packets = map.order == nullptr ? n : map.n_units;  // (device-packed: an upper bound)
   if (from == PackFrom::Estimate) {
     // no frame has run yet: what every chunk is likely to cost, from the roots its pixels look at (in ticks already)
+#ifndef RTC_PROFILE
     hipLaunchKernelGGL(rtc_estimate_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, s->dev, devCamera(cam), map, s->d_chunk_cost,
                        s->d_chunk_time, s->d_chunk_shape, s->d_pack_state);
+#else
+    HIP_TRY(ensureEstimateOob(s, stream));
+    hipLaunchKernelGGL(rtc_estimate_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, s->dev, devCamera(cam), map, s->d_chunk_cost,
+                       s->d_chunk_time, s->d_chunk_shape, s->d_pack_state, s->d_estimate_oob);
+#endif
   } else {
     hipLaunchKernelGGL(rtc_chunk_cost_kernel, dim3((n + 3u) / 4u), dim3(256), 0, stream, s->d_cost, map, max_depth, s->d_chunk_cost,
                        s->d_chunk_time, s->d_chunk_shape, s->d_pack_state);
@@ -554,6 +575,9 @@ int ensureScratch(rtc_scene* s, DevPixelMap& map, uint32_t blocks, uint32_t max_
   }
   map.ray_stack = static_cast<PendingRec*>(s->d_ray_stack);
   map.ray_stack_levels = max_depth + 2u;
+#ifdef RTC_PROFILE
+  map.ray_stack_waves = static_cast<uint32_t>(s->ray_stack_capacity / (static_cast<size_t>(map.ray_stack_levels) * 64u * 64u));
+#endif
   // Measured with 1 / 16 / 32 / 48 / 64: cover 0.96 / 0.93 / 0.92 / 0.90 / 0.88 ms, reflection_and_refraction depth 8
   // 3.29 / 3.24 / 3.16 / 3.05 / 2.84 ms, dragons 4K 8.33 / 7.99 / 7.59 / 7.18 / 6.60 ms: a wave that finishes its
   // packet before it starts the next keeps neighbouring pixels (the same objects, materials, BVH paths) together;
@@ -652,6 +676,9 @@ int launch(rtc_scene* s, const rtc_camera& cam, const DevPixelMap& map_in, uint3
     idle.packet_time = nullptr;
     idle.ray_stack = static_cast<PendingRec*>(s->d_ray_stack);
     idle.ray_stack_levels = 2;
+#ifdef RTC_PROFILE
+    idle.ray_stack_waves = static_cast<uint32_t>(s->ray_stack_capacity / (2u * 64u * 64u));
+#endif
     idle.pull_min_idle = 64;
     const KernelChoice kernel = renderKernel(s, map);
     DevScene dev = s->dev;
@@ -1994,6 +2021,12 @@ int uploadTables(const rtc_scene_desc& d, const SceneTraits& traits, const HostT
   D.bvh8 = s->tab->bvh8.p;
   D.n_bvh_nodes = static_cast<uint32_t>(RTC_BVH8 ? T.bvh8_nodes.size() : bvh4_nodes.size());
   D.n_bvh_leaves = static_cast<uint32_t>(walk_leaves.size());
+#ifdef RTC_PROFILE
+  D.n_root_recs = static_cast<uint32_t>(T.root_recs.size());
+  D.n_root_cull = static_cast<uint32_t>(T.root_cull.size() / 2u);
+  D.n_root_box = static_cast<uint32_t>(T.root_box.size() / 2u);
+  D.n_root_weight = static_cast<uint32_t>(T.root_weight.size());
+#endif
   D.bvh_leaf = s->tab->bvh_leaf.p;
   D.leaf_parent = s->tab->leaf_parent.p;
   D.node_parent = s->tab->node_parent.p;
@@ -2167,6 +2200,9 @@ void rtc_scene_destroy(rtc_scene* s) {
   if (s->d_sorted) (void)hipFree(s->d_sorted);
   if (s->d_cost) (void)hipFree(s->d_cost);
   if (s->d_chunk_cost) (void)hipFree(s->d_chunk_cost);
+#ifdef RTC_PROFILE
+  if (s->d_estimate_oob) (void)hipFree(s->d_estimate_oob);
+#endif
   if (s->d_packet_time) (void)hipFree(s->d_packet_time);
   if (s->launch_done) (void)hipEventDestroy(s->launch_done);
   if (s->d_ray_stack) (void)hipFree(s->d_ray_stack);
@@ -2771,8 +2807,18 @@ int rtc_get_chunk_times(rtc_scene* s, const rtc_camera* cam, uint32_t* estimated
       release();
       return fail(RTC_ERR_OUT_OF_MEMORY, "no stream");
     }
+#ifndef RTC_PROFILE
     hipLaunchKernelGGL(rtc_estimate_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s->stream, s->dev, devCamera(*cam), map, d_est, d_time,
                        d_shape, d_state);
+#else
+    if (ensureEstimateOob(s, s->stream) != hipSuccess) {
+      (void)hipGetLastError();
+      release();
+      return fail(RTC_ERR_OUT_OF_MEMORY, "estimate counter");
+    }
+    hipLaunchKernelGGL(rtc_estimate_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s->stream, s->dev, devCamera(*cam), map, d_est, d_time,
+                       d_shape, d_state, s->d_estimate_oob);
+#endif
     const hipError_t e1 = hipStreamSynchronize(s->stream);
     const hipError_t e2 = e1 == hipSuccess ? hipMemcpy(estimated, d_est, n * sizeof(uint32_t), hipMemcpyDeviceToHost) : e1;
     release();
@@ -2821,6 +2867,13 @@ int rtc_get_stats(rtc_scene* s, rtc_stats* out) {
     std::fprintf(stderr, "rtc walks: %llu lanes %llu node-steps %llu leaf-steps %llu lanes-at-nodes %llu lanes-at-leaves %llu | without a leaf: %llu walks | %s %llu\n",
                  h.prof4[0], h.prof4[1], h.prof4[2], h.prof4[3], h.prof4[4], h.prof4[5], h.prof4[6], RTC_BVH8 ? "bad refs" : "their node-steps", h.prof4[7]);
     std::fprintf(stderr, "rtc walk cycles: at nodes %llu at leaves %llu\n", h.prof5[5], h.prof5[6]);
+    // (accesses outside their allocation that the checks refused to make, by kind - must all be 0; the estimate kernel's
+    // root-table reads summed over the handle's life)
+    unsigned long long est = 0ull;
+    if (s->d_estimate_oob) HIP_TRY(hipMemcpy(&est, s->d_estimate_oob, sizeof est, hipMemcpyDeviceToHost));
+    std::fprintf(stderr, "rtc out of bounds: roots %llu staging %llu materials %llu patterns %llu lights %llu pending %llu canvas %llu estimate-roots %llu\n",
+                 h.oob[RTC_OOB_ROOTS], h.oob[RTC_OOB_STAGING], h.oob[RTC_OOB_MATERIALS], h.oob[RTC_OOB_PATTERNS], h.oob[RTC_OOB_LIGHTS],
+                 h.oob[RTC_OOB_PENDING], h.oob[RTC_OOB_CANVAS], est);
     for (int k = 0; k < 3; ++k)
       std::fprintf(stderr, "rtc walks of %s traces: %llu lanes %llu node-steps %llu leaf-steps %llu lanes-at-nodes %llu lanes-at-leaves %llu cycles-at-nodes %llu cycles-at-leaves %llu\n",
                    k == 0 ? "closest" : k == 1 ? "shadow" : "containers", h.prof6[8 * k], h.prof6[8 * k + 1], h.prof6[8 * k + 2], h.prof6[8 * k + 3],

@@ -222,6 +222,9 @@ struct DevScene {
   const Bvh4Node* __restrict__ bvh;     // all groups' BVHs; RootRec::geom = root node of a group's BVH (RTC_BVH8 == 0)
   const Bvh8Node* __restrict__ bvh8;    // ... as eight-wide compressed nodes (RTC_BVH8 == 1)
   uint32_t n_bvh_nodes, n_bvh_leaves;   // sizes of bvh / bvh8 and bvh_leaf (the RTC_PROFILE build checks every reference against them)
+#ifdef RTC_PROFILE
+  uint32_t n_root_recs, n_root_cull, n_root_box, n_root_weight;  // ... and of the root tables as allocated: records, pairs, pairs, floats
+#endif
   const BvhLeafRec* __restrict__ bvh_leaf; // the leaves referenced by the nodes' leaf ranges
   const uint32_t* __restrict__ leaf_parent;  // reference Group node directly above each leaf (RTC_NO_LEAF: none)
   const uint32_t* __restrict__ node_parent;  // reference Group above each Group node (RTC_NO_LEAF: none)
@@ -296,6 +299,10 @@ struct DevPixelMap {
   // 64 bytes, owned by the scene handle and sized for the launch (max_depth + 2 levels).
   PendingRec* __restrict__ ray_stack;
   uint32_t ray_stack_levels;
+#ifdef RTC_PROFILE
+  uint32_t ray_stack_waves;  // waves the buffer's CAPACITY holds ray_stack_levels levels for (the RTC_PROFILE build checks every slot
+                             // against it: an access outside the allocation, not a slot of a wave this launch does not have)
+#endif
   uint32_t pull_min_idle;  // a wave pulls its next packet only when at least this many lanes are idle (or none has a ray)
   uint32_t row_packets;    // without a schedule (`order` null): != 0: packet c is ROW c % 8 of chunk c / 8 (n_units = 8 n_chunks), else chunk c whole
 };
@@ -335,6 +342,16 @@ struct DevPackState {
 // all of it in one 48-byte block - 2048 waves x 4 counters + the pulls - the queue on that line WAS the end of the frame
 // (cover.json 1080p 0.70 ms; 0.66 with the work counter by chance in the other half of the line; 0.605 with a line per
 // counter; 0.575 with the counts summed per work-group first, a quarter of the atomics).
+// What the RTC_PROFILE build counts in DevStats::oob (and skips): an index into a table, a staging copy, a pending-ray
+// slot or a canvas write outside what was allocated for it.
+#define RTC_OOB_ROOTS 0      // root_recs / root_cull / root_box / root_weight, in memory or as staged into LDS
+#define RTC_OOB_STAGING 1    // a staging copy's source past its table, or its destination past the __shared__ array
+#define RTC_OOB_MATERIALS 2
+#define RTC_OOB_PATTERNS 3
+#define RTC_OOB_LIGHTS 4
+#define RTC_OOB_PENDING 5    // a slot of DevPixelMap::ray_stack outside the waves and levels it was sized for
+#define RTC_OOB_CANVAS 6     // a canvas / tile / cost write outside the launch's output
+#define RTC_OOB_KINDS 7
 struct DevStats {
   alignas(128) unsigned int next_chunk;  // work counter of the persistent waves
   alignas(128) unsigned long long primary;
@@ -350,6 +367,7 @@ struct DevStats {
   unsigned long long prof3[21]; // wave cycles in traces by lanes with a ray: [closest, shadow, behind][1-2, 3-4, 5-8, 9-16, 17-32, 33-48, 49-64]
   unsigned long long prof5[8];  // [5], [6]: wave cycles of all group walks at nodes / at leaves (the other slots: free)
   unsigned long long prof6[24]; // group walks by kind of trace [closest, shadow, containers][walks, lanes, node steps, leaf steps, lanes at nodes, lanes at leaves, wave cycles at nodes, at leaves]
+  unsigned long long oob[8];    // accesses outside their allocation, counted and not made (RTC_OOB_*)
   unsigned long long prof4[8];  // group walks: walks of a wave, their lanes, wave steps at nodes, at leaves, lanes at nodes, at leaves (summed over the steps), walks that reach no leaf, their node steps
   unsigned long long prof_t0, prof_t1, prof_busy;  // shortest / longest / summed wave lifetime
   unsigned long long prof_log[4096][4];            // per wave: lifetime, iterations, units, first<<32|last unit

@@ -191,6 +191,9 @@ struct rtc_scene {
   size_t cost_capacity = 0;
   std::vector<uint32_t> cost_key;  // pixel map the costs / the schedule belong to
   uint32_t* d_chunk_cost = nullptr;  // per-chunk sums of d_cost (rtc_chunk_cost_kernel)
+#ifdef RTC_PROFILE
+  unsigned long long* d_estimate_oob = nullptr;  // root-table indices of rtc_estimate_kernel outside their allocation (diagnostic builds)
+#endif
   size_t chunk_cost_capacity = 0;
   uint32_t* d_packet_time = nullptr;  // per packet of the measured schedule: the time its wave needed (DevPixelMap::packet_time)
   size_t packet_time_capacity = 0;

@@ -109,6 +109,26 @@ __shared__ unsigned long long rtc_prof_counts[4][40];
 #define RTC_KIND_ADD(slot, n) do { } while (0)
 #endif
 
+// Diagnostic builds (-DRTC_PROFILE) also check what the render kernels index against what was allocated for it: an
+// access outside is counted in DevStats::oob by kind (RTC_OOB_*, printed by rtc_get_stats) and not made - the index
+// becomes 0 or the access is skipped.  A check never traps.  In the product build RTC_IN_BOUNDS is `true` and
+// RTC_CHECK_INDEX the index itself.
+#ifdef RTC_PROFILE
+// what the launch's root loop and shading may index: root records, sphere pairs, box pairs, materials, patterns, light
+// words - the tables in memory as allocated, or what the staging copies put into LDS
+__shared__ uint32_t rtc_oob_avail[6];
+__device__ __forceinline__ bool rtc_in_bounds(uint32_t kind, bool ok) {
+  if (!ok) atomicAdd(&rtc_prof_stats->oob[kind], 1ull);
+  return ok;
+}
+#define RTC_IN_BOUNDS(kind, ok) rtc_in_bounds(kind, ok)
+#define RTC_CHECK_INDEX(kind, i, n) (rtc_in_bounds(kind, (i) < (n)) ? (i) : 0u)
+#define RTC_AVAIL(k) rtc_oob_avail[k]
+#else
+#define RTC_IN_BOUNDS(kind, ok) true
+#define RTC_CHECK_INDEX(kind, i, n) (i)
+#endif
+
 // Bound experiments (WRONG images, right dependency chains; never set in the product): bit 0: no shadow ray is traced;
 // bit 1: the walks of shadow rays visit no leaf (what their node phase alone costs); bit 2: triangles are tested in FP32
 // (what VERDICT r04 item 2's pre-test could save at the very most: every exact test replaced, not a survivor left).
@@ -1326,8 +1346,14 @@ __device__ __forceinline__ void trace(const DevScene& S, const RootRec* __restri
 #else
         const uint32_t whole = nc;
 #endif
+#ifdef RTC_PROFILE
+        // (the pairs this block reads: two per step of four roots, and one for the half step)
+        const bool reads_ok = RTC_IN_BOUNDS(RTC_OOB_ROOTS, (base >> 1) + 2u * ((whole + 3u) >> 2) + (whole < nc ? 1u : 0u) <= RTC_AVAIL(2));
+#else
+        constexpr bool reads_ok = true;
+#endif
 #pragma unroll 1
-        for (uint32_t first = 0; first < whole; first += 4u) {
+        for (uint32_t first = 0; reads_ok && first < whole; first += 4u) {
           const uint32_t k = roots_kept_box4<V, !FLAT>(block, ax, ay, az, rf);
           mine |= static_cast<unsigned long long>(k) << first;
           block += 2u * sizeof(RootBoxPair);
@@ -1336,11 +1362,14 @@ __device__ __forceinline__ void trace(const DevScene& S, const RootRec* __restri
           az += 2u * sizeof(RootBoxPair);
         }
 #if RTC_CULL_HALF_STEP
-        if (whole < nc) mine |= static_cast<unsigned long long>(roots_kept_box<V, !FLAT>(block, ax, ay, az, rf)) << whole;
+        if (reads_ok && whole < nc) mine |= static_cast<unsigned long long>(roots_kept_box<V, !FLAT>(block, ax, ay, az, rf)) << whole;
 #endif
       }
     } else {
       for (uint32_t i = 4u * member; i < nc; i += 4u * stride) {
+#ifdef RTC_PROFILE
+        if (!RTC_IN_BOUNDS(RTC_OOB_ROOTS, ((base + i) >> 1) + ((BOX && !(i + 2u < nc)) ? 1u : 2u) <= RTC_AVAIL(BOX ? 2 : 1))) continue;
+#endif
         unsigned long long k;
         if constexpr (BOX) {
           const char* const p0 = reinterpret_cast<const char*>(cull.box + ((base + i) >> 1));
@@ -1380,7 +1409,7 @@ __device__ __forceinline__ void trace(const DevScene& S, const RootRec* __restri
     };
     auto leaf_of_kind = [&](auto kind_tag, const uint32_t root) {
       constexpr uint32_t KIND = decltype(kind_tag)::value;
-      const RootRec& R = recs[root];
+      const RootRec& R = recs[RTC_CHECK_INDEX(RTC_OOB_ROOTS, root, RTC_AVAIL(0))];
       const uint32_t kf = R.kind_flags;
       const Ray lr = xform_ray(R.inv, ray);  // Shape.intersect: ray.transform(_inverse_transform)
       const CylParams cy{0.0, 0.0, false};
@@ -1426,8 +1455,13 @@ __device__ __forceinline__ void trace(const DevScene& S, const RootRec* __restri
         // Every lane holds every plane of the block (phase 1 has no say about them): the loop over them is the WAVE's -
         // one record address for all lanes, no per-lane bit scan, no integer multiply for a per-lane record address
         // (reflection_and_refraction runs six plane tests in every one of its 45 M traces).
+        // (the planes of the block are its roots [base + nc, base + n).  The loop used to start at max(n_bounded, base) -
+        // the same iterations in the source - and a world of 63 bounded roots whose planes reach into a second block
+        // rendered a dozen pixels off the oracle, with fewer shadow rays, in one-lane traces only: the compiled loop did
+        // not do what the source says.  Started at `base` with the bounded roots skipped, or with the planes taken from
+        // `mine` as a cooperative trace takes them, it was exact; so is this form.  tests/test_table_limits_gpu.py, bounded63-*)
         const uint32_t p1 = base + n;
-        for (uint32_t root = max(n_bounded, base); root < p1; ++root) {
+        for (uint32_t root = base + nc; root < p1; ++root) {
           if (__all(vis.done())) break;
           if (!vis.done()) leaf_of_kind(std::integral_constant<uint32_t, 1u>{}, root);
         }
@@ -1443,7 +1477,7 @@ __device__ __forceinline__ void trace(const DevScene& S, const RootRec* __restri
     while (mine != 0ull && !vis.done()) {
       const uint32_t bit = static_cast<uint32_t>(__builtin_ctzll(mine));
       mine &= mine - 1ull;
-      const RootRec& R = recs[base + bit];
+      const RootRec& R = recs[RTC_CHECK_INDEX(RTC_OOB_ROOTS, base + bit, RTC_AVAIL(0))];
       const uint32_t kf = R.kind_flags;
       if (FLAT || !(kf & RTC_ROOT_IS_GROUP)) {
         if (!FLAT && V::kAnyHit && ((kf >> 8) & 1u) == 0u) continue;  // (a shadow trace: a shape that casts no shadow, see visit_leaf)
@@ -2229,12 +2263,48 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
       double* dst = reinterpret_cast<double*>(dst_);
       for (uint32_t i = threadIdx.x; i < n_words; i += blockDim.x) dst[i] = src[i];
     };
+#ifndef RTC_PROFILE
     stage(lds_recs, S.root_recs, S.n_roots * (sizeof(RootRec) / 8u));
     if constexpr (BOX) stage(lds_box, S.root_box, ((S.n_roots + 7u) & ~7u) / 2u * (sizeof(RootBoxPair) / 8u));
     else stage(lds_cull, S.root_cull, ((S.n_roots + 3u) & ~3u) / 2u * (sizeof(RootCullPair) / 8u));
     stage(lds_mat, S.mat, S.n_materials * (sizeof(DevMaterial) / 8u));
     stage(lds_pat, S.pat, S.n_patterns * (sizeof(DevPattern) / 8u));
     stage(lds_light, S.light, S.n_lights * 6u);
+#else
+    // (the same copies, each held against its table's allocation and its array's length: a copy past either is counted
+    // and cut short, and what the root loop and the shading may index is what was staged)
+    auto words = [&](uint32_t n, size_t src_words, size_t dst_words) -> uint32_t {
+      const uint32_t m = static_cast<uint32_t>(min(static_cast<size_t>(n), min(src_words, dst_words)));
+      if (threadIdx.x == 0u) (void)RTC_IN_BOUNDS(RTC_OOB_STAGING, m == n);
+      return m;
+    };
+    constexpr uint32_t W_REC = sizeof(RootRec) / 8u, W_CULL = sizeof(RootCullPair) / 8u, W_BOX = sizeof(RootBoxPair) / 8u,
+                       W_MAT = sizeof(DevMaterial) / 8u, W_PAT = sizeof(DevPattern) / 8u;
+    const uint32_t w_recs = words(S.n_roots * W_REC, static_cast<size_t>(S.n_root_recs) * W_REC, sizeof lds_recs / 8u);
+    stage(lds_recs, S.root_recs, w_recs);
+    uint32_t w_box = 0u, w_cull = 0u;
+    if constexpr (BOX) {
+      w_box = words(((S.n_roots + 7u) & ~7u) / 2u * W_BOX, static_cast<size_t>(S.n_root_box) * W_BOX, sizeof lds_box / 8u);
+      stage(lds_box, S.root_box, w_box);
+    } else {
+      w_cull = words(((S.n_roots + 3u) & ~3u) / 2u * W_CULL, static_cast<size_t>(S.n_root_cull) * W_CULL, sizeof lds_cull / 8u);
+      stage(lds_cull, S.root_cull, w_cull);
+    }
+    const uint32_t w_mat = words(S.n_materials * W_MAT, static_cast<size_t>(S.n_materials) * W_MAT, sizeof lds_mat / 8u);
+    stage(lds_mat, S.mat, w_mat);
+    const uint32_t w_pat = words(S.n_patterns * W_PAT, static_cast<size_t>(S.n_patterns) * W_PAT, sizeof lds_pat / 8u);
+    stage(lds_pat, S.pat, w_pat);
+    const uint32_t w_light = words(S.n_lights * 6u, static_cast<size_t>(S.n_lights) * 6u, sizeof lds_light / 8u);
+    stage(lds_light, S.light, w_light);
+    if (threadIdx.x == 0u) {
+      rtc_oob_avail[0] = w_recs / W_REC;
+      rtc_oob_avail[1] = w_cull / W_CULL;
+      rtc_oob_avail[2] = w_box / W_BOX;
+      rtc_oob_avail[3] = w_mat / W_MAT;
+      rtc_oob_avail[4] = w_pat / W_PAT;
+      rtc_oob_avail[5] = w_light;
+    }
+#endif
     __syncthreads();
     recs = lds_recs;
     cull.sphere = lds_cull;
@@ -2243,6 +2313,22 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
     pats = lds_pat;
     lights = lds_light;
   }
+#ifdef RTC_PROFILE
+  if (!LDS) {  // (the tables in memory, as allocated)
+    if (threadIdx.x == 0u) {
+      rtc_oob_avail[0] = S.n_root_recs;
+      rtc_oob_avail[1] = S.n_root_cull;
+      rtc_oob_avail[2] = S.n_root_box;
+      rtc_oob_avail[3] = S.n_materials;
+      rtc_oob_avail[4] = S.n_patterns;
+      rtc_oob_avail[5] = 6u * S.n_lights;
+    }
+    __syncthreads();
+  }
+  // the launch's output: the rectangle, or the rank's tiles
+  const size_t out_extent = map.mode == 0u ? static_cast<size_t>(map.w) * map.h : static_cast<size_t>(map.n_my_tiles) * map.tile_w * map.tile_h;
+  const bool stack_ok = (static_cast<size_t>(blockIdx.x) * 4u + (threadIdx.x >> 6)) < map.ray_stack_waves;
+#endif
   const uint32_t lane = threadIdx.x & 63u;
   // (bits of a ballot below this lane, by mask and popcount.  v_mbcnt_lo / v_mbcnt_hi would do it in two instructions and
   // without the mask's two registers - and the three-wave kernel's register allocation comes out worse for it: 117
@@ -2296,11 +2382,17 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
     if (level < LDS_LEVELS) {
       store_pending_lds(pend_wave + level * 256 + lane, p);
     } else {
+#ifdef RTC_PROFILE
+      if (!RTC_IN_BOUNDS(RTC_OOB_PENDING, stack_ok && static_cast<uint32_t>(level) < map.ray_stack_levels)) return;
+#endif
       store_pending(stack + static_cast<size_t>(level) * 64u, p);
     }
   };
   auto load_level = [&](int level, uint32_t of_lane) -> Pending {
     if (level < LDS_LEVELS) return load_pending_lds(pend_wave + level * 256 + of_lane);
+#ifdef RTC_PROFILE
+    if (!RTC_IN_BOUNDS(RTC_OOB_PENDING, stack_ok && static_cast<uint32_t>(level) < map.ray_stack_levels && of_lane < 64u)) return Pending{};
+#endif
     return load_pending(stack + static_cast<size_t>(level) * 64u - lane + of_lane);
   };
 
@@ -2329,7 +2421,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
         have_cur = true;
       } else {
         sp = base = 0;
-        if (has_pixel) {
+        if (has_pixel && RTC_IN_BOUNDS(RTC_OOB_CANVAS, out_index < out_extent)) {
           double* __restrict__ o = out + 3 * out_index;  // Canvas pixel, canvas.zig:132-137
           const double acc_r = acc[0], acc_g = acc[1], acc_b = acc[2];
           if (!shared) {  // the whole ray tree ran in this lane: the pixel is written exactly once
@@ -2359,6 +2451,12 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
           share_rays = 0u;
           has_pixel = false;
         }
+#ifdef RTC_PROFILE
+        else if (has_pixel) {  // (a pixel outside the output: counted above, not written)
+          share_rays = 0u;
+          has_pixel = false;
+        }
+#endif
       }
     }
     RTC_STAMP(8);
@@ -2376,7 +2474,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
         const uint32_t drank = bits_below(dmask);
         if (donor && drank < pairs) {
           mailbox[drank] = uint4{lane, static_cast<uint32_t>(base++), static_cast<uint32_t>(out_index), static_cast<uint32_t>(out_index >> 32)};
-          if (!shared) {
+          if (!shared && RTC_IN_BOUNDS(RTC_OOB_CANVAS, out_index < out_extent)) {
             // First hand-out of this pixel: from here on its shares are ADDED, so it starts from zero.  The canvas is
             // not cleared per launch (a pixel nobody shares is stored once); the store is at L2 before the taker —
             // a lane of this wave — can issue its first atomic.
@@ -2627,7 +2725,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
     const double* M = M_copy;
     DevCyl hcy{0.0, 0.0, 0u, 0u};
     if (FLAT || hv.root != RTC_NO_LEAF) {  // (a world without groups: every hit is a top-level object)
-      const RootRec& R = recs[hv.root];
+      const RootRec& R = recs[RTC_CHECK_INDEX(RTC_OOB_ROOTS, hv.root, RTC_AVAIL(0))];
       if constexpr (FLAT) {
 #pragma unroll
         for (int i = 0; i < 12; ++i) M_copy[i] = R.inv[i];
@@ -2647,6 +2745,9 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
       mat_index = meta.z;
       if (kind == 3u || kind == 6u) hcy = S.cyl[geom];
     }
+#ifdef RTC_PROFILE
+    mat_index = RTC_CHECK_INDEX(RTC_OOB_MATERIALS, mat_index, RTC_AVAIL(3));
+#endif
     RTC_STAMP(10);
     const double t = hv.t;
     // ---- n1 / n2 of PreComputations.new (world.zig:229-255), needed only if a refracted ray can be
@@ -2667,11 +2768,11 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
         RTC_STAMP(6);
       bv.flush();
       const double hit_ior = mats[mat_index].ior;
-      if (bv.best_leaf != RTC_NO_LEAF) n1 = mats[bv.best_mat].ior;
+      if (bv.best_leaf != RTC_NO_LEAF) n1 = mats[RTC_CHECK_INDEX(RTC_OOB_MATERIALS, bv.best_mat, RTC_AVAIL(3))].ior;
       if (!bv.hit_open) {
         n2 = hit_ior;
       } else if (bv.best_excl_leaf != RTC_NO_LEAF) {
-        n2 = mats[bv.best_excl_mat].ior;
+        n2 = mats[RTC_CHECK_INDEX(RTC_OOB_MATERIALS, bv.best_excl_mat, RTC_AVAIL(3))].ior;
       } else if (bv.hit_dups >= 2u) {
         n2 = hit_ior;
       }
@@ -2780,13 +2881,13 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
       constexpr bool SOLID_PATH = RTC_ALL_SOLID_FORM != 0 && !(WORLD == 2 && !BOX);
       Rgb color;
       if (SOLID_PATH && S.all_solid != 0u) {
-        const DevPattern& P = pats[mat.pattern];
+        const DevPattern& P = pats[RTC_CHECK_INDEX(RTC_OOB_PATTERNS, mat.pattern, RTC_AVAIL(4))];
         color = {P.rgb[0], P.rgb[1], P.rgb[2]};
       } else {
         const double opx = row_pt(M + 0, ovx, ovy, ovz);
         const double opy = row_pt(M + 4, ovx, ovy, ovz);
         const double opz = row_pt(M + 8, ovx, ovy, ovz);
-        color = pattern_at<CSG>(S, pats, mat.pattern, opx, opy, opz);
+        color = pattern_at<CSG>(S, pats, RTC_CHECK_INDEX(RTC_OOB_PATTERNS, mat.pattern, RTC_AVAIL(4)), opx, opy, opz);
       }
       RTC_STAMP(12);
       // With diffuse == 0 and specular == 0 lighting() returns `ambient` whether or not the
@@ -2803,6 +2904,9 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
       const uint32_t s_member = deal_lights ? (member & 3u) : member, s_stride = deal_lights ? 4u : stride;
       const unsigned calls_before = it_shadow_calls, traced_before = it_shadow_traced, share_before = it_share;
       for (uint32_t li = li_first; li < S.n_lights; li += li_step) {
+#ifdef RTC_PROFILE
+        if (!RTC_IN_BOUNDS(RTC_OOB_LIGHTS, 6u * li + 6u <= RTC_AVAIL(5))) continue;
+#endif
         const double* __restrict__ L = lights + 6ull * li;
         it_shadow_calls++;
         // isShadowed (world.zig:127-131) and lighting's point_to_light (material.zig:51) share this
@@ -3336,7 +3440,11 @@ __device__ __forceinline__ uint32_t pack_class(uint32_t t) {
 // (14 ms of wall time for dragons at 4K).  Writes what rtc_chunk_cost_kernel + rtc_chunk_time_kernel would have left.
 extern "C" __global__ void __launch_bounds__(256)
 rtc_estimate_kernel(const DevScene S, const DevCamera cam, const DevPixelMap map, uint32_t* __restrict__ chunk_cost,
-                    uint32_t* __restrict__ chunk_time, DevChunkShape* __restrict__ chunk_shape, DevPackState* __restrict__ state) {
+                    uint32_t* __restrict__ chunk_time, DevChunkShape* __restrict__ chunk_shape, DevPackState* __restrict__ state
+#ifdef RTC_PROFILE
+                    , unsigned long long* __restrict__ oob  // root-table indices outside their allocation (counted, not read)
+#endif
+                    ) {
   if (blockIdx.x == 0u) {
     uint32_t* z = reinterpret_cast<uint32_t*>(state);
     for (uint32_t i = threadIdx.x; i < sizeof(DevPackState) / sizeof(uint32_t); i += blockDim.x) z[i] = 0u;
@@ -3374,6 +3482,12 @@ rtc_estimate_kernel(const DevScene S, const DevCamera cam, const DevPixelMap map
   const float tan_a = 5.7f * ps * (len > 0.0f ? __builtin_sqrtf(m[0] * m[0] + m[4] * m[4] + m[8] * m[8]) * inv_len : 0.0f) + 1e-6f;
   float cost = 400.0f;  // a chunk of sky: ray generation and one trace that finds nothing
   for (uint32_t i = 0; i < S.n_roots; ++i) {
+#ifdef RTC_PROFILE
+    if ((i >> 1) >= S.n_root_cull || i >= S.n_root_recs || i >= S.n_root_weight) {
+      atomicAdd(oob, 1ull);
+      continue;
+    }
+#endif
     const RootCullPair P = S.root_cull[i >> 1];
     const float cx = P.cx[i & 1u], cy = P.cy[i & 1u], cz = P.cz[i & 1u], r2 = P.r2[i & 1u];
     bool seen = true;  // no finite bound (a plane): every pixel may see it
