@@ -6,6 +6,7 @@
 #   ray-tracer-challenge_amd/lib/librtc_host.so  product: scene model, JSON/OBJ loaders, Camera/World/Canvas API
 #   ray-tracer-challenge_amd/lib/rtc_host_kat    product unit tests (reference KATs for the build-time helpers)
 #   oracle/build/liboracle.so, oracle_kat        test infrastructure only
+#   tests/build/libarea_oracle.so                test infrastructure only: the area-light checker (tests/cpp/area_oracle.cpp)
 #
 # -ffp-contract=off everywhere: the reference's float mode is strict IEEE
 # (SURVEY F10); the GPU path and the oracle must round identically.
@@ -23,12 +24,18 @@ HOST_SRC := $(PKG)/host/rtc_scene.cpp $(PKG)/host/rtc_loader.cpp $(PKG)/host/rtc
             $(PKG)/host/rtc_api.cpp $(PKG)/host/rtc_host_capi.cpp
 HOST_HDR := $(wildcard $(PKG)/host/*.hpp) include/rtc.h include/rtc_host.h
 
-all: hip host oracle
+all: hip host oracle checker
 
 hip: $(LIB)/librtc_hip.so $(LIB)/librtc_multi.so
 host: $(LIB)/librtc_host.so $(LIB)/rtc_host_kat
 oracle:
 	$(MAKE) -C oracle
+
+# (the area-light checker includes the oracle's sources read-only; -pthread and -O3 as the oracle's own build)
+checker: tests/build/libarea_oracle.so
+tests/build/libarea_oracle.so: tests/cpp/area_oracle.cpp oracle/oracle_capi.cpp oracle/rtc_oracle.hpp oracle/rtc_oracle_scene.hpp include/rtc.h
+	mkdir -p tests/build
+	$(CXX) -std=c++17 -O3 -ffp-contract=off -fPIC -Wall -Wextra -pthread -shared -o $@ tests/cpp/area_oracle.cpp
 
 $(LIB):
 	mkdir -p $(LIB)
@@ -56,7 +63,7 @@ $(LIB)/rtc_host_kat: tests/cpp/host_kat_main.cpp $(LIB)/librtc_host.so $(HOST_HD
 	$(CXX) $(CXXFLAGS) -o $@ tests/cpp/host_kat_main.cpp -L$(LIB) -lrtc_host -lrtc_hip -Wl,-rpath,'$$ORIGIN'
 
 clean:
-	rm -rf $(LIB)
+	rm -rf $(LIB) tests/build
 	$(MAKE) -C oracle clean
 
-.PHONY: all hip host oracle clean
+.PHONY: all hip host oracle checker clean

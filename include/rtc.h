@@ -241,6 +241,41 @@ typedef struct rtc_scene rtc_scene; /* opaque; owns the device copies and one HI
 
 /* Validates `desc`, copies it into HBM on the current HIP device. */
 int rtc_scene_create(const rtc_scene_desc *desc, rtc_scene **out);
+
+/* ---- area lights (the book's bonus chapter "Rendering soft shadows") ---- */
+#define RTC_LIGHT_POINT 0u
+#define RTC_LIGHT_AREA 1u
+#define RTC_AREA_MAX_SAMPLES 4096u /* usteps * vsteps of one area light */
+
+/*
+ * World.lights of both kinds, in order (SoA, caller-owned, copied).  A point light is `corner` and `rgb`; an area
+ * light is area_light(corner, uvec, usteps, vvec, vsteps, rgb, jitter) with uvec / vvec its FULL edges: its samples are
+ *   point_on_light(u, v) = (corner + (uvec / usteps) * (u + ju)) + (vvec / vsteps) * (v + jv),
+ * v outer, u inner, ju = jv = 0.5 without jitter, and its lighting is
+ *   ambient + (sum over samples of the diffuse + specular terms / samples) * (unshadowed samples / samples).
+ * With jitter, ju / jv are a pure function of (seed, whole-image pixel, light, sample, axis) - DESIGN.md section 11 -
+ * so an image does not depend on how it was split into bands, tiles or launches.
+ */
+typedef struct rtc_light_desc {
+  uint32_t n_lights;
+  const uint8_t *kind;       /* RTC_LIGHT_*                                        */
+  const double *corner;      /* [n_lights][3] an area light's corner; a point light's position */
+  const double *uvec;        /* [n_lights][3] full edge (area lights only)         */
+  const double *vvec;        /* [n_lights][3]                                      */
+  const uint32_t *usteps;    /* [n_lights] >= 1 (area lights only)                 */
+  const uint32_t *vsteps;    /* [n_lights] >= 1; usteps * vsteps <= RTC_AREA_MAX_SAMPLES */
+  const uint8_t *jitter;     /* [n_lights] 0 / 1 (area lights only)                */
+  const double *rgb;         /* [n_lights][3] intensity                            */
+} rtc_light_desc;
+
+/*
+ * rtc_scene_create with World.lights given by `lights` (which replaces desc's light_pos / light_rgb; NULL: exactly
+ * rtc_scene_create).  Validated before anything touches the device (kinds, steps, the sample cap, finite values).
+ * A table of point lights only renders what rtc_scene_create renders, with the same kernel.
+ */
+int rtc_scene_create_with_lights(const rtc_scene_desc *desc, const rtc_light_desc *lights, rtc_scene **out);
+/* The seed of the area lights' jitter on this handle (default 0; a clone starts with its source's). */
+int rtc_scene_set_light_seed(rtc_scene *scene, uint64_t seed);
 void rtc_scene_destroy(rtc_scene *scene);
 
 /*

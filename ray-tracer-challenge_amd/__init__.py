@@ -89,16 +89,69 @@ class Stats(C.Structure):
                 ("shadow_traced", C.c_uint64), ("overflow", C.c_uint64)]
 
 
+RTC_LIGHT_POINT = 0
+RTC_LIGHT_AREA = 1
+RTC_AREA_MAX_SAMPLES = 4096
+
+
+class LightDesc(C.Structure):
+    """struct rtc_light_desc (include/rtc.h): World.lights of both kinds, in order."""
+
+    _fields_ = [("n_lights", C.c_uint32), ("kind", C.POINTER(C.c_uint8)), ("corner", C.POINTER(C.c_double)),
+                ("uvec", C.POINTER(C.c_double)), ("vvec", C.POINTER(C.c_double)), ("usteps", C.POINTER(C.c_uint32)),
+                ("vsteps", C.POINTER(C.c_uint32)), ("jitter", C.POINTER(C.c_uint8)), ("rgb", C.POINTER(C.c_double))]
+
+    @classmethod
+    def make(cls, lights):
+        """From a list of dicts {"kind": "point", "position", "intensity"} / {"kind": "area", "corner", "uvec", "usteps",
+        "vvec", "vsteps", "intensity", "jitter"}; the arrays are kept alive by the structure."""
+        n = len(lights)
+        arrays = {
+            "kind": np.array([RTC_LIGHT_AREA if l["kind"] == "area" else RTC_LIGHT_POINT for l in lights], dtype=np.uint8),
+            "corner": np.array([l["corner"] if l["kind"] == "area" else l["position"] for l in lights], dtype=np.float64).reshape(n, 3),
+            "uvec": np.array([l.get("uvec", (0, 0, 0)) for l in lights], dtype=np.float64).reshape(n, 3),
+            "vvec": np.array([l.get("vvec", (0, 0, 0)) for l in lights], dtype=np.float64).reshape(n, 3),
+            "usteps": np.array([l.get("usteps", 1) for l in lights], dtype=np.uint32),
+            "vsteps": np.array([l.get("vsteps", 1) for l in lights], dtype=np.uint32),
+            "jitter": np.array([1 if l.get("jitter", False) else 0 for l in lights], dtype=np.uint8),
+            "rgb": np.array([l["intensity"] for l in lights], dtype=np.float64).reshape(n, 3),
+        }
+        d = cls()
+        d.n_lights = n
+        for name, arr in arrays.items():
+            arr = np.ascontiguousarray(arr)
+            arrays[name] = arr
+            setattr(d, name, arr.ctypes.data_as(dict(cls._fields_)[name]))
+        d._arrays = arrays
+        return d
+
+    def to_list(self):
+        """The table as the dicts make() takes."""
+        out = []
+        for i in range(self.n_lights):
+            rgb = [self.rgb[3 * i + k] for k in range(3)]
+            corner = [self.corner[3 * i + k] for k in range(3)]
+            if self.kind[i] == RTC_LIGHT_AREA:
+                out.append({"kind": "area", "corner": corner, "uvec": [self.uvec[3 * i + k] for k in range(3)],
+                            "usteps": self.usteps[i], "vvec": [self.vvec[3 * i + k] for k in range(3)],
+                            "vsteps": self.vsteps[i], "intensity": rgb, "jitter": bool(self.jitter[i])})
+            else:
+                out.append({"kind": "point", "position": corner, "intensity": rgb})
+        return out
+
+
 # (include/rtc.h: what a host binds ...)
 RTC_SYMBOLS = ["rtc_scene_create", "rtc_scene_clone", "rtc_scene_destroy", "rtc_render", "rtc_render_rgba8", "rtc_render_device",
                "rtc_render_tiles_device", "rtc_assemble_tiles_device", "rtc_render_tile_list_device", "rtc_get_tile_costs",
                "rtc_assign_tiles", "rtc_assemble_tile_list_device", "rtc_assemble_tile_list_rgba8_device", "rtc_scatter_tile_list_device",
                "rtc_scatter_tile_list_rgba8_device", "rtc_scene_synchronize", "rtc_get_stats", "rtc_last_error", "rtc_status_name",
-               "rtc_grow_csg_lists", "rtc_canvas_register", "rtc_canvas_unregister", "rtc_rgba8_device"]
+               "rtc_grow_csg_lists", "rtc_canvas_register", "rtc_canvas_unregister", "rtc_rgba8_device",
+               "rtc_scene_create_with_lights", "rtc_scene_set_light_seed"]
 # (... and include/rtc_diag.h: diagnostics and tuning, for the tests, bench.py and tools/)
 RTC_DIAG_SYMBOLS = ["rtc_set_option", "rtc_last_kernel_name", "rtc_get_schedule", "rtc_get_chunk_times", "rtc_diag_build_tables", "rtc_diag_root_boxes"]
 HOST_SYMBOLS = ["rtch_last_error", "rtch_scene_load", "rtch_scene_free", "rtch_scene_desc", "rtch_scene_camera",
-                "rtch_camera_rotate", "rtch_camera_move", "rtch_camera_make", "rtch_canvas_ppm", "rtch_canvas_rgba8", "rtch_scene_render", "rtch_set_loader_threads"]
+                "rtch_camera_rotate", "rtch_camera_move", "rtch_camera_make", "rtch_canvas_ppm", "rtch_canvas_rgba8", "rtch_scene_render", "rtch_set_loader_threads",
+                "rtch_scene_lights"]
 
 MULTI_SYMBOLS = ["rtc_multi_create", "rtc_multi_destroy", "rtc_multi_render", "rtc_multi_render_rgba8", "rtc_multi_render_device", "rtc_multi_render_rgba8_device",
                  "rtc_multi_synchronize", "rtc_multi_stream", "rtc_multi_get_stats", "rtc_multi_balance", "rtc_multi_last_error"]
@@ -146,6 +199,8 @@ def hip_lib():
         lib.rtc_status_name.argtypes = [C.c_int]
         lib.rtc_scene_create.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_void_p)]
         lib.rtc_scene_clone.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        lib.rtc_scene_create_with_lights.argtypes = [C.POINTER(SceneDesc), C.POINTER(LightDesc), C.POINTER(C.c_void_p)]
+        lib.rtc_scene_set_light_seed.argtypes = [C.c_void_p, C.c_uint64]
         lib.rtc_scene_destroy.argtypes = [C.c_void_p]
         lib.rtc_scene_destroy.restype = None
         lib.rtc_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32] + [C.c_uint32] * 4 + [C.c_void_p]
@@ -192,6 +247,8 @@ def host_lib():
         lib.rtch_set_loader_threads.restype = None
         lib.rtch_scene_desc.argtypes = [C.c_void_p]
         lib.rtch_scene_desc.restype = C.POINTER(SceneDesc)
+        lib.rtch_scene_lights.argtypes = [C.c_void_p]
+        lib.rtch_scene_lights.restype = C.POINTER(LightDesc)
         lib.rtch_scene_camera.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Camera)]
         lib.rtch_camera_rotate.argtypes = [C.c_void_p, C.c_double]
         lib.rtch_camera_move.argtypes = [C.c_void_p, C.c_double]
@@ -323,6 +380,8 @@ class HostScene:
         _check_host(host_lib().rtch_scene_load(scene_json, data_dir.encode(), C.byref(self._h)))
         self.desc = host_lib().rtch_scene_desc(self._h).contents
         self.desc._owner = self   # the tables behind `desc` are this object's: HostScene(...).desc alone must keep them alive
+        self.lights = host_lib().rtch_scene_lights(self._h).contents  # World.lights of both kinds (rtc_light_desc)
+        self.lights._owner = self
 
     @classmethod
     def from_file(cls, name, data_dir=DATA_DIR):
@@ -375,12 +434,20 @@ def make_camera(hsize, vsize, fov, frm, to, up):
 class GpuScene:
     """rtc_scene: the flat scene resident in HBM; many renders per upload."""
 
-    def __init__(self, desc, _clone_of=None):
+    def __init__(self, desc, lights=None, _clone_of=None):
+        """lights: a LightDesc (HostScene.lights, LightDesc.make) that replaces desc's point lights
+        (rtc_scene_create_with_lights); None: rtc_scene_create."""
         self._s = C.c_void_p()
         if _clone_of is not None:
             _check_hip(hip_lib().rtc_scene_clone(_clone_of._s, C.byref(self._s)))
+        elif lights is not None:
+            _check_hip(hip_lib().rtc_scene_create_with_lights(C.byref(desc), C.byref(lights), C.byref(self._s)))
         else:
             _check_hip(hip_lib().rtc_scene_create(C.byref(desc), C.byref(self._s)))
+
+    def set_light_seed(self, seed):
+        """rtc_scene_set_light_seed: the seed of the area lights' jitter on this handle."""
+        _check_hip(hip_lib().rtc_scene_set_light_seed(self._s, seed))
 
     def clone(self):
         """rtc_scene_clone: a handle of its own (stream, schedule, counters) on the same device copy of the scene - one

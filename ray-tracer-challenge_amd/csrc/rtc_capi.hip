@@ -62,6 +62,17 @@ extern "C" __global__ void rtc_render_kernel_ext(const DevScene S, const DevCame
 extern "C" __global__ void rtc_render_kernel_bigworld_ext(const DevScene S, const DevCamera cam, const DevPixelMap map,
                                                           const uint32_t max_depth, double* __restrict__ out,
                                                           DevStats* __restrict__ stats, DevStats* __restrict__ next_stats);
+// The area-light kernels (rtc_scene_create_with_lights).  Their table edge - 16 lights select the LDS kernel, 17 the
+// big-world one - is tested in tests/test_area_lights_gpu.py (test_table_edge): the generated worlds of the point-light
+// limits module (tests/test_table_limits_gpu.py) have no light table to give them.
+extern "C" {
+__global__ void rtc_render_kernel_area(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                       double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                       const DevAreaLights area);
+__global__ void rtc_render_kernel_area_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                                double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                                const DevAreaLights area);
+}
 extern "C" __global__ void rtc_estimate_kernel(const DevScene S, const DevCamera cam, const DevPixelMap map,
                                                uint32_t* __restrict__ chunk_cost, uint32_t* __restrict__ chunk_time,
                                                DevChunkShape* __restrict__ chunk_shape, DevPackState* __restrict__ state
@@ -255,14 +266,27 @@ bool usesSimple3(const rtc_scene* s, const DevPixelMap& map) {
   return simple3Trial(s, map) && threeWaves(s);  // (between one and four chunks per wave: what the handle's trial says)
 }
 
+// (the area kernels stage an area row of RTC_AREA_ROW doubles beside each light's point row: their LDS holds
+// RTC_LDS_LIGHTS lights of both rows, so the same count decides)
 bool tablesInLds(const rtc_scene* s) {
   return s->dev.n_roots <= RTC_LDS_ROOTS && s->dev.n_materials <= RTC_LDS_MATERIALS &&
          s->dev.n_patterns <= RTC_LDS_PATTERNS && s->dev.n_lights <= RTC_LDS_LIGHTS;
 }
 
+// (the area kernels take one more argument, DevAreaLights: `area` instead of `fn`)
 struct KernelChoice {
   decltype(&rtc_render_kernel) fn;
   const char* name;
+  decltype(&rtc_render_kernel_area) area = nullptr;
+  KernelChoice(decltype(&rtc_render_kernel) f, const char* n) : fn(f), name(n) {}
+  KernelChoice(decltype(&rtc_render_kernel_area) a, const char* n) : fn(nullptr), name(n), area(a) {}
+  void launch(uint32_t blocks, hipStream_t stream, const rtc_scene* s, const DevScene& dev, const DevCamera& cam, const DevPixelMap& map,
+              uint32_t max_depth, double* d_out, DevStats* st_now, DevStats* st_next) const {
+    if (area)
+      hipLaunchKernelGGL(area, dim3(blocks), dim3(256), 0, stream, dev, cam, map, max_depth, d_out, st_now, st_next, s->area);
+    else
+      hipLaunchKernelGGL(fn, dim3(blocks), dim3(256), 0, stream, dev, cam, map, max_depth, d_out, st_now, st_next);
+  }
 };
 #define RTC_KERNEL(k) KernelChoice{k, #k}
 // The general kernel at three waves per SIMD (rtc_render_kernel3): forced by option "waves3", else what the handle's
@@ -290,6 +314,7 @@ KernelChoice ldsKernel(const rtc_scene* s, const DevPixelMap& map) {
   return s->ext_kernel ? RTC_KERNEL(rtc_render_kernel_ext) : RTC_KERNEL(rtc_render_kernel);
 }
 KernelChoice renderKernel(const rtc_scene* s, const DevPixelMap& map) {
+  if (s->area_kernel) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_area) : RTC_KERNEL(rtc_render_kernel_area_bigworld);
   if (tablesInLds(s)) return ldsKernel(s, map);
   return s->ext_kernel ? RTC_KERNEL(rtc_render_kernel_bigworld_ext) : RTC_KERNEL(rtc_render_kernel_bigworld);
 }
@@ -636,8 +661,7 @@ int enqueueRender(rtc_scene* s, const rtc_camera& cam, DevPixelMap& map, uint32_
   // hands part of its ray tree to a neighbour (render_body step 2a).
   const KernelChoice kernel = renderKernel(s, map);
   s->last_kernel = kernel.name;
-  hipLaunchKernelGGL(kernel.fn, dim3(blocks), dim3(256), 0, stream, s->dev, devCamera(cam), map, max_depth, d_out, st_now,
-                     st_next);
+  kernel.launch(blocks, stream, s, s->dev, devCamera(cam), map, max_depth, d_out, st_now, st_next);
   HIP_TRY(hipGetLastError());
   return RTC_OK;
 }
@@ -683,8 +707,8 @@ int launch(rtc_scene* s, const rtc_camera& cam, const DevPixelMap& map_in, uint3
     const KernelChoice kernel = renderKernel(s, map);
     DevScene dev = s->dev;
     dev.csg_buf = nullptr;
-    hipLaunchKernelGGL(kernel.fn, dim3(residentBlocks(s, map)), dim3(256), 0, stream, dev, devCamera(cam), idle, max_depth, d_out,
-                       s->d_stats + s->stats_parity, s->d_stats + (s->stats_parity ^ 1u));
+    kernel.launch(residentBlocks(s, map), stream, s, dev, devCamera(cam), idle, max_depth, d_out, s->d_stats + s->stats_parity,
+                  s->d_stats + (s->stats_parity ^ 1u));
     HIP_TRY(hipGetLastError());
   }
   s->trial_live = false;  // (set again below if this launch is a frame of a running trial)
@@ -904,6 +928,11 @@ struct HostTables {
   std::vector<uint2> node_kids;
   std::vector<double> node_box;
   std::vector<double> light;
+  // rtc_scene_create_with_lights with area lights: the kernels' area rows (DevAreaLights), and the points whose convex
+  // hull holds every point a light may shine from - a point light's position, an area light's four corners - for what
+  // the build reasons from light positions (the rooms).  Empty: point lights only, d.light_pos.
+  std::vector<double> area;
+  std::vector<double> light_extent;
   uint32_t n_live = 0;
   uint32_t n_root_kind[3] = {0, 0, 0};  // top-level spheres, planes, cubes (the table: [spheres][cubes][the rest][planes])
   float bvh_mag = 0.0f;
@@ -1159,11 +1188,15 @@ void buildRootTables(const rtc_scene_desc& d, const std::vector<uint32_t>& dfs_o
         if (d.cyl_closed[g]) R.kind_flags |= 0x200u;
       }
       if (k == RTC_CUBE && d.n_lights > 0) {  // a room: every light strictly inside the cube (object space)
+        // (an area light: its four corners, whose parallelogram holds every sample, jittered or not - the cube is convex)
+        const bool extent = !T.light_extent.empty();
+        const double* const pts = extent ? T.light_extent.data() : d.light_pos;
+        const size_t n_pts = extent ? T.light_extent.size() / 3u : d.n_lights;
         bool room = true;
-        for (uint32_t l = 0; l < d.n_lights && room; ++l)
+        for (size_t l = 0; l < n_pts && room; ++l)
           for (int r = 0; r < 3 && room; ++r) {
             const double* m = R.inv + 4 * r;
-            const double c = ((m[0] * d.light_pos[3ull * l] + m[1] * d.light_pos[3ull * l + 1]) + m[2] * d.light_pos[3ull * l + 2]) + m[3];
+            const double c = ((m[0] * pts[3ull * l] + m[1] * pts[3ull * l + 1]) + m[2] * pts[3ull * l + 2]) + m[3];
             room = std::fabs(c) <= 1.0 - 1e-6;
           }
         if (room) R.kind_flags |= RTC_ROOT_ROOM;
@@ -1981,6 +2014,13 @@ int uploadTables(const rtc_scene_desc& d, const SceneTraits& traits, const HostT
   s->general3_ok = RTC_BVH8 && !s->flat_kernel && !ext_kernel && d.n_roots <= RTC_LDS3_ROOTS && d.n_materials <= RTC_LDS3_MATERIALS &&
                    d.n_patterns <= RTC_LDS3_PATTERNS && d.n_lights <= RTC_LDS3_LIGHTS;
   HIP_TRY(s->tab->light.upload(light));
+  if (!T.area.empty()) {  // area lights: the area kernels, whatever the world's shape (no simple, flat or three-wave forms)
+    HIP_TRY(s->tab->area.upload(T.area));
+    s->area_kernel = true;
+    s->area.row = s->tab->area.p;
+    s->ext_kernel = true;
+    s->simple_kernel = s->flat_kernel = s->simple3_ok = s->general3_ok = false;
+  }
   if (const int st = initLaunchState(s); st != RTC_OK) return st;
   s->max_trav_stack = traits.max_stack;
   {
@@ -2001,6 +2041,12 @@ int uploadTables(const rtc_scene_desc& d, const SceneTraits& traits, const HostT
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
         &nb, ext_kernel ? rtc_render_kernel_bigworld_ext : rtc_render_kernel_bigworld, 256, 0));
     s->blocks_per_cu_big = static_cast<uint32_t>(std::max(nb, 1));
+    if (s->area_kernel) {
+      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_area, 256, 0));
+      s->blocks_per_cu_lds = static_cast<uint32_t>(std::max(nb, 1));
+      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_area_bigworld, 256, 0));
+      s->blocks_per_cu_big = static_cast<uint32_t>(std::max(nb, 1));
+    }
     if (const int v = static_cast<int>(rtcOptions().blocks_per_cu); v >= 1)  // (tuning option)
       s->blocks_per_cu_lds = std::min<uint32_t>(s->blocks_per_cu_lds, v), s->blocks_per_cu_big = std::min<uint32_t>(s->blocks_per_cu_big, v);
   }
@@ -2085,18 +2131,14 @@ static void warmHostCopies(const rtc_scene* s) {
   if (hipMemcpy(sink.data(), s->d_ray_stack, sink.size(), hipMemcpyDeviceToHost) != hipSuccess) (void)hipGetLastError();
 }
 
-int rtc_scene_create(const rtc_scene_desc* desc, rtc_scene** out) {
-  g_error.clear();
-  if (!desc || !out) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
-  *out = nullptr;
-  const rtc_scene_desc& d = *desc;
-  if (d.abi_version != RTC_ABI_VERSION)
-    return fail(RTC_ERR_INVALID_ARGUMENT, "abi_version %u, library speaks %u", d.abi_version, RTC_ABI_VERSION);
-
+// rtc_scene_create / rtc_scene_create_with_lights: `area` / `extent` as HostTables::area / light_extent (null: none).
+static int createScene(const rtc_scene_desc& d, std::vector<double>* area, std::vector<double>* extent, rtc_scene** out) {
   SceneTraits traits;
   if (const int st = validateScene(d, traits); st != RTC_OK) return st;
   HostTables tables;
+  if (extent) tables.light_extent = std::move(*extent);
   if (const int st = buildTables(d, traits, tables); st != RTC_OK) return st;
+  if (area) tables.area = std::move(*area);
   int n_dev = 0;
   if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0)
     return fail(RTC_ERR_NO_DEVICE, "no HIP device is visible; this library has no CPU path");
@@ -2129,6 +2171,90 @@ int rtc_scene_create(const rtc_scene_desc* desc, rtc_scene** out) {
   return RTC_OK;
 }
 
+int rtc_scene_create(const rtc_scene_desc* desc, rtc_scene** out) {
+  g_error.clear();
+  if (!desc || !out) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
+  *out = nullptr;
+  if (desc->abi_version != RTC_ABI_VERSION)
+    return fail(RTC_ERR_INVALID_ARGUMENT, "abi_version %u, library speaks %u", desc->abi_version, RTC_ABI_VERSION);
+  return createScene(*desc, nullptr, nullptr, out);
+}
+
+int rtc_scene_create_with_lights(const rtc_scene_desc* desc, const rtc_light_desc* lights, rtc_scene** out) {
+  if (!lights) return rtc_scene_create(desc, out);
+  g_error.clear();
+  if (!desc || !out) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
+  *out = nullptr;
+  if (desc->abi_version != RTC_ABI_VERSION)
+    return fail(RTC_ERR_INVALID_ARGUMENT, "abi_version %u, library speaks %u", desc->abi_version, RTC_ABI_VERSION);
+  const rtc_light_desc& L = *lights;
+  const uint32_t n = L.n_lights;
+  if (n > 0 && (!L.kind || !L.corner || !L.rgb)) return fail(RTC_ERR_INVALID_ARGUMENT, "light table: null kind / corner / rgb");
+  bool any_area = false;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (L.kind[i] != RTC_LIGHT_POINT && L.kind[i] != RTC_LIGHT_AREA)
+      return fail(RTC_ERR_UNSUPPORTED, "light %u: kind %u", i, static_cast<unsigned>(L.kind[i]));
+    any_area = any_area || L.kind[i] == RTC_LIGHT_AREA;
+  }
+  if (any_area && (!L.uvec || !L.vvec || !L.usteps || !L.vsteps || !L.jitter))
+    return fail(RTC_ERR_INVALID_ARGUMENT, "light table: an area light needs uvec, vvec, usteps, vsteps and jitter");
+  std::vector<double> pos(3ull * n), rgb(3ull * n), area(any_area ? static_cast<size_t>(RTC_AREA_ROW) * n : 0u, 0.0), extent;
+  for (uint32_t i = 0; i < n; ++i) {
+    const bool is_area = L.kind[i] == RTC_LIGHT_AREA;
+    const double* c = L.corner + 3ull * i;
+    bool finite = std::isfinite(c[0]) && std::isfinite(c[1]) && std::isfinite(c[2]);
+    for (int k = 0; k < 3; ++k) finite = finite && std::isfinite(L.rgb[3ull * i + k]);
+    if (is_area) {
+      for (int k = 0; k < 3; ++k) finite = finite && std::isfinite(L.uvec[3ull * i + k]) && std::isfinite(L.vvec[3ull * i + k]);
+      const uint64_t samples = static_cast<uint64_t>(L.usteps[i]) * L.vsteps[i];
+      if (L.usteps[i] == 0 || L.vsteps[i] == 0 || samples > RTC_AREA_MAX_SAMPLES)
+        return fail(RTC_ERR_INVALID_ARGUMENT, "light %u: %u x %u samples (1 to %u)", i, L.usteps[i], L.vsteps[i], RTC_AREA_MAX_SAMPLES);
+      if (L.jitter[i] > 1u) return fail(RTC_ERR_INVALID_ARGUMENT, "light %u: jitter %u", i, static_cast<unsigned>(L.jitter[i]));
+    }
+    if (!finite) return fail(RTC_ERR_INVALID_ARGUMENT, "light %u: a value that is not finite", i);
+    for (int k = 0; k < 3; ++k) rgb[3ull * i + k] = L.rgb[3ull * i + k];
+    if (!is_area) {
+      for (int k = 0; k < 3; ++k) pos[3ull * i + k] = c[k];
+      extent.insert(extent.end(), c, c + 3);
+    } else {
+      const double* u = L.uvec + 3ull * i;
+      const double* v = L.vvec + 3ull * i;
+      for (int k = 0; k < 3; ++k) pos[3ull * i + k] = (c[k] + u[k] * 0.5) + v[k] * 0.5;  // area_light's position
+      for (int corner = 0; corner < 4; ++corner)
+        for (int k = 0; k < 3; ++k) extent.push_back((c[k] + ((corner & 1) ? u[k] : 0.0)) + ((corner & 2) ? v[k] : 0.0));
+    }
+    if (any_area) {
+      double* row = area.data() + static_cast<size_t>(RTC_AREA_ROW) * i;
+      for (int k = 0; k < 3; ++k) {
+        row[k] = c[k];
+        row[9 + k] = L.rgb[3ull * i + k];
+        if (is_area) {
+          row[3 + k] = L.uvec[3ull * i + k] / static_cast<double>(L.usteps[i]);
+          row[6 + k] = L.vvec[3ull * i + k] / static_cast<double>(L.vsteps[i]);
+        }
+      }
+      const unsigned long long bits =
+          is_area ? (static_cast<unsigned long long>(L.usteps[i]) | static_cast<unsigned long long>(L.vsteps[i]) << RTC_AREA_STEP_BITS |
+                     1ull << RTC_AREA_KIND_BIT | static_cast<unsigned long long>(L.jitter[i] != 0u) << RTC_AREA_JITTER_BIT)
+                  : 0ull;
+      std::memcpy(&row[12], &bits, sizeof bits);
+    }
+  }
+  rtc_scene_desc d = *desc;
+  d.n_lights = n;
+  d.light_pos = pos.data();
+  d.light_rgb = rgb.data();
+  return createScene(d, any_area ? &area : nullptr, any_area ? &extent : nullptr, out);
+}
+
+int rtc_scene_set_light_seed(rtc_scene* s, uint64_t seed) {
+  g_error.clear();
+  if (!s) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
+  s->area.seed = seed;
+  for (rtc_scene* b : s->band) b->area.seed = seed;  // (the band clones rtc_render renders a large frame with)
+  return RTC_OK;
+}
+
 int rtc_scene_clone(const rtc_scene* src, rtc_scene** out) {
   g_error.clear();
   if (!src || !out) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
@@ -2149,6 +2275,8 @@ int rtc_scene_clone(const rtc_scene* src, rtc_scene** out) {
   s->dev.csg_buf = nullptr;
   s->has_csg = src->has_csg;
   s->ext_kernel = src->ext_kernel;
+  s->area_kernel = src->area_kernel;
+  s->area = src->area;  // (the rows the scene's device copy holds, and the source's seed)
   s->simple_kernel = src->simple_kernel;
   s->flat_kernel = src->flat_kernel;
   s->simple3_ok = src->simple3_ok;

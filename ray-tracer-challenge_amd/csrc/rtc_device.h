@@ -257,6 +257,34 @@ struct DevScene {
   uint32_t all_solid;     // every pattern of the world is a solid colour: a hit's colour needs no object-space point (cover, dragons, groups)
 };
 
+// World.lights of a scene with area lights (rtc_scene_create_with_lights): the extra argument of the area kernels only,
+// so that DevScene - and with it every other kernel's code - stays as it is.  One row of RTC_AREA_ROW doubles per light,
+// in World.lights order: corner (a point light's position), the CELL vectors uvec / usteps and vvec / vsteps, rgb, and
+// usteps | vsteps << 13 | area << 26 | jitter << 27 as the bits of the last double.  Point lights are shaded from
+// DevScene::light as in every other kernel; this table says which lights are area lights.
+#define RTC_AREA_ROW 13u
+#define RTC_AREA_STEP_BITS 13u
+#define RTC_AREA_KIND_BIT 26u
+#define RTC_AREA_JITTER_BIT 27u
+struct DevAreaLights {
+  const double* __restrict__ row;  // [n_lights][RTC_AREA_ROW]
+  unsigned long long seed;         // rtc_scene_set_light_seed
+};
+
+// The jitter of sample (u, v) of light l for the whole-image pixel p: a pure function, the same
+// bits in the kernels and in the checker.  splitmix64's finaliser on seed + golden * (c + 1).
+__host__ __device__ inline double rtc_area_jitter(unsigned long long seed, unsigned long long p, uint32_t n_lights, uint32_t l,
+                                                  uint32_t k, uint32_t axis) {
+  const unsigned long long c = ((p * n_lights + l) << 32) | (2ull * k + axis);
+  unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (c + 1ull);
+  z ^= z >> 30;
+  z *= 0xBF58476D1CE4E5B9ull;
+  z ^= z >> 27;
+  z *= 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return static_cast<double>(z >> 11) * 0x1.0p-53;
+}
+
 struct DevCamera {
   double half_width, half_height, pixel_size;
   double inv[12];  // rows 0..2 of Camera._inverse_transform

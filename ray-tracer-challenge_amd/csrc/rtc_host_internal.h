@@ -109,6 +109,7 @@ struct SceneTables {
   DevBuf<float> root_weight;
   DevBuf<uint4> leaf_meta;
   DevBuf<double> xf, tri, trin, node_box, light;
+  DevBuf<double> area;  // DevAreaLights::row (rtc_scene_create_with_lights with an area light; else empty)
   DevBuf<DevPattern> pat;
   DevBuf<DevCyl> cyl;
   DevBuf<DevMaterial> mat;
@@ -140,6 +141,8 @@ struct rtc_scene {
   bool simple_kernel = false;      // only top-level spheres / planes / cubes: the `simple` kernel
   bool flat_kernel = false;        // no groups at all (any leaf kind): the `flat` kernel
   const char* last_kernel = "";   // name of the render kernel of the last launch (rtc_last_kernel_name)
+  bool area_kernel = false;        // World.lights has an area light: the area kernels, with `area` as their extra argument
+  DevAreaLights area{};            // rows (in SceneTables::area) and this handle's jitter seed (rtc_scene_set_light_seed)
   bool simple3_ok = false;         // a simple world whose tables fit the three-waves-per-SIMD kernel's LDS (RTC_LDS3_*)
   void* d_csg_buf = nullptr;       // DevPixelMap::csg_buf, only for scenes with csg nodes
   size_t csg_buf_capacity = 0;     // bytes

@@ -2201,10 +2201,13 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned v) {
 // reflection / refraction children (one continues in registers, the other goes to the lane's stack).
 // Exit: the counter runs past n_chunks (`drained`) and no lane holds a ray; every wave reaches it.
 // ------------------------------------------------------------------------------------------
-template <bool LDS, bool CSG, int WORLD = 0, int WAVES = 2, bool COOP = false, bool BOX = true>
+// (AREA: World.lights may hold area lights - DevAreaLights, the area kernels' extra argument; compiled into those kernels only)
+template <bool LDS, bool CSG, int WORLD = 0, int WAVES = 2, bool COOP = false, bool BOX = true, bool AREA = false>
 __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& cam, const DevPixelMap& map,
                                             const uint32_t max_depth, double* __restrict__ out,
-                                            DevStats* __restrict__ stats, DevStats* __restrict__ next_stats) {
+                                            DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                            const DevAreaLights& area = DevAreaLights{}) {
+  static_assert(!AREA || !COOP, "the area kernels run no cooperative iterations");
   RTC_PRIO_PHASE(RTC_PRIO_WORK);
 #ifndef RTC_PROFILE
   if (blockIdx.x == 0u) {  // the next launch's counters (see DevStats)
@@ -2257,6 +2260,10 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
   const DevMaterial* __restrict__ mats = S.mat;
   const DevPattern* __restrict__ pats = S.pat;
   const double* __restrict__ lights = S.light;
+  const double* __restrict__ area_rows = AREA ? area.row : nullptr;
+#ifdef RTC_PROFILE
+  uint32_t area_avail = AREA ? RTC_AREA_ROW * S.n_lights : 0u;  // (words of the area table a light's row may reach)
+#endif
   if (LDS) {
     auto stage = [&](void* dst_, const void* src_, uint32_t n_words) {
       const double* __restrict__ src = reinterpret_cast<const double*>(src_);
@@ -2305,6 +2312,17 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
       rtc_oob_avail[5] = w_light;
     }
 #endif
+    if constexpr (AREA) {  // (the area rows beside the point table; tablesInLds counts them with the lights)
+      __shared__ double lds_area[RTC_AREA_ROW * N_LIGHTS];
+#ifndef RTC_PROFILE
+      stage(lds_area, area.row, S.n_lights * RTC_AREA_ROW);
+#else
+      const uint32_t w_area = words(S.n_lights * RTC_AREA_ROW, static_cast<size_t>(S.n_lights) * RTC_AREA_ROW, sizeof lds_area / 8u);
+      stage(lds_area, area.row, w_area);
+      area_avail = w_area;
+#endif
+      area_rows = lds_area;
+    }
     __syncthreads();
     recs = lds_recs;
     cull.sphere = lds_cull;
@@ -2906,7 +2924,123 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
       for (uint32_t li = li_first; li < S.n_lights; li += li_step) {
 #ifdef RTC_PROFILE
         if (!RTC_IN_BOUNDS(RTC_OOB_LIGHTS, 6u * li + 6u <= RTC_AVAIL(5))) continue;
+        if (AREA && !RTC_IN_BOUNDS(RTC_OOB_LIGHTS, RTC_AREA_ROW * li + RTC_AREA_ROW <= area_avail)) continue;
 #endif
+        if constexpr (AREA) {
+          const double* __restrict__ A = area_rows + static_cast<size_t>(RTC_AREA_ROW) * li;
+          const unsigned long long bits = static_cast<unsigned long long>(__double_as_longlong(A[12]));
+          if ((bits >> RTC_AREA_KIND_BIT) & 1ull) {
+            // ---- an area light (the book's bonus chapter): two passes over its samples, v outer, u inner.  The first
+            // builds the diffuse + specular sum and traces nothing; only when that sum is not zero - a sample in front of the
+            // surface, a material that is not pure ambient - does the second trace the samples' shadow rays.  What it yields
+            // is an integer count, so the colour does not depend on the order the rays ran in.
+            const uint32_t us = static_cast<uint32_t>(bits) & ((1u << RTC_AREA_STEP_BITS) - 1u);
+            const uint32_t vs = static_cast<uint32_t>(bits >> RTC_AREA_STEP_BITS) & ((1u << RTC_AREA_STEP_BITS) - 1u);
+            const bool jitter = (bits >> RTC_AREA_JITTER_BIT) & 1ull;
+            const uint32_t n_samples = us * vs;
+            it_shadow_calls += n_samples;
+            // the whole image's pixel of this ray tree (out_index travels with a ray handed to another lane): the jitter's key
+            unsigned long long pixel = 0ull;
+            if (jitter) {
+              uint32_t px, py;
+              if (map.mode == 0u) {
+                const uint32_t ry = static_cast<uint32_t>(out_index / map.w);
+                px = map.x0 + static_cast<uint32_t>(out_index - static_cast<size_t>(ry) * map.w);
+                py = map.y0 + ry;
+              } else {
+                const size_t per_tile = static_cast<size_t>(map.tile_w) * map.tile_h;
+                const uint32_t region = static_cast<uint32_t>(out_index / per_tile);
+                const uint32_t r = static_cast<uint32_t>(out_index - static_cast<size_t>(region) * per_tile);
+                const uint32_t ry = r / map.tile_w, rx = r - ry * map.tile_w;
+                const uint32_t tile = map.mode == 1u ? map.first_tile + region * map.tile_stride : map.tile_list[region];
+                const uint32_t ty = tile / map.tiles_x;
+                px = (tile - ty * map.tiles_x) * map.tile_w + rx;
+                py = ty * map.tile_h + ry;
+              }
+              pixel = static_cast<unsigned long long>(py) * cam.hsize + px;
+            }
+            // point_on_light(u, v) - over_point
+            auto to_sample = [&](uint32_t u, uint32_t v, double& vx, double& vy, double& vz) {
+              double ju = 0.5, jv = 0.5;
+              if (jitter) {
+                const uint32_t k = v * us + u;
+                ju = rtc_area_jitter(area.seed, pixel, S.n_lights, li, k, 0u);
+                jv = rtc_area_jitter(area.seed, pixel, S.n_lights, li, k, 1u);
+              }
+              const double fu = static_cast<double>(u) + ju, fv = static_cast<double>(v) + jv;
+              vx = ((A[0] + A[3] * fu) + A[6] * fv) - ovx;
+              vy = ((A[1] + A[4] * fu) + A[7] * fv) - ovy;
+              vz = ((A[2] + A[5] * fu) + A[8] * fv) - ovz;
+            };
+            const double er = color.r * A[9], eg = color.g * A[10], eb = color.b * A[11];  // effective_color
+            const double ka = mat.ambient;
+            double lr_ = er * ka, lg_ = eg * ka, lb_ = eb * ka;
+            double dr = 0.0, dg = 0.0, db = 0.0;
+            if (shadow_matters) {
+              for (uint32_t v = 0u; v < vs; ++v)
+                for (uint32_t u = 0u; u < us; ++u) {
+                  double vx, vy, vz;
+                  to_sample(u, v, vx, vy, vz);
+                  const double distance = __builtin_sqrt((vx * vx + vy * vy) + vz * vz);
+                  double lvx = vx, lvy = vy, lvz = vz;
+                  if (distance != 0.0) {
+                    lvx = vx / distance;
+                    lvy = vy / distance;
+                    lvz = vz / distance;
+                  }
+                  const double light_dot_normal = (lvx * nx + lvy * ny) + lvz * nz;
+                  if (light_dot_normal >= 0.0) {
+                    const double kd = mat.diffuse * light_dot_normal;
+                    dr = dr + er * kd;
+                    dg = dg + eg * kd;
+                    db = db + eb * kd;
+                    const double two_dot = 2.0 * light_dot_normal;
+                    const double rx = lvx - nx * two_dot, ry = lvy - ny * two_dot, rz = lvz - nz * two_dot;
+                    const double reflect_dot_eye = ((-rx) * ex + (-ry) * ey) + (-rz) * ez;
+                    if (reflect_dot_eye > 0.0) {
+                      const uint32_t n = mat.shininess_int;
+                      const double ks = mat.specular * (n != 0u && reflect_dot_eye < kInf ? pow_small_int(reflect_dot_eye, n)
+                                                                                          : zig_pow(reflect_dot_eye, mat.shininess));
+                      dr = dr + A[9] * ks;
+                      dg = dg + A[10] * ks;
+                      db = db + A[11] * ks;
+                    }
+                  }
+                }
+            }
+            if (!(dr == 0.0 && dg == 0.0 && db == 0.0)) {
+              uint32_t lit = 0u;
+              for (uint32_t v = 0u; v < vs; ++v)
+                for (uint32_t u = 0u; u < us; ++u) {
+                  double vx, vy, vz;
+                  to_sample(u, v, vx, vy, vz);
+                  const double distance = __builtin_sqrt((vx * vx + vy * vy) + vz * vz);
+                  double lvx = vx, lvy = vy, lvz = vz;
+                  if (distance != 0.0) {
+                    lvx = vx / distance;
+                    lvy = vy / distance;
+                    lvz = vz / distance;
+                  }
+                  it_shadow_traced++;
+                  it_share++;
+                  ShadowVisitor sv;
+                  sv.distance = distance;
+                  Ray sray{ovx, ovy, ovz, lvx, lvy, lvz};
+                  trace<CSG, WORLD, ShadowVisitor, TRAV, BOX>(S, recs, cull, sray, sv, it_overflow, trav_stack, member, stride);
+                  lit += sv.shadowed ? 0u : 1u;
+                }
+              const double samples = static_cast<double>(n_samples);
+              const double intensity = static_cast<double>(lit) / samples;  // intensity_at
+              lr_ = lr_ + (dr / samples) * intensity;
+              lg_ = lg_ + (dg / samples) * intensity;
+              lb_ = lb_ + (db / samples) * intensity;
+            }
+            sr = sr + lr_;
+            sg = sg + lg_;
+            sb = sb + lb_;
+            continue;
+          }
+        }
         const double* __restrict__ L = lights + 6ull * li;
         it_shadow_calls++;
         // isShadowed (world.zig:127-131) and lighting's point_to_light (material.zig:51) share this
@@ -3287,6 +3421,23 @@ extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
 rtc_render_kernel_bigworld_ext(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
                                double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats) {
   render_body<false, true>(S, cam, map, max_depth, out, stats, next_stats);
+}
+
+// Worlds with area lights (rtc_scene_create_with_lights; the book's bonus chapter): the general walk with the csg and
+// texture-map paths compiled in, World.lights' area rows as an extra argument (DevAreaLights) - every other kernel is
+// compiled without them.  Tables in LDS (the area rows beside the point lights, RTC_LDS_LIGHTS of them) or in memory.
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_area(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                       double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                       const DevAreaLights area) {
+  render_body<true, true, 0, 2, false, true, true>(S, cam, map, max_depth, out, stats, next_stats, area);
+}
+
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_area_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                const DevAreaLights area) {
+  render_body<false, true, 0, 2, false, true, true>(S, cam, map, max_depth, out, stats, next_stats, area);
 }
 
 // Rank 0's un-permute after the tile gather: one thread per canvas channel value, so both the read (a run

@@ -203,8 +203,32 @@ FlatScene flattenWorld(const World& world) {
     f.out.light_rgb.push_back(l.intensity.r);
     f.out.light_rgb.push_back(l.intensity.g);
     f.out.light_rgb.push_back(l.intensity.b);
+    const bool area = l.kind == RTC_LIGHT_AREA;
+    f.out.has_area_light = f.out.has_area_light || area;
+    f.out.light_kind.push_back(area ? RTC_LIGHT_AREA : RTC_LIGHT_POINT);
+    Flattener::push3(f.out.light_corner, area ? l.corner : l.position);
+    Flattener::push3(f.out.light_uvec, l.uvec);
+    Flattener::push3(f.out.light_vvec, l.vvec);
+    f.out.light_usteps.push_back(l.usteps);
+    f.out.light_vsteps.push_back(l.vsteps);
+    f.out.light_jitter.push_back(l.jitter ? 1u : 0u);
   }
   return std::move(f.out);
+}
+
+rtc_light_desc FlatScene::lights() const {
+  rtc_light_desc d;
+  std::memset(&d, 0, sizeof(d));
+  d.n_lights = static_cast<uint32_t>(light_kind.size());
+  d.kind = light_kind.data();
+  d.corner = light_corner.data();
+  d.uvec = light_uvec.data();
+  d.vvec = light_vvec.data();
+  d.usteps = light_usteps.data();
+  d.vsteps = light_vsteps.data();
+  d.jitter = light_jitter.data();
+  d.rgb = light_rgb.data();
+  return d;
 }
 
 rtc_scene_desc FlatScene::desc() const {

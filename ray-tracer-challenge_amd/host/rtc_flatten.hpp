@@ -38,9 +38,17 @@ struct FlatScene {
   std::vector<uint64_t> img_offset;
   std::vector<float> img_rgb;
   std::vector<double> light_pos, light_rgb;
+  // World.lights of both kinds (rtc_light_desc): light_pos / light_rgb above hold every light as a point light - an
+  // area light at its centre, so that a caller of rtc_scene_create alone still renders a valid world (hard shadows
+  // from the centres); rtc_scene_create_with_lights takes this table instead.
+  std::vector<uint8_t> light_kind, light_jitter;
+  std::vector<double> light_corner, light_uvec, light_vvec;
+  std::vector<uint32_t> light_usteps, light_vsteps;
+  bool has_area_light = false;
 
   // View over the vectors above; valid while *this is alive and unmodified.
   rtc_scene_desc desc() const;
+  rtc_light_desc lights() const;
 
   size_t leafCount() const { return leaf_kind.size(); }
   size_t nodeCount() const { return node_first.size(); }

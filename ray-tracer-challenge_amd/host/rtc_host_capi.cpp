@@ -18,6 +18,7 @@ struct HostScene {
   rtc::SceneInfo info;
   rtc::FlatScene flat;
   rtc_scene_desc desc;
+  rtc_light_desc lights;
 };
 
 template <typename F>
@@ -50,6 +51,7 @@ int rtch_scene_load(const char* scene_json, const char* data_dir, void** out) {
     hs->info = rtc::parseScene(scene_json, rtc::directoryLoader(data_dir ? data_dir : ""));
     hs->flat = rtc::flattenWorld(hs->info.world);
     hs->desc = hs->flat.desc();
+    hs->lights = hs->flat.lights();
     *out = hs.release();
   });
 }
@@ -61,6 +63,7 @@ void rtch_set_loader_threads(uint32_t threads) { rtc::setLoaderThreads(threads);
 void rtch_scene_free(void* h) { delete static_cast<HostScene*>(h); }
 
 const rtc_scene_desc* rtch_scene_desc(void* h) { return &static_cast<HostScene*>(h)->desc; }
+const rtc_light_desc* rtch_scene_lights(void* h) { return &static_cast<HostScene*>(h)->lights; }
 
 // Camera of the scene file; width/height 0 keep the file's values, otherwise they replace
 // camera.width/height before Camera.new runs (the reference has no such override).
@@ -124,7 +127,8 @@ int rtch_scene_render(void* h, uint32_t width, uint32_t height, uint32_t max_dep
     c.setTransform(c0.transform);
     cam = rtc::flattenCamera(c);
     rtc_scene* scene = nullptr;
-    int st = rtc_scene_create(&hs->desc, &scene);
+    // (a scene with area lights: its light table; point lights only: the description alone, as before)
+    int st = hs->flat.has_area_light ? rtc_scene_create_with_lights(&hs->desc, &hs->lights, &scene) : rtc_scene_create(&hs->desc, &scene);
     if (st == RTC_OK) {
       st = rtc_render(scene, &cam, max_depth, 0, 0, cam.hsize, cam.vsize, rgb_out);
       rtc_scene_destroy(scene);

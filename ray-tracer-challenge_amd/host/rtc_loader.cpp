@@ -12,6 +12,8 @@
 //   obj.zig:53-283      ObjParser
 #include "rtc_loader.hpp"
 
+#include "../../include/rtc.h"
+
 #include <sched.h>
 #include <zlib.h>
 
@@ -654,6 +656,34 @@ SceneInfo parseScene(const std::string& scene_json, const FileLoader& load_file_
 
   for (const Value& l : lights.arr) {  // scene.zig:593-606
     const auto& kv = unionMember(l, "light");
+    if (kv.first == "area-light") {  // the book's bonus chapter: area_light(corner, uvec, usteps, vvec, vsteps, intensity, jitter)
+      const Value& cfg = requireObject(kv.second, "area-light");
+      checkFields(cfg, {"corner", "uvec", "usteps", "vvec", "vsteps", "intensity", "jitter"}, "area-light");
+      double corner[3], u[3], v[3], c[3];
+      asVec3(requireField(cfg, "corner", "area-light"), "corner", corner);
+      asVec3(requireField(cfg, "uvec", "area-light"), "uvec", u);
+      asVec3(requireField(cfg, "vvec", "area-light"), "vvec", v);
+      asVec3(requireField(cfg, "intensity", "area-light"), "intensity", c);
+      const size_t us = asUsize(requireField(cfg, "usteps", "area-light"), "usteps");
+      const size_t vs = asUsize(requireField(cfg, "vsteps", "area-light"), "vsteps");
+      if (us == 0 || vs == 0) throw Error("InvalidData", "area-light: usteps and vsteps are at least 1");
+      if (us > RTC_AREA_MAX_SAMPLES || vs > RTC_AREA_MAX_SAMPLES || us * vs > RTC_AREA_MAX_SAMPLES)
+        throw Error("Overflow", "area-light: more than 4096 samples");
+      Light light;
+      light.kind = RTC_LIGHT_AREA;
+      light.corner = Tuple::point(corner[0], corner[1], corner[2]);
+      light.uvec = Tuple::vec3(u[0], u[1], u[2]);
+      light.vvec = Tuple::vec3(v[0], v[1], v[2]);
+      light.usteps = static_cast<uint32_t>(us);
+      light.vsteps = static_cast<uint32_t>(vs);
+      const Value* jitter = cfg.find("jitter");  // (optional: false)
+      light.jitter = jitter ? asBool(*jitter, "jitter") : false;
+      light.position = Tuple::point((corner[0] + u[0] * 0.5) + v[0] * 0.5, (corner[1] + u[1] * 0.5) + v[1] * 0.5,
+                                    (corner[2] + u[2] * 0.5) + v[2] * 0.5);
+      light.intensity = {c[0], c[1], c[2]};
+      info.world.lights.push_back(light);
+      continue;
+    }
     if (kv.first != "point-light") throw Error("UnknownField", "light." + kv.first);
     const Value& cfg = requireObject(kv.second, "point-light");
     checkFields(cfg, {"position", "intensity"}, "point-light");

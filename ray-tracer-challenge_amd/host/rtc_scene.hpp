@@ -89,8 +89,14 @@ struct Material {  // material.zig:18-25
 };
 
 struct Light {  // light.zig:14-15
-  Tuple position;
+  Tuple position;  // an area light: its centre, (corner + uvec / 2) + vvec / 2
   Color intensity;
+  // an area light (the book's bonus chapter "Rendering soft shadows"): rtc_light_desc's fields, uvec / vvec the full edges
+  uint8_t kind = 0;  // RTC_LIGHT_POINT / RTC_LIGHT_AREA
+  Tuple corner = Tuple::point(0.0, 0.0, 0.0);
+  Tuple uvec = Tuple::vec3(0.0, 0.0, 0.0), vvec = Tuple::vec3(0.0, 0.0, 0.0);
+  uint32_t usteps = 1, vsteps = 1;
+  bool jitter = false;
 };
 
 // ---------------------------------------------------------------- bounding boxes

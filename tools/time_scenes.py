@@ -3,6 +3,7 @@
 
     python tools/time_scenes.py [--set configs|mesh|misc|all] [--scenes a,b,..] [--size WxH] [--depth N]
                                 [--handles 3] [--settle 50] [--frames 20] [--option name=value ...] [--check]
+                                [--lights scene | area=N | grid=N]
 
   configs  the five BASELINE configs at their own sizes and depths (fresnel 300x300, cover / teapot 1080p, r&r 1080p
            depth 8, dragons 4K)                                                       [default]
@@ -11,7 +12,10 @@
 Each scene: `--handles` fresh scene handles (every handle measures its own first frame and packs its own schedule),
 `--settle` untimed frames, then `--frames` timed back to back; prints min [mean max] over the handles and the kernel
 that ran.  --check: also compares every 24th row with the CPU oracle (needs oracle/build/liboracle.so).
-The library directory is the package's, or $RTC_LIB_DIR (tools/variants.py points it at a variant build)."""
+The library directory is the package's, or $RTC_LIB_DIR (tools/variants.py points it at a variant build).
+--lights: the scene's light table through rtc_scene_create_with_lights (`scene`), with every area light at N x N samples
+(`area=N`), or every area light replaced by N x N point lights at its cells' centres, intensity / N^2 (`grid=N`: the same
+shadow rays through the point-light kernels); prints shadow_traced per frame and ns per traced shadow ray as well."""
 import argparse, importlib, os, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, "tests"))
@@ -38,6 +42,7 @@ ap.add_argument("--frames", type=int, default=20)
 ap.add_argument("--option", action="append", default=[])
 ap.add_argument("--check", action="store_true")
 ap.add_argument("--label", default="")
+ap.add_argument("--lights", default="")
 args = ap.parse_args()
 cases = SETS[args.set]
 if args.scenes:
@@ -51,14 +56,40 @@ if args.depth:
 for opt in args.option:
     n, v = opt.split("=")
     rtc.set_option(n, float(v))
+
+
+def light_table(hs, how):
+    """(None, or the LightDesc that --lights asks for)"""
+    if not how:
+        return None
+    lights = hs.lights.to_list()
+    if how.startswith("area="):
+        n = int(how.split("=")[1])
+        for l in lights:
+            if l["kind"] == "area": l["usteps"] = l["vsteps"] = n
+    elif how.startswith("grid="):
+        n, grid = int(how.split("=")[1]), []
+        for l in lights:
+            if l["kind"] != "area":
+                grid.append(l)
+                continue
+            for v in range(n):
+                for u in range(n):
+                    pos = [(l["corner"][k] + l["uvec"][k] / n * (u + 0.5)) + l["vvec"][k] / n * (v + 0.5) for k in range(3)]
+                    grid.append({"kind": "point", "position": pos, "intensity": [c / (n * n) for c in l["intensity"]]})
+        lights = grid
+    return rtc.LightDesc.make(lights)
+
+
 stream = torch.cuda.Stream(); torch.cuda.set_stream(stream)
 out = []
 for name, w, h, depth in cases:
     hs = rtc.HostScene.from_file(name + ".json"); cam = hs.camera(w, h)
     canvas = torch.empty((h, w, 3), dtype=torch.float64, device="cuda")
     ts, kernel, delta = [], "", None
+    table = light_table(hs, args.lights)
     for rep in range(args.handles):
-        gpu = rtc.GpuScene(hs.desc)
+        gpu = rtc.GpuScene(hs.desc, lights=table)
         for i in range(args.settle):
             gpu.render_device(cam, canvas.data_ptr(), depth, None, stream.cuda_stream)
         torch.cuda.synchronize()
@@ -79,5 +110,7 @@ for name, w, h, depth in cases:
         gpu.close()
     line = f"{name[:14]} {min(ts):.4f} [{sum(ts) / len(ts):.4f} {max(ts):.4f}] {kernel.replace('rtc_render_kernel', 'k')}"
     if delta is not None: line += f" maxdelta {delta:.2e}"
+    if args.lights:
+        line += f" shadow_traced {st['shadow_traced']} ns/shadow-ray {min(ts) * 1e6 / max(1, st['shadow_traced']):.3f}"
     out.append(line)
     print((args.label + " " if args.label else "") + line, flush=True)
