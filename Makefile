@@ -7,6 +7,7 @@
 #   ray-tracer-challenge_amd/lib/rtc_host_kat    product unit tests (reference KATs for the build-time helpers)
 #   oracle/build/liboracle.so, oracle_kat        test infrastructure only
 #   tests/build/libarea_oracle.so                test infrastructure only: the area-light checker (tests/cpp/area_oracle.cpp)
+#   tests/build/libcamera_oracle.so              test infrastructure only: the camera-sampling checker (tests/cpp/camera_oracle.cpp)
 #
 # -ffp-contract=off everywhere: the reference's float mode is strict IEEE
 # (SURVEY F10); the GPU path and the oracle must round identically.
@@ -32,10 +33,14 @@ oracle:
 	$(MAKE) -C oracle
 
 # (the area-light checker includes the oracle's sources read-only; -pthread and -O3 as the oracle's own build)
-checker: tests/build/libarea_oracle.so
+checker: tests/build/libarea_oracle.so tests/build/libcamera_oracle.so
 tests/build/libarea_oracle.so: tests/cpp/area_oracle.cpp oracle/oracle_capi.cpp oracle/rtc_oracle.hpp oracle/rtc_oracle_scene.hpp include/rtc.h
 	mkdir -p tests/build
 	$(CXX) -std=c++17 -O3 -ffp-contract=off -fPIC -Wall -Wextra -pthread -shared -o $@ tests/cpp/area_oracle.cpp
+# (the camera-sampling checker includes the area-light checker, read-only)
+tests/build/libcamera_oracle.so: tests/cpp/camera_oracle.cpp tests/cpp/area_oracle.cpp oracle/oracle_capi.cpp oracle/rtc_oracle.hpp oracle/rtc_oracle_scene.hpp include/rtc.h
+	mkdir -p tests/build
+	$(CXX) -std=c++17 -O3 -ffp-contract=off -fPIC -Wall -Wextra -Wno-subobject-linkage -pthread -shared -o $@ tests/cpp/camera_oracle.cpp
 
 $(LIB):
 	mkdir -p $(LIB)

@@ -276,6 +276,34 @@ typedef struct rtc_light_desc {
 int rtc_scene_create_with_lights(const rtc_scene_desc *desc, const rtc_light_desc *lights, rtc_scene **out);
 /* The seed of the area lights' jitter on this handle (default 0; a clone starts with its source's). */
 int rtc_scene_set_light_seed(rtc_scene *scene, uint64_t seed);
+
+/* ---- camera samples per pixel: anti-aliasing and focal blur ---- */
+#define RTC_SAMPLING_MAX_GRID 16u
+
+/*
+ * grid x grid samples per pixel, sample k = j * grid + i (j outer).  Sample k of pixel (x, y) goes through
+ *   world_x = half_width - (x + (i + jx) / grid) * pixel_size,  world_y = half_height - (y + (j + jy) / grid) * pixel_size,
+ * jx = jy = 0.5 without jitter.  aperture == 0: a pinhole, the ray of Camera.rayForPixel through that point (grid 1
+ * without jitter is rayForPixel to the bit).  aperture > 0: a lens of that radius in camera units, the ray from a point
+ * of the lens disc through (world_x, world_y, -1) * focal_distance; the lens is always jittered.  The pixel is the
+ * mean of its samples' colours.  The jitter is a pure function of (seed, whole-image pixel, sample, axis), so an image
+ * does not depend on how it was split into bands, tiles or launches; an area light's jitter is keyed on
+ * pixel * samples + k.  rtc_stats.primary counts every sample.
+ */
+typedef struct rtc_sampling {
+  uint32_t grid;          /* 1 .. RTC_SAMPLING_MAX_GRID                       */
+  uint32_t jitter;        /* 0 / 1: the sub-pixel offsets jittered            */
+  double aperture;        /* lens radius, finite, >= 0 (0: a pinhole)         */
+  double focal_distance;  /* finite, > 0 when aperture > 0 (else ignored)     */
+  uint64_t seed;
+} rtc_sampling;
+
+/*
+ * This handle's sampling for every render entry point (rtc_render, _rgba8, _device, _tiles_device,
+ * _tile_list_device; NULL: the default, grid 1, no jitter, aperture 0).  Validated before anything changes:
+ * RTC_ERR_INVALID_ARGUMENT otherwise.  A clone starts with its source's setting; rtc_render's band clones follow.
+ */
+int rtc_scene_set_sampling(rtc_scene *scene, const rtc_sampling *sampling);
 void rtc_scene_destroy(rtc_scene *scene);
 
 /*

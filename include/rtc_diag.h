@@ -28,7 +28,9 @@ extern "C" {
  * runs on at most one wave per this many chunks; 3, 0 = no cap), "build_threads" (threads rtc_scene_create builds the
  * groups' candidate BVHs with, one top-level group each; 0 = the library's choice, at most 16; the tables do not depend
  * on it), "box_cull" (read at create: a world of top-level spheres / planes / cubes runs the kernels whose root loop
- * rejects by world boxes - 1 - or by bounding spheres - 0; < 0: boxes if it has more cubes than spheres).
+ * rejects by world boxes - 1 - or by bounding spheres - 0; < 0: boxes if it has more cubes than spheres),
+ * "sampling_kernels" (!= 0: the camera-sampling kernels even with the default sampling - one centred ray per pixel -, so
+ * that their one-sample images can be held to the other kernels').
  * RTC_ERR_INVALID_ARGUMENT for a name the library does not know.
  * (The library reads no environment variables.)
  */

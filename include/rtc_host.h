@@ -14,7 +14,8 @@
  *   rtch_canvas_ppm      Canvas.ppm, canvas.zig:181-254
  *   rtch_canvas_rgba8    the RGBA8 framebuffer of lib.zig:146-153 (clamp, color.zig:61-71)
  *   rtch_scene_render    main.zig:92: load -> Camera.render -> Canvas, through rtc_scene_create / rtc_render
- *                        (rtc_scene_create_with_lights when the scene has an area light)
+ *                        (rtc_scene_create_with_lights when the scene has an area light; the camera's
+ *                        sampling, rtch_scene_sampling, through rtc_scene_set_sampling)
  *
  * Every function that returns int returns 0 on success; otherwise rtch_last_error()
  * holds "<ZigStyleErrorName>: detail" (thread-local).
@@ -45,6 +46,9 @@ const rtc_scene_desc *rtch_scene_desc(void *handle);
  * rtc_scene_create_with_lights.  The description's light_pos / light_rgb hold every light as a point light - an area
  * light at its centre - so rtc_scene_create alone renders the same world with hard shadows from the centres. */
 const rtc_light_desc *rtch_scene_lights(void *handle);
+/* The camera's "sampling" of the scene file (anti-aliasing, focal blur), or the defaults - grid 1, no jitter,
+ * aperture 0 - when it has none; pass it to rtc_scene_set_sampling.  Camera rotate / move leave it alone. */
+int rtch_scene_sampling(void *handle, rtc_sampling *out);
 int rtch_scene_camera(void *handle, uint32_t width, uint32_t height, rtc_camera *out);
 int rtch_camera_rotate(void *handle, double angle);
 int rtch_camera_move(void *handle, double distance);

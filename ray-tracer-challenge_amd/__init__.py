@@ -140,18 +140,29 @@ class LightDesc(C.Structure):
         return out
 
 
+class Sampling(C.Structure):
+    """struct rtc_sampling (include/rtc.h): camera samples per pixel - anti-aliasing and focal blur."""
+
+    _fields_ = [("grid", C.c_uint32), ("jitter", C.c_uint32), ("aperture", C.c_double), ("focal_distance", C.c_double),
+                ("seed", C.c_uint64)]
+
+    def to_dict(self):
+        return {"grid": self.grid, "jitter": bool(self.jitter), "aperture": self.aperture,
+                "focal_distance": self.focal_distance, "seed": self.seed}
+
+
 # (include/rtc.h: what a host binds ...)
 RTC_SYMBOLS = ["rtc_scene_create", "rtc_scene_clone", "rtc_scene_destroy", "rtc_render", "rtc_render_rgba8", "rtc_render_device",
                "rtc_render_tiles_device", "rtc_assemble_tiles_device", "rtc_render_tile_list_device", "rtc_get_tile_costs",
                "rtc_assign_tiles", "rtc_assemble_tile_list_device", "rtc_assemble_tile_list_rgba8_device", "rtc_scatter_tile_list_device",
                "rtc_scatter_tile_list_rgba8_device", "rtc_scene_synchronize", "rtc_get_stats", "rtc_last_error", "rtc_status_name",
                "rtc_grow_csg_lists", "rtc_canvas_register", "rtc_canvas_unregister", "rtc_rgba8_device",
-               "rtc_scene_create_with_lights", "rtc_scene_set_light_seed"]
+               "rtc_scene_create_with_lights", "rtc_scene_set_light_seed", "rtc_scene_set_sampling"]
 # (... and include/rtc_diag.h: diagnostics and tuning, for the tests, bench.py and tools/)
 RTC_DIAG_SYMBOLS = ["rtc_set_option", "rtc_last_kernel_name", "rtc_get_schedule", "rtc_get_chunk_times", "rtc_diag_build_tables", "rtc_diag_root_boxes"]
 HOST_SYMBOLS = ["rtch_last_error", "rtch_scene_load", "rtch_scene_free", "rtch_scene_desc", "rtch_scene_camera",
                 "rtch_camera_rotate", "rtch_camera_move", "rtch_camera_make", "rtch_canvas_ppm", "rtch_canvas_rgba8", "rtch_scene_render", "rtch_set_loader_threads",
-                "rtch_scene_lights"]
+                "rtch_scene_lights", "rtch_scene_sampling"]
 
 MULTI_SYMBOLS = ["rtc_multi_create", "rtc_multi_destroy", "rtc_multi_render", "rtc_multi_render_rgba8", "rtc_multi_render_device", "rtc_multi_render_rgba8_device",
                  "rtc_multi_synchronize", "rtc_multi_stream", "rtc_multi_get_stats", "rtc_multi_balance", "rtc_multi_last_error"]
@@ -201,6 +212,7 @@ def hip_lib():
         lib.rtc_scene_clone.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
         lib.rtc_scene_create_with_lights.argtypes = [C.POINTER(SceneDesc), C.POINTER(LightDesc), C.POINTER(C.c_void_p)]
         lib.rtc_scene_set_light_seed.argtypes = [C.c_void_p, C.c_uint64]
+        lib.rtc_scene_set_sampling.argtypes = [C.c_void_p, C.POINTER(Sampling)]
         lib.rtc_scene_destroy.argtypes = [C.c_void_p]
         lib.rtc_scene_destroy.restype = None
         lib.rtc_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32] + [C.c_uint32] * 4 + [C.c_void_p]
@@ -249,6 +261,7 @@ def host_lib():
         lib.rtch_scene_desc.restype = C.POINTER(SceneDesc)
         lib.rtch_scene_lights.argtypes = [C.c_void_p]
         lib.rtch_scene_lights.restype = C.POINTER(LightDesc)
+        lib.rtch_scene_sampling.argtypes = [C.c_void_p, C.POINTER(Sampling)]
         lib.rtch_scene_camera.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Camera)]
         lib.rtch_camera_rotate.argtypes = [C.c_void_p, C.c_double]
         lib.rtch_camera_move.argtypes = [C.c_void_p, C.c_double]
@@ -394,6 +407,12 @@ class HostScene:
         _check_host(host_lib().rtch_scene_camera(self._h, width, height, C.byref(cam)))
         return cam
 
+    def sampling(self):
+        """The camera's "sampling" of the scene file (rtch_scene_sampling), or the defaults: a Sampling."""
+        s = Sampling()
+        _check_host(host_lib().rtch_scene_sampling(self._h, C.byref(s)))
+        return s
+
     def rotate_camera(self, angle):
         """Renderer.rotateCamera (lib.zig:166-178): orbit the camera around its target, about `up`."""
         _check_host(host_lib().rtch_camera_rotate(self._h, C.c_double(angle)))
@@ -448,6 +467,15 @@ class GpuScene:
     def set_light_seed(self, seed):
         """rtc_scene_set_light_seed: the seed of the area lights' jitter on this handle."""
         _check_hip(hip_lib().rtc_scene_set_light_seed(self._s, seed))
+
+    def set_sampling(self, grid=1, jitter=False, aperture=0.0, focal_distance=1.0, seed=0):
+        """rtc_scene_set_sampling: grid x grid camera samples per pixel, optionally jittered, through a lens of radius
+        `aperture` focused at `focal_distance` (0: a pinhole).  A Sampling as `grid` is passed as it is; None: the default."""
+        if grid is None:
+            _check_hip(hip_lib().rtc_scene_set_sampling(self._s, None))
+            return
+        s = grid if isinstance(grid, Sampling) else Sampling(grid, 1 if jitter else 0, aperture, focal_distance, seed)
+        _check_hip(hip_lib().rtc_scene_set_sampling(self._s, C.byref(s)))
 
     def clone(self):
         """rtc_scene_clone: a handle of its own (stream, schedule, counters) on the same device copy of the scene - one

@@ -73,6 +73,22 @@ __global__ void rtc_render_kernel_area_bigworld(const DevScene S, const DevCamer
                                                 double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
                                                 const DevAreaLights area);
 }
+// The sampling kernels (rtc_scene_set_sampling: several camera samples per pixel).  Their table edges - the LDS limits of
+// lights and roots, for the point and the area form - are tested in tests/test_sampling_gpu.py (test_table_edge).
+extern "C" {
+__global__ void rtc_render_kernel_ms(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                     double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                     const DevSampling smp);
+__global__ void rtc_render_kernel_ms_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                              double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                              const DevSampling smp);
+__global__ void rtc_render_kernel_area_ms(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                          double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                          const DevAreaLights area, const DevSampling smp);
+__global__ void rtc_render_kernel_area_ms_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                                   double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                                   const DevAreaLights area, const DevSampling smp);
+}
 extern "C" __global__ void rtc_estimate_kernel(const DevScene S, const DevCamera cam, const DevPixelMap map,
                                                uint32_t* __restrict__ chunk_cost, uint32_t* __restrict__ chunk_time,
                                                DevChunkShape* __restrict__ chunk_shape, DevPackState* __restrict__ state
@@ -273,21 +289,34 @@ bool tablesInLds(const rtc_scene* s) {
          s->dev.n_patterns <= RTC_LDS_PATTERNS && s->dev.n_lights <= RTC_LDS_LIGHTS;
 }
 
-// (the area kernels take one more argument, DevAreaLights: `area` instead of `fn`)
+// (the area kernels take one more argument, DevAreaLights: `area` instead of `fn`; the sampling kernels DevSampling:
+// `ms`, and both: `area_ms`)
 struct KernelChoice {
   decltype(&rtc_render_kernel) fn;
   const char* name;
   decltype(&rtc_render_kernel_area) area = nullptr;
+  decltype(&rtc_render_kernel_ms) ms = nullptr;
+  decltype(&rtc_render_kernel_area_ms) area_ms = nullptr;
   KernelChoice(decltype(&rtc_render_kernel) f, const char* n) : fn(f), name(n) {}
   KernelChoice(decltype(&rtc_render_kernel_area) a, const char* n) : fn(nullptr), name(n), area(a) {}
+  KernelChoice(decltype(&rtc_render_kernel_ms) m, const char* n) : fn(nullptr), name(n), ms(m) {}
+  KernelChoice(decltype(&rtc_render_kernel_area_ms) am, const char* n) : fn(nullptr), name(n), area_ms(am) {}
   void launch(uint32_t blocks, hipStream_t stream, const rtc_scene* s, const DevScene& dev, const DevCamera& cam, const DevPixelMap& map,
               uint32_t max_depth, double* d_out, DevStats* st_now, DevStats* st_next) const {
-    if (area)
+    if (area_ms)
+      hipLaunchKernelGGL(area_ms, dim3(blocks), dim3(256), 0, stream, dev, cam, map, max_depth, d_out, st_now, st_next, s->area,
+                         s->sampling);
+    else if (ms)
+      hipLaunchKernelGGL(ms, dim3(blocks), dim3(256), 0, stream, dev, cam, map, max_depth, d_out, st_now, st_next, s->sampling);
+    else if (area)
       hipLaunchKernelGGL(area, dim3(blocks), dim3(256), 0, stream, dev, cam, map, max_depth, d_out, st_now, st_next, s->area);
     else
       hipLaunchKernelGGL(fn, dim3(blocks), dim3(256), 0, stream, dev, cam, map, max_depth, d_out, st_now, st_next);
   }
 };
+// The sampling kernels run when the handle's sampling is not the default (one centred ray per pixel, no lens) - or,
+// for tests, whenever option "sampling_kernels" is set.  Otherwise the kernels run exactly as before.
+bool samplingKernels(const rtc_scene* s) { return s->sampling_on || rtcOptions().sampling_kernels != 0.0; }
 #define RTC_KERNEL(k) KernelChoice{k, #k}
 // The general kernel at three waves per SIMD (rtc_render_kernel3): forced by option "waves3", else what the handle's
 // trial measured (KernelTune in launch()).
@@ -314,6 +343,10 @@ KernelChoice ldsKernel(const rtc_scene* s, const DevPixelMap& map) {
   return s->ext_kernel ? RTC_KERNEL(rtc_render_kernel_ext) : RTC_KERNEL(rtc_render_kernel);
 }
 KernelChoice renderKernel(const rtc_scene* s, const DevPixelMap& map) {
+  if (samplingKernels(s)) {
+    if (s->area_kernel) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_area_ms) : RTC_KERNEL(rtc_render_kernel_area_ms_bigworld);
+    return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_ms) : RTC_KERNEL(rtc_render_kernel_ms_bigworld);
+  }
   if (s->area_kernel) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_area) : RTC_KERNEL(rtc_render_kernel_area_bigworld);
   if (tablesInLds(s)) return ldsKernel(s, map);
   return s->ext_kernel ? RTC_KERNEL(rtc_render_kernel_bigworld_ext) : RTC_KERNEL(rtc_render_kernel_bigworld);
@@ -322,6 +355,7 @@ KernelChoice renderKernel(const rtc_scene* s, const DevPixelMap& map) {
 
 // Work-groups of the launch's kernel that are resident at once, and the waves in them.
 uint32_t residentBlocksAlone(const rtc_scene* s, const DevPixelMap& map) {
+  if (samplingKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_ms_lds : s->blocks_per_cu_ms_big);
   if (usesSimple3(s, map)) return s->n_cus * s->blocks_per_cu_simple3;
   if (tablesInLds(s) && usesGeneral3(s)) return s->n_cus * s->blocks_per_cu_general3;
   return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_lds : s->blocks_per_cu_big);
@@ -725,10 +759,11 @@ int launch(rtc_scene* s, const rtc_camera& cam, const DevPixelMap& map_in, uint3
   int trial_slot = -1;
   {
     rtc_scene::KernelTune& T = s->tune;
-    const bool eligible = (s->general3_ok && rtcOptions().waves3 < 0.0 && tablesInLds(s) &&
-                           !(s->tab && s->tab->handles.load(std::memory_order_relaxed) > 1) &&
-                           static_cast<double>(map.n_chunks) >= 4.0 * 4.0 * s->n_cus * s->blocks_per_cu_lds) ||
-                          simple3Trial(s, map);  // (a simple world's launch of a size where neither of its kernels always wins)
+    const bool eligible = !samplingKernels(s) &&  // (the sampling kernels have no three-wave form)
+                          ((s->general3_ok && rtcOptions().waves3 < 0.0 && tablesInLds(s) &&
+                            !(s->tab && s->tab->handles.load(std::memory_order_relaxed) > 1) &&
+                            static_cast<double>(map.n_chunks) >= 4.0 * 4.0 * s->n_cus * s->blocks_per_cu_lds) ||
+                           simple3Trial(s, map));  // (a simple world's launch of a size where neither of its kernels always wins)
     if (eligible && T.key != s->cost_key) {  // another pixel map: a trial of its own (the last choice stands until it ends)
       T.key = s->cost_key;
       T.state = 0;
@@ -2047,8 +2082,17 @@ int uploadTables(const rtc_scene_desc& d, const SceneTraits& traits, const HostT
       HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_area_bigworld, 256, 0));
       s->blocks_per_cu_big = static_cast<uint32_t>(std::max(nb, 1));
     }
-    if (const int v = static_cast<int>(rtcOptions().blocks_per_cu); v >= 1)  // (tuning option)
+    // (the sampling kernels of this world, whichever setting a handle of it takes later)
+    if (s->area_kernel) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_area_ms, 256, 0));
+    else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_ms, 256, 0));
+    s->blocks_per_cu_ms_lds = static_cast<uint32_t>(std::max(nb, 1));
+    if (s->area_kernel) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_area_ms_bigworld, 256, 0));
+    else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_ms_bigworld, 256, 0));
+    s->blocks_per_cu_ms_big = static_cast<uint32_t>(std::max(nb, 1));
+    if (const int v = static_cast<int>(rtcOptions().blocks_per_cu); v >= 1) {  // (tuning option)
       s->blocks_per_cu_lds = std::min<uint32_t>(s->blocks_per_cu_lds, v), s->blocks_per_cu_big = std::min<uint32_t>(s->blocks_per_cu_big, v);
+      s->blocks_per_cu_ms_lds = std::min<uint32_t>(s->blocks_per_cu_ms_lds, v), s->blocks_per_cu_ms_big = std::min<uint32_t>(s->blocks_per_cu_ms_big, v);
+    }
   }
   DevScene& D = s->dev;
   D.root_recs = s->tab->root_recs.p;
@@ -2255,6 +2299,39 @@ int rtc_scene_set_light_seed(rtc_scene* s, uint64_t seed) {
   return RTC_OK;
 }
 
+// The default: one centred ray per pixel through a pinhole (Camera.rayForPixel).
+static bool defaultSampling(const rtc_sampling& v) { return v.grid == 1u && v.jitter == 0u && v.aperture == 0.0; }
+
+static void applySampling(rtc_scene* s, const rtc_sampling& v) {
+  s->sampling_desc = v;
+  s->sampling_on = !defaultSampling(v);
+  DevSampling& d = s->sampling;
+  d.key = rtc_mix64(v.seed ^ 0x243F6A8885A308D3ull);
+  d.grid = v.grid;
+  d.samples = v.grid * v.grid;
+  d.weight = 1.0 / static_cast<double>(d.samples);
+  d.jitter = v.jitter;
+  d.aperture = v.aperture;
+  d.focal = v.aperture > 0.0 ? v.focal_distance : 1.0;
+}
+
+int rtc_scene_set_sampling(rtc_scene* s, const rtc_sampling* sampling) {
+  g_error.clear();
+  if (!s) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
+  rtc_sampling v{1u, 0u, 0.0, 1.0, 0ull};
+  if (sampling) {
+    v = *sampling;
+    if (v.grid < 1u || v.grid > RTC_SAMPLING_MAX_GRID) return fail(RTC_ERR_INVALID_ARGUMENT, "sampling: grid %u (1 to %u)", v.grid, RTC_SAMPLING_MAX_GRID);
+    if (v.jitter > 1u) return fail(RTC_ERR_INVALID_ARGUMENT, "sampling: jitter %u (0 or 1)", v.jitter);
+    if (!std::isfinite(v.aperture) || v.aperture < 0.0) return fail(RTC_ERR_INVALID_ARGUMENT, "sampling: aperture %g", v.aperture);
+    if (v.aperture > 0.0 && !(std::isfinite(v.focal_distance) && v.focal_distance > 0.0))
+      return fail(RTC_ERR_INVALID_ARGUMENT, "sampling: focal distance %g with an aperture", v.focal_distance);
+  }
+  applySampling(s, v);
+  for (rtc_scene* b : s->band) applySampling(b, v);  // (the band clones rtc_render renders a large frame with)
+  return RTC_OK;
+}
+
 int rtc_scene_clone(const rtc_scene* src, rtc_scene** out) {
   g_error.clear();
   if (!src || !out) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
@@ -2277,6 +2354,9 @@ int rtc_scene_clone(const rtc_scene* src, rtc_scene** out) {
   s->ext_kernel = src->ext_kernel;
   s->area_kernel = src->area_kernel;
   s->area = src->area;  // (the rows the scene's device copy holds, and the source's seed)
+  applySampling(s, src->sampling_desc);
+  s->blocks_per_cu_ms_lds = src->blocks_per_cu_ms_lds;
+  s->blocks_per_cu_ms_big = src->blocks_per_cu_ms_big;
   s->simple_kernel = src->simple_kernel;
   s->flat_kernel = src->flat_kernel;
   s->simple3_ok = src->simple3_ok;
@@ -2670,7 +2750,8 @@ int rtc_set_option(const char* name, double value) {
                {"sched_tmin", &o.sched_tmin}, {"bvh_leaf", &o.bvh_leaf}, {"bvh_one_axis", &o.bvh_one_axis},
                {"bvh_check", &o.bvh_check}, {"host_bands", &o.host_bands}, {"waves3", &o.waves3},
                {"measure_every", &o.measure_every}, {"sched_mix", &o.sched_mix},
-               {"inflight_chunks_per_wave", &o.inflight_chunks_per_wave}, {"build_threads", &o.build_threads}, {"box_cull", &o.box_cull}};
+               {"inflight_chunks_per_wave", &o.inflight_chunks_per_wave}, {"build_threads", &o.build_threads}, {"box_cull", &o.box_cull},
+               {"sampling_kernels", &o.sampling_kernels}};
   for (const auto& e : table)
     if (std::strcmp(e.name, name) == 0) {
       e.slot->set(value);

@@ -285,6 +285,30 @@ __host__ __device__ inline double rtc_area_jitter(unsigned long long seed, unsig
   return static_cast<double>(z >> 11) * 0x1.0p-53;
 }
 
+// Camera samples per pixel (rtc_scene_set_sampling): the extra argument of the sampling kernels
+// only, so that DevCamera - and with it every other kernel's code - stays as it is.  grid x grid samples per pixel,
+// sample k = j * grid + i; `key` is mix(seed ^ 0x243F6A8885A308D3), the per-handle half of the camera hash.
+struct DevSampling {
+  unsigned long long key;
+  double weight;           // 1 / samples: each sample's primary ray carries it
+  double aperture, focal;  // lens radius (0: a pinhole) and focal distance, in camera units
+  uint32_t grid, samples, jitter;
+};
+
+// j(axis) of sample k of the whole-image pixel p (axis 0 / 1: the sub-pixel offset, 2 and up: the lens): a pure function,
+// the same bits in the kernels and in the checker.  splitmix64's finaliser on key + golden * (c + 1).
+__host__ __device__ inline unsigned long long rtc_mix64(unsigned long long z) {
+  z ^= z >> 30;
+  z *= 0xBF58476D1CE4E5B9ull;
+  z ^= z >> 27;
+  z *= 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+__host__ __device__ inline double rtc_camera_jitter(unsigned long long key, unsigned long long p, uint32_t k, uint32_t axis) {
+  const unsigned long long c = (p << 32) | (static_cast<unsigned long long>(k) << 8) | axis;
+  return static_cast<double>(rtc_mix64(key + 0x9E3779B97F4A7C15ull * (c + 1ull)) >> 11) * 0x1.0p-53;
+}
+
 struct DevCamera {
   double half_width, half_height, pixel_size;
   double inv[12];  // rows 0..2 of Camera._inverse_transform

@@ -65,6 +65,7 @@ struct RtcOptions {
   RtcOption measure_every{1.0};        // a moving view is measured (and its schedule re-packed) every this many frames (see updateSchedule)
   RtcOption host_bands{0.0};           // bands rtc_render cuts a frame into (copy of band i under the render of band i + 1); 0: by size
   RtcOption box_cull{-1.0};            // a simple world's kernels reject roots by world boxes (1) or bounding spheres (0); < 0: boxes if it has more cubes than spheres
+  RtcOption sampling_kernels{0.0};     // != 0: the sampling kernels even with the default sampling (tests: one sample against the other kernels)
   RtcOption build_threads{0.0};        // threads of rtc_scene_create's candidate-BVH build (one top-level group each); 0: as many as the host allows, up to 8
 };
 inline RtcOptions& rtcOptions() {
@@ -143,6 +144,10 @@ struct rtc_scene {
   const char* last_kernel = "";   // name of the render kernel of the last launch (rtc_last_kernel_name)
   bool area_kernel = false;        // World.lights has an area light: the area kernels, with `area` as their extra argument
   DevAreaLights area{};            // rows (in SceneTables::area) and this handle's jitter seed (rtc_scene_set_light_seed)
+  rtc_sampling sampling_desc{1u, 0u, 0.0, 1.0, 0ull};  // rtc_scene_set_sampling (a clone starts with its source's)
+  DevSampling sampling{0ull, 1.0, 0.0, 1.0, 1u, 1u, 0u};  // ... as the sampling kernels' argument
+  bool sampling_on = false;        // not the default: the sampling kernels
+  uint32_t blocks_per_cu_ms_lds = 1, blocks_per_cu_ms_big = 1;  // resident work-groups of the world's sampling kernels
   bool simple3_ok = false;         // a simple world whose tables fit the three-waves-per-SIMD kernel's LDS (RTC_LDS3_*)
   void* d_csg_buf = nullptr;       // DevPixelMap::csg_buf, only for scenes with csg nodes
   size_t csg_buf_capacity = 0;     // bytes

@@ -2190,6 +2190,87 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned v) {
   return s;
 }
 
+// (MS) The whole image's pixel of a launch's output index: the rectangle, or the rank's tiles (DevPixelMap).
+__device__ __forceinline__ void map_pixel(const DevPixelMap& map, size_t out_index, uint32_t& px, uint32_t& py) {
+  if (map.mode == 0u) {
+    const uint32_t ry = static_cast<uint32_t>(out_index / map.w);
+    px = map.x0 + static_cast<uint32_t>(out_index - static_cast<size_t>(ry) * map.w);
+    py = map.y0 + ry;
+  } else {
+    const size_t per_tile = static_cast<size_t>(map.tile_w) * map.tile_h;
+    const uint32_t region = static_cast<uint32_t>(out_index / per_tile);
+    const uint32_t r = static_cast<uint32_t>(out_index - static_cast<size_t>(region) * per_tile);
+    const uint32_t ry = r / map.tile_w, rx = r - ry * map.tile_w;
+    const uint32_t tile = map.mode == 1u ? map.first_tile + region * map.tile_stride : map.tile_list[region];
+    const uint32_t ty = tile / map.tiles_x;
+    px = (tile - ty * map.tiles_x) * map.tile_w + rx;
+    py = ty * map.tile_h + ry;
+  }
+}
+
+// (MS) The primary ray of camera sample k of pixel (px, py) - DESIGN.md section 12.  Sub-pixel offsets (i + jx) / grid,
+// (j + jy) / grid; with grid 1 and no jitter this is Camera.rayForPixel (camera.zig:64-76) to the bit.  With an aperture
+// the origin is a point of the lens disc (rejection sampling on the camera hash, no sin / cos) and the ray passes through
+// the pixel's point on the focal plane.
+__device__ __forceinline__ Ray camera_sample(const DevCamera& cam, const DevSampling& smp, uint32_t px, uint32_t py, uint32_t k) {
+  const uint32_t j = k / smp.grid, i = k - j * smp.grid;
+  const unsigned long long p = static_cast<unsigned long long>(py) * cam.hsize + px;
+  double jx = 0.5, jy = 0.5;
+  if (smp.jitter) {
+    jx = rtc_camera_jitter(smp.key, p, k, 0u);
+    jy = rtc_camera_jitter(smp.key, p, k, 1u);
+  }
+  const double n = static_cast<double>(smp.grid);
+  const double ox = (static_cast<double>(i) + jx) / n, oy = (static_cast<double>(j) + jy) / n;
+  const double xoffset = (static_cast<double>(px) + ox) * cam.pixel_size;
+  const double yoffset = (static_cast<double>(py) + oy) * cam.pixel_size;
+  const double world_x = cam.half_width - xoffset;
+  const double world_y = cam.half_height - yoffset;
+  Ray r;
+  double pix_x, pix_y, pix_z;
+  if (smp.aperture > 0.0) {
+    double lx = 0.0, ly = 0.0;
+    for (uint32_t t = 0u; t < 32u; ++t) {
+      const double a = 2.0 * rtc_camera_jitter(smp.key, p, k, 2u + 2u * t) - 1.0;
+      const double b = 2.0 * rtc_camera_jitter(smp.key, p, k, 3u + 2u * t) - 1.0;
+      if ((a * a) + (b * b) <= 1.0) {
+        lx = a;
+        ly = b;
+        break;
+      }
+    }
+    const double f = smp.focal, ax = smp.aperture * lx, ay = smp.aperture * ly;
+    const double fx = world_x * f, fy = world_y * f;
+    pix_x = row_pt(cam.inv + 0, fx, fy, -f);
+    pix_y = row_pt(cam.inv + 4, fx, fy, -f);
+    pix_z = row_pt(cam.inv + 8, fx, fy, -f);
+    r.ox = row_pt(cam.inv + 0, ax, ay, 0.0);
+    r.oy = row_pt(cam.inv + 4, ax, ay, 0.0);
+    r.oz = row_pt(cam.inv + 8, ax, ay, 0.0);
+  } else {
+    pix_x = row_pt(cam.inv + 0, world_x, world_y, -1.0);
+    pix_y = row_pt(cam.inv + 4, world_x, world_y, -1.0);
+    pix_z = row_pt(cam.inv + 8, world_x, world_y, -1.0);
+    r.ox = row_pt(cam.inv + 0, 0.0, 0.0, 0.0);
+    r.oy = row_pt(cam.inv + 4, 0.0, 0.0, 0.0);
+    r.oz = row_pt(cam.inv + 8, 0.0, 0.0, 0.0);
+  }
+  double dx = pix_x - r.ox, dy = pix_y - r.oy, dz = pix_z - r.oz;
+  const double mag = __builtin_sqrt((dx * dx + dy * dy) + dz * dz);  // Tuple.normalized, tuple.zig:109-116
+  if (mag != 0.0) {
+    dx = dx / mag;
+    dy = dy / mag;
+    dz = dz / mag;
+  }
+  r.dx = dx;
+  r.dy = dy;
+  r.dz = dz;
+  return r;
+}
+// (MS) a lane's sample word: the sample index, and whether the lane owns the pixel (deals its samples, step 1)
+#define RTC_SAMPLE_MASK 0xFFFFu
+#define RTC_SAMPLE_OWNER 0x10000u
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
@@ -2202,12 +2283,14 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned v) {
 // Exit: the counter runs past n_chunks (`drained`) and no lane holds a ray; every wave reaches it.
 // ------------------------------------------------------------------------------------------
 // (AREA: World.lights may hold area lights - DevAreaLights, the area kernels' extra argument; compiled into those kernels only)
-template <bool LDS, bool CSG, int WORLD = 0, int WAVES = 2, bool COOP = false, bool BOX = true, bool AREA = false>
+// (MS: several camera samples per pixel - DevSampling, the sampling kernels' extra argument; compiled into those kernels only)
+template <bool LDS, bool CSG, int WORLD = 0, int WAVES = 2, bool COOP = false, bool BOX = true, bool AREA = false, bool MS = false>
 __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& cam, const DevPixelMap& map,
                                             const uint32_t max_depth, double* __restrict__ out,
                                             DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
-                                            const DevAreaLights& area = DevAreaLights{}) {
+                                            const DevAreaLights& area = DevAreaLights{}, const DevSampling& smp = DevSampling{}) {
   static_assert(!AREA || !COOP, "the area kernels run no cooperative iterations");
+  static_assert(!MS || !COOP, "the sampling kernels run no cooperative iterations");
   RTC_PRIO_PHASE(RTC_PRIO_WORK);
 #ifndef RTC_PROFILE
   if (blockIdx.x == 0u) {  // the next launch's counters (see DevStats)
@@ -2379,6 +2462,14 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
   double* const acc = lds_acc[threadIdx.x >> 6][threadIdx.x & 63u];
   uint32_t* const trav_stack = FLAT ? nullptr : &lds_trav[threadIdx.x >> 6][0][(RTC_BVH8 ? 2u : 1u) * (threadIdx.x & 63u)];
   acc[0] = acc[1] = acc[2] = 0.0;
+  // (MS) the lane's sample word (RTC_SAMPLE_*): which camera sample of its pixel the lane's rays belong to.  A lane that
+  // took over part of another lane's ray tree (step 2a) adds its share and is done; only the owner starts the pixel's next
+  // sample.  In LDS, 4 bytes a lane: the area kernel's two work-groups per CU leave 1 872 B per work-group beside its tables.
+  uint32_t* samp_word = nullptr;
+  if constexpr (MS) {
+    __shared__ uint32_t lds_sample[4][64];
+    samp_word = &lds_sample[threadIdx.x >> 6][threadIdx.x & 63u];
+  }
   unsigned n_primary = 0, n_secondary = 0, n_shadow_calls = 0, n_shadow_traced = 0, overflow = 0, n_stolen = 0;
   Pending cur;
   cur.ray = {0, 0, 0, 0, 0, 0};
@@ -2430,6 +2521,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
   for (;;) {
     RTC_STAMP(0);
     RTC_PRIO_PHASE(RTC_PRIO_DEAL);
+    bool next_sample = false;  // (MS) the lane's pixel goes on with its next camera sample (its ray: step 2b)
     // ---- 1. a lane without a ray pops its stack; an empty stack means its share of the pixel is done.
     // Shares of one pixel may finish in several lanes (step 2a): those are ADDED to the pixel, which the
     // first hand-out zeroed; a pixel whose whole ray tree stayed in one lane (most of them) is stored once.
@@ -2439,7 +2531,16 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
         have_cur = true;
       } else {
         sp = base = 0;
-        if (has_pixel && RTC_IN_BOUNDS(RTC_OOB_CANVAS, out_index < out_extent)) {
+        if constexpr (MS) {  // the pixel is written once, after its last sample
+          if (has_pixel) {
+            const uint32_t w = *samp_word;
+            if ((w & RTC_SAMPLE_OWNER) != 0u && (w & RTC_SAMPLE_MASK) + 1u < smp.samples) {
+              *samp_word = w + 1u;
+              next_sample = true;
+            }
+          }
+        }
+        if (!next_sample && has_pixel && RTC_IN_BOUNDS(RTC_OOB_CANVAS, out_index < out_extent)) {
           double* __restrict__ o = out + 3 * out_index;  // Canvas pixel, canvas.zig:132-137
           const double acc_r = acc[0], acc_g = acc[1], acc_b = acc[2];
           if (!shared) {  // the whole ray tree ran in this lane: the pixel is written exactly once
@@ -2470,7 +2571,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
           has_pixel = false;
         }
 #ifdef RTC_PROFILE
-        else if (has_pixel) {  // (a pixel outside the output: counted above, not written)
+        else if (has_pixel && !next_sample) {  // (a pixel outside the output: counted above, not written)
           share_rays = 0u;
           has_pixel = false;
         }
@@ -2482,7 +2583,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
     // largest unexplored sub-tree) of a busy lane.  Without this a pixel whose ray tree has 2^(depth+1)-1
     // nodes occupies ONE lane for that many iterations.
     {
-      const bool idle = !have_cur;
+      const bool idle = !have_cur && !next_sample;
       const bool donor = have_cur && sp > base;
       const unsigned long long imask = __ballot(idle), dmask = __ballot(donor);
       if (imask != 0ull && dmask != 0ull) {
@@ -2491,7 +2592,8 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
         const uint32_t irank = bits_below(imask);
         const uint32_t drank = bits_below(dmask);
         if (donor && drank < pairs) {
-          mailbox[drank] = uint4{lane, static_cast<uint32_t>(base++), static_cast<uint32_t>(out_index), static_cast<uint32_t>(out_index >> 32)};
+          // (MS: the donor's sample index rides above the lane number)
+          mailbox[drank] = uint4{MS ? lane | (*samp_word & RTC_SAMPLE_MASK) << 8 : lane, static_cast<uint32_t>(base++), static_cast<uint32_t>(out_index), static_cast<uint32_t>(out_index >> 32)};
           if (!shared && RTC_IN_BOUNDS(RTC_OOB_CANVAS, out_index < out_extent)) {
             // First hand-out of this pixel: from here on its shares are ADDED, so it starts from zero.  The canvas is
             // not cleared per launch (a pixel nobody shares is stored once); the store is at L2 before the taker —
@@ -2511,7 +2613,8 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
         if (idle && irank < pairs) {
           // (the donor's slot is read here, in program order before any lane of the wave can push into it again)
           const uint4 m = mailbox[irank];
-          cur = load_level(static_cast<int>(m.y), m.x);
+          cur = load_level(static_cast<int>(m.y), MS ? m.x & 63u : m.x);
+          if constexpr (MS) *samp_word = m.x >> 8;  // (the sample's index; not the owner)
           out_index = static_cast<size_t>(m.z) | (static_cast<size_t>(m.w) << 32);
           have_cur = true;
           has_pixel = true;
@@ -2524,7 +2627,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
     }
     RTC_STAMP(9);
     // ---- 2b. deal new pixels to the lanes that still want one
-    bool want = !have_cur, got_pixel = false;
+    bool want = !have_cur && !next_sample, got_pixel = false;
     uint32_t new_px = 0u, new_py = 0u;
     unsigned long long wmask = __ballot(want);
     while (wmask) {
@@ -2628,7 +2731,25 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
       chunk_pos += min(avail, static_cast<uint32_t>(__builtin_popcountll(wmask)));
       wmask = __ballot(want);
     }
-    if (got_pixel) {  // once per refill, however many items the pixels came from
+    if constexpr (MS) {
+      if (got_pixel || next_sample) {  // a new pixel's sample 0, or the owner's next sample of its pixel
+        uint32_t k = 0u;
+        if (next_sample) {
+          k = *samp_word & RTC_SAMPLE_MASK;
+          map_pixel(map, out_index, new_px, new_py);
+        } else {
+          *samp_word = RTC_SAMPLE_OWNER;
+          shared = false;
+          acc[0] = acc[1] = acc[2] = 0.0;
+        }
+        cur.ray = camera_sample(cam, smp, new_px, new_py, k);
+        cur.weight = smp.weight;  // (the pixel is the samples' mean: each adds 1 / samples of its colour)
+        cur.remaining = max_depth;
+        have_cur = true;
+        has_pixel = true;
+        n_primary++;
+      }
+    } else if (got_pixel) {  // once per refill, however many items the pixels came from
       // Camera.rayForPixel, camera.zig:64-76
       const double xoffset = (static_cast<double>(new_px) + 0.5) * cam.pixel_size;
       const double yoffset = (static_cast<double>(new_py) + 0.5) * cam.pixel_size;
@@ -2958,6 +3079,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
                 py = ty * map.tile_h + ry;
               }
               pixel = static_cast<unsigned long long>(py) * cam.hsize + px;
+              if constexpr (MS) pixel = pixel * smp.samples + (*samp_word & RTC_SAMPLE_MASK);  // (u64, wraps)
             }
             // point_on_light(u, v) - over_point
             auto to_sample = [&](uint32_t u, uint32_t v, double& vx, double& vy, double& vz) {
@@ -3438,6 +3560,37 @@ rtc_render_kernel_area_bigworld(const DevScene S, const DevCamera cam, const Dev
                                 double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
                                 const DevAreaLights area) {
   render_body<false, true, 0, 2, false, true, true>(S, cam, map, max_depth, out, stats, next_stats, area);
+}
+
+// Several camera samples per pixel (rtc_scene_set_sampling: anti-aliasing, focal blur): the general walk with the csg and
+// texture-map paths compiled in, the sampling parameters as an extra argument (DevSampling) - every other kernel is
+// compiled without them.  Point lights (tables in LDS or in memory), and the area-light forms.
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_ms(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                     double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                     const DevSampling smp) {
+  render_body<true, true, 0, 2, false, true, false, true>(S, cam, map, max_depth, out, stats, next_stats, DevAreaLights{}, smp);
+}
+
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_ms_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                              double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                              const DevSampling smp) {
+  render_body<false, true, 0, 2, false, true, false, true>(S, cam, map, max_depth, out, stats, next_stats, DevAreaLights{}, smp);
+}
+
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_area_ms(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                          double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                          const DevAreaLights area, const DevSampling smp) {
+  render_body<true, true, 0, 2, false, true, true, true>(S, cam, map, max_depth, out, stats, next_stats, area, smp);
+}
+
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_area_ms_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                   double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                   const DevAreaLights area, const DevSampling smp) {
+  render_body<false, true, 0, 2, false, true, true, true>(S, cam, map, max_depth, out, stats, next_stats, area, smp);
 }
 
 // Rank 0's un-permute after the tile gather: one thread per canvas channel value, so both the read (a run

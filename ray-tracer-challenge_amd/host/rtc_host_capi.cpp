@@ -65,6 +65,13 @@ void rtch_scene_free(void* h) { delete static_cast<HostScene*>(h); }
 const rtc_scene_desc* rtch_scene_desc(void* h) { return &static_cast<HostScene*>(h)->desc; }
 const rtc_light_desc* rtch_scene_lights(void* h) { return &static_cast<HostScene*>(h)->lights; }
 
+int rtch_scene_sampling(void* h, rtc_sampling* out) {
+  return guarded([&] {
+    const rtc::CameraSampling& s = static_cast<HostScene*>(h)->info.sampling;
+    *out = rtc_sampling{s.grid, s.jitter ? 1u : 0u, s.aperture, s.focal_distance, s.seed};
+  });
+}
+
 // Camera of the scene file; width/height 0 keep the file's values, otherwise they replace
 // camera.width/height before Camera.new runs (the reference has no such override).
 int rtch_scene_camera(void* h, uint32_t width, uint32_t height, rtc_camera* out) {
@@ -130,7 +137,10 @@ int rtch_scene_render(void* h, uint32_t width, uint32_t height, uint32_t max_dep
     // (a scene with area lights: its light table; point lights only: the description alone, as before)
     int st = hs->flat.has_area_light ? rtc_scene_create_with_lights(&hs->desc, &hs->lights, &scene) : rtc_scene_create(&hs->desc, &scene);
     if (st == RTC_OK) {
-      st = rtc_render(scene, &cam, max_depth, 0, 0, cam.hsize, cam.vsize, rgb_out);
+      rtc_sampling smp;
+      if (rtch_scene_sampling(h, &smp) != 0) smp = rtc_sampling{1u, 0u, 0.0, 1.0, 0u};
+      st = rtc_scene_set_sampling(scene, &smp);
+      if (st == RTC_OK) st = rtc_render(scene, &cam, max_depth, 0, 0, cam.hsize, cam.vsize, rgb_out);
       rtc_scene_destroy(scene);
     }
     if (st != RTC_OK) throw rtc::Error(rtc_status_name(st), rtc_last_error());

@@ -594,7 +594,7 @@ SceneInfo parseScene(const std::string& scene_json, const FileLoader& load_file_
   }
 
   const Value& cam = requireObject(requireField(root, "camera", "scene"), "camera");
-  checkFields(cam, {"width", "height", "field-of-view", "from", "to", "up"}, "camera");
+  checkFields(cam, {"width", "height", "field-of-view", "from", "to", "up", "sampling"}, "camera");
   SceneInfo info;
   info.camera = Camera::create(asUsize(requireField(cam, "width", "camera"), "width"),
                                asUsize(requireField(cam, "height", "camera"), "height"),
@@ -610,6 +610,28 @@ SceneInfo parseScene(const std::string& scene_json, const FileLoader& load_file_
   info.camera.saved_to = to;
   info.camera.saved_up = up;
   info.camera.setTransform(Matrix4::viewTransform(from, to, up));
+  if (const Value* smp = cam.find("sampling")) {  // (not in the reference: anti-aliasing and focal blur, every key optional)
+    requireObject(*smp, "sampling");
+    checkFields(*smp, {"grid", "jitter", "aperture", "focal-distance", "seed"}, "sampling");
+    CameraSampling& s = info.sampling;
+    if (const Value* v = smp->find("grid")) {
+      const size_t g = asUsize(*v, "grid");
+      if (g < 1 || g > 16) throw Error("InvalidData", "sampling: grid is 1 to 16");
+      s.grid = static_cast<uint32_t>(g);
+    }
+    if (const Value* v = smp->find("jitter")) s.jitter = asBool(*v, "jitter");
+    if (const Value* v = smp->find("aperture")) s.aperture = asFloat(*v, "aperture");
+    if (!std::isfinite(s.aperture) || s.aperture < 0.0) throw Error("InvalidData", "sampling: aperture is finite and at least 0");
+    if (const Value* v = smp->find("focal-distance")) {
+      s.focal_distance = asFloat(*v, "focal-distance");
+      if (!std::isfinite(s.focal_distance) || s.focal_distance <= 0.0) throw Error("InvalidData", "sampling: focal-distance is finite and above 0");
+    } else if (s.aperture > 0.0) {  // focused on the point the camera looks at
+      const double dx = t[0] - f[0], dy = t[1] - f[1], dz = t[2] - f[2];
+      s.focal_distance = std::sqrt((dx * dx + dy * dy) + dz * dz);
+      if (!(s.focal_distance > 0.0)) throw Error("InvalidData", "sampling: from == to, and no focal-distance");
+    }
+    if (const Value* v = smp->find("seed")) s.seed = static_cast<uint64_t>(asUsize(*v, "seed"));
+  }
 
   const Value& objects = requireArray(requireField(root, "objects", "scene"), "objects");
   // `lights` has no default in SceneConfig (scene.zig:206): it is required.

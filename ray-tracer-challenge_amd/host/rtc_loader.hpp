@@ -17,9 +17,20 @@ namespace rtc {
 using FileLoader = std::function<std::string(const std::string& file_name)>;
 FileLoader directoryLoader(const std::string& dir);  // main.zig:14-21 ("data/" + name)
 
+// The camera's optional "sampling" (not in the reference): camera samples per pixel, as
+// rtc_scene_set_sampling takes them.  Absent: one centred ray per pixel.
+struct CameraSampling {
+  uint32_t grid = 1;
+  bool jitter = false;
+  double aperture = 0.0;
+  double focal_distance = 1.0;  // (absent with an aperture: |to - from|)
+  uint64_t seed = 0;
+};
+
 struct SceneInfo {  // scene.zig:608-610
   Camera camera;
   World world;
+  CameraSampling sampling;
 };
 
 // scene.zig:612-661.  Throws rtc::Error whose .name is the Zig error name

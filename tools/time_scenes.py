@@ -3,7 +3,7 @@
 
     python tools/time_scenes.py [--set configs|mesh|misc|all] [--scenes a,b,..] [--size WxH] [--depth N]
                                 [--handles 3] [--settle 50] [--frames 20] [--option name=value ...] [--check]
-                                [--lights scene | area=N | grid=N]
+                                [--lights scene | area=N | grid=N] [--sampling grid[,aperture,focal]]
 
   configs  the five BASELINE configs at their own sizes and depths (fresnel 300x300, cover / teapot 1080p, r&r 1080p
            depth 8, dragons 4K)                                                       [default]
@@ -15,7 +15,11 @@ that ran.  --check: also compares every 24th row with the CPU oracle (needs orac
 The library directory is the package's, or $RTC_LIB_DIR (tools/variants.py points it at a variant build).
 --lights: the scene's light table through rtc_scene_create_with_lights (`scene`), with every area light at N x N samples
 (`area=N`), or every area light replaced by N x N point lights at its cells' centres, intensity / N^2 (`grid=N`: the same
-shadow rays through the point-light kernels); prints shadow_traced per frame and ns per traced shadow ray as well."""
+shadow rays through the point-light kernels); prints shadow_traced per frame and ns per traced shadow ray as well.
+--sampling: grid x grid jittered camera samples per pixel (rtc_scene_set_sampling), through a lens of that aperture
+focused at that distance when they are given; prints primary rays per frame and ns per primary ray as well (--check is
+not made then: the oracle renders one centred sample).  Option sampling_kernels=1 times the sampling kernels with one
+sample."""
 import argparse, importlib, os, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, "tests"))
@@ -43,6 +47,7 @@ ap.add_argument("--option", action="append", default=[])
 ap.add_argument("--check", action="store_true")
 ap.add_argument("--label", default="")
 ap.add_argument("--lights", default="")
+ap.add_argument("--sampling", default="")
 args = ap.parse_args()
 cases = SETS[args.set]
 if args.scenes:
@@ -90,6 +95,9 @@ for name, w, h, depth in cases:
     table = light_table(hs, args.lights)
     for rep in range(args.handles):
         gpu = rtc.GpuScene(hs.desc, lights=table)
+        if args.sampling:
+            sv = [float(v) for v in args.sampling.split(",")]
+            gpu.set_sampling(int(sv[0]), True, sv[1] if len(sv) > 1 else 0.0, sv[2] if len(sv) > 2 else 1.0)
         for i in range(args.settle):
             gpu.render_device(cam, canvas.data_ptr(), depth, None, stream.cuda_stream)
         torch.cuda.synchronize()
@@ -101,7 +109,7 @@ for name, w, h, depth in cases:
         kernel = gpu.last_kernel_name()
         st = gpu.stats()
         if st["overflow"]: kernel += " OVERFLOW"
-        if args.check and rep == 0:
+        if args.check and rep == 0 and not args.sampling:
             import numpy as np, oracle_binding as ob
             step = max(1, h // 24)
             want, c = ob.OracleScene(hs.desc).render(cam, depth, row_step=step, threads=os.cpu_count() and 16)
@@ -112,5 +120,7 @@ for name, w, h, depth in cases:
     if delta is not None: line += f" maxdelta {delta:.2e}"
     if args.lights:
         line += f" shadow_traced {st['shadow_traced']} ns/shadow-ray {min(ts) * 1e6 / max(1, st['shadow_traced']):.3f}"
+    if args.sampling or args.option:
+        line += f" primary {st['primary']} ns/primary-ray {min(ts) * 1e6 / max(1, st['primary']):.3f}"
     out.append(line)
     print((args.label + " " if args.label else "") + line, flush=True)
