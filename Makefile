@@ -8,6 +8,7 @@
 #   oracle/build/liboracle.so, oracle_kat        test infrastructure only
 #   tests/build/libarea_oracle.so                test infrastructure only: the area-light checker (tests/cpp/area_oracle.cpp)
 #   tests/build/libcamera_oracle.so              test infrastructure only: the camera-sampling checker (tests/cpp/camera_oracle.cpp)
+#   tests/build/libprogressive_oracle.so         test infrastructure only: the sample-pass checker (tests/cpp/progressive_oracle.cpp)
 #
 # -ffp-contract=off everywhere: the reference's float mode is strict IEEE
 # (SURVEY F10); the GPU path and the oracle must round identically.
@@ -33,7 +34,7 @@ oracle:
 	$(MAKE) -C oracle
 
 # (the area-light checker includes the oracle's sources read-only; -pthread and -O3 as the oracle's own build)
-checker: tests/build/libarea_oracle.so tests/build/libcamera_oracle.so
+checker: tests/build/libarea_oracle.so tests/build/libcamera_oracle.so tests/build/libprogressive_oracle.so
 tests/build/libarea_oracle.so: tests/cpp/area_oracle.cpp oracle/oracle_capi.cpp oracle/rtc_oracle.hpp oracle/rtc_oracle_scene.hpp include/rtc.h
 	mkdir -p tests/build
 	$(CXX) -std=c++17 -O3 -ffp-contract=off -fPIC -Wall -Wextra -pthread -shared -o $@ tests/cpp/area_oracle.cpp
@@ -41,6 +42,10 @@ tests/build/libarea_oracle.so: tests/cpp/area_oracle.cpp oracle/oracle_capi.cpp 
 tests/build/libcamera_oracle.so: tests/cpp/camera_oracle.cpp tests/cpp/area_oracle.cpp oracle/oracle_capi.cpp oracle/rtc_oracle.hpp oracle/rtc_oracle_scene.hpp include/rtc.h
 	mkdir -p tests/build
 	$(CXX) -std=c++17 -O3 -ffp-contract=off -fPIC -Wall -Wextra -Wno-subobject-linkage -pthread -shared -o $@ tests/cpp/camera_oracle.cpp
+# (the sample-pass checker includes the camera-sampling checker, read-only)
+tests/build/libprogressive_oracle.so: tests/cpp/progressive_oracle.cpp tests/cpp/camera_oracle.cpp tests/cpp/area_oracle.cpp oracle/oracle_capi.cpp oracle/rtc_oracle.hpp oracle/rtc_oracle_scene.hpp include/rtc.h
+	mkdir -p tests/build
+	$(CXX) -std=c++17 -O3 -ffp-contract=off -fPIC -Wall -Wextra -Wno-subobject-linkage -pthread -shared -o $@ tests/cpp/progressive_oracle.cpp
 
 $(LIB):
 	mkdir -p $(LIB)
@@ -55,7 +60,11 @@ $(LIB)/rtc_kernels.o: $(PKG)/csrc/rtc_kernels.hip $(PKG)/csrc/rtc_device.h tools
 $(LIB)/rtc_capi.o: $(PKG)/csrc/rtc_capi.hip $(wildcard $(PKG)/csrc/*.h) include/rtc.h | $(LIB)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
-$(LIB)/librtc_hip.so: $(LIB)/rtc_kernels.o $(LIB)/rtc_capi.o
+# (progressive rendering's accumulation: a translation unit of its own, so that the render kernels' code objects stay)
+$(LIB)/rtc_accum.o: $(PKG)/csrc/rtc_accum.hip $(PKG)/csrc/rtc_device.h | $(LIB)
+	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
+
+$(LIB)/librtc_hip.so: $(LIB)/rtc_kernels.o $(LIB)/rtc_capi.o $(LIB)/rtc_accum.o
 	$(HIPCC) --offload-arch=gfx950 -shared -fPIC -o $@ $^
 
 $(LIB)/librtc_multi.so: $(PKG)/csrc/rtc_multi.hip include/rtc_multi.h include/rtc.h $(LIB)/librtc_hip.so

@@ -304,6 +304,47 @@ typedef struct rtc_sampling {
  * RTC_ERR_INVALID_ARGUMENT otherwise.  A clone starts with its source's setting; rtc_render's band clones follow.
  */
 int rtc_scene_set_sampling(rtc_scene *scene, const rtc_sampling *sampling);
+
+/* ---- progressive rendering: sample passes accumulated on the device ---- */
+/* (pass + 1) * grid * grid may not exceed this: the camera hash holds a 24-bit global sample index. */
+#define RTC_SAMPLING_INDEX_LIMIT 16777216u
+
+/*
+ * The sample pass this handle renders (default 0; a clone starts with its source's, rtc_render's band clones follow).
+ * With S = grid * grid and N = hsize * vsize, pass P renders sample k of pixel p with the camera hash keyed on the
+ * global sample index P * S + k (the sub-pixel stratum is still that of k) and an area light's jitter keyed on
+ * (P * N + p) * S + k (u64, wrapping).  Pass 0 is the image of every earlier release.  A pass other than 0 always runs
+ * the sampling kernels; under the default sampling (one centred ray, no lens) every pass renders the same image unless
+ * the scene has a jittered area light.  RTC_ERR_INVALID_ARGUMENT, with nothing changed, unless
+ * (pass + 1) * S <= RTC_SAMPLING_INDEX_LIMIT; rtc_scene_set_sampling refuses a grid that breaks it at the current pass.
+ */
+int rtc_scene_set_sample_pass(rtc_scene *scene, uint32_t pass);
+
+/*
+ * One pass into running sums on the device: sum += frame (passes == 1: sum = frame, nothing is read), sumsq += r^2 + g^2 + b^2,
+ * and from the new sums, optionally, mean = sum / passes, rgba = the clamp of mean (the bits of rtc_rgba8_device(mean))
+ * and noise = sqrt((1/n) * sum over pixels of max(0, sumsq - passes * |mean|^2) / (3 * (passes - 1) * passes)), the
+ * RMS standard error of the running mean.  Plain adds and one correctly rounded divide: after P passes `sum` is the
+ * in-order sum of the P frames to the bit; the noise is reduced in a fixed order (the same inputs give the same bits).
+ * n_pixels is only a length: a rank accumulates its own tiles the same way.
+ */
+typedef struct rtc_accum {
+  const double *frame;  /* [n][3], required: the pass just rendered                         */
+  size_t n_pixels;      /* n >= 1                                                           */
+  uint32_t passes;      /* passes in the sums after this call, >= 1 (1: overwrite)          */
+  double *sum;          /* [n][3], required                                                 */
+  double *sumsq;        /* [n] or NULL                                                      */
+  double *mean;         /* [n][3] or NULL                                                   */
+  uint32_t *rgba;       /* [n] or NULL                                                      */
+  double *noise;        /* one device double or NULL; needs sumsq and passes >= 2           */
+} rtc_accum;
+
+/*
+ * Enqueues the accumulation on `hip_stream` (NULL: the handle's own stream), ordered after the handle's renders on any
+ * stream; every pointer is device memory on the handle's device.  Arguments are checked before the device is touched:
+ * RTC_ERR_INVALID_ARGUMENT otherwise.
+ */
+int rtc_scene_accumulate_device(rtc_scene *scene, const rtc_accum *accum, void *hip_stream);
 void rtc_scene_destroy(rtc_scene *scene);
 
 /*

@@ -15,7 +15,8 @@
  *   rtch_canvas_rgba8    the RGBA8 framebuffer of lib.zig:146-153 (clamp, color.zig:61-71)
  *   rtch_scene_render    main.zig:92: load -> Camera.render -> Canvas, through rtc_scene_create / rtc_render
  *                        (rtc_scene_create_with_lights when the scene has an area light; the camera's
- *                        sampling, rtch_scene_sampling, through rtc_scene_set_sampling)
+ *                        sampling, rtch_scene_sampling, through rtc_scene_set_sampling; its sample passes,
+ *                        rtch_scene_passes, through rtc_scene_set_sample_pass, averaged on the host)
  *
  * Every function that returns int returns 0 on success; otherwise rtch_last_error()
  * holds "<ZigStyleErrorName>: detail" (thread-local).
@@ -49,6 +50,10 @@ const rtc_light_desc *rtch_scene_lights(void *handle);
 /* The camera's "sampling" of the scene file (anti-aliasing, focal blur), or the defaults - grid 1, no jitter,
  * aperture 0 - when it has none; pass it to rtc_scene_set_sampling.  Camera rotate / move leave it alone. */
 int rtch_scene_sampling(void *handle, rtc_sampling *out);
+/* The camera's "sampling": {"passes": n} of the scene file (1 when absent): rtch_scene_render renders sample passes
+ * 0 .. n-1 (rtc_scene_set_sample_pass), sums them in pass order and divides by n once - the bits of
+ * rtc_scene_accumulate_device's mean after n passes. */
+int rtch_scene_passes(void *handle, uint32_t *out);
 int rtch_scene_camera(void *handle, uint32_t width, uint32_t height, rtc_camera *out);
 int rtch_camera_rotate(void *handle, double angle);
 int rtch_camera_move(void *handle, double distance);

@@ -151,18 +151,30 @@ class Sampling(C.Structure):
                 "focal_distance": self.focal_distance, "seed": self.seed}
 
 
+class Accum(C.Structure):
+    """struct rtc_accum (include/rtc.h): one pass into running sums on the device (rtc_scene_accumulate_device); device
+    pointers as integers, 0 for an optional output that is not wanted."""
+
+    _fields_ = [("frame", C.c_void_p), ("n_pixels", C.c_size_t), ("passes", C.c_uint32), ("sum", C.c_void_p),
+                ("sumsq", C.c_void_p), ("mean", C.c_void_p), ("rgba", C.c_void_p), ("noise", C.c_void_p)]
+
+
+RTC_SAMPLING_INDEX_LIMIT = 1 << 24   # (pass + 1) * grid * grid may not exceed it (include/rtc.h)
+
+
 # (include/rtc.h: what a host binds ...)
 RTC_SYMBOLS = ["rtc_scene_create", "rtc_scene_clone", "rtc_scene_destroy", "rtc_render", "rtc_render_rgba8", "rtc_render_device",
                "rtc_render_tiles_device", "rtc_assemble_tiles_device", "rtc_render_tile_list_device", "rtc_get_tile_costs",
                "rtc_assign_tiles", "rtc_assemble_tile_list_device", "rtc_assemble_tile_list_rgba8_device", "rtc_scatter_tile_list_device",
                "rtc_scatter_tile_list_rgba8_device", "rtc_scene_synchronize", "rtc_get_stats", "rtc_last_error", "rtc_status_name",
                "rtc_grow_csg_lists", "rtc_canvas_register", "rtc_canvas_unregister", "rtc_rgba8_device",
-               "rtc_scene_create_with_lights", "rtc_scene_set_light_seed", "rtc_scene_set_sampling"]
+               "rtc_scene_create_with_lights", "rtc_scene_set_light_seed", "rtc_scene_set_sampling",
+               "rtc_scene_set_sample_pass", "rtc_scene_accumulate_device"]
 # (... and include/rtc_diag.h: diagnostics and tuning, for the tests, bench.py and tools/)
 RTC_DIAG_SYMBOLS = ["rtc_set_option", "rtc_last_kernel_name", "rtc_get_schedule", "rtc_get_chunk_times", "rtc_diag_build_tables", "rtc_diag_root_boxes"]
 HOST_SYMBOLS = ["rtch_last_error", "rtch_scene_load", "rtch_scene_free", "rtch_scene_desc", "rtch_scene_camera",
                 "rtch_camera_rotate", "rtch_camera_move", "rtch_camera_make", "rtch_canvas_ppm", "rtch_canvas_rgba8", "rtch_scene_render", "rtch_set_loader_threads",
-                "rtch_scene_lights", "rtch_scene_sampling"]
+                "rtch_scene_lights", "rtch_scene_sampling", "rtch_scene_passes"]
 
 MULTI_SYMBOLS = ["rtc_multi_create", "rtc_multi_destroy", "rtc_multi_render", "rtc_multi_render_rgba8", "rtc_multi_render_device", "rtc_multi_render_rgba8_device",
                  "rtc_multi_synchronize", "rtc_multi_stream", "rtc_multi_get_stats", "rtc_multi_balance", "rtc_multi_last_error"]
@@ -213,6 +225,8 @@ def hip_lib():
         lib.rtc_scene_create_with_lights.argtypes = [C.POINTER(SceneDesc), C.POINTER(LightDesc), C.POINTER(C.c_void_p)]
         lib.rtc_scene_set_light_seed.argtypes = [C.c_void_p, C.c_uint64]
         lib.rtc_scene_set_sampling.argtypes = [C.c_void_p, C.POINTER(Sampling)]
+        lib.rtc_scene_set_sample_pass.argtypes = [C.c_void_p, C.c_uint32]
+        lib.rtc_scene_accumulate_device.argtypes = [C.c_void_p, C.POINTER(Accum), C.c_void_p]
         lib.rtc_scene_destroy.argtypes = [C.c_void_p]
         lib.rtc_scene_destroy.restype = None
         lib.rtc_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32] + [C.c_uint32] * 4 + [C.c_void_p]
@@ -262,6 +276,7 @@ def host_lib():
         lib.rtch_scene_lights.argtypes = [C.c_void_p]
         lib.rtch_scene_lights.restype = C.POINTER(LightDesc)
         lib.rtch_scene_sampling.argtypes = [C.c_void_p, C.POINTER(Sampling)]
+        lib.rtch_scene_passes.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         lib.rtch_scene_camera.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Camera)]
         lib.rtch_camera_rotate.argtypes = [C.c_void_p, C.c_double]
         lib.rtch_camera_move.argtypes = [C.c_void_p, C.c_double]
@@ -413,6 +428,12 @@ class HostScene:
         _check_host(host_lib().rtch_scene_sampling(self._h, C.byref(s)))
         return s
 
+    def passes(self):
+        """The camera's "sampling": {"passes": n} of the scene file (rtch_scene_passes; 1 when absent)."""
+        n = C.c_uint32()
+        _check_host(host_lib().rtch_scene_passes(self._h, C.byref(n)))
+        return n.value
+
     def rotate_camera(self, angle):
         """Renderer.rotateCamera (lib.zig:166-178): orbit the camera around its target, about `up`."""
         _check_host(host_lib().rtch_camera_rotate(self._h, C.c_double(angle)))
@@ -476,6 +497,14 @@ class GpuScene:
             return
         s = grid if isinstance(grid, Sampling) else Sampling(grid, 1 if jitter else 0, aperture, focal_distance, seed)
         _check_hip(hip_lib().rtc_scene_set_sampling(self._s, C.byref(s)))
+
+    def set_sample_pass(self, p):
+        """rtc_scene_set_sample_pass: the sample pass every later render of this handle draws (0: the default)."""
+        _check_hip(hip_lib().rtc_scene_set_sample_pass(self._s, p))
+
+    def accumulate_device(self, accum, stream=None):
+        """rtc_scene_accumulate_device: an Accum, enqueued on `stream` (None: the handle's own) after this handle's renders."""
+        _check_hip(hip_lib().rtc_scene_accumulate_device(self._s, C.byref(accum), stream))
 
     def clone(self):
         """rtc_scene_clone: a handle of its own (stream, schedule, counters) on the same device copy of the scene - one
@@ -567,6 +596,56 @@ class GpuScene:
             self.close()
         except Exception:
             pass
+
+
+class Progressive:
+    """Progressive rendering on the device: each step() renders the next sample pass of `gpu_scene` (rtc_scene_set_sample_pass)
+    into a frame buffer and accumulates it (rtc_scene_accumulate_device) into running sums, the mean and its RGBA8 clamp,
+    all torch tensors on the scene's device, on a torch stream of its own (`stream`).  The host decides when to stop, from
+    what step() returns; mean() and rgba8() order the caller's current stream after the last step."""
+
+    def __init__(self, gpu_scene, cam, max_depth=REFERENCE_DEPTH, noise=True):
+        import torch
+        self.gpu, self.cam, self.max_depth, self.noise_on = gpu_scene, cam, max_depth, noise
+        shape, dev = (cam.vsize, cam.hsize), "cuda"
+        self.frame = torch.empty(shape + (3,), dtype=torch.float64, device=dev)
+        self.sum = torch.empty(shape + (3,), dtype=torch.float64, device=dev)
+        self.sumsq = torch.empty(shape, dtype=torch.float64, device=dev) if noise else None
+        self._mean = torch.empty(shape + (3,), dtype=torch.float64, device=dev)
+        self._rgba = torch.empty(shape, dtype=torch.int32, device=dev)
+        self._noise = torch.empty(1, dtype=torch.float64, device=dev) if noise else None
+        self.stream = torch.cuda.Stream()   # (a stream of its own: the legacy default stream is no stream to the library)
+        self.passes = 0
+
+    def step(self):
+        """Renders and accumulates pass `passes`; returns the noise estimate after it (a float; None after the first pass
+        or without noise)."""
+        stream = self.stream.cuda_stream
+        self.gpu.set_sample_pass(self.passes)
+        self.gpu.render_device(self.cam, self.frame.data_ptr(), self.max_depth, stream=stream)
+        n = self.passes + 1
+        want_noise = self.noise_on and n >= 2
+        a = Accum(self.frame.data_ptr(), self.cam.hsize * self.cam.vsize, n, self.sum.data_ptr(),
+                  self.sumsq.data_ptr() if self.sumsq is not None else None, self._mean.data_ptr(), self._rgba.data_ptr(),
+                  self._noise.data_ptr() if want_noise else None)
+        self.gpu.accumulate_device(a, stream)
+        self.passes = n
+        if not want_noise:
+            return None
+        self.stream.synchronize()
+        return float(self._noise.item())
+
+    def mean(self):
+        """[h][w][3] f64 on the device: the mean of the passes so far."""
+        import torch
+        torch.cuda.current_stream().wait_stream(self.stream)
+        return self._mean
+
+    def rgba8(self):
+        """[h][w][4] u8 on the device: the clamp of mean(), the bits of rgba8_device(mean())."""
+        import torch
+        torch.cuda.current_stream().wait_stream(self.stream)
+        return self._rgba.view(self.cam.vsize, self.cam.hsize, 1).view(torch.uint8)
 
 
 def canvas_register(array):

@@ -89,6 +89,11 @@ __global__ void rtc_render_kernel_area_ms_bigworld(const DevScene S, const DevCa
                                                    double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
                                                    const DevAreaLights area, const DevSampling smp);
 }
+// Progressive rendering's accumulation (rtc_accum.hip): the grid's blocks for n pixels (the noise partials it writes, at
+// most) and the enqueue of its kernels.
+uint32_t rtcAccumBlocks(size_t n_pixels, bool wide);
+hipError_t rtcAccumLaunch(const double* frame, size_t n_pixels, uint32_t passes, double* sum, double* sumsq, double* mean,
+                          uint32_t* rgba, double* noise, double* partials, hipStream_t stream);
 extern "C" __global__ void rtc_estimate_kernel(const DevScene S, const DevCamera cam, const DevPixelMap map,
                                                uint32_t* __restrict__ chunk_cost, uint32_t* __restrict__ chunk_time,
                                                DevChunkShape* __restrict__ chunk_shape, DevPackState* __restrict__ state
@@ -303,20 +308,21 @@ struct KernelChoice {
   KernelChoice(decltype(&rtc_render_kernel_area_ms) am, const char* n) : fn(nullptr), name(n), area_ms(am) {}
   void launch(uint32_t blocks, hipStream_t stream, const rtc_scene* s, const DevScene& dev, const DevCamera& cam, const DevPixelMap& map,
               uint32_t max_depth, double* d_out, DevStats* st_now, DevStats* st_next) const {
+    DevSampling smp = s->sampling;  // (the pass's area-light offset, P * N * S: N is the camera's whole image)
+    smp.pixel_base = static_cast<unsigned long long>(smp.sample_base) * (static_cast<unsigned long long>(cam.hsize) * cam.vsize);
     if (area_ms)
-      hipLaunchKernelGGL(area_ms, dim3(blocks), dim3(256), 0, stream, dev, cam, map, max_depth, d_out, st_now, st_next, s->area,
-                         s->sampling);
+      hipLaunchKernelGGL(area_ms, dim3(blocks), dim3(256), 0, stream, dev, cam, map, max_depth, d_out, st_now, st_next, s->area, smp);
     else if (ms)
-      hipLaunchKernelGGL(ms, dim3(blocks), dim3(256), 0, stream, dev, cam, map, max_depth, d_out, st_now, st_next, s->sampling);
+      hipLaunchKernelGGL(ms, dim3(blocks), dim3(256), 0, stream, dev, cam, map, max_depth, d_out, st_now, st_next, smp);
     else if (area)
       hipLaunchKernelGGL(area, dim3(blocks), dim3(256), 0, stream, dev, cam, map, max_depth, d_out, st_now, st_next, s->area);
     else
       hipLaunchKernelGGL(fn, dim3(blocks), dim3(256), 0, stream, dev, cam, map, max_depth, d_out, st_now, st_next);
   }
 };
-// The sampling kernels run when the handle's sampling is not the default (one centred ray per pixel, no lens) - or,
-// for tests, whenever option "sampling_kernels" is set.  Otherwise the kernels run exactly as before.
-bool samplingKernels(const rtc_scene* s) { return s->sampling_on || rtcOptions().sampling_kernels != 0.0; }
+// The sampling kernels run when the handle's sampling is not the default (one centred ray per pixel, no lens), or its
+// sample pass is not 0 - or, for tests, whenever option "sampling_kernels" is set.  Otherwise the kernels run exactly as before.
+bool samplingKernels(const rtc_scene* s) { return s->sampling_on || s->sample_pass != 0u || rtcOptions().sampling_kernels != 0.0; }
 #define RTC_KERNEL(k) KernelChoice{k, #k}
 // The general kernel at three waves per SIMD (rtc_render_kernel3): forced by option "waves3", else what the handle's
 // trial measured (KernelTune in launch()).
@@ -2313,7 +2319,11 @@ static void applySampling(rtc_scene* s, const rtc_sampling& v) {
   d.jitter = v.jitter;
   d.aperture = v.aperture;
   d.focal = v.aperture > 0.0 ? v.focal_distance : 1.0;
+  d.sample_base = s->sample_pass * d.samples;  // (< RTC_SAMPLING_INDEX_LIMIT: both setters check)
 }
+
+// (pass + 1) * samples within the camera hash's 24-bit sample index
+static bool passFits(uint64_t pass, uint64_t samples) { return (pass + 1u) * samples <= RTC_SAMPLING_INDEX_LIMIT; }
 
 int rtc_scene_set_sampling(rtc_scene* s, const rtc_sampling* sampling) {
   g_error.clear();
@@ -2327,8 +2337,57 @@ int rtc_scene_set_sampling(rtc_scene* s, const rtc_sampling* sampling) {
     if (v.aperture > 0.0 && !(std::isfinite(v.focal_distance) && v.focal_distance > 0.0))
       return fail(RTC_ERR_INVALID_ARGUMENT, "sampling: focal distance %g with an aperture", v.focal_distance);
   }
+  if (!passFits(s->sample_pass, static_cast<uint64_t>(v.grid) * v.grid))
+    return fail(RTC_ERR_INVALID_ARGUMENT, "sampling: grid %u at sample pass %u exceeds %u sample indices", v.grid, s->sample_pass,
+                RTC_SAMPLING_INDEX_LIMIT);
   applySampling(s, v);
   for (rtc_scene* b : s->band) applySampling(b, v);  // (the band clones rtc_render renders a large frame with)
+  return RTC_OK;
+}
+
+int rtc_scene_set_sample_pass(rtc_scene* s, uint32_t pass) {
+  g_error.clear();
+  if (!s) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
+  const uint64_t samples = static_cast<uint64_t>(s->sampling.samples);
+  if (!passFits(pass, samples))
+    return fail(RTC_ERR_INVALID_ARGUMENT, "sample pass %u of %llu samples exceeds %u sample indices", pass, (unsigned long long)samples,
+                RTC_SAMPLING_INDEX_LIMIT);
+  s->sample_pass = pass;
+  applySampling(s, s->sampling_desc);
+  for (rtc_scene* b : s->band) {  // (the band clones rtc_render renders a large frame with)
+    b->sample_pass = pass;
+    applySampling(b, b->sampling_desc);
+  }
+  return RTC_OK;
+}
+
+int rtc_scene_accumulate_device(rtc_scene* s, const rtc_accum* a, void* hip_stream) {
+  g_error.clear();
+  if (!s || !a || !a->frame || !a->sum) return fail(RTC_ERR_INVALID_ARGUMENT, "accumulate: null argument");
+  if (a->n_pixels == 0 || a->n_pixels > (static_cast<size_t>(1) << 40))
+    return fail(RTC_ERR_INVALID_ARGUMENT, "accumulate: %zu pixels", a->n_pixels);
+  if (a->passes == 0u) return fail(RTC_ERR_INVALID_ARGUMENT, "accumulate: passes 0 (1 or more)");
+  if (a->noise && (!a->sumsq || a->passes < 2u))
+    return fail(RTC_ERR_INVALID_ARGUMENT, "accumulate: noise needs sumsq and passes >= 2 (passes %u)", a->passes);
+  HIP_TRY(hipSetDevice(s->device));
+  if (!hip_stream) HIP_TRY(ensureOwnStream(s));
+  hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : s->stream;
+  if (a->noise) {  // the per-block partials: the handle's scratch, grown when a larger image needs more
+    const size_t need = rtcAccumBlocks(a->n_pixels, false);
+    if (need > s->accum_partials_capacity) {
+      HIP_TRY(handleIdle(s));  // (an earlier call may still be using the old scratch)
+      if (s->d_accum_partials) (void)hipFree(s->d_accum_partials);
+      s->d_accum_partials = nullptr;
+      s->accum_partials_capacity = 0;
+      HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s->d_accum_partials), need * sizeof(double)));
+      s->accum_partials_capacity = need;
+    }
+  }
+  // ordered after the handle's renders as a launch is (launch()), and the next launch after this
+  if (s->last_stream != nullptr && stream != s->last_stream) HIP_TRY(hipStreamWaitEvent(stream, s->launch_done, 0));
+  HIP_TRY(rtcAccumLaunch(a->frame, a->n_pixels, a->passes, a->sum, a->sumsq, a->mean, a->rgba, a->noise, s->d_accum_partials, stream));
+  HIP_TRY(hipEventRecord(s->launch_done, stream));
+  s->last_stream = stream;
   return RTC_OK;
 }
 
@@ -2354,6 +2413,7 @@ int rtc_scene_clone(const rtc_scene* src, rtc_scene** out) {
   s->ext_kernel = src->ext_kernel;
   s->area_kernel = src->area_kernel;
   s->area = src->area;  // (the rows the scene's device copy holds, and the source's seed)
+  s->sample_pass = src->sample_pass;
   applySampling(s, src->sampling_desc);
   s->blocks_per_cu_ms_lds = src->blocks_per_cu_ms_lds;
   s->blocks_per_cu_ms_big = src->blocks_per_cu_ms_big;
@@ -2415,6 +2475,7 @@ void rtc_scene_destroy(rtc_scene* s) {
   if (s->launch_done) (void)hipEventDestroy(s->launch_done);
   if (s->d_ray_stack) (void)hipFree(s->d_ray_stack);
   if (s->d_csg_buf) (void)hipFree(s->d_csg_buf);
+  if (s->d_accum_partials) (void)hipFree(s->d_accum_partials);
   if (s->tab && !s->is_band) s->tab->handles.fetch_sub(1, std::memory_order_relaxed);
   delete s;
 }

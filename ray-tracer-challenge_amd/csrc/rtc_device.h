@@ -293,6 +293,10 @@ struct DevSampling {
   double weight;           // 1 / samples: each sample's primary ray carries it
   double aperture, focal;  // lens radius (0: a pinhole) and focal distance, in camera units
   uint32_t grid, samples, jitter;
+  // (rtc_scene_set_sample_pass) pass P: P * samples, added to the camera hash's sample index, and
+  // P * pixels * samples (u64, wrapping), added to an area light's key; 0 for pass 0.  Sample indices stay local (< samples).
+  uint32_t sample_base;
+  unsigned long long pixel_base;
 };
 
 // j(axis) of sample k of the whole-image pixel p (axis 0 / 1: the sub-pixel offset, 2 and up: the lens): a pure function,

@@ -147,6 +147,9 @@ struct rtc_scene {
   rtc_sampling sampling_desc{1u, 0u, 0.0, 1.0, 0ull};  // rtc_scene_set_sampling (a clone starts with its source's)
   DevSampling sampling{0ull, 1.0, 0.0, 1.0, 1u, 1u, 0u};  // ... as the sampling kernels' argument
   bool sampling_on = false;        // not the default: the sampling kernels
+  uint32_t sample_pass = 0;        // rtc_scene_set_sample_pass (a clone starts with its source's); not 0: the sampling kernels
+  double* d_accum_partials = nullptr;  // rtc_scene_accumulate_device's per-block noise partials, and the total behind them
+  size_t accum_partials_capacity = 0;  // doubles
   uint32_t blocks_per_cu_ms_lds = 1, blocks_per_cu_ms_big = 1;  // resident work-groups of the world's sampling kernels
   bool simple3_ok = false;         // a simple world whose tables fit the three-waves-per-SIMD kernel's LDS (RTC_LDS3_*)
   void* d_csg_buf = nullptr;       // DevPixelMap::csg_buf, only for scenes with csg nodes

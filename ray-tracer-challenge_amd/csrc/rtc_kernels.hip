@@ -2215,10 +2215,11 @@ __device__ __forceinline__ void map_pixel(const DevPixelMap& map, size_t out_ind
 __device__ __forceinline__ Ray camera_sample(const DevCamera& cam, const DevSampling& smp, uint32_t px, uint32_t py, uint32_t k) {
   const uint32_t j = k / smp.grid, i = k - j * smp.grid;
   const unsigned long long p = static_cast<unsigned long long>(py) * cam.hsize + px;
+  const uint32_t g = smp.sample_base + k;  // the global sample index of the pass (section 13): the hash's, not the stratum's
   double jx = 0.5, jy = 0.5;
   if (smp.jitter) {
-    jx = rtc_camera_jitter(smp.key, p, k, 0u);
-    jy = rtc_camera_jitter(smp.key, p, k, 1u);
+    jx = rtc_camera_jitter(smp.key, p, g, 0u);
+    jy = rtc_camera_jitter(smp.key, p, g, 1u);
   }
   const double n = static_cast<double>(smp.grid);
   const double ox = (static_cast<double>(i) + jx) / n, oy = (static_cast<double>(j) + jy) / n;
@@ -2231,8 +2232,8 @@ __device__ __forceinline__ Ray camera_sample(const DevCamera& cam, const DevSamp
   if (smp.aperture > 0.0) {
     double lx = 0.0, ly = 0.0;
     for (uint32_t t = 0u; t < 32u; ++t) {
-      const double a = 2.0 * rtc_camera_jitter(smp.key, p, k, 2u + 2u * t) - 1.0;
-      const double b = 2.0 * rtc_camera_jitter(smp.key, p, k, 3u + 2u * t) - 1.0;
+      const double a = 2.0 * rtc_camera_jitter(smp.key, p, g, 2u + 2u * t) - 1.0;
+      const double b = 2.0 * rtc_camera_jitter(smp.key, p, g, 3u + 2u * t) - 1.0;
       if ((a * a) + (b * b) <= 1.0) {
         lx = a;
         ly = b;
@@ -3079,7 +3080,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
                 py = ty * map.tile_h + ry;
               }
               pixel = static_cast<unsigned long long>(py) * cam.hsize + px;
-              if constexpr (MS) pixel = pixel * smp.samples + (*samp_word & RTC_SAMPLE_MASK);  // (u64, wraps)
+              if constexpr (MS) pixel = pixel * smp.samples + (*samp_word & RTC_SAMPLE_MASK) + smp.pixel_base;  // (u64, wraps)
             }
             // point_on_light(u, v) - over_point
             auto to_sample = [&](uint32_t u, uint32_t v, double& vx, double& vy, double& vz) {

@@ -5,6 +5,7 @@
 #include <cstring>
 #include <memory>
 #include <string>
+#include <vector>
 
 #include "../../include/rtc_host.h"
 #include "rtc_api.hpp"
@@ -72,6 +73,10 @@ int rtch_scene_sampling(void* h, rtc_sampling* out) {
   });
 }
 
+int rtch_scene_passes(void* h, uint32_t* out) {
+  return guarded([&] { *out = static_cast<HostScene*>(h)->info.sampling.passes; });
+}
+
 // Camera of the scene file; width/height 0 keep the file's values, otherwise they replace
 // camera.width/height before Camera.new runs (the reference has no such override).
 int rtch_scene_camera(void* h, uint32_t width, uint32_t height, rtc_camera* out) {
@@ -133,6 +138,11 @@ int rtch_scene_render(void* h, uint32_t width, uint32_t height, uint32_t max_dep
     rtc::Camera c = rtc::Camera::create(width ? width : c0.hsize, height ? height : c0.vsize, c0.fov);
     c.setTransform(c0.transform);
     cam = rtc::flattenCamera(c);
+    // (several sample passes: each rendered into `frame`, summed in pass order into rgb_out, divided once by their
+    // number - the bits of rtc_scene_accumulate_device's mean)
+    const uint32_t passes = hs->info.sampling.passes;
+    const size_t n = 3ull * cam.hsize * cam.vsize;
+    std::vector<double> frame(passes > 1u ? n : 0u);
     rtc_scene* scene = nullptr;
     // (a scene with area lights: its light table; point lights only: the description alone, as before)
     int st = hs->flat.has_area_light ? rtc_scene_create_with_lights(&hs->desc, &hs->lights, &scene) : rtc_scene_create(&hs->desc, &scene);
@@ -140,7 +150,14 @@ int rtch_scene_render(void* h, uint32_t width, uint32_t height, uint32_t max_dep
       rtc_sampling smp;
       if (rtch_scene_sampling(h, &smp) != 0) smp = rtc_sampling{1u, 0u, 0.0, 1.0, 0u};
       st = rtc_scene_set_sampling(scene, &smp);
-      if (st == RTC_OK) st = rtc_render(scene, &cam, max_depth, 0, 0, cam.hsize, cam.vsize, rgb_out);
+      for (uint32_t p = 0; p < passes && st == RTC_OK; ++p) {
+        if (p > 0u) st = rtc_scene_set_sample_pass(scene, p);
+        if (st == RTC_OK) st = rtc_render(scene, &cam, max_depth, 0, 0, cam.hsize, cam.vsize, p == 0u ? rgb_out : frame.data());
+        if (st == RTC_OK && p > 0u)
+          for (size_t i = 0; i < n; ++i) rgb_out[i] = rgb_out[i] + frame[i];
+      }
+      if (st == RTC_OK && passes > 1u)
+        for (size_t i = 0; i < n; ++i) rgb_out[i] = rgb_out[i] / static_cast<double>(passes);
       rtc_scene_destroy(scene);
     }
     if (st != RTC_OK) throw rtc::Error(rtc_status_name(st), rtc_last_error());

@@ -612,7 +612,7 @@ SceneInfo parseScene(const std::string& scene_json, const FileLoader& load_file_
   info.camera.setTransform(Matrix4::viewTransform(from, to, up));
   if (const Value* smp = cam.find("sampling")) {  // (not in the reference: anti-aliasing and focal blur, every key optional)
     requireObject(*smp, "sampling");
-    checkFields(*smp, {"grid", "jitter", "aperture", "focal-distance", "seed"}, "sampling");
+    checkFields(*smp, {"grid", "jitter", "aperture", "focal-distance", "seed", "passes"}, "sampling");
     CameraSampling& s = info.sampling;
     if (const Value* v = smp->find("grid")) {
       const size_t g = asUsize(*v, "grid");
@@ -631,6 +631,12 @@ SceneInfo parseScene(const std::string& scene_json, const FileLoader& load_file_
       if (!(s.focal_distance > 0.0)) throw Error("InvalidData", "sampling: from == to, and no focal-distance");
     }
     if (const Value* v = smp->find("seed")) s.seed = static_cast<uint64_t>(asUsize(*v, "seed"));
+    if (const Value* v = smp->find("passes")) {  // (progressive rendering, DESIGN.md section 13: sample passes 0 .. passes-1)
+      const size_t n = asUsize(*v, "passes");
+      const size_t most = RTC_SAMPLING_INDEX_LIMIT / (static_cast<size_t>(s.grid) * s.grid);
+      if (n < 1 || n > most) throw Error("InvalidData", "sampling: passes is 1 to " + std::to_string(most) + " at grid " + std::to_string(s.grid));
+      s.passes = static_cast<uint32_t>(n);
+    }
   }
 
   const Value& objects = requireArray(requireField(root, "objects", "scene"), "objects");

@@ -25,6 +25,7 @@ struct CameraSampling {
   double aperture = 0.0;
   double focal_distance = 1.0;  // (absent with an aperture: |to - from|)
   uint64_t seed = 0;
+  uint32_t passes = 1;  // sample passes rtch_scene_render averages (rtc_scene_set_sample_pass 0 .. passes-1; section 13)
 };
 
 struct SceneInfo {  // scene.zig:608-610

@@ -3,7 +3,7 @@
 
     python tools/time_scenes.py [--set configs|mesh|misc|all] [--scenes a,b,..] [--size WxH] [--depth N]
                                 [--handles 3] [--settle 50] [--frames 20] [--option name=value ...] [--check]
-                                [--lights scene | area=N | grid=N] [--sampling grid[,aperture,focal]]
+                                [--lights scene | area=N | grid=N] [--sampling grid[,aperture,focal]] [--passes P]
 
   configs  the five BASELINE configs at their own sizes and depths (fresnel 300x300, cover / teapot 1080p, r&r 1080p
            depth 8, dragons 4K)                                                       [default]
@@ -19,7 +19,11 @@ shadow rays through the point-light kernels); prints shadow_traced per frame and
 --sampling: grid x grid jittered camera samples per pixel (rtc_scene_set_sampling), through a lens of that aperture
 focused at that distance when they are given; prints primary rays per frame and ns per primary ray as well (--check is
 not made then: the oracle renders one centred sample).  Option sampling_kernels=1 times the sampling kernels with one
-sample."""
+sample.
+--passes P: the frames are sample pass P (rtc_scene_set_sample_pass; progressive rendering), and
+rtc_scene_accumulate_device of that pass (sums, sumsq, mean, rgba and noise) is timed on its own over as many calls, beside
+a device-to-device copy that moves as many bytes (it reads and writes half of them each); then a Progressive of 64 passes
+prints its noise after 4, 16 and 64."""
 import argparse, importlib, os, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, "tests"))
@@ -48,6 +52,7 @@ ap.add_argument("--check", action="store_true")
 ap.add_argument("--label", default="")
 ap.add_argument("--lights", default="")
 ap.add_argument("--sampling", default="")
+ap.add_argument("--passes", type=int, default=-1)
 args = ap.parse_args()
 cases = SETS[args.set]
 if args.scenes:
@@ -86,18 +91,42 @@ def light_table(hs, how):
     return rtc.LightDesc.make(lights)
 
 
+def time_accumulate(gpu, frame, n, passes):
+    """-> (ms per rtc_scene_accumulate_device call with every output, ms per copy of as many bytes, bytes moved per call)"""
+    dev = "cuda"
+    s, mean = torch.rand((n, 3), dtype=torch.float64, device=dev), torch.empty((n, 3), dtype=torch.float64, device=dev)
+    sq, rgba = torch.rand(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+    noise = torch.empty(1, dtype=torch.float64, device=dev)
+    a = rtc.Accum(frame.data_ptr(), n, max(passes, 2), s.data_ptr(), sq.data_ptr(), mean.data_ptr(), rgba.data_ptr(), noise.data_ptr())
+    nbytes = n * (24 + 24 + 8) + n * (24 + 8 + 24 + 4)   # read frame, sum, sumsq; write sum, sumsq, mean, rgba
+    src = torch.empty(nbytes // 2, dtype=torch.uint8, device=dev)
+    dst = torch.empty_like(src)
+
+    def timed(fn, reps=50):
+        for _ in range(10): fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(reps): fn()
+        e1.record(stream); torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps
+    return timed(lambda: gpu.accumulate_device(a, stream.cuda_stream)), timed(lambda: dst.copy_(src)), nbytes
+
+
 stream = torch.cuda.Stream(); torch.cuda.set_stream(stream)
 out = []
 for name, w, h, depth in cases:
     hs = rtc.HostScene.from_file(name + ".json"); cam = hs.camera(w, h)
     canvas = torch.empty((h, w, 3), dtype=torch.float64, device="cuda")
-    ts, kernel, delta = [], "", None
+    ts, kernel, delta, acc = [], "", None, []
     table = light_table(hs, args.lights)
     for rep in range(args.handles):
         gpu = rtc.GpuScene(hs.desc, lights=table)
         if args.sampling:
             sv = [float(v) for v in args.sampling.split(",")]
             gpu.set_sampling(int(sv[0]), True, sv[1] if len(sv) > 1 else 0.0, sv[2] if len(sv) > 2 else 1.0)
+        if args.passes >= 0:
+            gpu.set_sample_pass(args.passes)
         for i in range(args.settle):
             gpu.render_device(cam, canvas.data_ptr(), depth, None, stream.cuda_stream)
         torch.cuda.synchronize()
@@ -109,7 +138,9 @@ for name, w, h, depth in cases:
         kernel = gpu.last_kernel_name()
         st = gpu.stats()
         if st["overflow"]: kernel += " OVERFLOW"
-        if args.check and rep == 0 and not args.sampling:
+        if args.passes >= 0:
+            acc.append(time_accumulate(gpu, canvas, w * h, args.passes + 1))
+        if args.check and rep == 0 and not args.sampling and args.passes < 0:
             import numpy as np, oracle_binding as ob
             step = max(1, h // 24)
             want, c = ob.OracleScene(hs.desc).render(cam, depth, row_step=step, threads=os.cpu_count() and 16)
@@ -120,7 +151,21 @@ for name, w, h, depth in cases:
     if delta is not None: line += f" maxdelta {delta:.2e}"
     if args.lights:
         line += f" shadow_traced {st['shadow_traced']} ns/shadow-ray {min(ts) * 1e6 / max(1, st['shadow_traced']):.3f}"
-    if args.sampling or args.option:
+    if args.sampling or args.option or args.passes >= 0:
         line += f" primary {st['primary']} ns/primary-ray {min(ts) * 1e6 / max(1, st['primary']):.3f}"
+    if acc:
+        ms, copy_ms, nbytes = min(a[0] for a in acc), min(a[1] for a in acc), acc[0][2]
+        line += (f" | pass {args.passes} accumulate {ms:.4f} ms {nbytes / ms / 1e6:.0f} GB/s, copy of the same bytes {copy_ms:.4f} ms"
+                 f" {nbytes / copy_ms / 1e6:.0f} GB/s ({ms / copy_ms:.2f}x)")
+        gpu = rtc.GpuScene(hs.desc, lights=table)
+        if args.sampling:
+            gpu.set_sampling(int(sv[0]), True, sv[1] if len(sv) > 1 else 0.0, sv[2] if len(sv) > 2 else 1.0)
+        prog = rtc.Progressive(gpu, cam, depth)
+        noise = {}
+        for i in range(1, 65):
+            v = prog.step()
+            if i in (4, 16, 64): noise[i] = v
+        line += " | noise " + " ".join(f"{k}:{v:.3e}" for k, v in noise.items())
+        gpu.close()
     out.append(line)
     print((args.label + " " if args.label else "") + line, flush=True)
