@@ -9,6 +9,7 @@
 #   tests/build/libarea_oracle.so                test infrastructure only: the area-light checker (tests/cpp/area_oracle.cpp)
 #   tests/build/libcamera_oracle.so              test infrastructure only: the camera-sampling checker (tests/cpp/camera_oracle.cpp)
 #   tests/build/libprogressive_oracle.so         test infrastructure only: the sample-pass checker (tests/cpp/progressive_oracle.cpp)
+#   tests/build/libmotion_oracle.so              test infrastructure only: the motion-blur checker (tests/cpp/motion_oracle.cpp)
 #
 # -ffp-contract=off everywhere: the reference's float mode is strict IEEE
 # (SURVEY F10); the GPU path and the oracle must round identically.
@@ -34,7 +35,7 @@ oracle:
 	$(MAKE) -C oracle
 
 # (the area-light checker includes the oracle's sources read-only; -pthread and -O3 as the oracle's own build)
-checker: tests/build/libarea_oracle.so tests/build/libcamera_oracle.so tests/build/libprogressive_oracle.so
+checker: tests/build/libarea_oracle.so tests/build/libcamera_oracle.so tests/build/libprogressive_oracle.so tests/build/libmotion_oracle.so
 tests/build/libarea_oracle.so: tests/cpp/area_oracle.cpp oracle/oracle_capi.cpp oracle/rtc_oracle.hpp oracle/rtc_oracle_scene.hpp include/rtc.h
 	mkdir -p tests/build
 	$(CXX) -std=c++17 -O3 -ffp-contract=off -fPIC -Wall -Wextra -pthread -shared -o $@ tests/cpp/area_oracle.cpp
@@ -46,16 +47,29 @@ tests/build/libcamera_oracle.so: tests/cpp/camera_oracle.cpp tests/cpp/area_orac
 tests/build/libprogressive_oracle.so: tests/cpp/progressive_oracle.cpp tests/cpp/camera_oracle.cpp tests/cpp/area_oracle.cpp oracle/oracle_capi.cpp oracle/rtc_oracle.hpp oracle/rtc_oracle_scene.hpp include/rtc.h
 	mkdir -p tests/build
 	$(CXX) -std=c++17 -O3 -ffp-contract=off -fPIC -Wall -Wextra -Wno-subobject-linkage -pthread -shared -o $@ tests/cpp/progressive_oracle.cpp
+# (the motion-blur checker includes the camera-sampling checker, read-only)
+tests/build/libmotion_oracle.so: tests/cpp/motion_oracle.cpp tests/cpp/camera_oracle.cpp tests/cpp/area_oracle.cpp oracle/oracle_capi.cpp oracle/rtc_oracle.hpp oracle/rtc_oracle_scene.hpp include/rtc.h
+	mkdir -p tests/build
+	$(CXX) -std=c++17 -O3 -ffp-contract=off -fPIC -Wall -Wextra -Wno-subobject-linkage -pthread -shared -o $@ tests/cpp/motion_oracle.cpp
 
 $(LIB):
 	mkdir -p $(LIB)
 
 # (the compiler's resource-usage remarks of the product build are kept: lib/kernel_resources.json - registers, spills,
 # scratch bytes per lane, LDS of every kernel - is what bench.py quotes as roofline.scratch_bytes_per_lane)
-$(LIB)/rtc_kernels.o: $(PKG)/csrc/rtc_kernels.hip $(PKG)/csrc/rtc_device.h tools/kernel_resources.py | $(LIB)
+# (the motion kernels, rtc_motion.hip, are render_body of rtc_kernels.hip in a translation unit of their own: the file of
+# every other kernel compiles as before; the JSON holds the kernels of both)
+$(LIB)/rtc_kernels.o: $(PKG)/csrc/rtc_kernels.hip $(PKG)/csrc/rtc_device.h | $(LIB)
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o $@ $< 2> $(LIB)/rtc_kernels.remarks || (grep -v "remark:" $(LIB)/rtc_kernels.remarks >&2; exit 1)
 	@grep -v "remark:\|remarks generated\|\^\|^ *[0-9]* |" $(LIB)/rtc_kernels.remarks >&2 || true
-	python3 tools/kernel_resources.py --from-remarks $(LIB)/rtc_kernels.remarks --json $(LIB)/kernel_resources.json
+
+$(LIB)/rtc_motion.o: $(PKG)/csrc/rtc_motion.hip $(PKG)/csrc/rtc_kernels.hip $(PKG)/csrc/rtc_device.h | $(LIB)
+	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o $@ $< 2> $(LIB)/rtc_motion.remarks || (grep -v "remark:" $(LIB)/rtc_motion.remarks >&2; exit 1)
+	@grep -v "remark:\|remarks generated\|\^\|^ *[0-9]* |" $(LIB)/rtc_motion.remarks >&2 || true
+
+$(LIB)/kernel_resources.json: $(LIB)/rtc_kernels.o $(LIB)/rtc_motion.o tools/kernel_resources.py
+	cat $(LIB)/rtc_kernels.remarks $(LIB)/rtc_motion.remarks > $(LIB)/render_kernels.remarks
+	python3 tools/kernel_resources.py --from-remarks $(LIB)/render_kernels.remarks --json $@
 
 $(LIB)/rtc_capi.o: $(PKG)/csrc/rtc_capi.hip $(wildcard $(PKG)/csrc/*.h) include/rtc.h | $(LIB)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
@@ -64,7 +78,7 @@ $(LIB)/rtc_capi.o: $(PKG)/csrc/rtc_capi.hip $(wildcard $(PKG)/csrc/*.h) include/
 $(LIB)/rtc_accum.o: $(PKG)/csrc/rtc_accum.hip $(PKG)/csrc/rtc_device.h | $(LIB)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
-$(LIB)/librtc_hip.so: $(LIB)/rtc_kernels.o $(LIB)/rtc_capi.o $(LIB)/rtc_accum.o
+$(LIB)/librtc_hip.so: $(LIB)/rtc_kernels.o $(LIB)/rtc_motion.o $(LIB)/rtc_capi.o $(LIB)/rtc_accum.o | $(LIB)/kernel_resources.json
 	$(HIPCC) --offload-arch=gfx950 -shared -fPIC -o $@ $^
 
 $(LIB)/librtc_multi.so: $(PKG)/csrc/rtc_multi.hip include/rtc_multi.h include/rtc.h $(LIB)/librtc_hip.so

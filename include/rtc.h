@@ -345,6 +345,31 @@ typedef struct rtc_accum {
  * RTC_ERR_INVALID_ARGUMENT otherwise.
  */
 int rtc_scene_accumulate_device(rtc_scene *scene, const rtc_accum *accum, void *hip_stream);
+
+/* ---- motion blur: top-level objects that move while the shutter is open ---- */
+/*
+ * Root r (World.objects entry r, the scene description's roots[r]) moves by the world-space displacement
+ * D_r = displacement[3 r .. 3 r + 2] over the shutter interval: at time t in [0, 1) the root and its whole subtree -
+ * leaves, group boxes, normals, patterns - are where they rest, translated by t * D_r.  Lights and the camera do not
+ * move; motion is translation only.  Camera sample k of the whole-image pixel p in sample pass P has the time
+ * t = the camera hash of (seed, p, P * S + k) on axis 255 (the sub-pixel offsets use axes 0 and 1, the lens 2 .. 65):
+ * independent of bands, tiles and clones, new with every pass, and shared by the sample's reflected, refracted and
+ * shadow rays.  Root r is tested with the ray's origin shifted to (o.x - t * D.x, o.y - t * D.y, o.z - t * D.z) and the
+ * direction as it is; the hit object's normal and pattern are taken at p - t * D_r, component by component.  A root with
+ * D = (0, 0, 0) is tested with the very operands of a static one; a handle whose displacements are all zero is static
+ * and renders the bits of before.
+ */
+typedef struct rtc_motion {
+  uint32_t n_roots;            /* the handle's root count (rtc_scene_desc.n_roots) */
+  const double *displacement;  /* [n_roots][3], finite                           */
+} rtc_motion;
+
+/*
+ * This handle's motion for every render entry point (NULL: static).  Validated before anything changes:
+ * RTC_ERR_INVALID_ARGUMENT unless n_roots equals the handle's root count and every value is finite.  A clone starts
+ * with its source's motion; rtc_render's band clones follow.  librtc_multi renders static scenes.
+ */
+int rtc_scene_set_motion(rtc_scene *scene, const rtc_motion *motion);
 void rtc_scene_destroy(rtc_scene *scene);
 
 /*

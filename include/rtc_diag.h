@@ -30,7 +30,8 @@ extern "C" {
  * on it), "box_cull" (read at create: a world of top-level spheres / planes / cubes runs the kernels whose root loop
  * rejects by world boxes - 1 - or by bounding spheres - 0; < 0: boxes if it has more cubes than spheres),
  * "sampling_kernels" (!= 0: the camera-sampling kernels even with the default sampling - one centred ray per pixel -, so
- * that their one-sample images can be held to the other kernels').
+ * that their one-sample images can be held to the other kernels'), "motion_kernels" (!= 0: the motion kernels even on a
+ * static handle, with every displacement zero, so that their images can be held to the sampling kernels').
  * RTC_ERR_INVALID_ARGUMENT for a name the library does not know.
  * (The library reads no environment variables.)
  */

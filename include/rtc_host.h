@@ -16,7 +16,8 @@
  *   rtch_scene_render    main.zig:92: load -> Camera.render -> Canvas, through rtc_scene_create / rtc_render
  *                        (rtc_scene_create_with_lights when the scene has an area light; the camera's
  *                        sampling, rtch_scene_sampling, through rtc_scene_set_sampling; its sample passes,
- *                        rtch_scene_passes, through rtc_scene_set_sample_pass, averaged on the host)
+ *                        rtch_scene_passes, through rtc_scene_set_sample_pass, averaged on the host; the
+ *                        top-level objects' motion, rtch_scene_motion, through rtc_scene_set_motion)
  *
  * Every function that returns int returns 0 on success; otherwise rtch_last_error()
  * holds "<ZigStyleErrorName>: detail" (thread-local).
@@ -54,6 +55,10 @@ int rtch_scene_sampling(void *handle, rtc_sampling *out);
  * 0 .. n-1 (rtc_scene_set_sample_pass), sums them in pass order and divides by n once - the bits of
  * rtc_scene_accumulate_device's mean after n passes. */
 int rtch_scene_passes(void *handle, uint32_t *out);
+/* The top-level objects' "motion" of the scene file (motion blur): out[3 r .. 3 r + 2] = the
+ * displacement of root r over the shutter, (0, 0, 0) for a root without one; n must be the description's n_roots.  Pass
+ * it to rtc_scene_set_motion.  rtch_scene_render applies it. */
+int rtch_scene_motion(void *handle, double *out, uint32_t n);
 int rtch_scene_camera(void *handle, uint32_t width, uint32_t height, rtc_camera *out);
 int rtch_camera_rotate(void *handle, double angle);
 int rtch_camera_move(void *handle, double distance);

@@ -162,6 +162,12 @@ class Accum(C.Structure):
 RTC_SAMPLING_INDEX_LIMIT = 1 << 24   # (pass + 1) * grid * grid may not exceed it (include/rtc.h)
 
 
+class Motion(C.Structure):
+    """struct rtc_motion (include/rtc.h): a world-space displacement over the shutter per World.objects entry."""
+
+    _fields_ = [("n_roots", C.c_uint32), ("displacement", C.POINTER(C.c_double))]
+
+
 # (include/rtc.h: what a host binds ...)
 RTC_SYMBOLS = ["rtc_scene_create", "rtc_scene_clone", "rtc_scene_destroy", "rtc_render", "rtc_render_rgba8", "rtc_render_device",
                "rtc_render_tiles_device", "rtc_assemble_tiles_device", "rtc_render_tile_list_device", "rtc_get_tile_costs",
@@ -169,12 +175,12 @@ RTC_SYMBOLS = ["rtc_scene_create", "rtc_scene_clone", "rtc_scene_destroy", "rtc_
                "rtc_scatter_tile_list_rgba8_device", "rtc_scene_synchronize", "rtc_get_stats", "rtc_last_error", "rtc_status_name",
                "rtc_grow_csg_lists", "rtc_canvas_register", "rtc_canvas_unregister", "rtc_rgba8_device",
                "rtc_scene_create_with_lights", "rtc_scene_set_light_seed", "rtc_scene_set_sampling",
-               "rtc_scene_set_sample_pass", "rtc_scene_accumulate_device"]
+               "rtc_scene_set_sample_pass", "rtc_scene_accumulate_device", "rtc_scene_set_motion"]
 # (... and include/rtc_diag.h: diagnostics and tuning, for the tests, bench.py and tools/)
 RTC_DIAG_SYMBOLS = ["rtc_set_option", "rtc_last_kernel_name", "rtc_get_schedule", "rtc_get_chunk_times", "rtc_diag_build_tables", "rtc_diag_root_boxes"]
 HOST_SYMBOLS = ["rtch_last_error", "rtch_scene_load", "rtch_scene_free", "rtch_scene_desc", "rtch_scene_camera",
                 "rtch_camera_rotate", "rtch_camera_move", "rtch_camera_make", "rtch_canvas_ppm", "rtch_canvas_rgba8", "rtch_scene_render", "rtch_set_loader_threads",
-                "rtch_scene_lights", "rtch_scene_sampling", "rtch_scene_passes"]
+                "rtch_scene_lights", "rtch_scene_sampling", "rtch_scene_passes", "rtch_scene_motion"]
 
 MULTI_SYMBOLS = ["rtc_multi_create", "rtc_multi_destroy", "rtc_multi_render", "rtc_multi_render_rgba8", "rtc_multi_render_device", "rtc_multi_render_rgba8_device",
                  "rtc_multi_synchronize", "rtc_multi_stream", "rtc_multi_get_stats", "rtc_multi_balance", "rtc_multi_last_error"]
@@ -227,6 +233,7 @@ def hip_lib():
         lib.rtc_scene_set_sampling.argtypes = [C.c_void_p, C.POINTER(Sampling)]
         lib.rtc_scene_set_sample_pass.argtypes = [C.c_void_p, C.c_uint32]
         lib.rtc_scene_accumulate_device.argtypes = [C.c_void_p, C.POINTER(Accum), C.c_void_p]
+        lib.rtc_scene_set_motion.argtypes = [C.c_void_p, C.POINTER(Motion)]
         lib.rtc_scene_destroy.argtypes = [C.c_void_p]
         lib.rtc_scene_destroy.restype = None
         lib.rtc_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32] + [C.c_uint32] * 4 + [C.c_void_p]
@@ -277,6 +284,7 @@ def host_lib():
         lib.rtch_scene_lights.restype = C.POINTER(LightDesc)
         lib.rtch_scene_sampling.argtypes = [C.c_void_p, C.POINTER(Sampling)]
         lib.rtch_scene_passes.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        lib.rtch_scene_motion.argtypes = [C.c_void_p, _dp, C.c_uint32]
         lib.rtch_scene_camera.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Camera)]
         lib.rtch_camera_rotate.argtypes = [C.c_void_p, C.c_double]
         lib.rtch_camera_move.argtypes = [C.c_void_p, C.c_double]
@@ -434,6 +442,14 @@ class HostScene:
         _check_host(host_lib().rtch_scene_passes(self._h, C.byref(n)))
         return n.value
 
+    def motion(self):
+        """The top-level objects' "motion" of the scene file (rtch_scene_motion): an (n_roots, 3) array, zero for a root
+        without one."""
+        n = self.desc.n_roots
+        out = np.zeros((n, 3), dtype=np.float64)
+        _check_host(host_lib().rtch_scene_motion(self._h, out.ctypes.data_as(_dp), n))
+        return out
+
     def rotate_camera(self, angle):
         """Renderer.rotateCamera (lib.zig:166-178): orbit the camera around its target, about `up`."""
         _check_host(host_lib().rtch_camera_rotate(self._h, C.c_double(angle)))
@@ -501,6 +517,18 @@ class GpuScene:
     def set_sample_pass(self, p):
         """rtc_scene_set_sample_pass: the sample pass every later render of this handle draws (0: the default)."""
         _check_hip(hip_lib().rtc_scene_set_sample_pass(self._s, p))
+
+    def set_motion(self, displacements):
+        """rtc_scene_set_motion: an (n_roots, 3) array of world-space displacements over the shutter, one per World.objects
+        entry (HostScene.motion()); None: static."""
+        if displacements is None:
+            _check_hip(hip_lib().rtc_scene_set_motion(self._s, None))
+            return
+        d = np.ascontiguousarray(displacements, dtype=np.float64)
+        if d.ndim != 2 or d.shape[1] != 3:
+            raise ValueError(f"set_motion: displacements of shape {d.shape}, (n_roots, 3) expected")
+        m = Motion(d.shape[0], d.ctypes.data_as(_dp))
+        _check_hip(hip_lib().rtc_scene_set_motion(self._s, C.byref(m)))
 
     def accumulate_device(self, accum, stream=None):
         """rtc_scene_accumulate_device: an Accum, enqueued on `stream` (None: the handle's own) after this handle's renders."""

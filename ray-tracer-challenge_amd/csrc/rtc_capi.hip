@@ -89,6 +89,16 @@ __global__ void rtc_render_kernel_area_ms_bigworld(const DevScene S, const DevCa
                                                    double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
                                                    const DevAreaLights area, const DevSampling smp);
 }
+// The motion kernels (rtc_scene_set_motion: top-level objects that move while the shutter is open).  Their table edge -
+// RTC_LDS_ROOTS roots select the LDS kernel, one more the big-world one - is tested in tests/test_motion_gpu.py.
+extern "C" {
+__global__ void rtc_render_kernel_motion(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                         double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                         const DevAreaLights area, const DevSampling smp, const DevMotion mo);
+__global__ void rtc_render_kernel_motion_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                                  double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                                  const DevAreaLights area, const DevSampling smp, const DevMotion mo);
+}
 // Progressive rendering's accumulation (rtc_accum.hip): the grid's blocks for n pixels (the noise partials it writes, at
 // most) and the enqueue of its kernels.
 uint32_t rtcAccumBlocks(size_t n_pixels, bool wide);
@@ -295,22 +305,40 @@ bool tablesInLds(const rtc_scene* s) {
 }
 
 // (the area kernels take one more argument, DevAreaLights: `area` instead of `fn`; the sampling kernels DevSampling:
-// `ms`, and both: `area_ms`)
+// `ms`, and both: `area_ms`; the motion kernels both and DevMotion: `motion`)
 struct KernelChoice {
   decltype(&rtc_render_kernel) fn;
   const char* name;
   decltype(&rtc_render_kernel_area) area = nullptr;
   decltype(&rtc_render_kernel_ms) ms = nullptr;
   decltype(&rtc_render_kernel_area_ms) area_ms = nullptr;
+  decltype(&rtc_render_kernel_motion) motion = nullptr;
   KernelChoice(decltype(&rtc_render_kernel) f, const char* n) : fn(f), name(n) {}
   KernelChoice(decltype(&rtc_render_kernel_area) a, const char* n) : fn(nullptr), name(n), area(a) {}
   KernelChoice(decltype(&rtc_render_kernel_ms) m, const char* n) : fn(nullptr), name(n), ms(m) {}
   KernelChoice(decltype(&rtc_render_kernel_area_ms) am, const char* n) : fn(nullptr), name(n), area_ms(am) {}
+  KernelChoice(decltype(&rtc_render_kernel_motion) mo, const char* n) : fn(nullptr), name(n), motion(mo) {}
   void launch(uint32_t blocks, hipStream_t stream, const rtc_scene* s, const DevScene& dev, const DevCamera& cam, const DevPixelMap& map,
               uint32_t max_depth, double* d_out, DevStats* st_now, DevStats* st_next) const {
     DevSampling smp = s->sampling;  // (the pass's area-light offset, P * N * S: N is the camera's whole image)
     smp.pixel_base = static_cast<unsigned long long>(smp.sample_base) * (static_cast<unsigned long long>(cam.hsize) * cam.vsize);
-    if (area_ms)
+    if (motion) {
+      // the handle's root tables with the moving roots' bounds (or the scene's, all displacements zero: the option), and
+      // the scene's area rows (or zero rows: a point-only table)
+      DevScene md = dev;
+      DevMotion mo{s->tab->zero_disp.p};
+      smp.key = rtc_mix64(s->sampling_desc.seed ^ 0x243F6A8885A308D3ull);  // (the time's hash: also under the default sampling)
+      if (const MotionTables* m = s->motion.get()) {
+        md.root_recs = m->root_recs.p;
+        md.root_cull = m->root_cull.p;
+        md.root_box = m->root_box.p;
+        md.cull_cmax = m->cull_cmax;
+        md.cull_bmax = m->cull_bmax;
+        mo.disp = m->disp.p;
+      }
+      const DevAreaLights area = s->area_kernel ? s->area : DevAreaLights{s->tab->zero_rows.p, s->area.seed};
+      hipLaunchKernelGGL(motion, dim3(blocks), dim3(256), 0, stream, md, cam, map, max_depth, d_out, st_now, st_next, area, smp, mo);
+    } else if (area_ms)
       hipLaunchKernelGGL(area_ms, dim3(blocks), dim3(256), 0, stream, dev, cam, map, max_depth, d_out, st_now, st_next, s->area, smp);
     else if (ms)
       hipLaunchKernelGGL(ms, dim3(blocks), dim3(256), 0, stream, dev, cam, map, max_depth, d_out, st_now, st_next, smp);
@@ -323,6 +351,9 @@ struct KernelChoice {
 // The sampling kernels run when the handle's sampling is not the default (one centred ray per pixel, no lens), or its
 // sample pass is not 0 - or, for tests, whenever option "sampling_kernels" is set.  Otherwise the kernels run exactly as before.
 bool samplingKernels(const rtc_scene* s) { return s->sampling_on || s->sample_pass != 0u || rtcOptions().sampling_kernels != 0.0; }
+// The motion kernels run when a displacement of the handle is not zero - whatever the sampling and the pass: the image
+// depends on the shutter time - or, for tests, whenever option "motion_kernels" is set.
+bool motionKernels(const rtc_scene* s) { return s->motion != nullptr || rtcOptions().motion_kernels != 0.0; }
 #define RTC_KERNEL(k) KernelChoice{k, #k}
 // The general kernel at three waves per SIMD (rtc_render_kernel3): forced by option "waves3", else what the handle's
 // trial measured (KernelTune in launch()).
@@ -349,6 +380,7 @@ KernelChoice ldsKernel(const rtc_scene* s, const DevPixelMap& map) {
   return s->ext_kernel ? RTC_KERNEL(rtc_render_kernel_ext) : RTC_KERNEL(rtc_render_kernel);
 }
 KernelChoice renderKernel(const rtc_scene* s, const DevPixelMap& map) {
+  if (motionKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_motion) : RTC_KERNEL(rtc_render_kernel_motion_bigworld);
   if (samplingKernels(s)) {
     if (s->area_kernel) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_area_ms) : RTC_KERNEL(rtc_render_kernel_area_ms_bigworld);
     return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_ms) : RTC_KERNEL(rtc_render_kernel_ms_bigworld);
@@ -361,6 +393,7 @@ KernelChoice renderKernel(const rtc_scene* s, const DevPixelMap& map) {
 
 // Work-groups of the launch's kernel that are resident at once, and the waves in them.
 uint32_t residentBlocksAlone(const rtc_scene* s, const DevPixelMap& map) {
+  if (motionKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_motion_lds : s->blocks_per_cu_motion_big);
   if (samplingKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_ms_lds : s->blocks_per_cu_ms_big);
   if (usesSimple3(s, map)) return s->n_cus * s->blocks_per_cu_simple3;
   if (tablesInLds(s) && usesGeneral3(s)) return s->n_cus * s->blocks_per_cu_general3;
@@ -765,7 +798,7 @@ int launch(rtc_scene* s, const rtc_camera& cam, const DevPixelMap& map_in, uint3
   int trial_slot = -1;
   {
     rtc_scene::KernelTune& T = s->tune;
-    const bool eligible = !samplingKernels(s) &&  // (the sampling kernels have no three-wave form)
+    const bool eligible = !samplingKernels(s) && !motionKernels(s) &&  // (the sampling and motion kernels have no three-wave form)
                           ((s->general3_ok && rtcOptions().waves3 < 0.0 && tablesInLds(s) &&
                             !(s->tab && s->tab->handles.load(std::memory_order_relaxed) > 1) &&
                             static_cast<double>(map.n_chunks) >= 4.0 * 4.0 * s->n_cus * s->blocks_per_cu_lds) ||
@@ -1960,6 +1993,14 @@ int uploadTables(const rtc_scene_desc& d, const SceneTraits& traits, const HostT
     root_box_pairs[i].line_only = {a.line_only, b.line_only};
   }
   HIP_TRY(s->tab->root_box.upload(root_box_pairs));
+  {  // (what rtc_scene_set_motion makes a handle's motion tables from)
+    s->tab->h_root_recs = root_recs;
+    s->tab->h_root_cull = root_cull_pairs;
+    s->tab->h_root_box = root_box_pairs;
+    s->tab->h_root_order = T.root_order;
+    HIP_TRY(s->tab->zero_disp.upload(std::vector<double>(3ull * root_recs.size(), 0.0)));
+    HIP_TRY(s->tab->zero_rows.upload(std::vector<double>(static_cast<size_t>(RTC_AREA_ROW) * d.n_lights, 0.0)));
+  }
   HIP_TRY(s->tab->root_weight.upload(T.root_weight));
   HIP_TRY(s->tab->kids.upload(kids));
   HIP_TRY(s->tab->leaf_meta.upload(leaf_meta));
@@ -2095,9 +2136,14 @@ int uploadTables(const rtc_scene_desc& d, const SceneTraits& traits, const HostT
     if (s->area_kernel) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_area_ms_bigworld, 256, 0));
     else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_ms_bigworld, 256, 0));
     s->blocks_per_cu_ms_big = static_cast<uint32_t>(std::max(nb, 1));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_motion, 256, 0));  // (the motion kernels: one pair for every world)
+    s->blocks_per_cu_motion_lds = static_cast<uint32_t>(std::max(nb, 1));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_motion_bigworld, 256, 0));
+    s->blocks_per_cu_motion_big = static_cast<uint32_t>(std::max(nb, 1));
     if (const int v = static_cast<int>(rtcOptions().blocks_per_cu); v >= 1) {  // (tuning option)
       s->blocks_per_cu_lds = std::min<uint32_t>(s->blocks_per_cu_lds, v), s->blocks_per_cu_big = std::min<uint32_t>(s->blocks_per_cu_big, v);
       s->blocks_per_cu_ms_lds = std::min<uint32_t>(s->blocks_per_cu_ms_lds, v), s->blocks_per_cu_ms_big = std::min<uint32_t>(s->blocks_per_cu_ms_big, v);
+      s->blocks_per_cu_motion_lds = std::min<uint32_t>(s->blocks_per_cu_motion_lds, v), s->blocks_per_cu_motion_big = std::min<uint32_t>(s->blocks_per_cu_motion_big, v);
     }
   }
   DevScene& D = s->dev;
@@ -2391,6 +2437,119 @@ int rtc_scene_accumulate_device(rtc_scene* s, const rtc_accum* a, void* hip_stre
   return RTC_OK;
 }
 
+// FP32 bounds of a moving root, rounded outward (motion tables)
+static float roundDown(double x) {
+  float f = static_cast<float>(x);
+  if (static_cast<double>(f) > x) f = std::nextafterf(f, -INFINITY);
+  return f;
+}
+static float roundUp(double x) {
+  float f = static_cast<float>(x);
+  if (static_cast<double>(f) < x) f = std::nextafterf(f, INFINITY);
+  return f;
+}
+
+// A handle's motion tables: the displacements in table order, and the scene's root tables with every moving root's
+// bounds grown to the union of the bound at rest and the bound moved by D, and its "room" flag cleared (the room
+// early-out assumes the cube holds every light for good).
+static int makeMotionTables(const rtc_scene* s, const double* world_disp, std::shared_ptr<const MotionTables>& out) {
+  const SceneTables& tab = *s->tab;
+  const uint32_t n = s->dev.n_roots;
+  auto m = std::make_shared<MotionTables>();
+  std::vector<double> disp(3ull * n, 0.0);
+  std::vector<RootRec> recs = tab.h_root_recs;
+  std::vector<RootCullPair> cull = tab.h_root_cull;
+  std::vector<RootBoxPair> box = tab.h_root_box;
+  m->cull_cmax = s->dev.cull_cmax;
+  m->cull_bmax = s->dev.cull_bmax;
+  for (uint32_t i = 0; i < n; ++i) {
+    const double* D = world_disp + 3ull * tab.h_root_order[i];
+    if (D[0] == 0.0 && D[1] == 0.0 && D[2] == 0.0) continue;
+    for (int k = 0; k < 3; ++k) disp[3ull * i + k] = D[k];
+    recs[i].kind_flags &= ~RTC_ROOT_ROOM;
+    {  // the world box: -3e38 / +3e38 (no finite bound) stays
+      RootBoxPair& B = box[i / 2u];
+      const int e = static_cast<int>(i & 1u);
+      RootBoxPair::Pair* const axis[3] = {B.x, B.y, B.z};
+      bool bounded = true;
+      float lo[3], hi[3];
+      for (int k = 0; k < 3; ++k) {
+        const double l = axis[k][0][e], h = axis[k][1][e];
+        if (!(l > -1.0e37 && h < 1.0e37)) bounded = false;
+        lo[k] = roundDown(std::fmin(l, l + D[k]));
+        hi[k] = roundUp(std::fmax(h, h + D[k]));
+        if (!(std::fabs(lo[k]) < 1.0e37f && std::fabs(hi[k]) < 1.0e37f)) bounded = false;
+      }
+      for (int k = 0; k < 3; ++k) {
+        axis[k][0][e] = axis[k][2][e] = bounded ? lo[k] : -3.0e38f;
+        axis[k][1][e] = bounded ? hi[k] : 3.0e38f;
+        if (bounded) m->cull_bmax = std::fmax(m->cull_bmax, std::fmax(std::fabs(lo[k]), std::fabs(hi[k])));
+      }
+    }
+    {  // the bounding sphere: centre moved by D / 2, radius grown by |D| / 2 (r2 == +inf: no finite bound)
+      RootCullPair& C = cull[i / 2u];
+      const int e = static_cast<int>(i & 1u);
+      const double r2 = C.r2[e];
+      if (std::isfinite(r2) && r2 >= 0.0) {
+        uint32_t bits;
+        const float r2_old = C.r2[e];
+        std::memcpy(&bits, &r2_old, sizeof bits);
+        const uint32_t line_only = bits & 1u;
+        const double cx = static_cast<double>(C.cx[e]) + 0.5 * D[0], cy = static_cast<double>(C.cy[e]) + 0.5 * D[1],
+                     cz = static_cast<double>(C.cz[e]) + 0.5 * D[2];
+        const double r = std::sqrt(r2) + 0.5 * std::sqrt(D[0] * D[0] + D[1] * D[1] + D[2] * D[2]);
+        float r2f = roundUp(r * r * (1.0 + 1e-5));
+        std::memcpy(&bits, &r2f, sizeof bits);
+        if ((bits & 1u) != line_only) r2f = std::nextafterf(r2f, INFINITY);
+        const float cm = static_cast<float>(std::sqrt(cx * cx + cy * cy + cz * cz) * (1.0 + 1e-6));
+        if (std::isfinite(r2f) && std::isfinite(cm)) {
+          C.cx[e] = static_cast<float>(cx);
+          C.cy[e] = static_cast<float>(cy);
+          C.cz[e] = static_cast<float>(cz);
+          C.r2[e] = r2f;
+          m->cull_cmax = std::fmax(m->cull_cmax, cm);
+        } else {
+          C.cx[e] = C.cy[e] = C.cz[e] = 0.0f;
+          C.r2[e] = INFINITY;
+        }
+      }
+    }
+  }
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(m->disp.upload(disp));
+  HIP_TRY(m->root_recs.upload(recs));
+  HIP_TRY(m->root_cull.upload(cull));
+  HIP_TRY(m->root_box.upload(box));
+  out = std::move(m);
+  return RTC_OK;
+}
+
+int rtc_scene_set_motion(rtc_scene* s, const rtc_motion* motion) {
+  g_error.clear();
+  if (!s) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
+  bool moving = false;
+  if (motion) {
+    if (motion->n_roots != s->dev.n_roots)
+      return fail(RTC_ERR_INVALID_ARGUMENT, "motion: n_roots %u, the scene has %u", motion->n_roots, s->dev.n_roots);
+    if (motion->n_roots != 0u && !motion->displacement) return fail(RTC_ERR_INVALID_ARGUMENT, "motion: null displacement");
+    for (size_t i = 0; i < 3ull * motion->n_roots; ++i) {
+      const double v = motion->displacement[i];
+      if (!std::isfinite(v)) return fail(RTC_ERR_INVALID_ARGUMENT, "motion: displacement %zu of root %zu is %g", i % 3u, i / 3u, v);
+      moving = moving || v != 0.0;
+    }
+  }
+  std::shared_ptr<const MotionTables> tables;  // (all displacements zero: static)
+  if (moving) {
+    if (const int st = makeMotionTables(s, motion->displacement, tables); st != RTC_OK) return st;
+  }
+  // (the tables being replaced may still be read by a launch of this handle or of its band clones)
+  HIP_TRY(handleIdle(s));
+  for (rtc_scene* b : s->band) HIP_TRY(handleIdle(b));
+  s->motion = tables;
+  for (rtc_scene* b : s->band) b->motion = tables;  // (the band clones rtc_render renders a large frame with)
+  return RTC_OK;
+}
+
 int rtc_scene_clone(const rtc_scene* src, rtc_scene** out) {
   g_error.clear();
   if (!src || !out) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
@@ -2417,6 +2576,9 @@ int rtc_scene_clone(const rtc_scene* src, rtc_scene** out) {
   applySampling(s, src->sampling_desc);
   s->blocks_per_cu_ms_lds = src->blocks_per_cu_ms_lds;
   s->blocks_per_cu_ms_big = src->blocks_per_cu_ms_big;
+  s->motion = src->motion;  // (shared: read-only once made)
+  s->blocks_per_cu_motion_lds = src->blocks_per_cu_motion_lds;
+  s->blocks_per_cu_motion_big = src->blocks_per_cu_motion_big;
   s->simple_kernel = src->simple_kernel;
   s->flat_kernel = src->flat_kernel;
   s->simple3_ok = src->simple3_ok;
@@ -2812,7 +2974,7 @@ int rtc_set_option(const char* name, double value) {
                {"bvh_check", &o.bvh_check}, {"host_bands", &o.host_bands}, {"waves3", &o.waves3},
                {"measure_every", &o.measure_every}, {"sched_mix", &o.sched_mix},
                {"inflight_chunks_per_wave", &o.inflight_chunks_per_wave}, {"build_threads", &o.build_threads}, {"box_cull", &o.box_cull},
-               {"sampling_kernels", &o.sampling_kernels}};
+               {"sampling_kernels", &o.sampling_kernels}, {"motion_kernels", &o.motion_kernels}};
   for (const auto& e : table)
     if (std::strcmp(e.name, name) == 0) {
       e.slot->set(value);

@@ -313,6 +313,15 @@ __host__ __device__ inline double rtc_camera_jitter(unsigned long long key, unsi
   return static_cast<double>(rtc_mix64(key + 0x9E3779B97F4A7C15ull * (c + 1ull)) >> 11) * 0x1.0p-53;
 }
 
+// Motion blur (rtc_scene_set_motion): the extra argument of the motion kernels only.  Root r (table
+// order) moves by disp[3 r .. 3 r + 2] over the shutter; at time t it is tested with the ray's origin shifted by -t * D.
+// The time of camera sample k of the whole-image pixel p is the camera hash on axis RTC_MOTION_AXIS, at the global
+// sample index sample_base + k: independent of bands, tiles and clones, new with every pass.
+#define RTC_MOTION_AXIS 255u
+struct DevMotion {
+  const double* __restrict__ disp;  // [n_roots][3], in the root tables' order (all zero: the "motion_kernels" option)
+};
+
 struct DevCamera {
   double half_width, half_height, pixel_size;
   double inv[12];  // rows 0..2 of Camera._inverse_transform

@@ -66,6 +66,7 @@ struct RtcOptions {
   RtcOption host_bands{0.0};           // bands rtc_render cuts a frame into (copy of band i under the render of band i + 1); 0: by size
   RtcOption box_cull{-1.0};            // a simple world's kernels reject roots by world boxes (1) or bounding spheres (0); < 0: boxes if it has more cubes than spheres
   RtcOption sampling_kernels{0.0};     // != 0: the sampling kernels even with the default sampling (tests: one sample against the other kernels)
+  RtcOption motion_kernels{0.0};       // != 0: the motion kernels even on a static handle, all displacements zero (tests: against the _ms kernels)
   RtcOption build_threads{0.0};        // threads of rtc_scene_create's candidate-BVH build (one top-level group each); 0: as many as the host allows, up to 8
 };
 inline RtcOptions& rtcOptions() {
@@ -124,6 +125,25 @@ struct SceneTables {
   DevBuf<DevUv> uv;
   DevBuf<DevImage> img;
   DevBuf<float> img_rgb;
+  // motion blur (rtc_scene_set_motion): the root tables as uploaded, on the host, from which a handle's motion tables are
+  // made; the zero displacements of a static handle under option "motion_kernels"; and zero area rows, with which a
+  // point-only light table goes through the motion kernels (every row says "point light")
+  std::vector<RootRec> h_root_recs;
+  std::vector<RootCullPair> h_root_cull;
+  std::vector<RootBoxPair> h_root_box;
+  std::vector<uint32_t> h_root_order;  // table position -> World.objects index
+  DevBuf<double> zero_disp, zero_rows;
+};
+
+// A handle's motion (rtc_scene_set_motion): the displacements in table order, and copies of the root tables in which a
+// moving root's bounds cover its whole path and its "room" flag is cleared.  Read-only once made: a clone and the band
+// clones share them.
+struct MotionTables {
+  DevBuf<double> disp;             // DevMotion::disp, table order
+  DevBuf<RootRec> root_recs;
+  DevBuf<RootCullPair> root_cull;
+  DevBuf<RootBoxPair> root_box;
+  float cull_cmax = 0.0f, cull_bmax = 0.0f;
 };
 
 constexpr uint32_t RTC_MAX_HOST_BANDS = 4;
@@ -151,6 +171,8 @@ struct rtc_scene {
   double* d_accum_partials = nullptr;  // rtc_scene_accumulate_device's per-block noise partials, and the total behind them
   size_t accum_partials_capacity = 0;  // doubles
   uint32_t blocks_per_cu_ms_lds = 1, blocks_per_cu_ms_big = 1;  // resident work-groups of the world's sampling kernels
+  std::shared_ptr<const MotionTables> motion;  // rtc_scene_set_motion; null: static (a clone starts with its source's)
+  uint32_t blocks_per_cu_motion_lds = 1, blocks_per_cu_motion_big = 1;  // ... and of the motion kernels
   bool simple3_ok = false;         // a simple world whose tables fit the three-waves-per-SIMD kernel's LDS (RTC_LDS3_*)
   void* d_csg_buf = nullptr;       // DevPixelMap::csg_buf, only for scenes with csg nodes
   size_t csg_buf_capacity = 0;     // bytes

@@ -1303,11 +1303,19 @@ __device__ __forceinline__ uint32_t roots_kept_box4(const char* __restrict__ pai
 // group hold the same ray; lane `member` of the group takes every stride-th batch of four roots through both phases, and
 // the group's visitors are merged at the end: what one lane does in five batches and three exact tests in a row, eight
 // lanes do in one of each - the instruction stream of a wave with few rays left is what bounds it.  (0, 1): one lane, all.
-template <bool CSG, int WORLD, class V, int TRAV = RTC_LDS_TRAV, bool BOX = true>
+// (MOTION) which root the trace is in: only the closest-hit visitor of the motion kernels keeps it (MotionClosestVisitor)
+template <class V>
+__device__ __forceinline__ void motion_root(V&, uint32_t) {}
+
+// MOTION (the motion kernels only; a world with groups, one lane per ray): root r is tested at the lane's shutter time tm
+// with the ray's origin shifted by -tm * D_r (DevMotion); phase 1 reads tables whose bounds already cover the motion.
+template <bool CSG, int WORLD, class V, int TRAV = RTC_LDS_TRAV, bool BOX = true, bool MOTION = false>
 __device__ __forceinline__ void trace(const DevScene& S, const RootRec* __restrict__ recs,
                                       const CullTables& cull, const Ray& ray, V& vis, unsigned& overflow,
-                                      uint32_t* lds_stack, const uint32_t member = 0u, const uint32_t stride = 1u) {
+                                      uint32_t* lds_stack, const uint32_t member = 0u, const uint32_t stride = 1u,
+                                      const double* __restrict__ disp = nullptr, const double tm = 0.0) {
   constexpr bool SIMPLE = WORLD == 2, FLAT = WORLD >= 1;
+  static_assert(!MOTION || WORLD == 0, "the motion kernels walk the general world");
   // Phase 1 rejects a root by its world BOX (BOX: every kernel that walks groups, the flat kernels, and the simple kernels
   // of worlds that are mostly cubes) or by its bounding SPHERE (the simple kernels of worlds that are mostly spheres): a
   // cube's box is the cube where its sphere lets through half of the rays that miss it, a group's box is far tighter than
@@ -1479,9 +1487,21 @@ __device__ __forceinline__ void trace(const DevScene& S, const RootRec* __restri
       mine &= mine - 1ull;
       const RootRec& R = recs[RTC_CHECK_INDEX(RTC_OOB_ROOTS, base + bit, RTC_AVAIL(0))];
       const uint32_t kf = R.kind_flags;
+      // (MOTION: this root's ray, the origin shifted by -tm * D - with D = 0 the same bits; every other kernel tests `ray`
+      // itself: a copy of it, even an unchanged one, moves their register allocation)
+      Ray shifted;
+      if constexpr (MOTION) {
+        const double* __restrict__ D = disp + 3ull * (base + bit);
+        shifted = ray;
+        shifted.ox = ray.ox - tm * D[0];
+        shifted.oy = ray.oy - tm * D[1];
+        shifted.oz = ray.oz - tm * D[2];
+        motion_root(vis, base + bit);
+      }
+      const Ray& root_ray = MOTION ? shifted : ray;
       if (FLAT || !(kf & RTC_ROOT_IS_GROUP)) {
         if (!FLAT && V::kAnyHit && ((kf >> 8) & 1u) == 0u) continue;  // (a shadow trace: a shape that casts no shadow, see visit_leaf)
-        const Ray lr = xform_ray(R.inv, ray);  // Shape.intersect: ray.transform(_inverse_transform)
+        const Ray lr = xform_ray(R.inv, root_ray);  // Shape.intersect: ray.transform(_inverse_transform)
         if constexpr (V::kAnyHit && RTC_ROOM_EARLY_OUT) {
           if ((kf & RTC_ROOT_ROOM) && segment_stays_inside_cube(lr, vis.t_limit())) continue;
         }
@@ -1495,16 +1515,16 @@ __device__ __forceinline__ void trace(const DevScene& S, const RootRec* __restri
       vis.set_root(RTC_NO_LEAF);
       if constexpr (!FLAT) {
         if (CSG && (kf & RTC_ROOT_IS_CSG)) {
-          if constexpr (CSG) visit_csg(S, R.index, ray, vis, overflow);
+          if constexpr (CSG) visit_csg(S, R.index, root_ray, vis, overflow);
         } else {
 #if RTC_BVH8
           // (the three-wave kernel only: measured with and without it, dragons 4K 1.884 -> 1.859 ms and groups 0.890 -> 0.875
           // there; the two-wave kernel loses a per cent - teapot 0.256 -> 0.258, nefertiti 0.489 -> 0.495 -
           // profiles/r05/walk_experiments.md)
-          traverse_bvh8<CSG, V, TRAV>(S, R.geom, R.always_first, R.always_count, ray, vis, overflow, reinterpret_cast<uint2*>(lds_stack),
+          traverse_bvh8<CSG, V, TRAV>(S, R.geom, R.always_first, R.always_count, root_ray, vis, overflow, reinterpret_cast<uint2*>(lds_stack),
                                       (RTC_ROOT_NODE_IN_REC && TRAV == 2) ? reinterpret_cast<const uint4*>(R.inv) : nullptr);
 #else
-          traverse_bvh<CSG>(S, R.geom, ray, vis, overflow, lds_stack);
+          traverse_bvh<CSG>(S, R.geom, root_ray, vis, overflow, lds_stack);
 #endif
         }
       }
@@ -1589,6 +1609,17 @@ struct ClosestVisitor {
     if (group > 4u) merge_step<2>();
   }
 };
+
+// (MOTION) the closest hit and the root it lies under - a top-level object, a group or a csg unit -: the shading of a
+// moving root needs its displacement.  Found by ADL from trace() (unused where only the other kernels are compiled).
+struct MotionClosestVisitor : ClosestVisitor {
+  uint32_t hit_root = RTC_NO_LEAF, in_root = RTC_NO_LEAF;
+  __device__ __forceinline__ void entry(uint32_t l, uint32_t s, uint32_t m, double et, double eu, double ev) {
+    if (relevant(l, s, et)) hit_root = in_root;
+    ClosestVisitor::entry(l, s, m, et, eu, ev);
+  }
+};
+[[maybe_unused]] __device__ __forceinline__ void motion_root(MotionClosestVisitor& v, uint32_t r) { v.in_root = r; }
 
 // isShadowed (world.zig:126-154): any entry with 0 <= t < distance on a casts_shadow leaf.
 struct ShadowVisitor {
@@ -2285,13 +2316,18 @@ __device__ __forceinline__ Ray camera_sample(const DevCamera& cam, const DevSamp
 // ------------------------------------------------------------------------------------------
 // (AREA: World.lights may hold area lights - DevAreaLights, the area kernels' extra argument; compiled into those kernels only)
 // (MS: several camera samples per pixel - DevSampling, the sampling kernels' extra argument; compiled into those kernels only)
-template <bool LDS, bool CSG, int WORLD = 0, int WAVES = 2, bool COOP = false, bool BOX = true, bool AREA = false, bool MS = false>
+// (MOTION: top-level objects that move while the shutter is open - DevMotion, the motion kernels' extra argument; with MS
+// and AREA, compiled into those kernels only)
+template <bool LDS, bool CSG, int WORLD = 0, int WAVES = 2, bool COOP = false, bool BOX = true, bool AREA = false, bool MS = false,
+          bool MOTION = false>
 __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& cam, const DevPixelMap& map,
                                             const uint32_t max_depth, double* __restrict__ out,
                                             DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
-                                            const DevAreaLights& area = DevAreaLights{}, const DevSampling& smp = DevSampling{}) {
+                                            const DevAreaLights& area = DevAreaLights{}, const DevSampling& smp = DevSampling{},
+                                            const DevMotion& mo = DevMotion{}) {
   static_assert(!AREA || !COOP, "the area kernels run no cooperative iterations");
   static_assert(!MS || !COOP, "the sampling kernels run no cooperative iterations");
+  static_assert(!MOTION || (MS && AREA && WORLD == 0), "the motion kernels are the general area-sampling walk");
   RTC_PRIO_PHASE(RTC_PRIO_WORK);
 #ifndef RTC_PROFILE
   if (blockIdx.x == 0u) {  // the next launch's counters (see DevStats)
@@ -2835,17 +2871,28 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
     it_share += 2u;
     cur.remaining = min(cur.remaining, max_depth);  // termination never depends on a value read back from memory
     const Ray ray = cur.ray;
+    // (MOTION) the shutter time of the ray's camera sample, which its reflected, refracted and shadow rays share: the camera
+    // hash on its own axis, recomputed from the lane's pixel and sample word whenever a ray starts - a register for the
+    // length of the iteration, nothing in LDS
+    double tm = 0.0;
+    if constexpr (MOTION) {
+      uint32_t px, py;
+      map_pixel(map, out_index, px, py);
+      const unsigned long long p = static_cast<unsigned long long>(py) * cam.hsize + px;
+      tm = rtc_camera_jitter(smp.key, p, smp.sample_base + (*samp_word & RTC_SAMPLE_MASK), RTC_MOTION_AXIS);
+    }
 
     // ---- World.colorAt: intersect + hit (world.zig:111-115)
     RTC_STAMP(1);
 #ifdef RTC_PROFILE
     prof_iters += 1ull;
 #endif
-    ClosestVisitor hv;
+    using HitVisitor = typename std::conditional<MOTION, MotionClosestVisitor, ClosestVisitor>::type;
+    HitVisitor hv;
     RTC_COUNT(0);
     {
       RTC_HIST_BEGIN();
-      trace<CSG, WORLD, ClosestVisitor, TRAV, BOX>(S, recs, cull, ray, hv, it_overflow, trav_stack, member, stride);
+      trace<CSG, WORLD, HitVisitor, TRAV, BOX, MOTION>(S, recs, cull, ray, hv, it_overflow, trav_stack, member, stride, mo.disp, tm);
       RTC_HIST_END(0);
     }
     RTC_STAMP(2);
@@ -2902,7 +2949,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
       RTC_COUNT(4);
       {
         RTC_HIST_BEGIN();
-        trace<CSG, WORLD, BehindVisitor, TRAV, BOX>(S, recs, cull, ray, bv, it_overflow, trav_stack, member, stride);
+        trace<CSG, WORLD, BehindVisitor, TRAV, BOX, MOTION>(S, recs, cull, ray, bv, it_overflow, trav_stack, member, stride, mo.disp, tm);
         RTC_HIST_END(2);
       }
         RTC_STAMP(6);
@@ -2919,10 +2966,22 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
     }
     const double ptx = ray.ox + ray.dx * t, pty = ray.oy + ray.dy * t, ptz = ray.oz + ray.dz * t;  // ray.position
     const double ex = -ray.dx, ey = -ray.dy, ez = -ray.dz;                                          // eyev
+    // (MOTION) world space -> the hit object's space goes through the point where the hit root rests: p - tm * D, for the
+    // normal and for the pattern; a translation leaves the normal transform as it is
+    double spx = ptx, spy = pty, spz = ptz, mdx = 0.0, mdy = 0.0, mdz = 0.0;
+    if constexpr (MOTION) {
+      const double* __restrict__ D = mo.disp + 3ull * hv.hit_root;
+      mdx = D[0];
+      mdy = D[1];
+      mdz = D[2];
+      spx = ptx - tm * mdx;
+      spy = pty - tm * mdy;
+      spz = ptz - tm * mdz;
+    }
     // Shape.normalAt (shape.zig:338-350): local point, local normal, normalToWorld
-    const double lpx = row_pt(M + 0, ptx, pty, ptz);
-    const double lpy = row_pt(M + 4, ptx, pty, ptz);
-    const double lpz = row_pt(M + 8, ptx, pty, ptz);
+    const double lpx = row_pt(M + 0, spx, spy, spz);
+    const double lpy = row_pt(M + 4, spx, spy, spz);
+    const double lpz = row_pt(M + 8, spx, spy, spz);
     double lnx, lny, lnz;
     switch (SIMPLE ? min(kind, 2u) : kind) {
       case 0:  // sphere.zig:48-53
@@ -3024,9 +3083,15 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
         const DevPattern& P = pats[RTC_CHECK_INDEX(RTC_OOB_PATTERNS, mat.pattern, RTC_AVAIL(4))];
         color = {P.rgb[0], P.rgb[1], P.rgb[2]};
       } else {
-        const double opx = row_pt(M + 0, ovx, ovy, ovz);
-        const double opy = row_pt(M + 4, ovx, ovy, ovz);
-        const double opz = row_pt(M + 8, ovx, ovy, ovz);
+        double qx = ovx, qy = ovy, qz = ovz;  // (MOTION: over_point - tm * D)
+        if constexpr (MOTION) {
+          qx = ovx - tm * mdx;
+          qy = ovy - tm * mdy;
+          qz = ovz - tm * mdz;
+        }
+        const double opx = row_pt(M + 0, qx, qy, qz);
+        const double opy = row_pt(M + 4, qx, qy, qz);
+        const double opz = row_pt(M + 8, qx, qy, qz);
         color = pattern_at<CSG>(S, pats, RTC_CHECK_INDEX(RTC_OOB_PATTERNS, mat.pattern, RTC_AVAIL(4)), opx, opy, opz);
       }
       RTC_STAMP(12);
@@ -3149,7 +3214,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
                   ShadowVisitor sv;
                   sv.distance = distance;
                   Ray sray{ovx, ovy, ovz, lvx, lvy, lvz};
-                  trace<CSG, WORLD, ShadowVisitor, TRAV, BOX>(S, recs, cull, sray, sv, it_overflow, trav_stack, member, stride);
+                  trace<CSG, WORLD, ShadowVisitor, TRAV, BOX, MOTION>(S, recs, cull, sray, sv, it_overflow, trav_stack, member, stride, mo.disp, tm);
                   lit += sv.shadowed ? 0u : 1u;
                 }
               const double samples = static_cast<double>(n_samples);
@@ -3189,7 +3254,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
           RTC_COUNT(2);
           {
             RTC_HIST_BEGIN();
-            trace<CSG, WORLD, ShadowVisitor, TRAV, BOX>(S, recs, cull, sray, sv, it_overflow, trav_stack, s_member, s_stride);
+            trace<CSG, WORLD, ShadowVisitor, TRAV, BOX, MOTION>(S, recs, cull, sray, sv, it_overflow, trav_stack, s_member, s_stride, mo.disp, tm);
             RTC_HIST_END(1);
           }
                 RTC_STAMP(4);
@@ -3448,6 +3513,9 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
   }
 }
 
+// The kernels.  rtc_motion.hip includes this file with RTC_MOTION_TU defined and gets the motion kernels alone: a
+// translation unit of their own, so that this one - every other kernel - compiles in the time and to the code it did.
+#ifndef RTC_MOTION_TU
 extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
 rtc_render_kernel(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
                   double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats) {
@@ -4244,3 +4312,24 @@ rtc_pack_emit_kernel(const uint32_t* __restrict__ sorted, const uint32_t n_chunk
 #pragma unroll
   for (uint32_t q = 0; q < RTC_PACKET_ITEMS / 4u; ++q) row[q] = uint4{items[q * 4u], items[q * 4u + 1u], items[q * 4u + 2u], items[q * 4u + 3u]};
 }
+
+#else  // RTC_MOTION_TU
+
+// Motion blur (rtc_scene_set_motion): the area-sampling walk with the shutter time and the per-root shift compiled in
+// (DevMotion), for point-only and area light tables alike (a point-only table comes with zero rows: every light takes the
+// point path).  Every other kernel is compiled without it.
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_motion(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                         double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                         const DevAreaLights area, const DevSampling smp, const DevMotion mo) {
+  render_body<true, true, 0, 2, false, true, true, true, true>(S, cam, map, max_depth, out, stats, next_stats, area, smp, mo);
+}
+
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_motion_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                  double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                  const DevAreaLights area, const DevSampling smp, const DevMotion mo) {
+  render_body<false, true, 0, 2, false, true, true, true, true>(S, cam, map, max_depth, out, stats, next_stats, area, smp, mo);
+}
+
+#endif  // RTC_MOTION_TU

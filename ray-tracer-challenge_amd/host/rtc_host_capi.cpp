@@ -77,6 +77,22 @@ int rtch_scene_passes(void* h, uint32_t* out) {
   return guarded([&] { *out = static_cast<HostScene*>(h)->info.sampling.passes; });
 }
 
+int rtch_scene_motion(void* h, double* out, uint32_t n) {
+  return guarded([&] {
+    const HostScene* hs = static_cast<HostScene*>(h);
+    if (n != hs->desc.n_roots)
+      throw rtc::Error("InvalidArgument", "motion: n " + std::to_string(n) + ", the scene has " + std::to_string(hs->desc.n_roots) + " roots");
+    // (the description's roots are the World.objects entries in order, but for test shapes, which flattening drops)
+    uint32_t r = 0;
+    const auto& objects = hs->info.world.objects;
+    for (size_t i = 0; i < objects.size() && r < n; ++i) {
+      if (objects[i].kind == rtc::ShapeKind::TestShape) continue;
+      for (int k = 0; k < 3; ++k) out[3ull * r + k] = hs->info.motion[3 * i + k];
+      ++r;
+    }
+  });
+}
+
 // Camera of the scene file; width/height 0 keep the file's values, otherwise they replace
 // camera.width/height before Camera.new runs (the reference has no such override).
 int rtch_scene_camera(void* h, uint32_t width, uint32_t height, rtc_camera* out) {
@@ -150,6 +166,12 @@ int rtch_scene_render(void* h, uint32_t width, uint32_t height, uint32_t max_dep
       rtc_sampling smp;
       if (rtch_scene_sampling(h, &smp) != 0) smp = rtc_sampling{1u, 0u, 0.0, 1.0, 0u};
       st = rtc_scene_set_sampling(scene, &smp);
+      if (st == RTC_OK) {  // (the top-level objects' "motion"; all zero: static)
+        std::vector<double> disp(3ull * hs->desc.n_roots);
+        if (rtch_scene_motion(h, disp.data(), hs->desc.n_roots) != 0) throw rtc::Error("InvalidArgument", g_error);
+        const rtc_motion m{hs->desc.n_roots, disp.data()};
+        st = rtc_scene_set_motion(scene, &m);
+      }
       for (uint32_t p = 0; p < passes && st == RTC_OK; ++p) {
         if (p > 0u) st = rtc_scene_set_sample_pass(scene, p);
         if (st == RTC_OK) st = rtc_render(scene, &cam, max_depth, 0, 0, cam.hsize, cam.vsize, p == 0u ? rgb_out : frame.data());

@@ -443,7 +443,11 @@ Shape parseObject(const Value& object, const InheritedState& inherited, const De
                   const FileLoader& load_file_data, int depth = 0) {
   if (depth > 64) throw Error("StackOverflow", "shape definitions nest too deeply (cycle?)");
   requireObject(object, "object");
-  checkFields(object, {"type", "transform", "material", "casts-shadow"}, "object");
+  checkFields(object, {"type", "transform", "material", "casts-shadow", "motion"}, "object");
+  // (motion blur, DESIGN.md section 14: only a World.objects entry moves - parseScene reads its "motion" -, not a group's
+  // child, a csg operand or a shape definition's body)
+  if (depth != 0 && object.find("motion"))
+    throw Error("InvalidData", "object: \"motion\" is allowed on a top-level object only (not inside a group, a csg or a definition)");
 
   const Info info = inherit(object, inherited, load_file_data);
   std::optional<Material> material = info.material;
@@ -679,6 +683,16 @@ SceneInfo parseScene(const std::string& scene_json, const FileLoader& load_file_
       if (failed[i]) std::rethrow_exception(failed[i]);  // (the first object in the file's order that fails, as in the one loop)
       offsetShapeIds(built[i], reserveShapeIds(ids_drawn[i]));
       info.world.objects.push_back(std::move(built[i]));
+    }
+  }
+
+  // (not in the reference: an entry's optional "motion" [dx, dy, dz], its world-space displacement over the shutter)
+  info.motion.assign(3 * n_objects, 0.0);
+  for (size_t i = 0; i < n_objects; ++i) {
+    if (const Value* m = objects.arr[i].find("motion")) {
+      asVec3(*m, "motion", &info.motion[3 * i]);
+      for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(info.motion[3 * i + k])) throw Error("InvalidData", "motion: every component is finite");
     }
   }
 

@@ -32,6 +32,7 @@ struct SceneInfo {  // scene.zig:608-610
   Camera camera;
   World world;
   CameraSampling sampling;
+  std::vector<double> motion;  // [objects][3]: each top-level object's optional "motion" (DESIGN.md section 14), else 0
 };
 
 // scene.zig:612-661.  Throws rtc::Error whose .name is the Zig error name

@@ -4,6 +4,7 @@
     python tools/time_scenes.py [--set configs|mesh|misc|all] [--scenes a,b,..] [--size WxH] [--depth N]
                                 [--handles 3] [--settle 50] [--frames 20] [--option name=value ...] [--check]
                                 [--lights scene | area=N | grid=N] [--sampling grid[,aperture,focal]] [--passes P]
+                                [--motion R=dx,dy,dz ...]
 
   configs  the five BASELINE configs at their own sizes and depths (fresnel 300x300, cover / teapot 1080p, r&r 1080p
            depth 8, dragons 4K)                                                       [default]
@@ -23,7 +24,10 @@ sample.
 --passes P: the frames are sample pass P (rtc_scene_set_sample_pass; progressive rendering), and
 rtc_scene_accumulate_device of that pass (sums, sumsq, mean, rgba and noise) is timed on its own over as many calls, beside
 a device-to-device copy that moves as many bytes (it reads and writes half of them each); then a Progressive of 64 passes
-prints its noise after 4, 16 and 64."""
+prints its noise after 4, 16 and 64.
+--motion R=dx,dy,dz (repeatable): World.objects entry R moves by (dx, dy, dz) over the shutter (rtc_scene_set_motion; motion
+blur); prints primary rays per frame and ns per primary ray as well.  Option motion_kernels=1 times
+the motion kernels on the static scene."""
 import argparse, importlib, os, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, "tests"))
@@ -53,6 +57,7 @@ ap.add_argument("--label", default="")
 ap.add_argument("--lights", default="")
 ap.add_argument("--sampling", default="")
 ap.add_argument("--passes", type=int, default=-1)
+ap.add_argument("--motion", action="append", default=[])
 args = ap.parse_args()
 cases = SETS[args.set]
 if args.scenes:
@@ -127,6 +132,13 @@ for name, w, h, depth in cases:
             gpu.set_sampling(int(sv[0]), True, sv[1] if len(sv) > 1 else 0.0, sv[2] if len(sv) > 2 else 1.0)
         if args.passes >= 0:
             gpu.set_sample_pass(args.passes)
+        if args.motion:
+            import numpy as np
+            disp = np.zeros((hs.desc.n_roots, 3))
+            for m in args.motion:
+                r, d = m.split("=")
+                disp[int(r)] = [float(v) for v in d.split(",")]
+            gpu.set_motion(disp)
         for i in range(args.settle):
             gpu.render_device(cam, canvas.data_ptr(), depth, None, stream.cuda_stream)
         torch.cuda.synchronize()
@@ -151,7 +163,7 @@ for name, w, h, depth in cases:
     if delta is not None: line += f" maxdelta {delta:.2e}"
     if args.lights:
         line += f" shadow_traced {st['shadow_traced']} ns/shadow-ray {min(ts) * 1e6 / max(1, st['shadow_traced']):.3f}"
-    if args.sampling or args.option or args.passes >= 0:
+    if args.sampling or args.option or args.passes >= 0 or args.motion:
         line += f" primary {st['primary']} ns/primary-ray {min(ts) * 1e6 / max(1, st['primary']):.3f}"
     if acc:
         ms, copy_ms, nbytes = min(a[0] for a in acc), min(a[1] for a in acc), acc[0][2]

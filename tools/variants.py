@@ -34,7 +34,7 @@ for v in variants:
     out = os.path.join(REPO, "gpurun_out", "variants", name)
     os.makedirs(out, exist_ok=True)
     objs = []
-    for f in ("rtc_kernels", "rtc_capi"):
+    for f in ("rtc_kernels", "rtc_motion", "rtc_capi", "rtc_accum"):
         o = os.path.join(out, f + ".o")
         subprocess.check_call([HIPCC] + BASE + flags.split() + ["-c", "-o", o, os.path.join(PKG, "csrc", f + ".hip")], cwd=REPO)
         objs.append(o)
