@@ -370,6 +370,77 @@ typedef struct rtc_motion {
  * with its source's motion; rtc_render's band clones follow.  librtc_multi renders static scenes.
  */
 int rtc_scene_set_motion(rtc_scene *scene, const rtc_motion *motion);
+
+/* ---- adaptive sampling: progressive passes only for tiles still noisy ---- */
+#define RTC_ADAPTIVE_MAX_TILE 1024u
+
+/*
+ * The image is cut into tile_w x tile_h tiles, numbered row-major as rtc_render_tile_list_device numbers them; edge tiles
+ * hold only their pixels inside the image (n_t of them).  Round R = 0, 1, ... renders the active tiles at sample pass R
+ * (rtc_scene_set_sample_pass's keying) and adds them into whole-image sums; P_t counts tile t's passes.  After a round tile
+ * t stays active iff P_t < min_passes, or P_t < max_passes and noise_t > threshold, with
+ *   noise_t = sqrt((1/n_t) * sum over its pixels of max(0, sumsq - P_t * |mean|^2) / (3 (P_t - 1) P_t))
+ * (rtc_accum's noise restricted to the tile; +inf while P_t < 2).  A tile that stops is never touched again, so its
+ * passes are exactly 0 .. P_t - 1: tile t of an adaptive run is the progressive image after P_t passes, to the bit.
+ */
+typedef struct rtc_adaptive {
+  uint32_t tile_w, tile_h;  /* 1 .. RTC_ADAPTIVE_MAX_TILE                                               */
+  uint32_t min_passes;      /* >= 2 (the noise needs two passes)                                         */
+  uint32_t max_passes;      /* >= min_passes; max_passes * grid * grid <= RTC_SAMPLING_INDEX_LIMIT      */
+  double threshold;         /* finite, >= 0: absolute, in the units of rtc_accum's noise                */
+} rtc_adaptive;
+
+/*
+ * Caller-owned state of a run, device memory on the handle's device (N = hsize * vsize pixels, T tiles).  sum, sumsq,
+ * mean and rgba are as rtc_accum's, per tile at P_t passes (read and written only for tiles being accumulated).  `active`
+ * holds the n_active tiles still active, in ascending order; max_noise is the largest noise_t over all T tiles.
+ */
+typedef struct rtc_adaptive_state {
+  double *sum;            /* [N][3], required                                     */
+  double *sumsq;          /* [N], required                                        */
+  double *mean;           /* [N][3] or NULL                                       */
+  uint32_t *rgba;         /* [N] or NULL                                          */
+  uint32_t *tile_passes;  /* [T], required: P_t                                   */
+  double *tile_noise;     /* [T], required: noise_t                               */
+  uint32_t *active;       /* [T], required                                        */
+  uint32_t *n_active;     /* one, required                                        */
+  double *max_noise;      /* one or NULL                                          */
+  uint32_t round;         /* HOST field: the next round's R (begin: 0, step: + 1) */
+} rtc_adaptive_state;
+
+/* Zeroes every P_t, sets every noise_t (and max_noise) to +inf and makes every tile active; state->round = 0.
+ * Asynchronous on `hip_stream` (NULL: the handle's own stream) like rtc_scene_accumulate_device. */
+int rtc_scene_adaptive_begin_device(rtc_scene *scene, uint32_t hsize, uint32_t vsize, const rtc_adaptive *setting,
+                                    rtc_adaptive_state *state, void *hip_stream);
+
+/*
+ * No rendering: adds the compact tile frame d_frame[n_tiles][tile_h][tile_w][3] (as rtc_render_tile_list_device leaves
+ * it: region k is tile d_tiles[k]; d_tiles is device memory and holds distinct tiles) into the state's sums, one
+ * work-group per tile, with P_t = P_t + 1 (1: overwrite); writes noise_t in a fixed order, then
+ * applies the stopping rule to all T tiles and rebuilds `active`, n_active and max_noise by a scan.  The same inputs give
+ * the same bits; no atomics.  Asynchronous, ordered as rtc_scene_accumulate_device.
+ */
+int rtc_scene_adaptive_accumulate_device(rtc_scene *scene, uint32_t hsize, uint32_t vsize, const rtc_adaptive *setting,
+                                         const rtc_adaptive_state *state, const double *d_frame, const uint32_t *d_tiles,
+                                         uint32_t n_tiles, void *hip_stream);
+
+/*
+ * One round: reads back n_active and the active list (a small synchronising copy), renders that list at sample pass
+ * state->round into a frame buffer of the handle's (the handle's own sample pass is left as it is; its sampling, light
+ * jitter and motion apply), accumulates it and writes the new n_active to *n_active_out (0: the run is over, nothing
+ * was rendered).  Synchronous.
+ */
+int rtc_scene_adaptive_step(rtc_scene *scene, const rtc_camera *cam, uint32_t max_depth, const rtc_adaptive *setting,
+                            rtc_adaptive_state *state, uint32_t *n_active_out, void *hip_stream);
+
+/*
+ * A whole run with buffers of its own: begin, then rounds until no tile is active.  rgb_out [vsize][hsize][3] (host) gets
+ * the mean; tile_passes_out [T] (host, or NULL) every P_t.  Synchronous.
+ */
+int rtc_render_adaptive(rtc_scene *scene, const rtc_camera *cam, uint32_t max_depth, const rtc_adaptive *setting,
+                        double *rgb_out, uint32_t *tile_passes_out);
+/* (Every adaptive entry point checks all its arguments before the device is touched: RTC_ERR_INVALID_ARGUMENT, with
+ * nothing changed, otherwise.) */
 void rtc_scene_destroy(rtc_scene *scene);
 
 /*

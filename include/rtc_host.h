@@ -17,7 +17,8 @@
  *                        (rtc_scene_create_with_lights when the scene has an area light; the camera's
  *                        sampling, rtch_scene_sampling, through rtc_scene_set_sampling; its sample passes,
  *                        rtch_scene_passes, through rtc_scene_set_sample_pass, averaged on the host; the
- *                        top-level objects' motion, rtch_scene_motion, through rtc_scene_set_motion)
+ *                        top-level objects' motion, rtch_scene_motion, through rtc_scene_set_motion; its adaptive
+ *                        sampling, rtch_scene_adaptive, through rtc_render_adaptive)
  *
  * Every function that returns int returns 0 on success; otherwise rtch_last_error()
  * holds "<ZigStyleErrorName>: detail" (thread-local).
@@ -55,6 +56,10 @@ int rtch_scene_sampling(void *handle, rtc_sampling *out);
  * 0 .. n-1 (rtc_scene_set_sample_pass), sums them in pass order and divides by n once - the bits of
  * rtc_scene_accumulate_device's mean after n passes. */
 int rtch_scene_passes(void *handle, uint32_t *out);
+/* The camera's "sampling": {"adaptive": {"threshold": t, "min-passes": m, "tile": n or [w, h]}} of the scene file
+ * (adaptive sampling; min-passes 4 and tile 16 when absent, "passes" the maximum): *enabled = 1
+ * and the setting, or *enabled = 0 when the file has none.  rtch_scene_render then renders through rtc_render_adaptive. */
+int rtch_scene_adaptive(void *handle, int *enabled, rtc_adaptive *out);
 /* The top-level objects' "motion" of the scene file (motion blur): out[3 r .. 3 r + 2] = the
  * displacement of root r over the shutter, (0, 0, 0) for a root without one; n must be the description's n_roots.  Pass
  * it to rtc_scene_set_motion.  rtch_scene_render applies it. */

@@ -162,6 +162,32 @@ class Accum(C.Structure):
 RTC_SAMPLING_INDEX_LIMIT = 1 << 24   # (pass + 1) * grid * grid may not exceed it (include/rtc.h)
 
 
+class Adaptive(C.Structure):
+    """struct rtc_adaptive (include/rtc.h): adaptive sampling's setting - tile_w x tile_h tiles take sample passes until
+    min_passes, then until max_passes while their noise is above `threshold`."""
+
+    _fields_ = [("tile_w", C.c_uint32), ("tile_h", C.c_uint32), ("min_passes", C.c_uint32), ("max_passes", C.c_uint32),
+                ("threshold", C.c_double)]
+
+    @classmethod
+    def make(cls, threshold, max_passes, min_passes=4, tile=16):
+        tw, th = (tile, tile) if isinstance(tile, int) else tile
+        return cls(tw, th, min_passes, max_passes, threshold)
+
+    def to_dict(self):
+        return {"tile_w": self.tile_w, "tile_h": self.tile_h, "min_passes": self.min_passes, "max_passes": self.max_passes,
+                "threshold": self.threshold}
+
+
+class AdaptiveState(C.Structure):
+    """struct rtc_adaptive_state (include/rtc.h): a run's device buffers as integers (0: an optional one not wanted), and
+    `round`, a host field."""
+
+    _fields_ = [("sum", C.c_void_p), ("sumsq", C.c_void_p), ("mean", C.c_void_p), ("rgba", C.c_void_p), ("tile_passes", C.c_void_p),
+                ("tile_noise", C.c_void_p), ("active", C.c_void_p), ("n_active", C.c_void_p), ("max_noise", C.c_void_p),
+                ("round", C.c_uint32)]
+
+
 class Motion(C.Structure):
     """struct rtc_motion (include/rtc.h): a world-space displacement over the shutter per World.objects entry."""
 
@@ -175,12 +201,13 @@ RTC_SYMBOLS = ["rtc_scene_create", "rtc_scene_clone", "rtc_scene_destroy", "rtc_
                "rtc_scatter_tile_list_rgba8_device", "rtc_scene_synchronize", "rtc_get_stats", "rtc_last_error", "rtc_status_name",
                "rtc_grow_csg_lists", "rtc_canvas_register", "rtc_canvas_unregister", "rtc_rgba8_device",
                "rtc_scene_create_with_lights", "rtc_scene_set_light_seed", "rtc_scene_set_sampling",
-               "rtc_scene_set_sample_pass", "rtc_scene_accumulate_device", "rtc_scene_set_motion"]
+               "rtc_scene_set_sample_pass", "rtc_scene_accumulate_device", "rtc_scene_set_motion",
+               "rtc_scene_adaptive_begin_device", "rtc_scene_adaptive_accumulate_device", "rtc_scene_adaptive_step", "rtc_render_adaptive"]
 # (... and include/rtc_diag.h: diagnostics and tuning, for the tests, bench.py and tools/)
 RTC_DIAG_SYMBOLS = ["rtc_set_option", "rtc_last_kernel_name", "rtc_get_schedule", "rtc_get_chunk_times", "rtc_diag_build_tables", "rtc_diag_root_boxes"]
 HOST_SYMBOLS = ["rtch_last_error", "rtch_scene_load", "rtch_scene_free", "rtch_scene_desc", "rtch_scene_camera",
                 "rtch_camera_rotate", "rtch_camera_move", "rtch_camera_make", "rtch_canvas_ppm", "rtch_canvas_rgba8", "rtch_scene_render", "rtch_set_loader_threads",
-                "rtch_scene_lights", "rtch_scene_sampling", "rtch_scene_passes", "rtch_scene_motion"]
+                "rtch_scene_lights", "rtch_scene_sampling", "rtch_scene_passes", "rtch_scene_motion", "rtch_scene_adaptive"]
 
 MULTI_SYMBOLS = ["rtc_multi_create", "rtc_multi_destroy", "rtc_multi_render", "rtc_multi_render_rgba8", "rtc_multi_render_device", "rtc_multi_render_rgba8_device",
                  "rtc_multi_synchronize", "rtc_multi_stream", "rtc_multi_get_stats", "rtc_multi_balance", "rtc_multi_last_error"]
@@ -234,6 +261,13 @@ def hip_lib():
         lib.rtc_scene_set_sample_pass.argtypes = [C.c_void_p, C.c_uint32]
         lib.rtc_scene_accumulate_device.argtypes = [C.c_void_p, C.POINTER(Accum), C.c_void_p]
         lib.rtc_scene_set_motion.argtypes = [C.c_void_p, C.POINTER(Motion)]
+        lib.rtc_scene_adaptive_begin_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Adaptive), C.POINTER(AdaptiveState),
+                                                        C.c_void_p]
+        lib.rtc_scene_adaptive_accumulate_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Adaptive),
+                                                             C.POINTER(AdaptiveState), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.rtc_scene_adaptive_step.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.POINTER(Adaptive), C.POINTER(AdaptiveState),
+                                                C.POINTER(C.c_uint32), C.c_void_p]
+        lib.rtc_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.POINTER(Adaptive), C.c_void_p, C.c_void_p]
         lib.rtc_scene_destroy.argtypes = [C.c_void_p]
         lib.rtc_scene_destroy.restype = None
         lib.rtc_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32] + [C.c_uint32] * 4 + [C.c_void_p]
@@ -285,6 +319,7 @@ def host_lib():
         lib.rtch_scene_sampling.argtypes = [C.c_void_p, C.POINTER(Sampling)]
         lib.rtch_scene_passes.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         lib.rtch_scene_motion.argtypes = [C.c_void_p, _dp, C.c_uint32]
+        lib.rtch_scene_adaptive.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(Adaptive)]
         lib.rtch_scene_camera.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Camera)]
         lib.rtch_camera_rotate.argtypes = [C.c_void_p, C.c_double]
         lib.rtch_camera_move.argtypes = [C.c_void_p, C.c_double]
@@ -450,6 +485,13 @@ class HostScene:
         _check_host(host_lib().rtch_scene_motion(self._h, out.ctypes.data_as(_dp), n))
         return out
 
+    def adaptive(self):
+        """The camera's "sampling": {"adaptive": ...} of the scene file (rtch_scene_adaptive): an Adaptive whose max_passes
+        is "passes", or None when the file has none."""
+        on, a = C.c_int(), Adaptive()
+        _check_host(host_lib().rtch_scene_adaptive(self._h, C.byref(on), C.byref(a)))
+        return a if on.value else None
+
     def rotate_camera(self, angle):
         """Renderer.rotateCamera (lib.zig:166-178): orbit the camera around its target, about `up`."""
         _check_host(host_lib().rtch_camera_rotate(self._h, C.c_double(angle)))
@@ -533,6 +575,32 @@ class GpuScene:
     def accumulate_device(self, accum, stream=None):
         """rtc_scene_accumulate_device: an Accum, enqueued on `stream` (None: the handle's own) after this handle's renders."""
         _check_hip(hip_lib().rtc_scene_accumulate_device(self._s, C.byref(accum), stream))
+
+    def adaptive_begin(self, hsize, vsize, adaptive, state, stream=None):
+        """rtc_scene_adaptive_begin_device: every tile active at 0 passes (state.round = 0)."""
+        _check_hip(hip_lib().rtc_scene_adaptive_begin_device(self._s, hsize, vsize, C.byref(adaptive), C.byref(state), stream))
+
+    def adaptive_accumulate_device(self, hsize, vsize, adaptive, state, d_frame_ptr, d_tiles_ptr, n_tiles, stream=None):
+        """rtc_scene_adaptive_accumulate_device: a compact tile frame (region k: tile d_tiles[k]) into the run's sums, then
+        the stopping rule over every tile."""
+        _check_hip(hip_lib().rtc_scene_adaptive_accumulate_device(self._s, hsize, vsize, C.byref(adaptive), C.byref(state), d_frame_ptr,
+                                                                  d_tiles_ptr, n_tiles, stream))
+
+    def adaptive_step(self, cam, adaptive, state, max_depth=REFERENCE_DEPTH, stream=None):
+        """rtc_scene_adaptive_step: one round; returns the tiles still active after it."""
+        n = C.c_uint32()
+        _check_hip(hip_lib().rtc_scene_adaptive_step(self._s, C.byref(cam), max_depth, C.byref(adaptive), C.byref(state), C.byref(n),
+                                                     stream))
+        return n.value
+
+    def render_adaptive(self, cam, adaptive, max_depth=REFERENCE_DEPTH):
+        """rtc_render_adaptive: a whole run; returns ([h][w][3] f64 mean, [T] u32 passes per tile), host arrays."""
+        rgb = np.empty((cam.vsize, cam.hsize, 3), dtype=np.float64)
+        tx, ty = -(-cam.hsize // adaptive.tile_w), -(-cam.vsize // adaptive.tile_h)
+        passes = np.empty(tx * ty, dtype=np.uint32)
+        _check_hip(hip_lib().rtc_render_adaptive(self._s, C.byref(cam), max_depth, C.byref(adaptive), rgb.ctypes.data,
+                                                 passes.ctypes.data))
+        return rgb, passes
 
     def clone(self):
         """rtc_scene_clone: a handle of its own (stream, schedule, counters) on the same device copy of the scene - one
@@ -674,6 +742,70 @@ class Progressive:
         import torch
         torch.cuda.current_stream().wait_stream(self.stream)
         return self._rgba.view(self.cam.vsize, self.cam.hsize, 1).view(torch.uint8)
+
+
+class AdaptiveProgressive:
+    """Adaptive sampling on the device: each step() is one round of rtc_scene_adaptive_step - the tiles still noisy take
+    the next sample pass - into torch tensors on the scene's device, on a torch stream of its own (`stream`).  run() steps
+    until no tile is active; mean(), rgba8() and tile_passes() order the caller's current stream after the last round.
+    The scene's own sample pass is not changed."""
+
+    def __init__(self, gpu_scene, cam, max_depth=REFERENCE_DEPTH, adaptive=None):
+        import torch
+        if adaptive is None:
+            raise ValueError("AdaptiveProgressive: an Adaptive setting is required")
+        self.gpu, self.cam, self.max_depth, self.adaptive = gpu_scene, cam, max_depth, adaptive
+        shape, dev = (cam.vsize, cam.hsize), "cuda"
+        tx, ty = tile_grid(cam.hsize, cam.vsize, adaptive.tile_w, adaptive.tile_h)
+        n_tiles = tx * ty
+        self.sum = torch.empty(shape + (3,), dtype=torch.float64, device=dev)
+        self.sumsq = torch.empty(shape, dtype=torch.float64, device=dev)
+        self._mean = torch.empty(shape + (3,), dtype=torch.float64, device=dev)
+        self._rgba = torch.empty(shape, dtype=torch.int32, device=dev)
+        self._tile_passes = torch.empty(n_tiles, dtype=torch.int32, device=dev)
+        self.tile_noise = torch.empty(n_tiles, dtype=torch.float64, device=dev)
+        self.active = torch.empty(n_tiles, dtype=torch.int32, device=dev)
+        self.n_active = torch.empty(1, dtype=torch.int32, device=dev)
+        self.max_noise = torch.empty(1, dtype=torch.float64, device=dev)
+        self.state = AdaptiveState(self.sum.data_ptr(), self.sumsq.data_ptr(), self._mean.data_ptr(), self._rgba.data_ptr(),
+                                   self._tile_passes.data_ptr(), self.tile_noise.data_ptr(), self.active.data_ptr(),
+                                   self.n_active.data_ptr(), self.max_noise.data_ptr(), 0)
+        self.stream = torch.cuda.Stream()
+        self.stream.wait_stream(torch.cuda.current_stream())   # (the buffers were allocated on the current stream)
+        self.gpu.adaptive_begin(cam.hsize, cam.vsize, adaptive, self.state, self.stream.cuda_stream)
+        self.rounds = 0
+
+    def step(self):
+        """One round; returns the number of tiles still active after it (0: done, and nothing was rendered)."""
+        n = self.gpu.adaptive_step(self.cam, self.adaptive, self.state, self.max_depth, self.stream.cuda_stream)
+        self.rounds = self.state.round
+        return n
+
+    def run(self):
+        """Rounds until no tile is active; returns the number of rounds."""
+        while self.step():
+            pass
+        return self.rounds
+
+    def _wait(self):
+        import torch
+        torch.cuda.current_stream().wait_stream(self.stream)
+
+    def mean(self):
+        """[h][w][3] f64 on the device: each tile's mean after its passes."""
+        self._wait()
+        return self._mean
+
+    def rgba8(self):
+        """[h][w][4] u8 on the device: the clamp of mean()."""
+        import torch
+        self._wait()
+        return self._rgba.view(self.cam.vsize, self.cam.hsize, 1).view(torch.uint8)
+
+    def tile_passes(self):
+        """[T] int32 on the device: the passes each tile has taken."""
+        self._wait()
+        return self._tile_passes
 
 
 def canvas_register(array):

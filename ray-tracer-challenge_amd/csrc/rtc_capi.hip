@@ -104,6 +104,13 @@ __global__ void rtc_render_kernel_motion_bigworld(const DevScene S, const DevCam
 uint32_t rtcAccumBlocks(size_t n_pixels, bool wide);
 hipError_t rtcAccumLaunch(const double* frame, size_t n_pixels, uint32_t passes, double* sum, double* sumsq, double* mean,
                           uint32_t* rgba, double* noise, double* partials, hipStream_t stream);
+// Adaptive sampling's kernels (rtc_adaptive.hip): the enqueue of its begin, and of its accumulation and stopping rule.
+hipError_t rtcAdaptiveBeginLaunch(uint32_t n_tiles, uint32_t* tile_passes, double* tile_noise, uint32_t* active, uint32_t* n_active,
+                                  double* max_noise, hipStream_t stream);
+hipError_t rtcAdaptiveAccumLaunch(const double* frame, const uint32_t* list, uint32_t n_list, uint32_t hsize, uint32_t vsize,
+                                  uint32_t tile_w, uint32_t tile_h, uint32_t min_passes, uint32_t max_passes, double threshold,
+                                  double* sum, double* sumsq, double* mean, uint32_t* rgba, uint32_t* tile_passes, double* tile_noise,
+                                  uint32_t* active, uint32_t* n_active, double* max_noise, hipStream_t stream);
 extern "C" __global__ void rtc_estimate_kernel(const DevScene S, const DevCamera cam, const DevPixelMap map,
                                                uint32_t* __restrict__ chunk_cost, uint32_t* __restrict__ chunk_time,
                                                DevChunkShape* __restrict__ chunk_shape, DevPackState* __restrict__ state
@@ -2550,6 +2557,182 @@ int rtc_scene_set_motion(rtc_scene* s, const rtc_motion* motion) {
   return RTC_OK;
 }
 
+// ---- adaptive sampling
+// The setting's own fields, and the image's tile count (T < 2^31)
+static int checkAdaptive(const rtc_adaptive* a, uint32_t hsize, uint32_t vsize, uint32_t* n_tiles) {
+  if (!a) return fail(RTC_ERR_INVALID_ARGUMENT, "adaptive: null setting");
+  if (hsize == 0 || vsize == 0) return fail(RTC_ERR_INVALID_ARGUMENT, "adaptive: image %ux%u", hsize, vsize);
+  if (a->tile_w == 0 || a->tile_h == 0 || a->tile_w > RTC_ADAPTIVE_MAX_TILE || a->tile_h > RTC_ADAPTIVE_MAX_TILE)
+    return fail(RTC_ERR_INVALID_ARGUMENT, "adaptive: tile %ux%u (1 to %u)", a->tile_w, a->tile_h, RTC_ADAPTIVE_MAX_TILE);
+  if (a->min_passes < 2u) return fail(RTC_ERR_INVALID_ARGUMENT, "adaptive: min_passes %u (2 or more)", a->min_passes);
+  if (a->max_passes < a->min_passes)
+    return fail(RTC_ERR_INVALID_ARGUMENT, "adaptive: max_passes %u below min_passes %u", a->max_passes, a->min_passes);
+  if (!std::isfinite(a->threshold) || a->threshold < 0.0)
+    return fail(RTC_ERR_INVALID_ARGUMENT, "adaptive: threshold %g (finite, 0 or more)", a->threshold);
+  const uint64_t t = static_cast<uint64_t>((hsize + a->tile_w - 1u) / a->tile_w) * ((vsize + a->tile_h - 1u) / a->tile_h);
+  if (t >= (1ull << 31)) return fail(RTC_ERR_INVALID_ARGUMENT, "adaptive: %llu tiles", (unsigned long long)t);
+  *n_tiles = static_cast<uint32_t>(t);
+  return RTC_OK;
+}
+
+// ... and its passes within the camera hash's sample index at the handle's samples per pixel (checked last)
+static int checkAdaptivePasses(const rtc_adaptive* a, const rtc_scene* s) {
+  const uint64_t samples = s->sampling.samples;
+  if (static_cast<uint64_t>(a->max_passes) * samples > RTC_SAMPLING_INDEX_LIMIT)
+    return fail(RTC_ERR_INVALID_ARGUMENT, "adaptive: max_passes %u of %llu samples exceeds %u sample indices", a->max_passes,
+                (unsigned long long)samples, RTC_SAMPLING_INDEX_LIMIT);
+  return RTC_OK;
+}
+
+static int checkAdaptiveState(const rtc_adaptive_state* st) {
+  if (!st || !st->sum || !st->sumsq || !st->tile_passes || !st->tile_noise || !st->active || !st->n_active)
+    return fail(RTC_ERR_INVALID_ARGUMENT, "adaptive: null state or state buffer");
+  return RTC_OK;
+}
+
+// The stream a call runs on (NULL: the handle's own), ordered after the handle's last launch on any stream
+static int adaptiveStream(rtc_scene* s, void* hip_stream, hipStream_t* out) {
+  HIP_TRY(hipSetDevice(s->device));
+  if (!hip_stream) HIP_TRY(ensureOwnStream(s));
+  hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : s->stream;
+  if (s->last_stream != nullptr && stream != s->last_stream) HIP_TRY(hipStreamWaitEvent(stream, s->launch_done, 0));
+  *out = stream;
+  return RTC_OK;
+}
+
+int rtc_scene_adaptive_begin_device(rtc_scene* s, uint32_t hsize, uint32_t vsize, const rtc_adaptive* a, rtc_adaptive_state* st,
+                                    void* hip_stream) {
+  g_error.clear();
+  if (!s) return fail(RTC_ERR_INVALID_ARGUMENT, "adaptive: null scene");
+  if (const int e = checkAdaptiveState(st); e != RTC_OK) return e;
+  uint32_t n_tiles = 0;
+  if (const int e = checkAdaptive(a, hsize, vsize, &n_tiles); e != RTC_OK) return e;
+  if (const int e = checkAdaptivePasses(a, s); e != RTC_OK) return e;
+  hipStream_t stream;
+  if (const int e = adaptiveStream(s, hip_stream, &stream); e != RTC_OK) return e;
+  HIP_TRY(rtcAdaptiveBeginLaunch(n_tiles, st->tile_passes, st->tile_noise, st->active, st->n_active, st->max_noise, stream));
+  HIP_TRY(hipEventRecord(s->launch_done, stream));
+  s->last_stream = stream;
+  st->round = 0;
+  return RTC_OK;
+}
+
+int rtc_scene_adaptive_accumulate_device(rtc_scene* s, uint32_t hsize, uint32_t vsize, const rtc_adaptive* a,
+                                         const rtc_adaptive_state* st, const double* d_frame, const uint32_t* d_tiles, uint32_t n_list,
+                                         void* hip_stream) {
+  g_error.clear();
+  if (!s) return fail(RTC_ERR_INVALID_ARGUMENT, "adaptive: null scene");
+  if (const int e = checkAdaptiveState(st); e != RTC_OK) return e;
+  if (!d_frame || !d_tiles) return fail(RTC_ERR_INVALID_ARGUMENT, "adaptive: null frame or tile list");
+  uint32_t n_tiles = 0;
+  if (const int e = checkAdaptive(a, hsize, vsize, &n_tiles); e != RTC_OK) return e;
+  if (n_list == 0u || n_list > n_tiles) return fail(RTC_ERR_INVALID_ARGUMENT, "adaptive: %u listed tiles of %u", n_list, n_tiles);
+  if (const int e = checkAdaptivePasses(a, s); e != RTC_OK) return e;
+  hipStream_t stream;
+  if (const int e = adaptiveStream(s, hip_stream, &stream); e != RTC_OK) return e;
+  HIP_TRY(rtcAdaptiveAccumLaunch(d_frame, d_tiles, n_list, hsize, vsize, a->tile_w, a->tile_h, a->min_passes, a->max_passes, a->threshold,
+                                 st->sum, st->sumsq, st->mean, st->rgba, st->tile_passes, st->tile_noise, st->active, st->n_active,
+                                 st->max_noise, stream));
+  HIP_TRY(hipEventRecord(s->launch_done, stream));
+  s->last_stream = stream;
+  return RTC_OK;
+}
+
+int rtc_scene_adaptive_step(rtc_scene* s, const rtc_camera* cam, uint32_t max_depth, const rtc_adaptive* a, rtc_adaptive_state* st,
+                            uint32_t* n_active_out, void* hip_stream) {
+  g_error.clear();
+  if (!s || !n_active_out) return fail(RTC_ERR_INVALID_ARGUMENT, "adaptive: null argument");
+  if (const int e = checkAdaptiveState(st); e != RTC_OK) return e;
+  if (const int e = checkCamera(cam); e != RTC_OK) return e;
+  uint32_t n_tiles = 0;
+  if (const int e = checkAdaptive(a, cam->hsize, cam->vsize, &n_tiles); e != RTC_OK) return e;
+  if (const int e = checkAdaptivePasses(a, s); e != RTC_OK) return e;
+  hipStream_t stream;
+  if (const int e = adaptiveStream(s, hip_stream, &stream); e != RTC_OK) return e;
+  // the active list: its count, then its entries (the small synchronising copy of a round)
+  uint32_t n = 0;
+  HIP_TRY(hipMemcpyAsync(&n, st->n_active, sizeof n, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  if (n == 0u) {
+    *n_active_out = 0u;
+    return RTC_OK;
+  }
+  if (n > n_tiles || st->round >= a->max_passes)
+    return fail(RTC_ERR_INVALID_ARGUMENT, "adaptive: %u active tiles at round %u (%u tiles, max_passes %u): the state is not this run's", n,
+                st->round, n_tiles, a->max_passes);
+  s->h_adaptive_list.resize(n);
+  HIP_TRY(hipMemcpyAsync(s->h_adaptive_list.data(), st->active, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  const size_t need = static_cast<size_t>(n) * a->tile_w * a->tile_h * 3u;
+  if (need > s->adaptive_frame_capacity) {
+    HIP_TRY(handleIdle(s));  // (an earlier round may still be reading the old buffer)
+    if (s->d_adaptive_frame) (void)hipFree(s->d_adaptive_frame);
+    s->d_adaptive_frame = nullptr;
+    s->adaptive_frame_capacity = 0;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s->d_adaptive_frame), need * sizeof(double)));
+    s->adaptive_frame_capacity = need;
+  }
+  // round R at sample pass R; the handle's own pass is put back whatever happens
+  const uint32_t own_pass = s->sample_pass;
+  s->sample_pass = st->round;
+  applySampling(s, s->sampling_desc);
+  int rc = rtc_render_tile_list_device(s, cam, max_depth, a->tile_w, a->tile_h, s->h_adaptive_list.data(), n, s->d_adaptive_frame, stream);
+  s->sample_pass = own_pass;
+  applySampling(s, s->sampling_desc);
+  if (rc != RTC_OK) return rc;
+  rc = rtc_scene_adaptive_accumulate_device(s, cam->hsize, cam->vsize, a, st, s->d_adaptive_frame, s->d_tile_list, n, stream);
+  if (rc != RTC_OK) return rc;
+  st->round++;
+  HIP_TRY(hipMemcpyAsync(&n, st->n_active, sizeof n, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  *n_active_out = n;
+  return RTC_OK;
+}
+
+int rtc_render_adaptive(rtc_scene* s, const rtc_camera* cam, uint32_t max_depth, const rtc_adaptive* a, double* rgb_out,
+                        uint32_t* tile_passes_out) {
+  g_error.clear();
+  if (!s || !rgb_out) return fail(RTC_ERR_INVALID_ARGUMENT, "adaptive: null argument");
+  if (const int e = checkCamera(cam); e != RTC_OK) return e;
+  uint32_t n_tiles = 0;
+  if (const int e = checkAdaptive(a, cam->hsize, cam->vsize, &n_tiles); e != RTC_OK) return e;
+  if (const int e = checkAdaptivePasses(a, s); e != RTC_OK) return e;
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(ensureOwnStream(s));
+  // one allocation, carved at 16-byte boundaries: sum, sumsq, mean, tile_noise, tile_passes, active, n_active
+  const size_t n_px = static_cast<size_t>(cam->hsize) * cam->vsize;
+  auto up16 = [](size_t b) { return (b + 15u) & ~static_cast<size_t>(15u); };
+  const size_t b_sum = up16(n_px * 3u * sizeof(double)), b_sq = up16(n_px * sizeof(double)), b_noise = up16(n_tiles * sizeof(double)),
+               b_u32 = up16(n_tiles * sizeof(uint32_t));
+  char* base = nullptr;
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&base), 2u * b_sum + b_sq + b_noise + 2u * b_u32 + 16u));
+  struct Free {
+    rtc_scene* s;
+    char* p;
+    ~Free() {
+      (void)handleIdle(s);
+      (void)hipFree(p);
+    }
+  } release{s, base};
+  rtc_adaptive_state st{};
+  char* p = base;
+  st.sum = reinterpret_cast<double*>(p), p += b_sum;
+  st.sumsq = reinterpret_cast<double*>(p), p += b_sq;
+  st.mean = reinterpret_cast<double*>(p), p += b_sum;
+  st.tile_noise = reinterpret_cast<double*>(p), p += b_noise;
+  st.tile_passes = reinterpret_cast<uint32_t*>(p), p += b_u32;
+  st.active = reinterpret_cast<uint32_t*>(p), p += b_u32;
+  st.n_active = reinterpret_cast<uint32_t*>(p);
+  if (const int e = rtc_scene_adaptive_begin_device(s, cam->hsize, cam->vsize, a, &st, s->stream); e != RTC_OK) return e;
+  for (uint32_t n = 1; n != 0u;)
+    if (const int e = rtc_scene_adaptive_step(s, cam, max_depth, a, &st, &n, s->stream); e != RTC_OK) return e;
+  HIP_TRY(hipMemcpyAsync(rgb_out, st.mean, n_px * 3u * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  if (tile_passes_out)
+    HIP_TRY(hipMemcpyAsync(tile_passes_out, st.tile_passes, n_tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return RTC_OK;
+}
+
 int rtc_scene_clone(const rtc_scene* src, rtc_scene** out) {
   g_error.clear();
   if (!src || !out) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
@@ -2638,6 +2821,7 @@ void rtc_scene_destroy(rtc_scene* s) {
   if (s->d_ray_stack) (void)hipFree(s->d_ray_stack);
   if (s->d_csg_buf) (void)hipFree(s->d_csg_buf);
   if (s->d_accum_partials) (void)hipFree(s->d_accum_partials);
+  if (s->d_adaptive_frame) (void)hipFree(s->d_adaptive_frame);
   if (s->tab && !s->is_band) s->tab->handles.fetch_sub(1, std::memory_order_relaxed);
   delete s;
 }

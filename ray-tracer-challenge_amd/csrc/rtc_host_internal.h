@@ -170,6 +170,9 @@ struct rtc_scene {
   uint32_t sample_pass = 0;        // rtc_scene_set_sample_pass (a clone starts with its source's); not 0: the sampling kernels
   double* d_accum_partials = nullptr;  // rtc_scene_accumulate_device's per-block noise partials, and the total behind them
   size_t accum_partials_capacity = 0;  // doubles
+  double* d_adaptive_frame = nullptr;  // rtc_scene_adaptive_step's compact tile frame, and its size in doubles
+  size_t adaptive_frame_capacity = 0;
+  std::vector<uint32_t> h_adaptive_list;  // ... and the active list it read back
   uint32_t blocks_per_cu_ms_lds = 1, blocks_per_cu_ms_big = 1;  // resident work-groups of the world's sampling kernels
   std::shared_ptr<const MotionTables> motion;  // rtc_scene_set_motion; null: static (a clone starts with its source's)
   uint32_t blocks_per_cu_motion_lds = 1, blocks_per_cu_motion_big = 1;  // ... and of the motion kernels

@@ -3514,8 +3514,17 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
 }
 
 // The kernels.  rtc_motion.hip includes this file with RTC_MOTION_TU defined and gets the motion kernels alone: a
-// translation unit of their own, so that this one - every other kernel - compiles in the time and to the code it did.
-#ifndef RTC_MOTION_TU
+// translation unit of their own, so that this one compiles in the time and to the code it did.  rtc_kernels_ext.hip
+// includes it with RTC_EXT_TU defined: in the -DRTC_PROFILE diagnostic build, whose instrumented walk makes this unit's
+// compile about a third longer, it gets the csg / texture-map, flat and area-light kernels (rtc_render_kernel_ext to
+// rtc_render_kernel_area_bigworld below), so that neither unit takes the time of all of them.  The product build keeps
+// them here - that unit's code is the same as before to the byte - and its rtc_kernels_ext.o holds no kernel.
+#if (defined(RTC_EXT_TU) && defined(RTC_PROFILE)) || (!defined(RTC_MOTION_TU) && !defined(RTC_EXT_TU) && !defined(RTC_PROFILE))
+#define RTC_EXT_KERNELS_HERE 1
+#else
+#define RTC_EXT_KERNELS_HERE 0
+#endif
+#if !defined(RTC_MOTION_TU) && !defined(RTC_EXT_TU)
 extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
 rtc_render_kernel(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
                   double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats) {
@@ -3576,6 +3585,9 @@ rtc_render_kernel3(const DevScene S, const DevCamera cam, const DevPixelMap map,
 }
 #endif
 
+#endif  // !RTC_MOTION_TU && !RTC_EXT_TU
+
+#if RTC_EXT_KERNELS_HERE
 // The same two kernels with the csg and texture-map paths compiled in (template flag CSG), for scenes that
 // have csg nodes or texture maps.  Kept apart because the out-of-line calls cost the main loop ~150 spilled
 // VGPRs at every trace site (1.07 -> 1.38 ms on cover.json when csg was part of the only kernel).
@@ -3630,7 +3642,9 @@ rtc_render_kernel_area_bigworld(const DevScene S, const DevCamera cam, const Dev
                                 const DevAreaLights area) {
   render_body<false, true, 0, 2, false, true, true>(S, cam, map, max_depth, out, stats, next_stats, area);
 }
+#endif  // RTC_EXT_KERNELS_HERE
 
+#if !defined(RTC_MOTION_TU) && !defined(RTC_EXT_TU)
 // Several camera samples per pixel (rtc_scene_set_sampling: anti-aliasing, focal blur): the general walk with the csg and
 // texture-map paths compiled in, the sampling parameters as an extra argument (DevSampling) - every other kernel is
 // compiled without them.  Point lights (tables in LDS or in memory), and the area-light forms.
@@ -4313,7 +4327,7 @@ rtc_pack_emit_kernel(const uint32_t* __restrict__ sorted, const uint32_t n_chunk
   for (uint32_t q = 0; q < RTC_PACKET_ITEMS / 4u; ++q) row[q] = uint4{items[q * 4u], items[q * 4u + 1u], items[q * 4u + 2u], items[q * 4u + 3u]};
 }
 
-#else  // RTC_MOTION_TU
+#elif defined(RTC_MOTION_TU)
 
 // Motion blur (rtc_scene_set_motion): the area-sampling walk with the shutter time and the per-root shift compiled in
 // (DevMotion), for point-only and area light tables alike (a point-only table comes with zero rows: every light takes the

@@ -77,6 +77,14 @@ int rtch_scene_passes(void* h, uint32_t* out) {
   return guarded([&] { *out = static_cast<HostScene*>(h)->info.sampling.passes; });
 }
 
+int rtch_scene_adaptive(void* h, int* enabled, rtc_adaptive* out) {
+  return guarded([&] {
+    const rtc::CameraSampling& s = static_cast<HostScene*>(h)->info.sampling;
+    *enabled = s.adaptive ? 1 : 0;
+    *out = s.adaptive ? rtc_adaptive{s.tile_w, s.tile_h, s.min_passes, s.passes, s.threshold} : rtc_adaptive{0u, 0u, 0u, 0u, 0.0};
+  });
+}
+
 int rtch_scene_motion(void* h, double* out, uint32_t n) {
   return guarded([&] {
     const HostScene* hs = static_cast<HostScene*>(h);
@@ -172,13 +180,18 @@ int rtch_scene_render(void* h, uint32_t width, uint32_t height, uint32_t max_dep
         const rtc_motion m{hs->desc.n_roots, disp.data()};
         st = rtc_scene_set_motion(scene, &m);
       }
-      for (uint32_t p = 0; p < passes && st == RTC_OK; ++p) {
+      const rtc::CameraSampling& cs = hs->info.sampling;
+      if (cs.adaptive && st == RTC_OK) {  // (adaptive sampling: each tile's mean after its own passes, section 15)
+        const rtc_adaptive a{cs.tile_w, cs.tile_h, cs.min_passes, cs.passes, cs.threshold};
+        st = rtc_render_adaptive(scene, &cam, max_depth, &a, rgb_out, nullptr);
+      }
+      for (uint32_t p = 0; p < passes && st == RTC_OK && !cs.adaptive; ++p) {
         if (p > 0u) st = rtc_scene_set_sample_pass(scene, p);
         if (st == RTC_OK) st = rtc_render(scene, &cam, max_depth, 0, 0, cam.hsize, cam.vsize, p == 0u ? rgb_out : frame.data());
         if (st == RTC_OK && p > 0u)
           for (size_t i = 0; i < n; ++i) rgb_out[i] = rgb_out[i] + frame[i];
       }
-      if (st == RTC_OK && passes > 1u)
+      if (st == RTC_OK && passes > 1u && !cs.adaptive)
         for (size_t i = 0; i < n; ++i) rgb_out[i] = rgb_out[i] / static_cast<double>(passes);
       rtc_scene_destroy(scene);
     }

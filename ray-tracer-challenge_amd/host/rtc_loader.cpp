@@ -616,7 +616,7 @@ SceneInfo parseScene(const std::string& scene_json, const FileLoader& load_file_
   info.camera.setTransform(Matrix4::viewTransform(from, to, up));
   if (const Value* smp = cam.find("sampling")) {  // (not in the reference: anti-aliasing and focal blur, every key optional)
     requireObject(*smp, "sampling");
-    checkFields(*smp, {"grid", "jitter", "aperture", "focal-distance", "seed", "passes"}, "sampling");
+    checkFields(*smp, {"grid", "jitter", "aperture", "focal-distance", "seed", "passes", "adaptive"}, "sampling");
     CameraSampling& s = info.sampling;
     if (const Value* v = smp->find("grid")) {
       const size_t g = asUsize(*v, "grid");
@@ -640,6 +640,35 @@ SceneInfo parseScene(const std::string& scene_json, const FileLoader& load_file_
       const size_t most = RTC_SAMPLING_INDEX_LIMIT / (static_cast<size_t>(s.grid) * s.grid);
       if (n < 1 || n > most) throw Error("InvalidData", "sampling: passes is 1 to " + std::to_string(most) + " at grid " + std::to_string(s.grid));
       s.passes = static_cast<uint32_t>(n);
+    }
+    if (const Value* ad = smp->find("adaptive")) {  // (adaptive sampling, DESIGN.md section 15: "passes" is the maximum)
+      requireObject(*ad, "adaptive");
+      checkFields(*ad, {"threshold", "min-passes", "tile"}, "sampling.adaptive");
+      s.adaptive = true;
+      s.threshold = asFloat(requireField(*ad, "threshold", "sampling.adaptive"), "threshold");
+      if (!std::isfinite(s.threshold) || s.threshold < 0.0) throw Error("InvalidData", "sampling.adaptive: threshold is finite and at least 0");
+      if (const Value* v = ad->find("min-passes")) {
+        const size_t n = asUsize(*v, "min-passes");
+        if (n < 2 || n > s.passes)
+          throw Error("InvalidData", "sampling.adaptive: min-passes is 2 to passes (" + std::to_string(s.passes) + ")");
+        s.min_passes = static_cast<uint32_t>(n);
+      }
+      if (s.passes < s.min_passes)
+        throw Error("InvalidData", "sampling.adaptive: passes (" + std::to_string(s.passes) + ") is below min-passes (" +
+                                       std::to_string(s.min_passes) + ")");
+      if (const Value* v = ad->find("tile")) {
+        size_t wh[2];
+        if (v->type == Value::Array) {
+          if (v->arr.size() != 2) throw Error("LengthMismatch", "tile");
+          for (int i = 0; i < 2; ++i) wh[i] = asUsize(v->arr[i], "tile");
+        } else {
+          wh[0] = wh[1] = asUsize(*v, "tile");
+        }
+        for (size_t d : wh)
+          if (d < 1 || d > RTC_ADAPTIVE_MAX_TILE) throw Error("InvalidData", "sampling.adaptive: tile is 1 to " + std::to_string(RTC_ADAPTIVE_MAX_TILE));
+        s.tile_w = static_cast<uint32_t>(wh[0]);
+        s.tile_h = static_cast<uint32_t>(wh[1]);
+      }
     }
   }
 

@@ -26,6 +26,11 @@ struct CameraSampling {
   double focal_distance = 1.0;  // (absent with an aperture: |to - from|)
   uint64_t seed = 0;
   uint32_t passes = 1;  // sample passes rtch_scene_render averages (rtc_scene_set_sample_pass 0 .. passes-1; section 13)
+  // "adaptive" (section 15): passes only for tiles still noisy; "passes" is then the most a tile takes
+  bool adaptive = false;
+  double threshold = 0.0;
+  uint32_t min_passes = 4;
+  uint32_t tile_w = 16, tile_h = 16;
 };
 
 struct SceneInfo {  // scene.zig:608-610

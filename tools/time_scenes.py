@@ -4,7 +4,7 @@
     python tools/time_scenes.py [--set configs|mesh|misc|all] [--scenes a,b,..] [--size WxH] [--depth N]
                                 [--handles 3] [--settle 50] [--frames 20] [--option name=value ...] [--check]
                                 [--lights scene | area=N | grid=N] [--sampling grid[,aperture,focal]] [--passes P]
-                                [--motion R=dx,dy,dz ...]
+                                [--motion R=dx,dy,dz ...] [--adaptive threshold[,min,tile] [--max-passes N]]
 
   configs  the five BASELINE configs at their own sizes and depths (fresnel 300x300, cover / teapot 1080p, r&r 1080p
            depth 8, dragons 4K)                                                       [default]
@@ -27,8 +27,15 @@ a device-to-device copy that moves as many bytes (it reads and writes half of th
 prints its noise after 4, 16 and 64.
 --motion R=dx,dy,dz (repeatable): World.objects entry R moves by (dx, dy, dz) over the shutter (rtc_scene_set_motion; motion
 blur); prints primary rays per frame and ns per primary ray as well.  Option motion_kernels=1 times
-the motion kernels on the static scene."""
+the motion kernels on the static scene.
+--adaptive threshold[,min,tile]: adaptive sampling at up to --max-passes (64) passes, min passes 4 and
+16 x 16 tiles by default, with the --sampling of the frames: prints the rounds and tile-passes of a run against
+T * max_passes, its time (a second run, end to end on the host) against uniform progressive passes (render_device +
+rtc_scene_accumulate_device) up to the first pass count at which the largest tile noise is as low, the fused accumulation
+of a full tile list against rtc_scene_accumulate_device on the same pixels, and per round the read-back of the active list
+and the cost of a new list's re-measured schedule (its first render against the same list rendered again)."""
 import argparse, importlib, os, sys
+import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, "tests"))
 import torch
@@ -58,6 +65,8 @@ ap.add_argument("--lights", default="")
 ap.add_argument("--sampling", default="")
 ap.add_argument("--passes", type=int, default=-1)
 ap.add_argument("--motion", action="append", default=[])
+ap.add_argument("--adaptive", default="")
+ap.add_argument("--max-passes", type=int, default=64)
 args = ap.parse_args()
 cases = SETS[args.set]
 if args.scenes:
@@ -116,6 +125,95 @@ def time_accumulate(gpu, frame, n, passes):
         e1.record(stream); torch.cuda.synchronize()
         return e0.elapsed_time(e1) / reps
     return timed(lambda: gpu.accumulate_device(a, stream.cuda_stream)), timed(lambda: dst.copy_(src)), nbytes
+
+
+def events_ms(fn, reps):
+    fn(); torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(stream)
+    for _ in range(reps): fn()
+    e1.record(stream); torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def time_adaptive(hs, table, cam, depth):
+    """-> the --adaptive line (see the module's doc)"""
+    import time
+    f = args.adaptive.split(",")
+    a = rtc.Adaptive.make(float(f[0]), args.max_passes, int(f[1]) if len(f) > 1 else 4, int(f[2]) if len(f) > 2 else 16)
+    gpu = rtc.GpuScene(hs.desc, lights=table)
+    if args.sampling:
+        sv = [float(v) for v in args.sampling.split(",")]
+        gpu.set_sampling(int(sv[0]), True, sv[1] if len(sv) > 1 else 0.0, sv[2] if len(sv) > 2 else 1.0)
+    T = rtc.tile_grid(cam.hsize, cam.vsize, a.tile_w, a.tile_h)
+    T = T[0] * T[1]
+    rtc.AdaptiveProgressive(gpu, cam, depth, a).run()          # (warm-up: code objects, buffers)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    run = rtc.AdaptiveProgressive(gpu, cam, depth, a)
+    rounds = run.run()
+    torch.cuda.synchronize()
+    t_adaptive = (time.perf_counter() - t0) * 1e3
+    passes = run.tile_passes().cpu().numpy()
+    reached = float(run.max_noise.cpu()[0])
+    # uniform passes: every tile every round (threshold 0) gives the largest tile noise after each pass count
+    full = rtc.AdaptiveProgressive(gpu, cam, depth, rtc.Adaptive(a.tile_w, a.tile_h, 2, a.max_passes, 0.0))
+    uniform_p = None
+    for p in range(1, a.max_passes + 1):
+        full.step()
+        if p >= a.min_passes and float(full.max_noise.cpu()[0]) <= reached:
+            uniform_p = p
+            break
+    line = (f" | adaptive thr {a.threshold:g} min {a.min_passes} max {a.max_passes} tile {a.tile_w}x{a.tile_h}: {rounds} rounds,"
+            f" {int(passes.sum())} tile-passes of {T * a.max_passes} ({passes.sum() / (T * a.max_passes):.3f}),"
+            f" passes min/mean/max {passes.min()}/{passes.mean():.2f}/{passes.max()}, max tile noise {reached:.3e},"
+            f" {t_adaptive:.2f} ms")
+    if uniform_p is None:
+        line += f"; uniform passes do not reach it within {a.max_passes}"
+    else:
+        prog = rtc.Progressive(gpu, cam, depth)
+        for _ in range(uniform_p): prog.step()                  # (warm-up)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        prog = rtc.Progressive(gpu, cam, depth)
+        for _ in range(uniform_p): prog.step()
+        torch.cuda.synchronize()
+        t_uniform = (time.perf_counter() - t0) * 1e3
+        line += f"; uniform {uniform_p} passes {t_uniform:.2f} ms ({t_uniform / t_adaptive:.2f}x the adaptive run)"
+    # the fused accumulation on a full list against rtc_scene_accumulate_device, same pixels
+    n = cam.hsize * cam.vsize
+    st = full.state
+    tiles = torch.arange(T, dtype=torch.int32, device="cuda")
+    frame = torch.rand(T * a.tile_w * a.tile_h * 3, dtype=torch.float64, device="cuda")
+    t_fused = events_ms(lambda: gpu.adaptive_accumulate_device(cam.hsize, cam.vsize, rtc.Adaptive(a.tile_w, a.tile_h, 2, 1 << 16, 0.0),
+                                                               st, frame.data_ptr(), tiles.data_ptr(), T, stream.cuda_stream), 50)
+    t_scan = events_ms(lambda: gpu.adaptive_accumulate_device(cam.hsize, cam.vsize, rtc.Adaptive(a.tile_w, a.tile_h, 2, 1 << 16, 0.0),
+                                                              st, frame.data_ptr(), tiles.data_ptr(), 1, stream.cuda_stream), 50)
+    t_acc = time_accumulate(gpu, frame, n, 3)[0]
+    line += (f" | full-list accumulate + scan {t_fused:.4f} ms (one tile + scan {t_scan:.4f} ms), rtc_scene_accumulate_device"
+             f" {t_acc:.4f} ms ({t_fused / t_acc:.2f}x)")
+    # per round: the read-back of the active list, and a new list's re-measured schedule
+    half = np.arange(0, T, 2, dtype=np.uint32)
+    other = np.arange(1, T, 2, dtype=np.uint32)
+    buf = torch.empty(T * a.tile_w * a.tile_h * 3, dtype=torch.float64, device="cuda")
+    render = lambda l: gpu.render_tile_list_device(cam, buf.data_ptr(), a.tile_w, a.tile_h, l, depth, stream.cuda_stream)
+    firsts, agains = [], []
+    for _ in range(5):
+        render(other); torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream); render(half); e1.record(stream); torch.cuda.synchronize()
+        firsts.append(e0.elapsed_time(e1))
+        agains.append(events_ms(lambda: render(half), 5))
+    t_first, t_again = min(firsts), min(agains)
+    t0 = time.perf_counter()
+    for _ in range(50):
+        m = int(full.n_active.cpu()[0]) or T
+        full.active[:m].cpu()
+    t_read = (time.perf_counter() - t0) * 1e3 / 50
+    line += (f" | half the tiles: new list {t_first:.3f} ms, same list {t_again:.3f} ms (schedule +{t_first - t_again:.3f} ms,"
+             f" {100 * (t_first / t_again - 1):.0f}%), read-back of n_active and the list {t_read:.3f} ms")
+    gpu.close()
+    return line
 
 
 stream = torch.cuda.Stream(); torch.cuda.set_stream(stream)
@@ -179,5 +277,7 @@ for name, w, h, depth in cases:
             if i in (4, 16, 64): noise[i] = v
         line += " | noise " + " ".join(f"{k}:{v:.3e}" for k, v in noise.items())
         gpu.close()
+    if args.adaptive:
+        line += time_adaptive(hs, table, cam, depth)
     out.append(line)
     print((args.label + " " if args.label else "") + line, flush=True)
