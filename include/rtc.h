@@ -232,7 +232,7 @@ typedef struct rtc_camera {
 typedef struct rtc_stats {
   uint64_t primary;       /* camera.zig:117-118: one per pixel                                  */
   uint64_t secondary;     /* reflectedColor + refractedColor calls that recurse (world.zig:164,186) */
-  uint64_t shadow_calls;  /* isShadowed calls the reference makes (world.zig:92)                */
+  uint64_t shadow_calls;  /* isShadowed calls the reference makes (world.zig:92); a spot light makes no isShadowed call at a point outside its cone */
   uint64_t shadow_traced; /* shadow rays this library actually traced (skips provably inert ones) */
   uint64_t overflow;      /* lanes that overflowed a stack / csg list (must be 0)                */
 } rtc_stats;
@@ -370,6 +370,36 @@ typedef struct rtc_motion {
  * with its source's motion; rtc_render's band clones follow.  librtc_multi renders static scenes.
  */
 int rtc_scene_set_motion(rtc_scene *scene, const rtc_motion *motion);
+
+/* ---- spot lights: point lights that shine into a cone with a soft edge ---- */
+/*
+ * Light i (World.lights entry i, as the handle's light table holds it: point and area rows alike) with cone[i] == 1 is a
+ * point light with the unit axis a = axis[3 i .. 3 i + 2] / sqrt((x * x + y * y) + z * z) (tuple.zig's normalize) and
+ * -1 <= cos_outer[i] <= cos_inner[i] <= 1.  At a shading point with lv = point_to_light (v / distance):
+ *   c = -((lv.x * a.x + lv.y * a.y) + lv.z * a.z)
+ *   f = 1 if c >= cos_inner; else 0 if c <= cos_outer; else s = (c - cos_outer) / (cos_inner - cos_outer),
+ *       f = (s * s) * (3.0 - 2.0 * s)
+ * f == 0: the light gives `ambient` alone, and isShadowed is not called (no shadow_calls, no shadow ray).  Otherwise
+ * isShadowed runs as before, and an unshadowed point's diffuse and specular colours are each scaled by f once formed:
+ * (ambient + diffuse * f) + specular * f.  f == 1 gives the plain point light's bits; ambient is never scaled.
+ * cone[i] == 0: the light as it is (the entry's other fields are not read).
+ */
+typedef struct rtc_spot {
+  uint32_t n_lights;        /* the handle's light count                        */
+  const uint8_t *cone;      /* [n_lights]: 1 a cone, 0 none                    */
+  const double *axis;       /* [n_lights][3]: the cone's axis, any length > 0 */
+  const double *cos_inner;  /* [n_lights]: full light inside                  */
+  const double *cos_outer;  /* [n_lights]: no light outside                   */
+} rtc_spot;
+
+/*
+ * This handle's spot lights for every render entry point (NULL, or every flag 0: no cones, the handle's old kernels).
+ * Validated before anything changes: RTC_ERR_INVALID_ARGUMENT for a flag other than 0 or 1, a value that is not finite,
+ * an axis of zero or non-finite magnitude, a cosine outside [-1, 1], cos_outer > cos_inner, n_lights other than the
+ * handle's light count, or a cone on an area light.  A clone starts with its source's spots; rtc_render's band clones
+ * follow.  librtc_multi renders without cones.
+ */
+int rtc_scene_set_spots(rtc_scene *scene, const rtc_spot *spots);
 
 /* ---- adaptive sampling: progressive passes only for tiles still noisy ---- */
 #define RTC_ADAPTIVE_MAX_TILE 1024u

@@ -31,7 +31,9 @@ extern "C" {
  * rejects by world boxes - 1 - or by bounding spheres - 0; < 0: boxes if it has more cubes than spheres),
  * "sampling_kernels" (!= 0: the camera-sampling kernels even with the default sampling - one centred ray per pixel -, so
  * that their one-sample images can be held to the other kernels'), "motion_kernels" (!= 0: the motion kernels even on a
- * static handle, with every displacement zero, so that their images can be held to the sampling kernels').
+ * static handle, with every displacement zero, so that their images can be held to the sampling kernels'), "spot_kernels"
+ * (!= 0: the spot kernels even on a handle without cones, every flag zero, so that their images can be held to the
+ * motion kernels').
  * RTC_ERR_INVALID_ARGUMENT for a name the library does not know.
  * (The library reads no environment variables.)
  */

@@ -18,7 +18,8 @@
  *                        sampling, rtch_scene_sampling, through rtc_scene_set_sampling; its sample passes,
  *                        rtch_scene_passes, through rtc_scene_set_sample_pass, averaged on the host; the
  *                        top-level objects' motion, rtch_scene_motion, through rtc_scene_set_motion; its adaptive
- *                        sampling, rtch_scene_adaptive, through rtc_render_adaptive)
+ *                        sampling, rtch_scene_adaptive, through rtc_render_adaptive; its spot lights,
+ *                        rtch_scene_spots, through rtc_scene_set_spots)
  *
  * Every function that returns int returns 0 on success; otherwise rtch_last_error()
  * holds "<ZigStyleErrorName>: detail" (thread-local).
@@ -64,6 +65,11 @@ int rtch_scene_adaptive(void *handle, int *enabled, rtc_adaptive *out);
  * displacement of root r over the shutter, (0, 0, 0) for a root without one; n must be the description's n_roots.  Pass
  * it to rtc_scene_set_motion.  rtch_scene_render applies it. */
 int rtch_scene_motion(void *handle, double *out, uint32_t n);
+/* The scene file's "spot-light" entries (spot lights), in World.lights order: cone[i] 1 with the
+ * axis ("to" - position, or "direction") and the cosines of the half-angles (std::cos of "inner-angle", "outer-angle"),
+ * cone[i] 0 for every other light; n must be the light table's n_lights.  Pass them to rtc_scene_set_spots.
+ * rtch_scene_render applies them; rtch_scene_lights reports a spot as the point light it is. */
+int rtch_scene_spots(void *handle, uint8_t *cone, double *axis, double *cos_inner, double *cos_outer, uint32_t n);
 int rtch_scene_camera(void *handle, uint32_t width, uint32_t height, rtc_camera *out);
 int rtch_camera_rotate(void *handle, double angle);
 int rtch_camera_move(void *handle, double distance);

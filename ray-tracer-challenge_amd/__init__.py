@@ -194,6 +194,28 @@ class Motion(C.Structure):
     _fields_ = [("n_roots", C.c_uint32), ("displacement", C.POINTER(C.c_double))]
 
 
+class Spot(C.Structure):
+    """struct rtc_spot (include/rtc.h): a cone per World.lights entry (flag 0: the light as it is)."""
+
+    _fields_ = [("n_lights", C.c_uint32), ("cone", C.POINTER(C.c_uint8)), ("axis", C.POINTER(C.c_double)),
+                ("cos_inner", C.POINTER(C.c_double)), ("cos_outer", C.POINTER(C.c_double))]
+
+
+def spot_struct(spots):
+    """(Spot, the arrays it points into) of a dict of "cone", "axis", "cos_inner", "cos_outer" (GpuScene.set_spots); the
+    arrays must outlive the struct's use."""
+    cone = np.ascontiguousarray(spots["cone"], dtype=np.uint8)
+    axis = np.ascontiguousarray(spots["axis"], dtype=np.float64)
+    ci = np.ascontiguousarray(spots["cos_inner"], dtype=np.float64)
+    co = np.ascontiguousarray(spots["cos_outer"], dtype=np.float64)
+    n = cone.shape[0]
+    if cone.ndim != 1 or axis.shape != (n, 3) or ci.shape != (n,) or co.shape != (n,):
+        raise ValueError(f"spots: cone {cone.shape}, axis {axis.shape}, cos_inner {ci.shape}, cos_outer {co.shape}")
+    sp = Spot(n, cone.ctypes.data_as(C.POINTER(C.c_uint8)), axis.ctypes.data_as(C.POINTER(C.c_double)),
+              ci.ctypes.data_as(C.POINTER(C.c_double)), co.ctypes.data_as(C.POINTER(C.c_double)))
+    return sp, (cone, axis, ci, co)
+
+
 # (include/rtc.h: what a host binds ...)
 RTC_SYMBOLS = ["rtc_scene_create", "rtc_scene_clone", "rtc_scene_destroy", "rtc_render", "rtc_render_rgba8", "rtc_render_device",
                "rtc_render_tiles_device", "rtc_assemble_tiles_device", "rtc_render_tile_list_device", "rtc_get_tile_costs",
@@ -202,12 +224,14 @@ RTC_SYMBOLS = ["rtc_scene_create", "rtc_scene_clone", "rtc_scene_destroy", "rtc_
                "rtc_grow_csg_lists", "rtc_canvas_register", "rtc_canvas_unregister", "rtc_rgba8_device",
                "rtc_scene_create_with_lights", "rtc_scene_set_light_seed", "rtc_scene_set_sampling",
                "rtc_scene_set_sample_pass", "rtc_scene_accumulate_device", "rtc_scene_set_motion",
-               "rtc_scene_adaptive_begin_device", "rtc_scene_adaptive_accumulate_device", "rtc_scene_adaptive_step", "rtc_render_adaptive"]
+               "rtc_scene_adaptive_begin_device", "rtc_scene_adaptive_accumulate_device", "rtc_scene_adaptive_step", "rtc_render_adaptive",
+               "rtc_scene_set_spots"]
 # (... and include/rtc_diag.h: diagnostics and tuning, for the tests, bench.py and tools/)
 RTC_DIAG_SYMBOLS = ["rtc_set_option", "rtc_last_kernel_name", "rtc_get_schedule", "rtc_get_chunk_times", "rtc_diag_build_tables", "rtc_diag_root_boxes"]
 HOST_SYMBOLS = ["rtch_last_error", "rtch_scene_load", "rtch_scene_free", "rtch_scene_desc", "rtch_scene_camera",
                 "rtch_camera_rotate", "rtch_camera_move", "rtch_camera_make", "rtch_canvas_ppm", "rtch_canvas_rgba8", "rtch_scene_render", "rtch_set_loader_threads",
-                "rtch_scene_lights", "rtch_scene_sampling", "rtch_scene_passes", "rtch_scene_motion", "rtch_scene_adaptive"]
+                "rtch_scene_lights", "rtch_scene_sampling", "rtch_scene_passes", "rtch_scene_motion", "rtch_scene_adaptive",
+                "rtch_scene_spots"]
 
 MULTI_SYMBOLS = ["rtc_multi_create", "rtc_multi_destroy", "rtc_multi_render", "rtc_multi_render_rgba8", "rtc_multi_render_device", "rtc_multi_render_rgba8_device",
                  "rtc_multi_synchronize", "rtc_multi_stream", "rtc_multi_get_stats", "rtc_multi_balance", "rtc_multi_last_error"]
@@ -267,6 +291,7 @@ def hip_lib():
                                                              C.POINTER(AdaptiveState), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         lib.rtc_scene_adaptive_step.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.POINTER(Adaptive), C.POINTER(AdaptiveState),
                                                 C.POINTER(C.c_uint32), C.c_void_p]
+        lib.rtc_scene_set_spots.argtypes = [C.c_void_p, C.POINTER(Spot)]
         lib.rtc_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.POINTER(Adaptive), C.c_void_p, C.c_void_p]
         lib.rtc_scene_destroy.argtypes = [C.c_void_p]
         lib.rtc_scene_destroy.restype = None
@@ -319,6 +344,7 @@ def host_lib():
         lib.rtch_scene_sampling.argtypes = [C.c_void_p, C.POINTER(Sampling)]
         lib.rtch_scene_passes.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         lib.rtch_scene_motion.argtypes = [C.c_void_p, _dp, C.c_uint32]
+        lib.rtch_scene_spots.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), _dp, _dp, _dp, C.c_uint32]
         lib.rtch_scene_adaptive.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(Adaptive)]
         lib.rtch_scene_camera.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Camera)]
         lib.rtch_camera_rotate.argtypes = [C.c_void_p, C.c_double]
@@ -485,6 +511,15 @@ class HostScene:
         _check_host(host_lib().rtch_scene_motion(self._h, out.ctypes.data_as(_dp), n))
         return out
 
+    def spots(self):
+        """The scene file's "spot-light" entries (rtch_scene_spots), in World.lights order: a dict of "cone" (n,) uint8,
+        "axis" (n, 3), "cos_inner" and "cos_outer" (n,) - what GpuScene.set_spots takes -, or None without a cone."""
+        n = self.lights.n_lights
+        out = {"cone": np.zeros(n, dtype=np.uint8), "axis": np.zeros((n, 3)), "cos_inner": np.zeros(n), "cos_outer": np.zeros(n)}
+        _check_host(host_lib().rtch_scene_spots(self._h, out["cone"].ctypes.data_as(C.POINTER(C.c_uint8)), out["axis"].ctypes.data_as(_dp),
+                                                out["cos_inner"].ctypes.data_as(_dp), out["cos_outer"].ctypes.data_as(_dp), n))
+        return out if out["cone"].any() else None
+
     def adaptive(self):
         """The camera's "sampling": {"adaptive": ...} of the scene file (rtch_scene_adaptive): an Adaptive whose max_passes
         is "passes", or None when the file has none."""
@@ -571,6 +606,15 @@ class GpuScene:
             raise ValueError(f"set_motion: displacements of shape {d.shape}, (n_roots, 3) expected")
         m = Motion(d.shape[0], d.ctypes.data_as(_dp))
         _check_hip(hip_lib().rtc_scene_set_motion(self._s, C.byref(m)))
+
+    def set_spots(self, spots):
+        """rtc_scene_set_spots: a dict of "cone" (n_lights,) 0 / 1, "axis" (n_lights, 3), "cos_inner" and "cos_outer"
+        (n_lights,), one entry per World.lights entry (HostScene.spots()); None: no cones."""
+        if spots is None:
+            _check_hip(hip_lib().rtc_scene_set_spots(self._s, None))
+            return
+        sp, _keep = spot_struct(spots)
+        _check_hip(hip_lib().rtc_scene_set_spots(self._s, C.byref(sp)))
 
     def accumulate_device(self, accum, stream=None):
         """rtc_scene_accumulate_device: an Accum, enqueued on `stream` (None: the handle's own) after this handle's renders."""

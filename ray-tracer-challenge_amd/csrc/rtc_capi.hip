@@ -99,6 +99,16 @@ __global__ void rtc_render_kernel_motion_bigworld(const DevScene S, const DevCam
                                                   double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
                                                   const DevAreaLights area, const DevSampling smp, const DevMotion mo);
 }
+// The spot kernels (rtc_scene_set_spots: point lights that shine into a cone).  Their table edge - RTC_LDS_LIGHTS lights
+// select the LDS kernel, one more the big-world one - is tested in tests/test_spot_lights_gpu.py.
+extern "C" {
+__global__ void rtc_render_kernel_spot(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                       double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                       const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots);
+__global__ void rtc_render_kernel_spot_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                                double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                                const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots);
+}
 // Progressive rendering's accumulation (rtc_accum.hip): the grid's blocks for n pixels (the noise partials it writes, at
 // most) and the enqueue of its kernels.
 uint32_t rtcAccumBlocks(size_t n_pixels, bool wide);
@@ -312,7 +322,8 @@ bool tablesInLds(const rtc_scene* s) {
 }
 
 // (the area kernels take one more argument, DevAreaLights: `area` instead of `fn`; the sampling kernels DevSampling:
-// `ms`, and both: `area_ms`; the motion kernels both and DevMotion: `motion`)
+// `ms`, and both: `area_ms`; the motion kernels both and DevMotion: `motion`; the spot kernels those three and DevSpots:
+// `spot`)
 struct KernelChoice {
   decltype(&rtc_render_kernel) fn;
   const char* name;
@@ -320,18 +331,21 @@ struct KernelChoice {
   decltype(&rtc_render_kernel_ms) ms = nullptr;
   decltype(&rtc_render_kernel_area_ms) area_ms = nullptr;
   decltype(&rtc_render_kernel_motion) motion = nullptr;
+  decltype(&rtc_render_kernel_spot) spot = nullptr;
   KernelChoice(decltype(&rtc_render_kernel) f, const char* n) : fn(f), name(n) {}
   KernelChoice(decltype(&rtc_render_kernel_area) a, const char* n) : fn(nullptr), name(n), area(a) {}
   KernelChoice(decltype(&rtc_render_kernel_ms) m, const char* n) : fn(nullptr), name(n), ms(m) {}
   KernelChoice(decltype(&rtc_render_kernel_area_ms) am, const char* n) : fn(nullptr), name(n), area_ms(am) {}
   KernelChoice(decltype(&rtc_render_kernel_motion) mo, const char* n) : fn(nullptr), name(n), motion(mo) {}
+  KernelChoice(decltype(&rtc_render_kernel_spot) sk, const char* n) : fn(nullptr), name(n), spot(sk) {}
   void launch(uint32_t blocks, hipStream_t stream, const rtc_scene* s, const DevScene& dev, const DevCamera& cam, const DevPixelMap& map,
               uint32_t max_depth, double* d_out, DevStats* st_now, DevStats* st_next) const {
     DevSampling smp = s->sampling;  // (the pass's area-light offset, P * N * S: N is the camera's whole image)
     smp.pixel_base = static_cast<unsigned long long>(smp.sample_base) * (static_cast<unsigned long long>(cam.hsize) * cam.vsize);
-    if (motion) {
+    if (motion || spot) {
       // the handle's root tables with the moving roots' bounds (or the scene's, all displacements zero: the option), and
-      // the scene's area rows (or zero rows: a point-only table)
+      // the scene's area rows (or zero rows: a point-only table); the spot kernels also the handle's spot rows (or zero
+      // rows, every flag 0: the option)
       DevScene md = dev;
       DevMotion mo{s->tab->zero_disp.p};
       smp.key = rtc_mix64(s->sampling_desc.seed ^ 0x243F6A8885A308D3ull);  // (the time's hash: also under the default sampling)
@@ -344,7 +358,12 @@ struct KernelChoice {
         mo.disp = m->disp.p;
       }
       const DevAreaLights area = s->area_kernel ? s->area : DevAreaLights{s->tab->zero_rows.p, s->area.seed};
-      hipLaunchKernelGGL(motion, dim3(blocks), dim3(256), 0, stream, md, cam, map, max_depth, d_out, st_now, st_next, area, smp, mo);
+      if (spot) {
+        const DevSpots sp{s->spots ? s->spots->row.p : s->tab->zero_rows.p};
+        hipLaunchKernelGGL(spot, dim3(blocks), dim3(256), 0, stream, md, cam, map, max_depth, d_out, st_now, st_next, area, smp, mo, sp);
+      } else {
+        hipLaunchKernelGGL(motion, dim3(blocks), dim3(256), 0, stream, md, cam, map, max_depth, d_out, st_now, st_next, area, smp, mo);
+      }
     } else if (area_ms)
       hipLaunchKernelGGL(area_ms, dim3(blocks), dim3(256), 0, stream, dev, cam, map, max_depth, d_out, st_now, st_next, s->area, smp);
     else if (ms)
@@ -361,6 +380,9 @@ bool samplingKernels(const rtc_scene* s) { return s->sampling_on || s->sample_pa
 // The motion kernels run when a displacement of the handle is not zero - whatever the sampling and the pass: the image
 // depends on the shutter time - or, for tests, whenever option "motion_kernels" is set.
 bool motionKernels(const rtc_scene* s) { return s->motion != nullptr || rtcOptions().motion_kernels != 0.0; }
+// The spot kernels run when a light of the handle has a cone - whatever the sampling, the pass and the motion - or, for
+// tests, whenever option "spot_kernels" is set.
+bool spotKernels(const rtc_scene* s) { return s->spots != nullptr || rtcOptions().spot_kernels != 0.0; }
 #define RTC_KERNEL(k) KernelChoice{k, #k}
 // The general kernel at three waves per SIMD (rtc_render_kernel3): forced by option "waves3", else what the handle's
 // trial measured (KernelTune in launch()).
@@ -387,6 +409,7 @@ KernelChoice ldsKernel(const rtc_scene* s, const DevPixelMap& map) {
   return s->ext_kernel ? RTC_KERNEL(rtc_render_kernel_ext) : RTC_KERNEL(rtc_render_kernel);
 }
 KernelChoice renderKernel(const rtc_scene* s, const DevPixelMap& map) {
+  if (spotKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_spot) : RTC_KERNEL(rtc_render_kernel_spot_bigworld);
   if (motionKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_motion) : RTC_KERNEL(rtc_render_kernel_motion_bigworld);
   if (samplingKernels(s)) {
     if (s->area_kernel) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_area_ms) : RTC_KERNEL(rtc_render_kernel_area_ms_bigworld);
@@ -400,6 +423,7 @@ KernelChoice renderKernel(const rtc_scene* s, const DevPixelMap& map) {
 
 // Work-groups of the launch's kernel that are resident at once, and the waves in them.
 uint32_t residentBlocksAlone(const rtc_scene* s, const DevPixelMap& map) {
+  if (spotKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_spot_lds : s->blocks_per_cu_spot_big);
   if (motionKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_motion_lds : s->blocks_per_cu_motion_big);
   if (samplingKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_ms_lds : s->blocks_per_cu_ms_big);
   if (usesSimple3(s, map)) return s->n_cus * s->blocks_per_cu_simple3;
@@ -805,7 +829,7 @@ int launch(rtc_scene* s, const rtc_camera& cam, const DevPixelMap& map_in, uint3
   int trial_slot = -1;
   {
     rtc_scene::KernelTune& T = s->tune;
-    const bool eligible = !samplingKernels(s) && !motionKernels(s) &&  // (the sampling and motion kernels have no three-wave form)
+    const bool eligible = !samplingKernels(s) && !motionKernels(s) && !spotKernels(s) &&  // (the sampling, motion and spot kernels have no three-wave form)
                           ((s->general3_ok && rtcOptions().waves3 < 0.0 && tablesInLds(s) &&
                             !(s->tab && s->tab->handles.load(std::memory_order_relaxed) > 1) &&
                             static_cast<double>(map.n_chunks) >= 4.0 * 4.0 * s->n_cus * s->blocks_per_cu_lds) ||
@@ -2103,6 +2127,12 @@ int uploadTables(const rtc_scene_desc& d, const SceneTraits& traits, const HostT
   s->general3_ok = RTC_BVH8 && !s->flat_kernel && !ext_kernel && d.n_roots <= RTC_LDS3_ROOTS && d.n_materials <= RTC_LDS3_MATERIALS &&
                    d.n_patterns <= RTC_LDS3_PATTERNS && d.n_lights <= RTC_LDS3_LIGHTS;
   HIP_TRY(s->tab->light.upload(light));
+  s->tab->h_light_area.assign(d.n_lights, 0u);  // (which lights rtc_scene_set_spots refuses a cone on)
+  for (size_t i = 0; !T.area.empty() && i < d.n_lights; ++i) {
+    unsigned long long bits;
+    std::memcpy(&bits, &T.area[static_cast<size_t>(RTC_AREA_ROW) * i + 12u], sizeof bits);
+    s->tab->h_light_area[i] = static_cast<uint8_t>((bits >> RTC_AREA_KIND_BIT) & 1ull);
+  }
   if (!T.area.empty()) {  // area lights: the area kernels, whatever the world's shape (no simple, flat or three-wave forms)
     HIP_TRY(s->tab->area.upload(T.area));
     s->area_kernel = true;
@@ -2147,10 +2177,15 @@ int uploadTables(const rtc_scene_desc& d, const SceneTraits& traits, const HostT
     s->blocks_per_cu_motion_lds = static_cast<uint32_t>(std::max(nb, 1));
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_motion_bigworld, 256, 0));
     s->blocks_per_cu_motion_big = static_cast<uint32_t>(std::max(nb, 1));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_spot, 256, 0));  // (the spot kernels: one pair for every world)
+    s->blocks_per_cu_spot_lds = static_cast<uint32_t>(std::max(nb, 1));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_spot_bigworld, 256, 0));
+    s->blocks_per_cu_spot_big = static_cast<uint32_t>(std::max(nb, 1));
     if (const int v = static_cast<int>(rtcOptions().blocks_per_cu); v >= 1) {  // (tuning option)
       s->blocks_per_cu_lds = std::min<uint32_t>(s->blocks_per_cu_lds, v), s->blocks_per_cu_big = std::min<uint32_t>(s->blocks_per_cu_big, v);
       s->blocks_per_cu_ms_lds = std::min<uint32_t>(s->blocks_per_cu_ms_lds, v), s->blocks_per_cu_ms_big = std::min<uint32_t>(s->blocks_per_cu_ms_big, v);
       s->blocks_per_cu_motion_lds = std::min<uint32_t>(s->blocks_per_cu_motion_lds, v), s->blocks_per_cu_motion_big = std::min<uint32_t>(s->blocks_per_cu_motion_big, v);
+      s->blocks_per_cu_spot_lds = std::min<uint32_t>(s->blocks_per_cu_spot_lds, v), s->blocks_per_cu_spot_big = std::min<uint32_t>(s->blocks_per_cu_spot_big, v);
     }
   }
   DevScene& D = s->dev;
@@ -2557,6 +2592,63 @@ int rtc_scene_set_motion(rtc_scene* s, const rtc_motion* motion) {
   return RTC_OK;
 }
 
+// ---- spot lights
+// Validated before anything changes: first the table's own values - so that they are checked whatever the handle -, then
+// the table against the handle (its light count, its area lights).  Every flag 0 is no cone: the handle's old kernels.
+int rtc_scene_set_spots(rtc_scene* s, const rtc_spot* spots) {
+  g_error.clear();
+  if (!s) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
+  bool any = false;
+  std::vector<double> rows;
+  if (spots) {
+    const uint32_t n = spots->n_lights;
+    if (n != 0u && !spots->cone) return fail(RTC_ERR_INVALID_ARGUMENT, "spots: null cone");
+    for (uint32_t i = 0; i < n; ++i) {
+      if (spots->cone[i] > 1u) return fail(RTC_ERR_INVALID_ARGUMENT, "spots: cone flag %u of light %u (0 or 1)", spots->cone[i], i);
+      any = any || spots->cone[i] != 0u;
+    }
+    if (any && (!spots->axis || !spots->cos_inner || !spots->cos_outer))
+      return fail(RTC_ERR_INVALID_ARGUMENT, "spots: null axis, cos_inner or cos_outer");
+    rows.assign(static_cast<size_t>(RTC_SPOT_ROW) * n, 0.0);
+    for (uint32_t i = 0; i < n && any; ++i) {
+      if (spots->cone[i] == 0u) continue;  // (its other fields are not read)
+      const double* a = spots->axis + 3ull * i;
+      const double ci = spots->cos_inner[i], co = spots->cos_outer[i];
+      if (!(std::isfinite(a[0]) && std::isfinite(a[1]) && std::isfinite(a[2]) && std::isfinite(ci) && std::isfinite(co)))
+        return fail(RTC_ERR_INVALID_ARGUMENT, "spots: light %u: a value that is not finite", i);
+      const double mag = std::sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);  // (tuple.zig's normalize)
+      if (!(std::isfinite(mag) && mag > 0.0)) return fail(RTC_ERR_INVALID_ARGUMENT, "spots: light %u: axis of magnitude %g", i, mag);
+      if (!(ci >= -1.0 && ci <= 1.0 && co >= -1.0 && co <= 1.0))
+        return fail(RTC_ERR_INVALID_ARGUMENT, "spots: light %u: cosines %g, %g (-1 to 1)", i, ci, co);
+      if (co > ci) return fail(RTC_ERR_INVALID_ARGUMENT, "spots: light %u: cos_outer %g above cos_inner %g", i, co, ci);
+      double* r = rows.data() + static_cast<size_t>(RTC_SPOT_ROW) * i;
+      r[0] = a[0] / mag;
+      r[1] = a[1] / mag;
+      r[2] = a[2] / mag;
+      r[3] = ci;
+      r[4] = co;
+      r[5] = 1.0;
+    }
+    if (n != s->dev.n_lights) return fail(RTC_ERR_INVALID_ARGUMENT, "spots: n_lights %u, the scene has %u", n, s->dev.n_lights);
+    for (uint32_t i = 0; i < n && any; ++i)
+      if (spots->cone[i] != 0u && s->tab->h_light_area[i] != 0u)
+        return fail(RTC_ERR_INVALID_ARGUMENT, "spots: light %u is an area light (cones apply to point lights only)", i);
+  }
+  std::shared_ptr<const SpotTables> tables;  // (no cone: none)
+  if (any) {
+    auto t = std::make_shared<SpotTables>();
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(t->row.upload(rows));
+    tables = std::move(t);
+  }
+  // (the rows being replaced may still be read by a launch of this handle or of its band clones)
+  HIP_TRY(handleIdle(s));
+  for (rtc_scene* b : s->band) HIP_TRY(handleIdle(b));
+  s->spots = tables;
+  for (rtc_scene* b : s->band) b->spots = tables;  // (the band clones rtc_render renders a large frame with)
+  return RTC_OK;
+}
+
 // ---- adaptive sampling
 // The setting's own fields, and the image's tile count (T < 2^31)
 static int checkAdaptive(const rtc_adaptive* a, uint32_t hsize, uint32_t vsize, uint32_t* n_tiles) {
@@ -2762,6 +2854,9 @@ int rtc_scene_clone(const rtc_scene* src, rtc_scene** out) {
   s->motion = src->motion;  // (shared: read-only once made)
   s->blocks_per_cu_motion_lds = src->blocks_per_cu_motion_lds;
   s->blocks_per_cu_motion_big = src->blocks_per_cu_motion_big;
+  s->spots = src->spots;  // (shared: read-only once made)
+  s->blocks_per_cu_spot_lds = src->blocks_per_cu_spot_lds;
+  s->blocks_per_cu_spot_big = src->blocks_per_cu_spot_big;
   s->simple_kernel = src->simple_kernel;
   s->flat_kernel = src->flat_kernel;
   s->simple3_ok = src->simple3_ok;
@@ -3158,7 +3253,8 @@ int rtc_set_option(const char* name, double value) {
                {"bvh_check", &o.bvh_check}, {"host_bands", &o.host_bands}, {"waves3", &o.waves3},
                {"measure_every", &o.measure_every}, {"sched_mix", &o.sched_mix},
                {"inflight_chunks_per_wave", &o.inflight_chunks_per_wave}, {"build_threads", &o.build_threads}, {"box_cull", &o.box_cull},
-               {"sampling_kernels", &o.sampling_kernels}, {"motion_kernels", &o.motion_kernels}};
+               {"sampling_kernels", &o.sampling_kernels}, {"motion_kernels", &o.motion_kernels},
+               {"spot_kernels", &o.spot_kernels}};
   for (const auto& e : table)
     if (std::strcmp(e.name, name) == 0) {
       e.slot->set(value);

@@ -322,6 +322,23 @@ struct DevMotion {
   const double* __restrict__ disp;  // [n_roots][3], in the root tables' order (all zero: the "motion_kernels" option)
 };
 
+// Spot lights (rtc_scene_set_spots): the extra argument of the spot kernels only.  One row of
+// RTC_SPOT_ROW doubles per light, in World.lights order: the unit axis, cos_inner, cos_outer and a flag (1.0: a cone,
+// 0.0: the light as it is - every row of an area light, and every row under the "spot_kernels" option).
+#define RTC_SPOT_ROW 6u
+struct DevSpots {
+  const double* __restrict__ row;  // [n_lights][RTC_SPOT_ROW]
+};
+// The cone's factor at c = -(point_to_light . axis): 1 inside cos_inner, 0 outside cos_outer, smoothstep between - each
+// operation correctly rounded (-ffp-contract=off), the same bits in the kernels and in the checker.  cos_inner ==
+// cos_outer (a hard edge) never reaches the division.
+__host__ __device__ inline double rtc_spot_factor(double c, double cos_inner, double cos_outer) {
+  if (c >= cos_inner) return 1.0;
+  if (c <= cos_outer) return 0.0;
+  const double s = (c - cos_outer) / (cos_inner - cos_outer);
+  return (s * s) * (3.0 - 2.0 * s);
+}
+
 struct DevCamera {
   double half_width, half_height, pixel_size;
   double inv[12];  // rows 0..2 of Camera._inverse_transform

@@ -67,6 +67,7 @@ struct RtcOptions {
   RtcOption box_cull{-1.0};            // a simple world's kernels reject roots by world boxes (1) or bounding spheres (0); < 0: boxes if it has more cubes than spheres
   RtcOption sampling_kernels{0.0};     // != 0: the sampling kernels even with the default sampling (tests: one sample against the other kernels)
   RtcOption motion_kernels{0.0};       // != 0: the motion kernels even on a static handle, all displacements zero (tests: against the _ms kernels)
+  RtcOption spot_kernels{0.0};         // != 0: the spot kernels even on a handle without cones, every flag zero (tests: against the motion kernels)
   RtcOption build_threads{0.0};        // threads of rtc_scene_create's candidate-BVH build (one top-level group each); 0: as many as the host allows, up to 8
 };
 inline RtcOptions& rtcOptions() {
@@ -133,6 +134,14 @@ struct SceneTables {
   std::vector<RootBoxPair> h_root_box;
   std::vector<uint32_t> h_root_order;  // table position -> World.objects index
   DevBuf<double> zero_disp, zero_rows;
+  // spot lights (rtc_scene_set_spots): which lights are area lights (a cone on one is refused); a handle without cones
+  // passes zero_rows to the spot kernels as its spot rows (RTC_SPOT_ROW <= RTC_AREA_ROW: every flag zero)
+  std::vector<uint8_t> h_light_area;
+};
+
+// A handle's spot lights (rtc_scene_set_spots): DevSpots::row.  Read-only once made: a clone and the band clones share it.
+struct SpotTables {
+  DevBuf<double> row;
 };
 
 // A handle's motion (rtc_scene_set_motion): the displacements in table order, and copies of the root tables in which a
@@ -176,6 +185,8 @@ struct rtc_scene {
   uint32_t blocks_per_cu_ms_lds = 1, blocks_per_cu_ms_big = 1;  // resident work-groups of the world's sampling kernels
   std::shared_ptr<const MotionTables> motion;  // rtc_scene_set_motion; null: static (a clone starts with its source's)
   uint32_t blocks_per_cu_motion_lds = 1, blocks_per_cu_motion_big = 1;  // ... and of the motion kernels
+  std::shared_ptr<const SpotTables> spots;  // rtc_scene_set_spots; null: no cones (a clone starts with its source's)
+  uint32_t blocks_per_cu_spot_lds = 1, blocks_per_cu_spot_big = 1;  // ... and of the spot kernels
   bool simple3_ok = false;         // a simple world whose tables fit the three-waves-per-SIMD kernel's LDS (RTC_LDS3_*)
   void* d_csg_buf = nullptr;       // DevPixelMap::csg_buf, only for scenes with csg nodes
   size_t csg_buf_capacity = 0;     // bytes

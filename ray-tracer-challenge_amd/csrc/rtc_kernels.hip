@@ -2318,16 +2318,19 @@ __device__ __forceinline__ Ray camera_sample(const DevCamera& cam, const DevSamp
 // (MS: several camera samples per pixel - DevSampling, the sampling kernels' extra argument; compiled into those kernels only)
 // (MOTION: top-level objects that move while the shutter is open - DevMotion, the motion kernels' extra argument; with MS
 // and AREA, compiled into those kernels only)
+// (SPOT: point lights that shine into a cone - DevSpots, the spot kernels' extra argument; with MOTION, MS and AREA,
+// compiled into those kernels only)
 template <bool LDS, bool CSG, int WORLD = 0, int WAVES = 2, bool COOP = false, bool BOX = true, bool AREA = false, bool MS = false,
-          bool MOTION = false>
+          bool MOTION = false, bool SPOT = false>
 __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& cam, const DevPixelMap& map,
                                             const uint32_t max_depth, double* __restrict__ out,
                                             DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
                                             const DevAreaLights& area = DevAreaLights{}, const DevSampling& smp = DevSampling{},
-                                            const DevMotion& mo = DevMotion{}) {
+                                            const DevMotion& mo = DevMotion{}, const DevSpots& spots = DevSpots{}) {
   static_assert(!AREA || !COOP, "the area kernels run no cooperative iterations");
   static_assert(!MS || !COOP, "the sampling kernels run no cooperative iterations");
   static_assert(!MOTION || (MS && AREA && WORLD == 0), "the motion kernels are the general area-sampling walk");
+  static_assert(!SPOT || MOTION, "the spot kernels are the motion walk");
   RTC_PRIO_PHASE(RTC_PRIO_WORK);
 #ifndef RTC_PROFILE
   if (blockIdx.x == 0u) {  // the next launch's counters (see DevStats)
@@ -3230,7 +3233,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
           }
         }
         const double* __restrict__ L = lights + 6ull * li;
-        it_shadow_calls++;
+        if constexpr (!SPOT) it_shadow_calls++;  // (SPOT: below, once the cone has said whether isShadowed is called)
         // isShadowed (world.zig:127-131) and lighting's point_to_light (material.zig:51) share this
         const double vx = L[0] - ovx, vy = L[1] - ovy, vz = L[2] - ovz;
         const double distance = __builtin_sqrt((vx * vx + vy * vy) + vz * vz);
@@ -3244,7 +3247,19 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
         // or not (material.zig:62-73): that shadow ray cannot change the result either.
         const double light_dot_normal = (lvx * nx + lvy * ny) + lvz * nz;
         bool shadowed = false;
-        if (shadow_matters && light_dot_normal >= 0.0 && !(RTC_EXPERIMENT & 1)) {
+        // (SPOT) the cone's factor f at c = -(point_to_light . axis).  f == 0: the light gives `ambient` alone - what a
+        // shadowed point gets -, so isShadowed is not called: no count, no shadow ray.  li is wave-uniform (no cooperative
+        // iterations here): the row is read through the constant address space at a readfirstlane index - scalar loads,
+        // the rows being read-only while a launch runs - and nothing of it is staged in LDS.
+        double spot_f = 1.0;
+        if constexpr (SPOT) {
+          typedef const __attribute__((address_space(4))) double ConstRow;
+          ConstRow* C = (ConstRow*)spots.row + static_cast<size_t>(RTC_SPOT_ROW) * __builtin_amdgcn_readfirstlane(li);
+          if (C[5] != 0.0) spot_f = rtc_spot_factor(-((lvx * C[0] + lvy * C[1]) + lvz * C[2]), C[3], C[4]);
+          shadowed = spot_f == 0.0;
+          if (!shadowed) it_shadow_calls++;
+        }
+        if (!shadowed && shadow_matters && light_dot_normal >= 0.0 && !(RTC_EXPERIMENT & 1)) {
           it_shadow_traced++;
           it_share++;
           ShadowVisitor sv;
@@ -3271,6 +3286,11 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
             dr = er * kd;
             dg = eg * kd;
             db = eb * kd;
+            if constexpr (SPOT) {  // (the diffuse term scaled once it is formed; f == 1: the same bits)
+              dr = dr * spot_f;
+              dg = dg * spot_f;
+              db = db * spot_f;
+            }
             const double two_dot = 2.0 * light_dot_normal;  // point_to_light.reflect(normal)
             const double rx = lvx - nx * two_dot, ry = lvy - ny * two_dot, rz = lvz - nz * two_dot;
             const double reflect_dot_eye = ((-rx) * ex + (-ry) * ey) + (-rz) * ez;
@@ -3281,6 +3301,11 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
               pr = L[3] * ks;
               pg = L[4] * ks;
               pb = L[5] * ks;
+              if constexpr (SPOT) {  // (... and the specular term)
+                pr = pr * spot_f;
+                pg = pg * spot_f;
+                pb = pb * spot_f;
+              }
             }
           }
           lr_ = (lr_ + dr) + pr;
@@ -3514,17 +3539,18 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
 }
 
 // The kernels.  rtc_motion.hip includes this file with RTC_MOTION_TU defined and gets the motion kernels alone: a
-// translation unit of their own, so that this one compiles in the time and to the code it did.  rtc_kernels_ext.hip
+// translation unit of their own, so that this one compiles in the time and to the code it did; rtc_spot.hip likewise
+// with RTC_SPOT_TU and the spot kernels.  rtc_kernels_ext.hip
 // includes it with RTC_EXT_TU defined: in the -DRTC_PROFILE diagnostic build, whose instrumented walk makes this unit's
 // compile about a third longer, it gets the csg / texture-map, flat and area-light kernels (rtc_render_kernel_ext to
 // rtc_render_kernel_area_bigworld below), so that neither unit takes the time of all of them.  The product build keeps
 // them here - that unit's code is the same as before to the byte - and its rtc_kernels_ext.o holds no kernel.
-#if (defined(RTC_EXT_TU) && defined(RTC_PROFILE)) || (!defined(RTC_MOTION_TU) && !defined(RTC_EXT_TU) && !defined(RTC_PROFILE))
+#if (defined(RTC_EXT_TU) && defined(RTC_PROFILE)) || (!defined(RTC_MOTION_TU) && !defined(RTC_SPOT_TU) && !defined(RTC_EXT_TU) && !defined(RTC_PROFILE))
 #define RTC_EXT_KERNELS_HERE 1
 #else
 #define RTC_EXT_KERNELS_HERE 0
 #endif
-#if !defined(RTC_MOTION_TU) && !defined(RTC_EXT_TU)
+#if !defined(RTC_MOTION_TU) && !defined(RTC_SPOT_TU) && !defined(RTC_EXT_TU)
 extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
 rtc_render_kernel(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
                   double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats) {
@@ -3585,7 +3611,7 @@ rtc_render_kernel3(const DevScene S, const DevCamera cam, const DevPixelMap map,
 }
 #endif
 
-#endif  // !RTC_MOTION_TU && !RTC_EXT_TU
+#endif  // !RTC_MOTION_TU && !RTC_SPOT_TU && !RTC_EXT_TU
 
 #if RTC_EXT_KERNELS_HERE
 // The same two kernels with the csg and texture-map paths compiled in (template flag CSG), for scenes that
@@ -3644,7 +3670,7 @@ rtc_render_kernel_area_bigworld(const DevScene S, const DevCamera cam, const Dev
 }
 #endif  // RTC_EXT_KERNELS_HERE
 
-#if !defined(RTC_MOTION_TU) && !defined(RTC_EXT_TU)
+#if !defined(RTC_MOTION_TU) && !defined(RTC_SPOT_TU) && !defined(RTC_EXT_TU)
 // Several camera samples per pixel (rtc_scene_set_sampling: anti-aliasing, focal blur): the general walk with the csg and
 // texture-map paths compiled in, the sampling parameters as an extra argument (DevSampling) - every other kernel is
 // compiled without them.  Point lights (tables in LDS or in memory), and the area-light forms.
@@ -4346,4 +4372,23 @@ rtc_render_kernel_motion_bigworld(const DevScene S, const DevCamera cam, const D
   render_body<false, true, 0, 2, false, true, true, true, true>(S, cam, map, max_depth, out, stats, next_stats, area, smp, mo);
 }
 
-#endif  // RTC_MOTION_TU
+#elif defined(RTC_SPOT_TU)
+
+// Spot lights (rtc_scene_set_spots): the motion walk with the cones of point lights compiled in (DevSpots), one pair for
+// every world and every combination of sampling, passes, motion and area lights (a static handle passes zero
+// displacements, a point-only table zero area rows).  Every other kernel is compiled without it.
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_spot(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                       double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                       const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots) {
+  render_body<true, true, 0, 2, false, true, true, true, true, true>(S, cam, map, max_depth, out, stats, next_stats, area, smp, mo, spots);
+}
+
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_spot_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots) {
+  render_body<false, true, 0, 2, false, true, true, true, true, true>(S, cam, map, max_depth, out, stats, next_stats, area, smp, mo, spots);
+}
+
+#endif  // RTC_MOTION_TU / RTC_SPOT_TU

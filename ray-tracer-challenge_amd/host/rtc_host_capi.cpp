@@ -101,6 +101,22 @@ int rtch_scene_motion(void* h, double* out, uint32_t n) {
   });
 }
 
+int rtch_scene_spots(void* h, uint8_t* cone, double* axis, double* cos_inner, double* cos_outer, uint32_t n) {
+  return guarded([&] {
+    const HostScene* hs = static_cast<HostScene*>(h);
+    if (n != hs->lights.n_lights)
+      throw rtc::Error("InvalidArgument", "spots: n " + std::to_string(n) + ", the scene has " + std::to_string(hs->lights.n_lights) + " lights");
+    if (n != 0u && (!cone || !axis || !cos_inner || !cos_outer)) throw rtc::Error("InvalidArgument", "spots: null argument");
+    for (uint32_t i = 0; i < n; ++i) {  // (World.lights order: the light table's)
+      const rtc::SpotCone& c = hs->info.spots[i];
+      cone[i] = c.cone;
+      for (int k = 0; k < 3; ++k) axis[3ull * i + k] = c.axis[k];
+      cos_inner[i] = c.cos_inner;
+      cos_outer[i] = c.cos_outer;
+    }
+  });
+}
+
 // Camera of the scene file; width/height 0 keep the file's values, otherwise they replace
 // camera.width/height before Camera.new runs (the reference has no such override).
 int rtch_scene_camera(void* h, uint32_t width, uint32_t height, rtc_camera* out) {
@@ -179,6 +195,14 @@ int rtch_scene_render(void* h, uint32_t width, uint32_t height, uint32_t max_dep
         if (rtch_scene_motion(h, disp.data(), hs->desc.n_roots) != 0) throw rtc::Error("InvalidArgument", g_error);
         const rtc_motion m{hs->desc.n_roots, disp.data()};
         st = rtc_scene_set_motion(scene, &m);
+      }
+      if (st == RTC_OK) {  // (the "spot-light" entries' cones; none: the handle as it is)
+        const uint32_t nl = hs->lights.n_lights;
+        std::vector<uint8_t> cone(nl);
+        std::vector<double> axis(3ull * nl), ci(nl), co(nl);
+        if (rtch_scene_spots(h, cone.data(), axis.data(), ci.data(), co.data(), nl) != 0) throw rtc::Error("InvalidArgument", g_error);
+        const rtc_spot sp{nl, cone.data(), axis.data(), ci.data(), co.data()};
+        st = rtc_scene_set_spots(scene, &sp);
       }
       const rtc::CameraSampling& cs = hs->info.sampling;
       if (cs.adaptive && st == RTC_OK) {  // (adaptive sampling: each tile's mean after its own passes, section 15)

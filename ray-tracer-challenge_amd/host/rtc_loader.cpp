@@ -753,6 +753,49 @@ SceneInfo parseScene(const std::string& scene_json, const FileLoader& load_file_
                                     (corner[2] + u[2] * 0.5) + v[2] * 0.5);
       light.intensity = {c[0], c[1], c[2]};
       info.world.lights.push_back(light);
+      info.spots.emplace_back();
+      continue;
+    }
+    if (kv.first == "spot-light") {  // (not in the reference): a point light that shines into a cone
+      const Value& cfg = requireObject(kv.second, "spot-light");
+      checkFields(cfg, {"position", "intensity", "to", "direction", "outer-angle", "inner-angle"}, "spot-light");
+      // (an entry that names no cone at all is refused as the light kind this loader did not know before spot lights)
+      if (!cfg.find("to") && !cfg.find("direction") && !cfg.find("outer-angle"))
+        throw Error("UnknownField", "light.spot-light: a spot-light names its cone (\"to\" or \"direction\", and \"outer-angle\")");
+      double p[3], c[3], a[3];
+      asVec3(requireField(cfg, "position", "spot-light"), "position", p);
+      asVec3(requireField(cfg, "intensity", "spot-light"), "intensity", c);
+      const Value* to = cfg.find("to");
+      const Value* direction = cfg.find("direction");
+      if ((to != nullptr) == (direction != nullptr)) throw Error("InvalidData", "spot-light: exactly one of \"to\" and \"direction\"");
+      if (to) {
+        double t[3];
+        asVec3(*to, "to", t);
+        for (int k = 0; k < 3; ++k) a[k] = t[k] - p[k];
+      } else {
+        asVec3(*direction, "direction", a);
+      }
+      const double mag = std::sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);  // (the library normalizes it so)
+      if (!(std::isfinite(mag) && mag > 0.0))
+        throw Error("InvalidData", to ? "spot-light.to: a point other than position, at a finite distance"
+                                      : "spot-light.direction: a finite vector other than zero");
+      for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(p[k])) throw Error("InvalidData", "spot-light.position: every component is finite");
+      const double pi = std::acos(-1.0);
+      const double outer = asFloat(requireField(cfg, "outer-angle", "spot-light"), "outer-angle");
+      if (!(outer > 0.0 && outer <= pi)) throw Error("InvalidData", "spot-light.outer-angle: a half-angle in (0, pi] radians");
+      double inner = outer;  // (optional: a hard edge)
+      if (const Value* in = cfg.find("inner-angle")) {
+        inner = asFloat(*in, "inner-angle");
+        if (!(inner >= 0.0 && inner <= outer)) throw Error("InvalidData", "spot-light.inner-angle: a half-angle in [0, outer-angle] radians");
+      }
+      info.world.lights.push_back({Tuple::point(p[0], p[1], p[2]), {c[0], c[1], c[2]}});
+      SpotCone cone;
+      cone.cone = 1;
+      for (int k = 0; k < 3; ++k) cone.axis[k] = a[k];
+      cone.cos_inner = std::cos(inner);
+      cone.cos_outer = std::cos(outer);
+      info.spots.push_back(cone);
       continue;
     }
     if (kv.first != "point-light") throw Error("UnknownField", "light." + kv.first);
@@ -762,6 +805,7 @@ SceneInfo parseScene(const std::string& scene_json, const FileLoader& load_file_
     asVec3(requireField(cfg, "position", "point-light"), "position", p);
     asVec3(requireField(cfg, "intensity", "point-light"), "intensity", c);
     info.world.lights.push_back({Tuple::point(p[0], p[1], p[2]), {c[0], c[1], c[2]}});
+    info.spots.emplace_back();
   }
   return info;
 }

@@ -33,11 +33,20 @@ struct CameraSampling {
   uint32_t tile_w = 16, tile_h = 16;
 };
 
+// A "spot-light" entry's cone (not in the reference), as rtc_scene_set_spots takes it: the axis as
+// given ("to" - position, or "direction"), and the cosines of the half-angles (std::cos).  cone 0: a light without one.
+struct SpotCone {
+  uint8_t cone = 0;
+  double axis[3] = {0.0, 0.0, 0.0};
+  double cos_inner = 1.0, cos_outer = 1.0;
+};
+
 struct SceneInfo {  // scene.zig:608-610
   Camera camera;
   World world;
   CameraSampling sampling;
   std::vector<double> motion;  // [objects][3]: each top-level object's optional "motion" (DESIGN.md section 14), else 0
+  std::vector<SpotCone> spots;  // [lights]: a "spot-light" entry's cone (section 16); cone 0 for every other light
 };
 
 // scene.zig:612-661.  Throws rtc::Error whose .name is the Zig error name

@@ -5,6 +5,7 @@
                                 [--handles 3] [--settle 50] [--frames 20] [--option name=value ...] [--check]
                                 [--lights scene | area=N | grid=N] [--sampling grid[,aperture,focal]] [--passes P]
                                 [--motion R=dx,dy,dz ...] [--adaptive threshold[,min,tile] [--max-passes N]]
+                                [--spot L=ax,ay,az,inner,outer ...]
 
   configs  the five BASELINE configs at their own sizes and depths (fresnel 300x300, cover / teapot 1080p, r&r 1080p
            depth 8, dragons 4K)                                                       [default]
@@ -28,6 +29,9 @@ prints its noise after 4, 16 and 64.
 --motion R=dx,dy,dz (repeatable): World.objects entry R moves by (dx, dy, dz) over the shutter (rtc_scene_set_motion; motion
 blur); prints primary rays per frame and ns per primary ray as well.  Option motion_kernels=1 times
 the motion kernels on the static scene.
+--spot L=ax,ay,az,inner,outer (repeatable): World.lights entry L, a point light, becomes a spot light with that axis and
+those half-angles in radians (rtc_scene_set_spots); prints shadow_traced per frame and ns per primary
+ray as well.  Option spot_kernels=1 times the spot kernels without a cone.
 --adaptive threshold[,min,tile]: adaptive sampling at up to --max-passes (64) passes, min passes 4 and
 16 x 16 tiles by default, with the --sampling of the frames: prints the rounds and tile-passes of a run against
 T * max_passes, its time (a second run, end to end on the host) against uniform progressive passes (render_device +
@@ -65,6 +69,7 @@ ap.add_argument("--lights", default="")
 ap.add_argument("--sampling", default="")
 ap.add_argument("--passes", type=int, default=-1)
 ap.add_argument("--motion", action="append", default=[])
+ap.add_argument("--spot", action="append", default=[])
 ap.add_argument("--adaptive", default="")
 ap.add_argument("--max-passes", type=int, default=64)
 args = ap.parse_args()
@@ -237,6 +242,18 @@ for name, w, h, depth in cases:
                 r, d = m.split("=")
                 disp[int(r)] = [float(v) for v in d.split(",")]
             gpu.set_motion(disp)
+        if args.spot:
+            import math
+            import numpy as np
+            n = table.n_lights if table is not None else hs.desc.n_lights
+            spots = {"cone": np.zeros(n, dtype=np.uint8), "axis": np.zeros((n, 3)), "cos_inner": np.ones(n), "cos_outer": np.ones(n)}
+            for sp in args.spot:
+                l, v = sp.split("=")
+                ax, ay, az, inner, outer = (float(x) for x in v.split(","))
+                i = int(l)
+                spots["cone"][i], spots["axis"][i] = 1, (ax, ay, az)
+                spots["cos_inner"][i], spots["cos_outer"][i] = math.cos(inner), math.cos(outer)
+            gpu.set_spots(spots)
         for i in range(args.settle):
             gpu.render_device(cam, canvas.data_ptr(), depth, None, stream.cuda_stream)
         torch.cuda.synchronize()
@@ -259,9 +276,9 @@ for name, w, h, depth in cases:
         gpu.close()
     line = f"{name[:14]} {min(ts):.4f} [{sum(ts) / len(ts):.4f} {max(ts):.4f}] {kernel.replace('rtc_render_kernel', 'k')}"
     if delta is not None: line += f" maxdelta {delta:.2e}"
-    if args.lights:
+    if args.lights or args.spot or "spot_kernels=1" in args.option:
         line += f" shadow_traced {st['shadow_traced']} ns/shadow-ray {min(ts) * 1e6 / max(1, st['shadow_traced']):.3f}"
-    if args.sampling or args.option or args.passes >= 0 or args.motion:
+    if args.sampling or args.option or args.passes >= 0 or args.motion or args.spot:
         line += f" primary {st['primary']} ns/primary-ray {min(ts) * 1e6 / max(1, st['primary']):.3f}"
     if acc:
         ms, copy_ms, nbytes = min(a[0] for a in acc), min(a[1] for a in acc), acc[0][2]
