@@ -12,6 +12,7 @@
 #   tests/build/libmotion_oracle.so              test infrastructure only: the motion-blur checker (tests/cpp/motion_oracle.cpp)
 #   tests/build/libadaptive_oracle.so            test infrastructure only: the adaptive-sampling checker (tests/cpp/adaptive_oracle.cpp)
 #   tests/build/libspot_oracle.so                test infrastructure only: the spot-light checker (tests/cpp/spot_oracle.cpp)
+#   tests/build/libbump_oracle.so                test infrastructure only: the normal-perturbation checker (tests/cpp/bump_oracle.cpp)
 #
 # -ffp-contract=off everywhere: the reference's float mode is strict IEEE
 # (SURVEY F10); the GPU path and the oracle must round identically.
@@ -38,7 +39,7 @@ oracle:
 
 # (the area-light checker includes the oracle's sources read-only; -pthread and -O3 as the oracle's own build)
 checker: tests/build/libarea_oracle.so tests/build/libcamera_oracle.so tests/build/libprogressive_oracle.so tests/build/libmotion_oracle.so \
-         tests/build/libadaptive_oracle.so tests/build/libspot_oracle.so
+         tests/build/libadaptive_oracle.so tests/build/libspot_oracle.so tests/build/libbump_oracle.so
 tests/build/libarea_oracle.so: tests/cpp/area_oracle.cpp oracle/oracle_capi.cpp oracle/rtc_oracle.hpp oracle/rtc_oracle_scene.hpp include/rtc.h
 	mkdir -p tests/build
 	$(CXX) -std=c++17 -O3 -ffp-contract=off -fPIC -Wall -Wextra -pthread -shared -o $@ tests/cpp/area_oracle.cpp
@@ -62,14 +63,18 @@ tests/build/libadaptive_oracle.so: tests/cpp/adaptive_oracle.cpp tests/cpp/progr
 tests/build/libspot_oracle.so: tests/cpp/spot_oracle.cpp tests/cpp/motion_oracle.cpp tests/cpp/camera_oracle.cpp tests/cpp/area_oracle.cpp oracle/oracle_capi.cpp oracle/rtc_oracle.hpp oracle/rtc_oracle_scene.hpp include/rtc.h
 	mkdir -p tests/build
 	$(CXX) -std=c++17 -O3 -ffp-contract=off -fPIC -Wall -Wextra -Wno-subobject-linkage -pthread -shared -o $@ tests/cpp/spot_oracle.cpp
+# (the normal-perturbation checker includes the spot-light checker, read-only)
+tests/build/libbump_oracle.so: tests/cpp/bump_oracle.cpp tests/cpp/spot_oracle.cpp tests/cpp/motion_oracle.cpp tests/cpp/camera_oracle.cpp tests/cpp/area_oracle.cpp oracle/oracle_capi.cpp oracle/rtc_oracle.hpp oracle/rtc_oracle_scene.hpp include/rtc.h
+	mkdir -p tests/build
+	$(CXX) -std=c++17 -O3 -ffp-contract=off -fPIC -Wall -Wextra -Wno-subobject-linkage -pthread -shared -o $@ tests/cpp/bump_oracle.cpp
 
 $(LIB):
 	mkdir -p $(LIB)
 
 # (the compiler's resource-usage remarks of the product build are kept: lib/kernel_resources.json - registers, spills,
 # scratch bytes per lane, LDS of every kernel - is what bench.py quotes as roofline.scratch_bytes_per_lane)
-# (the motion kernels, rtc_motion.hip, and the spot kernels, rtc_spot.hip, are render_body of rtc_kernels.hip in
-# translation units of their own: the file of every other kernel compiles as before; the JSON holds the kernels of all)
+# (the motion kernels, rtc_motion.hip, the spot kernels, rtc_spot.hip, and the bump kernels, rtc_bump.hip, are render_body
+# of rtc_kernels.hip in translation units of their own: the file of every other kernel compiles as before; the JSON holds the kernels of all)
 $(LIB)/rtc_kernels.o: $(PKG)/csrc/rtc_kernels.hip $(PKG)/csrc/rtc_device.h | $(LIB)
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o $@ $< 2> $(LIB)/rtc_kernels.remarks || (grep -v "remark:" $(LIB)/rtc_kernels.remarks >&2; exit 1)
 	@grep -v "remark:\|remarks generated\|\^\|^ *[0-9]* |" $(LIB)/rtc_kernels.remarks >&2 || true
@@ -82,14 +87,18 @@ $(LIB)/rtc_spot.o: $(PKG)/csrc/rtc_spot.hip $(PKG)/csrc/rtc_kernels.hip $(PKG)/c
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o $@ $< 2> $(LIB)/rtc_spot.remarks || (grep -v "remark:" $(LIB)/rtc_spot.remarks >&2; exit 1)
 	@grep -v "remark:\|remarks generated\|\^\|^ *[0-9]* |" $(LIB)/rtc_spot.remarks >&2 || true
 
+$(LIB)/rtc_bump.o: $(PKG)/csrc/rtc_bump.hip $(PKG)/csrc/rtc_kernels.hip $(PKG)/csrc/rtc_device.h | $(LIB)
+	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o $@ $< 2> $(LIB)/rtc_bump.remarks || (grep -v "remark:" $(LIB)/rtc_bump.remarks >&2; exit 1)
+	@grep -v "remark:\|remarks generated\|\^\|^ *[0-9]* |" $(LIB)/rtc_bump.remarks >&2 || true
+
 # (rtc_kernels_ext.hip: in the -DRTC_PROFILE diagnostic build the csg / texture-map, flat and area-light kernels, in a
 # unit of their own so that the instrumented render kernels do not compile in one; in the product build it holds none)
 $(LIB)/rtc_kernels_ext.o: $(PKG)/csrc/rtc_kernels_ext.hip $(PKG)/csrc/rtc_kernels.hip $(PKG)/csrc/rtc_device.h | $(LIB)
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o $@ $< 2> $(LIB)/rtc_kernels_ext.remarks || (grep -v "remark:" $(LIB)/rtc_kernels_ext.remarks >&2; exit 1)
 	@grep -v "remark:\|remarks generated\|\^\|^ *[0-9]* |" $(LIB)/rtc_kernels_ext.remarks >&2 || true
 
-$(LIB)/kernel_resources.json: $(LIB)/rtc_kernels.o $(LIB)/rtc_kernels_ext.o $(LIB)/rtc_motion.o $(LIB)/rtc_spot.o tools/kernel_resources.py
-	cat $(LIB)/rtc_kernels.remarks $(LIB)/rtc_kernels_ext.remarks $(LIB)/rtc_motion.remarks $(LIB)/rtc_spot.remarks > $(LIB)/render_kernels.remarks
+$(LIB)/kernel_resources.json: $(LIB)/rtc_kernels.o $(LIB)/rtc_kernels_ext.o $(LIB)/rtc_motion.o $(LIB)/rtc_spot.o $(LIB)/rtc_bump.o tools/kernel_resources.py
+	cat $(LIB)/rtc_kernels.remarks $(LIB)/rtc_kernels_ext.remarks $(LIB)/rtc_motion.remarks $(LIB)/rtc_spot.remarks $(LIB)/rtc_bump.remarks > $(LIB)/render_kernels.remarks
 	python3 tools/kernel_resources.py --from-remarks $(LIB)/render_kernels.remarks --json $@
 
 $(LIB)/rtc_capi.o: $(PKG)/csrc/rtc_capi.hip $(wildcard $(PKG)/csrc/*.h) include/rtc.h | $(LIB)
@@ -103,7 +112,7 @@ $(LIB)/rtc_accum.o: $(PKG)/csrc/rtc_accum.hip $(PKG)/csrc/rtc_device.h | $(LIB)
 $(LIB)/rtc_adaptive.o: $(PKG)/csrc/rtc_adaptive.hip $(PKG)/csrc/rtc_device.h | $(LIB)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
-$(LIB)/librtc_hip.so: $(LIB)/rtc_kernels.o $(LIB)/rtc_kernels_ext.o $(LIB)/rtc_motion.o $(LIB)/rtc_spot.o $(LIB)/rtc_capi.o $(LIB)/rtc_accum.o $(LIB)/rtc_adaptive.o | $(LIB)/kernel_resources.json
+$(LIB)/librtc_hip.so: $(LIB)/rtc_kernels.o $(LIB)/rtc_kernels_ext.o $(LIB)/rtc_motion.o $(LIB)/rtc_spot.o $(LIB)/rtc_bump.o $(LIB)/rtc_capi.o $(LIB)/rtc_accum.o $(LIB)/rtc_adaptive.o | $(LIB)/kernel_resources.json
 	$(HIPCC) --offload-arch=gfx950 -shared -fPIC -o $@ $^
 
 $(LIB)/librtc_multi.so: $(PKG)/csrc/rtc_multi.hip include/rtc_multi.h include/rtc.h $(LIB)/librtc_hip.so

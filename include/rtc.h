@@ -401,6 +401,51 @@ typedef struct rtc_spot {
  */
 int rtc_scene_set_spots(rtc_scene *scene, const rtc_spot *spots);
 
+/* ---- normal perturbation: materials whose shading normal is bumped ---- */
+/*
+ * A bump belongs to a material row (mat_* tables).  For a hit on a leaf whose material has one, PreComputations.new
+ * (world.zig:196-250) changes in one place.  With lp the hit point in object space and ln the local normal exactly as
+ * Shape.normalAt (shape.zig:338-350) computes them (for a moving root: through p - tm * D, as rtc_scene_set_motion says):
+ *  1. The geometric normal ng is normalToWorld(ln), negated when dot(ng, eyev) < 0 (`inside`), as without a bump.
+ *     `inside`, over_point, under_point, the containers walk and n1 / n2 use ng and nothing else: a bump never changes
+ *     which object a shadow, reflected or refracted ray starts inside or outside of.
+ *  2. The shading normal ns: m = sqrt((ln.x * ln.x + ln.y * ln.y) + ln.z * ln.z) (tuple.zig's normalize); m == 0 gives
+ *     ns = ng.  Otherwise u = ln / m, q = B * lp with B = inverse[12] (rows 0..2 of a 4 x 4 affine inverse transform, each
+ *     row ((r0 * x + r1 * y) + r2 * z) + r3), d = field(q), ln' = u + d * amplitude (per component), ns =
+ *     normalToWorld(ln') (with its normalize), negated when `inside` is true - step 1's decision, not a new dot product.
+ *  3. ns replaces normalv in Material.lighting (point, spot and area lights alike), in reflectv, in refractedColor
+ *     (cos_i = dot(eyev, ns), and the refracted direction) and in schlick.  Nothing else reads it.
+ * The fields use + - * / sqrt floor fabs only, each operation correctly rounded, in the order written:
+ *   RTC_BUMP_NOISE    d = (N(q.x, q.y, q.z), N(q.x, q.y, q.z + 1.0), N(q.x, q.y, q.z + 2.0)), N = octaveNoise(...,
+ *                     octaves, persistence) of noise.zig:35-49 - the three evaluations of perturb.zig:31-43.
+ *   RTC_BUMP_RIPPLES  around the field's y axis: r = sqrt(q.x * q.x + q.z * q.z); r == 0 gives d = 0; otherwise
+ *                     v = 2.0 * (r - floor(r)) - 1.0, h = (4.0 * v) * (1.0 - fabs(v)), d = (h * (q.x / r), 0, h * (q.z / r)).
+ * A material of kind RTC_BUMP_NONE, or of amplitude 0 whatever its kind, takes the unperturbed branch: ln is never
+ * normalized first, ns is ng, and its pixels have the bits they have without a bump table (its other fields are not read).
+ */
+#define RTC_BUMP_NONE 0u
+#define RTC_BUMP_NOISE 1u
+#define RTC_BUMP_RIPPLES 2u
+#define RTC_BUMP_MAX_OCTAVES 16u
+
+typedef struct rtc_bump {
+  uint32_t n_materials;       /* the handle's material count                                          */
+  const uint8_t *kind;        /* [n_materials]: RTC_BUMP_*                                            */
+  const double *amplitude;    /* [n_materials]: >= 0                                                  */
+  const uint32_t *octaves;    /* [n_materials]: 1 .. RTC_BUMP_MAX_OCTAVES (RTC_BUMP_NOISE; PerturbInfo's default is 3) */
+  const double *persistence;  /* [n_materials]: finite (RTC_BUMP_NOISE; PerturbInfo's default is 0.8)   */
+  const double *inverse;      /* [n_materials][12]: B, rows 0..2; NULL: the identity for every material */
+} rtc_bump;
+
+/*
+ * This handle's bumps for every render entry point (NULL, or every material unperturbed: the handle's previous kernels and
+ * their bits).  Validated before anything changes: RTC_ERR_INVALID_ARGUMENT for n_materials other than the handle's, an
+ * unknown kind, a value that is not finite (the matrix included), a negative amplitude, or octaves of 0 or above
+ * RTC_BUMP_MAX_OCTAVES.  A clone starts with its source's bumps; rtc_render's band clones follow.  librtc_multi renders
+ * without bumps.
+ */
+int rtc_scene_set_bumps(rtc_scene *scene, const rtc_bump *bumps);
+
 /* ---- adaptive sampling: progressive passes only for tiles still noisy ---- */
 #define RTC_ADAPTIVE_MAX_TILE 1024u
 

@@ -33,7 +33,8 @@ extern "C" {
  * that their one-sample images can be held to the other kernels'), "motion_kernels" (!= 0: the motion kernels even on a
  * static handle, with every displacement zero, so that their images can be held to the sampling kernels'), "spot_kernels"
  * (!= 0: the spot kernels even on a handle without cones, every flag zero, so that their images can be held to the
- * motion kernels').
+ * motion kernels'), "bump_kernels" (!= 0: the bump kernels even on a handle without bumps, every row of kind none, so that
+ * their images can be held to the spot kernels').
  * RTC_ERR_INVALID_ARGUMENT for a name the library does not know.
  * (The library reads no environment variables.)
  */

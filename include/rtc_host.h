@@ -19,7 +19,8 @@
  *                        rtch_scene_passes, through rtc_scene_set_sample_pass, averaged on the host; the
  *                        top-level objects' motion, rtch_scene_motion, through rtc_scene_set_motion; its adaptive
  *                        sampling, rtch_scene_adaptive, through rtc_render_adaptive; its spot lights,
- *                        rtch_scene_spots, through rtc_scene_set_spots)
+ *                        rtch_scene_spots, through rtc_scene_set_spots; its materials' normal perturbation,
+ *                        rtch_scene_bumps, through rtc_scene_set_bumps)
  *
  * Every function that returns int returns 0 on success; otherwise rtch_last_error()
  * holds "<ZigStyleErrorName>: detail" (thread-local).
@@ -70,6 +71,12 @@ int rtch_scene_motion(void *handle, double *out, uint32_t n);
  * cone[i] 0 for every other light; n must be the light table's n_lights.  Pass them to rtc_scene_set_spots.
  * rtch_scene_render applies them; rtch_scene_lights reports a spot as the point light it is. */
 int rtch_scene_spots(void *handle, uint8_t *cone, double *axis, double *cos_inner, double *cos_outer, uint32_t n);
+/* The materials' "normal-perturbation" entries, in mat_* order: {"type": "noise" | "ripples",
+ * "amplitude": a >= 0, "octaves": 1 .. RTC_BUMP_MAX_OCTAVES (3), "persistence": p (0.8), "transform": a pattern's list};
+ * kind[i] RTC_BUMP_* (RTC_BUMP_NONE for a material without the key), inverse[12 i ..] rows 0..2 of the transform's
+ * inverse; n must be the description's n_materials.  A material with the key is a mat_* row of its own.  Pass them to
+ * rtc_scene_set_bumps.  rtch_scene_render applies them. */
+int rtch_scene_bumps(void *handle, uint8_t *kind, double *amplitude, uint32_t *octaves, double *persistence, double *inverse, uint32_t n);
 int rtch_scene_camera(void *handle, uint32_t width, uint32_t height, rtc_camera *out);
 int rtch_camera_rotate(void *handle, double angle);
 int rtch_camera_move(void *handle, double distance);

@@ -216,6 +216,41 @@ def spot_struct(spots):
     return sp, (cone, axis, ci, co)
 
 
+BUMP_NONE, BUMP_NOISE, BUMP_RIPPLES = 0, 1, 2  # RTC_BUMP_*
+BUMP_MAX_OCTAVES = 16  # RTC_BUMP_MAX_OCTAVES
+
+
+class Bump(C.Structure):
+    """struct rtc_bump (include/rtc.h): a bump per material row (kind BUMP_NONE: the material as it is)."""
+
+    _fields_ = [("n_materials", C.c_uint32), ("kind", C.POINTER(C.c_uint8)), ("amplitude", C.POINTER(C.c_double)),
+                ("octaves", C.POINTER(C.c_uint32)), ("persistence", C.POINTER(C.c_double)), ("inverse", C.POINTER(C.c_double))]
+
+
+def no_bumps(n_materials):
+    """Every kind BUMP_NONE, with PerturbInfo's defaults and identity transforms: a dict as GpuScene.set_bumps takes."""
+    inv = np.zeros((n_materials, 12))
+    inv[:, [0, 5, 10]] = 1.0
+    return {"kind": np.zeros(n_materials, dtype=np.uint8), "amplitude": np.zeros(n_materials),
+            "octaves": np.full(n_materials, 3, dtype=np.uint32), "persistence": np.full(n_materials, 0.8), "inverse": inv}
+
+
+def bump_struct(bumps):
+    """(Bump, the arrays it points into) of a dict of "kind", "amplitude", "octaves", "persistence", "inverse"
+    (GpuScene.set_bumps); the arrays must outlive the struct's use."""
+    kind = np.ascontiguousarray(bumps["kind"], dtype=np.uint8)
+    amp = np.ascontiguousarray(bumps["amplitude"], dtype=np.float64)
+    octv = np.ascontiguousarray(bumps["octaves"], dtype=np.uint32)
+    per = np.ascontiguousarray(bumps["persistence"], dtype=np.float64)
+    inv = np.ascontiguousarray(bumps["inverse"], dtype=np.float64)
+    n = kind.shape[0]
+    if kind.ndim != 1 or amp.shape != (n,) or octv.shape != (n,) or per.shape != (n,) or inv.shape != (n, 12):
+        raise ValueError(f"bumps: kind {kind.shape}, amplitude {amp.shape}, octaves {octv.shape}, persistence {per.shape}, inverse {inv.shape}")
+    b = Bump(n, kind.ctypes.data_as(C.POINTER(C.c_uint8)), amp.ctypes.data_as(C.POINTER(C.c_double)),
+             octv.ctypes.data_as(C.POINTER(C.c_uint32)), per.ctypes.data_as(C.POINTER(C.c_double)), inv.ctypes.data_as(C.POINTER(C.c_double)))
+    return b, (kind, amp, octv, per, inv)
+
+
 # (include/rtc.h: what a host binds ...)
 RTC_SYMBOLS = ["rtc_scene_create", "rtc_scene_clone", "rtc_scene_destroy", "rtc_render", "rtc_render_rgba8", "rtc_render_device",
                "rtc_render_tiles_device", "rtc_assemble_tiles_device", "rtc_render_tile_list_device", "rtc_get_tile_costs",
@@ -225,13 +260,13 @@ RTC_SYMBOLS = ["rtc_scene_create", "rtc_scene_clone", "rtc_scene_destroy", "rtc_
                "rtc_scene_create_with_lights", "rtc_scene_set_light_seed", "rtc_scene_set_sampling",
                "rtc_scene_set_sample_pass", "rtc_scene_accumulate_device", "rtc_scene_set_motion",
                "rtc_scene_adaptive_begin_device", "rtc_scene_adaptive_accumulate_device", "rtc_scene_adaptive_step", "rtc_render_adaptive",
-               "rtc_scene_set_spots"]
+               "rtc_scene_set_spots", "rtc_scene_set_bumps"]
 # (... and include/rtc_diag.h: diagnostics and tuning, for the tests, bench.py and tools/)
 RTC_DIAG_SYMBOLS = ["rtc_set_option", "rtc_last_kernel_name", "rtc_get_schedule", "rtc_get_chunk_times", "rtc_diag_build_tables", "rtc_diag_root_boxes"]
 HOST_SYMBOLS = ["rtch_last_error", "rtch_scene_load", "rtch_scene_free", "rtch_scene_desc", "rtch_scene_camera",
                 "rtch_camera_rotate", "rtch_camera_move", "rtch_camera_make", "rtch_canvas_ppm", "rtch_canvas_rgba8", "rtch_scene_render", "rtch_set_loader_threads",
                 "rtch_scene_lights", "rtch_scene_sampling", "rtch_scene_passes", "rtch_scene_motion", "rtch_scene_adaptive",
-                "rtch_scene_spots"]
+                "rtch_scene_spots", "rtch_scene_bumps"]
 
 MULTI_SYMBOLS = ["rtc_multi_create", "rtc_multi_destroy", "rtc_multi_render", "rtc_multi_render_rgba8", "rtc_multi_render_device", "rtc_multi_render_rgba8_device",
                  "rtc_multi_synchronize", "rtc_multi_stream", "rtc_multi_get_stats", "rtc_multi_balance", "rtc_multi_last_error"]
@@ -292,6 +327,7 @@ def hip_lib():
         lib.rtc_scene_adaptive_step.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.POINTER(Adaptive), C.POINTER(AdaptiveState),
                                                 C.POINTER(C.c_uint32), C.c_void_p]
         lib.rtc_scene_set_spots.argtypes = [C.c_void_p, C.POINTER(Spot)]
+        lib.rtc_scene_set_bumps.argtypes = [C.c_void_p, C.POINTER(Bump)]
         lib.rtc_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.POINTER(Adaptive), C.c_void_p, C.c_void_p]
         lib.rtc_scene_destroy.argtypes = [C.c_void_p]
         lib.rtc_scene_destroy.restype = None
@@ -345,6 +381,7 @@ def host_lib():
         lib.rtch_scene_passes.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         lib.rtch_scene_motion.argtypes = [C.c_void_p, _dp, C.c_uint32]
         lib.rtch_scene_spots.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), _dp, _dp, _dp, C.c_uint32]
+        lib.rtch_scene_bumps.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), _dp, C.POINTER(C.c_uint32), _dp, _dp, C.c_uint32]
         lib.rtch_scene_adaptive.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(Adaptive)]
         lib.rtch_scene_camera.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Camera)]
         lib.rtch_camera_rotate.argtypes = [C.c_void_p, C.c_double]
@@ -520,6 +557,17 @@ class HostScene:
                                                 out["cos_inner"].ctypes.data_as(_dp), out["cos_outer"].ctypes.data_as(_dp), n))
         return out if out["cone"].any() else None
 
+    def bumps(self):
+        """The materials' "normal-perturbation" entries (rtch_scene_bumps), in mat_* order: a dict of "kind" (n,) uint8,
+        "amplitude" (n,), "octaves" (n,) uint32, "persistence" (n,) and "inverse" (n, 12) - what GpuScene.set_bumps takes -,
+        or None when no material has one."""
+        n = self.desc.n_materials
+        out = no_bumps(n)
+        _check_host(host_lib().rtch_scene_bumps(self._h, out["kind"].ctypes.data_as(C.POINTER(C.c_uint8)), out["amplitude"].ctypes.data_as(_dp),
+                                                out["octaves"].ctypes.data_as(C.POINTER(C.c_uint32)), out["persistence"].ctypes.data_as(_dp),
+                                                out["inverse"].ctypes.data_as(_dp), n))
+        return out if out["kind"].any() else None
+
     def adaptive(self):
         """The camera's "sampling": {"adaptive": ...} of the scene file (rtch_scene_adaptive): an Adaptive whose max_passes
         is "passes", or None when the file has none."""
@@ -615,6 +663,15 @@ class GpuScene:
             return
         sp, _keep = spot_struct(spots)
         _check_hip(hip_lib().rtc_scene_set_spots(self._s, C.byref(sp)))
+
+    def set_bumps(self, bumps):
+        """rtc_scene_set_bumps: a dict of "kind" (n_materials,) BUMP_*, "amplitude", "octaves", "persistence" (n_materials,)
+        and "inverse" (n_materials, 12), one entry per material row (HostScene.bumps(), no_bumps()); None: no bumps."""
+        if bumps is None:
+            _check_hip(hip_lib().rtc_scene_set_bumps(self._s, None))
+            return
+        b, _keep = bump_struct(bumps)
+        _check_hip(hip_lib().rtc_scene_set_bumps(self._s, C.byref(b)))
 
     def accumulate_device(self, accum, stream=None):
         """rtc_scene_accumulate_device: an Accum, enqueued on `stream` (None: the handle's own) after this handle's renders."""

@@ -109,6 +109,17 @@ __global__ void rtc_render_kernel_spot_bigworld(const DevScene S, const DevCamer
                                                 double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
                                                 const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots);
 }
+// The bump kernels (rtc_scene_set_bumps: materials whose shading normal is perturbed): the spot kernels' tables and edge.
+extern "C" {
+__global__ void rtc_render_kernel_bump(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                       double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                       const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                       const DevBumps bumps);
+__global__ void rtc_render_kernel_bump_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                                double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                                const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                                const DevBumps bumps);
+}
 // Progressive rendering's accumulation (rtc_accum.hip): the grid's blocks for n pixels (the noise partials it writes, at
 // most) and the enqueue of its kernels.
 uint32_t rtcAccumBlocks(size_t n_pixels, bool wide);
@@ -323,7 +334,7 @@ bool tablesInLds(const rtc_scene* s) {
 
 // (the area kernels take one more argument, DevAreaLights: `area` instead of `fn`; the sampling kernels DevSampling:
 // `ms`, and both: `area_ms`; the motion kernels both and DevMotion: `motion`; the spot kernels those three and DevSpots:
-// `spot`)
+// `spot`; the bump kernels those four and DevBumps: `bump`)
 struct KernelChoice {
   decltype(&rtc_render_kernel) fn;
   const char* name;
@@ -332,17 +343,19 @@ struct KernelChoice {
   decltype(&rtc_render_kernel_area_ms) area_ms = nullptr;
   decltype(&rtc_render_kernel_motion) motion = nullptr;
   decltype(&rtc_render_kernel_spot) spot = nullptr;
+  decltype(&rtc_render_kernel_bump) bump = nullptr;
   KernelChoice(decltype(&rtc_render_kernel) f, const char* n) : fn(f), name(n) {}
   KernelChoice(decltype(&rtc_render_kernel_area) a, const char* n) : fn(nullptr), name(n), area(a) {}
   KernelChoice(decltype(&rtc_render_kernel_ms) m, const char* n) : fn(nullptr), name(n), ms(m) {}
   KernelChoice(decltype(&rtc_render_kernel_area_ms) am, const char* n) : fn(nullptr), name(n), area_ms(am) {}
   KernelChoice(decltype(&rtc_render_kernel_motion) mo, const char* n) : fn(nullptr), name(n), motion(mo) {}
   KernelChoice(decltype(&rtc_render_kernel_spot) sk, const char* n) : fn(nullptr), name(n), spot(sk) {}
+  KernelChoice(decltype(&rtc_render_kernel_bump) bk, const char* n) : fn(nullptr), name(n), bump(bk) {}
   void launch(uint32_t blocks, hipStream_t stream, const rtc_scene* s, const DevScene& dev, const DevCamera& cam, const DevPixelMap& map,
               uint32_t max_depth, double* d_out, DevStats* st_now, DevStats* st_next) const {
     DevSampling smp = s->sampling;  // (the pass's area-light offset, P * N * S: N is the camera's whole image)
     smp.pixel_base = static_cast<unsigned long long>(smp.sample_base) * (static_cast<unsigned long long>(cam.hsize) * cam.vsize);
-    if (motion || spot) {
+    if (motion || spot || bump) {
       // the handle's root tables with the moving roots' bounds (or the scene's, all displacements zero: the option), and
       // the scene's area rows (or zero rows: a point-only table); the spot kernels also the handle's spot rows (or zero
       // rows, every flag 0: the option)
@@ -358,7 +371,11 @@ struct KernelChoice {
         mo.disp = m->disp.p;
       }
       const DevAreaLights area = s->area_kernel ? s->area : DevAreaLights{s->tab->zero_rows.p, s->area.seed};
-      if (spot) {
+      if (bump) {  // (the handle's bump rows, or zero rows, every kind none: the option)
+        const DevSpots sp{s->spots ? s->spots->row.p : s->tab->zero_rows.p};
+        const DevBumps bp{s->bumps ? s->bumps->row.p : s->tab->zero_bump.p};
+        hipLaunchKernelGGL(bump, dim3(blocks), dim3(256), 0, stream, md, cam, map, max_depth, d_out, st_now, st_next, area, smp, mo, sp, bp);
+      } else if (spot) {
         const DevSpots sp{s->spots ? s->spots->row.p : s->tab->zero_rows.p};
         hipLaunchKernelGGL(spot, dim3(blocks), dim3(256), 0, stream, md, cam, map, max_depth, d_out, st_now, st_next, area, smp, mo, sp);
       } else {
@@ -383,6 +400,9 @@ bool motionKernels(const rtc_scene* s) { return s->motion != nullptr || rtcOptio
 // The spot kernels run when a light of the handle has a cone - whatever the sampling, the pass and the motion - or, for
 // tests, whenever option "spot_kernels" is set.
 bool spotKernels(const rtc_scene* s) { return s->spots != nullptr || rtcOptions().spot_kernels != 0.0; }
+// The bump kernels run when a material of the handle has a bump - whatever the sampling, the pass, the motion and the
+// cones - or, for tests, whenever option "bump_kernels" is set.
+bool bumpKernels(const rtc_scene* s) { return s->bumps != nullptr || rtcOptions().bump_kernels != 0.0; }
 #define RTC_KERNEL(k) KernelChoice{k, #k}
 // The general kernel at three waves per SIMD (rtc_render_kernel3): forced by option "waves3", else what the handle's
 // trial measured (KernelTune in launch()).
@@ -409,6 +429,7 @@ KernelChoice ldsKernel(const rtc_scene* s, const DevPixelMap& map) {
   return s->ext_kernel ? RTC_KERNEL(rtc_render_kernel_ext) : RTC_KERNEL(rtc_render_kernel);
 }
 KernelChoice renderKernel(const rtc_scene* s, const DevPixelMap& map) {
+  if (bumpKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_bump) : RTC_KERNEL(rtc_render_kernel_bump_bigworld);
   if (spotKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_spot) : RTC_KERNEL(rtc_render_kernel_spot_bigworld);
   if (motionKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_motion) : RTC_KERNEL(rtc_render_kernel_motion_bigworld);
   if (samplingKernels(s)) {
@@ -423,6 +444,7 @@ KernelChoice renderKernel(const rtc_scene* s, const DevPixelMap& map) {
 
 // Work-groups of the launch's kernel that are resident at once, and the waves in them.
 uint32_t residentBlocksAlone(const rtc_scene* s, const DevPixelMap& map) {
+  if (bumpKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_bump_lds : s->blocks_per_cu_bump_big);
   if (spotKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_spot_lds : s->blocks_per_cu_spot_big);
   if (motionKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_motion_lds : s->blocks_per_cu_motion_big);
   if (samplingKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_ms_lds : s->blocks_per_cu_ms_big);
@@ -829,7 +851,7 @@ int launch(rtc_scene* s, const rtc_camera& cam, const DevPixelMap& map_in, uint3
   int trial_slot = -1;
   {
     rtc_scene::KernelTune& T = s->tune;
-    const bool eligible = !samplingKernels(s) && !motionKernels(s) && !spotKernels(s) &&  // (the sampling, motion and spot kernels have no three-wave form)
+    const bool eligible = !samplingKernels(s) && !motionKernels(s) && !spotKernels(s) && !bumpKernels(s) &&  // (the sampling, motion, spot and bump kernels have no three-wave form)
                           ((s->general3_ok && rtcOptions().waves3 < 0.0 && tablesInLds(s) &&
                             !(s->tab && s->tab->handles.load(std::memory_order_relaxed) > 1) &&
                             static_cast<double>(map.n_chunks) >= 4.0 * 4.0 * s->n_cus * s->blocks_per_cu_lds) ||
@@ -2031,6 +2053,7 @@ int uploadTables(const rtc_scene_desc& d, const SceneTraits& traits, const HostT
     s->tab->h_root_order = T.root_order;
     HIP_TRY(s->tab->zero_disp.upload(std::vector<double>(3ull * root_recs.size(), 0.0)));
     HIP_TRY(s->tab->zero_rows.upload(std::vector<double>(static_cast<size_t>(RTC_AREA_ROW) * d.n_lights, 0.0)));
+    HIP_TRY(s->tab->zero_bump.upload(std::vector<double>(static_cast<size_t>(RTC_BUMP_ROW) * d.n_materials, 0.0)));
   }
   HIP_TRY(s->tab->root_weight.upload(T.root_weight));
   HIP_TRY(s->tab->kids.upload(kids));
@@ -2181,11 +2204,16 @@ int uploadTables(const rtc_scene_desc& d, const SceneTraits& traits, const HostT
     s->blocks_per_cu_spot_lds = static_cast<uint32_t>(std::max(nb, 1));
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_spot_bigworld, 256, 0));
     s->blocks_per_cu_spot_big = static_cast<uint32_t>(std::max(nb, 1));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_bump, 256, 0));  // (the bump kernels: one pair for every world)
+    s->blocks_per_cu_bump_lds = static_cast<uint32_t>(std::max(nb, 1));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_bump_bigworld, 256, 0));
+    s->blocks_per_cu_bump_big = static_cast<uint32_t>(std::max(nb, 1));
     if (const int v = static_cast<int>(rtcOptions().blocks_per_cu); v >= 1) {  // (tuning option)
       s->blocks_per_cu_lds = std::min<uint32_t>(s->blocks_per_cu_lds, v), s->blocks_per_cu_big = std::min<uint32_t>(s->blocks_per_cu_big, v);
       s->blocks_per_cu_ms_lds = std::min<uint32_t>(s->blocks_per_cu_ms_lds, v), s->blocks_per_cu_ms_big = std::min<uint32_t>(s->blocks_per_cu_ms_big, v);
       s->blocks_per_cu_motion_lds = std::min<uint32_t>(s->blocks_per_cu_motion_lds, v), s->blocks_per_cu_motion_big = std::min<uint32_t>(s->blocks_per_cu_motion_big, v);
       s->blocks_per_cu_spot_lds = std::min<uint32_t>(s->blocks_per_cu_spot_lds, v), s->blocks_per_cu_spot_big = std::min<uint32_t>(s->blocks_per_cu_spot_big, v);
+      s->blocks_per_cu_bump_lds = std::min<uint32_t>(s->blocks_per_cu_bump_lds, v), s->blocks_per_cu_bump_big = std::min<uint32_t>(s->blocks_per_cu_bump_big, v);
     }
   }
   DevScene& D = s->dev;
@@ -2649,6 +2677,68 @@ int rtc_scene_set_spots(rtc_scene* s, const rtc_spot* spots) {
   return RTC_OK;
 }
 
+// ---- normal perturbation
+// Validated before anything changes: first the table's own values - so that they are checked whatever the handle -, then
+// its material count against the handle's.  A row of kind none or of amplitude 0 is stored as kind none (the kernels'
+// unperturbed branch); every row so is no bump: the handle's previous kernels.
+int rtc_scene_set_bumps(rtc_scene* s, const rtc_bump* bumps) {
+  g_error.clear();
+  if (!s) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
+  bool any = false;
+  std::vector<double> rows;
+  if (bumps) {
+    const uint32_t n = bumps->n_materials;
+    if (n != 0u && !bumps->kind) return fail(RTC_ERR_INVALID_ARGUMENT, "bumps: null kind");
+    bool named = false, noise = false;
+    for (uint32_t i = 0; i < n; ++i) {
+      if (bumps->kind[i] > RTC_BUMP_RIPPLES) return fail(RTC_ERR_INVALID_ARGUMENT, "bumps: kind %u of material %u", bumps->kind[i], i);
+      named = named || bumps->kind[i] != RTC_BUMP_NONE;
+      noise = noise || bumps->kind[i] == RTC_BUMP_NOISE;
+    }
+    if (named && !bumps->amplitude) return fail(RTC_ERR_INVALID_ARGUMENT, "bumps: null amplitude");
+    if (noise && (!bumps->octaves || !bumps->persistence)) return fail(RTC_ERR_INVALID_ARGUMENT, "bumps: null octaves or persistence");
+    rows.assign(static_cast<size_t>(RTC_BUMP_ROW) * n, 0.0);
+    for (uint32_t i = 0; i < n; ++i) {
+      if (bumps->kind[i] == RTC_BUMP_NONE) continue;  // (its other fields are not read)
+      const double amp = bumps->amplitude[i];
+      if (!std::isfinite(amp)) return fail(RTC_ERR_INVALID_ARGUMENT, "bumps: material %u: an amplitude that is not finite", i);
+      if (amp < 0.0) return fail(RTC_ERR_INVALID_ARGUMENT, "bumps: material %u: amplitude %g below 0", i, amp);
+      double* r = rows.data() + static_cast<size_t>(RTC_BUMP_ROW) * i;
+      if (bumps->kind[i] == RTC_BUMP_NOISE) {
+        const uint32_t oct = bumps->octaves[i];
+        if (oct == 0u || oct > RTC_BUMP_MAX_OCTAVES)
+          return fail(RTC_ERR_INVALID_ARGUMENT, "bumps: material %u: %u octaves (1 to %u)", i, oct, RTC_BUMP_MAX_OCTAVES);
+        if (!std::isfinite(bumps->persistence[i]))
+          return fail(RTC_ERR_INVALID_ARGUMENT, "bumps: material %u: a persistence that is not finite", i);
+        r[13] = bumps->persistence[i];
+        r[15] = static_cast<double>(oct);
+      }
+      for (int k = 0; k < 12; ++k) {
+        const double v = bumps->inverse ? bumps->inverse[12ull * i + k] : (k == 0 || k == 5 || k == 10 ? 1.0 : 0.0);
+        if (!std::isfinite(v)) return fail(RTC_ERR_INVALID_ARGUMENT, "bumps: material %u: a matrix entry that is not finite", i);
+        r[k] = v;
+      }
+      r[12] = amp;
+      r[14] = amp == 0.0 ? 0.0 : static_cast<double>(bumps->kind[i]);
+      any = any || amp != 0.0;
+    }
+    if (n != s->dev.n_materials) return fail(RTC_ERR_INVALID_ARGUMENT, "bumps: n_materials %u, the scene has %u", n, s->dev.n_materials);
+  }
+  std::shared_ptr<const BumpTables> tables;  // (no bump: none)
+  if (any) {
+    auto t = std::make_shared<BumpTables>();
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(t->row.upload(rows));
+    tables = std::move(t);
+  }
+  // (the rows being replaced may still be read by a launch of this handle or of its band clones)
+  HIP_TRY(handleIdle(s));
+  for (rtc_scene* b : s->band) HIP_TRY(handleIdle(b));
+  s->bumps = tables;
+  for (rtc_scene* b : s->band) b->bumps = tables;  // (the band clones rtc_render renders a large frame with)
+  return RTC_OK;
+}
+
 // ---- adaptive sampling
 // The setting's own fields, and the image's tile count (T < 2^31)
 static int checkAdaptive(const rtc_adaptive* a, uint32_t hsize, uint32_t vsize, uint32_t* n_tiles) {
@@ -2857,6 +2947,9 @@ int rtc_scene_clone(const rtc_scene* src, rtc_scene** out) {
   s->spots = src->spots;  // (shared: read-only once made)
   s->blocks_per_cu_spot_lds = src->blocks_per_cu_spot_lds;
   s->blocks_per_cu_spot_big = src->blocks_per_cu_spot_big;
+  s->bumps = src->bumps;  // (shared: read-only once made)
+  s->blocks_per_cu_bump_lds = src->blocks_per_cu_bump_lds;
+  s->blocks_per_cu_bump_big = src->blocks_per_cu_bump_big;
   s->simple_kernel = src->simple_kernel;
   s->flat_kernel = src->flat_kernel;
   s->simple3_ok = src->simple3_ok;
@@ -3254,7 +3347,7 @@ int rtc_set_option(const char* name, double value) {
                {"measure_every", &o.measure_every}, {"sched_mix", &o.sched_mix},
                {"inflight_chunks_per_wave", &o.inflight_chunks_per_wave}, {"build_threads", &o.build_threads}, {"box_cull", &o.box_cull},
                {"sampling_kernels", &o.sampling_kernels}, {"motion_kernels", &o.motion_kernels},
-               {"spot_kernels", &o.spot_kernels}};
+               {"spot_kernels", &o.spot_kernels}, {"bump_kernels", &o.bump_kernels}};
   for (const auto& e : table)
     if (std::strcmp(e.name, name) == 0) {
       e.slot->set(value);

@@ -339,6 +339,15 @@ __host__ __device__ inline double rtc_spot_factor(double c, double cos_inner, do
   return (s * s) * (3.0 - 2.0 * s);
 }
 
+// Normal perturbation (rtc_scene_set_bumps): the extra argument of the bump kernels only.  One row
+// of RTC_BUMP_ROW doubles per material, in mat_* order: the bump's inverse transform B (3x4, rows 0..2), the amplitude,
+// the persistence, the kind (0.0 none, 1.0 RTC_BUMP_NOISE, 2.0 RTC_BUMP_RIPPLES) and the octaves.  A row of amplitude 0 is
+// stored as kind none; every row under the "bump_kernels" option on a handle without bumps is zero.
+#define RTC_BUMP_ROW 16u
+struct DevBumps {
+  const double* __restrict__ row;  // [n_materials][RTC_BUMP_ROW]
+};
+
 struct DevCamera {
   double half_width, half_height, pixel_size;
   double inv[12];  // rows 0..2 of Camera._inverse_transform

@@ -68,6 +68,7 @@ struct RtcOptions {
   RtcOption sampling_kernels{0.0};     // != 0: the sampling kernels even with the default sampling (tests: one sample against the other kernels)
   RtcOption motion_kernels{0.0};       // != 0: the motion kernels even on a static handle, all displacements zero (tests: against the _ms kernels)
   RtcOption spot_kernels{0.0};         // != 0: the spot kernels even on a handle without cones, every flag zero (tests: against the motion kernels)
+  RtcOption bump_kernels{0.0};         // != 0: the bump kernels even on a handle without bumps, every row of kind none (tests: against the spot kernels)
   RtcOption build_threads{0.0};        // threads of rtc_scene_create's candidate-BVH build (one top-level group each); 0: as many as the host allows, up to 8
 };
 inline RtcOptions& rtcOptions() {
@@ -137,6 +138,14 @@ struct SceneTables {
   // spot lights (rtc_scene_set_spots): which lights are area lights (a cone on one is refused); a handle without cones
   // passes zero_rows to the spot kernels as its spot rows (RTC_SPOT_ROW <= RTC_AREA_ROW: every flag zero)
   std::vector<uint8_t> h_light_area;
+  // normal perturbation (rtc_scene_set_bumps): the bump rows of a handle without bumps under the "bump_kernels" option
+  // (RTC_BUMP_ROW zeros per material: every kind none)
+  DevBuf<double> zero_bump;
+};
+
+// A handle's bumps (rtc_scene_set_bumps): DevBumps::row.  Read-only once made: a clone and the band clones share it.
+struct BumpTables {
+  DevBuf<double> row;
 };
 
 // A handle's spot lights (rtc_scene_set_spots): DevSpots::row.  Read-only once made: a clone and the band clones share it.
@@ -187,6 +196,8 @@ struct rtc_scene {
   uint32_t blocks_per_cu_motion_lds = 1, blocks_per_cu_motion_big = 1;  // ... and of the motion kernels
   std::shared_ptr<const SpotTables> spots;  // rtc_scene_set_spots; null: no cones (a clone starts with its source's)
   uint32_t blocks_per_cu_spot_lds = 1, blocks_per_cu_spot_big = 1;  // ... and of the spot kernels
+  std::shared_ptr<const BumpTables> bumps;  // rtc_scene_set_bumps; null: no bumps (a clone starts with its source's)
+  uint32_t blocks_per_cu_bump_lds = 1, blocks_per_cu_bump_big = 1;  // ... and of the bump kernels
   bool simple3_ok = false;         // a simple world whose tables fit the three-waves-per-SIMD kernel's LDS (RTC_LDS3_*)
   void* d_csg_buf = nullptr;       // DevPixelMap::csg_buf, only for scenes with csg nodes
   size_t csg_buf_capacity = 0;     // bytes

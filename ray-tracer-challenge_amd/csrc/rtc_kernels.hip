@@ -1826,6 +1826,18 @@ __device__ __forceinline__ double octave_noise(double x, double y, double z, uin
   }
   return total / max_value;
 }
+// RTC_BUMP_RIPPLES (rtc.h, rtc_scene_set_bumps): a parabolic wave of period 1 around the field's y axis, along the radial
+// direction - + - * / sqrt floor fabs only, each correctly rounded, in the order the header writes them.
+__device__ __forceinline__ void bump_ripples(double qx, double qz, double& dx, double& dz) {
+  dx = 0.0;
+  dz = 0.0;
+  const double r = __builtin_sqrt(qx * qx + qz * qz);
+  if (r == 0.0) return;
+  const double v = 2.0 * (r - __builtin_floor(r)) - 1.0;
+  const double h = (4.0 * v) * (1.0 - __builtin_fabs(v));
+  dx = h * (qx / r);
+  dz = h * (qz / r);
+}
 
 // TextureMap.patternAt + UvPattern.uvPatternAt (texture_map.zig).  Returns the sub-pattern the uv pattern
 // selects (align check, uv checkers), or RTC_NO_LEAF with the colour in `out` (uv test pattern, uv image).
@@ -2320,17 +2332,21 @@ __device__ __forceinline__ Ray camera_sample(const DevCamera& cam, const DevSamp
 // and AREA, compiled into those kernels only)
 // (SPOT: point lights that shine into a cone - DevSpots, the spot kernels' extra argument; with MOTION, MS and AREA,
 // compiled into those kernels only)
+// (BUMP: materials whose shading normal is perturbed - DevBumps, the bump kernels' extra argument; with SPOT, MOTION, MS
+// and AREA, compiled into those kernels only)
 template <bool LDS, bool CSG, int WORLD = 0, int WAVES = 2, bool COOP = false, bool BOX = true, bool AREA = false, bool MS = false,
-          bool MOTION = false, bool SPOT = false>
+          bool MOTION = false, bool SPOT = false, bool BUMP = false>
 __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& cam, const DevPixelMap& map,
                                             const uint32_t max_depth, double* __restrict__ out,
                                             DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
                                             const DevAreaLights& area = DevAreaLights{}, const DevSampling& smp = DevSampling{},
-                                            const DevMotion& mo = DevMotion{}, const DevSpots& spots = DevSpots{}) {
+                                            const DevMotion& mo = DevMotion{}, const DevSpots& spots = DevSpots{},
+                                            const DevBumps& bumps = DevBumps{}) {
   static_assert(!AREA || !COOP, "the area kernels run no cooperative iterations");
   static_assert(!MS || !COOP, "the sampling kernels run no cooperative iterations");
   static_assert(!MOTION || (MS && AREA && WORLD == 0), "the motion kernels are the general area-sampling walk");
   static_assert(!SPOT || MOTION, "the spot kernels are the motion walk");
+  static_assert(!BUMP || SPOT, "the bump kernels are the spot walk");
   RTC_PRIO_PHASE(RTC_PRIO_WORK);
 #ifndef RTC_PROFILE
   if (blockIdx.x == 0u) {  // the next launch's counters (see DevStats)
@@ -3063,10 +3079,54 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
         nz = nz / mag;
       }
     }
-    if (((nx * ex + ny * ey) + nz * ez) < 0.0) {  // inside: world.zig:218-221
+    const bool inside = ((nx * ex + ny * ey) + nz * ez) < 0.0;  // world.zig:218-221
+    if (inside) {
       nx = -nx;
       ny = -ny;
       nz = -nz;
+    }
+    // The shading normal: what Material.lighting, reflectv, refractedColor and schlick read.  (nx, ny, nz) stays the
+    // geometric normal: inside, over_point, under_point - and n1 / n2, traced above - come from it alone.
+    // (BUMP) a material with a bump (rtc_scene_set_bumps; the row is read per lane, mat_index being the lane's): the unit
+    // local normal plus the field at B * local point times the amplitude, through normalToWorld, negated by the decision
+    // above.  A row of kind none leaves the geometric normal's bits.
+    double hx = nx, hy = ny, hz = nz;
+    if constexpr (BUMP) {
+      const double* __restrict__ R = bumps.row + static_cast<size_t>(RTC_BUMP_ROW) * mat_index;
+      const double bump_kind = R[14];
+      const double lmag = bump_kind != 0.0 ? __builtin_sqrt((lnx * lnx + lny * lny) + lnz * lnz) : 0.0;  // tuple.zig's normalize
+      if (lmag != 0.0) {
+        const double qx = row_pt(R + 0, lpx, lpy, lpz);
+        const double qy = row_pt(R + 4, lpx, lpy, lpz);
+        const double qz = row_pt(R + 8, lpx, lpy, lpz);
+        double d0, d1, d2;
+        if (bump_kind == 1.0) {  // RTC_BUMP_NOISE: perturb.zig:31-43's three evaluations
+          const uint32_t octaves = static_cast<uint32_t>(R[15]);
+          const double persistence = R[13];
+          d0 = octave_noise(qx, qy, qz, octaves, persistence);
+          d1 = octave_noise(qx, qy, qz + 1.0, octaves, persistence);
+          d2 = octave_noise(qx, qy, qz + 2.0, octaves, persistence);
+        } else {  // RTC_BUMP_RIPPLES
+          d1 = 0.0;
+          bump_ripples(qx, qz, d0, d2);
+        }
+        const double amp = R[12];
+        const double bx = lnx / lmag + d0 * amp, by = lny / lmag + d1 * amp, bz = lnz / lmag + d2 * amp;
+        hx = (M[0] * bx + M[4] * by) + M[8] * bz;
+        hy = (M[1] * bx + M[5] * by) + M[9] * bz;
+        hz = (M[2] * bx + M[6] * by) + M[10] * bz;
+        const double mag = __builtin_sqrt((hx * hx + hy * hy) + hz * hz);
+        if (mag != 0.0) {
+          hx = hx / mag;
+          hy = hy / mag;
+          hz = hz / mag;
+        }
+        if (inside) {
+          hx = -hx;
+          hy = -hy;
+          hz = -hz;
+        }
+      }
     }
     RTC_STAMP(11);
     const double eps = 1e-5;
@@ -3179,14 +3239,14 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
                     lvy = vy / distance;
                     lvz = vz / distance;
                   }
-                  const double light_dot_normal = (lvx * nx + lvy * ny) + lvz * nz;
+                  const double light_dot_normal = (lvx * hx + lvy * hy) + lvz * hz;
                   if (light_dot_normal >= 0.0) {
                     const double kd = mat.diffuse * light_dot_normal;
                     dr = dr + er * kd;
                     dg = dg + eg * kd;
                     db = db + eb * kd;
                     const double two_dot = 2.0 * light_dot_normal;
-                    const double rx = lvx - nx * two_dot, ry = lvy - ny * two_dot, rz = lvz - nz * two_dot;
+                    const double rx = lvx - hx * two_dot, ry = lvy - hy * two_dot, rz = lvz - hz * two_dot;
                     const double reflect_dot_eye = ((-rx) * ex + (-ry) * ey) + (-rz) * ez;
                     if (reflect_dot_eye > 0.0) {
                       const uint32_t n = mat.shininess_int;
@@ -3245,7 +3305,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
         }
         // With light_dot_normal < 0 (light behind the surface) lighting() returns `ambient` shadowed
         // or not (material.zig:62-73): that shadow ray cannot change the result either.
-        const double light_dot_normal = (lvx * nx + lvy * ny) + lvz * nz;
+        const double light_dot_normal = (lvx * hx + lvy * hy) + lvz * hz;
         bool shadowed = false;
         // (SPOT) the cone's factor f at c = -(point_to_light . axis).  f == 0: the light gives `ambient` alone - what a
         // shadowed point gets -, so isShadowed is not called: no count, no shadow ray.  li is wave-uniform (no cooperative
@@ -3292,7 +3352,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
               db = db * spot_f;
             }
             const double two_dot = 2.0 * light_dot_normal;  // point_to_light.reflect(normal)
-            const double rx = lvx - nx * two_dot, ry = lvy - ny * two_dot, rz = lvz - nz * two_dot;
+            const double rx = lvx - hx * two_dot, ry = lvy - hy * two_dot, rz = lvz - hz * two_dot;
             const double reflect_dot_eye = ((-rx) * ex + (-ry) * ey) + (-rz) * ez;
             if (reflect_dot_eye > 0.0) {
               const uint32_t n = mat.shininess_int;
@@ -3345,7 +3405,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
     const bool transparent = !(mat.transparency == 0.0);
     if (!do_reflect && !transparent) continue;
 
-    const double cos_i = (ex * nx + ey * ny) + ez * nz;  // eyev.dot(normal)
+    const double cos_i = (ex * hx + ey * hy) + ez * hz;  // eyev.dot(normal)
     double w_reflect = mat.reflective, w_refract = mat.transparency;
     bool do_refract = false;
     double n_ratio = 1.0, sin2_t = 0.0;
@@ -3381,8 +3441,8 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
     Pending child;
     child.remaining = cur.remaining - 1u;
     if (do_reflect) {
-      const double two_dot = 2.0 * ((ray.dx * nx + ray.dy * ny) + ray.dz * nz);  // direction.reflect(normal)
-      child.ray = {ovx, ovy, ovz, ray.dx - nx * two_dot, ray.dy - ny * two_dot, ray.dz - nz * two_dot};
+      const double two_dot = 2.0 * ((ray.dx * hx + ray.dy * hy) + ray.dz * hz);  // direction.reflect(normal)
+      child.ray = {ovx, ovy, ovz, ray.dx - hx * two_dot, ray.dy - hy * two_dot, ray.dz - hz * two_dot};
       child.weight = cur.weight * w_reflect;
       it_secondary++;
     }
@@ -3391,7 +3451,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
       const double k = n_ratio * cos_i - cos_t;
       const double unx = ptx - nx * eps, uny = pty - ny * eps, unz = ptz - nz * eps;  // under_point
       Pending p;
-      p.ray = {unx, uny, unz, nx * k - ex * n_ratio, ny * k - ey * n_ratio, nz * k - ez * n_ratio};
+      p.ray = {unx, uny, unz, hx * k - ex * n_ratio, hy * k - ey * n_ratio, hz * k - ez * n_ratio};
       p.weight = cur.weight * w_refract;
       p.remaining = cur.remaining - 1u;
       it_secondary++;
@@ -3540,17 +3600,17 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
 
 // The kernels.  rtc_motion.hip includes this file with RTC_MOTION_TU defined and gets the motion kernels alone: a
 // translation unit of their own, so that this one compiles in the time and to the code it did; rtc_spot.hip likewise
-// with RTC_SPOT_TU and the spot kernels.  rtc_kernels_ext.hip
+// with RTC_SPOT_TU and the spot kernels, rtc_bump.hip with RTC_BUMP_TU and the bump kernels.  rtc_kernels_ext.hip
 // includes it with RTC_EXT_TU defined: in the -DRTC_PROFILE diagnostic build, whose instrumented walk makes this unit's
 // compile about a third longer, it gets the csg / texture-map, flat and area-light kernels (rtc_render_kernel_ext to
 // rtc_render_kernel_area_bigworld below), so that neither unit takes the time of all of them.  The product build keeps
 // them here - that unit's code is the same as before to the byte - and its rtc_kernels_ext.o holds no kernel.
-#if (defined(RTC_EXT_TU) && defined(RTC_PROFILE)) || (!defined(RTC_MOTION_TU) && !defined(RTC_SPOT_TU) && !defined(RTC_EXT_TU) && !defined(RTC_PROFILE))
+#if (defined(RTC_EXT_TU) && defined(RTC_PROFILE)) || (!defined(RTC_MOTION_TU) && !defined(RTC_SPOT_TU) && !defined(RTC_BUMP_TU) && !defined(RTC_EXT_TU) && !defined(RTC_PROFILE))
 #define RTC_EXT_KERNELS_HERE 1
 #else
 #define RTC_EXT_KERNELS_HERE 0
 #endif
-#if !defined(RTC_MOTION_TU) && !defined(RTC_SPOT_TU) && !defined(RTC_EXT_TU)
+#if !defined(RTC_MOTION_TU) && !defined(RTC_SPOT_TU) && !defined(RTC_BUMP_TU) && !defined(RTC_EXT_TU)
 extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
 rtc_render_kernel(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
                   double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats) {
@@ -3611,7 +3671,7 @@ rtc_render_kernel3(const DevScene S, const DevCamera cam, const DevPixelMap map,
 }
 #endif
 
-#endif  // !RTC_MOTION_TU && !RTC_SPOT_TU && !RTC_EXT_TU
+#endif  // !RTC_MOTION_TU && !RTC_SPOT_TU && !RTC_BUMP_TU && !RTC_EXT_TU
 
 #if RTC_EXT_KERNELS_HERE
 // The same two kernels with the csg and texture-map paths compiled in (template flag CSG), for scenes that
@@ -3670,7 +3730,7 @@ rtc_render_kernel_area_bigworld(const DevScene S, const DevCamera cam, const Dev
 }
 #endif  // RTC_EXT_KERNELS_HERE
 
-#if !defined(RTC_MOTION_TU) && !defined(RTC_SPOT_TU) && !defined(RTC_EXT_TU)
+#if !defined(RTC_MOTION_TU) && !defined(RTC_SPOT_TU) && !defined(RTC_BUMP_TU) && !defined(RTC_EXT_TU)
 // Several camera samples per pixel (rtc_scene_set_sampling: anti-aliasing, focal blur): the general walk with the csg and
 // texture-map paths compiled in, the sampling parameters as an extra argument (DevSampling) - every other kernel is
 // compiled without them.  Point lights (tables in LDS or in memory), and the area-light forms.
@@ -4391,4 +4451,26 @@ rtc_render_kernel_spot_bigworld(const DevScene S, const DevCamera cam, const Dev
   render_body<false, true, 0, 2, false, true, true, true, true, true>(S, cam, map, max_depth, out, stats, next_stats, area, smp, mo, spots);
 }
 
-#endif  // RTC_MOTION_TU / RTC_SPOT_TU
+#elif defined(RTC_BUMP_TU)
+
+// Normal perturbation (rtc_scene_set_bumps): the spot walk with the materials' bumps compiled in (DevBumps), one pair for
+// every world and every combination of sampling, passes, motion, area lights and cones (a handle without cones passes
+// zero spot rows).  Every other kernel is compiled without it.
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_bump(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                       double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                       const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots, const DevBumps bumps) {
+  render_body<true, true, 0, 2, false, true, true, true, true, true, true>(S, cam, map, max_depth, out, stats, next_stats, area, smp, mo,
+                                                                           spots, bumps);
+}
+
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_bump_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                const DevBumps bumps) {
+  render_body<false, true, 0, 2, false, true, true, true, true, true, true>(S, cam, map, max_depth, out, stats, next_stats, area, smp, mo,
+                                                                            spots, bumps);
+}
+
+#endif  // RTC_MOTION_TU / RTC_SPOT_TU / RTC_BUMP_TU

@@ -104,11 +104,17 @@ struct Flattener {
     std::string key;
     appendBits(key, params, RTC_MAT_STRIDE);
     key.append(reinterpret_cast<const char*>(&pat), 4);
+    if (m.bump.kind != 0) {  // (a material with a "normal-perturbation" is a row of its own; without one the key is as before)
+      const double bump[4] = {static_cast<double>(m.bump.kind), m.bump.amplitude, static_cast<double>(m.bump.octaves), m.bump.persistence};
+      appendBits(key, bump, 4);
+      appendBits(key, &m.bump.inverse.d[0][0], 12);
+    }
     auto it = material_ids.find(key);
     if (it != material_ids.end()) return it->second;
     const uint32_t id = static_cast<uint32_t>(out.mat_pattern.size());
     out.mat_params.insert(out.mat_params.end(), params, params + RTC_MAT_STRIDE);
     out.mat_pattern.push_back(pat);
+    out.mat_bump.push_back(m.bump);
     material_ids.emplace(std::move(key), id);
     return id;
   }

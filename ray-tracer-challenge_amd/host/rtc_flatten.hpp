@@ -25,6 +25,7 @@ struct FlatScene {
   std::vector<double> tri_p1, tri_e1, tri_e2, tri_n1, tri_n2, tri_n3;
   std::vector<double> mat_params;
   std::vector<uint32_t> mat_pattern;
+  std::vector<Bump> mat_bump;  // [n_materials]: each row's "normal-perturbation" (rtch_scene_bumps; not part of rtc_scene_desc)
   std::vector<uint8_t> pat_kind;
   std::vector<double> pat_inv, pat_rgb;
   std::vector<uint32_t> pat_a, pat_b;

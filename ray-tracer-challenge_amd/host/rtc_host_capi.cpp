@@ -117,6 +117,23 @@ int rtch_scene_spots(void* h, uint8_t* cone, double* axis, double* cos_inner, do
   });
 }
 
+int rtch_scene_bumps(void* h, uint8_t* kind, double* amplitude, uint32_t* octaves, double* persistence, double* inverse, uint32_t n) {
+  return guarded([&] {
+    const HostScene* hs = static_cast<HostScene*>(h);
+    if (n != hs->desc.n_materials)
+      throw rtc::Error("InvalidArgument", "bumps: n " + std::to_string(n) + ", the scene has " + std::to_string(hs->desc.n_materials) + " materials");
+    if (n != 0u && (!kind || !amplitude || !octaves || !persistence || !inverse)) throw rtc::Error("InvalidArgument", "bumps: null argument");
+    for (uint32_t i = 0; i < n; ++i) {  // (mat_* order)
+      const rtc::Bump& b = hs->flat.mat_bump[i];
+      kind[i] = b.kind;
+      amplitude[i] = b.amplitude;
+      octaves[i] = b.octaves;
+      persistence[i] = b.persistence;
+      for (int k = 0; k < 12; ++k) inverse[12ull * i + k] = b.inverse.d[k / 4][k % 4];
+    }
+  });
+}
+
 // Camera of the scene file; width/height 0 keep the file's values, otherwise they replace
 // camera.width/height before Camera.new runs (the reference has no such override).
 int rtch_scene_camera(void* h, uint32_t width, uint32_t height, rtc_camera* out) {
@@ -203,6 +220,15 @@ int rtch_scene_render(void* h, uint32_t width, uint32_t height, uint32_t max_dep
         if (rtch_scene_spots(h, cone.data(), axis.data(), ci.data(), co.data(), nl) != 0) throw rtc::Error("InvalidArgument", g_error);
         const rtc_spot sp{nl, cone.data(), axis.data(), ci.data(), co.data()};
         st = rtc_scene_set_spots(scene, &sp);
+      }
+      if (st == RTC_OK) {  // (the materials' "normal-perturbation" entries; none: the handle as it is)
+        const uint32_t nm = hs->desc.n_materials;
+        std::vector<uint8_t> kind(nm);
+        std::vector<uint32_t> oct(nm);
+        std::vector<double> amp(nm), per(nm), inv(12ull * nm);
+        if (rtch_scene_bumps(h, kind.data(), amp.data(), oct.data(), per.data(), inv.data(), nm) != 0) throw rtc::Error("InvalidArgument", g_error);
+        const rtc_bump bp{nm, kind.data(), amp.data(), oct.data(), per.data(), inv.data()};
+        st = rtc_scene_set_bumps(scene, &bp);
       }
       const rtc::CameraSampling& cs = hs->info.sampling;
       if (cs.adaptive && st == RTC_OK) {  // (adaptive sampling: each tile's mean after its own passes, section 15)

@@ -370,10 +370,58 @@ Pattern parsePattern(const Value& cfg, const FileLoader& load_file_data) {
 }
 
 // ---- scene.zig:407-430 ------------------------------------------------------------------
+const Value* presentField(const Value& obj, const char* k) {
+  const Value* v = obj.find(k);
+  return (v && v->type != Value::Null) ? v : nullptr;
+}
+
+// A material's "normal-perturbation" (not in the reference): {"type": "noise" | "ripples",
+// "amplitude": a, "octaves": n, "persistence": p, "transform": [...]}, the transform list as a pattern's.
+Bump parseBump(const Value& cfg) {
+  const char* what = "normal-perturbation";
+  requireObject(cfg, what);
+  checkFields(cfg, {"type", "amplitude", "octaves", "persistence", "transform"}, what);
+  Bump b;
+  const std::string& t = asString(requireField(cfg, "type", what), "normal-perturbation.type");
+  if (t == "noise") {
+    b.kind = RTC_BUMP_NOISE;
+  } else if (t == "ripples") {
+    b.kind = RTC_BUMP_RIPPLES;
+  } else {
+    throw Error("UnknownField", "normal-perturbation.type." + t);
+  }
+  b.amplitude = asFloat(requireField(cfg, "amplitude", what), "normal-perturbation.amplitude");
+  if (!(std::isfinite(b.amplitude) && b.amplitude >= 0.0)) throw Error("InvalidData", "normal-perturbation.amplitude: a finite number, 0 or above");
+  if (const Value* v = presentField(cfg, "octaves")) {
+    if (b.kind != RTC_BUMP_NOISE) throw Error("InvalidData", "normal-perturbation.octaves: of \"noise\" only");
+    const size_t n = asUsize(*v, "normal-perturbation.octaves");
+    if (n == 0 || n > RTC_BUMP_MAX_OCTAVES)
+      throw Error("InvalidData", "normal-perturbation.octaves: 1 to " + std::to_string(RTC_BUMP_MAX_OCTAVES));
+    b.octaves = static_cast<uint32_t>(n);
+  }
+  if (const Value* v = presentField(cfg, "persistence")) {
+    if (b.kind != RTC_BUMP_NOISE) throw Error("InvalidData", "normal-perturbation.persistence: of \"noise\" only");
+    b.persistence = asFloat(*v, "normal-perturbation.persistence");
+    if (!std::isfinite(b.persistence)) throw Error("InvalidData", "normal-perturbation.persistence: a finite number");
+  }
+  if (const Value* v = presentField(cfg, "transform")) {
+    const Matrix4 m = parseTransform(*v);
+    try {
+      b.inverse = m.inverse();
+    } catch (const Error&) {  // (NotInvertible, named by its key here)
+      throw Error("InvalidData", "normal-perturbation.transform: an invertible transform");
+    }
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 4; ++c)
+        if (!std::isfinite(b.inverse.d[r][c])) throw Error("InvalidData", "normal-perturbation.transform: an invertible transform");
+  }
+  return b;
+}
+
 Material parseMaterial(const Value& cfg, const std::optional<Material>& inherited, const FileLoader& load_file_data) {
   requireObject(cfg, "material");
   checkFields(cfg, {"pattern", "ambient", "diffuse", "specular", "shininess", "reflective", "transparency",
-                    "refractive-index"}, "material");
+                    "refractive-index", "normal-perturbation"}, "material");
   Material mat = inherited ? *inherited : Material{};
   auto present = [&](const char* k) -> const Value* {
     const Value* v = cfg.find(k);
@@ -387,6 +435,7 @@ Material parseMaterial(const Value& cfg, const std::optional<Material>& inherite
   if (auto* v = present("reflective")) mat.reflective = asFloat(*v, "reflective");
   if (auto* v = present("transparency")) mat.transparency = asFloat(*v, "transparency");
   if (auto* v = present("refractive-index")) mat.refractive_index = asFloat(*v, "refractive-index");
+  if (auto* v = present("normal-perturbation")) mat.bump = parseBump(*v);
   return mat;
 }
 
@@ -401,11 +450,6 @@ struct Info {
   Matrix4 transform;
   std::optional<bool> casts_shadow;
 };
-
-const Value* presentField(const Value& obj, const char* k) {
-  const Value* v = obj.find(k);
-  return (v && v->type != Value::Null) ? v : nullptr;
-}
 
 // scene.zig:164-190
 Info inherit(const Value& object, const InheritedState& inherited, const FileLoader& load_file_data) {

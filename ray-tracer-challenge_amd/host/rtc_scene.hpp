@@ -82,10 +82,21 @@ struct Pattern {  // patterns/pattern.zig:21-49
   }
 };
 
+// A material's "normal-perturbation" (not in the reference), as rtc_scene_set_bumps takes it:
+// kind RTC_BUMP_* (0: none), the inverse of its "transform".
+struct Bump {
+  uint8_t kind = 0;
+  double amplitude = 0.0;
+  uint32_t octaves = 3;       // PerturbInfo's defaults
+  double persistence = 0.8;
+  Matrix4 inverse = Matrix4::identity();
+};
+
 struct Material {  // material.zig:18-25
   Pattern pattern = Pattern::solid({1.0, 1.0, 1.0});
   double ambient = 0.1, diffuse = 0.9, specular = 0.9, shininess = 200.0;
   double reflective = 0.0, transparency = 0.0, refractive_index = 1.0;
+  Bump bump;  // (kind 0 in every scene of the reference)
 };
 
 struct Light {  // light.zig:14-15

@@ -5,7 +5,7 @@
                                 [--handles 3] [--settle 50] [--frames 20] [--option name=value ...] [--check]
                                 [--lights scene | area=N | grid=N] [--sampling grid[,aperture,focal]] [--passes P]
                                 [--motion R=dx,dy,dz ...] [--adaptive threshold[,min,tile] [--max-passes N]]
-                                [--spot L=ax,ay,az,inner,outer ...]
+                                [--spot L=ax,ay,az,inner,outer ...] [--bump MATERIAL=kind,amplitude[,scale] ...]
 
   configs  the five BASELINE configs at their own sizes and depths (fresnel 300x300, cover / teapot 1080p, r&r 1080p
            depth 8, dragons 4K)                                                       [default]
@@ -32,6 +32,10 @@ the motion kernels on the static scene.
 --spot L=ax,ay,az,inner,outer (repeatable): World.lights entry L, a point light, becomes a spot light with that axis and
 those half-angles in radians (rtc_scene_set_spots); prints shadow_traced per frame and ns per primary
 ray as well.  Option spot_kernels=1 times the spot kernels without a cone.
+--bump MATERIAL=kind,amplitude[,scale] (repeatable): material row MATERIAL (mat_* order) gets a bump of kind noise or
+ripples with that amplitude, its field scaled by `scale` (1) (rtc_scene_set_bumps); on a scene file
+with "normal-perturbation" entries those are applied first; --bump off applies none.  Option bump_kernels=1 times the
+bump kernels without a bump.
 --adaptive threshold[,min,tile]: adaptive sampling at up to --max-passes (64) passes, min passes 4 and
 16 x 16 tiles by default, with the --sampling of the frames: prints the rounds and tile-passes of a run against
 T * max_passes, its time (a second run, end to end on the host) against uniform progressive passes (render_device +
@@ -70,6 +74,7 @@ ap.add_argument("--sampling", default="")
 ap.add_argument("--passes", type=int, default=-1)
 ap.add_argument("--motion", action="append", default=[])
 ap.add_argument("--spot", action="append", default=[])
+ap.add_argument("--bump", action="append", default=[])
 ap.add_argument("--adaptive", default="")
 ap.add_argument("--max-passes", type=int, default=64)
 args = ap.parse_args()
@@ -224,7 +229,9 @@ def time_adaptive(hs, table, cam, depth):
 stream = torch.cuda.Stream(); torch.cuda.set_stream(stream)
 out = []
 for name, w, h, depth in cases:
-    hs = rtc.HostScene.from_file(name + ".json"); cam = hs.camera(w, h)
+    # (a scene given by its path may name files beside it)
+    hs = (rtc.HostScene.from_file(name + ".json", os.path.dirname(name)) if os.path.exists(name + ".json")
+          else rtc.HostScene.from_file(name + ".json")); cam = hs.camera(w, h)
     canvas = torch.empty((h, w, 3), dtype=torch.float64, device="cuda")
     ts, kernel, delta, acc = [], "", None, []
     table = light_table(hs, args.lights)
@@ -254,6 +261,19 @@ for name, w, h, depth in cases:
                 spots["cone"][i], spots["axis"][i] = 1, (ax, ay, az)
                 spots["cos_inner"][i], spots["cos_outer"][i] = math.cos(inner), math.cos(outer)
             gpu.set_spots(spots)
+        if args.bump or hs.bumps() is not None:
+            bumps = hs.bumps() or rtc.no_bumps(hs.desc.n_materials)
+            for b in args.bump:
+                if b == "off":
+                    continue
+                m, v = b.split("=")
+                f = v.split(",")
+                i, scale = int(m), float(f[2]) if len(f) > 2 else 1.0
+                bumps["kind"][i] = {"noise": rtc.BUMP_NOISE, "ripples": rtc.BUMP_RIPPLES}[f[0]]
+                bumps["amplitude"][i] = float(f[1])
+                bumps["inverse"][i] = [1.0 / scale, 0, 0, 0, 0, 1.0 / scale, 0, 0, 0, 0, 1.0 / scale, 0]
+            if "off" not in args.bump:
+                gpu.set_bumps(bumps)
         for i in range(args.settle):
             gpu.render_device(cam, canvas.data_ptr(), depth, None, stream.cuda_stream)
         torch.cuda.synchronize()
@@ -278,7 +298,7 @@ for name, w, h, depth in cases:
     if delta is not None: line += f" maxdelta {delta:.2e}"
     if args.lights or args.spot or "spot_kernels=1" in args.option:
         line += f" shadow_traced {st['shadow_traced']} ns/shadow-ray {min(ts) * 1e6 / max(1, st['shadow_traced']):.3f}"
-    if args.sampling or args.option or args.passes >= 0 or args.motion or args.spot:
+    if args.sampling or args.option or args.passes >= 0 or args.motion or args.spot or args.bump:
         line += f" primary {st['primary']} ns/primary-ray {min(ts) * 1e6 / max(1, st['primary']):.3f}"
     if acc:
         ms, copy_ms, nbytes = min(a[0] for a in acc), min(a[1] for a in acc), acc[0][2]
