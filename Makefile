@@ -13,6 +13,8 @@
 #   tests/build/libadaptive_oracle.so            test infrastructure only: the adaptive-sampling checker (tests/cpp/adaptive_oracle.cpp)
 #   tests/build/libspot_oracle.so                test infrastructure only: the spot-light checker (tests/cpp/spot_oracle.cpp)
 #   tests/build/libbump_oracle.so                test infrastructure only: the normal-perturbation checker (tests/cpp/bump_oracle.cpp)
+#   tests/build/libtorus_oracle.so               test infrastructure only: the torus checker (tests/cpp/torus_oracle.cpp)
+#   tests/build/libtorus_bounds.so               test infrastructure only: rtc_bounds.h's leaf bounds behind a C interface (tests/cpp/torus_bounds_shim.hip)
 #
 # -ffp-contract=off everywhere: the reference's float mode is strict IEEE
 # (SURVEY F10); the GPU path and the oracle must round identically.
@@ -39,7 +41,8 @@ oracle:
 
 # (the area-light checker includes the oracle's sources read-only; -pthread and -O3 as the oracle's own build)
 checker: tests/build/libarea_oracle.so tests/build/libcamera_oracle.so tests/build/libprogressive_oracle.so tests/build/libmotion_oracle.so \
-         tests/build/libadaptive_oracle.so tests/build/libspot_oracle.so tests/build/libbump_oracle.so
+         tests/build/libadaptive_oracle.so tests/build/libspot_oracle.so tests/build/libbump_oracle.so \
+         tests/build/libtorus_oracle.so tests/build/libtorus_bounds.so
 tests/build/libarea_oracle.so: tests/cpp/area_oracle.cpp oracle/oracle_capi.cpp oracle/rtc_oracle.hpp oracle/rtc_oracle_scene.hpp include/rtc.h
 	mkdir -p tests/build
 	$(CXX) -std=c++17 -O3 -ffp-contract=off -fPIC -Wall -Wextra -pthread -shared -o $@ tests/cpp/area_oracle.cpp
@@ -67,13 +70,21 @@ tests/build/libspot_oracle.so: tests/cpp/spot_oracle.cpp tests/cpp/motion_oracle
 tests/build/libbump_oracle.so: tests/cpp/bump_oracle.cpp tests/cpp/spot_oracle.cpp tests/cpp/motion_oracle.cpp tests/cpp/camera_oracle.cpp tests/cpp/area_oracle.cpp oracle/oracle_capi.cpp oracle/rtc_oracle.hpp oracle/rtc_oracle_scene.hpp include/rtc.h
 	mkdir -p tests/build
 	$(CXX) -std=c++17 -O3 -ffp-contract=off -fPIC -Wall -Wextra -Wno-subobject-linkage -pthread -shared -o $@ tests/cpp/bump_oracle.cpp
+# (the torus checker includes the normal-perturbation checker, read-only)
+tests/build/libtorus_oracle.so: tests/cpp/torus_oracle.cpp tests/cpp/bump_oracle.cpp tests/cpp/spot_oracle.cpp tests/cpp/motion_oracle.cpp tests/cpp/camera_oracle.cpp tests/cpp/area_oracle.cpp oracle/oracle_capi.cpp oracle/rtc_oracle.hpp oracle/rtc_oracle_scene.hpp include/rtc.h
+	mkdir -p tests/build
+	$(CXX) -std=c++17 -O3 -ffp-contract=off -fPIC -Wall -Wextra -Wno-subobject-linkage -pthread -shared -o $@ tests/cpp/torus_oracle.cpp
+# (the product's conservative leaf bounds, rtc_bounds.h - host code -, for the test that no checker entry lies outside them)
+tests/build/libtorus_bounds.so: tests/cpp/torus_bounds_shim.hip $(PKG)/csrc/rtc_bounds.h $(PKG)/csrc/rtc_host_internal.h $(PKG)/csrc/rtc_device.h include/rtc.h
+	mkdir -p tests/build
+	$(HIPCC) $(HIPFLAGS) -Wno-unused-function -shared -o $@ tests/cpp/torus_bounds_shim.hip
 
 $(LIB):
 	mkdir -p $(LIB)
 
 # (the compiler's resource-usage remarks of the product build are kept: lib/kernel_resources.json - registers, spills,
 # scratch bytes per lane, LDS of every kernel - is what bench.py quotes as roofline.scratch_bytes_per_lane)
-# (the motion kernels, rtc_motion.hip, the spot kernels, rtc_spot.hip, and the bump kernels, rtc_bump.hip, are render_body
+# (the motion kernels, rtc_motion.hip, the spot kernels, rtc_spot.hip, the bump kernels, rtc_bump.hip, and the torus kernels, rtc_torus.hip, are render_body
 # of rtc_kernels.hip in translation units of their own: the file of every other kernel compiles as before; the JSON holds the kernels of all)
 $(LIB)/rtc_kernels.o: $(PKG)/csrc/rtc_kernels.hip $(PKG)/csrc/rtc_device.h | $(LIB)
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o $@ $< 2> $(LIB)/rtc_kernels.remarks || (grep -v "remark:" $(LIB)/rtc_kernels.remarks >&2; exit 1)
@@ -91,14 +102,18 @@ $(LIB)/rtc_bump.o: $(PKG)/csrc/rtc_bump.hip $(PKG)/csrc/rtc_kernels.hip $(PKG)/c
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o $@ $< 2> $(LIB)/rtc_bump.remarks || (grep -v "remark:" $(LIB)/rtc_bump.remarks >&2; exit 1)
 	@grep -v "remark:\|remarks generated\|\^\|^ *[0-9]* |" $(LIB)/rtc_bump.remarks >&2 || true
 
+$(LIB)/rtc_torus.o: $(PKG)/csrc/rtc_torus.hip $(PKG)/csrc/rtc_kernels.hip $(PKG)/csrc/rtc_device.h | $(LIB)
+	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o $@ $< 2> $(LIB)/rtc_torus.remarks || (grep -v "remark:" $(LIB)/rtc_torus.remarks >&2; exit 1)
+	@grep -v "remark:\|remarks generated\|\^\|^ *[0-9]* |" $(LIB)/rtc_torus.remarks >&2 || true
+
 # (rtc_kernels_ext.hip: in the -DRTC_PROFILE diagnostic build the csg / texture-map, flat and area-light kernels, in a
 # unit of their own so that the instrumented render kernels do not compile in one; in the product build it holds none)
 $(LIB)/rtc_kernels_ext.o: $(PKG)/csrc/rtc_kernels_ext.hip $(PKG)/csrc/rtc_kernels.hip $(PKG)/csrc/rtc_device.h | $(LIB)
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o $@ $< 2> $(LIB)/rtc_kernels_ext.remarks || (grep -v "remark:" $(LIB)/rtc_kernels_ext.remarks >&2; exit 1)
 	@grep -v "remark:\|remarks generated\|\^\|^ *[0-9]* |" $(LIB)/rtc_kernels_ext.remarks >&2 || true
 
-$(LIB)/kernel_resources.json: $(LIB)/rtc_kernels.o $(LIB)/rtc_kernels_ext.o $(LIB)/rtc_motion.o $(LIB)/rtc_spot.o $(LIB)/rtc_bump.o tools/kernel_resources.py
-	cat $(LIB)/rtc_kernels.remarks $(LIB)/rtc_kernels_ext.remarks $(LIB)/rtc_motion.remarks $(LIB)/rtc_spot.remarks $(LIB)/rtc_bump.remarks > $(LIB)/render_kernels.remarks
+$(LIB)/kernel_resources.json: $(LIB)/rtc_kernels.o $(LIB)/rtc_kernels_ext.o $(LIB)/rtc_motion.o $(LIB)/rtc_spot.o $(LIB)/rtc_bump.o $(LIB)/rtc_torus.o tools/kernel_resources.py
+	cat $(LIB)/rtc_kernels.remarks $(LIB)/rtc_kernels_ext.remarks $(LIB)/rtc_motion.remarks $(LIB)/rtc_spot.remarks $(LIB)/rtc_bump.remarks $(LIB)/rtc_torus.remarks > $(LIB)/render_kernels.remarks
 	python3 tools/kernel_resources.py --from-remarks $(LIB)/render_kernels.remarks --json $@
 
 $(LIB)/rtc_capi.o: $(PKG)/csrc/rtc_capi.hip $(wildcard $(PKG)/csrc/*.h) include/rtc.h | $(LIB)
@@ -112,7 +127,7 @@ $(LIB)/rtc_accum.o: $(PKG)/csrc/rtc_accum.hip $(PKG)/csrc/rtc_device.h | $(LIB)
 $(LIB)/rtc_adaptive.o: $(PKG)/csrc/rtc_adaptive.hip $(PKG)/csrc/rtc_device.h | $(LIB)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
-$(LIB)/librtc_hip.so: $(LIB)/rtc_kernels.o $(LIB)/rtc_kernels_ext.o $(LIB)/rtc_motion.o $(LIB)/rtc_spot.o $(LIB)/rtc_bump.o $(LIB)/rtc_capi.o $(LIB)/rtc_accum.o $(LIB)/rtc_adaptive.o | $(LIB)/kernel_resources.json
+$(LIB)/librtc_hip.so: $(LIB)/rtc_kernels.o $(LIB)/rtc_kernels_ext.o $(LIB)/rtc_motion.o $(LIB)/rtc_spot.o $(LIB)/rtc_bump.o $(LIB)/rtc_torus.o $(LIB)/rtc_capi.o $(LIB)/rtc_accum.o $(LIB)/rtc_adaptive.o | $(LIB)/kernel_resources.json
 	$(HIPCC) --offload-arch=gfx950 -shared -fPIC -o $@ $^
 
 $(LIB)/librtc_multi.so: $(PKG)/csrc/rtc_multi.hip include/rtc_multi.h include/rtc.h $(LIB)/librtc_hip.so

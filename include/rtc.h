@@ -89,8 +89,49 @@ enum {
   RTC_CYLINDER = 3,        /* shapes/cylinder.zig */
   RTC_TRIANGLE = 4,        /* shapes/triangle.zig:17-81   */
   RTC_SMOOTH_TRIANGLE = 5, /* shapes/triangle.zig:210-274 */
-  RTC_CONE = 6             /* shapes/cone.zig; geometry in the cyl_* tables like a cylinder */
+  RTC_CONE = 6,            /* shapes/cone.zig; geometry in the cyl_* tables like a cylinder */
+  RTC_TORUS = 7            /* a ring torus (below); its two radii in the cyl_* tables */
 };
+
+/*
+ * RTC_TORUS - the book's last shape.  In object space the torus lies in the xz plane around the y axis:
+ *
+ *     (x^2 + y^2 + z^2 + R^2 - r^2)^2 = 4 R^2 (x^2 + z^2)        0 < r < R, both finite
+ *
+ * leaf_geom indexes the cyl_* tables: cyl_min = R (major radius), cyl_max = r (minor radius), cyl_closed is ignored.
+ * rtc_scene_create refuses a leaf_geom out of range (RTC_ERR_BAD_INDEX) and radii that are not finite or not
+ * 0 < r < R (RTC_ERR_INVALID_ARGUMENT).  Every operation below is an IEEE double operation, correctly rounded, in the
+ * order and with the parentheses written; only + - * / sqrt fabs and comparisons occur.
+ *
+ * localIntersect of the ray (o, d) emits up to four entries (t, 0, 0), t strictly ascending:
+ *   1. alpha = (dx dx + dy dy) + dz dz;   t0 = -((ox dx + oy dy) + oz dz) / alpha;   p = o + t0 d  (px = ox + t0 dx, ...)
+ *   2. bxz = (R + r) (1 + 1e-9), by = r (1 + 1e-9): the line against the box (-bxz, -by, -bxz) .. (bxz, by, bxz) with
+ *      Cube.localIntersect's arithmetic (checkAxis per axis on (o, d) with these bounds - |direction| < 1e-5 is
+ *      "parallel": numerator * infinity -, tmin = max of the three, tmax = min of the three, NaN operands ignored).
+ *      tmin > tmax: no entries.  Otherwise lo = tmin - t0, hi = tmax - t0; unless lo < hi and hi - lo is finite: no entries.
+ *      The box is part of the contract: a line that misses it has no entries, and no entry lies outside it.
+ *   3. beta = 2 ((px dx + py dy) + pz dz);   gamma = (((px px + py py) + pz pz) + R R) - r r;   f = 4 (R R)
+ *      c4 = alpha alpha                       c3 = (2 alpha) beta
+ *      c2 = (beta beta + (2 alpha) gamma) - f (dx dx + dz dz)
+ *      c1 = (2 beta) gamma - (2 f) (px dx + pz dz)
+ *      c0 = gamma gamma - f (px px + pz pz)          q(s) = c4 s^4 + c3 s^3 + c2 s^2 + c1 s + c0,  s = t - t0
+ *   4. A polynomial (a4 .. a0) is evaluated as P(x) = (((a4 x + a3) x + a2) x + a1) x + a0, its derivative
+ *      (b3 .. b0) = (4 a4, 3 a3, 2 a2, a1) as D(x) = ((b3 x + b2) x + b1) x + b0.  The cubic q' is the polynomial
+ *      (0, 4 c4, 3 c3, 2 c2, c1).  Its critical points: with (q0, q1, q2) = (3 (4 c4), 2 (3 c3), 2 c2) and
+ *      disc = q1 q1 - (4 q0) q2, none if not disc >= 0, else (-q1 - sqrt(disc)) / (2 q0) and (-q1 + sqrt(disc)) / (2 q0),
+ *      the smaller first.
+ *      scan(P, points, cap): a = lo, fa = P(lo); for every point b in turn, then for hi - a point is skipped unless
+ *      a < b < hi -: fb = P(b); if fa == 0 then emit a, else if (fa < 0) != (fb < 0) and fb != 0 then emit refine(a, b);
+ *      a = b, fa = fb.  After hi: if fa == 0 emit a.  emit(x) appends x unless the list holds cap roots or x is not above
+ *      the last one.
+ *      refine(l, h), with fa of the piece's lower end: x = (l + h) / 2; at most 80 times: fx = P(x); fx == 0 ends; if
+ *      (fx < 0) == (fa < 0) then l = x else h = x; d = D(x); xn = x - fx / d (l if d == 0); unless l < xn < h,
+ *      xn = (l + h) / 2; m = (l + h) / 2; stop = xn == x or not l < h or m == l or m == h; x = xn; stop ends.  The root is x.
+ *      The roots of q' are scan(q', the critical points, 3); the roots of q are scan(q, the roots of q', 4).
+ *   5. t = t0 + s for each root s.
+ *
+ * localNormalAt(p): rho = sqrt(px px + pz pz);  n = (px - R (px / rho), py, pz - R (pz / rho)), and (0, py, 0) if rho == 0.
+ */
 
 /* ---- pattern kinds: Pattern(T).Variant tags (patterns/pattern.zig:34-45) ---- */
 enum {

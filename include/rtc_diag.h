@@ -34,7 +34,8 @@ extern "C" {
  * static handle, with every displacement zero, so that their images can be held to the sampling kernels'), "spot_kernels"
  * (!= 0: the spot kernels even on a handle without cones, every flag zero, so that their images can be held to the
  * motion kernels'), "bump_kernels" (!= 0: the bump kernels even on a handle without bumps, every row of kind none, so that
- * their images can be held to the spot kernels').
+ * their images can be held to the spot kernels'), "torus_kernels" (!= 0: the torus kernels even on a handle without a
+ * torus, so that their images can be held to the bump kernels').
  * RTC_ERR_INVALID_ARGUMENT for a name the library does not know.
  * (The library reads no environment variables.)
  */

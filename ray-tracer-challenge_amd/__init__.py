@@ -217,6 +217,10 @@ def spot_struct(spots):
 
 
 BUMP_NONE, BUMP_NOISE, BUMP_RIPPLES = 0, 1, 2  # RTC_BUMP_*
+# leaf kinds (rtc.h); RTC_TORUS: a ring torus, its major and minor radius in cyl_min / cyl_max
+RTC_SPHERE, RTC_PLANE, RTC_CUBE, RTC_CYLINDER, RTC_TRIANGLE, RTC_SMOOTH_TRIANGLE, RTC_CONE, RTC_TORUS = range(8)
+# the options that select a kernel family on a handle that does not need it (set_option; tests and tools/time_scenes.py)
+KERNEL_OPTIONS = ("sampling_kernels", "motion_kernels", "spot_kernels", "bump_kernels", "torus_kernels")
 BUMP_MAX_OCTAVES = 16  # RTC_BUMP_MAX_OCTAVES
 
 

@@ -112,6 +112,13 @@ Sphere leafSphere(const rtc_scene_desc& d, uint32_t leaf) {
       const double lo[3] = {-1, d.cyl_min[g], -1}, hi[3] = {1, d.cyl_max[g], 1};
       return sphereOfBox(M, lo, hi);
     }
+    case RTC_TORUS: {
+      // Bounded, by contract: Torus.localIntersect (rtc.h, step 2) has no entry for a line that misses this box - the
+      // torus's object box grown by 1e-9, relative -, and searches for roots inside the line's interval of it only.
+      const double bxz = (d.cyl_min[g] + d.cyl_max[g]) * (1.0 + 1e-9), by = d.cyl_max[g] * (1.0 + 1e-9);
+      const double lo[3] = {-bxz, -by, -bxz}, hi[3] = {bxz, by, bxz};
+      return sphereOfBox(M, lo, hi);
+    }
     case RTC_CONE:
       // NOT bounded by its truncated box: for a ray parallel to one of the cone's halves the reference
       // appends the single surface hit t = -c / 2b WITHOUT the min < y < max filter (cone.zig:79-86),
@@ -195,6 +202,12 @@ Aabb leafWorldBox(const rtc_scene_desc& d, uint32_t leaf) {
     }
     case RTC_CYLINDER: {
       const double lo[3] = {-1, d.cyl_min[g], -1}, hi[3] = {1, d.cyl_max[g], 1};
+      addObjectBox(lo, hi);
+      break;
+    }
+    case RTC_TORUS: {  // the padded object box of rtc.h's step 2, see leafSphere()
+      const double bxz = (d.cyl_min[g] + d.cyl_max[g]) * (1.0 + 1e-9), by = d.cyl_max[g] * (1.0 + 1e-9);
+      const double lo[3] = {-bxz, -by, -bxz}, hi[3] = {bxz, by, bxz};
       addObjectBox(lo, hi);
       break;
     }

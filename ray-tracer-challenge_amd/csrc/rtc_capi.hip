@@ -120,6 +120,17 @@ __global__ void rtc_render_kernel_bump_bigworld(const DevScene S, const DevCamer
                                                 const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
                                                 const DevBumps bumps);
 }
+// The torus kernels (RTC_TORUS: a leaf of kind 7): the bump kernels' tables, arguments and edge.
+extern "C" {
+__global__ void rtc_render_kernel_torus(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                        double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                        const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                        const DevBumps bumps);
+__global__ void rtc_render_kernel_torus_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                                 double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                                 const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                                 const DevBumps bumps);
+}
 // Progressive rendering's accumulation (rtc_accum.hip): the grid's blocks for n pixels (the noise partials it writes, at
 // most) and the enqueue of its kernels.
 uint32_t rtcAccumBlocks(size_t n_pixels, bool wide);
@@ -334,7 +345,7 @@ bool tablesInLds(const rtc_scene* s) {
 
 // (the area kernels take one more argument, DevAreaLights: `area` instead of `fn`; the sampling kernels DevSampling:
 // `ms`, and both: `area_ms`; the motion kernels both and DevMotion: `motion`; the spot kernels those three and DevSpots:
-// `spot`; the bump kernels those four and DevBumps: `bump`)
+// `spot`; the bump kernels those four and DevBumps: `bump` - the torus kernels take the same arguments and travel in `bump` too)
 struct KernelChoice {
   decltype(&rtc_render_kernel) fn;
   const char* name;
@@ -403,6 +414,9 @@ bool spotKernels(const rtc_scene* s) { return s->spots != nullptr || rtcOptions(
 // The bump kernels run when a material of the handle has a bump - whatever the sampling, the pass, the motion and the
 // cones - or, for tests, whenever option "bump_kernels" is set.
 bool bumpKernels(const rtc_scene* s) { return s->bumps != nullptr || rtcOptions().bump_kernels != 0.0; }
+// The torus kernels run when a leaf of the handle's world is a torus - whatever the sampling, the pass, the motion, the
+// cones and the bumps: no other kernel knows kind 7 - or, for tests, whenever option "torus_kernels" is set.
+bool torusKernels(const rtc_scene* s) { return s->has_torus || rtcOptions().torus_kernels != 0.0; }
 #define RTC_KERNEL(k) KernelChoice{k, #k}
 // The general kernel at three waves per SIMD (rtc_render_kernel3): forced by option "waves3", else what the handle's
 // trial measured (KernelTune in launch()).
@@ -429,6 +443,7 @@ KernelChoice ldsKernel(const rtc_scene* s, const DevPixelMap& map) {
   return s->ext_kernel ? RTC_KERNEL(rtc_render_kernel_ext) : RTC_KERNEL(rtc_render_kernel);
 }
 KernelChoice renderKernel(const rtc_scene* s, const DevPixelMap& map) {
+  if (torusKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_torus) : RTC_KERNEL(rtc_render_kernel_torus_bigworld);
   if (bumpKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_bump) : RTC_KERNEL(rtc_render_kernel_bump_bigworld);
   if (spotKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_spot) : RTC_KERNEL(rtc_render_kernel_spot_bigworld);
   if (motionKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_motion) : RTC_KERNEL(rtc_render_kernel_motion_bigworld);
@@ -444,6 +459,7 @@ KernelChoice renderKernel(const rtc_scene* s, const DevPixelMap& map) {
 
 // Work-groups of the launch's kernel that are resident at once, and the waves in them.
 uint32_t residentBlocksAlone(const rtc_scene* s, const DevPixelMap& map) {
+  if (torusKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_torus_lds : s->blocks_per_cu_torus_big);
   if (bumpKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_bump_lds : s->blocks_per_cu_bump_big);
   if (spotKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_spot_lds : s->blocks_per_cu_spot_big);
   if (motionKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_motion_lds : s->blocks_per_cu_motion_big);
@@ -851,7 +867,7 @@ int launch(rtc_scene* s, const rtc_camera& cam, const DevPixelMap& map_in, uint3
   int trial_slot = -1;
   {
     rtc_scene::KernelTune& T = s->tune;
-    const bool eligible = !samplingKernels(s) && !motionKernels(s) && !spotKernels(s) && !bumpKernels(s) &&  // (the sampling, motion, spot and bump kernels have no three-wave form)
+    const bool eligible = !samplingKernels(s) && !motionKernels(s) && !spotKernels(s) && !bumpKernels(s) && !torusKernels(s) &&  // (the sampling, motion, spot, bump and torus kernels have no three-wave form)
                           ((s->general3_ok && rtcOptions().waves3 < 0.0 && tablesInLds(s) &&
                             !(s->tab && s->tab->handles.load(std::memory_order_relaxed) > 1) &&
                             static_cast<double>(map.n_chunks) >= 4.0 * 4.0 * s->n_cus * s->blocks_per_cu_lds) ||
@@ -1018,6 +1034,7 @@ struct RootBox {   // host form of one world box; uploaded two to a RootBoxPair.
 // What validateScene learns about a scene on the way.
 struct SceneTraits {
   bool has_csg = false;     // some node is a csg operation
+  bool has_torus = false;   // some leaf is a torus: the torus kernels
   bool ext_kernel = false;  // csg, texture maps or nested mixing patterns: the `_ext` kernels
   bool nested_patterns = false;  // a gradient / blend below a gradient / blend
   uint32_t max_stack = 0;   // traversal stack the deepest group tree needs
@@ -1168,11 +1185,20 @@ int validateScene(const rtc_scene_desc& d, SceneTraits& traits) {
   std::unordered_set<uint32_t> ids;
   for (uint32_t i = 0; i < d.n_leaves; ++i) {
     const uint8_t k = d.leaf_kind[i];
-    if (k > RTC_CONE) return fail(RTC_ERR_UNSUPPORTED, "leaf %u: kind %u is not implemented by this kernel", i, k);
+    if (k > RTC_TORUS) return fail(RTC_ERR_UNSUPPORTED, "leaf %u: kind %u is not implemented by this kernel", i, k);
     if (d.leaf_xform[i] >= d.n_xforms) return fail(RTC_ERR_BAD_INDEX, "leaf %u: xform index out of range", i);
     if (d.leaf_material[i] >= d.n_materials) return fail(RTC_ERR_BAD_INDEX, "leaf %u: material index out of range", i);
     if ((k == RTC_CYLINDER || k == RTC_CONE) && d.leaf_geom[i] >= d.n_cyls)
       return fail(RTC_ERR_BAD_INDEX, "leaf %u: cylinder index out of range", i);
+    if (k == RTC_TORUS) {  // the radii travel in the cyl_* rows: cyl_min the major radius R, cyl_max the minor radius r
+      if (d.leaf_geom[i] >= d.n_cyls) return fail(RTC_ERR_BAD_INDEX, "leaf %u: torus radii index out of range", i);
+      const double R = d.cyl_min[d.leaf_geom[i]], r = d.cyl_max[d.leaf_geom[i]];
+      if (!std::isfinite(R) || !std::isfinite(r))
+        return fail(RTC_ERR_INVALID_ARGUMENT, "leaf %u: a torus radius that is not finite", i);
+      if (!(0.0 < r && r < R))
+        return fail(RTC_ERR_INVALID_ARGUMENT, "leaf %u: torus radii %g (major) and %g (minor): a ring torus has 0 < minor < major", i, R, r);
+      traits.has_torus = true;
+    }
     if ((k == RTC_TRIANGLE || k == RTC_SMOOTH_TRIANGLE) && d.leaf_geom[i] >= d.n_tris)
       return fail(RTC_ERR_BAD_INDEX, "leaf %u: triangle index out of range", i);
     if (!ids.insert(d.leaf_id[i]).second)
@@ -1309,10 +1335,10 @@ void buildRootTables(const rtc_scene_desc& d, const std::vector<uint32_t>& dfs_o
       const uint32_t g = d.leaf_geom[ref];
       std::memcpy(R.inv, d.xf_inv + 16ull * d.leaf_xform[ref], sizeof R.inv);
       R.kind_flags = static_cast<uint32_t>(k) | (d.leaf_shadow[ref] ? 0x100u : 0u);
-      if (k == RTC_CYLINDER || k == RTC_CONE) {
+      if (k == RTC_CYLINDER || k == RTC_CONE || k == RTC_TORUS) {  // (a torus: its radii; cyl_closed is not read)
         R.ymin = d.cyl_min[g];
         R.ymax = d.cyl_max[g];
-        if (d.cyl_closed[g]) R.kind_flags |= 0x200u;
+        if (k != RTC_TORUS && d.cyl_closed[g]) R.kind_flags |= 0x200u;
       }
       if (k == RTC_CUBE && d.n_lights > 0) {  // a room: every light strictly inside the cube (object space)
         // (an area light: its four corners, whose parallelogram holds every sample, jittered or not - the cube is convex)
@@ -2124,6 +2150,7 @@ int uploadTables(const rtc_scene_desc& d, const SceneTraits& traits, const HostT
   HIP_TRY(s->tab->node_range.upload(node_range));
   const bool has_csg = traits.has_csg, ext_kernel = traits.ext_kernel;
   s->has_csg = has_csg;
+  s->has_torus = traits.has_torus;
   s->ext_kernel = ext_kernel;
   // Worlds without groups (or csg: a csg is a node) that fit the LDS tables run kernels without the group traversal:
   // `flat` (every leaf kind), or `simple` when all leaves are spheres, planes or cubes; each with an `_ext` form when
@@ -2208,12 +2235,17 @@ int uploadTables(const rtc_scene_desc& d, const SceneTraits& traits, const HostT
     s->blocks_per_cu_bump_lds = static_cast<uint32_t>(std::max(nb, 1));
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_bump_bigworld, 256, 0));
     s->blocks_per_cu_bump_big = static_cast<uint32_t>(std::max(nb, 1));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_torus, 256, 0));  // (the torus kernels: one pair for every world)
+    s->blocks_per_cu_torus_lds = static_cast<uint32_t>(std::max(nb, 1));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_torus_bigworld, 256, 0));
+    s->blocks_per_cu_torus_big = static_cast<uint32_t>(std::max(nb, 1));
     if (const int v = static_cast<int>(rtcOptions().blocks_per_cu); v >= 1) {  // (tuning option)
       s->blocks_per_cu_lds = std::min<uint32_t>(s->blocks_per_cu_lds, v), s->blocks_per_cu_big = std::min<uint32_t>(s->blocks_per_cu_big, v);
       s->blocks_per_cu_ms_lds = std::min<uint32_t>(s->blocks_per_cu_ms_lds, v), s->blocks_per_cu_ms_big = std::min<uint32_t>(s->blocks_per_cu_ms_big, v);
       s->blocks_per_cu_motion_lds = std::min<uint32_t>(s->blocks_per_cu_motion_lds, v), s->blocks_per_cu_motion_big = std::min<uint32_t>(s->blocks_per_cu_motion_big, v);
       s->blocks_per_cu_spot_lds = std::min<uint32_t>(s->blocks_per_cu_spot_lds, v), s->blocks_per_cu_spot_big = std::min<uint32_t>(s->blocks_per_cu_spot_big, v);
       s->blocks_per_cu_bump_lds = std::min<uint32_t>(s->blocks_per_cu_bump_lds, v), s->blocks_per_cu_bump_big = std::min<uint32_t>(s->blocks_per_cu_bump_big, v);
+      s->blocks_per_cu_torus_lds = std::min<uint32_t>(s->blocks_per_cu_torus_lds, v), s->blocks_per_cu_torus_big = std::min<uint32_t>(s->blocks_per_cu_torus_big, v);
     }
   }
   DevScene& D = s->dev;
@@ -2950,6 +2982,9 @@ int rtc_scene_clone(const rtc_scene* src, rtc_scene** out) {
   s->bumps = src->bumps;  // (shared: read-only once made)
   s->blocks_per_cu_bump_lds = src->blocks_per_cu_bump_lds;
   s->blocks_per_cu_bump_big = src->blocks_per_cu_bump_big;
+  s->has_torus = src->has_torus;
+  s->blocks_per_cu_torus_lds = src->blocks_per_cu_torus_lds;
+  s->blocks_per_cu_torus_big = src->blocks_per_cu_torus_big;
   s->simple_kernel = src->simple_kernel;
   s->flat_kernel = src->flat_kernel;
   s->simple3_ok = src->simple3_ok;
@@ -3347,7 +3382,8 @@ int rtc_set_option(const char* name, double value) {
                {"measure_every", &o.measure_every}, {"sched_mix", &o.sched_mix},
                {"inflight_chunks_per_wave", &o.inflight_chunks_per_wave}, {"build_threads", &o.build_threads}, {"box_cull", &o.box_cull},
                {"sampling_kernels", &o.sampling_kernels}, {"motion_kernels", &o.motion_kernels},
-               {"spot_kernels", &o.spot_kernels}, {"bump_kernels", &o.bump_kernels}};
+               {"spot_kernels", &o.spot_kernels}, {"bump_kernels", &o.bump_kernels},
+               {"torus_kernels", &o.torus_kernels}};
   for (const auto& e : table)
     if (std::strcmp(e.name, name) == 0) {
       e.slot->set(value);

@@ -69,6 +69,7 @@ struct RtcOptions {
   RtcOption motion_kernels{0.0};       // != 0: the motion kernels even on a static handle, all displacements zero (tests: against the _ms kernels)
   RtcOption spot_kernels{0.0};         // != 0: the spot kernels even on a handle without cones, every flag zero (tests: against the motion kernels)
   RtcOption bump_kernels{0.0};         // != 0: the bump kernels even on a handle without bumps, every row of kind none (tests: against the spot kernels)
+  RtcOption torus_kernels{0.0};        // != 0: the torus kernels even on a handle without a torus (tests: against the bump kernels)
   RtcOption build_threads{0.0};        // threads of rtc_scene_create's candidate-BVH build (one top-level group each); 0: as many as the host allows, up to 8
 };
 inline RtcOptions& rtcOptions() {
@@ -198,6 +199,8 @@ struct rtc_scene {
   uint32_t blocks_per_cu_spot_lds = 1, blocks_per_cu_spot_big = 1;  // ... and of the spot kernels
   std::shared_ptr<const BumpTables> bumps;  // rtc_scene_set_bumps; null: no bumps (a clone starts with its source's)
   uint32_t blocks_per_cu_bump_lds = 1, blocks_per_cu_bump_big = 1;  // ... and of the bump kernels
+  bool has_torus = false;          // a leaf of the world is a torus (RTC_TORUS): the torus kernels
+  uint32_t blocks_per_cu_torus_lds = 1, blocks_per_cu_torus_big = 1;  // resident work-groups per CU of the torus kernels
   bool simple3_ok = false;         // a simple world whose tables fit the three-waves-per-SIMD kernel's LDS (RTC_LDS3_*)
   void* d_csg_buf = nullptr;       // DevPixelMap::csg_buf, only for scenes with csg nodes
   size_t csg_buf_capacity = 0;     // bytes

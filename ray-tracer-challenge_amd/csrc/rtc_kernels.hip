@@ -324,12 +324,141 @@ __device__ __forceinline__ bool segment_stays_inside_cube(const Ray& r, double l
   return inside & clear(r.ox, r.dx) & clear(r.oy, r.dy) & clear(r.oz, r.dz);
 }
 
+#ifdef RTC_TORUS_TU
+// ------------------------------------------------------------------------------------------
+// RTC_TORUS (rtc.h): the real roots of the ray's quartic by the derivative chain - the roots of
+// q''/2 (closed form, one sqrt) split the search interval into pieces on which the cubic q' is monotone, its roots into
+// pieces on which q is monotone.  + - * / sqrt and comparisons only, each correctly rounded, in the order rtc.h writes
+// them: the CPU checker takes the same path, exit for exit.  Compiled into the torus kernels' translation unit only.
+// The roots travel by value - five registers' worth of doubles and a count -, never through an array: a runtime-indexed
+// array would live in scratch.
+// ------------------------------------------------------------------------------------------
+struct TorusRoots {
+  double s0, s1, s2, s3;
+  uint32_t n;
+};
+// appends x if the list has room and x is above its last entry (the list stays strictly ascending)
+__device__ __forceinline__ void torus_push(TorusRoots& o, uint32_t cap, double x) {
+  const double last = o.n == 1u ? o.s0 : (o.n == 2u ? o.s1 : (o.n == 3u ? o.s2 : o.s3));
+  if (o.n >= cap || (o.n != 0u && !(x > last))) return;
+  if (o.n == 0u) o.s0 = x;
+  else if (o.n == 1u) o.s1 = x;
+  else if (o.n == 2u) o.s2 = x;
+  else o.s3 = x;
+  ++o.n;
+}
+// One copy in the code object (as perlin_noise): not inlined, and both stages of the chain run the same loop body - a
+// cubic is a quartic whose leading coefficient is 0.0 (0.0 * x + a3 is a3).
+__device__ __noinline__ TorusRoots torus_quartic(double c4, double c3, double c2, double c1, double c0, double lo, double hi) {
+  TorusRoots k{0.0, 0.0, 0.0, 0.0, 0u};
+  if (!(lo < hi) || !(hi - lo < kInf)) return k;  // an empty or unbounded interval (or a NaN): no entries
+  double a4 = 0.0, a3 = 4.0 * c4, a2 = 3.0 * c3, a1 = 2.0 * c2, a0 = c1;  // q'
+  {
+    const double q0 = 3.0 * a3, q1 = 2.0 * a2, q2 = a1;  // q''
+    const double disc = q1 * q1 - (4.0 * q0) * q2;
+    if (disc >= 0.0) {
+      const double sq = __builtin_sqrt(disc);
+      const double k0 = (-q1 - sq) / (2.0 * q0), k1 = (-q1 + sq) / (2.0 * q0);
+      k.s0 = k1 < k0 ? k1 : k0;
+      k.s1 = k1 < k0 ? k0 : k1;
+      k.n = 2u;
+    }
+  }
+#pragma unroll 1
+  for (uint32_t stage = 0u; stage < 2u; ++stage) {
+    const double b3 = 4.0 * a4, b2 = 3.0 * a3, b1 = 2.0 * a2, b0 = a1;
+    auto P = [&](double x) { return (((a4 * x + a3) * x + a2) * x + a1) * x + a0; };
+    auto D = [&](double x) { return ((b3 * x + b2) * x + b1) * x + b0; };
+    TorusRoots out{0.0, 0.0, 0.0, 0.0, 0u};
+    const uint32_t cap = 3u + stage;
+    double a = lo, fa = P(lo);
+#pragma unroll 1
+    for (uint32_t i = 0u; i <= k.n; ++i) {
+      const double b = i == k.n ? hi : (i == 0u ? k.s0 : (i == 1u ? k.s1 : (i == 2u ? k.s2 : k.s3)));
+      if (i < k.n && !(b > a && b < hi)) continue;  // a critical point outside the interval, or not above the last one
+      const double fb = P(b);
+      if (fa == 0.0) {
+        torus_push(out, cap, a);
+      } else if ((fa < 0.0) != (fb < 0.0) && fb != 0.0) {
+        // a sign change on a monotone piece: Newton, safeguarded by bisection, at most 80 steps
+        double l = a, h = b;
+        double x = 0.5 * (l + h);
+#pragma unroll 1
+        for (uint32_t it = 0u; it < 80u; ++it) {
+          const double fx = P(x);
+          if (fx == 0.0) break;
+          if ((fx < 0.0) == (fa < 0.0)) l = x;
+          else h = x;
+          const double d = D(x);
+          double xn = d != 0.0 ? x - fx / d : l;
+          if (!(xn > l && xn < h)) xn = 0.5 * (l + h);
+          const double mid = 0.5 * (l + h);
+          const bool stop = xn == x || !(l < h) || mid == l || mid == h;
+          x = xn;
+          if (stop) break;
+        }
+        torus_push(out, cap, x);
+      }
+      a = b;
+      fa = fb;
+    }
+    if (fa == 0.0) torus_push(out, cap, a);
+    k = out;
+    a4 = c4;
+    a3 = c3;
+    a2 = c2;
+    a1 = c1;
+    a0 = c0;
+  }
+  return k;
+}
+#endif  // RTC_TORUS_TU
+
 // Emits the entries a leaf's localIntersect appends, in the reference's order, as f(t, u, v).
 // `r` is the ray in the leaf's object space.
 struct CylParams {
   double ymin, ymax;
   bool closed;
 };
+
+#ifdef RTC_TORUS_TU
+// Torus.localIntersect, steps 1 to 5 of rtc.h: the roots as ray parameters t, ascending.  cy.ymin is the major radius R,
+// cy.ymax the minor radius r (the cyl_* rows).
+__device__ __forceinline__ TorusRoots torus_roots(const CylParams& cy, const Ray& r) {
+  TorusRoots k{0.0, 0.0, 0.0, 0.0, 0u};
+  const double R = cy.ymin, rm = cy.ymax;
+  const double alpha = (r.dx * r.dx + r.dy * r.dy) + r.dz * r.dz;
+  const double t0 = -((r.ox * r.dx + r.oy * r.dy) + r.oz * r.dz) / alpha;  // step 1: the point nearest the centre
+  const double bxz = (R + rm) * (1.0 + 1e-9), by = rm * (1.0 + 1e-9);      // step 2: the padded object box
+  double tmin, tmax;
+  if (!slab(r, -bxz, -by, -bxz, bxz, by, bxz, tmin, tmax)) return k;
+  const double px = r.ox + t0 * r.dx, py = r.oy + t0 * r.dy, pz = r.oz + t0 * r.dz;
+  const double beta = 2.0 * ((px * r.dx + py * r.dy) + pz * r.dz);  // step 3
+  const double gamma = (((px * px + py * py) + pz * pz) + R * R) - rm * rm;
+  const double f = 4.0 * (R * R);
+  const double c4 = alpha * alpha;
+  const double c3 = (2.0 * alpha) * beta;
+  const double c2 = (beta * beta + (2.0 * alpha) * gamma) - f * (r.dx * r.dx + r.dz * r.dz);
+  const double c1 = (2.0 * beta) * gamma - (2.0 * f) * (px * r.dx + pz * r.dz);
+  const double c0 = gamma * gamma - f * (px * px + pz * pz);
+  k = torus_quartic(c4, c3, c2, c1, c0, tmin - t0, tmax - t0);  // step 4
+  k.s0 = t0 + k.s0;                                            // step 5
+  k.s1 = t0 + k.s1;
+  k.s2 = t0 + k.s2;
+  k.s3 = t0 + k.s3;
+  return k;
+}
+template <class F>
+__device__ __forceinline__ void torus_emit(const TorusRoots& k, F&& f) {
+  if (k.n > 0u) f(k.s0, 0.0, 0.0);
+  if (k.n > 1u) f(k.s1, 0.0, 0.0);
+  if (k.n > 2u) f(k.s2, 0.0, 0.0);
+  if (k.n > 3u) f(k.s3, 0.0, 0.0);
+}
+#define RTC_HAS_CYL_ROW(kind) ((kind) == 3u || (kind) == 6u || (kind) == 7u)
+#else
+#define RTC_HAS_CYL_ROW(kind) ((kind) == 3u || (kind) == 6u)
+#endif
 
 // SIMPLE: the world has only spheres, planes and cubes (the `simple` kernel variant); the other kinds are not compiled.
 template <bool SIMPLE = false, class F>
@@ -449,6 +578,13 @@ __device__ __forceinline__ void leaf_entries(uint32_t kind, const CylParams& cy,
       }
       break;
     }
+#ifdef RTC_TORUS_TU
+    case 7: {  // RTC_TORUS: up to four entries, ascending
+      if constexpr (SIMPLE) break;
+      torus_emit(torus_roots(cy, r), f);
+      break;
+    }
+#endif
     default: {  // 4 triangle.zig:29-63, 5 triangle.zig:225-259 (Moller-Trumbore, left-handed cross)
       if constexpr (SIMPLE) break;
       if constexpr ((RTC_EXPERIMENT & 4) != 0) {  // (bound experiment: what an FP32 triangle test in place of the exact one would buy at most)
@@ -557,7 +693,7 @@ __device__ __forceinline__ void visit_leaf(const DevScene& S, const BvhLeafRec& 
   }
   const uint32_t kind = meta.x & 0xFFu;
   CylParams cy{0.0, 0.0, false};
-  if (kind == 3u || kind == 6u) {
+  if (RTC_HAS_CYL_ROW(kind)) {
     const DevCyl c = S.cyl[meta.w];
     cy = {c.ymin, c.ymax, c.closed != 0u};
   }
@@ -576,6 +712,23 @@ __device__ __forceinline__ void visit_leaf(const DevScene& S, const BvhLeafRec& 
     vis.entry(leaf, shadow, meta.z, ht, hu, hv);
     return;
   }
+#ifdef RTC_TORUS_TU
+  if (kind == 7u) {  // a torus: the quartic is solved once, for the relevance pass and for the entries
+    const TorusRoots k = torus_roots(cy, lr);
+    bool rel = false;
+    double t_first = 0.0;
+    torus_emit(k, [&](double t, double, double) {
+      if (!rel && vis.relevant(leaf, shadow, t)) {
+        rel = true;
+        t_first = t;
+      }
+    });
+    if (!rel) return;
+    if (!chain_ok(S, L.parent, ray, t_first, degenerate)) return;
+    torus_emit(k, [&](double t, double u, double v) { vis.entry(leaf, shadow, meta.z, t, u, v); });
+    return;
+  }
+#endif
   bool relevant = false;
   double t_rel = 0.0;
   leaf_entries(kind, cy, L.tri, lr, [&](double t, double, double) {
@@ -625,7 +778,7 @@ __device__ __noinline__ uint32_t csg_collect(const DevScene& S, uint32_t unit, c
     }
     const uint32_t kind = meta.x & 0xFFu;
     CylParams cy{0.0, 0.0, false};
-    if (kind == 3u || kind == 6u) {
+    if (RTC_HAS_CYL_ROW(kind)) {
       const DevCyl c = S.cyl[meta.w];
       cy = {c.ymin, c.ymax, c.closed != 0u};
     }
@@ -2334,8 +2487,11 @@ __device__ __forceinline__ Ray camera_sample(const DevCamera& cam, const DevSamp
 // compiled into those kernels only)
 // (BUMP: materials whose shading normal is perturbed - DevBumps, the bump kernels' extra argument; with SPOT, MOTION, MS
 // and AREA, compiled into those kernels only)
+// (TORUS: leaf kind 7, a quartic - leaf_entries' and the normal's case 7 and the solver, torus_quartic; with BUMP, SPOT,
+// MOTION, MS and AREA, compiled into the torus kernels' translation unit only, under RTC_TORUS_TU: the device functions
+// that are not templates - csg_collect - see the kind through the unit, not through a parameter)
 template <bool LDS, bool CSG, int WORLD = 0, int WAVES = 2, bool COOP = false, bool BOX = true, bool AREA = false, bool MS = false,
-          bool MOTION = false, bool SPOT = false, bool BUMP = false>
+          bool MOTION = false, bool SPOT = false, bool BUMP = false, bool TORUS = false>
 __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& cam, const DevPixelMap& map,
                                             const uint32_t max_depth, double* __restrict__ out,
                                             DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
@@ -2347,6 +2503,12 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
   static_assert(!MOTION || (MS && AREA && WORLD == 0), "the motion kernels are the general area-sampling walk");
   static_assert(!SPOT || MOTION, "the spot kernels are the motion walk");
   static_assert(!BUMP || SPOT, "the bump kernels are the spot walk");
+  static_assert(!TORUS || BUMP, "the torus kernels are the bump walk");
+#ifdef RTC_TORUS_TU
+  static_assert(TORUS, "the torus translation unit compiles the torus kernels only: leaf kind 7 is compiled into every walk of it");
+#else
+  static_assert(!TORUS, "leaf kind 7 is compiled in the torus translation unit (rtc_torus.hip) only");
+#endif
   RTC_PRIO_PHASE(RTC_PRIO_WORK);
 #ifndef RTC_PROFILE
   if (blockIdx.x == 0u) {  // the next launch's counters (see DevStats)
@@ -2949,7 +3111,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
       kind = meta.x & 0xFFu;
       geom = meta.w;
       mat_index = meta.z;
-      if (kind == 3u || kind == 6u) hcy = S.cyl[geom];
+      if (RTC_HAS_CYL_ROW(kind)) hcy = S.cyl[geom];
     }
 #ifdef RTC_PROFILE
     mat_index = RTC_CHECK_INDEX(RTC_OOB_MATERIALS, mat_index, RTC_AVAIL(3));
@@ -3053,6 +3215,23 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
         }
         break;
       }
+#ifdef RTC_TORUS_TU
+      case 7: {  // RTC_TORUS (rtc.h): the point minus the nearest point of the tube's centre circle
+        if constexpr (TORUS) {
+          const double R = hcy.ymin;
+          const double rho = __builtin_sqrt(lpx * lpx + lpz * lpz);
+          lny = lpy;
+          if (rho == 0.0) {
+            lnx = 0.0;
+            lnz = 0.0;
+          } else {
+            lnx = lpx - R * (lpx / rho);
+            lnz = lpz - R * (lpz / rho);
+          }
+        }
+        break;
+      }
+#endif
       case 4: {  // triangle.zig:65-70: the stored face normal
         const double* __restrict__ N = S.trin + 9ull * geom;
         lnx = N[0]; lny = N[1]; lnz = N[2];
@@ -3600,17 +3779,18 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
 
 // The kernels.  rtc_motion.hip includes this file with RTC_MOTION_TU defined and gets the motion kernels alone: a
 // translation unit of their own, so that this one compiles in the time and to the code it did; rtc_spot.hip likewise
-// with RTC_SPOT_TU and the spot kernels, rtc_bump.hip with RTC_BUMP_TU and the bump kernels.  rtc_kernels_ext.hip
+// with RTC_SPOT_TU and the spot kernels, rtc_bump.hip with RTC_BUMP_TU and the bump kernels, rtc_torus.hip with RTC_TORUS_TU
+// and the torus kernels.  rtc_kernels_ext.hip
 // includes it with RTC_EXT_TU defined: in the -DRTC_PROFILE diagnostic build, whose instrumented walk makes this unit's
 // compile about a third longer, it gets the csg / texture-map, flat and area-light kernels (rtc_render_kernel_ext to
 // rtc_render_kernel_area_bigworld below), so that neither unit takes the time of all of them.  The product build keeps
 // them here - that unit's code is the same as before to the byte - and its rtc_kernels_ext.o holds no kernel.
-#if (defined(RTC_EXT_TU) && defined(RTC_PROFILE)) || (!defined(RTC_MOTION_TU) && !defined(RTC_SPOT_TU) && !defined(RTC_BUMP_TU) && !defined(RTC_EXT_TU) && !defined(RTC_PROFILE))
+#if (defined(RTC_EXT_TU) && defined(RTC_PROFILE)) || (!defined(RTC_MOTION_TU) && !defined(RTC_SPOT_TU) && !defined(RTC_BUMP_TU) && !defined(RTC_TORUS_TU) && !defined(RTC_EXT_TU) && !defined(RTC_PROFILE))
 #define RTC_EXT_KERNELS_HERE 1
 #else
 #define RTC_EXT_KERNELS_HERE 0
 #endif
-#if !defined(RTC_MOTION_TU) && !defined(RTC_SPOT_TU) && !defined(RTC_BUMP_TU) && !defined(RTC_EXT_TU)
+#if !defined(RTC_MOTION_TU) && !defined(RTC_SPOT_TU) && !defined(RTC_BUMP_TU) && !defined(RTC_TORUS_TU) && !defined(RTC_EXT_TU)
 extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
 rtc_render_kernel(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
                   double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats) {
@@ -3671,7 +3851,7 @@ rtc_render_kernel3(const DevScene S, const DevCamera cam, const DevPixelMap map,
 }
 #endif
 
-#endif  // !RTC_MOTION_TU && !RTC_SPOT_TU && !RTC_BUMP_TU && !RTC_EXT_TU
+#endif  // !RTC_MOTION_TU && !RTC_SPOT_TU && !RTC_BUMP_TU && !RTC_TORUS_TU && !RTC_EXT_TU
 
 #if RTC_EXT_KERNELS_HERE
 // The same two kernels with the csg and texture-map paths compiled in (template flag CSG), for scenes that
@@ -3730,7 +3910,7 @@ rtc_render_kernel_area_bigworld(const DevScene S, const DevCamera cam, const Dev
 }
 #endif  // RTC_EXT_KERNELS_HERE
 
-#if !defined(RTC_MOTION_TU) && !defined(RTC_SPOT_TU) && !defined(RTC_BUMP_TU) && !defined(RTC_EXT_TU)
+#if !defined(RTC_MOTION_TU) && !defined(RTC_SPOT_TU) && !defined(RTC_BUMP_TU) && !defined(RTC_TORUS_TU) && !defined(RTC_EXT_TU)
 // Several camera samples per pixel (rtc_scene_set_sampling: anti-aliasing, focal blur): the general walk with the csg and
 // texture-map paths compiled in, the sampling parameters as an extra argument (DevSampling) - every other kernel is
 // compiled without them.  Point lights (tables in LDS or in memory), and the area-light forms.
@@ -4473,4 +4653,26 @@ rtc_render_kernel_bump_bigworld(const DevScene S, const DevCamera cam, const Dev
                                                                             spots, bumps);
 }
 
-#endif  // RTC_MOTION_TU / RTC_SPOT_TU / RTC_BUMP_TU
+#elif defined(RTC_TORUS_TU)
+
+// Torus primitives (RTC_TORUS): the bump walk with leaf kind 7 compiled in, one pair for every
+// world and every combination of sampling, passes, motion, area lights, cones and bumps (a handle without bumps passes
+// zero bump rows).  Every other kernel is compiled without it.
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_torus(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                        double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                        const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots, const DevBumps bumps) {
+  render_body<true, true, 0, 2, false, true, true, true, true, true, true, true>(S, cam, map, max_depth, out, stats, next_stats, area, smp,
+                                                                                 mo, spots, bumps);
+}
+
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_torus_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                 double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                 const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                 const DevBumps bumps) {
+  render_body<false, true, 0, 2, false, true, true, true, true, true, true, true>(S, cam, map, max_depth, out, stats, next_stats, area,
+                                                                                  smp, mo, spots, bumps);
+}
+
+#endif  // RTC_MOTION_TU / RTC_SPOT_TU / RTC_BUMP_TU / RTC_TORUS_TU

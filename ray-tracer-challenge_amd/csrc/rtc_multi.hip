@@ -533,6 +533,10 @@ const char* rtc_multi_last_error(void) { return g_multi_error.c_str(); }
 int rtc_multi_create(const rtc_scene_desc* desc, uint32_t n_gpus, uint32_t flags, rtc_multi** out) {
   g_multi_error.clear();
   if (!desc || !out || n_gpus == 0) return mfail(RTC_ERR_INVALID_ARGUMENT, "null argument or no GPUs");
+  // (a torus, RTC_TORUS: its kernels are librtc_hip's single-GPU ones; a split frame would have to render without the shape)
+  for (uint32_t i = 0; i < desc->n_leaves && desc->leaf_kind; ++i)
+    if (desc->leaf_kind[i] == RTC_TORUS)
+      return mfail(RTC_ERR_UNSUPPORTED, "leaf %u is a torus: librtc_multi does not render tori, use rtc_scene_create", i);
   *out = nullptr;
   int n_dev = 0;
   if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) return mfail(RTC_ERR_NO_DEVICE, "no HIP device is visible");

@@ -144,6 +144,13 @@ struct Flattener {
         out.cyl_max.push_back(s.ymax);
         out.cyl_closed.push_back(s.closed ? 1 : 0);
         break;
+      case ShapeKind::Torus:  // (the radii in the cyl_* rows: cyl_min the major, cyl_max the minor; cyl_closed is not read)
+        kind = RTC_TORUS;
+        geom = static_cast<uint32_t>(out.cyl_min.size());
+        out.cyl_min.push_back(s.ymin);
+        out.cyl_max.push_back(s.ymax);
+        out.cyl_closed.push_back(0);
+        break;
       case ShapeKind::Triangle:
       case ShapeKind::SmoothTriangle: {
         const bool smooth = s.kind == ShapeKind::SmoothTriangle;

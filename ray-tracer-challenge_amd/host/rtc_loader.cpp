@@ -552,6 +552,17 @@ Shape parseObject(const Value& object, const InheritedState& inherited, const De
   } else if (t == "cone") {
     shape = Shape::cone();
     parseMinMaxClosed(payload, "cone", shape);
+  } else if (t == "torus") {  // (not in the reference): {"major-radius": R, "minor-radius": r}, a ring torus
+    const Value& cfg = requireObject(payload, "torus");
+    checkFields(cfg, {"major-radius", "minor-radius"}, "torus");
+    double major = 1.0, minor = 0.25;
+    if (auto* v = cfg.find("major-radius")) major = asFloat(*v, "torus.major-radius");
+    if (auto* v = cfg.find("minor-radius")) minor = asFloat(*v, "torus.minor-radius");
+    if (!std::isfinite(major)) throw Error("InvalidData", "torus.major-radius: not finite");
+    if (!std::isfinite(minor)) throw Error("InvalidData", "torus.minor-radius: not finite");
+    if (!(minor > 0.0)) throw Error("InvalidData", "torus.minor-radius: must be above 0");
+    if (!(minor < major)) throw Error("InvalidData", "torus.minor-radius: must be below torus.major-radius (a ring torus)");
+    shape = Shape::torus(major, minor);
   } else if (t == "triangle") {
     const Value& cfg = requireObject(payload, "triangle");
     checkFields(cfg, {"p1", "p2", "p3"}, "triangle");

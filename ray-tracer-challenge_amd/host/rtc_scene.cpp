@@ -50,6 +50,12 @@ BoundingBox Shape::bounds() const {
       box.max = Tuple::point(limit, ymax, limit);
       break;
     }
+    case ShapeKind::Torus: {  // rtc.h, RTC_TORUS step 2: the object box grown by 1e-9, the box every entry lies in
+      const double bxz = (ymin + ymax) * (1.0 + 1e-9), by = ymax * (1.0 + 1e-9);
+      box.min = Tuple::point(-bxz, -by, -bxz);
+      box.max = Tuple::point(bxz, by, bxz);
+      break;
+    }
     case ShapeKind::Triangle:        // triangle.zig:72-79
     case ShapeKind::SmoothTriangle:  // triangle.zig:267-274
       box.add(p1);

@@ -178,7 +178,8 @@ struct BoundingBox {  // bounding_box.zig:21-22
 
 // ---------------------------------------------------------------- shapes
 enum class ShapeKind : uint8_t {
-  Sphere, Plane, Cube, Cylinder, Cone, Triangle, SmoothTriangle, Group, TestShape, Csg
+  Sphere, Plane, Cube, Cylinder, Cone, Triangle, SmoothTriangle, Group, TestShape, Csg,
+  Torus  // (not in the reference: the book's "Next Steps" shape)
 };
 enum class CsgOp : uint8_t { Union = 1, Intersection = 2, Difference = 3 };  // csg.zig:16-20 (== RTC_CSG_*)
 
@@ -209,7 +210,8 @@ struct Shape {
   bool casts_shadow = true;
   ShapeKind kind = ShapeKind::Sphere;
 
-  // cylinder / cone (cylinder.zig:26-28)
+  // cylinder / cone (cylinder.zig:26-28); a torus keeps its major radius in ymin and its minor radius in ymax, as the
+  // cyl_* tables of the flattened description carry them
   double ymin = -kInf, ymax = kInf;
   bool closed = false;
   // triangle / smooth triangle (triangle.zig:21-26, 214-221)
@@ -236,6 +238,12 @@ struct Shape {
   static Shape cube() { return make(ShapeKind::Cube); }
   static Shape cylinder() { return make(ShapeKind::Cylinder); }
   static Shape cone() { return make(ShapeKind::Cone); }
+  static Shape torus(double major_radius = 1.0, double minor_radius = 0.25) {  // a ring torus: 0 < minor < major
+    Shape s = make(ShapeKind::Torus);
+    s.ymin = major_radius;
+    s.ymax = minor_radius;
+    return s;
+  }
   static Shape testShape() { return make(ShapeKind::TestShape); }
   static Shape triangle(const Tuple& p1, const Tuple& p2, const Tuple& p3) {  // shape.zig:186-204
     Shape s = make(ShapeKind::Triangle);

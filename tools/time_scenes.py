@@ -36,6 +36,8 @@ ray as well.  Option spot_kernels=1 times the spot kernels without a cone.
 ripples with that amplitude, its field scaled by `scale` (1) (rtc_scene_set_bumps); on a scene file
 with "normal-perturbation" entries those are applied first; --bump off applies none.  Option bump_kernels=1 times the
 bump kernels without a bump.
+--torus: the torus kernels on a scene without a torus, as option torus_kernels=1; a scene with a
+torus runs them anyway.
 --adaptive threshold[,min,tile]: adaptive sampling at up to --max-passes (64) passes, min passes 4 and
 16 x 16 tiles by default, with the --sampling of the frames: prints the rounds and tile-passes of a run against
 T * max_passes, its time (a second run, end to end on the host) against uniform progressive passes (render_device +
@@ -75,6 +77,7 @@ ap.add_argument("--passes", type=int, default=-1)
 ap.add_argument("--motion", action="append", default=[])
 ap.add_argument("--spot", action="append", default=[])
 ap.add_argument("--bump", action="append", default=[])
+ap.add_argument("--torus", action="store_true")
 ap.add_argument("--adaptive", default="")
 ap.add_argument("--max-passes", type=int, default=64)
 args = ap.parse_args()
@@ -90,6 +93,8 @@ if args.depth:
 for opt in args.option:
     n, v = opt.split("=")
     rtc.set_option(n, float(v))
+if args.torus:  # (the torus kernels on a scene without a torus: what carrying the flag costs)
+    rtc.set_option("torus_kernels", 1.0)
 
 
 def light_table(hs, how):
@@ -298,7 +303,7 @@ for name, w, h, depth in cases:
     if delta is not None: line += f" maxdelta {delta:.2e}"
     if args.lights or args.spot or "spot_kernels=1" in args.option:
         line += f" shadow_traced {st['shadow_traced']} ns/shadow-ray {min(ts) * 1e6 / max(1, st['shadow_traced']):.3f}"
-    if args.sampling or args.option or args.passes >= 0 or args.motion or args.spot or args.bump:
+    if args.sampling or args.option or args.passes >= 0 or args.motion or args.spot or args.bump or args.torus:
         line += f" primary {st['primary']} ns/primary-ray {min(ts) * 1e6 / max(1, st['primary']):.3f}"
     if acc:
         ms, copy_ms, nbytes = min(a[0] for a in acc), min(a[1] for a in acc), acc[0][2]
