@@ -153,6 +153,7 @@ enum {
 #define RTC_TEX_PLANAR 1u
 #define RTC_TEX_CYLINDRICAL 2u
 #define RTC_TEX_CUBIC 3u
+#define RTC_TEX_MESH 4u /* not in the reference: (u, v) from the hit triangle's texture row, see rtc_scene_set_mesh_uvs */
 /* rtc_scene_desc::uv_kind: UvPattern variants (texture_map.zig:9-121) */
 #define RTC_UV_ALIGN_CHECK 0u /* uv_sub = central, upper-left, upper-right, bottom-left, bottom-right */
 #define RTC_UV_CHECKERS 1u    /* uv_size = width, height; uv_sub[0..1] = a, b                        */
@@ -486,6 +487,39 @@ typedef struct rtc_bump {
  * without bumps.
  */
 int rtc_scene_set_bumps(rtc_scene *scene, const rtc_bump *bumps);
+
+/* ---- UV-mapped mesh textures: OBJ texture coordinates on triangles ---- */
+/*
+ * RTC_TEX_MESH is a fifth tex_mapping.  It uses tex_uv entry 0, like every mapping but the cubic one.  Where the other
+ * mappings find (u, v) from the pattern-space point, a texture map of this mapping is evaluated for a hit whose leaf is a
+ * triangle (RTC_TRIANGLE or RTC_SMOOTH_TRIANGLE) with
+ *   - that triangle's texture row (a1, b1, a2, b2, a3, b3): the (u, v) of p1, p2, p3, row leaf_geom of the table below;
+ *   - the entry's barycentrics (u, v), exactly as Moller-Trumbore (triangle.zig:29-63, 225-259) produced them for the entry
+ *     that became the hit - the values the smooth normal n2 * u + n3 * v + n1 * (1 - u - v) is formed with.
+ *     w  = (1.0 - u) - v
+ *     tu = (a2 * u + a3 * v) + a1 * w
+ *     tv = (b2 * u + b3 * v) + b1 * w
+ *     each of tu, tv: if it is < 0.0 or > 1.0, it becomes x - floor(x)      (tiling; 0.0 and 1.0 stay)
+ * After that the uv pattern of tex_uv entry 0 - align check, uv checkers, uv image with either interpolation, uv test - is
+ * evaluated at (tu, tv) as for every other mapping.  The pattern's own inverse transform is not applied to (tu, tv): the row
+ * is the placement.  A sub-pattern the uv pattern selects (align check, uv checkers) is evaluated at the object point, as
+ * for the other mappings.  On a hit whose leaf is not a triangle, and on a handle without a texture table, the row is six
+ * zeros and (u, v) = (0, 0): tu = tv = 0.  The map may sit wherever a texture map may - below stripes, checkers, a perturb,
+ * a blend -: the hit's triangle and barycentrics are constants of the whole pattern evaluation (a perturb moves the object
+ * point, never them).  Only + - * floor and comparisons are added, each operation correctly rounded, in the order written.
+ */
+typedef struct rtc_mesh_uvs {
+  uint32_t n_tris;  /* the handle's triangle count (rtc_scene_desc::n_tris) */
+  const double *uv; /* [n_tris][6]: (a1, b1, a2, b2, a3, b3) per triangle, in tri_* order */
+} rtc_mesh_uvs;
+
+/*
+ * This handle's texture rows for every render entry point (NULL: the all-zero rows).  Validated before anything changes:
+ * RTC_ERR_INVALID_ARGUMENT for an n_tris other than the handle's, or a value that is not finite.  A clone starts with its
+ * source's rows; rtc_render's band clones follow.  A handle whose description has a map of mapping RTC_TEX_MESH renders
+ * with the meshuv kernels whether or not it has a table; librtc_multi refuses such a description.
+ */
+int rtc_scene_set_mesh_uvs(rtc_scene *scene, const rtc_mesh_uvs *uvs);
 
 /* ---- adaptive sampling: progressive passes only for tiles still noisy ---- */
 #define RTC_ADAPTIVE_MAX_TILE 1024u

@@ -35,7 +35,8 @@ extern "C" {
  * (!= 0: the spot kernels even on a handle without cones, every flag zero, so that their images can be held to the
  * motion kernels'), "bump_kernels" (!= 0: the bump kernels even on a handle without bumps, every row of kind none, so that
  * their images can be held to the spot kernels'), "torus_kernels" (!= 0: the torus kernels even on a handle without a
- * torus, so that their images can be held to the bump kernels').
+ * torus, so that their images can be held to the bump kernels'), "meshuv_kernels" (!= 0: the meshuv kernels even on a
+ * handle without a texture map of mapping RTC_TEX_MESH, so that their images can be held to the handle's ordinary kernels').
  * RTC_ERR_INVALID_ARGUMENT for a name the library does not know.
  * (The library reads no environment variables.)
  */

@@ -20,7 +20,8 @@
  *                        top-level objects' motion, rtch_scene_motion, through rtc_scene_set_motion; its adaptive
  *                        sampling, rtch_scene_adaptive, through rtc_render_adaptive; its spot lights,
  *                        rtch_scene_spots, through rtc_scene_set_spots; its materials' normal perturbation,
- *                        rtch_scene_bumps, through rtc_scene_set_bumps)
+ *                        rtch_scene_bumps, through rtc_scene_set_bumps; its triangles' texture rows,
+ *                        rtch_scene_mesh_uvs, through rtc_scene_set_mesh_uvs)
  *
  * Every function that returns int returns 0 on success; otherwise rtch_last_error()
  * holds "<ZigStyleErrorName>: detail" (thread-local).
@@ -77,6 +78,11 @@ int rtch_scene_spots(void *handle, uint8_t *cone, double *axis, double *cos_inne
  * inverse; n must be the description's n_materials.  A material with the key is a mat_* row of its own.  Pass them to
  * rtc_scene_set_bumps.  rtch_scene_render applies them. */
 int rtch_scene_bumps(void *handle, uint8_t *kind, double *amplitude, uint32_t *octaves, double *persistence, double *inverse, uint32_t n);
+/* The triangles' texture rows (UV-mapped mesh textures), in tri_* order: out[6 i ..] = (a1, b1, a2,
+ * b2, a3, b3), the (u, v) of triangle i's p1, p2, p3 - from a "from-obj" with "texture-coordinates": true (`vt` lines and
+ * the faces' t fields) or a "triangle" with "uv1", "uv2", "uv3"; six zeros for every other triangle; n must be the
+ * description's n_tris.  Pass them to rtc_scene_set_mesh_uvs.  rtch_scene_render applies them. */
+int rtch_scene_mesh_uvs(void *handle, double *out, uint32_t n);
 int rtch_scene_camera(void *handle, uint32_t width, uint32_t height, rtc_camera *out);
 int rtch_camera_rotate(void *handle, double angle);
 int rtch_camera_move(void *handle, double distance);

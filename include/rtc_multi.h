@@ -42,7 +42,8 @@ typedef struct rtc_multi rtc_multi; /* opaque: per frame slot n scene handles an
 /* Replicates the scene on devices 0 .. n_gpus-1 of this process and creates the communicators (ncclCommInitAll).
  * Its handles render one centred camera sample per pixel: rtc_scene_set_sampling (rtc.h) has no multi-GPU form yet;
  * neither have rtc_scene_set_spots and rtc_scene_set_bumps: it renders without cones and without bumps.
- * A description with a torus (RTC_TORUS) is refused with RTC_ERR_UNSUPPORTED: its kernels are single-GPU ones. */
+ * A description with a torus (RTC_TORUS) is refused with RTC_ERR_UNSUPPORTED: its kernels are single-GPU ones; so is one
+ * with a texture map of mapping RTC_TEX_MESH (rtc_scene_set_mesh_uvs has no multi-GPU form). */
 int rtc_multi_create(const rtc_scene_desc *desc, uint32_t n_gpus, uint32_t flags, rtc_multi **out);
 void rtc_multi_destroy(rtc_multi *m);
 

@@ -220,8 +220,15 @@ BUMP_NONE, BUMP_NOISE, BUMP_RIPPLES = 0, 1, 2  # RTC_BUMP_*
 # leaf kinds (rtc.h); RTC_TORUS: a ring torus, its major and minor radius in cyl_min / cyl_max
 RTC_SPHERE, RTC_PLANE, RTC_CUBE, RTC_CYLINDER, RTC_TRIANGLE, RTC_SMOOTH_TRIANGLE, RTC_CONE, RTC_TORUS = range(8)
 # the options that select a kernel family on a handle that does not need it (set_option; tests and tools/time_scenes.py)
-KERNEL_OPTIONS = ("sampling_kernels", "motion_kernels", "spot_kernels", "bump_kernels", "torus_kernels")
+KERNEL_OPTIONS = ("sampling_kernels", "motion_kernels", "spot_kernels", "bump_kernels", "torus_kernels", "meshuv_kernels")
+# texture mappings (rtc.h); RTC_TEX_MESH: (u, v) from the hit triangle's texture row
+RTC_TEX_SPHERICAL, RTC_TEX_PLANAR, RTC_TEX_CYLINDRICAL, RTC_TEX_CUBIC, RTC_TEX_MESH = range(5)
 BUMP_MAX_OCTAVES = 16  # RTC_BUMP_MAX_OCTAVES
+
+
+class MeshUvs(C.Structure):
+    """struct rtc_mesh_uvs (include/rtc.h): a texture row (a1, b1, a2, b2, a3, b3) per triangle, in tri_* order."""
+    _fields_ = [("n_tris", C.c_uint32), ("uv", C.POINTER(C.c_double))]
 
 
 class Bump(C.Structure):
@@ -264,13 +271,13 @@ RTC_SYMBOLS = ["rtc_scene_create", "rtc_scene_clone", "rtc_scene_destroy", "rtc_
                "rtc_scene_create_with_lights", "rtc_scene_set_light_seed", "rtc_scene_set_sampling",
                "rtc_scene_set_sample_pass", "rtc_scene_accumulate_device", "rtc_scene_set_motion",
                "rtc_scene_adaptive_begin_device", "rtc_scene_adaptive_accumulate_device", "rtc_scene_adaptive_step", "rtc_render_adaptive",
-               "rtc_scene_set_spots", "rtc_scene_set_bumps"]
+               "rtc_scene_set_spots", "rtc_scene_set_bumps", "rtc_scene_set_mesh_uvs"]
 # (... and include/rtc_diag.h: diagnostics and tuning, for the tests, bench.py and tools/)
 RTC_DIAG_SYMBOLS = ["rtc_set_option", "rtc_last_kernel_name", "rtc_get_schedule", "rtc_get_chunk_times", "rtc_diag_build_tables", "rtc_diag_root_boxes"]
 HOST_SYMBOLS = ["rtch_last_error", "rtch_scene_load", "rtch_scene_free", "rtch_scene_desc", "rtch_scene_camera",
                 "rtch_camera_rotate", "rtch_camera_move", "rtch_camera_make", "rtch_canvas_ppm", "rtch_canvas_rgba8", "rtch_scene_render", "rtch_set_loader_threads",
                 "rtch_scene_lights", "rtch_scene_sampling", "rtch_scene_passes", "rtch_scene_motion", "rtch_scene_adaptive",
-                "rtch_scene_spots", "rtch_scene_bumps"]
+                "rtch_scene_spots", "rtch_scene_bumps", "rtch_scene_mesh_uvs"]
 
 MULTI_SYMBOLS = ["rtc_multi_create", "rtc_multi_destroy", "rtc_multi_render", "rtc_multi_render_rgba8", "rtc_multi_render_device", "rtc_multi_render_rgba8_device",
                  "rtc_multi_synchronize", "rtc_multi_stream", "rtc_multi_get_stats", "rtc_multi_balance", "rtc_multi_last_error"]
@@ -332,6 +339,7 @@ def hip_lib():
                                                 C.POINTER(C.c_uint32), C.c_void_p]
         lib.rtc_scene_set_spots.argtypes = [C.c_void_p, C.POINTER(Spot)]
         lib.rtc_scene_set_bumps.argtypes = [C.c_void_p, C.POINTER(Bump)]
+        lib.rtc_scene_set_mesh_uvs.argtypes = [C.c_void_p, C.POINTER(MeshUvs)]
         lib.rtc_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.POINTER(Adaptive), C.c_void_p, C.c_void_p]
         lib.rtc_scene_destroy.argtypes = [C.c_void_p]
         lib.rtc_scene_destroy.restype = None
@@ -386,6 +394,7 @@ def host_lib():
         lib.rtch_scene_motion.argtypes = [C.c_void_p, _dp, C.c_uint32]
         lib.rtch_scene_spots.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), _dp, _dp, _dp, C.c_uint32]
         lib.rtch_scene_bumps.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), _dp, C.POINTER(C.c_uint32), _dp, _dp, C.c_uint32]
+        lib.rtch_scene_mesh_uvs.argtypes = [C.c_void_p, _dp, C.c_uint32]
         lib.rtch_scene_adaptive.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(Adaptive)]
         lib.rtch_scene_camera.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Camera)]
         lib.rtch_camera_rotate.argtypes = [C.c_void_p, C.c_double]
@@ -572,6 +581,14 @@ class HostScene:
                                                 out["inverse"].ctypes.data_as(_dp), n))
         return out if out["kind"].any() else None
 
+    def mesh_uvs(self):
+        """The triangles' texture rows (rtch_scene_mesh_uvs), in tri_* order: an (n_tris, 6) array of (a1, b1, a2, b2, a3, b3)
+        - what GpuScene.set_mesh_uvs takes -, or None when no triangle has texture coordinates."""
+        n = self.desc.n_tris
+        out = np.zeros((n, 6))
+        _check_host(host_lib().rtch_scene_mesh_uvs(self._h, out.ctypes.data_as(_dp), n))
+        return out if out.any() else None
+
     def adaptive(self):
         """The camera's "sampling": {"adaptive": ...} of the scene file (rtch_scene_adaptive): an Adaptive whose max_passes
         is "passes", or None when the file has none."""
@@ -676,6 +693,18 @@ class GpuScene:
             return
         b, _keep = bump_struct(bumps)
         _check_hip(hip_lib().rtc_scene_set_bumps(self._s, C.byref(b)))
+
+    def set_mesh_uvs(self, uvs):
+        """rtc_scene_set_mesh_uvs: an (n_tris, 6) array of texture rows (a1, b1, a2, b2, a3, b3), one per triangle in tri_*
+        order (HostScene.mesh_uvs()); None: the all-zero rows."""
+        if uvs is None:
+            _check_hip(hip_lib().rtc_scene_set_mesh_uvs(self._s, None))
+            return
+        u = np.ascontiguousarray(uvs, dtype=np.float64)
+        if u.ndim != 2 or u.shape[1] != 6:
+            raise ValueError(f"set_mesh_uvs: rows of shape {u.shape}, (n_tris, 6) expected")
+        m = MeshUvs(u.shape[0], u.ctypes.data_as(_dp))
+        _check_hip(hip_lib().rtc_scene_set_mesh_uvs(self._s, C.byref(m)))
 
     def accumulate_device(self, accum, stream=None):
         """rtc_scene_accumulate_device: an Accum, enqueued on `stream` (None: the handle's own) after this handle's renders."""

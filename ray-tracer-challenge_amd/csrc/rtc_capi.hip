@@ -131,6 +131,18 @@ __global__ void rtc_render_kernel_torus_bigworld(const DevScene S, const DevCame
                                                  const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
                                                  const DevBumps bumps);
 }
+// The meshuv kernels (RTC_TEX_MESH: texture maps that read the hit triangle's texture row): the torus kernels' tables and
+// edge, and the rows (DevMeshUvs) as one more argument.
+extern "C" {
+__global__ void rtc_render_kernel_meshuv(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                         double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                         const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                         const DevBumps bumps, const DevMeshUvs muv);
+__global__ void rtc_render_kernel_meshuv_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                                  double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                                  const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                                  const DevBumps bumps, const DevMeshUvs muv);
+}
 // Progressive rendering's accumulation (rtc_accum.hip): the grid's blocks for n pixels (the noise partials it writes, at
 // most) and the enqueue of its kernels.
 uint32_t rtcAccumBlocks(size_t n_pixels, bool wide);
@@ -345,7 +357,8 @@ bool tablesInLds(const rtc_scene* s) {
 
 // (the area kernels take one more argument, DevAreaLights: `area` instead of `fn`; the sampling kernels DevSampling:
 // `ms`, and both: `area_ms`; the motion kernels both and DevMotion: `motion`; the spot kernels those three and DevSpots:
-// `spot`; the bump kernels those four and DevBumps: `bump` - the torus kernels take the same arguments and travel in `bump` too)
+// `spot`; the bump kernels those four and DevBumps: `bump` - the torus kernels take the same arguments and travel in `bump` too;
+// the meshuv kernels those five and DevMeshUvs: `meshuv`)
 struct KernelChoice {
   decltype(&rtc_render_kernel) fn;
   const char* name;
@@ -355,6 +368,7 @@ struct KernelChoice {
   decltype(&rtc_render_kernel_motion) motion = nullptr;
   decltype(&rtc_render_kernel_spot) spot = nullptr;
   decltype(&rtc_render_kernel_bump) bump = nullptr;
+  decltype(&rtc_render_kernel_meshuv) meshuv = nullptr;
   KernelChoice(decltype(&rtc_render_kernel) f, const char* n) : fn(f), name(n) {}
   KernelChoice(decltype(&rtc_render_kernel_area) a, const char* n) : fn(nullptr), name(n), area(a) {}
   KernelChoice(decltype(&rtc_render_kernel_ms) m, const char* n) : fn(nullptr), name(n), ms(m) {}
@@ -362,11 +376,12 @@ struct KernelChoice {
   KernelChoice(decltype(&rtc_render_kernel_motion) mo, const char* n) : fn(nullptr), name(n), motion(mo) {}
   KernelChoice(decltype(&rtc_render_kernel_spot) sk, const char* n) : fn(nullptr), name(n), spot(sk) {}
   KernelChoice(decltype(&rtc_render_kernel_bump) bk, const char* n) : fn(nullptr), name(n), bump(bk) {}
+  KernelChoice(decltype(&rtc_render_kernel_meshuv) uk, const char* n) : fn(nullptr), name(n), meshuv(uk) {}
   void launch(uint32_t blocks, hipStream_t stream, const rtc_scene* s, const DevScene& dev, const DevCamera& cam, const DevPixelMap& map,
               uint32_t max_depth, double* d_out, DevStats* st_now, DevStats* st_next) const {
     DevSampling smp = s->sampling;  // (the pass's area-light offset, P * N * S: N is the camera's whole image)
     smp.pixel_base = static_cast<unsigned long long>(smp.sample_base) * (static_cast<unsigned long long>(cam.hsize) * cam.vsize);
-    if (motion || spot || bump) {
+    if (motion || spot || bump || meshuv) {
       // the handle's root tables with the moving roots' bounds (or the scene's, all displacements zero: the option), and
       // the scene's area rows (or zero rows: a point-only table); the spot kernels also the handle's spot rows (or zero
       // rows, every flag 0: the option)
@@ -382,7 +397,12 @@ struct KernelChoice {
         mo.disp = m->disp.p;
       }
       const DevAreaLights area = s->area_kernel ? s->area : DevAreaLights{s->tab->zero_rows.p, s->area.seed};
-      if (bump) {  // (the handle's bump rows, or zero rows, every kind none: the option)
+      if (meshuv) {  // (the handle's texture rows, or none: every row six zeros)
+        const DevSpots sp{s->spots ? s->spots->row.p : s->tab->zero_rows.p};
+        const DevBumps bp{s->bumps ? s->bumps->row.p : s->tab->zero_bump.p};
+        const DevMeshUvs uv{s->mesh_uvs ? s->mesh_uvs->row.p : nullptr};
+        hipLaunchKernelGGL(meshuv, dim3(blocks), dim3(256), 0, stream, md, cam, map, max_depth, d_out, st_now, st_next, area, smp, mo, sp, bp, uv);
+      } else if (bump) {  // (the handle's bump rows, or zero rows, every kind none: the option)
         const DevSpots sp{s->spots ? s->spots->row.p : s->tab->zero_rows.p};
         const DevBumps bp{s->bumps ? s->bumps->row.p : s->tab->zero_bump.p};
         hipLaunchKernelGGL(bump, dim3(blocks), dim3(256), 0, stream, md, cam, map, max_depth, d_out, st_now, st_next, area, smp, mo, sp, bp);
@@ -417,6 +437,9 @@ bool bumpKernels(const rtc_scene* s) { return s->bumps != nullptr || rtcOptions(
 // The torus kernels run when a leaf of the handle's world is a torus - whatever the sampling, the pass, the motion, the
 // cones and the bumps: no other kernel knows kind 7 - or, for tests, whenever option "torus_kernels" is set.
 bool torusKernels(const rtc_scene* s) { return s->has_torus || rtcOptions().torus_kernels != 0.0; }
+// The meshuv kernels run when a texture map of the handle's scene has mapping RTC_TEX_MESH - whatever else the handle
+// holds, tori included: no other kernel knows mapping 4 - or, for tests, whenever option "meshuv_kernels" is set.
+bool meshuvKernels(const rtc_scene* s) { return s->has_mesh_map || rtcOptions().meshuv_kernels != 0.0; }
 #define RTC_KERNEL(k) KernelChoice{k, #k}
 // The general kernel at three waves per SIMD (rtc_render_kernel3): forced by option "waves3", else what the handle's
 // trial measured (KernelTune in launch()).
@@ -443,6 +466,7 @@ KernelChoice ldsKernel(const rtc_scene* s, const DevPixelMap& map) {
   return s->ext_kernel ? RTC_KERNEL(rtc_render_kernel_ext) : RTC_KERNEL(rtc_render_kernel);
 }
 KernelChoice renderKernel(const rtc_scene* s, const DevPixelMap& map) {
+  if (meshuvKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_meshuv) : RTC_KERNEL(rtc_render_kernel_meshuv_bigworld);
   if (torusKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_torus) : RTC_KERNEL(rtc_render_kernel_torus_bigworld);
   if (bumpKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_bump) : RTC_KERNEL(rtc_render_kernel_bump_bigworld);
   if (spotKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_spot) : RTC_KERNEL(rtc_render_kernel_spot_bigworld);
@@ -459,6 +483,7 @@ KernelChoice renderKernel(const rtc_scene* s, const DevPixelMap& map) {
 
 // Work-groups of the launch's kernel that are resident at once, and the waves in them.
 uint32_t residentBlocksAlone(const rtc_scene* s, const DevPixelMap& map) {
+  if (meshuvKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_meshuv_lds : s->blocks_per_cu_meshuv_big);
   if (torusKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_torus_lds : s->blocks_per_cu_torus_big);
   if (bumpKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_bump_lds : s->blocks_per_cu_bump_big);
   if (spotKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_spot_lds : s->blocks_per_cu_spot_big);
@@ -867,7 +892,7 @@ int launch(rtc_scene* s, const rtc_camera& cam, const DevPixelMap& map_in, uint3
   int trial_slot = -1;
   {
     rtc_scene::KernelTune& T = s->tune;
-    const bool eligible = !samplingKernels(s) && !motionKernels(s) && !spotKernels(s) && !bumpKernels(s) && !torusKernels(s) &&  // (the sampling, motion, spot, bump and torus kernels have no three-wave form)
+    const bool eligible = !samplingKernels(s) && !motionKernels(s) && !spotKernels(s) && !bumpKernels(s) && !torusKernels(s) && !meshuvKernels(s) &&  // (the sampling, motion, spot, bump, torus and meshuv kernels have no three-wave form)
                           ((s->general3_ok && rtcOptions().waves3 < 0.0 && tablesInLds(s) &&
                             !(s->tab && s->tab->handles.load(std::memory_order_relaxed) > 1) &&
                             static_cast<double>(map.n_chunks) >= 4.0 * 4.0 * s->n_cus * s->blocks_per_cu_lds) ||
@@ -1035,6 +1060,7 @@ struct RootBox {   // host form of one world box; uploaded two to a RootBoxPair.
 struct SceneTraits {
   bool has_csg = false;     // some node is a csg operation
   bool has_torus = false;   // some leaf is a torus: the torus kernels
+  bool has_mesh_map = false;  // some texture map has mapping RTC_TEX_MESH: the meshuv kernels
   bool ext_kernel = false;  // csg, texture maps or nested mixing patterns: the `_ext` kernels
   bool nested_patterns = false;  // a gradient / blend below a gradient / blend
   uint32_t max_stack = 0;   // traversal stack the deepest group tree needs
@@ -1102,7 +1128,8 @@ int validateScene(const rtc_scene_desc& d, SceneTraits& traits) {
     }
   }
   for (uint32_t i = 0; i < d.n_texmaps; ++i) {
-    if (d.tex_mapping[i] > RTC_TEX_CUBIC) return fail(RTC_ERR_UNSUPPORTED, "texture map %u: mapping %u", i, d.tex_mapping[i]);
+    if (d.tex_mapping[i] == RTC_TEX_MESH) traits.has_mesh_map = true;
+    else if (d.tex_mapping[i] > RTC_TEX_CUBIC) return fail(RTC_ERR_UNSUPPORTED, "texture map %u: mapping %u", i, d.tex_mapping[i]);
     for (int f = 0; f < 6; ++f)
       if (d.tex_uv[6ull * i + f] >= d.n_uvs) return fail(RTC_ERR_BAD_INDEX, "texture map %u: uv pattern index out of range", i);
   }
@@ -2151,6 +2178,8 @@ int uploadTables(const rtc_scene_desc& d, const SceneTraits& traits, const HostT
   const bool has_csg = traits.has_csg, ext_kernel = traits.ext_kernel;
   s->has_csg = has_csg;
   s->has_torus = traits.has_torus;
+  s->has_mesh_map = traits.has_mesh_map;
+  s->n_tris = d.n_tris;
   s->ext_kernel = ext_kernel;
   // Worlds without groups (or csg: a csg is a node) that fit the LDS tables run kernels without the group traversal:
   // `flat` (every leaf kind), or `simple` when all leaves are spheres, planes or cubes; each with an `_ext` form when
@@ -2239,6 +2268,10 @@ int uploadTables(const rtc_scene_desc& d, const SceneTraits& traits, const HostT
     s->blocks_per_cu_torus_lds = static_cast<uint32_t>(std::max(nb, 1));
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_torus_bigworld, 256, 0));
     s->blocks_per_cu_torus_big = static_cast<uint32_t>(std::max(nb, 1));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_meshuv, 256, 0));  // (the meshuv kernels: one pair for every world)
+    s->blocks_per_cu_meshuv_lds = static_cast<uint32_t>(std::max(nb, 1));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_meshuv_bigworld, 256, 0));
+    s->blocks_per_cu_meshuv_big = static_cast<uint32_t>(std::max(nb, 1));
     if (const int v = static_cast<int>(rtcOptions().blocks_per_cu); v >= 1) {  // (tuning option)
       s->blocks_per_cu_lds = std::min<uint32_t>(s->blocks_per_cu_lds, v), s->blocks_per_cu_big = std::min<uint32_t>(s->blocks_per_cu_big, v);
       s->blocks_per_cu_ms_lds = std::min<uint32_t>(s->blocks_per_cu_ms_lds, v), s->blocks_per_cu_ms_big = std::min<uint32_t>(s->blocks_per_cu_ms_big, v);
@@ -2246,6 +2279,7 @@ int uploadTables(const rtc_scene_desc& d, const SceneTraits& traits, const HostT
       s->blocks_per_cu_spot_lds = std::min<uint32_t>(s->blocks_per_cu_spot_lds, v), s->blocks_per_cu_spot_big = std::min<uint32_t>(s->blocks_per_cu_spot_big, v);
       s->blocks_per_cu_bump_lds = std::min<uint32_t>(s->blocks_per_cu_bump_lds, v), s->blocks_per_cu_bump_big = std::min<uint32_t>(s->blocks_per_cu_bump_big, v);
       s->blocks_per_cu_torus_lds = std::min<uint32_t>(s->blocks_per_cu_torus_lds, v), s->blocks_per_cu_torus_big = std::min<uint32_t>(s->blocks_per_cu_torus_big, v);
+      s->blocks_per_cu_meshuv_lds = std::min<uint32_t>(s->blocks_per_cu_meshuv_lds, v), s->blocks_per_cu_meshuv_big = std::min<uint32_t>(s->blocks_per_cu_meshuv_big, v);
     }
   }
   DevScene& D = s->dev;
@@ -2771,6 +2805,35 @@ int rtc_scene_set_bumps(rtc_scene* s, const rtc_bump* bumps) {
   return RTC_OK;
 }
 
+// ---- mesh texture coordinates
+// Validated before anything changes: first the table's own values - so that they are checked whatever the handle -, then
+// its triangle count against the handle's.  NULL (or a handle without triangles): no table, every row six zeros.
+int rtc_scene_set_mesh_uvs(rtc_scene* s, const rtc_mesh_uvs* uvs) {
+  g_error.clear();
+  if (!s) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
+  std::shared_ptr<const MeshUvTables> tables;  // (NULL: none)
+  if (uvs) {
+    const uint32_t n = uvs->n_tris;
+    if (n != 0u && !uvs->uv) return fail(RTC_ERR_INVALID_ARGUMENT, "mesh uvs: null uv");
+    for (size_t i = 0; i < static_cast<size_t>(RTC_MESHUV_ROW) * n; ++i)
+      if (!std::isfinite(uvs->uv[i]))
+        return fail(RTC_ERR_INVALID_ARGUMENT, "mesh uvs: triangle %zu: a texture coordinate that is not finite", i / RTC_MESHUV_ROW);
+    if (n != s->n_tris) return fail(RTC_ERR_INVALID_ARGUMENT, "mesh uvs: n_tris %u, the scene has %u", n, s->n_tris);
+    if (n != 0u) {
+      auto t = std::make_shared<MeshUvTables>();
+      HIP_TRY(hipSetDevice(s->device));
+      HIP_TRY(t->row.upload(std::vector<double>(uvs->uv, uvs->uv + static_cast<size_t>(RTC_MESHUV_ROW) * n)));
+      tables = std::move(t);
+    }
+  }
+  // (the rows being replaced may still be read by a launch of this handle or of its band clones)
+  HIP_TRY(handleIdle(s));
+  for (rtc_scene* b : s->band) HIP_TRY(handleIdle(b));
+  s->mesh_uvs = tables;
+  for (rtc_scene* b : s->band) b->mesh_uvs = tables;  // (the band clones rtc_render renders a large frame with)
+  return RTC_OK;
+}
+
 // ---- adaptive sampling
 // The setting's own fields, and the image's tile count (T < 2^31)
 static int checkAdaptive(const rtc_adaptive* a, uint32_t hsize, uint32_t vsize, uint32_t* n_tiles) {
@@ -2985,6 +3048,11 @@ int rtc_scene_clone(const rtc_scene* src, rtc_scene** out) {
   s->has_torus = src->has_torus;
   s->blocks_per_cu_torus_lds = src->blocks_per_cu_torus_lds;
   s->blocks_per_cu_torus_big = src->blocks_per_cu_torus_big;
+  s->has_mesh_map = src->has_mesh_map;
+  s->n_tris = src->n_tris;
+  s->mesh_uvs = src->mesh_uvs;  // (shared: read-only once made)
+  s->blocks_per_cu_meshuv_lds = src->blocks_per_cu_meshuv_lds;
+  s->blocks_per_cu_meshuv_big = src->blocks_per_cu_meshuv_big;
   s->simple_kernel = src->simple_kernel;
   s->flat_kernel = src->flat_kernel;
   s->simple3_ok = src->simple3_ok;
@@ -3383,7 +3451,7 @@ int rtc_set_option(const char* name, double value) {
                {"inflight_chunks_per_wave", &o.inflight_chunks_per_wave}, {"build_threads", &o.build_threads}, {"box_cull", &o.box_cull},
                {"sampling_kernels", &o.sampling_kernels}, {"motion_kernels", &o.motion_kernels},
                {"spot_kernels", &o.spot_kernels}, {"bump_kernels", &o.bump_kernels},
-               {"torus_kernels", &o.torus_kernels}};
+               {"torus_kernels", &o.torus_kernels}, {"meshuv_kernels", &o.meshuv_kernels}};
   for (const auto& e : table)
     if (std::strcmp(e.name, name) == 0) {
       e.slot->set(value);

@@ -348,6 +348,14 @@ struct DevBumps {
   const double* __restrict__ row;  // [n_materials][RTC_BUMP_ROW]
 };
 
+// Mesh texture coordinates (rtc_scene_set_mesh_uvs): the extra argument of the meshuv kernels only.
+// One row of RTC_MESHUV_ROW doubles per triangle, in tri_* order: (a1, b1, a2, b2, a3, b3), the (u, v) of p1, p2, p3.
+// Null on a handle without a table: every row is six zeros (RTC_TEX_MESH in rtc.h).
+#define RTC_MESHUV_ROW 6u
+struct DevMeshUvs {
+  const double* __restrict__ row;  // [n_tris][RTC_MESHUV_ROW], or null
+};
+
 struct DevCamera {
   double half_width, half_height, pixel_size;
   double inv[12];  // rows 0..2 of Camera._inverse_transform

@@ -1992,10 +1992,28 @@ __device__ __forceinline__ void bump_ripples(double qx, double qz, double& dx, d
   dz = h * (qz / r);
 }
 
+#ifdef RTC_MESHUV_TU
+// RTC_TEX_MESH (rtc.h): what the pattern evaluation of the meshuv kernels knows of the hit - the
+// texture table, the hit triangle's index in it (RTC_NO_LEAF: the hit leaf is no triangle, or the handle has no table: six
+// zeros and (0, 0)) and the entry's barycentrics.  Constants of the whole evaluation, passed by value: three scalars and a
+// pointer, never an array.  Compiled into the meshuv kernels' translation unit only - in every other unit the two macros
+// are empty and the pattern functions have the arguments they had.
+struct MeshUvHit {
+  const double* rows;
+  uint32_t tri;
+  double u, v;
+};
+#define RTC_MESHUV_PARAM , const MeshUvHit mh
+#define RTC_MESHUV_ARG , mh
+#else
+#define RTC_MESHUV_PARAM
+#define RTC_MESHUV_ARG
+#endif
+
 // TextureMap.patternAt + UvPattern.uvPatternAt (texture_map.zig).  Returns the sub-pattern the uv pattern
 // selects (align check, uv checkers), or RTC_NO_LEAF with the colour in `out` (uv test pattern, uv image).
 // Out of line: scenes without texture maps never run it.
-__device__ __noinline__ uint32_t texture_map_at(const DevScene& S, uint32_t tex, double px, double py, double pz, Rgb& out) {
+__device__ __noinline__ uint32_t texture_map_at(const DevScene& S, uint32_t tex, double px, double py, double pz, Rgb& out RTC_MESHUV_PARAM) {
   const DevTexMap tm = S.tex[tex];
   const double kPi = 3.14159265358979323846264338327950288;
   double u, v;
@@ -2015,6 +2033,21 @@ __device__ __noinline__ uint32_t texture_map_at(const DevScene& S, uint32_t tex,
     const double raw_u = theta / (2.0 * kPi);
     u = 1.0 - (raw_u + 0.5);
     v = zig_mod(py, 1.0);
+#ifdef RTC_MESHUV_TU
+  } else if (tm.mapping == 4u) {  // RTC_TEX_MESH (rtc.h): the hit triangle's texture row at the entry's barycentrics
+    double a1 = 0.0, b1 = 0.0, a2 = 0.0, b2 = 0.0, a3 = 0.0, b3 = 0.0, bu = 0.0, bv = 0.0;
+    if (mh.tri != RTC_NO_LEAF) {
+      const double* __restrict__ R = mh.rows + static_cast<size_t>(RTC_MESHUV_ROW) * mh.tri;
+      a1 = R[0]; b1 = R[1]; a2 = R[2]; b2 = R[3]; a3 = R[4]; b3 = R[5];
+      bu = mh.u;
+      bv = mh.v;
+    }
+    const double w = (1.0 - bu) - bv;
+    u = (a2 * bu + a3 * bv) + a1 * w;
+    v = (b2 * bu + b3 * bv) + b1 * w;
+    if (u < 0.0 || u > 1.0) u = u - __builtin_floor(u);  // tiling; 0.0 and 1.0 stay
+    if (v < 0.0 || v > 1.0) v = v - __builtin_floor(v);
+#endif
   } else {  // cubic, :219-303; faces: front 0, back 1, left 2, right 3, up 4, down 5
     const double coord = zmax(__builtin_fabs(px), zmax(__builtin_fabs(py), __builtin_fabs(pz)));
     face = 1u;
@@ -2084,7 +2117,7 @@ __device__ __noinline__ uint32_t texture_map_at(const DevScene& S, uint32_t tex,
 // A perturb on the way moves the object point, for everything below it: (ox, oy, oz) is in/out.
 template <bool EXT>
 __device__ __forceinline__ bool pattern_chain(const DevScene& S, const DevPattern* __restrict__ pat, uint32_t& idx,
-                                              double& ox, double& oy, double& oz, Rgb& out) {
+                                              double& ox, double& oy, double& oz, Rgb& out RTC_MESHUV_PARAM) {
   for (int guard = 0; guard < 64; ++guard) {
     const DevPattern& P = pat[idx];
     const uint32_t kind = P.kind;
@@ -2109,7 +2142,7 @@ __device__ __forceinline__ bool pattern_chain(const DevScene& S, const DevPatter
     } else if (EXT && kind == 8) {  // texture_map.zig: (u, v) from the PATTERN point, then a uv pattern
       if constexpr (EXT) {          // (only the *_ext kernels carry this path)
         Rgb c;
-        const uint32_t next = texture_map_at(S, P.a, px, py, pz, c);
+        const uint32_t next = texture_map_at(S, P.a, px, py, pz, c RTC_MESHUV_ARG);
         if (next == RTC_NO_LEAF) {
           out = c;
           return true;
@@ -2143,8 +2176,8 @@ __device__ __forceinline__ bool pattern_chain(const DevScene& S, const DevPatter
 // rtc_scene_create sends a scene with nested mixing patterns there and refuses more than RTC_PATTERN_STACK levels.
 template <bool EXT>
 __device__ __forceinline__ bool pattern_chain(const DevScene& S, const DevPattern* __restrict__ pat, uint32_t& idx,
-                                              double& ox, double& oy, double& oz, Rgb& out);
-__device__ __noinline__ Rgb pattern_tree(const DevScene& S, const DevPattern* pat, uint32_t idx, double ox, double oy, double oz) {
+                                              double& ox, double& oy, double& oz, Rgb& out RTC_MESHUV_PARAM);
+__device__ __noinline__ Rgb pattern_tree(const DevScene& S, const DevPattern* pat, uint32_t idx, double ox, double oy, double oz RTC_MESHUV_PARAM) {
   struct Frame {
     double w, x, y, z;
     uint32_t idx;
@@ -2155,7 +2188,7 @@ __device__ __noinline__ Rgb pattern_tree(const DevScene& S, const DevPattern* pa
   double w = 1.0;
   for (int guard = 0; guard < 4096; ++guard) {
     Rgb c;
-    if (pattern_chain<true>(S, pat, idx, ox, oy, oz, c)) {  // a select-chain that ends in a colour
+    if (pattern_chain<true>(S, pat, idx, ox, oy, oz, c RTC_MESHUV_ARG)) {  // a select-chain that ends in a colour
       acc.r += w * c.r;
       acc.g += w * c.g;
       acc.b += w * c.b;
@@ -2198,9 +2231,9 @@ __device__ __noinline__ Rgb pattern_tree(const DevScene& S, const DevPattern* pa
 // evaluated here; a mixing pattern below a mixing pattern goes to pattern_tree (the *_ext kernels).
 template <bool EXT>
 __device__ __forceinline__ Rgb pattern_at(const DevScene& S, const DevPattern* __restrict__ pat, uint32_t idx, double ox,
-                                          double oy, double oz) {
+                                          double oy, double oz RTC_MESHUV_PARAM) {
   Rgb out;
-  if (pattern_chain<EXT>(S, pat, idx, ox, oy, oz, out)) return out;
+  if (pattern_chain<EXT>(S, pat, idx, ox, oy, oz, out RTC_MESHUV_ARG)) return out;
   const DevPattern& P = pat[idx];
   const uint32_t kind = P.kind;
   const double* __restrict__ m = P.inv;
@@ -2210,10 +2243,10 @@ __device__ __forceinline__ Rgb pattern_at(const DevScene& S, const DevPattern* _
   Rgb ca{0, 0, 0}, cb{0, 0, 0};
   {  // both children start from the mixing pattern's own object point (a perturb below moves its copy only)
     double ax = ox, ay = oy, az = oz, bx = ox, by = oy, bz = oz;
-    const bool a_ends = pattern_chain<EXT>(S, pat, ia, ax, ay, az, ca);
-    const bool b_ends = pattern_chain<EXT>(S, pat, ib, bx, by, bz, cb);
+    const bool a_ends = pattern_chain<EXT>(S, pat, ia, ax, ay, az, ca RTC_MESHUV_ARG);
+    const bool b_ends = pattern_chain<EXT>(S, pat, ib, bx, by, bz, cb RTC_MESHUV_ARG);
     if constexpr (EXT) {
-      if (!(a_ends && b_ends)) return pattern_tree(S, pat, idx, ox, oy, oz);  // nested mixing patterns
+      if (!(a_ends && b_ends)) return pattern_tree(S, pat, idx, ox, oy, oz RTC_MESHUV_ARG);  // nested mixing patterns
     }
   }
   if (kind == 6) {  // blend.zig:21-24
@@ -2490,14 +2523,18 @@ __device__ __forceinline__ Ray camera_sample(const DevCamera& cam, const DevSamp
 // (TORUS: leaf kind 7, a quartic - leaf_entries' and the normal's case 7 and the solver, torus_quartic; with BUMP, SPOT,
 // MOTION, MS and AREA, compiled into the torus kernels' translation unit only, under RTC_TORUS_TU: the device functions
 // that are not templates - csg_collect - see the kind through the unit, not through a parameter)
+// (MESHUV: texture maps of mapping RTC_TEX_MESH - DevMeshUvs, the meshuv kernels' extra argument; the hit's triangle and
+// barycentrics reach the pattern evaluation, texture_map_at's mapping-4 branch reads the triangle's texture row.  With TORUS
+// and everything below it, compiled into the meshuv kernels' translation unit only, under RTC_MESHUV_TU, which implies
+// RTC_TORUS_TU: one family renders a world that holds tori and textured meshes)
 template <bool LDS, bool CSG, int WORLD = 0, int WAVES = 2, bool COOP = false, bool BOX = true, bool AREA = false, bool MS = false,
-          bool MOTION = false, bool SPOT = false, bool BUMP = false, bool TORUS = false>
+          bool MOTION = false, bool SPOT = false, bool BUMP = false, bool TORUS = false, bool MESHUV = false>
 __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& cam, const DevPixelMap& map,
                                             const uint32_t max_depth, double* __restrict__ out,
                                             DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
                                             const DevAreaLights& area = DevAreaLights{}, const DevSampling& smp = DevSampling{},
                                             const DevMotion& mo = DevMotion{}, const DevSpots& spots = DevSpots{},
-                                            const DevBumps& bumps = DevBumps{}) {
+                                            const DevBumps& bumps = DevBumps{}, const DevMeshUvs& muv = DevMeshUvs{}) {
   static_assert(!AREA || !COOP, "the area kernels run no cooperative iterations");
   static_assert(!MS || !COOP, "the sampling kernels run no cooperative iterations");
   static_assert(!MOTION || (MS && AREA && WORLD == 0), "the motion kernels are the general area-sampling walk");
@@ -2508,6 +2545,13 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
   static_assert(TORUS, "the torus translation unit compiles the torus kernels only: leaf kind 7 is compiled into every walk of it");
 #else
   static_assert(!TORUS, "leaf kind 7 is compiled in the torus translation unit (rtc_torus.hip) only");
+#endif
+  static_assert(!MESHUV || TORUS, "the meshuv kernels are the torus walk");
+#ifdef RTC_MESHUV_TU
+  static_assert(MESHUV, "the meshuv translation unit compiles the meshuv kernels only: its pattern functions take the hit");
+#else
+  static_assert(!MESHUV, "mapping RTC_TEX_MESH is compiled in the meshuv translation unit (rtc_meshuv.hip) only");
+  (void)muv;
 #endif
   RTC_PRIO_PHASE(RTC_PRIO_WORK);
 #ifndef RTC_PROFILE
@@ -3334,7 +3378,11 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
         const double opx = row_pt(M + 0, qx, qy, qz);
         const double opy = row_pt(M + 4, qx, qy, qz);
         const double opz = row_pt(M + 8, qx, qy, qz);
-        color = pattern_at<CSG>(S, pats, RTC_CHECK_INDEX(RTC_OOB_PATTERNS, mat.pattern, RTC_AVAIL(4)), opx, opy, opz);
+#ifdef RTC_MESHUV_TU
+        // (MESHUV) the hit's triangle - geom is its tri_* index - and the entry's barycentrics, as Moller-Trumbore left them
+        const MeshUvHit mh{muv.row, ((kind == 4u || kind == 5u) && muv.row != nullptr) ? geom : RTC_NO_LEAF, hv.u, hv.v};
+#endif
+        color = pattern_at<CSG>(S, pats, RTC_CHECK_INDEX(RTC_OOB_PATTERNS, mat.pattern, RTC_AVAIL(4)), opx, opy, opz RTC_MESHUV_ARG);
       }
       RTC_STAMP(12);
       // With diffuse == 0 and specular == 0 lighting() returns `ambient` whether or not the
@@ -3780,7 +3828,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
 // The kernels.  rtc_motion.hip includes this file with RTC_MOTION_TU defined and gets the motion kernels alone: a
 // translation unit of their own, so that this one compiles in the time and to the code it did; rtc_spot.hip likewise
 // with RTC_SPOT_TU and the spot kernels, rtc_bump.hip with RTC_BUMP_TU and the bump kernels, rtc_torus.hip with RTC_TORUS_TU
-// and the torus kernels.  rtc_kernels_ext.hip
+// and the torus kernels, rtc_meshuv.hip with RTC_MESHUV_TU (and, with it, RTC_TORUS_TU) and the meshuv kernels.  rtc_kernels_ext.hip
 // includes it with RTC_EXT_TU defined: in the -DRTC_PROFILE diagnostic build, whose instrumented walk makes this unit's
 // compile about a third longer, it gets the csg / texture-map, flat and area-light kernels (rtc_render_kernel_ext to
 // rtc_render_kernel_area_bigworld below), so that neither unit takes the time of all of them.  The product build keeps
@@ -4653,6 +4701,29 @@ rtc_render_kernel_bump_bigworld(const DevScene S, const DevCamera cam, const Dev
                                                                             spots, bumps);
 }
 
+#elif defined(RTC_MESHUV_TU)
+
+// UV-mapped mesh textures (RTC_TEX_MESH): the torus walk with the hit's triangle and barycentrics
+// handed to the pattern evaluation and the texture rows (DevMeshUvs) as one more argument; one pair for every world, tori
+// included.  Every other kernel is compiled without it.
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_meshuv(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                         double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                         const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots, const DevBumps bumps,
+                         const DevMeshUvs muv) {
+  render_body<true, true, 0, 2, false, true, true, true, true, true, true, true, true>(S, cam, map, max_depth, out, stats, next_stats, area,
+                                                                                       smp, mo, spots, bumps, muv);
+}
+
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_meshuv_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                  double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                  const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                  const DevBumps bumps, const DevMeshUvs muv) {
+  render_body<false, true, 0, 2, false, true, true, true, true, true, true, true, true>(S, cam, map, max_depth, out, stats, next_stats,
+                                                                                        area, smp, mo, spots, bumps, muv);
+}
+
 #elif defined(RTC_TORUS_TU)
 
 // Torus primitives (RTC_TORUS): the bump walk with leaf kind 7 compiled in, one pair for every
@@ -4675,4 +4746,4 @@ rtc_render_kernel_torus_bigworld(const DevScene S, const DevCamera cam, const De
                                                                                   smp, mo, spots, bumps);
 }
 
-#endif  // RTC_MOTION_TU / RTC_SPOT_TU / RTC_BUMP_TU / RTC_TORUS_TU
+#endif  // RTC_MOTION_TU / RTC_SPOT_TU / RTC_BUMP_TU / RTC_MESHUV_TU / RTC_TORUS_TU

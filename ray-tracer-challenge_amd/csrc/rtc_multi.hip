@@ -533,6 +533,10 @@ const char* rtc_multi_last_error(void) { return g_multi_error.c_str(); }
 int rtc_multi_create(const rtc_scene_desc* desc, uint32_t n_gpus, uint32_t flags, rtc_multi** out) {
   g_multi_error.clear();
   if (!desc || !out || n_gpus == 0) return mfail(RTC_ERR_INVALID_ARGUMENT, "null argument or no GPUs");
+  // (a texture map of mapping RTC_TEX_MESH: the meshuv kernels and rtc_scene_set_mesh_uvs are librtc_hip's single-GPU ones)
+  for (uint32_t i = 0; i < desc->n_texmaps && desc->tex_mapping; ++i)
+    if (desc->tex_mapping[i] == RTC_TEX_MESH)
+      return mfail(RTC_ERR_UNSUPPORTED, "texture map %u has mapping RTC_TEX_MESH: librtc_multi does not render mesh maps, use rtc_scene_create", i);
   // (a torus, RTC_TORUS: its kernels are librtc_hip's single-GPU ones; a split frame would have to render without the shape)
   for (uint32_t i = 0; i < desc->n_leaves && desc->leaf_kind; ++i)
     if (desc->leaf_kind[i] == RTC_TORUS)

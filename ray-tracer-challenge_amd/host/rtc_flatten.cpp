@@ -57,12 +57,22 @@ struct Flattener {
     return id;
   }
 
+  // (a mesh map - RTC_TEX_MESH, DESIGN.md section 19 - belongs to a material that from-obj copies into every triangle: the
+  // copies share one TextureMap, which is one table entry, so that a mesh is one material row and not one per triangle.
+  // Every other mapping is its own entry per pattern, as before.)
+  std::map<const TextureMap*, uint32_t> mesh_map_ids;
+
   uint32_t internTextureMap(const TextureMap& tm) {
+    if (tm.mapping == TexMapping::Mesh) {
+      auto it = mesh_map_ids.find(&tm);
+      if (it != mesh_map_ids.end()) return it->second;
+    }
     uint32_t uv[6];
     for (size_t f = 0; f < 6; ++f) uv[f] = f < tm.faces.size() ? internUv(tm.faces[f]) : uv[0];
     const uint32_t id = static_cast<uint32_t>(out.tex_mapping.size());
     out.tex_mapping.push_back(static_cast<uint8_t>(tm.mapping));
     out.tex_uv.insert(out.tex_uv.end(), uv, uv + 6);
+    if (tm.mapping == TexMapping::Mesh) mesh_map_ids.emplace(&tm, id);
     return id;
   }
 
@@ -162,6 +172,7 @@ struct Flattener {
         push3(out.tri_n1, smooth ? s.n1 : s.normal);
         push3(out.tri_n2, smooth ? s.n2 : Tuple{});
         push3(out.tri_n3, smooth ? s.n3 : Tuple{});
+        out.tri_uv.insert(out.tri_uv.end(), s.tex_uv, s.tex_uv + 6);
         break;
       }
       default: break;

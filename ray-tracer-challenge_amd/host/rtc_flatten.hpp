@@ -23,6 +23,7 @@ struct FlatScene {
   std::vector<double> cyl_min, cyl_max;
   std::vector<uint8_t> cyl_closed;
   std::vector<double> tri_p1, tri_e1, tri_e2, tri_n1, tri_n2, tri_n3;
+  std::vector<double> tri_uv;  // [n_tris][6]: each triangle's texture row (rtch_scene_mesh_uvs; not part of rtc_scene_desc)
   std::vector<double> mat_params;
   std::vector<uint32_t> mat_pattern;
   std::vector<Bump> mat_bump;  // [n_materials]: each row's "normal-perturbation" (rtch_scene_bumps; not part of rtc_scene_desc)

@@ -134,6 +134,17 @@ int rtch_scene_bumps(void* h, uint8_t* kind, double* amplitude, uint32_t* octave
   });
 }
 
+// The triangles' texture rows (RTC_TEX_MESH), in tri_* order, as rtc_scene_set_mesh_uvs takes them.
+int rtch_scene_mesh_uvs(void* h, double* uv, uint32_t n) {
+  return guarded([&] {
+    const HostScene* hs = static_cast<HostScene*>(h);
+    if (n != hs->desc.n_tris)
+      throw rtc::Error("InvalidArgument", "mesh uvs: n " + std::to_string(n) + ", the scene has " + std::to_string(hs->desc.n_tris) + " triangles");
+    if (n != 0u && !uv) throw rtc::Error("InvalidArgument", "mesh uvs: null argument");
+    for (size_t i = 0; i < 6ull * n; ++i) uv[i] = hs->flat.tri_uv[i];
+  });
+}
+
 // Camera of the scene file; width/height 0 keep the file's values, otherwise they replace
 // camera.width/height before Camera.new runs (the reference has no such override).
 int rtch_scene_camera(void* h, uint32_t width, uint32_t height, rtc_camera* out) {
@@ -229,6 +240,13 @@ int rtch_scene_render(void* h, uint32_t width, uint32_t height, uint32_t max_dep
         if (rtch_scene_bumps(h, kind.data(), amp.data(), oct.data(), per.data(), inv.data(), nm) != 0) throw rtc::Error("InvalidArgument", g_error);
         const rtc_bump bp{nm, kind.data(), amp.data(), oct.data(), per.data(), inv.data()};
         st = rtc_scene_set_bumps(scene, &bp);
+      }
+      if (st == RTC_OK && hs->desc.n_tris != 0u) {  // (the triangles' texture rows; all zero: the handle as it is)
+        const std::vector<double>& rows = hs->flat.tri_uv;
+        bool any = false;
+        for (const double x : rows) any = any || x != 0.0;
+        const rtc_mesh_uvs mu{hs->desc.n_tris, rows.data()};
+        if (any) st = rtc_scene_set_mesh_uvs(scene, &mu);
       }
       const rtc::CameraSampling& cs = hs->info.sampling;
       if (cs.adaptive && st == RTC_OK) {  // (adaptive sampling: each tile's mean after its own passes, section 15)

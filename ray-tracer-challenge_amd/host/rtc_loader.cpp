@@ -298,6 +298,10 @@ UvPattern parseUvPattern(const Value& cfg, const FileLoader& load_file_data) {
       }
     }
     uv.image = std::make_shared<const UvImageData>(decodePng(load_file_data(file)));
+  } else if (t == "test") {  // UvTestPattern (texture_map.zig:13-17): colour = (u, v, 0); the reference's scene files cannot name it
+    requireObject(kv.second, "test");
+    checkFields(kv.second, {}, "test");
+    uv.kind = UvKind::Test;
   } else {
     throw Error("UnknownField", "uv-pattern." + t);
   }
@@ -349,6 +353,8 @@ Pattern parsePattern(const Value& cfg, const FileLoader& load_file_data) {
       single(TexMapping::Planar);
     } else if (mk.first == "cylindrical") {
       single(TexMapping::Cylindrical);
+    } else if (mk.first == "mesh") {  // (not in the reference): (u, v) from the hit triangle's texture row
+      single(TexMapping::Mesh);
     } else if (mk.first == "cubic") {
       requireObject(mk.second, "cubic");
       checkFields(mk.second, {"front", "back", "left", "right", "up", "down"}, "cubic");
@@ -526,12 +532,13 @@ Shape parseObject(const Value& object, const InheritedState& inherited, const De
     shape = std::move(parent);
   } else if (t == "from-obj") {
     const Value& cfg = requireObject(payload, "from-obj");
-    checkFields(cfg, {"file", "normalize"}, "from-obj");
+    checkFields(cfg, {"file", "normalize", "texture-coordinates"}, "from-obj");
     const std::string& file = asString(requireField(cfg, "file", "from-obj"), "file");
     bool normalize = true;  // scene.zig:124-127
     if (auto* v = cfg.find("normalize")) normalize = asBool(*v, "normalize");
     const std::string obj = load_file_data(file);
     ObjParser parser;
+    if (auto* v = cfg.find("texture-coordinates")) parser.texture_coordinates = asBool(*v, "texture-coordinates");  // 
     ObjParser::InheritedState st;
     st.material = material;
     st.casts_shadow = casts_shadow;
@@ -565,13 +572,27 @@ Shape parseObject(const Value& object, const InheritedState& inherited, const De
     shape = Shape::torus(major, minor);
   } else if (t == "triangle") {
     const Value& cfg = requireObject(payload, "triangle");
-    checkFields(cfg, {"p1", "p2", "p3"}, "triangle");
+    checkFields(cfg, {"p1", "p2", "p3", "uv1", "uv2", "uv3"}, "triangle");
     double a[3], b[3], c[3];
     asVec3(requireField(cfg, "p1", "triangle"), "p1", a);
     asVec3(requireField(cfg, "p2", "triangle"), "p2", b);
     asVec3(requireField(cfg, "p3", "triangle"), "p3", c);
     shape = Shape::triangle(Tuple::point(a[0], a[1], a[2]), Tuple::point(b[0], b[1], b[2]),
                             Tuple::point(c[0], c[1], c[2]));
+    // (not in the reference) "uv1", "uv2", "uv3": [u, v] of p1, p2, p3 - together or not at all
+    const char* const uv_keys[3] = {"uv1", "uv2", "uv3"};
+    const bool any_uv = cfg.find("uv1") || cfg.find("uv2") || cfg.find("uv3");
+    for (int k = 0; k < 3 && any_uv; ++k) {
+      const Value* v = cfg.find(uv_keys[k]);
+      if (!v) throw Error("MissingField", std::string("triangle.") + uv_keys[k] + ": uv1, uv2 and uv3 go together");
+      if (v->type != Value::Array || v->arr.size() != 2)
+        throw Error("InvalidData", std::string("triangle.") + uv_keys[k] + ": expected [u, v]");
+      for (int j = 0; j < 2; ++j) {
+        const double x = asFloat(v->arr[j], (std::string("triangle.") + uv_keys[k]).c_str());
+        if (!std::isfinite(x)) throw Error("InvalidData", std::string("triangle.") + uv_keys[k] + ": not finite");
+        shape.tex_uv[2 * k + j] = x;
+      }
+    }
   } else if (t == "group") {
     requireArray(payload, "group");
     shape = Shape::group();
@@ -926,10 +947,11 @@ size_t parseUsizeToken(Token tok) {  // std.fmt.parseInt(usize, tok, 10)
 struct FaceVertex {
   size_t vertex_index;
   std::optional<size_t> normal_index;
+  std::optional<size_t> texture_index;  // (only with "texture-coordinates")
 };
 
-// obj.zig:85-99 — "v", "v/t", "v/t/n", "v//n"
-FaceVertex handleFaceHelper(Token token) {
+// obj.zig:85-99 — "v", "v/t", "v/t/n", "v//n".  `with_texture`: the t field too, where it is there and not empty.
+FaceVertex handleFaceHelper(Token token, bool with_texture) {
   // std.mem.splitScalar keeps empty fields: field 0 is the vertex, field 2 (if there is one) the normal.
   Token parts[3];
   size_t n_parts = 0, start = 0;
@@ -943,6 +965,7 @@ FaceVertex handleFaceHelper(Token token) {
   }
   FaceVertex fv;
   fv.vertex_index = parseUsizeToken(parts[0]);
+  if (with_texture && n_parts >= 2 && !parts[1].empty()) fv.texture_index = parseUsizeToken(parts[1]);
   if (n_parts < 3) return fv;  // no texture field, or no normal field
   fv.normal_index = parseUsizeToken(parts[2]);
   return fv;
@@ -972,9 +995,14 @@ void ObjParser::handleLine(std::string_view line, const InheritedState& state) {
     const double y = parseFloatToken(tok(2, "IncompleteVertex"));
     const double z = parseFloatToken(tok(3, "IncompleteVertex"));
     normals.push_back(Tuple::vec3(x, y, z));
+  } else if (first == "vt" && texture_coordinates) {  // vt u v [w]: w is not read
+    const double u = parseFloatToken(tok(1, "IncompleteVertex"));
+    const double v = parseFloatToken(tok(2, "IncompleteVertex"));
+    if (!std::isfinite(u) || !std::isfinite(v)) throw LineError{"NonFiniteVertex"};  // (rtc_scene_set_mesh_uvs takes finite rows only)
+    texcoords.emplace_back(u, v);
   } else if (first == "f") {  // obj.zig:101-150 — fan triangulation
-    const FaceVertex firstv = handleFaceHelper(tok(1, "IncompleteFace"));
-    FaceVertex last = handleFaceHelper(tok(2, "IncompleteFace"));
+    const FaceVertex firstv = handleFaceHelper(tok(1, "IncompleteFace"), texture_coordinates);
+    FaceVertex last = handleFaceHelper(tok(2, "IncompleteFace"), texture_coordinates);
     if (tokens.size() < 4) throw LineError{"IncompleteFace"};
     auto vertexAt = [&](size_t idx) -> const Tuple& {
       if (idx == 0 || idx > vertices.size()) throw Error("IndexOutOfBounds", "face vertex " + std::to_string(idx));
@@ -984,8 +1012,16 @@ void ObjParser::handleLine(std::string_view line, const InheritedState& state) {
       if (idx == 0 || idx > normals.size()) throw Error("IndexOutOfBounds", "face normal " + std::to_string(idx));
       return normals[idx - 1];
     };
+    auto texAt = [&](const FaceVertex& fv, double* out) {  // a vertex without a t field: (0, 0)
+      out[0] = out[1] = 0.0;
+      if (!fv.texture_index) return;
+      const size_t idx = *fv.texture_index;
+      if (idx == 0 || idx > texcoords.size()) throw Error("IndexOutOfBounds", "face texture " + std::to_string(idx));
+      out[0] = texcoords[idx - 1].first;  // 1-indexed
+      out[1] = texcoords[idx - 1].second;
+    };
     for (size_t i = 3; i < tokens.size(); ++i) {
-      const FaceVertex current = handleFaceHelper(tokens[i]);
+      const FaceVertex current = handleFaceHelper(tokens[i], texture_coordinates);
       const Tuple& p1 = vertexAt(firstv.vertex_index);
       const Tuple& p2 = vertexAt(last.vertex_index);
       const Tuple& p3 = vertexAt(current.vertex_index);
@@ -993,6 +1029,11 @@ void ObjParser::handleLine(std::string_view line, const InheritedState& state) {
                       ? Shape::smoothTriangle(p1, p2, p3, normalAt(*firstv.normal_index), normalAt(*last.normal_index),
                                               normalAt(*current.normal_index))
                       : Shape::triangle(p1, p2, p3);
+      if (texture_coordinates) {  // the fan's firstv, last, current
+        texAt(firstv, tri.tex_uv + 0);
+        texAt(last, tri.tex_uv + 2);
+        texAt(current, tri.tex_uv + 4);
+      }
       tri.material = state.material ? *state.material : Material{};  // copied into EVERY triangle
       tri.casts_shadow = state.casts_shadow ? *state.casts_shadow : true;
       activeGroup().addChild(std::move(tri));
@@ -1052,8 +1093,9 @@ void ObjParser::loadObj(const std::string& obj, const InheritedState& state, boo
   for (const Token line : lines) {
     try {
       handleLine(line, state);
-    } catch (const LineError&) {
+    } catch (const LineError& e) {
       lines_ignored += 1;  // obj.zig:277
+      ignored_by_error[e.name] += 1;
     }
   }
 }

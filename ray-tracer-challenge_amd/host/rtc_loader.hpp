@@ -78,7 +78,16 @@ class ObjParser {
   double scale = 1.0;
   std::vector<Tuple> vertices;
   std::vector<Tuple> normals;
+  // "texture-coordinates" of from-obj (not in the reference).  false: `vt` lines are ignored lines
+  // and a face vertex's t field is never read, as in obj.zig.  true: `vt u v [w]` lines fill `texcoords`, and a face
+  // vertex's t field, 1-indexed into them, gives its triangles' texture rows ((0, 0) for a vertex without one).
+  bool texture_coordinates = false;
+  std::vector<std::pair<double, double>> texcoords;
   size_t lines_ignored = 0;
+  // the same count by the name of the line error that made the line an ignored one ("UnknownFirstToken",
+  // "IncompleteVertex", "InvalidCharacter", ...): what a refusal by name of one line is, where a line error never leaves
+  // the parser (obj.zig:277)
+  std::map<std::string, size_t> ignored_by_error;
 
  private:
   long active_group_ = -1;  // -1: default group, else index into default_group.children

@@ -34,7 +34,8 @@ struct UvImageData {  // Canvas(T) made by Canvas.fromImage (canvas.zig:34-46): 
   std::vector<float> rgb;  // [height][width][3]
 };
 enum class UvKind : uint8_t { AlignCheck = 0, Checkers = 1, Image = 2, Test = 3 };        // == RTC_UV_*
-enum class TexMapping : uint8_t { Spherical = 0, Planar = 1, Cylindrical = 2, Cubic = 3 };  // == RTC_TEX_*
+enum class TexMapping : uint8_t { Spherical = 0, Planar = 1, Cylindrical = 2, Cubic = 3,
+                                  Mesh = 4 };  // == RTC_TEX_* (Mesh: not in the reference)
 struct UvPattern {  // texture_map.zig:107-171
   UvKind kind = UvKind::Test;
   double width = 0.0, height = 0.0;                 // UvCheckers
@@ -216,6 +217,9 @@ struct Shape {
   bool closed = false;
   // triangle / smooth triangle (triangle.zig:21-26, 214-221)
   Tuple p1, p2, p3, e1, e2, normal, n1, n2, n3;
+  // a triangle's texture row (not in the reference; RTC_TEX_MESH): the (u, v) of p1, p2, p3, as
+  // rtc_scene_set_mesh_uvs takes them.  Copied with the triangle - divide, definitions -; six zeros without coordinates.
+  double tex_uv[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   // group (group.zig:21-23); a csg keeps {left, right} here (csg.zig:28-31)
   std::vector<Shape> children;
   BoundingBox bbox;

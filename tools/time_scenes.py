@@ -38,6 +38,11 @@ with "normal-perturbation" entries those are applied first; --bump off applies n
 bump kernels without a bump.
 --torus: the torus kernels on a scene without a torus, as option torus_kernels=1; a scene with a
 torus runs them anyway.
+--meshuv: the meshuv kernels on a scene without a mesh map, as option meshuv_kernels=1; a scene
+with a mesh map runs them anyway, with its triangles' texture rows (HostScene.mesh_uvs()) applied.
+--mesh-as-planar: every mesh map of the description (RTC_TEX_MESH) becomes a planar map in a copy of it - the same table
+entries, one per mesh, so the handle keeps its tables and its kernel form; with --meshuv the same kernels run: what the
+mapping-4 branch costs against the planar one on the same scene.
 --adaptive threshold[,min,tile]: adaptive sampling at up to --max-passes (64) passes, min passes 4 and
 16 x 16 tiles by default, with the --sampling of the frames: prints the rounds and tile-passes of a run against
 T * max_passes, its time (a second run, end to end on the host) against uniform progressive passes (render_device +
@@ -78,6 +83,8 @@ ap.add_argument("--motion", action="append", default=[])
 ap.add_argument("--spot", action="append", default=[])
 ap.add_argument("--bump", action="append", default=[])
 ap.add_argument("--torus", action="store_true")
+ap.add_argument("--meshuv", action="store_true")
+ap.add_argument("--mesh-as-planar", action="store_true")
 ap.add_argument("--adaptive", default="")
 ap.add_argument("--max-passes", type=int, default=64)
 args = ap.parse_args()
@@ -95,6 +102,8 @@ for opt in args.option:
     rtc.set_option(n, float(v))
 if args.torus:  # (the torus kernels on a scene without a torus: what carrying the flag costs)
     rtc.set_option("torus_kernels", 1.0)
+if args.meshuv:  # (the meshuv kernels on a scene without a mesh map: what carrying the flag costs)
+    rtc.set_option("meshuv_kernels", 1.0)
 
 
 def light_table(hs, how):
@@ -237,11 +246,20 @@ for name, w, h, depth in cases:
     # (a scene given by its path may name files beside it)
     hs = (rtc.HostScene.from_file(name + ".json", os.path.dirname(name)) if os.path.exists(name + ".json")
           else rtc.HostScene.from_file(name + ".json")); cam = hs.camera(w, h)
+    desc, keep = hs.desc, None
+    if args.mesh_as_planar:
+        import ctypes, numpy as np
+        keep = np.array([hs.desc.tex_mapping[i] for i in range(hs.desc.n_texmaps)], dtype=np.uint8)
+        keep[keep == rtc.RTC_TEX_MESH] = rtc.RTC_TEX_PLANAR
+        desc = type(hs.desc)()  # (a copy of the struct, field by field: every other table is shared)
+        for field, _ in hs.desc._fields_:
+            setattr(desc, field, getattr(hs.desc, field))
+        desc.tex_mapping = keep.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
     canvas = torch.empty((h, w, 3), dtype=torch.float64, device="cuda")
     ts, kernel, delta, acc = [], "", None, []
     table = light_table(hs, args.lights)
     for rep in range(args.handles):
-        gpu = rtc.GpuScene(hs.desc, lights=table)
+        gpu = rtc.GpuScene(desc, lights=table)
         if args.sampling:
             sv = [float(v) for v in args.sampling.split(",")]
             gpu.set_sampling(int(sv[0]), True, sv[1] if len(sv) > 1 else 0.0, sv[2] if len(sv) > 2 else 1.0)
@@ -279,6 +297,8 @@ for name, w, h, depth in cases:
                 bumps["inverse"][i] = [1.0 / scale, 0, 0, 0, 0, 1.0 / scale, 0, 0, 0, 0, 1.0 / scale, 0]
             if "off" not in args.bump:
                 gpu.set_bumps(bumps)
+        if hs.mesh_uvs() is not None:  # (the triangles' texture rows: what a mesh map reads)
+            gpu.set_mesh_uvs(hs.mesh_uvs())
         for i in range(args.settle):
             gpu.render_device(cam, canvas.data_ptr(), depth, None, stream.cuda_stream)
         torch.cuda.synchronize()
@@ -303,7 +323,7 @@ for name, w, h, depth in cases:
     if delta is not None: line += f" maxdelta {delta:.2e}"
     if args.lights or args.spot or "spot_kernels=1" in args.option:
         line += f" shadow_traced {st['shadow_traced']} ns/shadow-ray {min(ts) * 1e6 / max(1, st['shadow_traced']):.3f}"
-    if args.sampling or args.option or args.passes >= 0 or args.motion or args.spot or args.bump or args.torus:
+    if args.sampling or args.option or args.passes >= 0 or args.motion or args.spot or args.bump or args.torus or args.meshuv:
         line += f" primary {st['primary']} ns/primary-ray {min(ts) * 1e6 / max(1, st['primary']):.3f}"
     if acc:
         ms, copy_ms, nbytes = min(a[0] for a in acc), min(a[1] for a in acc), acc[0][2]
