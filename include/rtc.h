@@ -521,6 +521,55 @@ typedef struct rtc_mesh_uvs {
  */
 int rtc_scene_set_mesh_uvs(rtc_scene *scene, const rtc_mesh_uvs *uvs);
 
+/* ---- glossy reflection and refraction: rough materials scatter their rays ---- */
+/*
+ * A material row has two roughness values, `reflection` and `transmission`, each finite and in [0, 1]; 0 is today's
+ * perfectly sharp mirror or glass.
+ *
+ * Path code.  Every ray of a pixel's ray tree has one: the primary ray 1, the reflected child of a ray with code c 2 c,
+ * the refracted child 2 c + 1 (max_depth <= RTC_MAX_DEPTH = 16: a code is below 2^17).
+ *
+ * Direction.  At a hit whose material has reflection > 0 the reflected direction d is formed exactly as without gloss,
+ * from the shading normal, and then replaced:
+ *   s  = the first of 32 draws (a, b, c), each component 2.0 * J(3 t + i) - 1.0 with t = 0 .. 31 and i = 0, 1, 2,
+ *        for which ((a * a) + (b * b)) + (c * c) <= 1.0; if none passes, s = (0, 0, 0) (the lens sampler's rule)
+ *   e  = d + s * roughness                                   (per component)
+ *   m  = sqrt((e.x * e.x + e.y * e.y) + e.z * e.z)
+ *   d' = e / m when m != 0, else d                           (tuple.zig's normalize)
+ *   the child's direction is d' when dot(d', ng) > 0.0, otherwise d
+ * ng is the geometric normal after its `inside` flip; dot is (x + y) + z.  d' is a unit vector, as the next hit's eyev must
+ * be for Material.lighting.  For transmission > 0 the same steps are applied to the refracted direction, with the child's
+ * code 2 c + 1, and d' is used when dot(d', ng) < 0.0.  Weights, n1 / n2, schlick, over_point, under_point and the counts
+ * of secondary rays are untouched.  Only + - * / sqrt and comparisons are added, each correctly rounded, in the order written.
+ *
+ * Draws.  With GOLD = 0x9E3779B97F4A7C15 and rtc_mix64 splitmix64's finaliser (the camera hash's),
+ *   J(axis) = (rtc_mix64(h + GOLD * (((code << 8) | axis) + 1)) >> 11) * 2^-53
+ *   h       = rtc_mix64(key + GOLD * (((p << 32) | (g << 8)) + 1))
+ *   key     = rtc_mix64(seed ^ 0x13198A2E03707344)
+ * p is the whole-image pixel (y * hsize + x), g the global sample index sample_base + k of rtc_scene_set_sample_pass,
+ * code the child's path code.  A ray's draws do not depend on bands, tiles, clones, the lane that traced it or the order;
+ * they are new for every camera sample and every pass, so progressive and adaptive rendering converge a rough surface.
+ * Like the lens, gloss is always sampled: a 1 x 1 grid without jitter at pass 0 still scatters.
+ *
+ * A row whose two values are 0 takes the unscattered branch and draws nothing: its pixels have the bits they have without
+ * a table.
+ */
+typedef struct rtc_gloss {
+  uint32_t n_materials;       /* the handle's material count (rtc_scene_desc::n_materials) */
+  const double *reflection;   /* [n_materials], each finite and in [0, 1]; NULL: all zeros */
+  const double *transmission; /* [n_materials], each finite and in [0, 1]; NULL: all zeros */
+  uint64_t seed;              /* of the draws (above) */
+} rtc_gloss;
+
+/*
+ * This handle's roughness rows for every render entry point.  Validated before anything changes: RTC_ERR_INVALID_ARGUMENT
+ * for an n_materials other than the handle's, or a value that is not finite or outside [0, 1]; the previous table stays in
+ * force.  NULL, or a table whose every row is zero, gives the handle its previous kernels back.  A clone starts with its
+ * source's table; rtc_render's band clones follow.  A handle with a rough row renders with the gloss kernels
+ * (rtc_render_kernel_gloss, _gloss_bigworld).  librtc_multi renders without gloss.
+ */
+int rtc_scene_set_gloss(rtc_scene *scene, const rtc_gloss *gloss);
+
 /* ---- adaptive sampling: progressive passes only for tiles still noisy ---- */
 #define RTC_ADAPTIVE_MAX_TILE 1024u
 

@@ -21,7 +21,8 @@
  *                        sampling, rtch_scene_adaptive, through rtc_render_adaptive; its spot lights,
  *                        rtch_scene_spots, through rtc_scene_set_spots; its materials' normal perturbation,
  *                        rtch_scene_bumps, through rtc_scene_set_bumps; its triangles' texture rows,
- *                        rtch_scene_mesh_uvs, through rtc_scene_set_mesh_uvs)
+ *                        rtch_scene_mesh_uvs, through rtc_scene_set_mesh_uvs; its materials' roughness,
+ *                        rtch_scene_gloss, through rtc_scene_set_gloss)
  *
  * Every function that returns int returns 0 on success; otherwise rtch_last_error()
  * holds "<ZigStyleErrorName>: detail" (thread-local).
@@ -83,6 +84,12 @@ int rtch_scene_bumps(void *handle, uint8_t *kind, double *amplitude, uint32_t *o
  * the faces' t fields) or a "triangle" with "uv1", "uv2", "uv3"; six zeros for every other triangle; n must be the
  * description's n_tris.  Pass them to rtc_scene_set_mesh_uvs.  rtch_scene_render applies them. */
 int rtch_scene_mesh_uvs(void *handle, double *out, uint32_t n);
+/* The materials' "roughness" (glossy reflection and refraction), in mat_* order: a number (both
+ * values) or {"reflection": a, "transmission": b}, each in [0, 1]; and *seed, the camera's "sampling": {"gloss-seed": n}
+ * (0 without).  n must be the description's n_materials.  A material with the key is a mat_* row of its own only when a
+ * value is non-zero.  *present: 1 when a material of the file has the key.  Pass them to rtc_scene_set_gloss.
+ * rtch_scene_render applies them. */
+int rtch_scene_gloss(void *handle, double *reflection, double *transmission, uint64_t *seed, int *present, uint32_t n);
 int rtch_scene_camera(void *handle, uint32_t width, uint32_t height, rtc_camera *out);
 int rtch_camera_rotate(void *handle, double angle);
 int rtch_camera_move(void *handle, double distance);

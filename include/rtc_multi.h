@@ -43,7 +43,8 @@ typedef struct rtc_multi rtc_multi; /* opaque: per frame slot n scene handles an
  * Its handles render one centred camera sample per pixel: rtc_scene_set_sampling (rtc.h) has no multi-GPU form yet;
  * neither have rtc_scene_set_spots and rtc_scene_set_bumps: it renders without cones and without bumps.
  * A description with a torus (RTC_TORUS) is refused with RTC_ERR_UNSUPPORTED: its kernels are single-GPU ones; so is one
- * with a texture map of mapping RTC_TEX_MESH (rtc_scene_set_mesh_uvs has no multi-GPU form). */
+ * with a texture map of mapping RTC_TEX_MESH (rtc_scene_set_mesh_uvs has no multi-GPU form).
+ * rtc_scene_set_gloss has no multi-GPU form either: it renders without gloss, every mirror and glass sharp. */
 int rtc_multi_create(const rtc_scene_desc *desc, uint32_t n_gpus, uint32_t flags, rtc_multi **out);
 void rtc_multi_destroy(rtc_multi *m);
 

@@ -220,7 +220,7 @@ BUMP_NONE, BUMP_NOISE, BUMP_RIPPLES = 0, 1, 2  # RTC_BUMP_*
 # leaf kinds (rtc.h); RTC_TORUS: a ring torus, its major and minor radius in cyl_min / cyl_max
 RTC_SPHERE, RTC_PLANE, RTC_CUBE, RTC_CYLINDER, RTC_TRIANGLE, RTC_SMOOTH_TRIANGLE, RTC_CONE, RTC_TORUS = range(8)
 # the options that select a kernel family on a handle that does not need it (set_option; tests and tools/time_scenes.py)
-KERNEL_OPTIONS = ("sampling_kernels", "motion_kernels", "spot_kernels", "bump_kernels", "torus_kernels", "meshuv_kernels")
+KERNEL_OPTIONS = ("sampling_kernels", "motion_kernels", "spot_kernels", "bump_kernels", "torus_kernels", "meshuv_kernels", "gloss_kernels")
 # texture mappings (rtc.h); RTC_TEX_MESH: (u, v) from the hit triangle's texture row
 RTC_TEX_SPHERICAL, RTC_TEX_PLANAR, RTC_TEX_CYLINDRICAL, RTC_TEX_CUBIC, RTC_TEX_MESH = range(5)
 BUMP_MAX_OCTAVES = 16  # RTC_BUMP_MAX_OCTAVES
@@ -229,6 +229,30 @@ BUMP_MAX_OCTAVES = 16  # RTC_BUMP_MAX_OCTAVES
 class MeshUvs(C.Structure):
     """struct rtc_mesh_uvs (include/rtc.h): a texture row (a1, b1, a2, b2, a3, b3) per triangle, in tri_* order."""
     _fields_ = [("n_tris", C.c_uint32), ("uv", C.POINTER(C.c_double))]
+
+
+class Gloss(C.Structure):
+    """struct rtc_gloss (include/rtc.h): a (reflection, transmission) roughness per material row, and the draws' seed."""
+
+    _fields_ = [("n_materials", C.c_uint32), ("reflection", C.POINTER(C.c_double)), ("transmission", C.POINTER(C.c_double)),
+                ("seed", C.c_uint64)]
+
+
+def gloss_struct(gloss):
+    """(Gloss, the arrays it points into) of a dict of "reflection" and "transmission" ((n,) each; one may be missing or None:
+    all zeros) and an optional "seed" (GpuScene.set_gloss); the arrays must outlive the struct's use."""
+    r, t = gloss.get("reflection"), gloss.get("transmission")
+    r = None if r is None else np.ascontiguousarray(r, dtype=np.float64)
+    t = None if t is None else np.ascontiguousarray(t, dtype=np.float64)
+    if r is None and t is None:
+        raise ValueError("gloss: neither reflection nor transmission")
+    n = (r if r is not None else t).shape[0]
+    for a in (r, t):
+        if a is not None and a.shape != (n,):
+            raise ValueError(f"gloss: an array of shape {a.shape}, ({n},) expected")
+    g = Gloss(n, r.ctypes.data_as(C.POINTER(C.c_double)) if r is not None else None,
+              t.ctypes.data_as(C.POINTER(C.c_double)) if t is not None else None, int(gloss.get("seed", 0)))
+    return g, (r, t)
 
 
 class Bump(C.Structure):
@@ -271,13 +295,13 @@ RTC_SYMBOLS = ["rtc_scene_create", "rtc_scene_clone", "rtc_scene_destroy", "rtc_
                "rtc_scene_create_with_lights", "rtc_scene_set_light_seed", "rtc_scene_set_sampling",
                "rtc_scene_set_sample_pass", "rtc_scene_accumulate_device", "rtc_scene_set_motion",
                "rtc_scene_adaptive_begin_device", "rtc_scene_adaptive_accumulate_device", "rtc_scene_adaptive_step", "rtc_render_adaptive",
-               "rtc_scene_set_spots", "rtc_scene_set_bumps", "rtc_scene_set_mesh_uvs"]
+               "rtc_scene_set_spots", "rtc_scene_set_bumps", "rtc_scene_set_mesh_uvs", "rtc_scene_set_gloss"]
 # (... and include/rtc_diag.h: diagnostics and tuning, for the tests, bench.py and tools/)
 RTC_DIAG_SYMBOLS = ["rtc_set_option", "rtc_last_kernel_name", "rtc_get_schedule", "rtc_get_chunk_times", "rtc_diag_build_tables", "rtc_diag_root_boxes"]
 HOST_SYMBOLS = ["rtch_last_error", "rtch_scene_load", "rtch_scene_free", "rtch_scene_desc", "rtch_scene_camera",
                 "rtch_camera_rotate", "rtch_camera_move", "rtch_camera_make", "rtch_canvas_ppm", "rtch_canvas_rgba8", "rtch_scene_render", "rtch_set_loader_threads",
                 "rtch_scene_lights", "rtch_scene_sampling", "rtch_scene_passes", "rtch_scene_motion", "rtch_scene_adaptive",
-                "rtch_scene_spots", "rtch_scene_bumps", "rtch_scene_mesh_uvs"]
+                "rtch_scene_spots", "rtch_scene_bumps", "rtch_scene_mesh_uvs", "rtch_scene_gloss"]
 
 MULTI_SYMBOLS = ["rtc_multi_create", "rtc_multi_destroy", "rtc_multi_render", "rtc_multi_render_rgba8", "rtc_multi_render_device", "rtc_multi_render_rgba8_device",
                  "rtc_multi_synchronize", "rtc_multi_stream", "rtc_multi_get_stats", "rtc_multi_balance", "rtc_multi_last_error"]
@@ -340,6 +364,7 @@ def hip_lib():
         lib.rtc_scene_set_spots.argtypes = [C.c_void_p, C.POINTER(Spot)]
         lib.rtc_scene_set_bumps.argtypes = [C.c_void_p, C.POINTER(Bump)]
         lib.rtc_scene_set_mesh_uvs.argtypes = [C.c_void_p, C.POINTER(MeshUvs)]
+        lib.rtc_scene_set_gloss.argtypes = [C.c_void_p, C.POINTER(Gloss)]
         lib.rtc_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.POINTER(Adaptive), C.c_void_p, C.c_void_p]
         lib.rtc_scene_destroy.argtypes = [C.c_void_p]
         lib.rtc_scene_destroy.restype = None
@@ -395,6 +420,7 @@ def host_lib():
         lib.rtch_scene_spots.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), _dp, _dp, _dp, C.c_uint32]
         lib.rtch_scene_bumps.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), _dp, C.POINTER(C.c_uint32), _dp, _dp, C.c_uint32]
         lib.rtch_scene_mesh_uvs.argtypes = [C.c_void_p, _dp, C.c_uint32]
+        lib.rtch_scene_gloss.argtypes = [C.c_void_p, _dp, _dp, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.c_uint32]
         lib.rtch_scene_adaptive.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(Adaptive)]
         lib.rtch_scene_camera.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Camera)]
         lib.rtch_camera_rotate.argtypes = [C.c_void_p, C.c_double]
@@ -589,6 +615,18 @@ class HostScene:
         _check_host(host_lib().rtch_scene_mesh_uvs(self._h, out.ctypes.data_as(_dp), n))
         return out if out.any() else None
 
+    def gloss(self):
+        """The materials' "roughness" entries (rtch_scene_gloss), in mat_* order, and the camera's "gloss-seed": a dict of
+        "reflection" (n,), "transmission" (n,) and "seed" - what GpuScene.set_gloss takes -, or None when no material of the
+        file has the key."""
+        n = self.desc.n_materials
+        out = {"reflection": np.zeros(n), "transmission": np.zeros(n)}
+        seed, present = C.c_uint64(), C.c_int()
+        _check_host(host_lib().rtch_scene_gloss(self._h, out["reflection"].ctypes.data_as(_dp), out["transmission"].ctypes.data_as(_dp),
+                                                C.byref(seed), C.byref(present), n))
+        out["seed"] = seed.value
+        return out if present.value else None
+
     def adaptive(self):
         """The camera's "sampling": {"adaptive": ...} of the scene file (rtch_scene_adaptive): an Adaptive whose max_passes
         is "passes", or None when the file has none."""
@@ -705,6 +743,15 @@ class GpuScene:
             raise ValueError(f"set_mesh_uvs: rows of shape {u.shape}, (n_tris, 6) expected")
         m = MeshUvs(u.shape[0], u.ctypes.data_as(_dp))
         _check_hip(hip_lib().rtc_scene_set_mesh_uvs(self._s, C.byref(m)))
+
+    def set_gloss(self, gloss):
+        """rtc_scene_set_gloss: a dict of "reflection" and "transmission" ((n_materials,) each; one may be missing: all zeros)
+        and an optional "seed" (HostScene.gloss()); None: no gloss - as every row zero, the handle's previous kernels."""
+        if gloss is None:
+            _check_hip(hip_lib().rtc_scene_set_gloss(self._s, None))
+            return
+        g, _keep = gloss_struct(gloss)
+        _check_hip(hip_lib().rtc_scene_set_gloss(self._s, C.byref(g)))
 
     def accumulate_device(self, accum, stream=None):
         """rtc_scene_accumulate_device: an Accum, enqueued on `stream` (None: the handle's own) after this handle's renders."""

@@ -143,6 +143,18 @@ __global__ void rtc_render_kernel_meshuv_bigworld(const DevScene S, const DevCam
                                                   const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
                                                   const DevBumps bumps, const DevMeshUvs muv);
 }
+// The gloss kernels (rtc_scene_set_gloss: rough materials scatter their rays): the meshuv kernels' tables and edge, and the
+// roughness rows with the hash key (DevGloss) as one more argument.
+extern "C" {
+__global__ void rtc_render_kernel_gloss(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                        double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                        const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                        const DevBumps bumps, const DevMeshUvs muv, const DevGloss gloss);
+__global__ void rtc_render_kernel_gloss_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                                 double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                                 const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                                 const DevBumps bumps, const DevMeshUvs muv, const DevGloss gloss);
+}
 // Progressive rendering's accumulation (rtc_accum.hip): the grid's blocks for n pixels (the noise partials it writes, at
 // most) and the enqueue of its kernels.
 uint32_t rtcAccumBlocks(size_t n_pixels, bool wide);
@@ -358,7 +370,7 @@ bool tablesInLds(const rtc_scene* s) {
 // (the area kernels take one more argument, DevAreaLights: `area` instead of `fn`; the sampling kernels DevSampling:
 // `ms`, and both: `area_ms`; the motion kernels both and DevMotion: `motion`; the spot kernels those three and DevSpots:
 // `spot`; the bump kernels those four and DevBumps: `bump` - the torus kernels take the same arguments and travel in `bump` too;
-// the meshuv kernels those five and DevMeshUvs: `meshuv`)
+// the meshuv kernels those five and DevMeshUvs: `meshuv`; the gloss kernels those six and DevGloss: `gloss`)
 struct KernelChoice {
   decltype(&rtc_render_kernel) fn;
   const char* name;
@@ -369,6 +381,7 @@ struct KernelChoice {
   decltype(&rtc_render_kernel_spot) spot = nullptr;
   decltype(&rtc_render_kernel_bump) bump = nullptr;
   decltype(&rtc_render_kernel_meshuv) meshuv = nullptr;
+  decltype(&rtc_render_kernel_gloss) gloss = nullptr;
   KernelChoice(decltype(&rtc_render_kernel) f, const char* n) : fn(f), name(n) {}
   KernelChoice(decltype(&rtc_render_kernel_area) a, const char* n) : fn(nullptr), name(n), area(a) {}
   KernelChoice(decltype(&rtc_render_kernel_ms) m, const char* n) : fn(nullptr), name(n), ms(m) {}
@@ -377,11 +390,12 @@ struct KernelChoice {
   KernelChoice(decltype(&rtc_render_kernel_spot) sk, const char* n) : fn(nullptr), name(n), spot(sk) {}
   KernelChoice(decltype(&rtc_render_kernel_bump) bk, const char* n) : fn(nullptr), name(n), bump(bk) {}
   KernelChoice(decltype(&rtc_render_kernel_meshuv) uk, const char* n) : fn(nullptr), name(n), meshuv(uk) {}
+  KernelChoice(decltype(&rtc_render_kernel_gloss) gk, const char* n) : fn(nullptr), name(n), gloss(gk) {}
   void launch(uint32_t blocks, hipStream_t stream, const rtc_scene* s, const DevScene& dev, const DevCamera& cam, const DevPixelMap& map,
               uint32_t max_depth, double* d_out, DevStats* st_now, DevStats* st_next) const {
     DevSampling smp = s->sampling;  // (the pass's area-light offset, P * N * S: N is the camera's whole image)
     smp.pixel_base = static_cast<unsigned long long>(smp.sample_base) * (static_cast<unsigned long long>(cam.hsize) * cam.vsize);
-    if (motion || spot || bump || meshuv) {
+    if (motion || spot || bump || meshuv || gloss) {
       // the handle's root tables with the moving roots' bounds (or the scene's, all displacements zero: the option), and
       // the scene's area rows (or zero rows: a point-only table); the spot kernels also the handle's spot rows (or zero
       // rows, every flag 0: the option)
@@ -397,7 +411,14 @@ struct KernelChoice {
         mo.disp = m->disp.p;
       }
       const DevAreaLights area = s->area_kernel ? s->area : DevAreaLights{s->tab->zero_rows.p, s->area.seed};
-      if (meshuv) {  // (the handle's texture rows, or none: every row six zeros)
+      if (gloss) {  // (the handle's roughness rows, or zero rows, every material smooth: the option)
+        const DevSpots sp{s->spots ? s->spots->row.p : s->tab->zero_rows.p};
+        const DevBumps bp{s->bumps ? s->bumps->row.p : s->tab->zero_bump.p};
+        const DevMeshUvs uv{s->mesh_uvs ? s->mesh_uvs->row.p : nullptr};
+        // (RTC_GLOSS_ROW <= RTC_BUMP_ROW: the zero bump rows serve as zero roughness rows)
+        const DevGloss gl{s->gloss ? s->gloss->row.p : s->tab->zero_bump.p, s->gloss ? s->gloss->key : 0ull};
+        hipLaunchKernelGGL(gloss, dim3(blocks), dim3(256), 0, stream, md, cam, map, max_depth, d_out, st_now, st_next, area, smp, mo, sp, bp, uv, gl);
+      } else if (meshuv) {  // (the handle's texture rows, or none: every row six zeros)
         const DevSpots sp{s->spots ? s->spots->row.p : s->tab->zero_rows.p};
         const DevBumps bp{s->bumps ? s->bumps->row.p : s->tab->zero_bump.p};
         const DevMeshUvs uv{s->mesh_uvs ? s->mesh_uvs->row.p : nullptr};
@@ -440,6 +461,9 @@ bool torusKernels(const rtc_scene* s) { return s->has_torus || rtcOptions().toru
 // The meshuv kernels run when a texture map of the handle's scene has mapping RTC_TEX_MESH - whatever else the handle
 // holds, tori included: no other kernel knows mapping 4 - or, for tests, whenever option "meshuv_kernels" is set.
 bool meshuvKernels(const rtc_scene* s) { return s->has_mesh_map || rtcOptions().meshuv_kernels != 0.0; }
+// The gloss kernels run when a row of the handle's roughness table is non-zero (rtc_scene_set_gloss keeps no other table)
+// - whatever else the handle holds: they are the meshuv walk - or, for tests, whenever option "gloss_kernels" is set.
+bool glossKernels(const rtc_scene* s) { return s->gloss != nullptr || rtcOptions().gloss_kernels != 0.0; }
 #define RTC_KERNEL(k) KernelChoice{k, #k}
 // The general kernel at three waves per SIMD (rtc_render_kernel3): forced by option "waves3", else what the handle's
 // trial measured (KernelTune in launch()).
@@ -466,6 +490,7 @@ KernelChoice ldsKernel(const rtc_scene* s, const DevPixelMap& map) {
   return s->ext_kernel ? RTC_KERNEL(rtc_render_kernel_ext) : RTC_KERNEL(rtc_render_kernel);
 }
 KernelChoice renderKernel(const rtc_scene* s, const DevPixelMap& map) {
+  if (glossKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_gloss) : RTC_KERNEL(rtc_render_kernel_gloss_bigworld);
   if (meshuvKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_meshuv) : RTC_KERNEL(rtc_render_kernel_meshuv_bigworld);
   if (torusKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_torus) : RTC_KERNEL(rtc_render_kernel_torus_bigworld);
   if (bumpKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_bump) : RTC_KERNEL(rtc_render_kernel_bump_bigworld);
@@ -483,6 +508,7 @@ KernelChoice renderKernel(const rtc_scene* s, const DevPixelMap& map) {
 
 // Work-groups of the launch's kernel that are resident at once, and the waves in them.
 uint32_t residentBlocksAlone(const rtc_scene* s, const DevPixelMap& map) {
+  if (glossKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_gloss_lds : s->blocks_per_cu_gloss_big);
   if (meshuvKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_meshuv_lds : s->blocks_per_cu_meshuv_big);
   if (torusKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_torus_lds : s->blocks_per_cu_torus_big);
   if (bumpKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_bump_lds : s->blocks_per_cu_bump_big);
@@ -892,7 +918,7 @@ int launch(rtc_scene* s, const rtc_camera& cam, const DevPixelMap& map_in, uint3
   int trial_slot = -1;
   {
     rtc_scene::KernelTune& T = s->tune;
-    const bool eligible = !samplingKernels(s) && !motionKernels(s) && !spotKernels(s) && !bumpKernels(s) && !torusKernels(s) && !meshuvKernels(s) &&  // (the sampling, motion, spot, bump, torus and meshuv kernels have no three-wave form)
+    const bool eligible = !samplingKernels(s) && !motionKernels(s) && !spotKernels(s) && !bumpKernels(s) && !torusKernels(s) && !meshuvKernels(s) && !glossKernels(s) &&  // (the sampling, motion, spot, bump, torus, meshuv and gloss kernels have no three-wave form)
                           ((s->general3_ok && rtcOptions().waves3 < 0.0 && tablesInLds(s) &&
                             !(s->tab && s->tab->handles.load(std::memory_order_relaxed) > 1) &&
                             static_cast<double>(map.n_chunks) >= 4.0 * 4.0 * s->n_cus * s->blocks_per_cu_lds) ||
@@ -2272,6 +2298,10 @@ int uploadTables(const rtc_scene_desc& d, const SceneTraits& traits, const HostT
     s->blocks_per_cu_meshuv_lds = static_cast<uint32_t>(std::max(nb, 1));
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_meshuv_bigworld, 256, 0));
     s->blocks_per_cu_meshuv_big = static_cast<uint32_t>(std::max(nb, 1));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_gloss, 256, 0));  // (the gloss kernels: one pair for every world)
+    s->blocks_per_cu_gloss_lds = static_cast<uint32_t>(std::max(nb, 1));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_gloss_bigworld, 256, 0));
+    s->blocks_per_cu_gloss_big = static_cast<uint32_t>(std::max(nb, 1));
     if (const int v = static_cast<int>(rtcOptions().blocks_per_cu); v >= 1) {  // (tuning option)
       s->blocks_per_cu_lds = std::min<uint32_t>(s->blocks_per_cu_lds, v), s->blocks_per_cu_big = std::min<uint32_t>(s->blocks_per_cu_big, v);
       s->blocks_per_cu_ms_lds = std::min<uint32_t>(s->blocks_per_cu_ms_lds, v), s->blocks_per_cu_ms_big = std::min<uint32_t>(s->blocks_per_cu_ms_big, v);
@@ -2280,6 +2310,7 @@ int uploadTables(const rtc_scene_desc& d, const SceneTraits& traits, const HostT
       s->blocks_per_cu_bump_lds = std::min<uint32_t>(s->blocks_per_cu_bump_lds, v), s->blocks_per_cu_bump_big = std::min<uint32_t>(s->blocks_per_cu_bump_big, v);
       s->blocks_per_cu_torus_lds = std::min<uint32_t>(s->blocks_per_cu_torus_lds, v), s->blocks_per_cu_torus_big = std::min<uint32_t>(s->blocks_per_cu_torus_big, v);
       s->blocks_per_cu_meshuv_lds = std::min<uint32_t>(s->blocks_per_cu_meshuv_lds, v), s->blocks_per_cu_meshuv_big = std::min<uint32_t>(s->blocks_per_cu_meshuv_big, v);
+      s->blocks_per_cu_gloss_lds = std::min<uint32_t>(s->blocks_per_cu_gloss_lds, v), s->blocks_per_cu_gloss_big = std::min<uint32_t>(s->blocks_per_cu_gloss_big, v);
     }
   }
   DevScene& D = s->dev;
@@ -2834,6 +2865,46 @@ int rtc_scene_set_mesh_uvs(rtc_scene* s, const rtc_mesh_uvs* uvs) {
   return RTC_OK;
 }
 
+// ---- glossy reflection and refraction
+// Validated before anything changes: first the table's own values - so that they are checked whatever the handle -, then
+// its material count against the handle's.  An array that is NULL is all zeros; every row zero is no gloss: the handle's
+// previous kernels.
+int rtc_scene_set_gloss(rtc_scene* s, const rtc_gloss* gloss) {
+  g_error.clear();
+  if (!s) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
+  bool any = false;
+  std::vector<double> rows;
+  if (gloss) {
+    const uint32_t n = gloss->n_materials;
+    rows.assign(static_cast<size_t>(RTC_GLOSS_ROW) * n, 0.0);
+    for (uint32_t i = 0; i < n; ++i) {
+      const double v[2] = {gloss->reflection ? gloss->reflection[i] : 0.0, gloss->transmission ? gloss->transmission[i] : 0.0};
+      for (int k = 0; k < 2; ++k) {
+        const char* what = k == 0 ? "reflection" : "transmission";
+        if (!std::isfinite(v[k])) return fail(RTC_ERR_INVALID_ARGUMENT, "gloss: material %u: a %s roughness that is not finite", i, what);
+        if (v[k] < 0.0 || v[k] > 1.0) return fail(RTC_ERR_INVALID_ARGUMENT, "gloss: material %u: %s roughness %g outside [0, 1]", i, what, v[k]);
+        rows[static_cast<size_t>(RTC_GLOSS_ROW) * i + k] = v[k];
+        any = any || v[k] != 0.0;
+      }
+    }
+    if (n != s->dev.n_materials) return fail(RTC_ERR_INVALID_ARGUMENT, "gloss: n_materials %u, the scene has %u", n, s->dev.n_materials);
+  }
+  std::shared_ptr<const GlossTables> tables;  // (no rough row: none)
+  if (any) {
+    auto t = std::make_shared<GlossTables>();
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(t->row.upload(rows));
+    t->key = rtc_mix64(gloss->seed ^ RTC_GLOSS_SALT);
+    tables = std::move(t);
+  }
+  // (the rows being replaced may still be read by a launch of this handle or of its band clones)
+  HIP_TRY(handleIdle(s));
+  for (rtc_scene* b : s->band) HIP_TRY(handleIdle(b));
+  s->gloss = tables;
+  for (rtc_scene* b : s->band) b->gloss = tables;  // (the band clones rtc_render renders a large frame with)
+  return RTC_OK;
+}
+
 // ---- adaptive sampling
 // The setting's own fields, and the image's tile count (T < 2^31)
 static int checkAdaptive(const rtc_adaptive* a, uint32_t hsize, uint32_t vsize, uint32_t* n_tiles) {
@@ -3053,6 +3124,9 @@ int rtc_scene_clone(const rtc_scene* src, rtc_scene** out) {
   s->mesh_uvs = src->mesh_uvs;  // (shared: read-only once made)
   s->blocks_per_cu_meshuv_lds = src->blocks_per_cu_meshuv_lds;
   s->blocks_per_cu_meshuv_big = src->blocks_per_cu_meshuv_big;
+  s->gloss = src->gloss;  // (shared: read-only once made)
+  s->blocks_per_cu_gloss_lds = src->blocks_per_cu_gloss_lds;
+  s->blocks_per_cu_gloss_big = src->blocks_per_cu_gloss_big;
   s->simple_kernel = src->simple_kernel;
   s->flat_kernel = src->flat_kernel;
   s->simple3_ok = src->simple3_ok;
@@ -3451,7 +3525,8 @@ int rtc_set_option(const char* name, double value) {
                {"inflight_chunks_per_wave", &o.inflight_chunks_per_wave}, {"build_threads", &o.build_threads}, {"box_cull", &o.box_cull},
                {"sampling_kernels", &o.sampling_kernels}, {"motion_kernels", &o.motion_kernels},
                {"spot_kernels", &o.spot_kernels}, {"bump_kernels", &o.bump_kernels},
-               {"torus_kernels", &o.torus_kernels}, {"meshuv_kernels", &o.meshuv_kernels}};
+               {"torus_kernels", &o.torus_kernels}, {"meshuv_kernels", &o.meshuv_kernels},
+               {"gloss_kernels", &o.gloss_kernels}};
   for (const auto& e : table)
     if (std::strcmp(e.name, name) == 0) {
       e.slot->set(value);

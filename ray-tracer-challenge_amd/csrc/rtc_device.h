@@ -356,6 +356,27 @@ struct DevMeshUvs {
   const double* __restrict__ row;  // [n_tris][RTC_MESHUV_ROW], or null
 };
 
+// Glossy reflection and refraction (rtc_scene_set_gloss): the extra argument of the gloss kernels
+// only.  One row of RTC_GLOSS_ROW doubles per material, in mat_* order: (reflection, transmission) roughness; every row
+// under the "gloss_kernels" option on a handle without gloss is zero.  key = rtc_mix64(seed ^ RTC_GLOSS_SALT).
+#define RTC_GLOSS_ROW 2u
+#define RTC_GLOSS_SALT 0x13198A2E03707344ull
+#define RTC_GLOSS_DRAWS 32u
+struct DevGloss {
+  const double* __restrict__ row;  // [n_materials][RTC_GLOSS_ROW]
+  unsigned long long key;
+};
+// The draws of one ray (rtc.h): h belongs to camera sample g (global index) of the whole-image pixel p, J(axis) to the ray
+// of path code `code` in that sample's tree.  Pure functions: the same bits in the kernels and in the checker, whichever
+// band, tile, clone or lane traces the ray.
+__host__ __device__ inline unsigned long long rtc_gloss_sample_key(unsigned long long key, unsigned long long p, unsigned long long g) {
+  return rtc_mix64(key + 0x9E3779B97F4A7C15ull * (((p << 32) | (g << 8)) + 1ull));
+}
+__host__ __device__ inline double rtc_gloss_jitter(unsigned long long h, uint32_t code, uint32_t axis) {
+  const unsigned long long c = (static_cast<unsigned long long>(code) << 8) | axis;
+  return static_cast<double>(rtc_mix64(h + 0x9E3779B97F4A7C15ull * (c + 1ull)) >> 11) * 0x1.0p-53;
+}
+
 struct DevCamera {
   double half_width, half_height, pixel_size;
   double inv[12];  // rows 0..2 of Camera._inverse_transform

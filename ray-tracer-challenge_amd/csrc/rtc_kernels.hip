@@ -2369,7 +2369,22 @@ struct Pending {
   Ray ray;
   double weight;
   uint32_t remaining;
+#ifdef RTC_GLOSS_TU
+  // (GLOSS) the ray's path code in its pixel's ray tree: the primary ray 1, the reflected child of c
+  // 2 c, the refracted child 2 c + 1 (below 2^17: max_depth <= RTC_MAX_DEPTH).  In memory and in LDS it rides in the upper
+  // half of the word that holds `remaining`: the record stays 64 bytes.  Compiled into the gloss kernels' unit only.
+  uint32_t code;
+#endif
 };
+#ifdef RTC_GLOSS_TU
+#define RTC_PENDING_TAIL(p) (static_cast<unsigned long long>((p).remaining) | (static_cast<unsigned long long>((p).code) << 32))
+#define RTC_PENDING_CODE(p, word) (p).code = static_cast<uint32_t>((word) >> 32)
+#define RTC_SET_CODE(p, c) (p).code = (c)
+#else
+#define RTC_PENDING_TAIL(p) (p).remaining
+#define RTC_PENDING_CODE(p, word)
+#define RTC_SET_CODE(p, c)
+#endif
 
 // A Pending as it sits on a lane's stack in memory: one 64-byte line, moved as four 16-byte accesses.
 typedef unsigned long long Quad2 __attribute__((ext_vector_type(2)));  // 16 bytes, moved as bits
@@ -2381,7 +2396,7 @@ __device__ __forceinline__ void store_pending(PendingRec* dst, const Pending& p)
   a.x = dbits(p.ray.ox); a.y = dbits(p.ray.oy);
   b.x = dbits(p.ray.oz); b.y = dbits(p.ray.dx);
   c.x = dbits(p.ray.dy); c.y = dbits(p.ray.dz);
-  e.x = dbits(p.weight); e.y = p.remaining;
+  e.x = dbits(p.weight); e.y = RTC_PENDING_TAIL(p);
   d[0] = a; d[1] = b; d[2] = c; d[3] = e;
 }
 __device__ __forceinline__ Pending load_pending(const PendingRec* src) {
@@ -2391,6 +2406,7 @@ __device__ __forceinline__ Pending load_pending(const PendingRec* src) {
   p.ray = {bitsd(a.x), bitsd(a.y), bitsd(b.x), bitsd(b.y), bitsd(c.x), bitsd(c.y)};
   p.weight = bitsd(e.x);
   p.remaining = static_cast<uint32_t>(e.y);
+  RTC_PENDING_CODE(p, e.y);
   return p;
 }
 
@@ -2401,7 +2417,7 @@ __device__ __forceinline__ void store_pending_lds(Quad2* dst, const Pending& p) 
   a.x = dbits(p.ray.ox); a.y = dbits(p.ray.oy);
   b.x = dbits(p.ray.oz); b.y = dbits(p.ray.dx);
   c.x = dbits(p.ray.dy); c.y = dbits(p.ray.dz);
-  e.x = dbits(p.weight); e.y = p.remaining;
+  e.x = dbits(p.weight); e.y = RTC_PENDING_TAIL(p);
   dst[0] = a; dst[64] = b; dst[128] = c; dst[192] = e;
 }
 __device__ __forceinline__ Pending load_pending_lds(const Quad2* src) {
@@ -2410,6 +2426,7 @@ __device__ __forceinline__ Pending load_pending_lds(const Quad2* src) {
   p.ray = {bitsd(a.x), bitsd(a.y), bitsd(b.x), bitsd(b.y), bitsd(c.x), bitsd(c.y)};
   p.weight = bitsd(e.x);
   p.remaining = static_cast<uint32_t>(e.y);
+  RTC_PENDING_CODE(p, e.y);
   return p;
 }
 
@@ -2497,6 +2514,43 @@ __device__ __forceinline__ Ray camera_sample(const DevCamera& cam, const DevSamp
   r.dz = dz;
   return r;
 }
+#ifdef RTC_GLOSS_TU
+// (GLOSS, rtc.h's rtc_scene_set_gloss) the direction d of a rough material's child ray, scattered:
+// s is the first of RTC_GLOSS_DRAWS draws of the ray's own hash (h: its camera sample's, code: its path code) that lies in
+// the unit ball - none: (0, 0, 0), the lens sampler's rule -, e = d + s * rough, d' = e / |e| (|e| == 0: d), and d' is
+// taken when it lies on the child's side of the geometric normal ng (the reflection's above it, the refraction's below),
+// else d stays.  Only + - * / sqrt and comparisons, each correctly rounded, in the order of rtc.h.  The draws are made one
+// triple at a time and never kept.  Out of line, by value: a lane whose material is smooth never comes here, and the
+// walk's registers are not the sampler's.  Compiled into the gloss kernels' translation unit only.
+struct GlossDir {
+  double x, y, z;
+};
+__device__ __noinline__ GlossDir gloss_scatter(unsigned long long h, uint32_t code, double rough, double dx, double dy, double dz,
+                                               double ngx, double ngy, double ngz, bool below) {
+  double sx = 0.0, sy = 0.0, sz = 0.0;
+  for (uint32_t t = 0u; t < RTC_GLOSS_DRAWS; ++t) {
+    const double a = 2.0 * rtc_gloss_jitter(h, code, 3u * t + 0u) - 1.0;
+    const double b = 2.0 * rtc_gloss_jitter(h, code, 3u * t + 1u) - 1.0;
+    const double c = 2.0 * rtc_gloss_jitter(h, code, 3u * t + 2u) - 1.0;
+    if (((a * a) + (b * b)) + (c * c) <= 1.0) {
+      sx = a;
+      sy = b;
+      sz = c;
+      break;
+    }
+  }
+  const double ex = dx + sx * rough, ey = dy + sy * rough, ez = dz + sz * rough;
+  const double m = __builtin_sqrt((ex * ex + ey * ey) + ez * ez);  // tuple.zig's normalize
+  GlossDir r{dx, dy, dz};
+  if (m != 0.0) {
+    const double ux = ex / m, uy = ey / m, uz = ez / m;
+    const double side = (ux * ngx + uy * ngy) + uz * ngz;
+    if (below ? side < 0.0 : side > 0.0) r = GlossDir{ux, uy, uz};
+  }
+  return r;
+}
+#endif
+
 // (MS) a lane's sample word: the sample index, and whether the lane owns the pixel (deals its samples, step 1)
 #define RTC_SAMPLE_MASK 0xFFFFu
 #define RTC_SAMPLE_OWNER 0x10000u
@@ -2527,14 +2581,18 @@ __device__ __forceinline__ Ray camera_sample(const DevCamera& cam, const DevSamp
 // barycentrics reach the pattern evaluation, texture_map_at's mapping-4 branch reads the triangle's texture row.  With TORUS
 // and everything below it, compiled into the meshuv kernels' translation unit only, under RTC_MESHUV_TU, which implies
 // RTC_TORUS_TU: one family renders a world that holds tori and textured meshes)
+// (GLOSS: rough materials whose reflected and refracted rays are scattered - DevGloss, the gloss kernels' extra argument;
+// a Pending carries its ray's path code, the draws come from gloss_scatter.  With MESHUV and everything below it, compiled
+// into the gloss kernels' translation unit only, under RTC_GLOSS_TU, which implies RTC_MESHUV_TU and RTC_TORUS_TU)
 template <bool LDS, bool CSG, int WORLD = 0, int WAVES = 2, bool COOP = false, bool BOX = true, bool AREA = false, bool MS = false,
-          bool MOTION = false, bool SPOT = false, bool BUMP = false, bool TORUS = false, bool MESHUV = false>
+          bool MOTION = false, bool SPOT = false, bool BUMP = false, bool TORUS = false, bool MESHUV = false, bool GLOSS = false>
 __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& cam, const DevPixelMap& map,
                                             const uint32_t max_depth, double* __restrict__ out,
                                             DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
                                             const DevAreaLights& area = DevAreaLights{}, const DevSampling& smp = DevSampling{},
                                             const DevMotion& mo = DevMotion{}, const DevSpots& spots = DevSpots{},
-                                            const DevBumps& bumps = DevBumps{}, const DevMeshUvs& muv = DevMeshUvs{}) {
+                                            const DevBumps& bumps = DevBumps{}, const DevMeshUvs& muv = DevMeshUvs{},
+                                            const DevGloss& gloss = DevGloss{}) {
   static_assert(!AREA || !COOP, "the area kernels run no cooperative iterations");
   static_assert(!MS || !COOP, "the sampling kernels run no cooperative iterations");
   static_assert(!MOTION || (MS && AREA && WORLD == 0), "the motion kernels are the general area-sampling walk");
@@ -2552,6 +2610,13 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
 #else
   static_assert(!MESHUV, "mapping RTC_TEX_MESH is compiled in the meshuv translation unit (rtc_meshuv.hip) only");
   (void)muv;
+#endif
+  static_assert(!GLOSS || MESHUV, "the gloss kernels are the meshuv walk");
+#ifdef RTC_GLOSS_TU
+  static_assert(GLOSS, "the gloss translation unit compiles the gloss kernels only: its Pending carries the path code");
+#else
+  static_assert(!GLOSS, "rough materials are compiled in the gloss translation unit (rtc_gloss.hip) only");
+  (void)gloss;
 #endif
   RTC_PRIO_PHASE(RTC_PRIO_WORK);
 #ifndef RTC_PROFILE
@@ -2737,6 +2802,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
   cur.ray = {0, 0, 0, 0, 0, 0};
   cur.weight = 0.0;
   cur.remaining = 0u;
+  RTC_SET_CODE(cur, 0u);
   // The lane's pending refraction siblings: a deque.  The lane itself pops the newest entry (depth
   // first); an idle neighbour may take the OLDEST one (the largest sub-tree) through the mailbox.
   // It lives in a buffer of its own rather than in scratch: scratch interleaves the lanes dword by dword,
@@ -3007,6 +3073,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
         cur.ray = camera_sample(cam, smp, new_px, new_py, k);
         cur.weight = smp.weight;  // (the pixel is the samples' mean: each adds 1 / samples of its colour)
         cur.remaining = max_depth;
+        RTC_SET_CODE(cur, 1u);  // (GLOSS) the primary ray
         have_cur = true;
         has_pixel = true;
         n_primary++;
@@ -3035,6 +3102,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
       cur.ray.dz = dz;
       cur.weight = 1.0;
       cur.remaining = max_depth;
+      RTC_SET_CODE(cur, 1u);  // (GLOSS) the primary ray
       have_cur = true;
       has_pixel = true;
       shared = false;
@@ -3667,10 +3735,37 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
     RTC_STAMP(13);
     Pending child;
     child.remaining = cur.remaining - 1u;
+#ifdef RTC_GLOSS_TU
+    // (GLOSS) the material's roughness pair, read per lane as the bump row is (mat_index is the lane's); a lane whose
+    // children are both smooth hashes nothing and leaves the directions' bits.  The hash of the ray's camera sample: the
+    // whole-image pixel and the global sample index, as the shutter time's.
+    double rough_r = 0.0, rough_t = 0.0;
+    unsigned long long gloss_h = 0ull;
+    if constexpr (GLOSS) {
+      const double* __restrict__ G = gloss.row + static_cast<size_t>(RTC_GLOSS_ROW) * mat_index;
+      if (do_reflect) rough_r = G[0];
+      if (do_refract) rough_t = G[1];
+      if (rough_r > 0.0 || rough_t > 0.0) {
+        uint32_t px, py;
+        map_pixel(map, out_index, px, py);
+        const unsigned long long p = static_cast<unsigned long long>(py) * cam.hsize + px;
+        gloss_h = rtc_gloss_sample_key(gloss.key, p, static_cast<unsigned long long>(smp.sample_base) + (*samp_word & RTC_SAMPLE_MASK));
+      }
+    }
+#endif
     if (do_reflect) {
       const double two_dot = 2.0 * ((ray.dx * hx + ray.dy * hy) + ray.dz * hz);  // direction.reflect(normal)
       child.ray = {ovx, ovy, ovz, ray.dx - hx * two_dot, ray.dy - hy * two_dot, ray.dz - hz * two_dot};
       child.weight = cur.weight * w_reflect;
+      RTC_SET_CODE(child, 2u * cur.code);
+#ifdef RTC_GLOSS_TU
+      if (rough_r > 0.0) {
+        const GlossDir g = gloss_scatter(gloss_h, child.code, rough_r, child.ray.dx, child.ray.dy, child.ray.dz, nx, ny, nz, false);
+        child.ray.dx = g.x;
+        child.ray.dy = g.y;
+        child.ray.dz = g.z;
+      }
+#endif
       it_secondary++;
     }
     if (do_refract) {
@@ -3681,6 +3776,15 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
       p.ray = {unx, uny, unz, hx * k - ex * n_ratio, hy * k - ey * n_ratio, hz * k - ez * n_ratio};
       p.weight = cur.weight * w_refract;
       p.remaining = cur.remaining - 1u;
+      RTC_SET_CODE(p, 2u * cur.code + 1u);
+#ifdef RTC_GLOSS_TU
+      if (rough_t > 0.0) {
+        const GlossDir g = gloss_scatter(gloss_h, p.code, rough_t, p.ray.dx, p.ray.dy, p.ray.dz, nx, ny, nz, true);
+        p.ray.dx = g.x;
+        p.ray.dy = g.y;
+        p.ray.dz = g.z;
+      }
+#endif
       it_secondary++;
       if (do_reflect) {  // both children: the reflection continues in registers, the refraction waits
         if constexpr (COOP) {
@@ -3828,7 +3932,8 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
 // The kernels.  rtc_motion.hip includes this file with RTC_MOTION_TU defined and gets the motion kernels alone: a
 // translation unit of their own, so that this one compiles in the time and to the code it did; rtc_spot.hip likewise
 // with RTC_SPOT_TU and the spot kernels, rtc_bump.hip with RTC_BUMP_TU and the bump kernels, rtc_torus.hip with RTC_TORUS_TU
-// and the torus kernels, rtc_meshuv.hip with RTC_MESHUV_TU (and, with it, RTC_TORUS_TU) and the meshuv kernels.  rtc_kernels_ext.hip
+// and the torus kernels, rtc_meshuv.hip with RTC_MESHUV_TU (and, with it, RTC_TORUS_TU) and the meshuv kernels, rtc_gloss.hip
+// with RTC_GLOSS_TU (and, with it, both of those) and the gloss kernels.  rtc_kernels_ext.hip
 // includes it with RTC_EXT_TU defined: in the -DRTC_PROFILE diagnostic build, whose instrumented walk makes this unit's
 // compile about a third longer, it gets the csg / texture-map, flat and area-light kernels (rtc_render_kernel_ext to
 // rtc_render_kernel_area_bigworld below), so that neither unit takes the time of all of them.  The product build keeps
@@ -4701,6 +4806,29 @@ rtc_render_kernel_bump_bigworld(const DevScene S, const DevCamera cam, const Dev
                                                                             spots, bumps);
 }
 
+#elif defined(RTC_GLOSS_TU)
+
+// Glossy reflection and refraction (rtc_scene_set_gloss): the meshuv walk with every ray's path code in
+// its Pending, the child directions of a rough material scattered, and the roughness rows (DevGloss) as one more argument;
+// one pair for every world, tori and textured meshes included.  Every other kernel is compiled without it.
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_gloss(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                        double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                        const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots, const DevBumps bumps,
+                        const DevMeshUvs muv, const DevGloss gloss) {
+  render_body<true, true, 0, 2, false, true, true, true, true, true, true, true, true, true>(S, cam, map, max_depth, out, stats, next_stats,
+                                                                                             area, smp, mo, spots, bumps, muv, gloss);
+}
+
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_gloss_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                 double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                 const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                 const DevBumps bumps, const DevMeshUvs muv, const DevGloss gloss) {
+  render_body<false, true, 0, 2, false, true, true, true, true, true, true, true, true, true>(S, cam, map, max_depth, out, stats, next_stats,
+                                                                                              area, smp, mo, spots, bumps, muv, gloss);
+}
+
 #elif defined(RTC_MESHUV_TU)
 
 // UV-mapped mesh textures (RTC_TEX_MESH): the torus walk with the hit's triangle and barycentrics
@@ -4746,4 +4874,4 @@ rtc_render_kernel_torus_bigworld(const DevScene S, const DevCamera cam, const De
                                                                                   smp, mo, spots, bumps);
 }
 
-#endif  // RTC_MOTION_TU / RTC_SPOT_TU / RTC_BUMP_TU / RTC_MESHUV_TU / RTC_TORUS_TU
+#endif  // RTC_MOTION_TU / RTC_SPOT_TU / RTC_BUMP_TU / RTC_GLOSS_TU / RTC_MESHUV_TU / RTC_TORUS_TU

@@ -119,12 +119,21 @@ struct Flattener {
       appendBits(key, bump, 4);
       appendBits(key, &m.bump.inverse.d[0][0], 12);
     }
+    // (a material with a "roughness" is a row of its own only when a value is non-zero; with zeros, or without the key, the
+    // key is as before)
+    out.gloss_present = out.gloss_present || m.roughness.present;
+    if (m.roughness.reflection != 0.0 || m.roughness.transmission != 0.0) {
+      const double rough[2] = {m.roughness.reflection, m.roughness.transmission};
+      appendBits(key, rough, 2);
+    }
     auto it = material_ids.find(key);
     if (it != material_ids.end()) return it->second;
     const uint32_t id = static_cast<uint32_t>(out.mat_pattern.size());
     out.mat_params.insert(out.mat_params.end(), params, params + RTC_MAT_STRIDE);
     out.mat_pattern.push_back(pat);
     out.mat_bump.push_back(m.bump);
+    out.mat_gloss.push_back(m.roughness.reflection);
+    out.mat_gloss.push_back(m.roughness.transmission);
     material_ids.emplace(std::move(key), id);
     return id;
   }

@@ -26,6 +26,8 @@ struct FlatScene {
   std::vector<double> tri_uv;  // [n_tris][6]: each triangle's texture row (rtch_scene_mesh_uvs; not part of rtc_scene_desc)
   std::vector<double> mat_params;
   std::vector<uint32_t> mat_pattern;
+  std::vector<double> mat_gloss;  // [n_materials][2]: each row's "roughness" (reflection, transmission) (rtch_scene_gloss; not part of rtc_scene_desc)
+  bool gloss_present = false;     // some material of the scene has the "roughness" key
   std::vector<Bump> mat_bump;  // [n_materials]: each row's "normal-perturbation" (rtch_scene_bumps; not part of rtc_scene_desc)
   std::vector<uint8_t> pat_kind;
   std::vector<double> pat_inv, pat_rgb;

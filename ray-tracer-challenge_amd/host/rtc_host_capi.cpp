@@ -134,6 +134,23 @@ int rtch_scene_bumps(void* h, uint8_t* kind, double* amplitude, uint32_t* octave
   });
 }
 
+// The materials' "roughness" (DESIGN.md section 20), in mat_* order, and the camera's "gloss-seed", as rtc_scene_set_gloss
+// takes them; *present: some material of the file has the key.
+int rtch_scene_gloss(void* h, double* reflection, double* transmission, uint64_t* seed, int* present, uint32_t n) {
+  return guarded([&] {
+    const HostScene* hs = static_cast<HostScene*>(h);
+    if (n != hs->desc.n_materials)
+      throw rtc::Error("InvalidArgument", "gloss: n " + std::to_string(n) + ", the scene has " + std::to_string(hs->desc.n_materials) + " materials");
+    if (n != 0u && (!reflection || !transmission)) throw rtc::Error("InvalidArgument", "gloss: null argument");
+    for (uint32_t i = 0; i < n; ++i) {  // (mat_* order)
+      reflection[i] = hs->flat.mat_gloss[2ull * i + 0];
+      transmission[i] = hs->flat.mat_gloss[2ull * i + 1];
+    }
+    if (seed) *seed = hs->info.sampling.gloss_seed;
+    if (present) *present = hs->flat.gloss_present ? 1 : 0;
+  });
+}
+
 // The triangles' texture rows (RTC_TEX_MESH), in tri_* order, as rtc_scene_set_mesh_uvs takes them.
 int rtch_scene_mesh_uvs(void* h, double* uv, uint32_t n) {
   return guarded([&] {
@@ -247,6 +264,13 @@ int rtch_scene_render(void* h, uint32_t width, uint32_t height, uint32_t max_dep
         for (const double x : rows) any = any || x != 0.0;
         const rtc_mesh_uvs mu{hs->desc.n_tris, rows.data()};
         if (any) st = rtc_scene_set_mesh_uvs(scene, &mu);
+      }
+      if (st == RTC_OK && hs->flat.gloss_present) {  // (the materials' roughness; all zero: the handle as it is)
+        const uint32_t nm = hs->desc.n_materials;
+        std::vector<double> refl(nm), trans(nm);
+        for (uint32_t i = 0; i < nm; ++i) refl[i] = hs->flat.mat_gloss[2ull * i], trans[i] = hs->flat.mat_gloss[2ull * i + 1];
+        const rtc_gloss gl{nm, refl.data(), trans.data(), hs->info.sampling.gloss_seed};
+        st = rtc_scene_set_gloss(scene, &gl);
       }
       const rtc::CameraSampling& cs = hs->info.sampling;
       if (cs.adaptive && st == RTC_OK) {  // (adaptive sampling: each tile's mean after its own passes, section 15)

@@ -424,10 +424,31 @@ Bump parseBump(const Value& cfg) {
   return b;
 }
 
+// A material's "roughness" (not in the reference): a number, meaning both values, or
+// {"reflection": a, "transmission": b} (either may be absent: 0); each finite and in [0, 1].
+Roughness parseRoughness(const Value& cfg) {
+  auto one = [](const Value& v, const char* key) {
+    if (v.type != Value::Number) throw Error("InvalidData", std::string(key) + ": a number in [0, 1]");
+    const double x = asFloat(v, key);
+    if (!(std::isfinite(x) && x >= 0.0 && x <= 1.0)) throw Error("InvalidData", std::string(key) + ": a number in [0, 1]");
+    return x;
+  };
+  Roughness r;
+  r.present = true;
+  if (cfg.type == Value::Object) {
+    checkFields(cfg, {"reflection", "transmission"}, "roughness");
+    if (const Value* v = presentField(cfg, "reflection")) r.reflection = one(*v, "roughness.reflection");
+    if (const Value* v = presentField(cfg, "transmission")) r.transmission = one(*v, "roughness.transmission");
+  } else {
+    r.reflection = r.transmission = one(cfg, "roughness");
+  }
+  return r;
+}
+
 Material parseMaterial(const Value& cfg, const std::optional<Material>& inherited, const FileLoader& load_file_data) {
   requireObject(cfg, "material");
   checkFields(cfg, {"pattern", "ambient", "diffuse", "specular", "shininess", "reflective", "transparency",
-                    "refractive-index", "normal-perturbation"}, "material");
+                    "refractive-index", "normal-perturbation", "roughness"}, "material");
   Material mat = inherited ? *inherited : Material{};
   auto present = [&](const char* k) -> const Value* {
     const Value* v = cfg.find(k);
@@ -442,6 +463,7 @@ Material parseMaterial(const Value& cfg, const std::optional<Material>& inherite
   if (auto* v = present("transparency")) mat.transparency = asFloat(*v, "transparency");
   if (auto* v = present("refractive-index")) mat.refractive_index = asFloat(*v, "refractive-index");
   if (auto* v = present("normal-perturbation")) mat.bump = parseBump(*v);
+  if (auto* v = present("roughness")) mat.roughness = parseRoughness(*v);
   return mat;
 }
 
@@ -692,7 +714,7 @@ SceneInfo parseScene(const std::string& scene_json, const FileLoader& load_file_
   info.camera.setTransform(Matrix4::viewTransform(from, to, up));
   if (const Value* smp = cam.find("sampling")) {  // (not in the reference: anti-aliasing and focal blur, every key optional)
     requireObject(*smp, "sampling");
-    checkFields(*smp, {"grid", "jitter", "aperture", "focal-distance", "seed", "passes", "adaptive"}, "sampling");
+    checkFields(*smp, {"grid", "jitter", "aperture", "focal-distance", "seed", "passes", "adaptive", "gloss-seed"}, "sampling");
     CameraSampling& s = info.sampling;
     if (const Value* v = smp->find("grid")) {
       const size_t g = asUsize(*v, "grid");
@@ -711,6 +733,7 @@ SceneInfo parseScene(const std::string& scene_json, const FileLoader& load_file_
       if (!(s.focal_distance > 0.0)) throw Error("InvalidData", "sampling: from == to, and no focal-distance");
     }
     if (const Value* v = smp->find("seed")) s.seed = static_cast<uint64_t>(asUsize(*v, "seed"));
+    if (const Value* v = smp->find("gloss-seed")) s.gloss_seed = static_cast<uint64_t>(asUsize(*v, "gloss-seed"));  // (section 20)
     if (const Value* v = smp->find("passes")) {  // (progressive rendering, DESIGN.md section 13: sample passes 0 .. passes-1)
       const size_t n = asUsize(*v, "passes");
       const size_t most = RTC_SAMPLING_INDEX_LIMIT / (static_cast<size_t>(s.grid) * s.grid);

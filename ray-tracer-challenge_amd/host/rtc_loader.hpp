@@ -31,6 +31,7 @@ struct CameraSampling {
   double threshold = 0.0;
   uint32_t min_passes = 4;
   uint32_t tile_w = 16, tile_h = 16;
+  uint64_t gloss_seed = 0;  // "gloss-seed" (section 20): rtc_gloss::seed of the materials' "roughness"
 };
 
 // A "spot-light" entry's cone (not in the reference), as rtc_scene_set_spots takes it: the axis as

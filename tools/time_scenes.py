@@ -43,6 +43,10 @@ with a mesh map runs them anyway, with its triangles' texture rows (HostScene.me
 --mesh-as-planar: every mesh map of the description (RTC_TEX_MESH) becomes a planar map in a copy of it - the same table
 entries, one per mesh, so the handle keeps its tables and its kernel form; with --meshuv the same kernels run: what the
 mapping-4 branch costs against the planar one on the same scene.
+--gloss MATERIAL=refl[,trans] (repeatable): material row MATERIAL (mat_* order) gets that reflection roughness and (0 without)
+that transmission roughness (rtc_scene_set_gloss; glossy reflection and refraction); on a scene file
+with "roughness" entries those are applied first; --gloss off applies none.  Option gloss_kernels=1 times the gloss kernels
+without a rough material.  With --passes the noise run has the same table.
 --adaptive threshold[,min,tile]: adaptive sampling at up to --max-passes (64) passes, min passes 4 and
 16 x 16 tiles by default, with the --sampling of the frames: prints the rounds and tile-passes of a run against
 T * max_passes, its time (a second run, end to end on the host) against uniform progressive passes (render_device +
@@ -82,6 +86,7 @@ ap.add_argument("--passes", type=int, default=-1)
 ap.add_argument("--motion", action="append", default=[])
 ap.add_argument("--spot", action="append", default=[])
 ap.add_argument("--bump", action="append", default=[])
+ap.add_argument("--gloss", action="append", default=[])
 ap.add_argument("--torus", action="store_true")
 ap.add_argument("--meshuv", action="store_true")
 ap.add_argument("--mesh-as-planar", action="store_true")
@@ -104,6 +109,21 @@ if args.torus:  # (the torus kernels on a scene without a torus: what carrying t
     rtc.set_option("torus_kernels", 1.0)
 if args.meshuv:  # (the meshuv kernels on a scene without a mesh map: what carrying the flag costs)
     rtc.set_option("meshuv_kernels", 1.0)
+
+
+def gloss_table(hs):
+    """the scene file's "roughness" rows with the --gloss entries over them; None: no table (--gloss off, or nothing to set)"""
+    if "off" in args.gloss or not (args.gloss or hs.gloss() is not None):
+        return None
+    import numpy as np
+    n = hs.desc.n_materials
+    gloss = hs.gloss() or {"reflection": np.zeros(n), "transmission": np.zeros(n), "seed": 0}
+    for g in args.gloss:
+        m, v = g.split("=")
+        f = [float(x) for x in v.split(",")]
+        gloss["reflection"][int(m)] = f[0]
+        gloss["transmission"][int(m)] = f[1] if len(f) > 1 else 0.0
+    return gloss
 
 
 def light_table(hs, how):
@@ -299,6 +319,9 @@ for name, w, h, depth in cases:
                 gpu.set_bumps(bumps)
         if hs.mesh_uvs() is not None:  # (the triangles' texture rows: what a mesh map reads)
             gpu.set_mesh_uvs(hs.mesh_uvs())
+        gloss = gloss_table(hs)
+        if gloss is not None:
+            gpu.set_gloss(gloss)
         for i in range(args.settle):
             gpu.render_device(cam, canvas.data_ptr(), depth, None, stream.cuda_stream)
         torch.cuda.synchronize()
@@ -323,7 +346,7 @@ for name, w, h, depth in cases:
     if delta is not None: line += f" maxdelta {delta:.2e}"
     if args.lights or args.spot or "spot_kernels=1" in args.option:
         line += f" shadow_traced {st['shadow_traced']} ns/shadow-ray {min(ts) * 1e6 / max(1, st['shadow_traced']):.3f}"
-    if args.sampling or args.option or args.passes >= 0 or args.motion or args.spot or args.bump or args.torus or args.meshuv:
+    if args.sampling or args.option or args.passes >= 0 or args.motion or args.spot or args.bump or args.torus or args.meshuv or args.gloss:
         line += f" primary {st['primary']} ns/primary-ray {min(ts) * 1e6 / max(1, st['primary']):.3f}"
     if acc:
         ms, copy_ms, nbytes = min(a[0] for a in acc), min(a[1] for a in acc), acc[0][2]
@@ -332,6 +355,10 @@ for name, w, h, depth in cases:
         gpu = rtc.GpuScene(hs.desc, lights=table)
         if args.sampling:
             gpu.set_sampling(int(sv[0]), True, sv[1] if len(sv) > 1 else 0.0, sv[2] if len(sv) > 2 else 1.0)
+        if hs.bumps() is not None and "off" not in args.bump: gpu.set_bumps(hs.bumps())
+        if hs.spots() is not None: gpu.set_spots(hs.spots())
+        if hs.mesh_uvs() is not None: gpu.set_mesh_uvs(hs.mesh_uvs())
+        if gloss_table(hs) is not None: gpu.set_gloss(gloss_table(hs))
         prog = rtc.Progressive(gpu, cam, depth)
         noise = {}
         for i in range(1, 65):
