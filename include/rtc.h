@@ -570,6 +570,63 @@ typedef struct rtc_gloss {
  */
 int rtc_scene_set_gloss(rtc_scene *scene, const rtc_gloss *gloss);
 
+/* ---- ambient occlusion: hemisphere rays dim a material's ambient term ---- */
+/*
+ * A material row has one value, `radius`, finite and >= 0; 0 is the material's ambient term as it is.  The table also has
+ * `samples` (1 .. RTC_OCCLUSION_MAX_SAMPLES) and a `seed`.
+ *
+ * The step.  At every hit - of a primary or of a secondary ray - whose material row has radius > 0 and whose
+ * material.ambient != 0.0, once, before the lights:
+ *   for k = 0 .. samples - 1:
+ *     s  = the gloss sampler's rule: the first of 32 triples (a, b, c), each component 2.0 * J(3 t + i) - 1.0 with
+ *          t = 0 .. 31 and i = 0, 1, 2, for which q = ((a * a) + (b * b)) + (c * c) <= 1.0
+ *     if no triple is accepted, or q == 0.0:  d = ng
+ *     else  r = sqrt(q);  u = (a / r, b / r, c / r)
+ *           e = ng + u                                          (per component)
+ *           m = sqrt((e.x * e.x + e.y * e.y) + e.z * e.z)
+ *           d = e / m when m != 0, else ng                      (tuple.zig's normalize)
+ *     occluded_k = what World.isShadowed finds for a ray from over_point along d with distance = radius: the same
+ *                  intersections, the same casts_shadow filter, the same comparison of t with distance; under motion at the
+ *                  ray's shutter time, like every shadow ray
+ *   vis = double(samples - count(occluded)) / double(samples)
+ *   ka  = material.ambient * vis
+ * ng is the geometric normal after its `inside` flip - the one over_point, under_point and the gloss side rule use -, not a
+ * bumped shading normal.  ng + a unit vector is a cosine-weighted direction of ng's hemisphere: no side rule is needed.  ka
+ * takes material.ambient's place in Material.lighting for every light of that hit, point, spot and area lights alike;
+ * vis == 1.0 leaves the bits as they are.  Only + - * / sqrt and comparisons are added, each correctly rounded, in the
+ * order written.
+ *
+ * Draws.  rtc_scene_set_gloss's functions with a key of their own:
+ *   J(axis) = (rtc_mix64(h + GOLD * (((word << 8) | axis) + 1)) >> 11) * 2^-53,   word = (k << 17) | code
+ *   h       = rtc_mix64(key + GOLD * (((p << 32) | (g << 8)) + 1))
+ *   key     = rtc_mix64(seed ^ 0xA4093822299F31D0)
+ * code is the path code of the ray that made the hit (below 2^17), k the sample (below 64: word is below 2^23), p the
+ * whole-image pixel, g the global sample index.  The draws do not depend on bands, tiles, clones, the lane or the order;
+ * they are new for every camera sample and every pass, so progressive and adaptive rendering converge the term.  Like gloss
+ * and the lens, occlusion is always sampled.
+ *
+ * Counts.  Each such hit adds `samples` to shadow_calls and `samples` to shadow_traced.  A hit whose row is 0, or whose
+ * material.ambient == 0.0, draws nothing and counts nothing: its pixels have the bits they have without a table.
+ */
+#define RTC_OCCLUSION_MAX_SAMPLES 64u
+
+typedef struct rtc_occlusion {
+  uint32_t n_materials; /* the handle's material count (rtc_scene_desc::n_materials) */
+  const double *radius; /* [n_materials], each finite and >= 0; NULL: all zeros */
+  uint32_t samples;     /* hemisphere rays per hit, 1 .. RTC_OCCLUSION_MAX_SAMPLES */
+  uint64_t seed;        /* of the draws (above) */
+} rtc_occlusion;
+
+/*
+ * This handle's occlusion radii for every render entry point.  Validated before anything changes: RTC_ERR_INVALID_ARGUMENT
+ * for a radius that is not finite or below 0, for samples outside 1 .. RTC_OCCLUSION_MAX_SAMPLES, and then for an
+ * n_materials other than the handle's; the previous table stays in force.  NULL, or a table whose every row is zero, gives
+ * the handle its previous kernels back.  A clone starts with its source's table; rtc_render's band clones follow.  A handle
+ * with a radius renders with the occlusion kernels (rtc_render_kernel_occl, _occl_bigworld).  librtc_multi renders without
+ * occlusion.  rtc_scene_desc and RTC_ABI_VERSION are as they were.
+ */
+int rtc_scene_set_occlusion(rtc_scene *scene, const rtc_occlusion *occlusion);
+
 /* ---- adaptive sampling: progressive passes only for tiles still noisy ---- */
 #define RTC_ADAPTIVE_MAX_TILE 1024u
 

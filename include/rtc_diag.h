@@ -38,7 +38,9 @@ extern "C" {
  * torus, so that their images can be held to the bump kernels'), "meshuv_kernels" (!= 0: the meshuv kernels even on a
  * handle without a texture map of mapping RTC_TEX_MESH, so that their images can be held to the handle's ordinary kernels'),
  * "gloss_kernels" (!= 0: the gloss kernels even on a handle without a rough material, every roughness row zero, so that
- * their images can be held to the handle's ordinary kernels').
+ * their images can be held to the handle's ordinary kernels'), "occlusion_kernels" (!= 0: the occlusion kernels even on a
+ * handle without an occlusion radius, every radius row zero, so that their images can be held to the handle's ordinary
+ * kernels').
  * RTC_ERR_INVALID_ARGUMENT for a name the library does not know.
  * (The library reads no environment variables.)
  */

@@ -22,7 +22,8 @@
  *                        rtch_scene_spots, through rtc_scene_set_spots; its materials' normal perturbation,
  *                        rtch_scene_bumps, through rtc_scene_set_bumps; its triangles' texture rows,
  *                        rtch_scene_mesh_uvs, through rtc_scene_set_mesh_uvs; its materials' roughness,
- *                        rtch_scene_gloss, through rtc_scene_set_gloss)
+ *                        rtch_scene_gloss, through rtc_scene_set_gloss; its materials' occlusion radii,
+ *                        rtch_scene_occlusion, through rtc_scene_set_occlusion)
  *
  * Every function that returns int returns 0 on success; otherwise rtch_last_error()
  * holds "<ZigStyleErrorName>: detail" (thread-local).
@@ -90,6 +91,12 @@ int rtch_scene_mesh_uvs(void *handle, double *out, uint32_t n);
  * value is non-zero.  *present: 1 when a material of the file has the key.  Pass them to rtc_scene_set_gloss.
  * rtch_scene_render applies them. */
 int rtch_scene_gloss(void *handle, double *reflection, double *transmission, uint64_t *seed, int *present, uint32_t n);
+/* The materials' "ambient-occlusion" (DESIGN.md section 21), in mat_* order: a number (the radius) or {"radius": r},
+ * finite and >= 0; *samples and *seed, the camera's "sampling": {"occlusion-samples": n, "occlusion-seed": s} (1 and 0
+ * without).  n must be the description's n_materials.  A material with the key is a mat_* row of its own only when the
+ * value is non-zero.  *present: 1 when a material of the file has the key.  Pass them to rtc_scene_set_occlusion.
+ * rtch_scene_render applies them. */
+int rtch_scene_occlusion(void *handle, double *radius, uint32_t *samples, uint64_t *seed, int *present, uint32_t n);
 int rtch_scene_camera(void *handle, uint32_t width, uint32_t height, rtc_camera *out);
 int rtch_camera_rotate(void *handle, double angle);
 int rtch_camera_move(void *handle, double distance);

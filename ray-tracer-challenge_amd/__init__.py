@@ -220,7 +220,8 @@ BUMP_NONE, BUMP_NOISE, BUMP_RIPPLES = 0, 1, 2  # RTC_BUMP_*
 # leaf kinds (rtc.h); RTC_TORUS: a ring torus, its major and minor radius in cyl_min / cyl_max
 RTC_SPHERE, RTC_PLANE, RTC_CUBE, RTC_CYLINDER, RTC_TRIANGLE, RTC_SMOOTH_TRIANGLE, RTC_CONE, RTC_TORUS = range(8)
 # the options that select a kernel family on a handle that does not need it (set_option; tests and tools/time_scenes.py)
-KERNEL_OPTIONS = ("sampling_kernels", "motion_kernels", "spot_kernels", "bump_kernels", "torus_kernels", "meshuv_kernels", "gloss_kernels")
+KERNEL_OPTIONS = ("sampling_kernels", "motion_kernels", "spot_kernels", "bump_kernels", "torus_kernels", "meshuv_kernels", "gloss_kernels",
+                  "occlusion_kernels")
 # texture mappings (rtc.h); RTC_TEX_MESH: (u, v) from the hit triangle's texture row
 RTC_TEX_SPHERICAL, RTC_TEX_PLANAR, RTC_TEX_CYLINDRICAL, RTC_TEX_CUBIC, RTC_TEX_MESH = range(5)
 BUMP_MAX_OCTAVES = 16  # RTC_BUMP_MAX_OCTAVES
@@ -253,6 +254,31 @@ def gloss_struct(gloss):
     g = Gloss(n, r.ctypes.data_as(C.POINTER(C.c_double)) if r is not None else None,
               t.ctypes.data_as(C.POINTER(C.c_double)) if t is not None else None, int(gloss.get("seed", 0)))
     return g, (r, t)
+
+
+OCCLUSION_MAX_SAMPLES = 64  # RTC_OCCLUSION_MAX_SAMPLES
+
+
+class Occlusion(C.Structure):
+    """struct rtc_occlusion (include/rtc.h): an occlusion radius per material row, the rays per hit and the draws' seed."""
+
+    _fields_ = [("n_materials", C.c_uint32), ("radius", C.POINTER(C.c_double)), ("samples", C.c_uint32), ("seed", C.c_uint64)]
+
+
+def occlusion_struct(occlusion):
+    """(Occlusion, the array it points into) of a dict of "radius" ((n,); None: all zeros, with "n_materials"), and optional
+    "samples" (1) and "seed" (0) (GpuScene.set_occlusion); the array must outlive the struct's use."""
+    r = occlusion.get("radius")
+    if r is None:
+        n = int(occlusion["n_materials"])
+    else:
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        if r.ndim != 1:
+            raise ValueError(f"occlusion: a radius array of shape {r.shape}, (n,) expected")
+        n = r.shape[0]
+    o = Occlusion(n, r.ctypes.data_as(C.POINTER(C.c_double)) if r is not None else None, int(occlusion.get("samples", 1)),
+                  int(occlusion.get("seed", 0)))
+    return o, r
 
 
 class Bump(C.Structure):
@@ -295,13 +321,14 @@ RTC_SYMBOLS = ["rtc_scene_create", "rtc_scene_clone", "rtc_scene_destroy", "rtc_
                "rtc_scene_create_with_lights", "rtc_scene_set_light_seed", "rtc_scene_set_sampling",
                "rtc_scene_set_sample_pass", "rtc_scene_accumulate_device", "rtc_scene_set_motion",
                "rtc_scene_adaptive_begin_device", "rtc_scene_adaptive_accumulate_device", "rtc_scene_adaptive_step", "rtc_render_adaptive",
-               "rtc_scene_set_spots", "rtc_scene_set_bumps", "rtc_scene_set_mesh_uvs", "rtc_scene_set_gloss"]
+               "rtc_scene_set_spots", "rtc_scene_set_bumps", "rtc_scene_set_mesh_uvs", "rtc_scene_set_gloss",
+               "rtc_scene_set_occlusion"]
 # (... and include/rtc_diag.h: diagnostics and tuning, for the tests, bench.py and tools/)
 RTC_DIAG_SYMBOLS = ["rtc_set_option", "rtc_last_kernel_name", "rtc_get_schedule", "rtc_get_chunk_times", "rtc_diag_build_tables", "rtc_diag_root_boxes"]
 HOST_SYMBOLS = ["rtch_last_error", "rtch_scene_load", "rtch_scene_free", "rtch_scene_desc", "rtch_scene_camera",
                 "rtch_camera_rotate", "rtch_camera_move", "rtch_camera_make", "rtch_canvas_ppm", "rtch_canvas_rgba8", "rtch_scene_render", "rtch_set_loader_threads",
                 "rtch_scene_lights", "rtch_scene_sampling", "rtch_scene_passes", "rtch_scene_motion", "rtch_scene_adaptive",
-                "rtch_scene_spots", "rtch_scene_bumps", "rtch_scene_mesh_uvs", "rtch_scene_gloss"]
+                "rtch_scene_spots", "rtch_scene_bumps", "rtch_scene_mesh_uvs", "rtch_scene_gloss", "rtch_scene_occlusion"]
 
 MULTI_SYMBOLS = ["rtc_multi_create", "rtc_multi_destroy", "rtc_multi_render", "rtc_multi_render_rgba8", "rtc_multi_render_device", "rtc_multi_render_rgba8_device",
                  "rtc_multi_synchronize", "rtc_multi_stream", "rtc_multi_get_stats", "rtc_multi_balance", "rtc_multi_last_error"]
@@ -365,6 +392,7 @@ def hip_lib():
         lib.rtc_scene_set_bumps.argtypes = [C.c_void_p, C.POINTER(Bump)]
         lib.rtc_scene_set_mesh_uvs.argtypes = [C.c_void_p, C.POINTER(MeshUvs)]
         lib.rtc_scene_set_gloss.argtypes = [C.c_void_p, C.POINTER(Gloss)]
+        lib.rtc_scene_set_occlusion.argtypes = [C.c_void_p, C.POINTER(Occlusion)]
         lib.rtc_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.POINTER(Adaptive), C.c_void_p, C.c_void_p]
         lib.rtc_scene_destroy.argtypes = [C.c_void_p]
         lib.rtc_scene_destroy.restype = None
@@ -421,6 +449,7 @@ def host_lib():
         lib.rtch_scene_bumps.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), _dp, C.POINTER(C.c_uint32), _dp, _dp, C.c_uint32]
         lib.rtch_scene_mesh_uvs.argtypes = [C.c_void_p, _dp, C.c_uint32]
         lib.rtch_scene_gloss.argtypes = [C.c_void_p, _dp, _dp, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.c_uint32]
+        lib.rtch_scene_occlusion.argtypes = [C.c_void_p, _dp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.c_uint32]
         lib.rtch_scene_adaptive.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(Adaptive)]
         lib.rtch_scene_camera.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Camera)]
         lib.rtch_camera_rotate.argtypes = [C.c_void_p, C.c_double]
@@ -627,6 +656,18 @@ class HostScene:
         out["seed"] = seed.value
         return out if present.value else None
 
+    def occlusion(self):
+        """The materials' "ambient-occlusion" radii (rtch_scene_occlusion), in mat_* order, and the camera's
+        "occlusion-samples" and "occlusion-seed": a dict of "radius" (n,), "samples" and "seed" - what
+        GpuScene.set_occlusion takes -, or None when no material of the file has the key."""
+        n = self.desc.n_materials
+        out = {"radius": np.zeros(n)}
+        samples, seed, present = C.c_uint32(), C.c_uint64(), C.c_int()
+        _check_host(host_lib().rtch_scene_occlusion(self._h, out["radius"].ctypes.data_as(_dp), C.byref(samples), C.byref(seed),
+                                                    C.byref(present), n))
+        out["samples"], out["seed"] = samples.value, seed.value
+        return out if present.value else None
+
     def adaptive(self):
         """The camera's "sampling": {"adaptive": ...} of the scene file (rtch_scene_adaptive): an Adaptive whose max_passes
         is "passes", or None when the file has none."""
@@ -752,6 +793,15 @@ class GpuScene:
             return
         g, _keep = gloss_struct(gloss)
         _check_hip(hip_lib().rtc_scene_set_gloss(self._s, C.byref(g)))
+
+    def set_occlusion(self, occlusion):
+        """rtc_scene_set_occlusion: a dict of "radius" ((n_materials,)) and optional "samples" (1) and "seed" (0)
+        (HostScene.occlusion()); None: no occlusion - as every row zero, the handle's previous kernels."""
+        if occlusion is None:
+            _check_hip(hip_lib().rtc_scene_set_occlusion(self._s, None))
+            return
+        o, _keep = occlusion_struct(occlusion)
+        _check_hip(hip_lib().rtc_scene_set_occlusion(self._s, C.byref(o)))
 
     def accumulate_device(self, accum, stream=None):
         """rtc_scene_accumulate_device: an Accum, enqueued on `stream` (None: the handle's own) after this handle's renders."""

@@ -377,6 +377,19 @@ __host__ __device__ inline double rtc_gloss_jitter(unsigned long long h, uint32_
   return static_cast<double>(rtc_mix64(h + 0x9E3779B97F4A7C15ull * (c + 1ull)) >> 11) * 0x1.0p-53;
 }
 
+// Ambient occlusion (rtc_scene_set_occlusion): the extra argument of the occlusion kernels only.  One
+// double per material, in mat_* order: the radius (0: the material's ambient term as it is); every row under the
+// "occlusion_kernels" option on a handle without a table is zero.  key = rtc_mix64(seed ^ RTC_OCCLUSION_SALT); the draws
+// are rtc_gloss_sample_key's and rtc_gloss_jitter's, at word (k << RTC_OCCLUSION_SAMPLE_SHIFT) | code for sample k of the
+// hit of the ray with path code `code` (a code is below 2^17, k below 64: the word is below 2^23).
+#define RTC_OCCLUSION_SALT 0xA4093822299F31D0ull
+#define RTC_OCCLUSION_SAMPLE_SHIFT 17u
+struct DevOcclusion {
+  const double* __restrict__ row;  // [n_materials]
+  unsigned long long key;
+  uint32_t samples;  // 1 .. RTC_OCCLUSION_MAX_SAMPLES
+};
+
 struct DevCamera {
   double half_width, half_height, pixel_size;
   double inv[12];  // rows 0..2 of Camera._inverse_transform

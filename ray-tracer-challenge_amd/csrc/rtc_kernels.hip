@@ -2550,6 +2550,37 @@ __device__ __noinline__ GlossDir gloss_scatter(unsigned long long h, uint32_t co
   return r;
 }
 #endif
+#ifdef RTC_OCCL_TU
+// (OCCL, rtc.h's rtc_scene_set_occlusion) the direction of one occlusion sample at a hit with
+// geometric normal ng: u is the first of RTC_GLOSS_DRAWS draws of the sample's own word (h: the camera sample's hash, word:
+// (k << 17) | the hit ray's path code) inside the unit ball, normalised; e = ng + u, d = e / |e| - a cosine-weighted
+// direction of ng's hemisphere; no draw accepted, a draw at the centre or |e| == 0: ng.  Only + - * / sqrt and comparisons,
+// each correctly rounded, in the order of rtc.h.  The draws are made one triple at a time and never kept.  Out of line, by
+// value, as gloss_scatter: the walk's registers are not the sampler's, and nothing of it is live across the trace that
+// follows.  Compiled into the occlusion kernels' translation unit only.
+__device__ __noinline__ GlossDir occl_direction(unsigned long long h, uint32_t word, double ngx, double ngy, double ngz) {
+  GlossDir r{ngx, ngy, ngz};
+  for (uint32_t t = 0u; t < RTC_GLOSS_DRAWS; ++t) {
+    const double a = 2.0 * rtc_gloss_jitter(h, word, 3u * t + 0u) - 1.0;
+    const double b = 2.0 * rtc_gloss_jitter(h, word, 3u * t + 1u) - 1.0;
+    const double c = 2.0 * rtc_gloss_jitter(h, word, 3u * t + 2u) - 1.0;
+    const double q = ((a * a) + (b * b)) + (c * c);
+    if (q <= 1.0) {
+      if (q != 0.0) {
+        const double len = __builtin_sqrt(q);
+        const double ex = ngx + a / len, ey = ngy + b / len, ez = ngz + c / len;
+        const double m = __builtin_sqrt((ex * ex + ey * ey) + ez * ez);  // tuple.zig's normalize
+        if (m != 0.0) r = GlossDir{ex / m, ey / m, ez / m};
+      }
+      break;
+    }
+  }
+  return r;
+}
+#define RTC_KA(mat) occl_ka
+#else
+#define RTC_KA(mat) (mat).ambient
+#endif
 
 // (MS) a lane's sample word: the sample index, and whether the lane owns the pixel (deals its samples, step 1)
 #define RTC_SAMPLE_MASK 0xFFFFu
@@ -2584,15 +2615,19 @@ __device__ __noinline__ GlossDir gloss_scatter(unsigned long long h, uint32_t co
 // (GLOSS: rough materials whose reflected and refracted rays are scattered - DevGloss, the gloss kernels' extra argument;
 // a Pending carries its ray's path code, the draws come from gloss_scatter.  With MESHUV and everything below it, compiled
 // into the gloss kernels' translation unit only, under RTC_GLOSS_TU, which implies RTC_MESHUV_TU and RTC_TORUS_TU)
+// (OCCL: ambient occlusion - DevOcclusion, the occlusion kernels' extra argument: a material with a radius has its ambient
+// term scaled by the share of hemisphere rays that leave the hit unoccluded within that radius.  With GLOSS and everything
+// below it, compiled into the occlusion kernels' translation unit only, under RTC_OCCL_TU, which implies RTC_GLOSS_TU)
 template <bool LDS, bool CSG, int WORLD = 0, int WAVES = 2, bool COOP = false, bool BOX = true, bool AREA = false, bool MS = false,
-          bool MOTION = false, bool SPOT = false, bool BUMP = false, bool TORUS = false, bool MESHUV = false, bool GLOSS = false>
+          bool MOTION = false, bool SPOT = false, bool BUMP = false, bool TORUS = false, bool MESHUV = false, bool GLOSS = false,
+          bool OCCL = false>
 __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& cam, const DevPixelMap& map,
                                             const uint32_t max_depth, double* __restrict__ out,
                                             DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
                                             const DevAreaLights& area = DevAreaLights{}, const DevSampling& smp = DevSampling{},
                                             const DevMotion& mo = DevMotion{}, const DevSpots& spots = DevSpots{},
                                             const DevBumps& bumps = DevBumps{}, const DevMeshUvs& muv = DevMeshUvs{},
-                                            const DevGloss& gloss = DevGloss{}) {
+                                            const DevGloss& gloss = DevGloss{}, const DevOcclusion& occl = DevOcclusion{}) {
   static_assert(!AREA || !COOP, "the area kernels run no cooperative iterations");
   static_assert(!MS || !COOP, "the sampling kernels run no cooperative iterations");
   static_assert(!MOTION || (MS && AREA && WORLD == 0), "the motion kernels are the general area-sampling walk");
@@ -2617,6 +2652,13 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
 #else
   static_assert(!GLOSS, "rough materials are compiled in the gloss translation unit (rtc_gloss.hip) only");
   (void)gloss;
+#endif
+  static_assert(!OCCL || GLOSS, "the occlusion kernels are the gloss walk");
+#ifdef RTC_OCCL_TU
+  static_assert(OCCL, "the occlusion translation unit compiles the occlusion kernels only");
+#else
+  static_assert(!OCCL, "ambient occlusion is compiled in the occlusion translation unit (rtc_occlusion.hip) only");
+  (void)occl;
 #endif
   RTC_PRIO_PHASE(RTC_PRIO_WORK);
 #ifndef RTC_PROFILE
@@ -3422,6 +3464,37 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
     RTC_STAMP(11);
     const double eps = 1e-5;
     const double ovx = ptx + nx * eps, ovy = pty + ny * eps, ovz = ptz + nz * eps;  // over_point
+#ifdef RTC_OCCL_TU
+    // (OCCL) the hit's ambient factor, once, before the colour and the lights' temporaries exist: the material's radius is
+    // read per lane (mat_index is the lane's); only a lane with a radius and an ambient term forms the hash of its camera
+    // sample - the whole-image pixel and the global sample index, as the gloss block below - and traces `samples` shadow-type
+    // rays of that length from over_point, the area branch's call.  What the loop keeps is an integer count, so the factor
+    // does not depend on the order the rays ran in; every sample is a call of isShadowed and is traced.
+    double occl_ka = mats[mat_index].ambient;
+    if constexpr (OCCL) {
+      const double occl_radius = occl.row[mat_index];
+      if (occl_radius > 0.0 && occl_ka != 0.0) {
+        uint32_t opx, opy;
+        map_pixel(map, out_index, opx, opy);
+        const unsigned long long occl_h = rtc_gloss_sample_key(
+            occl.key, static_cast<unsigned long long>(opy) * cam.hsize + opx,
+            static_cast<unsigned long long>(smp.sample_base) + (*samp_word & RTC_SAMPLE_MASK));
+        uint32_t clear = 0u;
+        for (uint32_t k = 0u; k < occl.samples; ++k) {
+          const GlossDir od = occl_direction(occl_h, (k << RTC_OCCLUSION_SAMPLE_SHIFT) | cur.code, nx, ny, nz);
+          it_shadow_calls++;
+          it_shadow_traced++;
+          it_share++;
+          ShadowVisitor sv;
+          sv.distance = occl_radius;
+          Ray sray{ovx, ovy, ovz, od.x, od.y, od.z};
+          trace<CSG, WORLD, ShadowVisitor, TRAV, BOX, MOTION>(S, recs, cull, sray, sv, it_overflow, trav_stack, member, stride, mo.disp, tm);
+          clear += sv.shadowed ? 0u : 1u;
+        }
+        if (clear != occl.samples) occl_ka = occl_ka * (static_cast<double>(clear) / static_cast<double>(occl.samples));
+      }
+    }
+#endif
     // ---- World.shadeHit, lights loop (world.zig:89-96)
     double sr = 0.0, sg = 0.0, sb = 0.0;
     {
@@ -3519,7 +3592,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
               vz = ((A[2] + A[5] * fu) + A[8] * fv) - ovz;
             };
             const double er = color.r * A[9], eg = color.g * A[10], eb = color.b * A[11];  // effective_color
-            const double ka = mat.ambient;
+            const double ka = RTC_KA(mat);
             double lr_ = er * ka, lg_ = eg * ka, lb_ = eb * ka;
             double dr = 0.0, dg = 0.0, db = 0.0;
             if (shadow_matters) {
@@ -3632,7 +3705,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
         }
         // Material.lighting (material.zig:40-74)
         const double er = color.r * L[3], eg = color.g * L[4], eb = color.b * L[5];  // effective_color
-        const double ka = mat.ambient;
+        const double ka = RTC_KA(mat);
         double lr_ = er * ka, lg_ = eg * ka, lb_ = eb * ka;
         if (!shadowed) {
           double dr = 0.0, dg = 0.0, db = 0.0, pr = 0.0, pg = 0.0, pb = 0.0;
@@ -3933,7 +4006,8 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
 // translation unit of their own, so that this one compiles in the time and to the code it did; rtc_spot.hip likewise
 // with RTC_SPOT_TU and the spot kernels, rtc_bump.hip with RTC_BUMP_TU and the bump kernels, rtc_torus.hip with RTC_TORUS_TU
 // and the torus kernels, rtc_meshuv.hip with RTC_MESHUV_TU (and, with it, RTC_TORUS_TU) and the meshuv kernels, rtc_gloss.hip
-// with RTC_GLOSS_TU (and, with it, both of those) and the gloss kernels.  rtc_kernels_ext.hip
+// with RTC_GLOSS_TU (and, with it, both of those) and the gloss kernels, rtc_occlusion.hip with RTC_OCCL_TU (and, with it, those
+// three) and the occlusion kernels.  rtc_kernels_ext.hip
 // includes it with RTC_EXT_TU defined: in the -DRTC_PROFILE diagnostic build, whose instrumented walk makes this unit's
 // compile about a third longer, it gets the csg / texture-map, flat and area-light kernels (rtc_render_kernel_ext to
 // rtc_render_kernel_area_bigworld below), so that neither unit takes the time of all of them.  The product build keeps
@@ -4806,6 +4880,30 @@ rtc_render_kernel_bump_bigworld(const DevScene S, const DevCamera cam, const Dev
                                                                             spots, bumps);
 }
 
+#elif defined(RTC_OCCL_TU)
+
+// Ambient occlusion (rtc_scene_set_occlusion): the gloss walk with every hit's ambient term scaled by
+// the share of its hemisphere rays that are not occluded within the material's radius, and the radius rows (DevOcclusion)
+// as one more argument; one pair for every world, tori, textured meshes and rough materials included.  Every other kernel
+// is compiled without it.
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_occl(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                       double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                       const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots, const DevBumps bumps,
+                       const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl) {
+  render_body<true, true, 0, 2, false, true, true, true, true, true, true, true, true, true, true>(
+      S, cam, map, max_depth, out, stats, next_stats, area, smp, mo, spots, bumps, muv, gloss, occl);
+}
+
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_occl_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                const DevBumps bumps, const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl) {
+  render_body<false, true, 0, 2, false, true, true, true, true, true, true, true, true, true, true>(
+      S, cam, map, max_depth, out, stats, next_stats, area, smp, mo, spots, bumps, muv, gloss, occl);
+}
+
 #elif defined(RTC_GLOSS_TU)
 
 // Glossy reflection and refraction (rtc_scene_set_gloss): the meshuv walk with every ray's path code in
@@ -4874,4 +4972,4 @@ rtc_render_kernel_torus_bigworld(const DevScene S, const DevCamera cam, const De
                                                                                   smp, mo, spots, bumps);
 }
 
-#endif  // RTC_MOTION_TU / RTC_SPOT_TU / RTC_BUMP_TU / RTC_GLOSS_TU / RTC_MESHUV_TU / RTC_TORUS_TU
+#endif  // RTC_MOTION_TU / RTC_SPOT_TU / RTC_BUMP_TU / RTC_OCCL_TU / RTC_GLOSS_TU / RTC_MESHUV_TU / RTC_TORUS_TU

@@ -126,6 +126,13 @@ struct Flattener {
       const double rough[2] = {m.roughness.reflection, m.roughness.transmission};
       appendBits(key, rough, 2);
     }
+    // (likewise a material with an "ambient-occlusion": a row of its own only when the radius is non-zero)
+    out.occlusion_present = out.occlusion_present || m.occlusion.present;
+    if (m.occlusion.radius != 0.0) {
+      // (a tag before the value: a radius never shares a key with a roughness pair of the same bits)
+      const double occl[3] = {-1.0, m.occlusion.radius, -1.0};
+      appendBits(key, occl, 3);
+    }
     auto it = material_ids.find(key);
     if (it != material_ids.end()) return it->second;
     const uint32_t id = static_cast<uint32_t>(out.mat_pattern.size());
@@ -134,6 +141,7 @@ struct Flattener {
     out.mat_bump.push_back(m.bump);
     out.mat_gloss.push_back(m.roughness.reflection);
     out.mat_gloss.push_back(m.roughness.transmission);
+    out.mat_occlusion.push_back(m.occlusion.radius);
     material_ids.emplace(std::move(key), id);
     return id;
   }

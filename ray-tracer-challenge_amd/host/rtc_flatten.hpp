@@ -28,6 +28,8 @@ struct FlatScene {
   std::vector<uint32_t> mat_pattern;
   std::vector<double> mat_gloss;  // [n_materials][2]: each row's "roughness" (reflection, transmission) (rtch_scene_gloss; not part of rtc_scene_desc)
   bool gloss_present = false;     // some material of the scene has the "roughness" key
+  std::vector<double> mat_occlusion;  // [n_materials]: each row's "ambient-occlusion" radius (rtch_scene_occlusion; not part of rtc_scene_desc)
+  bool occlusion_present = false;     // some material of the scene has the "ambient-occlusion" key
   std::vector<Bump> mat_bump;  // [n_materials]: each row's "normal-perturbation" (rtch_scene_bumps; not part of rtc_scene_desc)
   std::vector<uint8_t> pat_kind;
   std::vector<double> pat_inv, pat_rgb;

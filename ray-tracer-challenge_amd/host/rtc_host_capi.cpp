@@ -151,6 +151,21 @@ int rtch_scene_gloss(void* h, double* reflection, double* transmission, uint64_t
   });
 }
 
+// The materials' "ambient-occlusion" radii, in mat_* order, and the camera's "occlusion-samples" and
+// "occlusion-seed", as rtc_scene_set_occlusion takes them; *present: some material of the file has the key.
+int rtch_scene_occlusion(void* h, double* radius, uint32_t* samples, uint64_t* seed, int* present, uint32_t n) {
+  return guarded([&] {
+    const HostScene* hs = static_cast<HostScene*>(h);
+    if (n != hs->desc.n_materials)
+      throw rtc::Error("InvalidArgument", "occlusion: n " + std::to_string(n) + ", the scene has " + std::to_string(hs->desc.n_materials) + " materials");
+    if (n != 0u && !radius) throw rtc::Error("InvalidArgument", "occlusion: null argument");
+    for (uint32_t i = 0; i < n; ++i) radius[i] = hs->flat.mat_occlusion[i];  // (mat_* order)
+    if (samples) *samples = hs->info.sampling.occlusion_samples;
+    if (seed) *seed = hs->info.sampling.occlusion_seed;
+    if (present) *present = hs->flat.occlusion_present ? 1 : 0;
+  });
+}
+
 // The triangles' texture rows (RTC_TEX_MESH), in tri_* order, as rtc_scene_set_mesh_uvs takes them.
 int rtch_scene_mesh_uvs(void* h, double* uv, uint32_t n) {
   return guarded([&] {
@@ -271,6 +286,11 @@ int rtch_scene_render(void* h, uint32_t width, uint32_t height, uint32_t max_dep
         for (uint32_t i = 0; i < nm; ++i) refl[i] = hs->flat.mat_gloss[2ull * i], trans[i] = hs->flat.mat_gloss[2ull * i + 1];
         const rtc_gloss gl{nm, refl.data(), trans.data(), hs->info.sampling.gloss_seed};
         st = rtc_scene_set_gloss(scene, &gl);
+      }
+      if (st == RTC_OK && hs->flat.occlusion_present) {  // (the materials' occlusion radii; all zero: the handle as it is)
+        const rtc_occlusion oc{hs->desc.n_materials, hs->flat.mat_occlusion.data(), hs->info.sampling.occlusion_samples,
+                               hs->info.sampling.occlusion_seed};
+        st = rtc_scene_set_occlusion(scene, &oc);
       }
       const rtc::CameraSampling& cs = hs->info.sampling;
       if (cs.adaptive && st == RTC_OK) {  // (adaptive sampling: each tile's mean after its own passes, section 15)

@@ -445,10 +445,30 @@ Roughness parseRoughness(const Value& cfg) {
   return r;
 }
 
+// A material's "ambient-occlusion" (not in the reference): a number, the radius, or {"radius": r}
+// (absent: 0); finite and >= 0.
+Occlusion parseOcclusion(const Value& cfg) {
+  auto one = [](const Value& v, const char* key) {
+    if (v.type != Value::Number) throw Error("InvalidData", std::string(key) + ": a number >= 0");
+    const double x = asFloat(v, key);
+    if (!(std::isfinite(x) && x >= 0.0)) throw Error("InvalidData", std::string(key) + ": a number >= 0");
+    return x;
+  };
+  Occlusion o;
+  o.present = true;
+  if (cfg.type == Value::Object) {
+    checkFields(cfg, {"radius"}, "ambient-occlusion");
+    if (const Value* v = presentField(cfg, "radius")) o.radius = one(*v, "ambient-occlusion.radius");
+  } else {
+    o.radius = one(cfg, "ambient-occlusion");
+  }
+  return o;
+}
+
 Material parseMaterial(const Value& cfg, const std::optional<Material>& inherited, const FileLoader& load_file_data) {
   requireObject(cfg, "material");
   checkFields(cfg, {"pattern", "ambient", "diffuse", "specular", "shininess", "reflective", "transparency",
-                    "refractive-index", "normal-perturbation", "roughness"}, "material");
+                    "refractive-index", "normal-perturbation", "roughness", "ambient-occlusion"}, "material");
   Material mat = inherited ? *inherited : Material{};
   auto present = [&](const char* k) -> const Value* {
     const Value* v = cfg.find(k);
@@ -464,6 +484,7 @@ Material parseMaterial(const Value& cfg, const std::optional<Material>& inherite
   if (auto* v = present("refractive-index")) mat.refractive_index = asFloat(*v, "refractive-index");
   if (auto* v = present("normal-perturbation")) mat.bump = parseBump(*v);
   if (auto* v = present("roughness")) mat.roughness = parseRoughness(*v);
+  if (auto* v = present("ambient-occlusion")) mat.occlusion = parseOcclusion(*v);
   return mat;
 }
 
@@ -714,7 +735,8 @@ SceneInfo parseScene(const std::string& scene_json, const FileLoader& load_file_
   info.camera.setTransform(Matrix4::viewTransform(from, to, up));
   if (const Value* smp = cam.find("sampling")) {  // (not in the reference: anti-aliasing and focal blur, every key optional)
     requireObject(*smp, "sampling");
-    checkFields(*smp, {"grid", "jitter", "aperture", "focal-distance", "seed", "passes", "adaptive", "gloss-seed"}, "sampling");
+    checkFields(*smp, {"grid", "jitter", "aperture", "focal-distance", "seed", "passes", "adaptive", "gloss-seed", "occlusion-samples",
+                       "occlusion-seed"}, "sampling");
     CameraSampling& s = info.sampling;
     if (const Value* v = smp->find("grid")) {
       const size_t g = asUsize(*v, "grid");
@@ -734,6 +756,12 @@ SceneInfo parseScene(const std::string& scene_json, const FileLoader& load_file_
     }
     if (const Value* v = smp->find("seed")) s.seed = static_cast<uint64_t>(asUsize(*v, "seed"));
     if (const Value* v = smp->find("gloss-seed")) s.gloss_seed = static_cast<uint64_t>(asUsize(*v, "gloss-seed"));  // (section 20)
+    if (const Value* v = smp->find("occlusion-samples")) {  // (section 21)
+      const size_t n = asUsize(*v, "occlusion-samples");
+      if (n < 1 || n > RTC_OCCLUSION_MAX_SAMPLES) throw Error("InvalidData", "occlusion-samples: 1 .. " + std::to_string(RTC_OCCLUSION_MAX_SAMPLES));
+      s.occlusion_samples = static_cast<uint32_t>(n);
+    }
+    if (const Value* v = smp->find("occlusion-seed")) s.occlusion_seed = static_cast<uint64_t>(asUsize(*v, "occlusion-seed"));
     if (const Value* v = smp->find("passes")) {  // (progressive rendering, DESIGN.md section 13: sample passes 0 .. passes-1)
       const size_t n = asUsize(*v, "passes");
       const size_t most = RTC_SAMPLING_INDEX_LIMIT / (static_cast<size_t>(s.grid) * s.grid);

@@ -32,6 +32,8 @@ struct CameraSampling {
   uint32_t min_passes = 4;
   uint32_t tile_w = 16, tile_h = 16;
   uint64_t gloss_seed = 0;  // "gloss-seed" (section 20): rtc_gloss::seed of the materials' "roughness"
+  uint32_t occlusion_samples = 1;  // "occlusion-samples" (section 21): rtc_occlusion::samples of the materials' "ambient-occlusion"
+  uint64_t occlusion_seed = 0;     // "occlusion-seed": rtc_occlusion::seed
 };
 
 // A "spot-light" entry's cone (not in the reference), as rtc_scene_set_spots takes it: the axis as

@@ -100,12 +100,20 @@ struct Roughness {
   bool present = false;
 };
 
+// A material's "ambient-occlusion" (not in the reference), as rtc_scene_set_occlusion takes it: the
+// length of the hemisphere rays that dim its ambient term, >= 0.  `present`: the material, or one it inherits from, has the key.
+struct Occlusion {
+  double radius = 0.0;
+  bool present = false;
+};
+
 struct Material {  // material.zig:18-25
   Pattern pattern = Pattern::solid({1.0, 1.0, 1.0});
   double ambient = 0.1, diffuse = 0.9, specular = 0.9, shininess = 200.0;
   double reflective = 0.0, transparency = 0.0, refractive_index = 1.0;
   Bump bump;  // (kind 0 in every scene of the reference)
   Roughness roughness;  // (0, 0 in every scene of the reference)
+  Occlusion occlusion;  // (0 in every scene of the reference)
 };
 
 struct Light {  // light.zig:14-15

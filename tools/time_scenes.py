@@ -47,6 +47,10 @@ mapping-4 branch costs against the planar one on the same scene.
 that transmission roughness (rtc_scene_set_gloss; glossy reflection and refraction); on a scene file
 with "roughness" entries those are applied first; --gloss off applies none.  Option gloss_kernels=1 times the gloss kernels
 without a rough material.  With --passes the noise run has the same table.
+--occlusion MATERIAL=radius (repeatable): material row MATERIAL (mat_* order) gets that ambient-occlusion radius
+(rtc_scene_set_occlusion; DESIGN.md section 21), --occlusion-samples N hemisphere rays per hit (default: the scene file's, or 1);
+on a scene file with "ambient-occlusion" entries those are applied first; --occlusion off applies none.  Option
+occlusion_kernels=1 times the occlusion kernels without a radius.  With --passes the noise run has the same table.
 --adaptive threshold[,min,tile]: adaptive sampling at up to --max-passes (64) passes, min passes 4 and
 16 x 16 tiles by default, with the --sampling of the frames: prints the rounds and tile-passes of a run against
 T * max_passes, its time (a second run, end to end on the host) against uniform progressive passes (render_device +
@@ -87,6 +91,8 @@ ap.add_argument("--motion", action="append", default=[])
 ap.add_argument("--spot", action="append", default=[])
 ap.add_argument("--bump", action="append", default=[])
 ap.add_argument("--gloss", action="append", default=[])
+ap.add_argument("--occlusion", action="append", default=[])
+ap.add_argument("--occlusion-samples", type=int, default=0)
 ap.add_argument("--torus", action="store_true")
 ap.add_argument("--meshuv", action="store_true")
 ap.add_argument("--mesh-as-planar", action="store_true")
@@ -124,6 +130,21 @@ def gloss_table(hs):
         gloss["reflection"][int(m)] = f[0]
         gloss["transmission"][int(m)] = f[1] if len(f) > 1 else 0.0
     return gloss
+
+
+def occlusion_table(hs):
+    """the scene file's "ambient-occlusion" rows with the --occlusion entries over them; None: no table (--occlusion off, or
+    nothing to set)"""
+    if "off" in args.occlusion or not (args.occlusion or hs.occlusion() is not None):
+        return None
+    import numpy as np
+    occlusion = hs.occlusion() or {"radius": np.zeros(hs.desc.n_materials), "samples": 1, "seed": 0}
+    for o in args.occlusion:
+        m, v = o.split("=")
+        occlusion["radius"][int(m)] = float(v)
+    if args.occlusion_samples:
+        occlusion["samples"] = args.occlusion_samples
+    return occlusion
 
 
 def light_table(hs, how):
@@ -322,6 +343,9 @@ for name, w, h, depth in cases:
         gloss = gloss_table(hs)
         if gloss is not None:
             gpu.set_gloss(gloss)
+        occlusion = occlusion_table(hs)
+        if occlusion is not None:
+            gpu.set_occlusion(occlusion)
         for i in range(args.settle):
             gpu.render_device(cam, canvas.data_ptr(), depth, None, stream.cuda_stream)
         torch.cuda.synchronize()
@@ -346,7 +370,7 @@ for name, w, h, depth in cases:
     if delta is not None: line += f" maxdelta {delta:.2e}"
     if args.lights or args.spot or "spot_kernels=1" in args.option:
         line += f" shadow_traced {st['shadow_traced']} ns/shadow-ray {min(ts) * 1e6 / max(1, st['shadow_traced']):.3f}"
-    if args.sampling or args.option or args.passes >= 0 or args.motion or args.spot or args.bump or args.torus or args.meshuv or args.gloss:
+    if args.sampling or args.option or args.passes >= 0 or args.motion or args.spot or args.bump or args.torus or args.meshuv or args.gloss or args.occlusion:
         line += f" primary {st['primary']} ns/primary-ray {min(ts) * 1e6 / max(1, st['primary']):.3f}"
     if acc:
         ms, copy_ms, nbytes = min(a[0] for a in acc), min(a[1] for a in acc), acc[0][2]
@@ -359,6 +383,7 @@ for name, w, h, depth in cases:
         if hs.spots() is not None: gpu.set_spots(hs.spots())
         if hs.mesh_uvs() is not None: gpu.set_mesh_uvs(hs.mesh_uvs())
         if gloss_table(hs) is not None: gpu.set_gloss(gloss_table(hs))
+        if occlusion_table(hs) is not None: gpu.set_occlusion(occlusion_table(hs))
         prog = rtc.Progressive(gpu, cam, depth)
         noise = {}
         for i in range(1, 65):
