@@ -3939,6 +3939,10 @@ int rtc_get_stats(rtc_scene* s, rtc_stats* out) {
       std::fprintf(stderr, "rtc walks of %s traces: %llu lanes %llu node-steps %llu leaf-steps %llu lanes-at-nodes %llu lanes-at-leaves %llu cycles-at-nodes %llu cycles-at-leaves %llu\n",
                    k == 0 ? "closest" : k == 1 ? "shadow" : "containers", h.prof6[8 * k], h.prof6[8 * k + 1], h.prof6[8 * k + 2], h.prof6[8 * k + 3],
                    h.prof6[8 * k + 4], h.prof6[8 * k + 5], h.prof6[8 * k + 6], h.prof6[8 * k + 7]);
+    for (int k = 0; k < 3; ++k)
+      std::fprintf(stderr, "rtc cube tests of %s traces: %llu lanes, %llu with tmax < 0, %llu named entirely behind | wave steps %llu, left without the tmax < 0 tests %llu, without the named ones %llu\n",
+                   k == 0 ? "closest" : k == 1 ? "shadow" : "containers", h.prof7[6 * k], h.prof7[6 * k + 1], h.prof7[6 * k + 2], h.prof7[6 * k + 3],
+                   h.prof7[6 * k + 4], h.prof7[6 * k + 5]);
     std::fprintf(stderr, "rtc trace cycles by lanes with a ray (1-2, 3-4, 5-8, 9-16, 17-32, 33-48, 49-64):");
     for (int k = 0; k < 3; ++k) {
       std::fprintf(stderr, " %s", k == 0 ? "closest" : k == 1 ? "| shadow" : "| behind");

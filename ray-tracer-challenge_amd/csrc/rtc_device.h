@@ -501,6 +501,7 @@ struct DevStats {
   unsigned long long prof5[8];  // [5], [6]: wave cycles of all group walks at nodes / at leaves (the other slots: free)
   unsigned long long prof6[24]; // group walks by kind of trace [closest, shadow, containers][walks, lanes, node steps, leaf steps, lanes at nodes, lanes at leaves, wave cycles at nodes, at leaves]
   unsigned long long oob[8];    // accesses outside their allocation, counted and not made (RTC_OOB_*)
+  unsigned long long prof7[18]; // exact cube tests of the root loop's kind-by-kind phase 2 [closest, shadow, containers][tests (lanes), with tmax < 0, named by cube_entirely_behind, wave steps, wave steps left without the tmax < 0 tests, without the named ones]
   unsigned long long prof4[8];  // group walks: walks of a wave, their lanes, wave steps at nodes, at leaves, lanes at nodes, at leaves (summed over the steps), walks that reach no leaf, their node steps
   unsigned long long prof_t0, prof_t1, prof_busy;  // shortest / longest / summed wave lifetime
   unsigned long long prof_log[4096][4];            // per wave: lifetime, iterations, units, first<<32|last unit

@@ -88,12 +88,13 @@ __shared__ DevStats* rtc_prof_stats;
 #define RTC_WALK_ADD(slot, n) do { (void)(n); } while (0)
 #define RTC_AUX_ADD(slot, n) do { (void)(n); } while (0)
 #define RTC_KIND_ADD(slot, n) do { (void)(n); } while (0)
+#define RTC_CUBE_ADD(slot, n) do { (void)(n); } while (0)
 #elif defined(RTC_PROFILE)
 __shared__ DevStats* rtc_prof_stats;
 // (diagnostic builds: the walks' counts and cycles - DevStats::prof4, prof5, prof6 - are summed per wave in LDS
 // by the first active lane and added to the launch's counters when the wave ends: with an atomic per count and walk on
 // eight words of memory the diagnostic frame was eleven times the product's)
-__shared__ unsigned long long rtc_prof_counts[4][40];
+__shared__ unsigned long long rtc_prof_counts[4][58];
 #define RTC_PROF_ADD_(slot, n)                                                                                        \
   do {                                                                                                                 \
     const unsigned long long n_ = static_cast<unsigned long long>(n);                                                  \
@@ -103,10 +104,12 @@ __shared__ unsigned long long rtc_prof_counts[4][40];
 #define RTC_WALK_ADD(slot, n) RTC_PROF_ADD_(slot, n)
 #define RTC_AUX_ADD(slot, n) RTC_PROF_ADD_(8 + (slot), n)
 #define RTC_KIND_ADD(slot, n) RTC_PROF_ADD_(16 + (slot), n)
+#define RTC_CUBE_ADD(slot, n) RTC_PROF_ADD_(40 + (slot), n)
 #else
 #define RTC_WALK_ADD(slot, n) do { } while (0)
 #define RTC_AUX_ADD(slot, n) do { } while (0)
 #define RTC_KIND_ADD(slot, n) do { } while (0)
+#define RTC_CUBE_ADD(slot, n) do { } while (0)
 #endif
 
 // Diagnostic builds (-DRTC_PROFILE) also check what the render kernels index against what was allocated for it: an
@@ -151,6 +154,9 @@ __device__ __forceinline__ bool rtc_in_bounds(uint32_t kind, bool ok) {
 #endif
 #ifndef RTC_ROOM_EARLY_OUT
 #define RTC_ROOM_EARLY_OUT 1    // shadow rays inside a cube that contains every light (segment_stays_inside_cube)
+#endif
+#ifndef RTC_CUBE_BEHIND_EARLY_OUT
+#define RTC_CUBE_BEHIND_EARLY_OUT 1  // shadow traces of the simple kernels that cull by boxes skip a cube behind the ray's origin (cube_entirely_behind)
 #endif
 // Wave priority by phase of the iteration (s_setprio, round 5; profiles/r05/wave_priority.md).  The three waves of a SIMD
 // are at different places of the same loop; which of them issues when more than one could is the arbiter's choice, and
@@ -322,6 +328,36 @@ __device__ __forceinline__ bool segment_stays_inside_cube(const Ray& r, double l
     return !(ad >= 1e-5) | (ahead > (limit * ad) * (1.0 + 1e-12));
   };
   return inside & clear(r.ox, r.dx) & clear(r.oy, r.dy) & clear(r.oz, r.dz);
+}
+
+// A ray that starts beyond one of a cube's faces and does not travel back towards it: the cube is behind it, and both of
+// its entries - if it has any - are negative, which a closest-hit and a shadow trace ignore (V::kFrontOnly); known
+// WITHOUT xform_ray's successors, the six quotients of cube_slab, exactly, by the reference's own arithmetic (cube.zig
+// checkAxis, cube_slab above).  On an axis with o > 1:
+//   * both numerators, -1 - o and 1 - o, are negative, and their signs are exact: o >= 1 + 2^-52, so 1 - o <= -2^-52
+//     (a difference of neighbours is exact) and -1 - o <= -2;
+//   * d >= 1e-5: both quotients are negative - and, with d <= 1e10, at least 2^-52 / 1e10 > 1e-26 in magnitude, far
+//     from a quotient that underflows to -0, which `t >= 0` would let through (an infinite d gives exactly that);
+//   * |d| < 1e-5, either sign (the reference's "parallel" rule): both are numerator x inf = -inf;
+//   * so the axis's far parameter is negative, the cube's tmax - a minimum over the axes that ignores NaNs - is negative,
+//     and tmin <= tmax or there is no entry at all.
+// On an axis with o < -1 both numerators are positive (1 - o >= 2, -1 - o >= 2^-52), and only a direction that is not
+// "parallel", d <= -1e-5, makes the quotients negative: the parallel rule multiplies by +inf whatever the sign of d, and
+// a cube whose three axes all give +inf has both entries at t = +inf, which ClosestVisitor::entry's tie rule looks at.
+// An infinite o gives -inf / d = -inf: nothing to guard.  A NaN in o or d compares false and the full test runs.
+// The ray that leaves a cube's face at over_point - two shadow rays and a reflected ray per hit on cover.json's cubes -
+// has that cube 1e-5 behind it, inside phase 1's FP32 margin: each of those traces ran the whole test on the cube it
+// stands on.  The containers pass wants negative entries and never asks; a refracted ray starts inside the cube
+// (under_point) and fails `|o| > 1` by itself.
+// (The conditions are restated, not called, by the checks that hold them to the reference's arithmetic: `_predicate` in
+// tests/test_cube_behind_cpu.py and `behind` in tests/cpp/cube_behind_check.cpp.  A change here is a change in all three.)
+__device__ __forceinline__ bool cube_entirely_behind(const Ray& lr) {
+  auto behind = [](double o, double d) {
+    const double ad = __builtin_fabs(d);
+    const bool above = (o > 1.0) & ((d >= 0.0) | (ad < 1e-5)), below = (o < -1.0) & (d <= -1e-5);
+    return (above | below) & (ad <= 1e10);
+  };
+  return behind(lr.ox, lr.dx) | behind(lr.oy, lr.dy) | behind(lr.oz, lr.dz);
 }
 
 #ifdef RTC_TORUS_TU
@@ -1568,6 +1604,13 @@ __device__ __forceinline__ void trace(const DevScene& S, const RootRec* __restri
       const unsigned long long below_a = a >= 64u ? ~0ull : (1ull << a) - 1ull;
       return below_b & ~below_a;
     };
+#if defined(RTC_PROFILE) && !defined(RTC_PROFILE_LITE)
+    uint32_t cube_tests = 0u, cube_neg = 0u, cube_pred = 0u;  // this lane's exact cube tests of the block; those with tmax < 0; those cube_entirely_behind names
+#endif
+    // (cube_entirely_behind stands in the shadow traces of rtc_render_kernel_simple_b / _simple3_b - worlds of cubes - and
+    // nowhere else: in closest-hit traces, in the other kernels without groups and in the `while (mine)` path it was
+    // measured and lost)
+    constexpr bool kCubeBehind = SIMPLE && BOX && V::kAnyHit && V::kFrontOnly && RTC_CUBE_BEHIND_EARLY_OUT;
     auto leaf_of_kind = [&](auto kind_tag, const uint32_t root) {
       constexpr uint32_t KIND = decltype(kind_tag)::value;
       const RootRec& R = recs[RTC_CHECK_INDEX(RTC_OOB_ROOTS, root, RTC_AVAIL(0))];
@@ -1578,6 +1621,24 @@ __device__ __forceinline__ void trace(const DevScene& S, const RootRec* __restri
       vis.set_root(root);
       if constexpr (KIND == 2u && V::kAnyHit && RTC_ROOM_EARLY_OUT) {
         if ((kf & RTC_ROOT_ROOM) && segment_stays_inside_cube(lr, vis.t_limit())) return;
+      }
+#if defined(RTC_PROFILE) && !defined(RTC_PROFILE_LITE)
+      if constexpr (KIND == 2u) {  // (what cube_entirely_behind can save at most, and what it does save: cube_counts below)
+        double c_tmin, c_tmax;
+        cube_slab(lr, c_tmin, c_tmax);
+        const bool neg = c_tmax < 0.0, pred = cube_entirely_behind(lr);
+        constexpr uint32_t K = V::kAnyHit ? 6u : (V::kBehindOnly ? 12u : 0u);
+        RTC_CUBE_ADD(K + 0u, __builtin_popcountll(__ballot(true)));
+        RTC_CUBE_ADD(K + 1u, __builtin_popcountll(__ballot(neg)));
+        RTC_CUBE_ADD(K + 2u, __builtin_popcountll(__ballot(pred)));
+        RTC_CUBE_ADD(K + 3u, 1);
+        cube_neg += neg ? 1u : 0u;
+        cube_pred += pred ? 1u : 0u;
+        cube_tests += 1u;
+      }
+#endif
+      if constexpr (KIND == 2u && kCubeBehind) {
+        if (cube_entirely_behind(lr)) return;
       }
       if constexpr (KIND == 1u && V::kFrontOnly && RTC_PLANE_EARLY_OUT) {
         // A plane's one entry is t = -o.y / d.y (plane.zig:25-36), and the division is 13 of the test's ~35 instructions.
@@ -1632,6 +1693,17 @@ __device__ __forceinline__ void trace(const DevScene& S, const RootRec* __restri
       }
       leaves_of_kind(std::integral_constant<uint32_t, 0u>{}, mine & range(0u, k1));
       leaves_of_kind(std::integral_constant<uint32_t, 2u>{}, mine & range(k1, k2));
+#if defined(RTC_PROFILE) && !defined(RTC_PROFILE_LITE)
+      {  // the cube loop is as long as its lane with the most tests: the wave-level steps that would remain without the
+         // tests whose interval ends behind the origin, and without those the early-out names
+        constexpr uint32_t K = V::kAnyHit ? 6u : (V::kBehindOnly ? 12u : 0u);
+        uint32_t left_neg = 0u, left_pred = 0u;
+        while (__ballot(cube_tests - cube_neg > left_neg) != 0ull) ++left_neg;
+        while (__ballot(cube_tests - cube_pred > left_pred) != 0ull) ++left_pred;
+        RTC_CUBE_ADD(K + 4u, left_neg);
+        RTC_CUBE_ADD(K + 5u, left_pred);
+      }
+#endif
       if constexpr (SIMPLE) continue;  // (a simple world has nothing else)
       mine &= range(k2, n_bounded);    // the other leaf kinds: cylinders, cones, triangles
     }
@@ -2670,7 +2742,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
   (void)next_stats;
   if (threadIdx.x == 0u) rtc_prof_stats = stats;
 #ifndef RTC_PROFILE_LITE
-  if (threadIdx.x < 160u) rtc_prof_counts[threadIdx.x / 40u][threadIdx.x % 40u] = 0ull;
+  for (uint32_t i = threadIdx.x; i < 4u * 58u; i += blockDim.x) rtc_prof_counts[i / 58u][i % 58u] = 0ull;
 #endif
   __syncthreads();
 #endif
@@ -3952,6 +4024,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
       atomicAdd(&stats->prof5[i], rtc_prof_counts[threadIdx.x >> 6][8 + i]);
     }
     for (int i = 0; i < 24; ++i) atomicAdd(&stats->prof6[i], rtc_prof_counts[threadIdx.x >> 6][16 + i]);
+    for (int i = 0; i < 18; ++i) atomicAdd(&stats->prof7[i], rtc_prof_counts[threadIdx.x >> 6][40 + i]);
 #endif
     const unsigned wid = (blockIdx.x * 4u + (threadIdx.x >> 6)) & 4095u;
     stats->prof_log[wid][0] = prof_t - prof_start;
