@@ -81,6 +81,12 @@ int rtc_diag_build_tables(const rtc_scene_desc *desc, uint64_t *digest, double *
 int rtc_diag_root_boxes(const rtc_scene_desc *desc, float *boxes, uint32_t *world_index, uint32_t capacity, uint32_t *n_roots,
                         float *scales);
 
+/* Diagnostic (tests/test_containers_cpu.py): the FP32 bounding spheres phase 1 tests in the simple kernels that cull by
+ * spheres, in the same table order as rtc_diag_root_boxes (its `world_index`): `spheres[4 i ...]` = centre x y z, radius
+ * squared (no finite bound: +inf), `*cmax` = the largest |centre| of a bounded root (the scale of the kernel's rounding
+ * margin).  `spheres` may be NULL (then only *n_roots and *cmax). */
+int rtc_diag_root_spheres(const rtc_scene_desc *desc, float *spheres, uint32_t capacity, uint32_t *n_roots, float *cmax);
+
 #ifdef __cplusplus
 }
 #endif

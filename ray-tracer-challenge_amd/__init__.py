@@ -324,7 +324,7 @@ RTC_SYMBOLS = ["rtc_scene_create", "rtc_scene_clone", "rtc_scene_destroy", "rtc_
                "rtc_scene_set_spots", "rtc_scene_set_bumps", "rtc_scene_set_mesh_uvs", "rtc_scene_set_gloss",
                "rtc_scene_set_occlusion"]
 # (... and include/rtc_diag.h: diagnostics and tuning, for the tests, bench.py and tools/)
-RTC_DIAG_SYMBOLS = ["rtc_set_option", "rtc_last_kernel_name", "rtc_get_schedule", "rtc_get_chunk_times", "rtc_diag_build_tables", "rtc_diag_root_boxes"]
+RTC_DIAG_SYMBOLS = ["rtc_set_option", "rtc_last_kernel_name", "rtc_get_schedule", "rtc_get_chunk_times", "rtc_diag_build_tables", "rtc_diag_root_boxes", "rtc_diag_root_spheres"]
 HOST_SYMBOLS = ["rtch_last_error", "rtch_scene_load", "rtch_scene_free", "rtch_scene_desc", "rtch_scene_camera",
                 "rtch_camera_rotate", "rtch_camera_move", "rtch_camera_make", "rtch_canvas_ppm", "rtch_canvas_rgba8", "rtch_scene_render", "rtch_set_loader_threads",
                 "rtch_scene_lights", "rtch_scene_sampling", "rtch_scene_passes", "rtch_scene_motion", "rtch_scene_adaptive",
@@ -1070,6 +1070,19 @@ def root_boxes(desc):
     _check_hip(lib.rtc_diag_root_boxes(C.byref(desc), boxes.ctypes.data_as(f32p), order.ctypes.data_as(_u32p), n.value, C.byref(n),
                                        scales.ctypes.data_as(f32p)))
     return boxes, order, (float(scales[0]), float(scales[1]))
+
+
+def root_spheres(desc):
+    """rtc_diag_root_spheres: (spheres [n][4] f32: centre, radius squared - in root_boxes' table order; cull_cmax) of a scene
+    description, as rtc_scene_create builds them - no device needed."""
+    lib = hip_lib()
+    n, cmax = C.c_uint32(0), C.c_float(0.0)
+    f32p = C.POINTER(C.c_float)
+    lib.rtc_diag_root_spheres.argtypes = [C.c_void_p, f32p, C.c_uint32, _u32p, f32p]
+    _check_hip(lib.rtc_diag_root_spheres(C.byref(desc), None, 0, C.byref(n), None))
+    spheres = np.zeros((n.value, 4), dtype=np.float32)
+    _check_hip(lib.rtc_diag_root_spheres(C.byref(desc), spheres.ctypes.data_as(f32p), n.value, C.byref(n), C.byref(cmax)))
+    return spheres, float(cmax.value)
 
 
 def set_option(name, value):

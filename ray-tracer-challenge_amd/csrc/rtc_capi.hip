@@ -3587,6 +3587,26 @@ int rtc_diag_root_boxes(const rtc_scene_desc* desc, float* boxes, uint32_t* worl
   return RTC_OK;
 }
 
+int rtc_diag_root_spheres(const rtc_scene_desc* desc, float* spheres, uint32_t capacity, uint32_t* n_roots, float* cmax) {
+  g_error.clear();
+  if (!desc || !n_roots) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
+  SceneTraits traits;
+  if (const int st = validateScene(*desc, traits); st != RTC_OK) return st;
+  HostTables tables;
+  if (const int st = buildTables(*desc, traits, tables); st != RTC_OK) return st;
+  *n_roots = desc->n_roots;
+  if (cmax) *cmax = tables.cull_cmax;
+  if (capacity < desc->n_roots) return spheres ? fail(RTC_ERR_INVALID_ARGUMENT, "%u roots, room for %u", desc->n_roots, capacity) : RTC_OK;
+  for (uint32_t i = 0; spheres && i < desc->n_roots; ++i) {
+    const RootCull& C = tables.root_cull[i];
+    spheres[4ull * i + 0] = C.cx;
+    spheres[4ull * i + 1] = C.cy;
+    spheres[4ull * i + 2] = C.cz;
+    spheres[4ull * i + 3] = C.r2;
+  }
+  return RTC_OK;
+}
+
 int rtc_set_option(const char* name, double value) {
   g_error.clear();
   if (!name) return fail(RTC_ERR_INVALID_ARGUMENT, "null option name");
@@ -3943,6 +3963,9 @@ int rtc_get_stats(rtc_scene* s, rtc_stats* out) {
       std::fprintf(stderr, "rtc cube tests of %s traces: %llu lanes, %llu with tmax < 0, %llu named entirely behind | wave steps %llu, left without the tmax < 0 tests %llu, without the named ones %llu\n",
                    k == 0 ? "closest" : k == 1 ? "shadow" : "containers", h.prof7[6 * k], h.prof7[6 * k + 1], h.prof7[6 * k + 2], h.prof7[6 * k + 3],
                    h.prof7[6 * k + 4], h.prof7[6 * k + 5]);
+    // (the containers pass of the kernels without groups: its wave invocations counted by the first active lane, and the wave steps
+    // of its exact tests - prof5[7], prof5[4])
+    std::fprintf(stderr, "rtc containers pass: waves traced %llu | wave steps of exact tests %llu\n", h.prof5[7], h.prof5[4]);
     std::fprintf(stderr, "rtc trace cycles by lanes with a ray (1-2, 3-4, 5-8, 9-16, 17-32, 33-48, 49-64):");
     for (int k = 0; k < 3; ++k) {
       std::fprintf(stderr, " %s", k == 0 ? "closest" : k == 1 ? "| shadow" : "| behind");

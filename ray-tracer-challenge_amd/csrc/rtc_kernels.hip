@@ -158,6 +158,9 @@ __device__ __forceinline__ bool rtc_in_bounds(uint32_t kind, bool ok) {
 #ifndef RTC_CUBE_BEHIND_EARLY_OUT
 #define RTC_CUBE_BEHIND_EARLY_OUT 1  // shadow traces of the simple kernels that cull by boxes skip a cube behind the ray's origin (cube_entirely_behind)
 #endif
+#ifndef RTC_CONTAINERS_SOLIDS
+#define RTC_CONTAINERS_SOLIDS 1      // simple worlds: the containers pass drops a solid whose bound lies behind the origin and a plane whose entry cannot be negative (trace(), kSolids)
+#endif
 // Wave priority by phase of the iteration (s_setprio, round 5; profiles/r05/wave_priority.md).  The three waves of a SIMD
 // are at different places of the same loop; which of them issues when more than one could is the arbiter's choice, and
 // with equal priorities it serves them alike.  Here a wave says what it is doing: fetching work (RTC_PRIO_DEAL: popping its
@@ -1342,7 +1345,11 @@ struct CullTables {  // what phase 1 of the root loop reads (in LDS where the wo
 
 // Phase 1 of the root loop for TWO roots: the arithmetic runs as packed FP32 (v_pk_fma_f32 & co: one instruction per
 // pair of roots), only the comparisons are per root.  Returns bit 0 / bit 1 = root 0 / 1 of the pair must be tested.
-template <class V, bool GROUPS>
+// SOLIDS (the containers pass of a simple world, RTC_CONTAINERS_SOLIDS): every bounded root is a sphere or a cube - two
+// entries or none -, so a root whose bound lies entirely behind the origin has an even number of entries there and the
+// pass, which uses a root only if that number is odd, has no use for it.  (An open surface - a triangle, an open cylinder -
+// can have ONE: the other worlds keep it.)
+template <class V, bool GROUPS, bool SOLIDS = false>
 __device__ __forceinline__ uint32_t roots_kept(const RootCullPair& R, const RayF ray) {  // by value: by reference, three fields went through scratch memory
   // explicit FMAs: this file is compiled with contraction off for the FP64 path, but nothing here has
   // to round like the reference
@@ -1363,7 +1370,7 @@ __device__ __forceinline__ uint32_t roots_kept(const RootCullPair& R, const RayF
     const bool sided = (ac[e] > T[e]) & (bb[e] > T[e]) & !line_only;  // origin outside, sphere clearly on one side of it
     const bool behind = sided & (b[e] < 0.0f);            // entirely at t < 0
     const bool front = sided & (b[e] > 0.0f);             // entirely at t > 0
-    const bool culled = miss | (behind & V::kFrontOnly) | (front & V::kBehindOnly);
+    const bool culled = miss | (behind & (V::kFrontOnly | SOLIDS)) | (front & V::kBehindOnly);
     kept |= culled ? 0u : (1u << e);
   }
   return kept;
@@ -1515,9 +1522,20 @@ __device__ __forceinline__ void trace(const DevScene& S, const RootRec* __restri
   // in one kernel - spheres by spheres, the rest by boxes - lose to either (cover 0.496, reflection_and_refraction 1.785:
   // the three-wave kernel has no registers for two kinds of ray set-up): rtc_scene_create picks the kernel by what the
   // world is made of (profiles/r05/root_cull_boxes.md).
+  // (RTC_CONTAINERS_SOLIDS) The containers pass uses a root only if an ODD number of its entries lies at t < 0
+  // (BehindVisitor::flush; hit_dups is read only when the hit leaf is such a root).  In a simple world a bounded root is a sphere or
+  // a cube - odd exactly when the origin is inside it -, so its bound must REACH the origin: the box interval by the margin of the
+  // other two visitors, the sphere by roots_kept's SOLIDS (tests/test_containers_cpu.py).  On cover every one of the pass's
+  // 21 813 wave steps of cube tests per frame was a cube behind the origin (profiles/containers/).
+  constexpr bool kSolids = SIMPLE && RTC_CONTAINERS_SOLIDS && V::kBehindOnly;
   const auto rf = [&]() {
-    if constexpr (BOX) return ray_box(ray, S, vis);
-    else return ray_f32(ray, S.cull_cmax);
+    if constexpr (BOX) {
+      RayB b = ray_box(ray, S, vis);
+      if constexpr (kSolids) b.t_lo = -1.0002e-4f;
+      return b;
+    } else {
+      return ray_f32(ray, S.cull_cmax);
+    }
   }();
   // (the table is sorted [spheres][cubes][the rest][planes]: a plane has no bound, phase 1 stops where the planes begin)
   const uint32_t n_bounded = S.n_roots - S.n_root_planes;
@@ -1576,7 +1594,7 @@ __device__ __forceinline__ void trace(const DevScene& S, const RootRec* __restri
           if (i + 2u < nc) k |= roots_kept_box<V, !FLAT>(p1, p1 + rf.onx, p1 + rf.ony, p1 + rf.onz, rf) << 2;
         } else {
           const RootCullPair p0 = cull.sphere[(base + i) >> 1], p1 = cull.sphere[((base + i) >> 1) + 1u];
-          k = roots_kept<V, !FLAT>(p0, rf) | (roots_kept<V, !FLAT>(p1, rf) << 2);
+          k = roots_kept<V, !FLAT, kSolids>(p0, rf) | (roots_kept<V, !FLAT, kSolids>(p1, rf) << 2);
         }
         mine |= k << i;
       }
@@ -1657,6 +1675,12 @@ __device__ __forceinline__ void trace(const DevScene& S, const RootRec* __restri
           const bool beyond = ao > (vis.t_limit() * ad) * (1.0 + 1e-12);
           if (!(negative | beyond)) vis.entry(leaf, shadow, material, -lr.oy / lr.dy, 0.0, 0.0);
         }
+      } else if constexpr (KIND == 1u && kSolids) {
+        // The pass looks at a plane's one entry t = -o.y / d.y only if t < 0 (the plane's own `t == hit_t` counts for hit_dups,
+        // which is read only when the hit leaf is open - and the plane that was hit at t >= 0 is not).  o.y and d.y of
+        // different signs - `o.y > 0` against `d.y > 0`, a zero or a NaN on the side of the negatives - give a quotient that
+        // is positive, a zero of either sign or a NaN: none is < 0, and the division is not made.
+        if (__builtin_fabs(lr.dy) > 1e-5 && (lr.oy > 0.0) == (lr.dy > 0.0)) vis.entry(leaf, shadow, material, -lr.oy / lr.dy, 0.0, 0.0);
       } else {
         leaf_entries<SIMPLE>(KIND, cy, nullptr, lr, [&](double t, double u, double v) { vis.entry(leaf, shadow, material, t, u, v); });
       }
@@ -1665,6 +1689,7 @@ __device__ __forceinline__ void trace(const DevScene& S, const RootRec* __restri
       while (m != 0ull && !vis.done()) {
         const uint32_t bit = static_cast<uint32_t>(__builtin_ctzll(m));
         m &= m - 1ull;
+        if constexpr (V::kBehindOnly) RTC_AUX_ADD(4, 1);  // (diagnostic builds: wave steps of the containers pass's exact tests)
         leaf_of_kind(kind_tag, base + bit);
       }
     };
@@ -1685,6 +1710,7 @@ __device__ __forceinline__ void trace(const DevScene& S, const RootRec* __restri
         const uint32_t p1 = base + n;
         for (uint32_t root = base + nc; root < p1; ++root) {
           if (__all(vis.done())) break;
+          if constexpr (V::kBehindOnly) RTC_AUX_ADD(4, 1);
           if (!vis.done()) leaf_of_kind(std::integral_constant<uint32_t, 1u>{}, root);
         }
 
@@ -1884,7 +1910,14 @@ struct ShadowVisitor {
 //        open leaf other than the hit leaf, else 1 (or the hit leaf again if it has a second
 //        entry at exactly t_hit: the reference does not `break` on an empty list).
 // Identity is the leaf index; rtc_scene_create rejects scenes whose leaves share a Shape.id.
-struct BehindVisitor {
+// SELECTS (the simple kernels): "is this open leaf the later one" updates its three fields with selects on one condition.
+// Written as a branch - the form every other kernel keeps, instruction for instruction - the simple kernels' last flush was
+// compiled to code that, on a TIE in t (cur_last == best_t, the larger leaf wins), moved the leaf but kept the earlier
+// leaf's material: two glass spheres with one transform and different refractive indices gave n1 of the wrong sphere
+// (rtc_render_kernel_simple3: the material's move stood inside the not-greater branch, in front of the tie's decision;
+// profiles/containers/flush_tie_isa.txt holds those instructions; tests/test_containers_gpu.py, `ties` and `ties3`).
+template <bool SELECTS>
+struct BehindVisitorT {
   static constexpr bool kAnyHit = false;  // the first entry that counts ends the trace: visiting order is free
   uint32_t hit_leaf;
   double hit_t;
@@ -1900,9 +1933,29 @@ struct BehindVisitor {
   bool hit_open = false;
   uint32_t hit_dups = 0;
   __device__ __forceinline__ void set_root(uint32_t) {}
+  // (SELECTS) is the open leaf (bt, bl) later than (at, al)?  bl is a leaf
+  static __device__ __forceinline__ bool later_than(double at, uint32_t al, double bt, uint32_t bl) {
+    return (bt > at) | ((bt == at) & ((al == RTC_NO_LEAF) | (bl > al)));
+  }
 
+  // LAST: the flush after a leaf's last entry that no other entry follows (render_body's after the trace, merge_group's) - the
+  // copy that was compiled wrongly; the flushes between two leaves (entry()) stay branches in every kernel: with selects
+  // there as well fresnel lost 3.7 % and reflection_and_refraction 1.9 % (profiles/containers/times_1080p_depth5.txt)
+  template <bool LAST = false>
   __device__ __forceinline__ void flush() {
-    if (cur != RTC_NO_LEAF && (cur_cnt & 1u)) {
+    if constexpr (SELECTS && LAST) {
+      const bool open = cur != RTC_NO_LEAF && (cur_cnt & 1u) != 0u;
+      const bool is_hit = cur == hit_leaf;
+      const bool take = open && later_than(best_t, best_leaf, cur_last, cur);
+      const bool take_excl = open && !is_hit && later_than(best_excl_t, best_excl_leaf, cur_last, cur);
+      best_t = take ? cur_last : best_t;
+      best_leaf = take ? cur : best_leaf;
+      best_mat = take ? cur_mat : best_mat;
+      best_excl_t = take_excl ? cur_last : best_excl_t;
+      best_excl_leaf = take_excl ? cur : best_excl_leaf;
+      best_excl_mat = take_excl ? cur_mat : best_excl_mat;
+      hit_open = hit_open || (open && is_hit);
+    } else if (cur != RTC_NO_LEAF && (cur_cnt & 1u)) {
       if (cur_last > best_t || (cur_last == best_t && (best_leaf == RTC_NO_LEAF || cur > best_leaf))) {
         best_t = cur_last;
         best_leaf = cur;
@@ -1948,7 +2001,7 @@ struct BehindVisitor {
   // (every root was tested by ONE lane of the group, so the entries of a leaf did arrive together; what is merged are the
   // lanes' flushed results: the latest open leaf, the latest one other than the hit leaf, the hit leaf's own state)
   __device__ __forceinline__ void merge_group(uint32_t group) {
-    flush();
+    flush<true>();
     auto later = [](double at, uint32_t al, double bt, uint32_t bl) {  // is (bt, bl) the later open leaf?
       return bl != RTC_NO_LEAF && (al == RTC_NO_LEAF || bt > at || (bt == at && bl > al));
     };
@@ -1958,15 +2011,25 @@ struct BehindVisitor {
       const uint32_t ol = group8_other<STEP>(best_leaf), om = group8_other<STEP>(best_mat);
       const uint32_t oel = group8_other<STEP>(best_excl_leaf), oem = group8_other<STEP>(best_excl_mat);
       const uint32_t oopen = group8_other<STEP>(hit_open ? 1u : 0u), odups = group8_other<STEP>(hit_dups);
-      if (later(best_t, best_leaf, ot, ol)) {
-        best_t = ot;
-        best_leaf = ol;
-        best_mat = om;
-      }
-      if (later(best_excl_t, best_excl_leaf, oet, oel)) {
-        best_excl_t = oet;
-        best_excl_leaf = oel;
-        best_excl_mat = oem;
+      if constexpr (SELECTS) {
+        const bool take = later(best_t, best_leaf, ot, ol), take_excl = later(best_excl_t, best_excl_leaf, oet, oel);
+        best_t = take ? ot : best_t;
+        best_leaf = take ? ol : best_leaf;
+        best_mat = take ? om : best_mat;
+        best_excl_t = take_excl ? oet : best_excl_t;
+        best_excl_leaf = take_excl ? oel : best_excl_leaf;
+        best_excl_mat = take_excl ? oem : best_excl_mat;
+      } else {
+        if (later(best_t, best_leaf, ot, ol)) {
+          best_t = ot;
+          best_leaf = ol;
+          best_mat = om;
+        }
+        if (later(best_excl_t, best_excl_leaf, oet, oel)) {
+          best_excl_t = oet;
+          best_excl_leaf = oel;
+          best_excl_mat = oem;
+        }
       }
       hit_open = hit_open || oopen != 0u;
       hit_dups += odups;
@@ -3350,17 +3413,19 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
     if (cur.remaining != 0u && !(mats[mat_index].transparency == 0.0)) {
       RTC_STAMP(5);
       it_share += 2u;
+      using BehindVisitor = BehindVisitorT<WORLD == 2>;
       BehindVisitor bv;
       bv.hit_leaf = hv.leaf;
       bv.hit_t = t;
       RTC_COUNT(4);
+      RTC_AUX_ADD(7, 1);  // (diagnostic builds: the passes of the wave, counted by its first active lane - RTC_COUNT's are lane 0's)
       {
         RTC_HIST_BEGIN();
         trace<CSG, WORLD, BehindVisitor, TRAV, BOX, MOTION>(S, recs, cull, ray, bv, it_overflow, trav_stack, member, stride, mo.disp, tm);
         RTC_HIST_END(2);
       }
         RTC_STAMP(6);
-      bv.flush();
+      bv.template flush<true>();
       const double hit_ior = mats[mat_index].ior;
       if (bv.best_leaf != RTC_NO_LEAF) n1 = mats[RTC_CHECK_INDEX(RTC_OOB_MATERIALS, bv.best_mat, RTC_AVAIL(3))].ior;
       if (!bv.hit_open) {
