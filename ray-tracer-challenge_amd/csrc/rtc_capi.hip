@@ -3966,6 +3966,13 @@ int rtc_get_stats(rtc_scene* s, rtc_stats* out) {
     // (the containers pass of the kernels without groups: its wave invocations counted by the first active lane, and the wave steps
     // of its exact tests - prof5[7], prof5[4])
     std::fprintf(stderr, "rtc containers pass: waves traced %llu | wave steps of exact tests %llu\n", h.prof5[7], h.prof5[4]);
+    // (the specular power of the point-light branch, by light - the first and all after it; a cooperative iteration that deals
+    // its lights counts under its first active lane's -: wave executions, those in which no lane's material has a specular
+    // term at a base <= 1, and the lanes inside both - prof5[0..3], two 32-bit counts a word: one launch's counts, which stay
+    // far below 2^32; the low word would carry into the high one if launches were summed by the thousand)
+    for (int l = 0; l < 2; ++l)
+      std::fprintf(stderr, "rtc specular power, light %s: wave executions %llu, no lane needs it %llu | lanes %llu, in those %llu\n", l ? "1+" : "0",
+                   h.prof5[l] & 0xFFFFFFFFull, h.prof5[l] >> 32, h.prof5[2 + l] & 0xFFFFFFFFull, h.prof5[2 + l] >> 32);
     std::fprintf(stderr, "rtc trace cycles by lanes with a ray (1-2, 3-4, 5-8, 9-16, 17-32, 33-48, 49-64):");
     for (int k = 0; k < 3; ++k) {
       std::fprintf(stderr, " %s", k == 0 ? "closest" : k == 1 ? "| shadow" : "| behind");

@@ -498,7 +498,7 @@ struct DevStats {
   unsigned long long prof[16];  // wave cycles per section
   unsigned long long prof2[8];  // trace invocations (wave level) and active lanes: closest, shadow, behind
   unsigned long long prof3[21]; // wave cycles in traces by lanes with a ray: [closest, shadow, behind][1-2, 3-4, 5-8, 9-16, 17-32, 33-48, 49-64]
-  unsigned long long prof5[8];  // [5], [6]: wave cycles of all group walks at nodes / at leaves; [4]: wave steps of the containers pass's exact tests (kernels without groups), [7]: its wave invocations (RTC_AUX_ADD; [0]..[3]: free)
+  unsigned long long prof5[8];  // [5], [6]: wave cycles of all group walks at nodes / at leaves; [4]: wave steps of the containers pass's exact tests (kernels without groups), [7]: its wave invocations (RTC_AUX_ADD); [0], [1]: wave executions of the point-light specular power for light 0 / the later lights, low word all, high word those no lane needs; [2], [3]: the lanes inside them, likewise
   unsigned long long prof6[24]; // group walks by kind of trace [closest, shadow, containers][walks, lanes, node steps, leaf steps, lanes at nodes, lanes at leaves, wave cycles at nodes, at leaves]
   unsigned long long oob[8];    // accesses outside their allocation, counted and not made (RTC_OOB_*)
   unsigned long long prof7[18]; // exact cube tests of the root loop's kind-by-kind phase 2 [closest, shadow, containers][tests (lanes), with tmax < 0, named by cube_entirely_behind, wave steps, wave steps left without the tmax < 0 tests, without the named ones]

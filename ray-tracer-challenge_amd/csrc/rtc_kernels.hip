@@ -158,6 +158,9 @@ __device__ __forceinline__ bool rtc_in_bounds(uint32_t kind, bool ok) {
 #ifndef RTC_CUBE_BEHIND_EARLY_OUT
 #define RTC_CUBE_BEHIND_EARLY_OUT 1  // shadow traces of the simple kernels that cull by boxes skip a cube behind the ray's origin (cube_entirely_behind)
 #endif
+#ifndef RTC_SPECULAR_SKIP
+#define RTC_SPECULAR_SKIP 1          // the simple kernels skip the specular power of a point light in a wave none of whose lanes' materials has a specular term (render_body, kSpecularSkip)
+#endif
 #ifndef RTC_CONTAINERS_SOLIDS
 #define RTC_CONTAINERS_SOLIDS 1      // simple worlds: the containers pass drops a solid whose bound lies behind the origin and a plane whose entry cannot be negative (trace(), kSolids)
 #endif
@@ -2831,6 +2834,9 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
   // again after almost every pixel, so nearly every push and pop stays here: the pops no longer wait for memory and the
   // 2048 resident waves no longer cycle 59 MB of stack lines through the L2s (142 MB written per cover frame).
   constexpr bool SIMPLE = WORLD == 2, FLAT = WORLD >= 1;
+  // (specular_skip: the point-light branch of the five simple kernels; every other kernel keeps its instructions.  What was
+  // counted and measured: profiles/specular_skip/)
+  constexpr bool kSpecularSkip = SIMPLE && RTC_SPECULAR_SKIP;
   constexpr int LDS_LEVELS = (FLAT || !LDS) ? 2 : 1;  // (what fits beside the tables at WAVES work-groups per CU)
   __shared__ Quad2 lds_pend[4][LDS_LEVELS][4][64];
   // The colour a lane has accumulated for its pixel: touched once per iteration and when the pixel is finished, live
@@ -3861,8 +3867,27 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
             const double reflect_dot_eye = ((-rx) * ex + (-ry) * ey) + (-rz) * ez;
             if (reflect_dot_eye > 0.0) {
               const uint32_t n = mat.shininess_int;
-              const double ks = mat.specular * (n != 0u && reflect_dot_eye < kInf ? pow_small_int(reflect_dot_eye, n)
-                                                                                  : zig_pow(reflect_dot_eye, mat.shininess));
+              // (specular_skip) a lane whose material has no specular term keeps ks = specular, the zero itself: for
+              // 0 < x <= 1 pow_small_int's squaring loop yields a finite value >= +0, and (+-0) * that is +-0 with
+              // specular's sign.  zig_pow's path (n == 0: it can overflow, and 0 * inf is a NaN) and x > 1 stay as they
+              // were.  The power is a loop, so the wave branches around it when no lane needs it.
+              // (written nested on purpose: the compiler flattens it to the one-line form's three compares, but lays the kernel out
+              // differently, and a world without such a material - cubes.json - keeps the parent's time: profiles/HISTORY.md)
+              bool ks_is_specular = false;
+              if (mat.specular == 0.0) ks_is_specular = n != 0u && reflect_dot_eye <= 1.0;
+#ifdef RTC_PROFILE
+              {  // (diagnostic builds: wave executions of the power by light, those no lane needs, and the lanes inside them;
+                 // two 32-bit counts a word: good for one launch's counts - under 2^32 lanes -, not for sums over many)
+                const unsigned long long lanes_ = static_cast<unsigned long long>(__builtin_popcountll(__ballot(true)));
+                const unsigned long long idle_ = __ballot(!ks_is_specular) == 0ull ? 1ull : 0ull;
+                RTC_AUX_ADD(li != 0u ? 1 : 0, 1ull + (idle_ << 32));
+                RTC_AUX_ADD(li != 0u ? 3 : 2, lanes_ + ((idle_ * lanes_) << 32));
+              }
+#endif
+              double ks = mat.specular;
+              if (!(kSpecularSkip && ks_is_specular))
+                ks = mat.specular * (n != 0u && reflect_dot_eye < kInf ? pow_small_int(reflect_dot_eye, n)
+                                                                       : zig_pow(reflect_dot_eye, mat.shininess));
               pr = L[3] * ks;
               pg = L[4] * ks;
               pb = L[5] * ks;
