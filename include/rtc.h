@@ -627,6 +627,54 @@ typedef struct rtc_occlusion {
  */
 int rtc_scene_set_occlusion(rtc_scene *scene, const rtc_occlusion *occlusion);
 
+/* ---- shadow filters: light through a filtering material is dimmed and tinted, not blocked ---- */
+/*
+ * A material row has a shadow filter: three doubles (fr, fg, fb), each finite and in [0, 1]; (0, 0, 0) is the material as
+ * it is - it blocks light.
+ *
+ * The step.  Every call of World.isShadowed that a LIGHT makes - the point and spot branch of the lights loop, and each
+ * sample of an area light - yields a transmittance instead of a bool:
+ *   T = (1.0, 1.0, 1.0)
+ *   for every entry (leaf, t) the reference's intersect would have appended, with 0.0 <= t < distance and the leaf
+ *   casting a shadow:
+ *     T.r = T.r * fr[material of leaf];  T.g = T.g * fg[...];  T.b = T.b * fb[...]
+ *   blocked = T.r == 0.0 && T.g == 0.0 && T.b == 0.0          (the walk may stop as soon as this holds)
+ * The entries that count are the ones isShadowed counts today: a sphere in the way gives two, a plane or a triangle one, a
+ * csg unit those its rule lets through; an entry behind the origin (t < 0.0), or at or beyond the light (t >= distance),
+ * gives none.  The order of the product is the walk's and is free: every factor is in [0, 1], a zero factor gives exactly
+ * zero in any order, and two factors commute exactly; only three or more partial factors can differ, in the last bits.
+ *
+ * Point and spot lights (Material.lighting).  Where `blocked` holds, the shadowed branch as it is.  Otherwise
+ *   (dr, dg, db) = (dr * T.r, dg * T.g, db * T.b)     the diffuse term, after the spot factor
+ *   (pr, pg, pb) = (pr * T.r, pg * T.g, pb * T.b)     the specular term, after the spot factor
+ * before the sum (ambient + diffuse) + specular.  T == (1, 1, 1) leaves the bits as they are.
+ *
+ * Area lights.  Sample k yields T_k; the scalar intensity = lit / samples becomes three values,
+ *   intensity.c = (((0.0 + T_0.c) + T_1.c) + ...) / samples        per channel, in the loop's order: v outer, u inner
+ * and (dr / samples) * intensity becomes (dr / samples) * intensity.r, and so for g and b.  When every T_k is (0, 0, 0) or
+ * (1, 1, 1) the sum is the integer count and the bits are the ones without a table.
+ *
+ * Unchanged: shadow_matters, the light_dot_normal test and the spot cone's early answer, which decide whether isShadowed
+ * is called and traced at all, and the counts shadow_calls and shadow_traced.  The occlusion rays of
+ * rtc_scene_set_occlusion stay binary: any entry of a casts_shadow leaf within the radius occludes, whatever its filter -
+ * a pane of glass still darkens the corner behind it.  A leaf with "shadow": false contributes nothing, whatever its
+ * material's filter.  Only * and + and comparisons are added, each correctly rounded.
+ */
+typedef struct rtc_shadow_filters {
+  uint32_t n_materials; /* the handle's material count (rtc_scene_desc::n_materials) */
+  const double *rgb;    /* [n_materials][3], each finite and in [0, 1]; NULL: all zeros */
+} rtc_shadow_filters;
+
+/*
+ * This handle's shadow filters for every render entry point.  Validated before anything changes:
+ * RTC_ERR_INVALID_ARGUMENT for a value that is not finite or outside [0, 1], and then for an n_materials other than the
+ * handle's; the previous table stays in force.  NULL, or a table whose every row is zero, gives the handle its previous
+ * kernels back.  A clone starts with its source's table; rtc_render's band clones follow.  A handle with a non-zero row
+ * renders with the shadow-filter kernels (rtc_render_kernel_sfilter, _sfilter_bigworld).  librtc_multi renders without
+ * shadow filters.  rtc_scene_desc and RTC_ABI_VERSION are as they were.
+ */
+int rtc_scene_set_shadow_filters(rtc_scene *scene, const rtc_shadow_filters *filters);
+
 /* ---- adaptive sampling: progressive passes only for tiles still noisy ---- */
 #define RTC_ADAPTIVE_MAX_TILE 1024u
 

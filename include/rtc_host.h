@@ -23,7 +23,8 @@
  *                        rtch_scene_bumps, through rtc_scene_set_bumps; its triangles' texture rows,
  *                        rtch_scene_mesh_uvs, through rtc_scene_set_mesh_uvs; its materials' roughness,
  *                        rtch_scene_gloss, through rtc_scene_set_gloss; its materials' occlusion radii,
- *                        rtch_scene_occlusion, through rtc_scene_set_occlusion)
+ *                        rtch_scene_occlusion, through rtc_scene_set_occlusion; its materials' shadow filters,
+ *                        rtch_scene_shadow_filters, through rtc_scene_set_shadow_filters)
  *
  * Every function that returns int returns 0 on success; otherwise rtch_last_error()
  * holds "<ZigStyleErrorName>: detail" (thread-local).
@@ -97,6 +98,12 @@ int rtch_scene_gloss(void *handle, double *reflection, double *transmission, uin
  * value is non-zero.  *present: 1 when a material of the file has the key.  Pass them to rtc_scene_set_occlusion.
  * rtch_scene_render applies them. */
 int rtch_scene_occlusion(void *handle, double *radius, uint32_t *samples, uint64_t *seed, int *present, uint32_t n);
+/* The materials' "shadow-filter" (DESIGN.md section 22), in mat_* order, three doubles a row: a number f - (f, f, f) -, an
+ * array [r, g, b], or true - the material's transparency in each channel -, every value finite and in [0, 1].  n must be
+ * the description's n_materials; rgb holds 3 * n doubles.  A material with the key is a mat_* row of its own only when a
+ * value is non-zero.  *present: 1 when a material of the file has the key.  Pass them to rtc_scene_set_shadow_filters.
+ * rtch_scene_render applies them. */
+int rtch_scene_shadow_filters(void *handle, double *rgb, int *present, uint32_t n);
 int rtch_scene_camera(void *handle, uint32_t width, uint32_t height, rtc_camera *out);
 int rtch_camera_rotate(void *handle, double angle);
 int rtch_camera_move(void *handle, double distance);

@@ -221,7 +221,7 @@ BUMP_NONE, BUMP_NOISE, BUMP_RIPPLES = 0, 1, 2  # RTC_BUMP_*
 RTC_SPHERE, RTC_PLANE, RTC_CUBE, RTC_CYLINDER, RTC_TRIANGLE, RTC_SMOOTH_TRIANGLE, RTC_CONE, RTC_TORUS = range(8)
 # the options that select a kernel family on a handle that does not need it (set_option; tests and tools/time_scenes.py)
 KERNEL_OPTIONS = ("sampling_kernels", "motion_kernels", "spot_kernels", "bump_kernels", "torus_kernels", "meshuv_kernels", "gloss_kernels",
-                  "occlusion_kernels")
+                  "occlusion_kernels", "shadow_filter_kernels")
 # texture mappings (rtc.h); RTC_TEX_MESH: (u, v) from the hit triangle's texture row
 RTC_TEX_SPHERICAL, RTC_TEX_PLANAR, RTC_TEX_CYLINDRICAL, RTC_TEX_CUBIC, RTC_TEX_MESH = range(5)
 BUMP_MAX_OCTAVES = 16  # RTC_BUMP_MAX_OCTAVES
@@ -281,6 +281,28 @@ def occlusion_struct(occlusion):
     return o, r
 
 
+class ShadowFilters(C.Structure):
+    """struct rtc_shadow_filters (include/rtc.h): three doubles per material row, the share of a light's red, green and blue
+    that an entry of the material lets through."""
+
+    _fields_ = [("n_materials", C.c_uint32), ("rgb", C.POINTER(C.c_double))]
+
+
+def shadow_filters_struct(filters):
+    """(ShadowFilters, the array it points into) of a dict of "rgb" ((n, 3); None: all zeros, with "n_materials")
+    (GpuScene.set_shadow_filters); the array must outlive the struct's use."""
+    rgb = filters.get("rgb")
+    if rgb is None:
+        n = int(filters["n_materials"])
+    else:
+        rgb = np.ascontiguousarray(rgb, dtype=np.float64)
+        if rgb.ndim != 2 or rgb.shape[1] != 3:
+            raise ValueError(f"shadow filters: an rgb array of shape {rgb.shape}, (n, 3) expected")
+        n = rgb.shape[0]
+    f = ShadowFilters(n, rgb.ctypes.data_as(C.POINTER(C.c_double)) if rgb is not None else None)
+    return f, rgb
+
+
 class Bump(C.Structure):
     """struct rtc_bump (include/rtc.h): a bump per material row (kind BUMP_NONE: the material as it is)."""
 
@@ -322,13 +344,14 @@ RTC_SYMBOLS = ["rtc_scene_create", "rtc_scene_clone", "rtc_scene_destroy", "rtc_
                "rtc_scene_set_sample_pass", "rtc_scene_accumulate_device", "rtc_scene_set_motion",
                "rtc_scene_adaptive_begin_device", "rtc_scene_adaptive_accumulate_device", "rtc_scene_adaptive_step", "rtc_render_adaptive",
                "rtc_scene_set_spots", "rtc_scene_set_bumps", "rtc_scene_set_mesh_uvs", "rtc_scene_set_gloss",
-               "rtc_scene_set_occlusion"]
+               "rtc_scene_set_occlusion", "rtc_scene_set_shadow_filters"]
 # (... and include/rtc_diag.h: diagnostics and tuning, for the tests, bench.py and tools/)
 RTC_DIAG_SYMBOLS = ["rtc_set_option", "rtc_last_kernel_name", "rtc_get_schedule", "rtc_get_chunk_times", "rtc_diag_build_tables", "rtc_diag_root_boxes", "rtc_diag_root_spheres"]
 HOST_SYMBOLS = ["rtch_last_error", "rtch_scene_load", "rtch_scene_free", "rtch_scene_desc", "rtch_scene_camera",
                 "rtch_camera_rotate", "rtch_camera_move", "rtch_camera_make", "rtch_canvas_ppm", "rtch_canvas_rgba8", "rtch_scene_render", "rtch_set_loader_threads",
                 "rtch_scene_lights", "rtch_scene_sampling", "rtch_scene_passes", "rtch_scene_motion", "rtch_scene_adaptive",
-                "rtch_scene_spots", "rtch_scene_bumps", "rtch_scene_mesh_uvs", "rtch_scene_gloss", "rtch_scene_occlusion"]
+                "rtch_scene_spots", "rtch_scene_bumps", "rtch_scene_mesh_uvs", "rtch_scene_gloss", "rtch_scene_occlusion",
+                "rtch_scene_shadow_filters"]
 
 MULTI_SYMBOLS = ["rtc_multi_create", "rtc_multi_destroy", "rtc_multi_render", "rtc_multi_render_rgba8", "rtc_multi_render_device", "rtc_multi_render_rgba8_device",
                  "rtc_multi_synchronize", "rtc_multi_stream", "rtc_multi_get_stats", "rtc_multi_balance", "rtc_multi_last_error"]
@@ -393,6 +416,7 @@ def hip_lib():
         lib.rtc_scene_set_mesh_uvs.argtypes = [C.c_void_p, C.POINTER(MeshUvs)]
         lib.rtc_scene_set_gloss.argtypes = [C.c_void_p, C.POINTER(Gloss)]
         lib.rtc_scene_set_occlusion.argtypes = [C.c_void_p, C.POINTER(Occlusion)]
+        lib.rtc_scene_set_shadow_filters.argtypes = [C.c_void_p, C.POINTER(ShadowFilters)]
         lib.rtc_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.POINTER(Adaptive), C.c_void_p, C.c_void_p]
         lib.rtc_scene_destroy.argtypes = [C.c_void_p]
         lib.rtc_scene_destroy.restype = None
@@ -450,6 +474,7 @@ def host_lib():
         lib.rtch_scene_mesh_uvs.argtypes = [C.c_void_p, _dp, C.c_uint32]
         lib.rtch_scene_gloss.argtypes = [C.c_void_p, _dp, _dp, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.c_uint32]
         lib.rtch_scene_occlusion.argtypes = [C.c_void_p, _dp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.c_uint32]
+        lib.rtch_scene_shadow_filters.argtypes = [C.c_void_p, _dp, C.POINTER(C.c_int), C.c_uint32]
         lib.rtch_scene_adaptive.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(Adaptive)]
         lib.rtch_scene_camera.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Camera)]
         lib.rtch_camera_rotate.argtypes = [C.c_void_p, C.c_double]
@@ -668,6 +693,15 @@ class HostScene:
         out["samples"], out["seed"] = samples.value, seed.value
         return out if present.value else None
 
+    def shadow_filters(self):
+        """The materials' "shadow-filter" rows (rtch_scene_shadow_filters), in mat_* order: a dict of "rgb" (n, 3) - what
+        GpuScene.set_shadow_filters takes -, or None when no material of the file has the key."""
+        n = self.desc.n_materials
+        out = {"rgb": np.zeros((n, 3))}
+        present = C.c_int()
+        _check_host(host_lib().rtch_scene_shadow_filters(self._h, out["rgb"].ctypes.data_as(_dp), C.byref(present), n))
+        return out if present.value else None
+
     def adaptive(self):
         """The camera's "sampling": {"adaptive": ...} of the scene file (rtch_scene_adaptive): an Adaptive whose max_passes
         is "passes", or None when the file has none."""
@@ -802,6 +836,15 @@ class GpuScene:
             return
         o, _keep = occlusion_struct(occlusion)
         _check_hip(hip_lib().rtc_scene_set_occlusion(self._s, C.byref(o)))
+
+    def set_shadow_filters(self, filters):
+        """rtc_scene_set_shadow_filters: a dict of "rgb" ((n_materials, 3)) (HostScene.shadow_filters()); None: no filter -
+        as every row zero, the handle's previous kernels."""
+        if filters is None:
+            _check_hip(hip_lib().rtc_scene_set_shadow_filters(self._s, None))
+            return
+        f, _keep = shadow_filters_struct(filters)
+        _check_hip(hip_lib().rtc_scene_set_shadow_filters(self._s, C.byref(f)))
 
     def accumulate_device(self, accum, stream=None):
         """rtc_scene_accumulate_device: an Accum, enqueued on `stream` (None: the handle's own) after this handle's renders."""

@@ -167,6 +167,20 @@ __global__ void rtc_render_kernel_occl_bigworld(const DevScene S, const DevCamer
                                                 const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
                                                 const DevBumps bumps, const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl);
 }
+// The shadow-filter kernels (rtc_scene_set_shadow_filters: light through a filtering material is dimmed and tinted, not
+// blocked): the occlusion kernels' tables and edge, and the filter rows (DevShadowFilter) as one more argument.
+extern "C" {
+__global__ void rtc_render_kernel_sfilter(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                          double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                          const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                          const DevBumps bumps, const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl,
+                                          const DevShadowFilter sfilt);
+__global__ void rtc_render_kernel_sfilter_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                                   double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                                   const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                                   const DevBumps bumps, const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl,
+                                                   const DevShadowFilter sfilt);
+}
 // Progressive rendering's accumulation (rtc_accum.hip): the grid's blocks for n pixels (the noise partials it writes, at
 // most) and the enqueue of its kernels.
 uint32_t rtcAccumBlocks(size_t n_pixels, bool wide);
@@ -383,7 +397,7 @@ bool tablesInLds(const rtc_scene* s) {
 // `ms`, and both: `area_ms`; the motion kernels both and DevMotion: `motion`; the spot kernels those three and DevSpots:
 // `spot`; the bump kernels those four and DevBumps: `bump` - the torus kernels take the same arguments and travel in `bump` too;
 // the meshuv kernels those five and DevMeshUvs: `meshuv`; the gloss kernels those six and DevGloss: `gloss`;
-// the occlusion kernels those seven and DevOcclusion: `occl`)
+// the occlusion kernels those seven and DevOcclusion: `occl`; the shadow-filter kernels those eight and DevShadowFilter: `sfilt`)
 struct KernelChoice {
   decltype(&rtc_render_kernel) fn;
   const char* name;
@@ -396,6 +410,7 @@ struct KernelChoice {
   decltype(&rtc_render_kernel_meshuv) meshuv = nullptr;
   decltype(&rtc_render_kernel_gloss) gloss = nullptr;
   decltype(&rtc_render_kernel_occl) occl = nullptr;
+  decltype(&rtc_render_kernel_sfilter) sfilt = nullptr;
   KernelChoice(decltype(&rtc_render_kernel) f, const char* n) : fn(f), name(n) {}
   KernelChoice(decltype(&rtc_render_kernel_area) a, const char* n) : fn(nullptr), name(n), area(a) {}
   KernelChoice(decltype(&rtc_render_kernel_ms) m, const char* n) : fn(nullptr), name(n), ms(m) {}
@@ -406,11 +421,12 @@ struct KernelChoice {
   KernelChoice(decltype(&rtc_render_kernel_meshuv) uk, const char* n) : fn(nullptr), name(n), meshuv(uk) {}
   KernelChoice(decltype(&rtc_render_kernel_gloss) gk, const char* n) : fn(nullptr), name(n), gloss(gk) {}
   KernelChoice(decltype(&rtc_render_kernel_occl) ok, const char* n) : fn(nullptr), name(n), occl(ok) {}
+  KernelChoice(decltype(&rtc_render_kernel_sfilter) fk, const char* n) : fn(nullptr), name(n), sfilt(fk) {}
   void launch(uint32_t blocks, hipStream_t stream, const rtc_scene* s, const DevScene& dev, const DevCamera& cam, const DevPixelMap& map,
               uint32_t max_depth, double* d_out, DevStats* st_now, DevStats* st_next) const {
     DevSampling smp = s->sampling;  // (the pass's area-light offset, P * N * S: N is the camera's whole image)
     smp.pixel_base = static_cast<unsigned long long>(smp.sample_base) * (static_cast<unsigned long long>(cam.hsize) * cam.vsize);
-    if (motion || spot || bump || meshuv || gloss || occl) {
+    if (motion || spot || bump || meshuv || gloss || occl || sfilt) {
       // the handle's root tables with the moving roots' bounds (or the scene's, all displacements zero: the option), and
       // the scene's area rows (or zero rows: a point-only table); the spot kernels also the handle's spot rows (or zero
       // rows, every flag 0: the option)
@@ -426,7 +442,17 @@ struct KernelChoice {
         mo.disp = m->disp.p;
       }
       const DevAreaLights area = s->area_kernel ? s->area : DevAreaLights{s->tab->zero_rows.p, s->area.seed};
-      if (occl) {  // (the handle's radius rows, or zero rows, no material occluded: the option; and the gloss kernels' tables)
+      if (sfilt) {  // (the handle's filter rows, or zero rows, every material opaque: the option; and the occlusion kernels' tables)
+        const DevSpots sp{s->spots ? s->spots->row.p : s->tab->zero_rows.p};
+        const DevBumps bp{s->bumps ? s->bumps->row.p : s->tab->zero_bump.p};
+        const DevMeshUvs uv{s->mesh_uvs ? s->mesh_uvs->row.p : nullptr};
+        const DevGloss gl{s->gloss ? s->gloss->row.p : s->tab->zero_bump.p, s->gloss ? s->gloss->key : 0ull};
+        const DevOcclusion oc{s->occlusion ? s->occlusion->row.p : s->tab->zero_bump.p, s->occlusion ? s->occlusion->key : 0ull,
+                              s->occlusion ? s->occlusion->samples : 1u};
+        // (three doubles per material, 3 <= RTC_BUMP_ROW: the zero bump rows serve as zero filter rows)
+        const DevShadowFilter sf{s->shadow_filters ? s->shadow_filters->row.p : s->tab->zero_bump.p};
+        hipLaunchKernelGGL(sfilt, dim3(blocks), dim3(256), 0, stream, md, cam, map, max_depth, d_out, st_now, st_next, area, smp, mo, sp, bp, uv, gl, oc, sf);
+      } else if (occl) {  // (the handle's radius rows, or zero rows, no material occluded: the option; and the gloss kernels' tables)
         const DevSpots sp{s->spots ? s->spots->row.p : s->tab->zero_rows.p};
         const DevBumps bp{s->bumps ? s->bumps->row.p : s->tab->zero_bump.p};
         const DevMeshUvs uv{s->mesh_uvs ? s->mesh_uvs->row.p : nullptr};
@@ -491,6 +517,10 @@ bool glossKernels(const rtc_scene* s) { return s->gloss != nullptr || rtcOptions
 // The occlusion kernels run when a row of the handle's radius table is non-zero (rtc_scene_set_occlusion keeps no other
 // table) - whatever else the handle holds: they are the gloss walk - or, for tests, whenever option "occlusion_kernels" is set.
 bool occlusionKernels(const rtc_scene* s) { return s->occlusion != nullptr || rtcOptions().occlusion_kernels != 0.0; }
+// The shadow-filter kernels run when a row of the handle's filter table is non-zero (rtc_scene_set_shadow_filters keeps no
+// other table) - whatever else the handle holds: they are the occlusion walk - or, for tests, whenever option
+// "shadow_filter_kernels" is set.
+bool shadowFilterKernels(const rtc_scene* s) { return s->shadow_filters != nullptr || rtcOptions().shadow_filter_kernels != 0.0; }
 #define RTC_KERNEL(k) KernelChoice{k, #k}
 // The general kernel at three waves per SIMD (rtc_render_kernel3): forced by option "waves3", else what the handle's
 // trial measured (KernelTune in launch()).
@@ -517,6 +547,7 @@ KernelChoice ldsKernel(const rtc_scene* s, const DevPixelMap& map) {
   return s->ext_kernel ? RTC_KERNEL(rtc_render_kernel_ext) : RTC_KERNEL(rtc_render_kernel);
 }
 KernelChoice renderKernel(const rtc_scene* s, const DevPixelMap& map) {
+  if (shadowFilterKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_sfilter) : RTC_KERNEL(rtc_render_kernel_sfilter_bigworld);
   if (occlusionKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_occl) : RTC_KERNEL(rtc_render_kernel_occl_bigworld);
   if (glossKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_gloss) : RTC_KERNEL(rtc_render_kernel_gloss_bigworld);
   if (meshuvKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_meshuv) : RTC_KERNEL(rtc_render_kernel_meshuv_bigworld);
@@ -536,6 +567,7 @@ KernelChoice renderKernel(const rtc_scene* s, const DevPixelMap& map) {
 
 // Work-groups of the launch's kernel that are resident at once, and the waves in them.
 uint32_t residentBlocksAlone(const rtc_scene* s, const DevPixelMap& map) {
+  if (shadowFilterKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_sfilt_lds : s->blocks_per_cu_sfilt_big);
   if (occlusionKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_occl_lds : s->blocks_per_cu_occl_big);
   if (glossKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_gloss_lds : s->blocks_per_cu_gloss_big);
   if (meshuvKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_meshuv_lds : s->blocks_per_cu_meshuv_big);
@@ -947,7 +979,7 @@ int launch(rtc_scene* s, const rtc_camera& cam, const DevPixelMap& map_in, uint3
   int trial_slot = -1;
   {
     rtc_scene::KernelTune& T = s->tune;
-    const bool eligible = !samplingKernels(s) && !motionKernels(s) && !spotKernels(s) && !bumpKernels(s) && !torusKernels(s) && !meshuvKernels(s) && !glossKernels(s) && !occlusionKernels(s) &&  // (the sampling, motion, spot, bump, torus, meshuv, gloss and occlusion kernels have no three-wave form)
+    const bool eligible = !samplingKernels(s) && !motionKernels(s) && !spotKernels(s) && !bumpKernels(s) && !torusKernels(s) && !meshuvKernels(s) && !glossKernels(s) && !occlusionKernels(s) && !shadowFilterKernels(s) &&  // (the sampling, motion, spot, bump, torus, meshuv, gloss, occlusion and shadow-filter kernels have no three-wave form)
                           ((s->general3_ok && rtcOptions().waves3 < 0.0 && tablesInLds(s) &&
                             !(s->tab && s->tab->handles.load(std::memory_order_relaxed) > 1) &&
                             static_cast<double>(map.n_chunks) >= 4.0 * 4.0 * s->n_cus * s->blocks_per_cu_lds) ||
@@ -2335,6 +2367,10 @@ int uploadTables(const rtc_scene_desc& d, const SceneTraits& traits, const HostT
     s->blocks_per_cu_occl_lds = static_cast<uint32_t>(std::max(nb, 1));
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_occl_bigworld, 256, 0));
     s->blocks_per_cu_occl_big = static_cast<uint32_t>(std::max(nb, 1));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_sfilter, 256, 0));  // (the shadow-filter kernels: one pair for every world)
+    s->blocks_per_cu_sfilt_lds = static_cast<uint32_t>(std::max(nb, 1));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_sfilter_bigworld, 256, 0));
+    s->blocks_per_cu_sfilt_big = static_cast<uint32_t>(std::max(nb, 1));
     if (const int v = static_cast<int>(rtcOptions().blocks_per_cu); v >= 1) {  // (tuning option)
       s->blocks_per_cu_lds = std::min<uint32_t>(s->blocks_per_cu_lds, v), s->blocks_per_cu_big = std::min<uint32_t>(s->blocks_per_cu_big, v);
       s->blocks_per_cu_ms_lds = std::min<uint32_t>(s->blocks_per_cu_ms_lds, v), s->blocks_per_cu_ms_big = std::min<uint32_t>(s->blocks_per_cu_ms_big, v);
@@ -2345,6 +2381,7 @@ int uploadTables(const rtc_scene_desc& d, const SceneTraits& traits, const HostT
       s->blocks_per_cu_meshuv_lds = std::min<uint32_t>(s->blocks_per_cu_meshuv_lds, v), s->blocks_per_cu_meshuv_big = std::min<uint32_t>(s->blocks_per_cu_meshuv_big, v);
       s->blocks_per_cu_gloss_lds = std::min<uint32_t>(s->blocks_per_cu_gloss_lds, v), s->blocks_per_cu_gloss_big = std::min<uint32_t>(s->blocks_per_cu_gloss_big, v);
       s->blocks_per_cu_occl_lds = std::min<uint32_t>(s->blocks_per_cu_occl_lds, v), s->blocks_per_cu_occl_big = std::min<uint32_t>(s->blocks_per_cu_occl_big, v);
+      s->blocks_per_cu_sfilt_lds = std::min<uint32_t>(s->blocks_per_cu_sfilt_lds, v), s->blocks_per_cu_sfilt_big = std::min<uint32_t>(s->blocks_per_cu_sfilt_big, v);
     }
   }
   DevScene& D = s->dev;
@@ -2979,6 +3016,43 @@ int rtc_scene_set_occlusion(rtc_scene* s, const rtc_occlusion* occlusion) {
   return RTC_OK;
 }
 
+// ---- shadow filters
+// Validated before anything changes: first the table's own values - so that they are checked whatever the handle -, then
+// its material count against the handle's.  An rgb array that is NULL is all zeros; every row zero is no filter: the
+// handle's previous kernels.
+int rtc_scene_set_shadow_filters(rtc_scene* s, const rtc_shadow_filters* f) {
+  g_error.clear();
+  if (!s) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
+  bool any = false;
+  std::vector<double> rows;
+  if (f) {
+    const uint32_t n = f->n_materials;
+    rows.assign(3ull * n, 0.0);
+    for (uint32_t i = 0; i < n; ++i)
+      for (uint32_t c = 0; c < 3u; ++c) {
+        const double v = f->rgb ? f->rgb[3ull * i + c] : 0.0;
+        if (!std::isfinite(v)) return fail(RTC_ERR_INVALID_ARGUMENT, "shadow filters: material %u: a value that is not finite", i);
+        if (v < 0.0 || v > 1.0) return fail(RTC_ERR_INVALID_ARGUMENT, "shadow filters: material %u: value %g outside [0, 1]", i, v);
+        rows[3ull * i + c] = v;
+        any = any || v != 0.0;
+      }
+    if (n != s->dev.n_materials) return fail(RTC_ERR_INVALID_ARGUMENT, "shadow filters: n_materials %u, the scene has %u", n, s->dev.n_materials);
+  }
+  std::shared_ptr<const ShadowFilterTables> tables;  // (no row that lets light through: none)
+  if (any) {
+    auto t = std::make_shared<ShadowFilterTables>();
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(t->row.upload(rows));
+    tables = std::move(t);
+  }
+  // (the rows being replaced may still be read by a launch of this handle or of its band clones)
+  HIP_TRY(handleIdle(s));
+  for (rtc_scene* b : s->band) HIP_TRY(handleIdle(b));
+  s->shadow_filters = tables;
+  for (rtc_scene* b : s->band) b->shadow_filters = tables;  // (the band clones rtc_render renders a large frame with)
+  return RTC_OK;
+}
+
 // ---- adaptive sampling
 // The setting's own fields, and the image's tile count (T < 2^31)
 static int checkAdaptive(const rtc_adaptive* a, uint32_t hsize, uint32_t vsize, uint32_t* n_tiles) {
@@ -3204,6 +3278,9 @@ int rtc_scene_clone(const rtc_scene* src, rtc_scene** out) {
   s->occlusion = src->occlusion;  // (shared: read-only once made)
   s->blocks_per_cu_occl_lds = src->blocks_per_cu_occl_lds;
   s->blocks_per_cu_occl_big = src->blocks_per_cu_occl_big;
+  s->shadow_filters = src->shadow_filters;  // (shared: read-only once made)
+  s->blocks_per_cu_sfilt_lds = src->blocks_per_cu_sfilt_lds;
+  s->blocks_per_cu_sfilt_big = src->blocks_per_cu_sfilt_big;
   s->simple_kernel = src->simple_kernel;
   s->flat_kernel = src->flat_kernel;
   s->simple3_ok = src->simple3_ok;
@@ -3623,7 +3700,8 @@ int rtc_set_option(const char* name, double value) {
                {"sampling_kernels", &o.sampling_kernels}, {"motion_kernels", &o.motion_kernels},
                {"spot_kernels", &o.spot_kernels}, {"bump_kernels", &o.bump_kernels},
                {"torus_kernels", &o.torus_kernels}, {"meshuv_kernels", &o.meshuv_kernels},
-               {"gloss_kernels", &o.gloss_kernels}, {"occlusion_kernels", &o.occlusion_kernels}};
+               {"gloss_kernels", &o.gloss_kernels}, {"occlusion_kernels", &o.occlusion_kernels},
+               {"shadow_filter_kernels", &o.shadow_filter_kernels}};
   for (const auto& e : table)
     if (std::strcmp(e.name, name) == 0) {
       e.slot->set(value);

@@ -390,6 +390,14 @@ struct DevOcclusion {
   uint32_t samples;  // 1 .. RTC_OCCLUSION_MAX_SAMPLES
 };
 
+// Shadow filters (rtc_scene_set_shadow_filters): the extra argument of the shadow-filter kernels only.
+// Three doubles per material, in mat_* order: the share of a light's red, green and blue that an entry of the material lets
+// through, each in [0, 1] (0, 0, 0: the material blocks light); every row under the "shadow_filter_kernels" option on a
+// handle without a table is zero.
+struct DevShadowFilter {
+  const double* __restrict__ row;  // [n_materials][3]
+};
+
 struct DevCamera {
   double half_width, half_height, pixel_size;
   double inv[12];  // rows 0..2 of Camera._inverse_transform

@@ -73,6 +73,7 @@ struct RtcOptions {
   RtcOption meshuv_kernels{0.0};       // != 0: the meshuv kernels even on a handle without a mesh map (tests: against the handle's ordinary kernels)
   RtcOption gloss_kernels{0.0};        // != 0: the gloss kernels even on a handle without a rough material, every row zero (tests: against the handle's ordinary kernels)
   RtcOption occlusion_kernels{0.0};    // != 0: the occlusion kernels even on a handle without a radius, every row zero (tests: against the handle's ordinary kernels)
+  RtcOption shadow_filter_kernels{0.0};  // != 0: the shadow-filter kernels even on a handle without a filter, every row zero (tests: against the handle's ordinary kernels)
   RtcOption build_threads{0.0};        // threads of rtc_scene_create's candidate-BVH build (one top-level group each); 0: as many as the host allows, up to 8
 };
 inline RtcOptions& rtcOptions() {
@@ -171,6 +172,12 @@ struct OcclusionTables {
   uint32_t samples = 1u;
 };
 
+// A handle's shadow-filter rows (rtc_scene_set_shadow_filters): DevShadowFilter::row.  Read-only once made: a clone and the
+// band clones share it.
+struct ShadowFilterTables {
+  DevBuf<double> row;
+};
+
 // A handle's spot lights (rtc_scene_set_spots): DevSpots::row.  Read-only once made: a clone and the band clones share it.
 struct SpotTables {
   DevBuf<double> row;
@@ -231,6 +238,8 @@ struct rtc_scene {
   uint32_t blocks_per_cu_gloss_lds = 1, blocks_per_cu_gloss_big = 1;  // resident work-groups per CU of the gloss kernels
   std::shared_ptr<const OcclusionTables> occlusion;  // rtc_scene_set_occlusion; null: no row with a radius (a clone starts with its source's)
   uint32_t blocks_per_cu_occl_lds = 1, blocks_per_cu_occl_big = 1;  // resident work-groups per CU of the occlusion kernels
+  std::shared_ptr<const ShadowFilterTables> shadow_filters;  // rtc_scene_set_shadow_filters; null: no non-zero row (a clone starts with its source's)
+  uint32_t blocks_per_cu_sfilt_lds = 1, blocks_per_cu_sfilt_big = 1;  // resident work-groups per CU of the shadow-filter kernels
   bool simple3_ok = false;         // a simple world whose tables fit the three-waves-per-SIMD kernel's LDS (RTC_LDS3_*)
   void* d_csg_buf = nullptr;       // DevPixelMap::csg_buf, only for scenes with csg nodes
   size_t csg_buf_capacity = 0;     // bytes

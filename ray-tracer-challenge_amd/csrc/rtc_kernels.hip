@@ -726,7 +726,7 @@ __device__ __forceinline__ void visit_leaf(const DevScene& S, const BvhLeafRec& 
   const BvhLeafRec L = Lm;
   // isShadowed (world.zig:136-147) counts an entry only if its shape casts a shadow: a leaf that does not - a glass display
   // case around a mesh - has nothing a shadow trace could use, whatever its test would say.
-  if (V::kAnyHit && ((L.kind_flags >> 8) & 1u) == 0u) return;
+  if (V::kShadowOnly && ((L.kind_flags >> 8) & 1u) == 0u) return;
   const uint32_t leaf = L.leaf;
   const uint4 meta{L.kind_flags, L.xform, L.material, L.geom};
   if (meta.y != cur_xf) {  // Shape.intersect: ray.transform(_inverse_transform), shape.zig:314-318
@@ -1242,7 +1242,7 @@ __device__ __forceinline__ void traverse_bvh8(const DevScene& S, const uint32_t 
       g_base = h1.x;
       g_bits = (V::kAnyHit ? inner : permute_by_octant(inner, oct)) | (imask << 8);
       l_hits = hits & (h1.y >> 24);
-      if constexpr (V::kAnyHit) {
+      if constexpr (V::kShadowOnly) {
         // (a shadow trace does not even fetch the records of a leaf range none of whose shapes casts a shadow: bit 7 of
         // the range's meta byte, set at build time - in dragons.json the display case around every dragon is such a leaf
         // and a child of its group's root node: every shadow walk through a group used to fetch and test it)
@@ -1754,7 +1754,7 @@ __device__ __forceinline__ void trace(const DevScene& S, const RootRec* __restri
       }
       const Ray& root_ray = MOTION ? shifted : ray;
       if (FLAT || !(kf & RTC_ROOT_IS_GROUP)) {
-        if (!FLAT && V::kAnyHit && ((kf >> 8) & 1u) == 0u) continue;  // (a shadow trace: a shape that casts no shadow, see visit_leaf)
+        if (!FLAT && V::kShadowOnly && ((kf >> 8) & 1u) == 0u) continue;  // (a shadow trace: a shape that casts no shadow, see visit_leaf)
         const Ray lr = xform_ray(R.inv, root_ray);  // Shape.intersect: ray.transform(_inverse_transform)
         if constexpr (V::kAnyHit && RTC_ROOM_EARLY_OUT) {
           if ((kf & RTC_ROOT_ROOM) && segment_stays_inside_cube(lr, vis.t_limit())) continue;
@@ -1809,6 +1809,7 @@ __device__ __forceinline__ double group8_other(double x) {
 // lexicographic min of (t, depth-first leaf index) over entries with t >= 0.
 struct ClosestVisitor {
   static constexpr bool kAnyHit = false;  // the first entry that counts ends the trace: visiting order is free
+  static constexpr bool kShadowOnly = false;  // only entries of leaves that cast a shadow count: the others are not even tested
   double t = kInf;
   uint32_t leaf = RTC_NO_LEAF;
   uint32_t root = RTC_NO_LEAF;      // World.objects index when the hit leaf IS a top-level object
@@ -1878,6 +1879,7 @@ struct MotionClosestVisitor : ClosestVisitor {
 // isShadowed (world.zig:126-154): any entry with 0 <= t < distance on a casts_shadow leaf.
 struct ShadowVisitor {
   static constexpr bool kAnyHit = true;  // the first entry that counts ends the trace: visiting order is free
+  static constexpr bool kShadowOnly = true;
   double distance;
   bool shadowed = false;
   __device__ __forceinline__ void set_root(uint32_t) {}
@@ -1904,6 +1906,61 @@ struct ShadowVisitor {
   }
 };
 
+// A light's isShadowed with shadow filters (rtc.h's rtc_scene_set_shadow_filters): the product of the
+// filter rows of EVERY entry with 0 <= t < distance on a casts_shadow leaf - the entries ShadowVisitor::relevant accepts.
+// Not an any-hit walk: the walk hands every entry over exactly once, as it does to the containers pass, which counts them;
+// what kAnyHit would select besides - the slot-order descent, the room and cube early-outs that answer for a box without
+// enumerating its entries - stays off.  kShadowOnly keeps what holds for every walk that wants casts_shadow entries only:
+// leaves and leaf ranges that cast none are not fetched.  The trace may stop once all three channels are zero: a zero
+// factor gives exactly zero whatever follows.  The row is read by the lane that found the entry.  Compiled into the
+// shadow-filter kernels' translation unit only: no other unit has a use for it.
+#ifdef RTC_SFILT_TU
+struct FilterVisitor {
+  static constexpr bool kAnyHit = false;
+  static constexpr bool kShadowOnly = true;
+  double distance;
+  double tr = 1.0, tg = 1.0, tb = 1.0;  // the transmittance so far
+  const double* __restrict__ filter;    // DevShadowFilter::row, [n_materials][3]
+  __device__ __forceinline__ void set_root(uint32_t) {}
+  static constexpr bool kFrontOnly = true;
+  static constexpr bool kBehindOnly = false;
+  __device__ __forceinline__ double t_limit() const { return distance; }
+  __device__ __forceinline__ void entry(uint32_t, uint32_t casts_shadow, uint32_t material, double et, double, double) {
+    if (et >= 0.0 && et < distance && casts_shadow) {
+      const double* __restrict__ f = filter + 3ull * material;
+      tr = tr * f[0];
+      tg = tg * f[1];
+      tb = tb * f[2];
+    }
+  }
+  __device__ __forceinline__ bool relevant(uint32_t, uint32_t casts_shadow, double et) const {
+    return et >= 0.0 && et < distance && casts_shadow;
+  }
+  // (the box rules are ShadowVisitor's: an entry counts in the same range)
+  __device__ __forceinline__ bool cullf(float tn, float tf) const {
+    const float lim = static_cast<float>(distance);
+    return tf < -1e-4f * (1.0f + __builtin_fabsf(tf)) || tn > lim + 1e-4f * (1.0f + __builtin_fabsf(tn) + __builtin_fabsf(lim));
+  }
+  __device__ __forceinline__ float far_limit() const { return (static_cast<float>(distance) * 1.0001f + 1.0001e-4f) * 1.0002f; }
+  __device__ __forceinline__ bool cull_limits(float tn, float tf, float limit) const { return (tf < -1.0002e-4f) | (tn > limit); }
+  __device__ __forceinline__ void box_limits(float& lo, float& hi) const { lo = -1.0002e-4f; hi = far_limit(); }
+  __device__ __forceinline__ bool done() const { return tr == 0.0 && tg == 0.0 && tb == 0.0; }  // blocked
+  // (a cooperative trace: every lane of the group multiplied the factors of its own share of the roots; the butterfly's
+  // two sides form the same product of two, which commutes exactly, so every lane leaves with the same bits)
+  template <int STEP>
+  __device__ __forceinline__ void merge_step() {
+    tr = tr * group8_other<STEP>(tr);
+    tg = tg * group8_other<STEP>(tg);
+    tb = tb * group8_other<STEP>(tb);
+  }
+  __device__ __forceinline__ void merge_group(uint32_t group) {
+    merge_step<0>();
+    merge_step<1>();
+    if (group > 4u) merge_step<2>();
+  }
+};
+#endif
+
 // The containers walk of PreComputations.new (world.zig:229-255), as a reduction.
 // Entries before the hit in the sorted list are exactly those with t < 0.  A leaf with an
 // odd number of them is still in `containers` when the hit is reached, at the position of
@@ -1922,6 +1979,7 @@ struct ShadowVisitor {
 template <bool SELECTS>
 struct BehindVisitorT {
   static constexpr bool kAnyHit = false;  // the first entry that counts ends the trace: visiting order is free
+  static constexpr bool kShadowOnly = false;
   uint32_t hit_leaf;
   double hit_t;
   // running state of the leaf currently being visited (entries of one leaf arrive together)
@@ -2719,6 +2777,34 @@ __device__ __noinline__ GlossDir occl_direction(unsigned long long h, uint32_t w
 #else
 #define RTC_KA(mat) (mat).ambient
 #endif
+// (SFILT, rtc.h's rtc_scene_set_shadow_filters) what a light's shadow ray yields.  In the shadow-filter
+// kernels' translation unit: the walk is FilterVisitor's, a point or spot light's diffuse and specular terms are multiplied
+// by the transmittance per channel, and an area light sums its samples' transmittances per channel, from 0.0 in the loop's
+// order.  In every other unit the macros expand to what stood in their place: the any-hit walk, the terms as they are, the
+// integer count.
+#ifdef RTC_SFILT_TU
+#define RTC_LIGHT_VISITOR FilterVisitor
+#define RTC_LIGHT_VISITOR_SET(sv) (sv).filter = sfilt.row
+#define RTC_LIGHT_BLOCKED(sv) (sv).done()
+#define RTC_SF_DECL double sf_r = 1.0, sf_g = 1.0, sf_b = 1.0
+#define RTC_SF_TAKE(sv) sf_r = (sv).tr, sf_g = (sv).tg, sf_b = (sv).tb
+#define RTC_SF(x, c) ((x) * sf_##c)
+#define RTC_LIT_DECL double lit_r = 0.0, lit_g = 0.0, lit_b = 0.0
+#define RTC_LIT_ADD(sv) lit_r = lit_r + (sv).tr, lit_g = lit_g + (sv).tg, lit_b = lit_b + (sv).tb
+#define RTC_LIT_INTENSITY(samples) const double intensity_r = lit_r / samples, intensity_g = lit_g / samples, intensity_b = lit_b / samples
+#define RTC_INTENSITY(c) intensity_##c
+#else
+#define RTC_LIGHT_VISITOR ShadowVisitor
+#define RTC_LIGHT_VISITOR_SET(sv) (void)0
+#define RTC_LIGHT_BLOCKED(sv) (sv).shadowed
+#define RTC_SF_DECL (void)0
+#define RTC_SF_TAKE(sv) (void)0
+#define RTC_SF(x, c) x
+#define RTC_LIT_DECL uint32_t lit = 0u
+#define RTC_LIT_ADD(sv) lit += (sv).shadowed ? 0u : 1u
+#define RTC_LIT_INTENSITY(samples) const double intensity = static_cast<double>(lit) / samples
+#define RTC_INTENSITY(c) intensity
+#endif
 
 // (MS) a lane's sample word: the sample index, and whether the lane owns the pixel (deals its samples, step 1)
 #define RTC_SAMPLE_MASK 0xFFFFu
@@ -2756,16 +2842,20 @@ __device__ __noinline__ GlossDir occl_direction(unsigned long long h, uint32_t w
 // (OCCL: ambient occlusion - DevOcclusion, the occlusion kernels' extra argument: a material with a radius has its ambient
 // term scaled by the share of hemisphere rays that leave the hit unoccluded within that radius.  With GLOSS and everything
 // below it, compiled into the occlusion kernels' translation unit only, under RTC_OCCL_TU, which implies RTC_GLOSS_TU)
+// (SFILT: shadow filters - DevShadowFilter, the shadow-filter kernels' extra argument: a light's shadow ray multiplies the
+// filter rows of the entries it crosses instead of stopping at the first.  With OCCL and everything below it, compiled into
+// the shadow-filter kernels' translation unit only, under RTC_SFILT_TU, which implies RTC_OCCL_TU)
 template <bool LDS, bool CSG, int WORLD = 0, int WAVES = 2, bool COOP = false, bool BOX = true, bool AREA = false, bool MS = false,
           bool MOTION = false, bool SPOT = false, bool BUMP = false, bool TORUS = false, bool MESHUV = false, bool GLOSS = false,
-          bool OCCL = false>
+          bool OCCL = false, bool SFILT = false>
 __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& cam, const DevPixelMap& map,
                                             const uint32_t max_depth, double* __restrict__ out,
                                             DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
                                             const DevAreaLights& area = DevAreaLights{}, const DevSampling& smp = DevSampling{},
                                             const DevMotion& mo = DevMotion{}, const DevSpots& spots = DevSpots{},
                                             const DevBumps& bumps = DevBumps{}, const DevMeshUvs& muv = DevMeshUvs{},
-                                            const DevGloss& gloss = DevGloss{}, const DevOcclusion& occl = DevOcclusion{}) {
+                                            const DevGloss& gloss = DevGloss{}, const DevOcclusion& occl = DevOcclusion{},
+                                            const DevShadowFilter& sfilt = DevShadowFilter{}) {
   static_assert(!AREA || !COOP, "the area kernels run no cooperative iterations");
   static_assert(!MS || !COOP, "the sampling kernels run no cooperative iterations");
   static_assert(!MOTION || (MS && AREA && WORLD == 0), "the motion kernels are the general area-sampling walk");
@@ -2797,6 +2887,13 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
 #else
   static_assert(!OCCL, "ambient occlusion is compiled in the occlusion translation unit (rtc_occlusion.hip) only");
   (void)occl;
+#endif
+  static_assert(!SFILT || OCCL, "the shadow-filter kernels are the occlusion walk");
+#ifdef RTC_SFILT_TU
+  static_assert(SFILT, "the shadow-filter translation unit compiles the shadow-filter kernels only");
+#else
+  static_assert(!SFILT, "shadow filters are compiled in the shadow-filter translation unit (rtc_shadowfilter.hip) only");
+  (void)sfilt;
 #endif
   RTC_PRIO_PHASE(RTC_PRIO_WORK);
 #ifndef RTC_PROFILE
@@ -3771,7 +3868,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
                 }
             }
             if (!(dr == 0.0 && dg == 0.0 && db == 0.0)) {
-              uint32_t lit = 0u;
+              RTC_LIT_DECL;
               for (uint32_t v = 0u; v < vs; ++v)
                 for (uint32_t u = 0u; u < us; ++u) {
                   double vx, vy, vz;
@@ -3785,17 +3882,18 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
                   }
                   it_shadow_traced++;
                   it_share++;
-                  ShadowVisitor sv;
+                  RTC_LIGHT_VISITOR sv;
                   sv.distance = distance;
+                  RTC_LIGHT_VISITOR_SET(sv);
                   Ray sray{ovx, ovy, ovz, lvx, lvy, lvz};
-                  trace<CSG, WORLD, ShadowVisitor, TRAV, BOX, MOTION>(S, recs, cull, sray, sv, it_overflow, trav_stack, member, stride, mo.disp, tm);
-                  lit += sv.shadowed ? 0u : 1u;
+                  trace<CSG, WORLD, RTC_LIGHT_VISITOR, TRAV, BOX, MOTION>(S, recs, cull, sray, sv, it_overflow, trav_stack, member, stride, mo.disp, tm);
+                  RTC_LIT_ADD(sv);
                 }
               const double samples = static_cast<double>(n_samples);
-              const double intensity = static_cast<double>(lit) / samples;  // intensity_at
-              lr_ = lr_ + (dr / samples) * intensity;
-              lg_ = lg_ + (dg / samples) * intensity;
-              lb_ = lb_ + (db / samples) * intensity;
+              RTC_LIT_INTENSITY(samples);  // intensity_at
+              lr_ = lr_ + (dr / samples) * RTC_INTENSITY(r);
+              lg_ = lg_ + (dg / samples) * RTC_INTENSITY(g);
+              lb_ = lb_ + (db / samples) * RTC_INTENSITY(b);
             }
             sr = sr + lr_;
             sg = sg + lg_;
@@ -3818,6 +3916,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
         // or not (material.zig:62-73): that shadow ray cannot change the result either.
         const double light_dot_normal = (lvx * hx + lvy * hy) + lvz * hz;
         bool shadowed = false;
+        RTC_SF_DECL;  // (SFILT: the transmittance of this light's shadow ray; (1, 1, 1) where none is traced)
         // (SPOT) the cone's factor f at c = -(point_to_light . axis).  f == 0: the light gives `ambient` alone - what a
         // shadowed point gets -, so isShadowed is not called: no count, no shadow ray.  li is wave-uniform (no cooperative
         // iterations here): the row is read through the constant address space at a readfirstlane index - scalar loads,
@@ -3833,18 +3932,20 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
         if (!shadowed && shadow_matters && light_dot_normal >= 0.0 && !(RTC_EXPERIMENT & 1)) {
           it_shadow_traced++;
           it_share++;
-          ShadowVisitor sv;
+          RTC_LIGHT_VISITOR sv;
           sv.distance = distance;
+          RTC_LIGHT_VISITOR_SET(sv);
           Ray sray{ovx, ovy, ovz, lvx, lvy, lvz};
           RTC_STAMP(3);
           RTC_COUNT(2);
           {
             RTC_HIST_BEGIN();
-            trace<CSG, WORLD, ShadowVisitor, TRAV, BOX, MOTION>(S, recs, cull, sray, sv, it_overflow, trav_stack, s_member, s_stride, mo.disp, tm);
+            trace<CSG, WORLD, RTC_LIGHT_VISITOR, TRAV, BOX, MOTION>(S, recs, cull, sray, sv, it_overflow, trav_stack, s_member, s_stride, mo.disp, tm);
             RTC_HIST_END(1);
           }
                 RTC_STAMP(4);
-          shadowed = sv.shadowed;
+          shadowed = RTC_LIGHT_BLOCKED(sv);
+          RTC_SF_TAKE(sv);
         }
         // Material.lighting (material.zig:40-74)
         const double er = color.r * L[3], eg = color.g * L[4], eb = color.b * L[5];  // effective_color
@@ -3898,9 +3999,10 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
               }
             }
           }
-          lr_ = (lr_ + dr) + pr;
-          lg_ = (lg_ + dg) + pg;
-          lb_ = (lb_ + db) + pb;
+          // (SFILT: both terms times the transmittance, after the spot factor; (1, 1, 1): the same bits)
+          lr_ = (lr_ + RTC_SF(dr, r)) + RTC_SF(pr, r);
+          lg_ = (lg_ + RTC_SF(dg, g)) + RTC_SF(pg, g);
+          lb_ = (lb_ + RTC_SF(db, b)) + RTC_SF(pb, b);
         }
         sr = sr + lr_;
         sg = sg + lg_;
@@ -4170,7 +4272,8 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
 // with RTC_SPOT_TU and the spot kernels, rtc_bump.hip with RTC_BUMP_TU and the bump kernels, rtc_torus.hip with RTC_TORUS_TU
 // and the torus kernels, rtc_meshuv.hip with RTC_MESHUV_TU (and, with it, RTC_TORUS_TU) and the meshuv kernels, rtc_gloss.hip
 // with RTC_GLOSS_TU (and, with it, both of those) and the gloss kernels, rtc_occlusion.hip with RTC_OCCL_TU (and, with it, those
-// three) and the occlusion kernels.  rtc_kernels_ext.hip
+// three) and the occlusion kernels, rtc_shadowfilter.hip with RTC_SFILT_TU (and, with it, those four) and the shadow-filter
+// kernels.  rtc_kernels_ext.hip
 // includes it with RTC_EXT_TU defined: in the -DRTC_PROFILE diagnostic build, whose instrumented walk makes this unit's
 // compile about a third longer, it gets the csg / texture-map, flat and area-light kernels (rtc_render_kernel_ext to
 // rtc_render_kernel_area_bigworld below), so that neither unit takes the time of all of them.  The product build keeps
@@ -5043,6 +5146,31 @@ rtc_render_kernel_bump_bigworld(const DevScene S, const DevCamera cam, const Dev
                                                                             spots, bumps);
 }
 
+#elif defined(RTC_SFILT_TU)
+
+// Shadow filters (rtc_scene_set_shadow_filters): the occlusion walk with every light's shadow ray
+// multiplying the filter rows of the entries it crosses (FilterVisitor), and the filter rows (DevShadowFilter) as one more
+// argument; one pair for every world, tori, textured meshes, rough materials and occlusion radii included.  Every other
+// kernel is compiled without it.
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_sfilter(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                          double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                          const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots, const DevBumps bumps,
+                          const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl, const DevShadowFilter sfilt) {
+  render_body<true, true, 0, 2, false, true, true, true, true, true, true, true, true, true, true, true>(
+      S, cam, map, max_depth, out, stats, next_stats, area, smp, mo, spots, bumps, muv, gloss, occl, sfilt);
+}
+
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_sfilter_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                   double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                   const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                   const DevBumps bumps, const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl,
+                                   const DevShadowFilter sfilt) {
+  render_body<false, true, 0, 2, false, true, true, true, true, true, true, true, true, true, true, true>(
+      S, cam, map, max_depth, out, stats, next_stats, area, smp, mo, spots, bumps, muv, gloss, occl, sfilt);
+}
+
 #elif defined(RTC_OCCL_TU)
 
 // Ambient occlusion (rtc_scene_set_occlusion): the gloss walk with every hit's ambient term scaled by
@@ -5135,4 +5263,4 @@ rtc_render_kernel_torus_bigworld(const DevScene S, const DevCamera cam, const De
                                                                                   smp, mo, spots, bumps);
 }
 
-#endif  // RTC_MOTION_TU / RTC_SPOT_TU / RTC_BUMP_TU / RTC_OCCL_TU / RTC_GLOSS_TU / RTC_MESHUV_TU / RTC_TORUS_TU
+#endif  // RTC_MOTION_TU / RTC_SPOT_TU / RTC_BUMP_TU / RTC_SFILT_TU / RTC_OCCL_TU / RTC_GLOSS_TU / RTC_MESHUV_TU / RTC_TORUS_TU

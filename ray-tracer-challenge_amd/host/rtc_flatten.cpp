@@ -133,6 +133,13 @@ struct Flattener {
       const double occl[3] = {-1.0, m.occlusion.radius, -1.0};
       appendBits(key, occl, 3);
     }
+    // (likewise a material with a "shadow-filter": a row of its own only when a value is non-zero)
+    out.shadow_filter_present = out.shadow_filter_present || m.shadow_filter.present;
+    if (m.shadow_filter.r != 0.0 || m.shadow_filter.g != 0.0 || m.shadow_filter.b != 0.0) {
+      // (a tag of its own before the values: a filter never shares a key with a radius or a roughness pair of the same bits)
+      const double filt[5] = {-2.0, m.shadow_filter.r, m.shadow_filter.g, m.shadow_filter.b, -2.0};
+      appendBits(key, filt, 5);
+    }
     auto it = material_ids.find(key);
     if (it != material_ids.end()) return it->second;
     const uint32_t id = static_cast<uint32_t>(out.mat_pattern.size());
@@ -142,6 +149,9 @@ struct Flattener {
     out.mat_gloss.push_back(m.roughness.reflection);
     out.mat_gloss.push_back(m.roughness.transmission);
     out.mat_occlusion.push_back(m.occlusion.radius);
+    out.mat_shadow_filter.push_back(m.shadow_filter.r);
+    out.mat_shadow_filter.push_back(m.shadow_filter.g);
+    out.mat_shadow_filter.push_back(m.shadow_filter.b);
     material_ids.emplace(std::move(key), id);
     return id;
   }

@@ -30,6 +30,8 @@ struct FlatScene {
   bool gloss_present = false;     // some material of the scene has the "roughness" key
   std::vector<double> mat_occlusion;  // [n_materials]: each row's "ambient-occlusion" radius (rtch_scene_occlusion; not part of rtc_scene_desc)
   bool occlusion_present = false;     // some material of the scene has the "ambient-occlusion" key
+  std::vector<double> mat_shadow_filter;  // [n_materials][3]: each row's "shadow-filter" (rtch_scene_shadow_filters; not part of rtc_scene_desc)
+  bool shadow_filter_present = false;     // some material of the scene has the "shadow-filter" key
   std::vector<Bump> mat_bump;  // [n_materials]: each row's "normal-perturbation" (rtch_scene_bumps; not part of rtc_scene_desc)
   std::vector<uint8_t> pat_kind;
   std::vector<double> pat_inv, pat_rgb;

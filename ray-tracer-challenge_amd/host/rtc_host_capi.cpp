@@ -166,6 +166,19 @@ int rtch_scene_occlusion(void* h, double* radius, uint32_t* samples, uint64_t* s
   });
 }
 
+// The materials' "shadow-filter" rows, in mat_* order, three doubles each, as
+// rtc_scene_set_shadow_filters takes them; *present: some material of the file has the key.
+int rtch_scene_shadow_filters(void* h, double* rgb, int* present, uint32_t n) {
+  return guarded([&] {
+    const HostScene* hs = static_cast<HostScene*>(h);
+    if (n != hs->desc.n_materials)
+      throw rtc::Error("InvalidArgument", "shadow filters: n " + std::to_string(n) + ", the scene has " + std::to_string(hs->desc.n_materials) + " materials");
+    if (n != 0u && !rgb) throw rtc::Error("InvalidArgument", "shadow filters: null argument");
+    for (size_t i = 0; i < 3u * static_cast<size_t>(n); ++i) rgb[i] = hs->flat.mat_shadow_filter[i];  // (mat_* order)
+    if (present) *present = hs->flat.shadow_filter_present ? 1 : 0;
+  });
+}
+
 // The triangles' texture rows (RTC_TEX_MESH), in tri_* order, as rtc_scene_set_mesh_uvs takes them.
 int rtch_scene_mesh_uvs(void* h, double* uv, uint32_t n) {
   return guarded([&] {
@@ -291,6 +304,10 @@ int rtch_scene_render(void* h, uint32_t width, uint32_t height, uint32_t max_dep
         const rtc_occlusion oc{hs->desc.n_materials, hs->flat.mat_occlusion.data(), hs->info.sampling.occlusion_samples,
                                hs->info.sampling.occlusion_seed};
         st = rtc_scene_set_occlusion(scene, &oc);
+      }
+      if (st == RTC_OK && hs->flat.shadow_filter_present) {  // (the materials' shadow filters; all zero: the handle as it is)
+        const rtc_shadow_filters sf{hs->desc.n_materials, hs->flat.mat_shadow_filter.data()};
+        st = rtc_scene_set_shadow_filters(scene, &sf);
       }
       const rtc::CameraSampling& cs = hs->info.sampling;
       if (cs.adaptive && st == RTC_OK) {  // (adaptive sampling: each tile's mean after its own passes, section 15)

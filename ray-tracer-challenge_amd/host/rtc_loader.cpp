@@ -465,10 +465,36 @@ Occlusion parseOcclusion(const Value& cfg) {
   return o;
 }
 
+// A material's "shadow-filter" (not in the reference): a number f - (f, f, f) -, [r, g, b], or true
+// - the material's transparency in each channel, taken by parseMaterial once the material's own keys are read -; each
+// value finite and in [0, 1].
+ShadowFilter parseShadowFilter(const Value& cfg) {
+  auto one = [](const Value& v) {
+    if (v.type != Value::Number) throw Error("InvalidData", "shadow-filter: a number in [0, 1], [r, g, b] or true");
+    const double x = asFloat(v, "shadow-filter");
+    if (!(std::isfinite(x) && x >= 0.0 && x <= 1.0)) throw Error("InvalidData", "shadow-filter: a number in [0, 1]");
+    return x;
+  };
+  ShadowFilter f;
+  f.present = true;
+  if (cfg.type == Value::Bool) {
+    if (!cfg.b) throw Error("InvalidData", "shadow-filter: a number in [0, 1], [r, g, b] or true");
+    f.from_transparency = true;
+  } else if (cfg.type == Value::Array) {
+    if (cfg.arr.size() != 3) throw Error("LengthMismatch", "shadow-filter: [r, g, b]");
+    f.r = one(cfg.arr[0]);
+    f.g = one(cfg.arr[1]);
+    f.b = one(cfg.arr[2]);
+  } else {
+    f.r = f.g = f.b = one(cfg);
+  }
+  return f;
+}
+
 Material parseMaterial(const Value& cfg, const std::optional<Material>& inherited, const FileLoader& load_file_data) {
   requireObject(cfg, "material");
   checkFields(cfg, {"pattern", "ambient", "diffuse", "specular", "shininess", "reflective", "transparency",
-                    "refractive-index", "normal-perturbation", "roughness", "ambient-occlusion"}, "material");
+                    "refractive-index", "normal-perturbation", "roughness", "ambient-occlusion", "shadow-filter"}, "material");
   Material mat = inherited ? *inherited : Material{};
   auto present = [&](const char* k) -> const Value* {
     const Value* v = cfg.find(k);
@@ -485,6 +511,12 @@ Material parseMaterial(const Value& cfg, const std::optional<Material>& inherite
   if (auto* v = present("normal-perturbation")) mat.bump = parseBump(*v);
   if (auto* v = present("roughness")) mat.roughness = parseRoughness(*v);
   if (auto* v = present("ambient-occlusion")) mat.occlusion = parseOcclusion(*v);
+  if (auto* v = present("shadow-filter")) mat.shadow_filter = parseShadowFilter(*v);
+  if (mat.shadow_filter.from_transparency) {  // (`true`, the material's own or an inherited one: this material's transparency)
+    const double t = mat.transparency;
+    if (!(std::isfinite(t) && t >= 0.0 && t <= 1.0)) throw Error("InvalidData", "shadow-filter: true needs a transparency in [0, 1]");
+    mat.shadow_filter.r = mat.shadow_filter.g = mat.shadow_filter.b = t;
+  }
   return mat;
 }
 

@@ -107,6 +107,16 @@ struct Occlusion {
   bool present = false;
 };
 
+// A material's "shadow-filter" (not in the reference), as rtc_scene_set_shadow_filters takes it: the
+// share of a light's red, green and blue that one entry of the material lets through, each in [0, 1]; (0, 0, 0) blocks.
+// `from_transparency`: the key is `true` - the three values are the material's transparency, also where a material that
+// inherits the key sets a transparency of its own.  `present`: the material, or one it inherits from, has the key.
+struct ShadowFilter {
+  double r = 0.0, g = 0.0, b = 0.0;
+  bool from_transparency = false;
+  bool present = false;
+};
+
 struct Material {  // material.zig:18-25
   Pattern pattern = Pattern::solid({1.0, 1.0, 1.0});
   double ambient = 0.1, diffuse = 0.9, specular = 0.9, shininess = 200.0;
@@ -114,6 +124,7 @@ struct Material {  // material.zig:18-25
   Bump bump;  // (kind 0 in every scene of the reference)
   Roughness roughness;  // (0, 0 in every scene of the reference)
   Occlusion occlusion;  // (0 in every scene of the reference)
+  ShadowFilter shadow_filter;  // (0, 0, 0 in every scene of the reference)
 };
 
 struct Light {  // light.zig:14-15

@@ -51,6 +51,10 @@ without a rough material.  With --passes the noise run has the same table.
 (rtc_scene_set_occlusion; DESIGN.md section 21), --occlusion-samples N hemisphere rays per hit (default: the scene file's, or 1);
 on a scene file with "ambient-occlusion" entries those are applied first; --occlusion off applies none.  Option
 occlusion_kernels=1 times the occlusion kernels without a radius.  With --passes the noise run has the same table.
+--shadow-filter MATERIAL=r,g,b (repeatable): material row MATERIAL (mat_* order) lets that share of a light's red, green
+and blue through each of its entries (rtc_scene_set_shadow_filters); on a scene file with
+"shadow-filter" entries those are applied first; --shadow-filter off applies none.  Option shadow_filter_kernels=1 times the
+shadow-filter kernels without a filter.  With --passes the noise run has the same table.
 --adaptive threshold[,min,tile]: adaptive sampling at up to --max-passes (64) passes, min passes 4 and
 16 x 16 tiles by default, with the --sampling of the frames: prints the rounds and tile-passes of a run against
 T * max_passes, its time (a second run, end to end on the host) against uniform progressive passes (render_device +
@@ -93,6 +97,7 @@ ap.add_argument("--bump", action="append", default=[])
 ap.add_argument("--gloss", action="append", default=[])
 ap.add_argument("--occlusion", action="append", default=[])
 ap.add_argument("--occlusion-samples", type=int, default=0)
+ap.add_argument("--shadow-filter", action="append", default=[])
 ap.add_argument("--torus", action="store_true")
 ap.add_argument("--meshuv", action="store_true")
 ap.add_argument("--mesh-as-planar", action="store_true")
@@ -145,6 +150,19 @@ def occlusion_table(hs):
     if args.occlusion_samples:
         occlusion["samples"] = args.occlusion_samples
     return occlusion
+
+
+def shadow_filter_table(hs):
+    """the scene file's "shadow-filter" rows with the --shadow-filter entries over them; None: no table (--shadow-filter off,
+    or nothing to set)"""
+    if "off" in args.shadow_filter or not (args.shadow_filter or hs.shadow_filters() is not None):
+        return None
+    import numpy as np
+    filters = hs.shadow_filters() or {"rgb": np.zeros((hs.desc.n_materials, 3))}
+    for f in args.shadow_filter:
+        m, v = f.split("=")
+        filters["rgb"][int(m)] = [float(x) for x in v.split(",")]
+    return filters
 
 
 def light_table(hs, how):
@@ -346,6 +364,9 @@ for name, w, h, depth in cases:
         occlusion = occlusion_table(hs)
         if occlusion is not None:
             gpu.set_occlusion(occlusion)
+        filters = shadow_filter_table(hs)
+        if filters is not None:
+            gpu.set_shadow_filters(filters)
         for i in range(args.settle):
             gpu.render_device(cam, canvas.data_ptr(), depth, None, stream.cuda_stream)
         torch.cuda.synchronize()
@@ -370,7 +391,7 @@ for name, w, h, depth in cases:
     if delta is not None: line += f" maxdelta {delta:.2e}"
     if args.lights or args.spot or "spot_kernels=1" in args.option:
         line += f" shadow_traced {st['shadow_traced']} ns/shadow-ray {min(ts) * 1e6 / max(1, st['shadow_traced']):.3f}"
-    if args.sampling or args.option or args.passes >= 0 or args.motion or args.spot or args.bump or args.torus or args.meshuv or args.gloss or args.occlusion:
+    if args.sampling or args.option or args.passes >= 0 or args.motion or args.spot or args.bump or args.torus or args.meshuv or args.gloss or args.occlusion or args.shadow_filter:
         line += f" primary {st['primary']} ns/primary-ray {min(ts) * 1e6 / max(1, st['primary']):.3f}"
     if acc:
         ms, copy_ms, nbytes = min(a[0] for a in acc), min(a[1] for a in acc), acc[0][2]
@@ -384,6 +405,7 @@ for name, w, h, depth in cases:
         if hs.mesh_uvs() is not None: gpu.set_mesh_uvs(hs.mesh_uvs())
         if gloss_table(hs) is not None: gpu.set_gloss(gloss_table(hs))
         if occlusion_table(hs) is not None: gpu.set_occlusion(occlusion_table(hs))
+        if shadow_filter_table(hs) is not None: gpu.set_shadow_filters(shadow_filter_table(hs))
         prog = rtc.Progressive(gpu, cam, depth)
         noise = {}
         for i in range(1, 65):
