@@ -675,6 +675,60 @@ typedef struct rtc_shadow_filters {
  */
 int rtc_scene_set_shadow_filters(rtc_scene *scene, const rtc_shadow_filters *filters);
 
+/* ---- participating media: absorbing materials and a uniform fog attenuate a ray along its way ---- */
+/*
+ * Tables.  A material row has an absorption (ar, ag, ab) per unit of world distance, each finite and >= 0; (0, 0, 0) is the
+ * material as it is.  The handle has one atmosphere: fog_density, finite and >= 0, and fog_color[3], each finite and >= 0.
+ *
+ * A ray's medium.  Every ray of the colorAt tree carries a medium: a material index, or RTC_NO_MEDIUM for the atmosphere.
+ *   - A camera ray, with or without sampling or a lens, is in the atmosphere: the camera is taken to stand outside every
+ *     solid.
+ *   - A reflected child has its parent's medium.
+ *   - A refracted child has the material whose ior the parent's hit took for n2 (PreComputations.new's containers walk),
+ *     by exactly the selection made for n2:
+ *       the hit's material, where the hit shape is not among the containers at the hit (the ray enters it);
+ *       else the material of the last container that remains once the hit shape is removed, if there is one;
+ *       else the hit's material, if the hit's t occurs twice or more among the hit shape's entries;
+ *       else RTC_NO_MEDIUM - the case where n2 stays 1.0.
+ *
+ * The step.  Applied to every ray of the tree after its closest-hit trace, whatever its remaining depth, before shading and
+ * before the children are formed.  W is the ray's weight, one value per channel; acc the pixel's colour; (dx, dy, dz) the
+ * ray's direction; c runs over r, g, b:
+ *   sigma = medium == RTC_NO_MEDIUM ? (fog_density, fog_density, fog_density) : absorption[medium]
+ *   hit at t:  dist = t * sqrt((dx*dx + dy*dy) + dz*dz)
+ *              T.c  = sigma.c == 0.0 ? 1.0 : exp(-(sigma.c * dist))
+ *   miss:      T.c  = sigma.c == 0.0 ? 1.0 : 0.0
+ *   if medium == RTC_NO_MEDIUM && fog_density > 0.0:
+ *              acc.c = acc.c + W.c * ((1.0 - T.c) * fog_color.c)
+ *   W.c = W.c * T.c
+ * On a hit the ray goes on as before with W: the hit contributes W.c * s.c, the children get W.c * w_reflect and
+ * W.c * w_refract.  On a miss the ray ends as before after the in-scatter term.  An all-zero table and a density of zero
+ * leave every bit as it is: T == 1 multiplies exactly and the fog term is not formed.  Nothing is culled by a small weight:
+ * primary, secondary, shadow_calls and shadow_traced are those of the same handle without media.  exp is the FP64 library
+ * function: its last bits may differ between implementations.
+ *
+ * Unchanged.  Shadow rays - the products of rtc_scene_set_shadow_filters included - and occlusion rays are not attenuated
+ * by media.  The fog is not lit by the lights: it is a constant in-scatter colour.  Gloss draws, sampling, motion,
+ * accumulation and the adaptive loop stay as they are.
+ */
+#define RTC_NO_MEDIUM 0xFFFFFFFFu
+typedef struct rtc_media {
+  uint32_t n_materials;     /* the handle's material count (rtc_scene_desc::n_materials) */
+  const double *absorption; /* [n_materials][3], each finite and >= 0; NULL: all zeros */
+  double fog_density;       /* finite and >= 0; 0: no fog */
+  double fog_color[3];      /* each finite and >= 0 */
+} rtc_media;
+
+/*
+ * This handle's media for every render entry point.  Validated on the host before anything changes:
+ * RTC_ERR_INVALID_ARGUMENT for a value that is not finite or is negative, and then for an n_materials other than the
+ * handle's; the previous table stays in force.  NULL, or a table whose every row is zero with a density of zero, gives the
+ * handle its previous kernels back.  A clone starts with its source's media; rtc_render's band clones follow.  A handle with
+ * an absorbing row or a fog renders with the media kernels (rtc_render_kernel_media, _media_bigworld).  librtc_multi renders
+ * without media.  rtc_scene_desc, rtc_camera and RTC_ABI_VERSION are as they were.
+ */
+int rtc_scene_set_media(rtc_scene *scene, const rtc_media *media);
+
 /* ---- adaptive sampling: progressive passes only for tiles still noisy ---- */
 #define RTC_ADAPTIVE_MAX_TILE 1024u
 

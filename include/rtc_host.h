@@ -24,7 +24,8 @@
  *                        rtch_scene_mesh_uvs, through rtc_scene_set_mesh_uvs; its materials' roughness,
  *                        rtch_scene_gloss, through rtc_scene_set_gloss; its materials' occlusion radii,
  *                        rtch_scene_occlusion, through rtc_scene_set_occlusion; its materials' shadow filters,
- *                        rtch_scene_shadow_filters, through rtc_scene_set_shadow_filters)
+ *                        rtch_scene_shadow_filters, through rtc_scene_set_shadow_filters; its materials' absorption
+ *                        and its atmosphere, rtch_scene_media, through rtc_scene_set_media)
  *
  * Every function that returns int returns 0 on success; otherwise rtch_last_error()
  * holds "<ZigStyleErrorName>: detail" (thread-local).
@@ -104,6 +105,14 @@ int rtch_scene_occlusion(void *handle, double *radius, uint32_t *samples, uint64
  * value is non-zero.  *present: 1 when a material of the file has the key.  Pass them to rtc_scene_set_shadow_filters.
  * rtch_scene_render applies them. */
 int rtch_scene_shadow_filters(void *handle, double *rgb, int *present, uint32_t n);
+/* The materials' "absorption" (DESIGN.md section 23), in mat_* order, three doubles a row: a number a - (a, a, a) -, an
+ * array [r, g, b], or {"color": [r, g, b], "distance": d} - white light has that colour after d units: -log(color.c) / d,
+ * color.c in (0, 1], d > 0 -, every value finite and >= 0; and the scene's "atmosphere": {"density": d, "color": [r, g, b]}
+ * in fog[4]: the density, then the colour (all zero without the key).  n must be the description's n_materials; absorption
+ * holds 3 * n doubles.  A material with the key is a mat_* row of its own only when a value is non-zero.  *present: 1 when
+ * a material of the file has the key or the file has an atmosphere.  Pass them to rtc_scene_set_media.  rtch_scene_render
+ * applies them. */
+int rtch_scene_media(void *handle, double *absorption, double *fog, int *present, uint32_t n);
 int rtch_scene_camera(void *handle, uint32_t width, uint32_t height, rtc_camera *out);
 int rtch_camera_rotate(void *handle, double angle);
 int rtch_camera_move(void *handle, double distance);

@@ -46,7 +46,8 @@ typedef struct rtc_multi rtc_multi; /* opaque: per frame slot n scene handles an
  * with a texture map of mapping RTC_TEX_MESH (rtc_scene_set_mesh_uvs has no multi-GPU form).
  * rtc_scene_set_gloss has no multi-GPU form either: it renders without gloss, every mirror and glass sharp; nor has
  * rtc_scene_set_occlusion: it renders without ambient occlusion, every ambient term as the material has it; nor has
- * rtc_scene_set_shadow_filters: it renders without shadow filters, every shadow-casting material opaque to light. */
+ * rtc_scene_set_shadow_filters: it renders without shadow filters, every shadow-casting material opaque to light; nor has
+ * rtc_scene_set_media: it renders without media, no material absorbing and no fog. */
 int rtc_multi_create(const rtc_scene_desc *desc, uint32_t n_gpus, uint32_t flags, rtc_multi **out);
 void rtc_multi_destroy(rtc_multi *m);
 

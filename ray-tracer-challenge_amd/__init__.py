@@ -221,7 +221,8 @@ BUMP_NONE, BUMP_NOISE, BUMP_RIPPLES = 0, 1, 2  # RTC_BUMP_*
 RTC_SPHERE, RTC_PLANE, RTC_CUBE, RTC_CYLINDER, RTC_TRIANGLE, RTC_SMOOTH_TRIANGLE, RTC_CONE, RTC_TORUS = range(8)
 # the options that select a kernel family on a handle that does not need it (set_option; tests and tools/time_scenes.py)
 KERNEL_OPTIONS = ("sampling_kernels", "motion_kernels", "spot_kernels", "bump_kernels", "torus_kernels", "meshuv_kernels", "gloss_kernels",
-                  "occlusion_kernels", "shadow_filter_kernels")
+                  "occlusion_kernels", "shadow_filter_kernels", "media_kernels")
+NO_MEDIUM = 0xFFFFFFFF  # RTC_NO_MEDIUM: a ray in the atmosphere
 # texture mappings (rtc.h); RTC_TEX_MESH: (u, v) from the hit triangle's texture row
 RTC_TEX_SPHERICAL, RTC_TEX_PLANAR, RTC_TEX_CYLINDRICAL, RTC_TEX_CUBIC, RTC_TEX_MESH = range(5)
 BUMP_MAX_OCTAVES = 16  # RTC_BUMP_MAX_OCTAVES
@@ -303,6 +304,33 @@ def shadow_filters_struct(filters):
     return f, rgb
 
 
+class Media(C.Structure):
+    """struct rtc_media (include/rtc.h): three doubles per material row, what a unit of world distance inside the material
+    absorbs of red, green and blue, and the one atmosphere - a fog's density and colour."""
+
+    _fields_ = [("n_materials", C.c_uint32), ("absorption", C.POINTER(C.c_double)), ("fog_density", C.c_double),
+                ("fog_color", C.c_double * 3)]
+
+
+def media_struct(media):
+    """(Media, the array it points into) of a dict of "absorption" ((n, 3); None: all zeros, with "n_materials"),
+    "fog_density" (0) and "fog_color" ((0, 0, 0)) (GpuScene.set_media); the array must outlive the struct's use."""
+    a = media.get("absorption")
+    if a is None:
+        n = int(media["n_materials"])
+    else:
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError(f"media: an absorption array of shape {a.shape}, (n, 3) expected")
+        n = a.shape[0]
+    color = [float(x) for x in media.get("fog_color", (0.0, 0.0, 0.0))]
+    if len(color) != 3:
+        raise ValueError(f"media: a fog colour of {len(color)} values, 3 expected")
+    m = Media(n, a.ctypes.data_as(C.POINTER(C.c_double)) if a is not None else None, float(media.get("fog_density", 0.0)),
+              (C.c_double * 3)(*color))
+    return m, a
+
+
 class Bump(C.Structure):
     """struct rtc_bump (include/rtc.h): a bump per material row (kind BUMP_NONE: the material as it is)."""
 
@@ -344,14 +372,14 @@ RTC_SYMBOLS = ["rtc_scene_create", "rtc_scene_clone", "rtc_scene_destroy", "rtc_
                "rtc_scene_set_sample_pass", "rtc_scene_accumulate_device", "rtc_scene_set_motion",
                "rtc_scene_adaptive_begin_device", "rtc_scene_adaptive_accumulate_device", "rtc_scene_adaptive_step", "rtc_render_adaptive",
                "rtc_scene_set_spots", "rtc_scene_set_bumps", "rtc_scene_set_mesh_uvs", "rtc_scene_set_gloss",
-               "rtc_scene_set_occlusion", "rtc_scene_set_shadow_filters"]
+               "rtc_scene_set_occlusion", "rtc_scene_set_shadow_filters", "rtc_scene_set_media"]
 # (... and include/rtc_diag.h: diagnostics and tuning, for the tests, bench.py and tools/)
 RTC_DIAG_SYMBOLS = ["rtc_set_option", "rtc_last_kernel_name", "rtc_get_schedule", "rtc_get_chunk_times", "rtc_diag_build_tables", "rtc_diag_root_boxes", "rtc_diag_root_spheres"]
 HOST_SYMBOLS = ["rtch_last_error", "rtch_scene_load", "rtch_scene_free", "rtch_scene_desc", "rtch_scene_camera",
                 "rtch_camera_rotate", "rtch_camera_move", "rtch_camera_make", "rtch_canvas_ppm", "rtch_canvas_rgba8", "rtch_scene_render", "rtch_set_loader_threads",
                 "rtch_scene_lights", "rtch_scene_sampling", "rtch_scene_passes", "rtch_scene_motion", "rtch_scene_adaptive",
                 "rtch_scene_spots", "rtch_scene_bumps", "rtch_scene_mesh_uvs", "rtch_scene_gloss", "rtch_scene_occlusion",
-                "rtch_scene_shadow_filters"]
+                "rtch_scene_shadow_filters", "rtch_scene_media"]
 
 MULTI_SYMBOLS = ["rtc_multi_create", "rtc_multi_destroy", "rtc_multi_render", "rtc_multi_render_rgba8", "rtc_multi_render_device", "rtc_multi_render_rgba8_device",
                  "rtc_multi_synchronize", "rtc_multi_stream", "rtc_multi_get_stats", "rtc_multi_balance", "rtc_multi_last_error"]
@@ -417,6 +445,7 @@ def hip_lib():
         lib.rtc_scene_set_gloss.argtypes = [C.c_void_p, C.POINTER(Gloss)]
         lib.rtc_scene_set_occlusion.argtypes = [C.c_void_p, C.POINTER(Occlusion)]
         lib.rtc_scene_set_shadow_filters.argtypes = [C.c_void_p, C.POINTER(ShadowFilters)]
+        lib.rtc_scene_set_media.argtypes = [C.c_void_p, C.POINTER(Media)]
         lib.rtc_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.POINTER(Adaptive), C.c_void_p, C.c_void_p]
         lib.rtc_scene_destroy.argtypes = [C.c_void_p]
         lib.rtc_scene_destroy.restype = None
@@ -475,6 +504,7 @@ def host_lib():
         lib.rtch_scene_gloss.argtypes = [C.c_void_p, _dp, _dp, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.c_uint32]
         lib.rtch_scene_occlusion.argtypes = [C.c_void_p, _dp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.c_uint32]
         lib.rtch_scene_shadow_filters.argtypes = [C.c_void_p, _dp, C.POINTER(C.c_int), C.c_uint32]
+        lib.rtch_scene_media.argtypes = [C.c_void_p, _dp, _dp, C.POINTER(C.c_int), C.c_uint32]
         lib.rtch_scene_adaptive.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(Adaptive)]
         lib.rtch_scene_camera.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Camera)]
         lib.rtch_camera_rotate.argtypes = [C.c_void_p, C.c_double]
@@ -702,6 +732,17 @@ class HostScene:
         _check_host(host_lib().rtch_scene_shadow_filters(self._h, out["rgb"].ctypes.data_as(_dp), C.byref(present), n))
         return out if present.value else None
 
+    def media(self):
+        """The materials' "absorption" rows, in mat_* order, and the scene's "atmosphere" (rtch_scene_media): a dict of
+        "absorption" (n, 3), "fog_density" and "fog_color" - what GpuScene.set_media takes -, or None when no material of the
+        file has the key and the file has no atmosphere."""
+        n = self.desc.n_materials
+        a, fog = np.zeros((n, 3)), np.zeros(4)
+        present = C.c_int()
+        _check_host(host_lib().rtch_scene_media(self._h, a.ctypes.data_as(_dp), fog.ctypes.data_as(_dp), C.byref(present), n))
+        out = {"absorption": a, "fog_density": float(fog[0]), "fog_color": [float(x) for x in fog[1:]]}
+        return out if present.value else None
+
     def adaptive(self):
         """The camera's "sampling": {"adaptive": ...} of the scene file (rtch_scene_adaptive): an Adaptive whose max_passes
         is "passes", or None when the file has none."""
@@ -845,6 +886,15 @@ class GpuScene:
             return
         f, _keep = shadow_filters_struct(filters)
         _check_hip(hip_lib().rtc_scene_set_shadow_filters(self._s, C.byref(f)))
+
+    def set_media(self, media):
+        """rtc_scene_set_media: a dict of "absorption" ((n_materials, 3)), "fog_density" and "fog_color" (HostScene.media());
+        None: no media - as every row and the density zero, the handle's previous kernels."""
+        if media is None:
+            _check_hip(hip_lib().rtc_scene_set_media(self._s, None))
+            return
+        m, _keep = media_struct(media)
+        _check_hip(hip_lib().rtc_scene_set_media(self._s, C.byref(m)))
 
     def accumulate_device(self, accum, stream=None):
         """rtc_scene_accumulate_device: an Accum, enqueued on `stream` (None: the handle's own) after this handle's renders."""

@@ -181,6 +181,20 @@ __global__ void rtc_render_kernel_sfilter_bigworld(const DevScene S, const DevCa
                                                    const DevBumps bumps, const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl,
                                                    const DevShadowFilter sfilt);
 }
+// The media kernels (rtc_scene_set_media: absorbing materials and a uniform fog): the shadow-filter kernels' tables and
+// edge, and the absorption rows, the atmosphere and the pending rays' fifth quarter (DevMedia) as one more argument.
+extern "C" {
+__global__ void rtc_render_kernel_media(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                        double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                        const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                        const DevBumps bumps, const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl,
+                                        const DevShadowFilter sfilt, const DevMedia media);
+__global__ void rtc_render_kernel_media_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                                 double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                                 const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                                 const DevBumps bumps, const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl,
+                                                 const DevShadowFilter sfilt, const DevMedia media);
+}
 // Progressive rendering's accumulation (rtc_accum.hip): the grid's blocks for n pixels (the noise partials it writes, at
 // most) and the enqueue of its kernels.
 uint32_t rtcAccumBlocks(size_t n_pixels, bool wide);
@@ -397,7 +411,8 @@ bool tablesInLds(const rtc_scene* s) {
 // `ms`, and both: `area_ms`; the motion kernels both and DevMotion: `motion`; the spot kernels those three and DevSpots:
 // `spot`; the bump kernels those four and DevBumps: `bump` - the torus kernels take the same arguments and travel in `bump` too;
 // the meshuv kernels those five and DevMeshUvs: `meshuv`; the gloss kernels those six and DevGloss: `gloss`;
-// the occlusion kernels those seven and DevOcclusion: `occl`; the shadow-filter kernels those eight and DevShadowFilter: `sfilt`)
+// the occlusion kernels those seven and DevOcclusion: `occl`; the shadow-filter kernels those eight and DevShadowFilter: `sfilt`;
+// the media kernels those nine and DevMedia: `media`)
 struct KernelChoice {
   decltype(&rtc_render_kernel) fn;
   const char* name;
@@ -411,6 +426,7 @@ struct KernelChoice {
   decltype(&rtc_render_kernel_gloss) gloss = nullptr;
   decltype(&rtc_render_kernel_occl) occl = nullptr;
   decltype(&rtc_render_kernel_sfilter) sfilt = nullptr;
+  decltype(&rtc_render_kernel_media) media = nullptr;
   KernelChoice(decltype(&rtc_render_kernel) f, const char* n) : fn(f), name(n) {}
   KernelChoice(decltype(&rtc_render_kernel_area) a, const char* n) : fn(nullptr), name(n), area(a) {}
   KernelChoice(decltype(&rtc_render_kernel_ms) m, const char* n) : fn(nullptr), name(n), ms(m) {}
@@ -422,11 +438,12 @@ struct KernelChoice {
   KernelChoice(decltype(&rtc_render_kernel_gloss) gk, const char* n) : fn(nullptr), name(n), gloss(gk) {}
   KernelChoice(decltype(&rtc_render_kernel_occl) ok, const char* n) : fn(nullptr), name(n), occl(ok) {}
   KernelChoice(decltype(&rtc_render_kernel_sfilter) fk, const char* n) : fn(nullptr), name(n), sfilt(fk) {}
+  KernelChoice(decltype(&rtc_render_kernel_media) mk, const char* n) : fn(nullptr), name(n), media(mk) {}
   void launch(uint32_t blocks, hipStream_t stream, const rtc_scene* s, const DevScene& dev, const DevCamera& cam, const DevPixelMap& map,
               uint32_t max_depth, double* d_out, DevStats* st_now, DevStats* st_next) const {
     DevSampling smp = s->sampling;  // (the pass's area-light offset, P * N * S: N is the camera's whole image)
     smp.pixel_base = static_cast<unsigned long long>(smp.sample_base) * (static_cast<unsigned long long>(cam.hsize) * cam.vsize);
-    if (motion || spot || bump || meshuv || gloss || occl || sfilt) {
+    if (motion || spot || bump || meshuv || gloss || occl || sfilt || media) {
       // the handle's root tables with the moving roots' bounds (or the scene's, all displacements zero: the option), and
       // the scene's area rows (or zero rows: a point-only table); the spot kernels also the handle's spot rows (or zero
       // rows, every flag 0: the option)
@@ -442,7 +459,24 @@ struct KernelChoice {
         mo.disp = m->disp.p;
       }
       const DevAreaLights area = s->area_kernel ? s->area : DevAreaLights{s->tab->zero_rows.p, s->area.seed};
-      if (sfilt) {  // (the handle's filter rows, or zero rows, every material opaque: the option; and the occlusion kernels' tables)
+      if (media) {  // (the handle's absorption rows and atmosphere, or zero rows and no fog: the option; and the shadow-filter kernels' tables)
+        const DevSpots sp{s->spots ? s->spots->row.p : s->tab->zero_rows.p};
+        const DevBumps bp{s->bumps ? s->bumps->row.p : s->tab->zero_bump.p};
+        const DevMeshUvs uv{s->mesh_uvs ? s->mesh_uvs->row.p : nullptr};
+        const DevGloss gl{s->gloss ? s->gloss->row.p : s->tab->zero_bump.p, s->gloss ? s->gloss->key : 0ull};
+        const DevOcclusion oc{s->occlusion ? s->occlusion->row.p : s->tab->zero_bump.p, s->occlusion ? s->occlusion->key : 0ull,
+                              s->occlusion ? s->occlusion->samples : 1u};
+        const DevShadowFilter sf{s->shadow_filters ? s->shadow_filters->row.p : s->tab->zero_bump.p};
+        // (three doubles per material, 3 <= RTC_BUMP_ROW: the zero bump rows serve as zero absorption rows; the fifth
+        // quarter of the pending rays in memory: ensureScratch sized it with the ray stack)
+        DevMedia me{s->tab->zero_bump.p, 0.0, {0.0, 0.0, 0.0}, s->d_media_stack};
+        if (const MediaTables* m = s->media.get()) {
+          me.absorption = m->row.p;
+          me.fog_density = m->fog_density;
+          for (int c = 0; c < 3; ++c) me.fog_color[c] = m->fog_color[c];
+        }
+        hipLaunchKernelGGL(media, dim3(blocks), dim3(256), 0, stream, md, cam, map, max_depth, d_out, st_now, st_next, area, smp, mo, sp, bp, uv, gl, oc, sf, me);
+      } else if (sfilt) {  // (the handle's filter rows, or zero rows, every material opaque: the option; and the occlusion kernels' tables)
         const DevSpots sp{s->spots ? s->spots->row.p : s->tab->zero_rows.p};
         const DevBumps bp{s->bumps ? s->bumps->row.p : s->tab->zero_bump.p};
         const DevMeshUvs uv{s->mesh_uvs ? s->mesh_uvs->row.p : nullptr};
@@ -521,6 +555,9 @@ bool occlusionKernels(const rtc_scene* s) { return s->occlusion != nullptr || rt
 // other table) - whatever else the handle holds: they are the occlusion walk - or, for tests, whenever option
 // "shadow_filter_kernels" is set.
 bool shadowFilterKernels(const rtc_scene* s) { return s->shadow_filters != nullptr || rtcOptions().shadow_filter_kernels != 0.0; }
+// The media kernels run when the handle has an absorbing row or a fog (rtc_scene_set_media keeps no other table) - whatever
+// else the handle holds: they are the shadow-filter walk - or, for tests, whenever option "media_kernels" is set.
+bool mediaKernels(const rtc_scene* s) { return s->media != nullptr || rtcOptions().media_kernels != 0.0; }
 #define RTC_KERNEL(k) KernelChoice{k, #k}
 // The general kernel at three waves per SIMD (rtc_render_kernel3): forced by option "waves3", else what the handle's
 // trial measured (KernelTune in launch()).
@@ -547,6 +584,7 @@ KernelChoice ldsKernel(const rtc_scene* s, const DevPixelMap& map) {
   return s->ext_kernel ? RTC_KERNEL(rtc_render_kernel_ext) : RTC_KERNEL(rtc_render_kernel);
 }
 KernelChoice renderKernel(const rtc_scene* s, const DevPixelMap& map) {
+  if (mediaKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_media) : RTC_KERNEL(rtc_render_kernel_media_bigworld);
   if (shadowFilterKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_sfilter) : RTC_KERNEL(rtc_render_kernel_sfilter_bigworld);
   if (occlusionKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_occl) : RTC_KERNEL(rtc_render_kernel_occl_bigworld);
   if (glossKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_gloss) : RTC_KERNEL(rtc_render_kernel_gloss_bigworld);
@@ -567,6 +605,7 @@ KernelChoice renderKernel(const rtc_scene* s, const DevPixelMap& map) {
 
 // Work-groups of the launch's kernel that are resident at once, and the waves in them.
 uint32_t residentBlocksAlone(const rtc_scene* s, const DevPixelMap& map) {
+  if (mediaKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_media_lds : s->blocks_per_cu_media_big);
   if (shadowFilterKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_sfilt_lds : s->blocks_per_cu_sfilt_big);
   if (occlusionKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_occl_lds : s->blocks_per_cu_occl_big);
   if (glossKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_gloss_lds : s->blocks_per_cu_gloss_big);
@@ -852,6 +891,19 @@ int ensureScratch(rtc_scene* s, DevPixelMap& map, uint32_t blocks, uint32_t max_
     HIP_TRY(hipMalloc(&s->d_ray_stack, need));
     s->ray_stack_capacity = need;
   }
+  if (mediaKernels(s)) {
+    // (the media kernels' fifth quarter of every pending ray, 16 bytes beside the record's 64: a quarter of the ray stack's
+    // capacity holds a slot for every slot of it, whatever the launch's depth)
+    const size_t need_x = s->ray_stack_capacity / 4u;
+    if (need_x > s->media_stack_capacity) {
+      HIP_TRY(handleIdle(s));  // (the last launch may still be using the old buffer)
+      if (s->d_media_stack) (void)hipFree(s->d_media_stack);
+      s->d_media_stack = nullptr;
+      s->media_stack_capacity = 0;
+      HIP_TRY(hipMalloc(&s->d_media_stack, need_x));
+      s->media_stack_capacity = need_x;
+    }
+  }
   map.ray_stack = static_cast<PendingRec*>(s->d_ray_stack);
   map.ray_stack_levels = max_depth + 2u;
 #ifdef RTC_PROFILE
@@ -979,7 +1031,7 @@ int launch(rtc_scene* s, const rtc_camera& cam, const DevPixelMap& map_in, uint3
   int trial_slot = -1;
   {
     rtc_scene::KernelTune& T = s->tune;
-    const bool eligible = !samplingKernels(s) && !motionKernels(s) && !spotKernels(s) && !bumpKernels(s) && !torusKernels(s) && !meshuvKernels(s) && !glossKernels(s) && !occlusionKernels(s) && !shadowFilterKernels(s) &&  // (the sampling, motion, spot, bump, torus, meshuv, gloss, occlusion and shadow-filter kernels have no three-wave form)
+    const bool eligible = !samplingKernels(s) && !motionKernels(s) && !spotKernels(s) && !bumpKernels(s) && !torusKernels(s) && !meshuvKernels(s) && !glossKernels(s) && !occlusionKernels(s) && !shadowFilterKernels(s) && !mediaKernels(s) &&  // (the sampling, motion, spot, bump, torus, meshuv, gloss, occlusion, shadow-filter and media kernels have no three-wave form)
                           ((s->general3_ok && rtcOptions().waves3 < 0.0 && tablesInLds(s) &&
                             !(s->tab && s->tab->handles.load(std::memory_order_relaxed) > 1) &&
                             static_cast<double>(map.n_chunks) >= 4.0 * 4.0 * s->n_cus * s->blocks_per_cu_lds) ||
@@ -2371,6 +2423,10 @@ int uploadTables(const rtc_scene_desc& d, const SceneTraits& traits, const HostT
     s->blocks_per_cu_sfilt_lds = static_cast<uint32_t>(std::max(nb, 1));
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_sfilter_bigworld, 256, 0));
     s->blocks_per_cu_sfilt_big = static_cast<uint32_t>(std::max(nb, 1));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_media, 256, 0));  // (the media kernels: one pair for every world)
+    s->blocks_per_cu_media_lds = static_cast<uint32_t>(std::max(nb, 1));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_media_bigworld, 256, 0));
+    s->blocks_per_cu_media_big = static_cast<uint32_t>(std::max(nb, 1));
     if (const int v = static_cast<int>(rtcOptions().blocks_per_cu); v >= 1) {  // (tuning option)
       s->blocks_per_cu_lds = std::min<uint32_t>(s->blocks_per_cu_lds, v), s->blocks_per_cu_big = std::min<uint32_t>(s->blocks_per_cu_big, v);
       s->blocks_per_cu_ms_lds = std::min<uint32_t>(s->blocks_per_cu_ms_lds, v), s->blocks_per_cu_ms_big = std::min<uint32_t>(s->blocks_per_cu_ms_big, v);
@@ -2382,6 +2438,7 @@ int uploadTables(const rtc_scene_desc& d, const SceneTraits& traits, const HostT
       s->blocks_per_cu_gloss_lds = std::min<uint32_t>(s->blocks_per_cu_gloss_lds, v), s->blocks_per_cu_gloss_big = std::min<uint32_t>(s->blocks_per_cu_gloss_big, v);
       s->blocks_per_cu_occl_lds = std::min<uint32_t>(s->blocks_per_cu_occl_lds, v), s->blocks_per_cu_occl_big = std::min<uint32_t>(s->blocks_per_cu_occl_big, v);
       s->blocks_per_cu_sfilt_lds = std::min<uint32_t>(s->blocks_per_cu_sfilt_lds, v), s->blocks_per_cu_sfilt_big = std::min<uint32_t>(s->blocks_per_cu_sfilt_big, v);
+      s->blocks_per_cu_media_lds = std::min<uint32_t>(s->blocks_per_cu_media_lds, v), s->blocks_per_cu_media_big = std::min<uint32_t>(s->blocks_per_cu_media_big, v);
     }
   }
   DevScene& D = s->dev;
@@ -3053,6 +3110,54 @@ int rtc_scene_set_shadow_filters(rtc_scene* s, const rtc_shadow_filters* f) {
   return RTC_OK;
 }
 
+// ---- participating media
+// Validated on the host before any HIP call and before anything changes: first the table's own values - so that they are
+// checked whatever the handle -, then its material count against the handle's.  An absorption array that is NULL is all
+// zeros; every row zero and a density of zero is no medium: the handle's previous kernels.
+int rtc_scene_set_media(rtc_scene* s, const rtc_media* m) {
+  g_error.clear();
+  if (!s) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
+  bool any = false;
+  std::vector<double> rows;
+  if (m) {
+    const uint32_t n = m->n_materials;
+    for (uint32_t i = 0; i < n && m->absorption; ++i)
+      for (uint32_t c = 0; c < 3u; ++c) {
+        const double v = m->absorption[3ull * i + c];
+        if (!std::isfinite(v)) return fail(RTC_ERR_INVALID_ARGUMENT, "media: material %u: an absorption that is not finite", i);
+        if (v < 0.0) return fail(RTC_ERR_INVALID_ARGUMENT, "media: material %u: absorption %g is negative", i, v);
+        any = any || v != 0.0;
+      }
+    if (!std::isfinite(m->fog_density)) return fail(RTC_ERR_INVALID_ARGUMENT, "media: a fog density that is not finite");
+    if (m->fog_density < 0.0) return fail(RTC_ERR_INVALID_ARGUMENT, "media: fog density %g is negative", m->fog_density);
+    for (uint32_t c = 0; c < 3u; ++c) {
+      if (!std::isfinite(m->fog_color[c])) return fail(RTC_ERR_INVALID_ARGUMENT, "media: a fog colour that is not finite");
+      if (m->fog_color[c] < 0.0) return fail(RTC_ERR_INVALID_ARGUMENT, "media: fog colour %g is negative", m->fog_color[c]);
+    }
+    any = any || m->fog_density != 0.0;
+    if (n != s->dev.n_materials) return fail(RTC_ERR_INVALID_ARGUMENT, "media: n_materials %u, the scene has %u", n, s->dev.n_materials);
+    if (any) {
+      rows.assign(3ull * n, 0.0);
+      if (m->absorption) rows.assign(m->absorption, m->absorption + 3ull * n);
+    }
+  }
+  std::shared_ptr<const MediaTables> tables;  // (nothing absorbs and there is no fog: none)
+  if (any) {
+    auto t = std::make_shared<MediaTables>();
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(t->row.upload(rows));
+    t->fog_density = m->fog_density;
+    for (int c = 0; c < 3; ++c) t->fog_color[c] = m->fog_color[c];
+    tables = std::move(t);
+  }
+  // (the rows being replaced may still be read by a launch of this handle or of its band clones)
+  HIP_TRY(handleIdle(s));
+  for (rtc_scene* b : s->band) HIP_TRY(handleIdle(b));
+  s->media = tables;
+  for (rtc_scene* b : s->band) b->media = tables;  // (the band clones rtc_render renders a large frame with)
+  return RTC_OK;
+}
+
 // ---- adaptive sampling
 // The setting's own fields, and the image's tile count (T < 2^31)
 static int checkAdaptive(const rtc_adaptive* a, uint32_t hsize, uint32_t vsize, uint32_t* n_tiles) {
@@ -3281,6 +3386,9 @@ int rtc_scene_clone(const rtc_scene* src, rtc_scene** out) {
   s->shadow_filters = src->shadow_filters;  // (shared: read-only once made)
   s->blocks_per_cu_sfilt_lds = src->blocks_per_cu_sfilt_lds;
   s->blocks_per_cu_sfilt_big = src->blocks_per_cu_sfilt_big;
+  s->media = src->media;  // (shared: read-only once made; the fifth-quarter buffer is the handle's own, made at its first launch)
+  s->blocks_per_cu_media_lds = src->blocks_per_cu_media_lds;
+  s->blocks_per_cu_media_big = src->blocks_per_cu_media_big;
   s->simple_kernel = src->simple_kernel;
   s->flat_kernel = src->flat_kernel;
   s->simple3_ok = src->simple3_ok;
@@ -3338,6 +3446,7 @@ void rtc_scene_destroy(rtc_scene* s) {
   if (s->d_packet_time) (void)hipFree(s->d_packet_time);
   if (s->launch_done) (void)hipEventDestroy(s->launch_done);
   if (s->d_ray_stack) (void)hipFree(s->d_ray_stack);
+  if (s->d_media_stack) (void)hipFree(s->d_media_stack);
   if (s->d_csg_buf) (void)hipFree(s->d_csg_buf);
   if (s->d_accum_partials) (void)hipFree(s->d_accum_partials);
   if (s->d_adaptive_frame) (void)hipFree(s->d_adaptive_frame);
@@ -3701,7 +3810,7 @@ int rtc_set_option(const char* name, double value) {
                {"spot_kernels", &o.spot_kernels}, {"bump_kernels", &o.bump_kernels},
                {"torus_kernels", &o.torus_kernels}, {"meshuv_kernels", &o.meshuv_kernels},
                {"gloss_kernels", &o.gloss_kernels}, {"occlusion_kernels", &o.occlusion_kernels},
-               {"shadow_filter_kernels", &o.shadow_filter_kernels}};
+               {"shadow_filter_kernels", &o.shadow_filter_kernels}, {"media_kernels", &o.media_kernels}};
   for (const auto& e : table)
     if (std::strcmp(e.name, name) == 0) {
       e.slot->set(value);

@@ -398,6 +398,22 @@ struct DevShadowFilter {
   const double* __restrict__ row;  // [n_materials][3]
 };
 
+// Participating media (rtc_scene_set_media): the extra argument of the media kernels only.  Three
+// doubles per material, in mat_* order: the absorption per unit of world distance of red, green and blue, each >= 0
+// (0, 0, 0: the material as it is), and the one atmosphere; under the "media_kernels" option on a handle without media
+// every row, the density and the colour are zero.  `stack_ext`: the fifth 16-byte quarter - the green and blue weights -
+// of the pending rays whose record is in DevPixelMap::ray_stack, [resident waves][ray_stack_levels][64 lanes] as that
+// buffer is, 16 bytes a slot; sized with it, launch by launch.
+#ifndef RTC_NO_MEDIUM
+#define RTC_NO_MEDIUM 0xFFFFFFFFu  // (rtc.h's: a ray in the atmosphere)
+#endif
+struct DevMedia {
+  const double* __restrict__ absorption;  // [n_materials][3]
+  double fog_density;
+  double fog_color[3];
+  void* __restrict__ stack_ext;
+};
+
 struct DevCamera {
   double half_width, half_height, pixel_size;
   double inv[12];  // rows 0..2 of Camera._inverse_transform

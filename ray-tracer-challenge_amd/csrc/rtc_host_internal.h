@@ -74,6 +74,7 @@ struct RtcOptions {
   RtcOption gloss_kernels{0.0};        // != 0: the gloss kernels even on a handle without a rough material, every row zero (tests: against the handle's ordinary kernels)
   RtcOption occlusion_kernels{0.0};    // != 0: the occlusion kernels even on a handle without a radius, every row zero (tests: against the handle's ordinary kernels)
   RtcOption shadow_filter_kernels{0.0};  // != 0: the shadow-filter kernels even on a handle without a filter, every row zero (tests: against the handle's ordinary kernels)
+  RtcOption media_kernels{0.0};        // != 0: the media kernels even on a handle without media, every row and the density zero (tests: against the handle's ordinary kernels)
   RtcOption build_threads{0.0};        // threads of rtc_scene_create's candidate-BVH build (one top-level group each); 0: as many as the host allows, up to 8
 };
 inline RtcOptions& rtcOptions() {
@@ -178,6 +179,14 @@ struct ShadowFilterTables {
   DevBuf<double> row;
 };
 
+// A handle's media (rtc_scene_set_media): DevMedia's absorption rows and atmosphere.  Read-only once made: a clone and the
+// band clones share it.
+struct MediaTables {
+  DevBuf<double> row;
+  double fog_density = 0.0;
+  double fog_color[3] = {0.0, 0.0, 0.0};
+};
+
 // A handle's spot lights (rtc_scene_set_spots): DevSpots::row.  Read-only once made: a clone and the band clones share it.
 struct SpotTables {
   DevBuf<double> row;
@@ -240,6 +249,8 @@ struct rtc_scene {
   uint32_t blocks_per_cu_occl_lds = 1, blocks_per_cu_occl_big = 1;  // resident work-groups per CU of the occlusion kernels
   std::shared_ptr<const ShadowFilterTables> shadow_filters;  // rtc_scene_set_shadow_filters; null: no non-zero row (a clone starts with its source's)
   uint32_t blocks_per_cu_sfilt_lds = 1, blocks_per_cu_sfilt_big = 1;  // resident work-groups per CU of the shadow-filter kernels
+  std::shared_ptr<const MediaTables> media;  // rtc_scene_set_media; null: no absorbing row and no fog (a clone starts with its source's)
+  uint32_t blocks_per_cu_media_lds = 1, blocks_per_cu_media_big = 1;  // resident work-groups per CU of the media kernels
   bool simple3_ok = false;         // a simple world whose tables fit the three-waves-per-SIMD kernel's LDS (RTC_LDS3_*)
   void* d_csg_buf = nullptr;       // DevPixelMap::csg_buf, only for scenes with csg nodes
   size_t csg_buf_capacity = 0;     // bytes
@@ -308,6 +319,8 @@ struct rtc_scene {
   hipEvent_t launch_done = nullptr;   // recorded behind everything a launch enqueues; a launch on ANOTHER stream waits for it
   void* d_ray_stack = nullptr;     // DevPixelMap::ray_stack
   size_t ray_stack_capacity = 0;   // bytes
+  void* d_media_stack = nullptr;   // DevMedia::stack_ext: the media kernels' fifth quarter of every pending ray (ensureScratch)
+  size_t media_stack_capacity = 0; // bytes: a quarter of ray_stack_capacity, or 0 while no media kernel has run
   // ---- host output of a large frame (rtc_render): rendered in horizontal bands one after the other, each copied to the
   // caller while the next renders.  A band is a pixel map of its own: the lower bands run on clones of this handle (made on
   // first use), which keep their band's schedule from frame to frame.

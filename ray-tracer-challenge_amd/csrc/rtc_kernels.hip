@@ -2571,15 +2571,47 @@ struct Pending {
   // half of the word that holds `remaining`: the record stays 64 bytes.  Compiled into the gloss kernels' unit only.
   uint32_t code;
 #endif
+#ifdef RTC_MEDIA_TU
+  // (MEDIA) `weight` is the red channel's; the green and blue weights travel in a fifth 16-byte
+  // quarter beside the record (render_body), and the ray's medium - a material index, or RTC_NO_MEDIUM - rides in the upper
+  // half of the word that holds `remaining` (8 bits: at most RTC_MAX_DEPTH) and the path code (24 bits: below 2^17): every
+  // 32-bit material index fits, and the record itself stays 64 bytes.  Compiled into the media kernels' unit only.
+  double weight_g, weight_b;
+  uint32_t medium;
+#endif
 };
-#ifdef RTC_GLOSS_TU
+#ifdef RTC_MEDIA_TU
+static_assert(RTC_MAX_DEPTH < 256, "a Pending's `remaining` has eight bits beside the path code and the medium");
+#define RTC_PENDING_TAIL(p) \
+  (static_cast<unsigned long long>((p).remaining) | (static_cast<unsigned long long>((p).code) << 8) | (static_cast<unsigned long long>((p).medium) << 32))
+#define RTC_PENDING_REMAINING(word) (static_cast<uint32_t>(word) & 0xFFu)
+#define RTC_PENDING_CODE(p, word) (p).code = (static_cast<uint32_t>(word) >> 8), (p).medium = static_cast<uint32_t>((word) >> 32)
+#define RTC_SET_CODE(p, c) (p).code = (c)
+#elif defined(RTC_GLOSS_TU)
 #define RTC_PENDING_TAIL(p) (static_cast<unsigned long long>((p).remaining) | (static_cast<unsigned long long>((p).code) << 32))
+#define RTC_PENDING_REMAINING(word) static_cast<uint32_t>(word)
 #define RTC_PENDING_CODE(p, word) (p).code = static_cast<uint32_t>((word) >> 32)
 #define RTC_SET_CODE(p, c) (p).code = (c)
 #else
 #define RTC_PENDING_TAIL(p) (p).remaining
+#define RTC_PENDING_REMAINING(word) static_cast<uint32_t>(word)
 #define RTC_PENDING_CODE(p, word)
 #define RTC_SET_CODE(p, c)
+#endif
+// (MEDIA) what the media unit adds where a ray is made, weighted or moved; nothing in every other unit
+#ifdef RTC_MEDIA_TU
+#define RTC_W(p, c) (p).weight_##c
+#define RTC_MEDIA_START(p, w) (p).weight_g = (w), (p).weight_b = (w), (p).medium = RTC_NO_MEDIUM
+#define RTC_MEDIA_KID(kid, parent, w, m) \
+  (kid).weight_g = (parent).weight_g * (w), (kid).weight_b = (parent).weight_b * (w), (kid).medium = (m)
+#define RTC_MEDIA_PUSH_EXTRA(level, p) push_extra(level, p)
+#define RTC_MEDIA_LOAD_EXTRA(p, level, of_lane) load_extra(p, level, of_lane)
+#else
+#define RTC_W(p, c) (p).weight
+#define RTC_MEDIA_START(p, w) (void)0
+#define RTC_MEDIA_KID(kid, parent, w, m) (void)0
+#define RTC_MEDIA_PUSH_EXTRA(level, p) (void)0
+#define RTC_MEDIA_LOAD_EXTRA(p, level, of_lane) (void)0
 #endif
 
 // A Pending as it sits on a lane's stack in memory: one 64-byte line, moved as four 16-byte accesses.
@@ -2601,7 +2633,7 @@ __device__ __forceinline__ Pending load_pending(const PendingRec* src) {
   Pending p;
   p.ray = {bitsd(a.x), bitsd(a.y), bitsd(b.x), bitsd(b.y), bitsd(c.x), bitsd(c.y)};
   p.weight = bitsd(e.x);
-  p.remaining = static_cast<uint32_t>(e.y);
+  p.remaining = RTC_PENDING_REMAINING(e.y);
   RTC_PENDING_CODE(p, e.y);
   return p;
 }
@@ -2621,7 +2653,7 @@ __device__ __forceinline__ Pending load_pending_lds(const Quad2* src) {
   Pending p;
   p.ray = {bitsd(a.x), bitsd(a.y), bitsd(b.x), bitsd(b.y), bitsd(c.x), bitsd(c.y)};
   p.weight = bitsd(e.x);
-  p.remaining = static_cast<uint32_t>(e.y);
+  p.remaining = RTC_PENDING_REMAINING(e.y);
   RTC_PENDING_CODE(p, e.y);
   return p;
 }
@@ -2845,9 +2877,13 @@ __device__ __noinline__ GlossDir occl_direction(unsigned long long h, uint32_t w
 // (SFILT: shadow filters - DevShadowFilter, the shadow-filter kernels' extra argument: a light's shadow ray multiplies the
 // filter rows of the entries it crosses instead of stopping at the first.  With OCCL and everything below it, compiled into
 // the shadow-filter kernels' translation unit only, under RTC_SFILT_TU, which implies RTC_OCCL_TU)
+// (MEDIA: participating media - DevMedia, the media kernels' extra argument: every ray of the tree carries a medium and a
+// weight per channel, and is attenuated along its segment (Beer-Lambert absorption in a material, a uniform fog outside).
+// With SFILT and everything below it, compiled into the media kernels' translation unit only, under RTC_MEDIA_TU, which
+// implies RTC_SFILT_TU)
 template <bool LDS, bool CSG, int WORLD = 0, int WAVES = 2, bool COOP = false, bool BOX = true, bool AREA = false, bool MS = false,
           bool MOTION = false, bool SPOT = false, bool BUMP = false, bool TORUS = false, bool MESHUV = false, bool GLOSS = false,
-          bool OCCL = false, bool SFILT = false>
+          bool OCCL = false, bool SFILT = false, bool MEDIA = false>
 __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& cam, const DevPixelMap& map,
                                             const uint32_t max_depth, double* __restrict__ out,
                                             DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
@@ -2855,7 +2891,8 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
                                             const DevMotion& mo = DevMotion{}, const DevSpots& spots = DevSpots{},
                                             const DevBumps& bumps = DevBumps{}, const DevMeshUvs& muv = DevMeshUvs{},
                                             const DevGloss& gloss = DevGloss{}, const DevOcclusion& occl = DevOcclusion{},
-                                            const DevShadowFilter& sfilt = DevShadowFilter{}) {
+                                            const DevShadowFilter& sfilt = DevShadowFilter{},
+                                            const DevMedia& media = DevMedia{}) {
   static_assert(!AREA || !COOP, "the area kernels run no cooperative iterations");
   static_assert(!MS || !COOP, "the sampling kernels run no cooperative iterations");
   static_assert(!MOTION || (MS && AREA && WORLD == 0), "the motion kernels are the general area-sampling walk");
@@ -2894,6 +2931,13 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
 #else
   static_assert(!SFILT, "shadow filters are compiled in the shadow-filter translation unit (rtc_shadowfilter.hip) only");
   (void)sfilt;
+#endif
+  static_assert(!MEDIA || SFILT, "the media kernels are the shadow-filter walk");
+#ifdef RTC_MEDIA_TU
+  static_assert(MEDIA, "the media translation unit compiles the media kernels only: its Pending carries a medium and three weights");
+#else
+  static_assert(!MEDIA, "participating media are compiled in the media translation unit (rtc_media.hip) only");
+  (void)media;
 #endif
   RTC_PRIO_PHASE(RTC_PRIO_WORK);
 #ifndef RTC_PROFILE
@@ -2943,7 +2987,9 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
   // per lane: the top of the BVH walk's stack (the eight-wide walk's entries are pairs of words)
   // (the three-wave general kernel keeps two entries in LDS: the eight-wide walk's stack is as deep as the tree and
   // mostly one or two entries long)
-  constexpr int TRAV = (WAVES == 3 && RTC_BVH8) ? 2 : RTC_LDS_TRAV;
+  // (MEDIA: the general media kernel keeps two entries fewer in LDS - 4 096 bytes, what the fifth quarter of its pending
+  // rays' one LDS level takes: two work-groups per CU stay resident)
+  constexpr int TRAV = (WAVES == 3 && RTC_BVH8) ? 2 : ((MEDIA && LDS && !FLAT) ? RTC_LDS_TRAV - 2 : RTC_LDS_TRAV);
   __shared__ uint32_t lds_trav[FLAT ? 1 : 4][FLAT ? 1 : TRAV][RTC_BVH8 ? 128 : 64];
   const RootRec* __restrict__ recs = S.root_recs;
   CullTables cull{S.root_cull, S.root_box};
@@ -3083,6 +3129,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
   cur.weight = 0.0;
   cur.remaining = 0u;
   RTC_SET_CODE(cur, 0u);
+  RTC_MEDIA_START(cur, 0.0);
   // The lane's pending refraction siblings: a deque.  The lane itself pops the newest entry (depth
   // first); an idle neighbour may take the OLDEST one (the largest sub-tree) through the mailbox.
   // It lives in a buffer of its own rather than in scratch: scratch interleaves the lanes dword by dword,
@@ -3112,6 +3159,41 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
 #endif
     return load_pending(stack + static_cast<size_t>(level) * 64u - lane + of_lane);
   };
+#ifdef RTC_MEDIA_TU
+  // (MEDIA) the fifth quarter of every record - the green and blue weights - beside the four: for the levels in LDS in an
+  // array of its own ([wave][level][lane]), for the levels in memory in DevMedia::stack_ext, laid out and sized as
+  // DevPixelMap::ray_stack is ([wave][level][lane], 16 bytes a slot).  It moves wherever the record moves: push, pop, and
+  // the read of a neighbour's oldest level.
+  __shared__ Quad2 lds_pend_x[4][LDS_LEVELS][64];
+  Quad2* const pend_x_wave = &lds_pend_x[threadIdx.x >> 6][0][0];
+  Quad2* const stack_x = static_cast<Quad2*>(media.stack_ext) +
+      (static_cast<size_t>(blockIdx.x) * 4u + (threadIdx.x >> 6)) * map.ray_stack_levels * 64u + lane;
+  auto push_extra = [&](int level, const Pending& p) {
+    Quad2 x;
+    x.x = dbits(p.weight_g); x.y = dbits(p.weight_b);
+    if (level < LDS_LEVELS) {
+      pend_x_wave[level * 64 + lane] = x;
+    } else {
+#ifdef RTC_PROFILE
+      if (!RTC_IN_BOUNDS(RTC_OOB_PENDING, stack_ok && static_cast<uint32_t>(level) < map.ray_stack_levels)) return;
+#endif
+      stack_x[static_cast<size_t>(level) * 64u] = x;
+    }
+  };
+  auto load_extra = [&](Pending& p, int level, uint32_t of_lane) {
+    Quad2 x;
+    if (level < LDS_LEVELS) {
+      x = pend_x_wave[level * 64 + of_lane];
+    } else {
+#ifdef RTC_PROFILE
+      if (!RTC_IN_BOUNDS(RTC_OOB_PENDING, stack_ok && static_cast<uint32_t>(level) < map.ray_stack_levels && of_lane < 64u)) return;
+#endif
+      x = (stack_x + static_cast<size_t>(level) * 64u - lane)[of_lane];
+    }
+    p.weight_g = bitsd(x.x);
+    p.weight_b = bitsd(x.y);
+  };
+#endif
 
 #ifdef RTC_PROFILE
   unsigned long long prof_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -3136,6 +3218,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
     if (!have_cur) {
       if (sp > base) {
         cur = load_level(--sp, lane);
+        RTC_MEDIA_LOAD_EXTRA(cur, sp, lane);
         have_cur = true;
       } else {
         sp = base = 0;
@@ -3222,6 +3305,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
           // (the donor's slot is read here, in program order before any lane of the wave can push into it again)
           const uint4 m = mailbox[irank];
           cur = load_level(static_cast<int>(m.y), MS ? m.x & 63u : m.x);
+          RTC_MEDIA_LOAD_EXTRA(cur, static_cast<int>(m.y), MS ? m.x & 63u : m.x);
           if constexpr (MS) *samp_word = m.x >> 8;  // (the sample's index; not the owner)
           out_index = static_cast<size_t>(m.z) | (static_cast<size_t>(m.w) << 32);
           have_cur = true;
@@ -3352,6 +3436,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
         }
         cur.ray = camera_sample(cam, smp, new_px, new_py, k);
         cur.weight = smp.weight;  // (the pixel is the samples' mean: each adds 1 / samples of its colour)
+        RTC_MEDIA_START(cur, smp.weight);  // (MEDIA: the camera stands in the atmosphere)
         cur.remaining = max_depth;
         RTC_SET_CODE(cur, 1u);  // (GLOSS) the primary ray
         have_cur = true;
@@ -3381,6 +3466,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
       cur.ray.dy = dy;
       cur.ray.dz = dz;
       cur.weight = 1.0;
+      RTC_MEDIA_START(cur, 1.0);
       cur.remaining = max_depth;
       RTC_SET_CODE(cur, 1u);  // (GLOSS) the primary ray
       have_cur = true;
@@ -3469,6 +3555,44 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
       RTC_HIST_END(0);
     }
     RTC_STAMP(2);
+#ifdef RTC_MEDIA_TU
+    // (MEDIA, rtc.h's rtc_scene_set_media) the step: the segment's transmittance per channel, before shading and before the
+    // children are formed; in the atmosphere the fog's in-scatter goes to the pixel.  sigma == 0 gives T == 1 exactly and
+    // a density of zero forms no fog term: a handle without media keeps its bits.  A wave none of whose lanes has a
+    // non-zero sigma branches around the three exp.
+    if constexpr (MEDIA) {
+      const bool atmosphere = cur.medium == RTC_NO_MEDIUM;
+      double s_r = media.fog_density, s_g = media.fog_density, s_b = media.fog_density;
+      if (!atmosphere) {
+        const double* __restrict__ A = media.absorption + 3ull * cur.medium;
+        s_r = A[0];
+        s_g = A[1];
+        s_b = A[2];
+      }
+      double t_r = 1.0, t_g = 1.0, t_b = 1.0;
+      if (__any(s_r != 0.0 || s_g != 0.0 || s_b != 0.0)) {
+        if (hv.leaf != RTC_NO_LEAF) {
+          const double dist = hv.t * __builtin_sqrt((ray.dx * ray.dx + ray.dy * ray.dy) + ray.dz * ray.dz);
+          t_r = s_r == 0.0 ? 1.0 : exp(-(s_r * dist));
+          t_g = s_g == 0.0 ? 1.0 : exp(-(s_g * dist));
+          t_b = s_b == 0.0 ? 1.0 : exp(-(s_b * dist));
+        } else {
+          t_r = s_r == 0.0 ? 1.0 : 0.0;
+          t_g = s_g == 0.0 ? 1.0 : 0.0;
+          t_b = s_b == 0.0 ? 1.0 : 0.0;
+        }
+      }
+      if (atmosphere && media.fog_density > 0.0) {
+        acc[0] = acc[0] + cur.weight * ((1.0 - t_r) * media.fog_color[0]);
+        acc[1] = acc[1] + cur.weight_g * ((1.0 - t_g) * media.fog_color[1]);
+        acc[2] = acc[2] + cur.weight_b * ((1.0 - t_b) * media.fog_color[2]);
+      }
+      cur.weight = cur.weight * t_r;
+      cur.weight_g = cur.weight_g * t_g;
+      cur.weight_b = cur.weight_b * t_b;
+    }
+    uint32_t kid_medium = RTC_NO_MEDIUM;  // the medium of a refracted child: the material that supplies n2, or none
+#endif
     if (hv.leaf == RTC_NO_LEAF) continue;  // black (world.zig:119)
 
     // ---- PreComputations.new (world.zig:212-227)
@@ -3538,6 +3662,10 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
       } else if (bv.hit_dups >= 2u) {
         n2 = hit_ior;
       }
+#ifdef RTC_MEDIA_TU
+      // (MEDIA) the refracted child's medium: the material whose ior was just taken for n2
+      kid_medium = !bv.hit_open ? mat_index : (bv.best_excl_leaf != RTC_NO_LEAF ? bv.best_excl_mat : (bv.hit_dups >= 2u ? mat_index : RTC_NO_MEDIUM));
+#endif
     }
     const double ptx = ray.ox + ray.dx * t, pty = ray.oy + ray.dy * t, ptz = ray.oz + ray.dz * t;  // ray.position
     const double ex = -ray.dx, ey = -ray.dy, ez = -ray.dz;                                          // eyev
@@ -4025,8 +4153,8 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
       yield.contrib[2] = cur.weight * sb;
     } else {
       acc[0] += cur.weight * sr;
-      acc[1] += cur.weight * sg;
-      acc[2] += cur.weight * sb;
+      acc[1] += RTC_W(cur, g) * sg;
+      acc[2] += RTC_W(cur, b) * sb;
     }
 
     RTC_STAMP(6);
@@ -4094,6 +4222,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
       const double two_dot = 2.0 * ((ray.dx * hx + ray.dy * hy) + ray.dz * hz);  // direction.reflect(normal)
       child.ray = {ovx, ovy, ovz, ray.dx - hx * two_dot, ray.dy - hy * two_dot, ray.dz - hz * two_dot};
       child.weight = cur.weight * w_reflect;
+      RTC_MEDIA_KID(child, cur, w_reflect, cur.medium);  // (MEDIA: a reflected child stays in its parent's medium)
       RTC_SET_CODE(child, 2u * cur.code);
 #ifdef RTC_GLOSS_TU
       if (rough_r > 0.0) {
@@ -4112,6 +4241,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
       Pending p;
       p.ray = {unx, uny, unz, hx * k - ex * n_ratio, hy * k - ey * n_ratio, hz * k - ez * n_ratio};
       p.weight = cur.weight * w_refract;
+      RTC_MEDIA_KID(p, cur, w_refract, kid_medium);
       p.remaining = cur.remaining - 1u;
       RTC_SET_CODE(p, 2u * cur.code + 1u);
 #ifdef RTC_GLOSS_TU
@@ -4129,6 +4259,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
           yield.n_kids = 1u;
         } else {
           if (sp < stack_cap) {
+            RTC_MEDIA_PUSH_EXTRA(sp, p);
             push_level(sp++, p);
           } else {
             overflow = CSG ? (overflow | 1u) : 1u;
@@ -4273,7 +4404,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
 // and the torus kernels, rtc_meshuv.hip with RTC_MESHUV_TU (and, with it, RTC_TORUS_TU) and the meshuv kernels, rtc_gloss.hip
 // with RTC_GLOSS_TU (and, with it, both of those) and the gloss kernels, rtc_occlusion.hip with RTC_OCCL_TU (and, with it, those
 // three) and the occlusion kernels, rtc_shadowfilter.hip with RTC_SFILT_TU (and, with it, those four) and the shadow-filter
-// kernels.  rtc_kernels_ext.hip
+// kernels, rtc_media.hip with RTC_MEDIA_TU (and, with it, those five) and the media kernels.  rtc_kernels_ext.hip
 // includes it with RTC_EXT_TU defined: in the -DRTC_PROFILE diagnostic build, whose instrumented walk makes this unit's
 // compile about a third longer, it gets the csg / texture-map, flat and area-light kernels (rtc_render_kernel_ext to
 // rtc_render_kernel_area_bigworld below), so that neither unit takes the time of all of them.  The product build keeps
@@ -5146,6 +5277,32 @@ rtc_render_kernel_bump_bigworld(const DevScene S, const DevCamera cam, const Dev
                                                                             spots, bumps);
 }
 
+#elif defined(RTC_MEDIA_TU)
+
+// Participating media (rtc_scene_set_media): the shadow-filter walk with a medium and a weight per
+// channel carried by every ray of the tree, the segment's transmittance applied after every closest-hit trace, and the
+// absorption rows, the atmosphere and the pending rays' fifth quarter in memory (DevMedia) as one more argument; one pair
+// for every world.  Every other kernel is compiled without it.
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_media(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                        double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                        const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots, const DevBumps bumps,
+                        const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl, const DevShadowFilter sfilt,
+                        const DevMedia media) {
+  render_body<true, true, 0, 2, false, true, true, true, true, true, true, true, true, true, true, true, true>(
+      S, cam, map, max_depth, out, stats, next_stats, area, smp, mo, spots, bumps, muv, gloss, occl, sfilt, media);
+}
+
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_media_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                 double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                 const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                 const DevBumps bumps, const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl,
+                                 const DevShadowFilter sfilt, const DevMedia media) {
+  render_body<false, true, 0, 2, false, true, true, true, true, true, true, true, true, true, true, true, true>(
+      S, cam, map, max_depth, out, stats, next_stats, area, smp, mo, spots, bumps, muv, gloss, occl, sfilt, media);
+}
+
 #elif defined(RTC_SFILT_TU)
 
 // Shadow filters (rtc_scene_set_shadow_filters): the occlusion walk with every light's shadow ray
@@ -5263,4 +5420,4 @@ rtc_render_kernel_torus_bigworld(const DevScene S, const DevCamera cam, const De
                                                                                   smp, mo, spots, bumps);
 }
 
-#endif  // RTC_MOTION_TU / RTC_SPOT_TU / RTC_BUMP_TU / RTC_SFILT_TU / RTC_OCCL_TU / RTC_GLOSS_TU / RTC_MESHUV_TU / RTC_TORUS_TU
+#endif  // RTC_MOTION_TU / RTC_SPOT_TU / RTC_BUMP_TU / RTC_MEDIA_TU / RTC_SFILT_TU / RTC_OCCL_TU / RTC_GLOSS_TU / RTC_MESHUV_TU / RTC_TORUS_TU

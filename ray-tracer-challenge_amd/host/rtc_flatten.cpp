@@ -140,6 +140,13 @@ struct Flattener {
       const double filt[5] = {-2.0, m.shadow_filter.r, m.shadow_filter.g, m.shadow_filter.b, -2.0};
       appendBits(key, filt, 5);
     }
+    // (likewise a material with an "absorption": a row of its own only when a value is non-zero)
+    out.absorption_present = out.absorption_present || m.absorption.present;
+    if (m.absorption.r != 0.0 || m.absorption.g != 0.0 || m.absorption.b != 0.0) {
+      // (a tag of its own before the values: an absorption never shares a key with a filter of the same bits)
+      const double absn[5] = {-3.0, m.absorption.r, m.absorption.g, m.absorption.b, -3.0};
+      appendBits(key, absn, 5);
+    }
     auto it = material_ids.find(key);
     if (it != material_ids.end()) return it->second;
     const uint32_t id = static_cast<uint32_t>(out.mat_pattern.size());
@@ -152,6 +159,9 @@ struct Flattener {
     out.mat_shadow_filter.push_back(m.shadow_filter.r);
     out.mat_shadow_filter.push_back(m.shadow_filter.g);
     out.mat_shadow_filter.push_back(m.shadow_filter.b);
+    out.mat_absorption.push_back(m.absorption.r);
+    out.mat_absorption.push_back(m.absorption.g);
+    out.mat_absorption.push_back(m.absorption.b);
     material_ids.emplace(std::move(key), id);
     return id;
   }

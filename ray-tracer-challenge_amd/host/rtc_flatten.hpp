@@ -32,6 +32,8 @@ struct FlatScene {
   bool occlusion_present = false;     // some material of the scene has the "ambient-occlusion" key
   std::vector<double> mat_shadow_filter;  // [n_materials][3]: each row's "shadow-filter" (rtch_scene_shadow_filters; not part of rtc_scene_desc)
   bool shadow_filter_present = false;     // some material of the scene has the "shadow-filter" key
+  std::vector<double> mat_absorption;  // [n_materials][3]: each row's "absorption" (rtch_scene_media; not part of rtc_scene_desc)
+  bool absorption_present = false;     // some material of the scene has the "absorption" key
   std::vector<Bump> mat_bump;  // [n_materials]: each row's "normal-perturbation" (rtch_scene_bumps; not part of rtc_scene_desc)
   std::vector<uint8_t> pat_kind;
   std::vector<double> pat_inv, pat_rgb;

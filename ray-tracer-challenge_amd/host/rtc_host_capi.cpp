@@ -179,6 +179,22 @@ int rtch_scene_shadow_filters(void* h, double* rgb, int* present, uint32_t n) {
   });
 }
 
+// The materials' "absorption" rows, in mat_* order, three doubles each, and the scene's "atmosphere"
+// (fog[0]: the density; fog[1..3]: the colour), as rtc_scene_set_media takes them; *present: some material of the file has
+// the key, or the file has an atmosphere.
+int rtch_scene_media(void* h, double* absorption, double* fog, int* present, uint32_t n) {
+  return guarded([&] {
+    const HostScene* hs = static_cast<HostScene*>(h);
+    if (n != hs->desc.n_materials)
+      throw rtc::Error("InvalidArgument", "media: n " + std::to_string(n) + ", the scene has " + std::to_string(hs->desc.n_materials) + " materials");
+    if ((n != 0u && !absorption) || !fog) throw rtc::Error("InvalidArgument", "media: null argument");
+    for (size_t i = 0; i < 3u * static_cast<size_t>(n); ++i) absorption[i] = hs->flat.mat_absorption[i];  // (mat_* order)
+    fog[0] = hs->info.fog_density;
+    for (int c = 0; c < 3; ++c) fog[1 + c] = hs->info.fog_color[c];
+    if (present) *present = (hs->flat.absorption_present || hs->info.atmosphere_present) ? 1 : 0;
+  });
+}
+
 // The triangles' texture rows (RTC_TEX_MESH), in tri_* order, as rtc_scene_set_mesh_uvs takes them.
 int rtch_scene_mesh_uvs(void* h, double* uv, uint32_t n) {
   return guarded([&] {
@@ -308,6 +324,11 @@ int rtch_scene_render(void* h, uint32_t width, uint32_t height, uint32_t max_dep
       if (st == RTC_OK && hs->flat.shadow_filter_present) {  // (the materials' shadow filters; all zero: the handle as it is)
         const rtc_shadow_filters sf{hs->desc.n_materials, hs->flat.mat_shadow_filter.data()};
         st = rtc_scene_set_shadow_filters(scene, &sf);
+      }
+      if (st == RTC_OK && (hs->flat.absorption_present || hs->info.atmosphere_present)) {  // (the media; all zero: the handle as it is)
+        const rtc_media me{hs->desc.n_materials, hs->flat.mat_absorption.data(), hs->info.fog_density,
+                           {hs->info.fog_color[0], hs->info.fog_color[1], hs->info.fog_color[2]}};
+        st = rtc_scene_set_media(scene, &me);
       }
       const rtc::CameraSampling& cs = hs->info.sampling;
       if (cs.adaptive && st == RTC_OK) {  // (adaptive sampling: each tile's mean after its own passes, section 15)

@@ -491,10 +491,54 @@ ShadowFilter parseShadowFilter(const Value& cfg) {
   return f;
 }
 
+// A material's "absorption" (not in the reference): a number a - (a, a, a) -, [r, g, b], or
+// {"color": [r, g, b], "distance": d} - white light has that colour after d units inside the material: -log(color.c) / d,
+// color.c in (0, 1], d > 0 and finite; a -0.0 is stored as 0.0 -; each value finite and >= 0.
+Absorption parseAbsorption(const Value& cfg) {
+  auto one = [](const Value& v) {
+    if (v.type != Value::Number) throw Error("InvalidData", "absorption: a number >= 0, [r, g, b] or {color, distance}");
+    const double x = asFloat(v, "absorption");
+    if (!(std::isfinite(x) && x >= 0.0)) throw Error("InvalidData", "absorption: a finite number >= 0");
+    return x;
+  };
+  Absorption a;
+  a.present = true;
+  if (cfg.type == Value::Object) {
+    checkFields(cfg, {"color", "distance"}, "absorption");
+    const Value& col = requireField(cfg, "color", "absorption");
+    if (col.type != Value::Array) throw Error("InvalidData", "absorption: color is [r, g, b]");
+    if (col.arr.size() != 3) throw Error("LengthMismatch", "absorption: color is [r, g, b]");
+    const Value& dv = requireField(cfg, "distance", "absorption");
+    if (dv.type != Value::Number) throw Error("InvalidData", "absorption: distance is a number > 0");
+    const double d = asFloat(dv, "absorption");
+    if (!(std::isfinite(d) && d > 0.0)) throw Error("InvalidData", "absorption: distance is a finite number > 0");
+    double s[3];
+    for (int i = 0; i < 3; ++i) {
+      if (col.arr[i].type != Value::Number) throw Error("InvalidData", "absorption: color is three numbers in (0, 1]");
+      const double c = asFloat(col.arr[i], "absorption");
+      if (!(c > 0.0 && c <= 1.0)) throw Error("InvalidData", "absorption: color is three numbers in (0, 1]");
+      const double v = -std::log(c) / d;
+      if (!std::isfinite(v)) throw Error("InvalidData", "absorption: color and distance give a value that is not finite");
+      s[i] = v == 0.0 ? 0.0 : v;  // (-0.0 is stored as 0.0)
+    }
+    a.r = s[0];
+    a.g = s[1];
+    a.b = s[2];
+  } else if (cfg.type == Value::Array) {
+    if (cfg.arr.size() != 3) throw Error("LengthMismatch", "absorption: [r, g, b]");
+    a.r = one(cfg.arr[0]);
+    a.g = one(cfg.arr[1]);
+    a.b = one(cfg.arr[2]);
+  } else {
+    a.r = a.g = a.b = one(cfg);
+  }
+  return a;
+}
+
 Material parseMaterial(const Value& cfg, const std::optional<Material>& inherited, const FileLoader& load_file_data) {
   requireObject(cfg, "material");
   checkFields(cfg, {"pattern", "ambient", "diffuse", "specular", "shininess", "reflective", "transparency",
-                    "refractive-index", "normal-perturbation", "roughness", "ambient-occlusion", "shadow-filter"}, "material");
+                    "refractive-index", "normal-perturbation", "roughness", "ambient-occlusion", "shadow-filter", "absorption"}, "material");
   Material mat = inherited ? *inherited : Material{};
   auto present = [&](const char* k) -> const Value* {
     const Value* v = cfg.find(k);
@@ -512,6 +556,7 @@ Material parseMaterial(const Value& cfg, const std::optional<Material>& inherite
   if (auto* v = present("roughness")) mat.roughness = parseRoughness(*v);
   if (auto* v = present("ambient-occlusion")) mat.occlusion = parseOcclusion(*v);
   if (auto* v = present("shadow-filter")) mat.shadow_filter = parseShadowFilter(*v);
+  if (auto* v = present("absorption")) mat.absorption = parseAbsorption(*v);
   if (mat.shadow_filter.from_transparency) {  // (`true`, the material's own or an inherited one: this material's transparency)
     const double t = mat.transparency;
     if (!(std::isfinite(t) && t >= 0.0 && t <= 1.0)) throw Error("InvalidData", "shadow-filter: true needs a transparency in [0, 1]");
@@ -735,7 +780,7 @@ unsigned loaderThreads() {
 SceneInfo parseScene(const std::string& scene_json, const FileLoader& load_file_data) {
   const Value root = json::parse(scene_json);
   requireObject(root, "scene");
-  checkFields(root, {"shape-definitions", "camera", "lights", "objects"}, "scene");
+  checkFields(root, {"shape-definitions", "camera", "lights", "objects", "atmosphere"}, "scene");
 
   Definitions definitions;
   if (const Value* defs = root.find("shape-definitions")) {
@@ -761,6 +806,24 @@ SceneInfo parseScene(const std::string& scene_json, const FileLoader& load_file_
   const Tuple from = Tuple::point(f[0], f[1], f[2]);
   const Tuple to = Tuple::point(t[0], t[1], t[2]);
   const Tuple up = Tuple::vec3(u[0], u[1], u[2]);
+  // "atmosphere" (not in the reference): the uniform fog outside every solid
+  if (const Value* atm = root.find("atmosphere")) {
+    requireObject(*atm, "atmosphere");
+    checkFields(*atm, {"density", "color"}, "atmosphere");
+    info.atmosphere_present = true;
+    const Value& dv = requireField(*atm, "density", "atmosphere");
+    if (dv.type != Value::Number) throw Error("InvalidData", "atmosphere: density is a number >= 0");
+    info.fog_density = asFloat(dv, "atmosphere");
+    if (!(std::isfinite(info.fog_density) && info.fog_density >= 0.0)) throw Error("InvalidData", "atmosphere: density is a finite number >= 0");
+    const Value& col = requireField(*atm, "color", "atmosphere");
+    if (col.type != Value::Array) throw Error("InvalidData", "atmosphere: color is [r, g, b]");
+    if (col.arr.size() != 3) throw Error("LengthMismatch", "atmosphere: color is [r, g, b]");
+    for (int i = 0; i < 3; ++i) {
+      if (col.arr[i].type != Value::Number) throw Error("InvalidData", "atmosphere: color is three numbers >= 0");
+      info.fog_color[i] = asFloat(col.arr[i], "atmosphere");
+      if (!(std::isfinite(info.fog_color[i]) && info.fog_color[i] >= 0.0)) throw Error("InvalidData", "atmosphere: color is three finite numbers >= 0");
+    }
+  }
   info.camera.saved_from = from;
   info.camera.saved_to = to;
   info.camera.saved_up = up;

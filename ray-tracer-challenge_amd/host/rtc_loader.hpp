@@ -50,6 +50,10 @@ struct SceneInfo {  // scene.zig:608-610
   CameraSampling sampling;
   std::vector<double> motion;  // [objects][3]: each top-level object's optional "motion" (DESIGN.md section 14), else 0
   std::vector<SpotCone> spots;  // [lights]: a "spot-light" entry's cone (section 16); cone 0 for every other light
+  // the scene's "atmosphere": {"density": d, "color": [r, g, b]} (section 23): rtc_media's fog; all zero without the key
+  bool atmosphere_present = false;
+  double fog_density = 0.0;
+  double fog_color[3] = {0.0, 0.0, 0.0};
 };
 
 // scene.zig:612-661.  Throws rtc::Error whose .name is the Zig error name

@@ -117,6 +117,14 @@ struct ShadowFilter {
   bool present = false;
 };
 
+// A material's "absorption" (not in the reference), as rtc_scene_set_media takes it: what a unit of
+// world distance inside the material absorbs of red, green and blue, each >= 0; (0, 0, 0): the material as it is.
+// `present`: the material, or one it inherits from, has the key.
+struct Absorption {
+  double r = 0.0, g = 0.0, b = 0.0;
+  bool present = false;
+};
+
 struct Material {  // material.zig:18-25
   Pattern pattern = Pattern::solid({1.0, 1.0, 1.0});
   double ambient = 0.1, diffuse = 0.9, specular = 0.9, shininess = 200.0;
@@ -125,6 +133,7 @@ struct Material {  // material.zig:18-25
   Roughness roughness;  // (0, 0 in every scene of the reference)
   Occlusion occlusion;  // (0 in every scene of the reference)
   ShadowFilter shadow_filter;  // (0, 0, 0 in every scene of the reference)
+  Absorption absorption;  // (0, 0, 0 in every scene of the reference)
 };
 
 struct Light {  // light.zig:14-15

@@ -55,6 +55,10 @@ occlusion_kernels=1 times the occlusion kernels without a radius.  With --passes
 and blue through each of its entries (rtc_scene_set_shadow_filters); on a scene file with
 "shadow-filter" entries those are applied first; --shadow-filter off applies none.  Option shadow_filter_kernels=1 times the
 shadow-filter kernels without a filter.  With --passes the noise run has the same table.
+--media MATERIAL=r,g,b (repeatable): material row MATERIAL (mat_* order) absorbs that much of red, green and blue per unit of
+world distance; --media fog=density,r,g,b: the atmosphere (rtc_scene_set_media); on a scene file with
+"absorption" entries or an "atmosphere" those are applied first; --media off applies none.  Option media_kernels=1 times the
+media kernels without media.  With --passes the noise run has the same table.
 --adaptive threshold[,min,tile]: adaptive sampling at up to --max-passes (64) passes, min passes 4 and
 16 x 16 tiles by default, with the --sampling of the frames: prints the rounds and tile-passes of a run against
 T * max_passes, its time (a second run, end to end on the host) against uniform progressive passes (render_device +
@@ -98,6 +102,7 @@ ap.add_argument("--gloss", action="append", default=[])
 ap.add_argument("--occlusion", action="append", default=[])
 ap.add_argument("--occlusion-samples", type=int, default=0)
 ap.add_argument("--shadow-filter", action="append", default=[])
+ap.add_argument("--media", action="append", default=[])
 ap.add_argument("--torus", action="store_true")
 ap.add_argument("--meshuv", action="store_true")
 ap.add_argument("--mesh-as-planar", action="store_true")
@@ -163,6 +168,22 @@ def shadow_filter_table(hs):
         m, v = f.split("=")
         filters["rgb"][int(m)] = [float(x) for x in v.split(",")]
     return filters
+
+
+def media_table(hs):
+    """the scene file's media with the --media entries over them; None: no table (--media off, or nothing to set)"""
+    if "off" in args.media or not (args.media or hs.media() is not None):
+        return None
+    import numpy as np
+    media = hs.media() or {"absorption": np.zeros((hs.desc.n_materials, 3)), "fog_density": 0.0, "fog_color": [0.0, 0.0, 0.0]}
+    for f in args.media:
+        m, v = f.split("=")
+        v = [float(x) for x in v.split(",")]
+        if m == "fog":
+            media["fog_density"], media["fog_color"] = v[0], v[1:]
+        else:
+            media["absorption"][int(m)] = v
+    return media
 
 
 def light_table(hs, how):
@@ -367,6 +388,9 @@ for name, w, h, depth in cases:
         filters = shadow_filter_table(hs)
         if filters is not None:
             gpu.set_shadow_filters(filters)
+        media = media_table(hs)
+        if media is not None:
+            gpu.set_media(media)
         for i in range(args.settle):
             gpu.render_device(cam, canvas.data_ptr(), depth, None, stream.cuda_stream)
         torch.cuda.synchronize()
@@ -391,7 +415,7 @@ for name, w, h, depth in cases:
     if delta is not None: line += f" maxdelta {delta:.2e}"
     if args.lights or args.spot or "spot_kernels=1" in args.option:
         line += f" shadow_traced {st['shadow_traced']} ns/shadow-ray {min(ts) * 1e6 / max(1, st['shadow_traced']):.3f}"
-    if args.sampling or args.option or args.passes >= 0 or args.motion or args.spot or args.bump or args.torus or args.meshuv or args.gloss or args.occlusion or args.shadow_filter:
+    if args.sampling or args.option or args.passes >= 0 or args.motion or args.spot or args.bump or args.torus or args.meshuv or args.gloss or args.occlusion or args.shadow_filter or args.media:
         line += f" primary {st['primary']} ns/primary-ray {min(ts) * 1e6 / max(1, st['primary']):.3f}"
     if acc:
         ms, copy_ms, nbytes = min(a[0] for a in acc), min(a[1] for a in acc), acc[0][2]
@@ -406,6 +430,7 @@ for name, w, h, depth in cases:
         if gloss_table(hs) is not None: gpu.set_gloss(gloss_table(hs))
         if occlusion_table(hs) is not None: gpu.set_occlusion(occlusion_table(hs))
         if shadow_filter_table(hs) is not None: gpu.set_shadow_filters(shadow_filter_table(hs))
+        if media_table(hs) is not None: gpu.set_media(media_table(hs))
         prog = rtc.Progressive(gpu, cam, depth)
         noise = {}
         for i in range(1, 65):
