@@ -161,6 +161,9 @@ __device__ __forceinline__ bool rtc_in_bounds(uint32_t kind, bool ok) {
 #ifndef RTC_SPECULAR_SKIP
 #define RTC_SPECULAR_SKIP 1          // the simple kernels skip the specular power of a point light in a wave none of whose lanes' materials has a specular term (render_body, kSpecularSkip)
 #endif
+#ifndef RTC_ROOTS32
+#define RTC_ROOTS32 1                // rtc_render_kernel_simple3_b, whose worlds have at most RTC_LDS3_ROOTS roots: its closest-hit and shadow traces run one block of the root loop with a 32-bit survivor mask, phase 1's bits shifted in as they are formed (trace(), MAX_ROOTS; render_body, ROOTS)
+#endif
 #ifndef RTC_CONTAINERS_SOLIDS
 #define RTC_CONTAINERS_SOLIDS 1      // simple worlds: the containers pass drops a solid whose bound lies behind the origin and a plane whose entry cannot be negative (trace(), kSolids)
 #endif
@@ -1487,6 +1490,61 @@ __device__ __forceinline__ uint32_t roots_kept_box4(const char* __restrict__ pai
   return kept;
 }
 
+// (RTC_ROOTS32) The same test for RECORDS x 2 roots whose survivor bits are SHIFTED INTO `m` from below, the last root
+// first: the caller walks the table from its top record down, so after the walk root r's bit stands at bit r of the one
+// 32-bit word.  A root is the same compare as above - `!(max(tn, t_lo) > min(tf, t_hi))`, a NaN keeps - and one add with
+// carry, m + m + kept (v_addc_co_u32 with the compare's lane mask as its carry-in): two vector instructions where the
+// form above has a compare, a select and an OR per root and the caller a 64-bit shift per step.  The adds are written
+// as instructions because the compiler has no other way to them: from `m + m + kept` in the source it makes a select, a
+// shift and an OR (twelve instructions per four roots).  The compares stay the compiler's (__builtin_amdgcn_fcmpf), which
+// schedules them among the min / max.  (worlds without groups only: no `line_only`)
+template <class V, int RECORDS>
+__device__ __forceinline__ uint32_t roots_shifted_in_box(uint32_t m, const char* __restrict__ ax, const char* __restrict__ ay,
+                                                         const char* __restrict__ az, const RayB& rb) {
+  constexpr uint32_t NEXT = sizeof(RootBoxPair);
+  static_assert(RECORDS == 1 || RECORDS == 2, "the half step and the step of four roots");
+  Float2 nx[RECORDS], fx[RECORDS], ny[RECORDS], fy[RECORDS], nz[RECORDS], fz[RECORDS];
+  unsigned long long kept[2 * RECORDS];  // per root: the wave's lanes that keep it
+#pragma unroll
+  for (int r = 0; r < RECORDS; ++r) {  // (all plane pairs fetched before any is used, as in roots_kept_box4)
+    nx[r] = *reinterpret_cast<const Float2*>(ax + r * NEXT);
+    fx[r] = *reinterpret_cast<const Float2*>(ax + r * NEXT + 8);
+    ny[r] = *reinterpret_cast<const Float2*>(ay + r * NEXT);
+    fy[r] = *reinterpret_cast<const Float2*>(ay + r * NEXT + 8);
+    nz[r] = *reinterpret_cast<const Float2*>(az + r * NEXT);
+    fz[r] = *reinterpret_cast<const Float2*>(az + r * NEXT + 8);
+  }
+#pragma unroll
+  for (int r = RECORDS - 1; r >= 0; --r) {
+    const Float2 tnx = __builtin_elementwise_fma(nx[r], Float2(rb.ix), Float2(rb.cnx)), tny = __builtin_elementwise_fma(ny[r], Float2(rb.iy), Float2(rb.cny)),
+                 tnz = __builtin_elementwise_fma(nz[r], Float2(rb.iz), Float2(rb.cnz));
+    const Float2 tfx = __builtin_elementwise_fma(fx[r], Float2(rb.ix), Float2(rb.cfx)), tfy = __builtin_elementwise_fma(fy[r], Float2(rb.iy), Float2(rb.cfy)),
+                 tfz = __builtin_elementwise_fma(fz[r], Float2(rb.iz), Float2(rb.cfz));
+#pragma unroll
+    for (int e = 1; e >= 0; --e) {
+      const float tn = fmaxf(fmaxf(tnx[e], tny[e]), tnz[e]), tf = fminf(fminf(tfx[e], tfy[e]), tfz[e]);
+      kept[2 * r + e] = __builtin_amdgcn_fcmpf(fmaxf(tn, rb.t_lo), fminf(tf, rb.t_hi), 13);  // (13: unordered or <=, `!(a > b)`)
+    }
+  }
+  // (s_nop 1: a lane mask written by a vector compare may be read by a vector instruction two wait states later at the
+  // earliest, and the compiler pads nothing inside the string - the last compare may stand right in front of it.  Each
+  // add writes its carry-out to vcc, which nothing reads.)
+  if constexpr (RECORDS == 2) {
+    asm("s_nop 1\n\t"
+        "v_addc_co_u32_e64 %0, vcc, %0, %0, %1\n\t"
+        "v_addc_co_u32_e64 %0, vcc, %0, %0, %2\n\t"
+        "v_addc_co_u32_e64 %0, vcc, %0, %0, %3\n\t"
+        "v_addc_co_u32_e64 %0, vcc, %0, %0, %4"
+        : "+v"(m) : "s"(kept[3]), "s"(kept[2]), "s"(kept[1]), "s"(kept[0]) : "vcc");
+  } else {
+    asm("s_nop 1\n\t"
+        "v_addc_co_u32_e64 %0, vcc, %0, %0, %1\n\t"
+        "v_addc_co_u32_e64 %0, vcc, %0, %0, %2"
+        : "+v"(m) : "s"(kept[1]), "s"(kept[0]) : "vcc");
+  }
+  return m;
+}
+
 // World.intersect's loop over World.objects (world.zig:74), two-phase so that no load depends on a
 // previous one and no lane waits for roots only its neighbours need:
 //   phase 1 streams the FP32 bounds (world boxes or bounding spheres: BOX) of up to 64 roots (wave-uniform addresses) and
@@ -1508,12 +1566,19 @@ __device__ __forceinline__ void motion_root(V&, uint32_t) {}
 
 // MOTION (the motion kernels only; a world with groups, one lane per ray): root r is tested at the lane's shutter time tm
 // with the ray's origin shifted by -tm * D_r (DevMotion); phase 1 reads tables whose bounds already cover the motion.
-template <bool CSG, int WORLD, class V, int TRAV = RTC_LDS_TRAV, bool BOX = true, bool MOTION = false>
+// MAX_ROOTS: how many roots the kernel's world can have.  64: any number, in blocks of 64 (one 64-bit survivor mask per lane
+// and block).  32 (RTC_ROOTS32; a three-wave simple kernel, whose worlds rtc_scene_create holds to RTC_LDS3_ROOTS): one
+// block at base 0 and a 32-bit mask - no block loop, half the mask and bit-scan instructions, and a box form of phase 1
+// that shifts its survivor bits into that one register (roots_shifted_in_box).  Which traces take it: render_body, ROOTS.
+template <bool CSG, int WORLD, class V, int TRAV = RTC_LDS_TRAV, bool BOX = true, bool MOTION = false, int MAX_ROOTS = 64>
 __device__ __forceinline__ void trace(const DevScene& S, const RootRec* __restrict__ recs,
                                       const CullTables& cull, const Ray& ray, V& vis, unsigned& overflow,
                                       uint32_t* lds_stack, const uint32_t member = 0u, const uint32_t stride = 1u,
                                       const double* __restrict__ disp = nullptr, const double tm = 0.0) {
   constexpr bool SIMPLE = WORLD == 2, FLAT = WORLD >= 1;
+  constexpr bool R32 = MAX_ROOTS == 32;
+  static_assert(MAX_ROOTS == 64 || (R32 && SIMPLE && RTC_LDS3_ROOTS == 32), "the 32-root form is the three-wave simple kernels'");
+  using Mask = std::conditional_t<R32, uint32_t, unsigned long long>;  // one survivor bit per root of a block
   static_assert(!MOTION || WORLD == 0, "the motion kernels walk the general world");
   // Phase 1 rejects a root by its world BOX (BOX: every kernel that walks groups, the flat kernels, and the simple kernels
   // of worlds that are mostly cubes) or by its bounding SPHERE (the simple kernels of worlds that are mostly spheres): a
@@ -1542,10 +1607,13 @@ __device__ __forceinline__ void trace(const DevScene& S, const RootRec* __restri
   }();
   // (the table is sorted [spheres][cubes][the rest][planes]: a plane has no bound, phase 1 stops where the planes begin)
   const uint32_t n_bounded = S.n_roots - S.n_root_planes;
-  for (uint32_t base = 0; base < S.n_roots; base += 64u) {
-    const uint32_t n = min(64u, S.n_roots - base);
-    const uint32_t nc = n_bounded > base ? min(n, n_bounded - base) : 0u;  // roots of this block that phase 1 tests
-    unsigned long long mine = 0ull;
+  // (R32: bits [0, x) of a 32-bit mask, x up to 32 - `(1u << 32) - 1u` is not defined, and 32 roots keep bit 31)
+  [[maybe_unused]] const auto below32 = [](uint32_t x) -> uint32_t { return x >= 32u ? ~0u : (1u << x) - 1u; };
+  // (R32: the one block, base 0 - the loop is gone once compiled; its `continue` below is why it is still written as one)
+  for (uint32_t base = 0; base < (R32 ? 1u : S.n_roots); base += 64u) {
+    const uint32_t n = R32 ? S.n_roots : min(64u, S.n_roots - base);
+    const uint32_t nc = R32 ? n_bounded : (n_bounded > base ? min(n, n_bounded - base) : 0u);  // roots of this block that phase 1 tests
+    Mask mine = 0u;
     RTC_PRIO_PHASE(BOX ? RTC_PRIO_CULL : RTC_PRIO_CULL_SPHERES);
     // the tables are padded with entries no ray keeps: the spheres to a multiple of four roots (r2 = -inf), the boxes to eight (lo > hi)
     if (BOX && FLAT && stride == 1u) {
@@ -1570,25 +1638,46 @@ __device__ __forceinline__ void trace(const DevScene& S, const RootRec* __restri
 #else
         constexpr bool reads_ok = true;
 #endif
-#pragma unroll 1
-        for (uint32_t first = 0; reads_ok && first < whole; first += 4u) {
-          const uint32_t k = roots_kept_box4<V, !FLAT>(block, ax, ay, az, rf);
-          mine |= static_cast<unsigned long long>(k) << first;
-          block += 2u * sizeof(RootBoxPair);
-          ax += 2u * sizeof(RootBoxPair);
-          ay += 2u * sizeof(RootBoxPair);
-          az += 2u * sizeof(RootBoxPair);
-        }
+        if constexpr (R32) {
+          // The same records from the TOP down - the half step's one first, then the steps of four -, every root's bit
+          // shifted into `mine` as it is formed: when the walk arrives at record 0, root r's bit stands at bit r (at most
+          // 32 shifts: the table is padded to eight roots, and there are at most 32).  The three addresses carry the
+          // table's base from before the loop and a step moves each by one add.
+          const uint32_t steps = (whole + 3u) >> 2;  // steps of four roots
+          ax += steps * (2u * static_cast<uint32_t>(sizeof(RootBoxPair)));
+          ay += steps * (2u * static_cast<uint32_t>(sizeof(RootBoxPair)));
+          az += steps * (2u * static_cast<uint32_t>(sizeof(RootBoxPair)));
 #if RTC_CULL_HALF_STEP
-        if (reads_ok && whole < nc) mine |= static_cast<unsigned long long>(roots_kept_box<V, !FLAT>(block, ax, ay, az, rf)) << whole;
+          if (reads_ok && whole < nc) mine = roots_shifted_in_box<V, 1>(mine, ax, ay, az, rf);
 #endif
+#pragma unroll 1
+          for (uint32_t step = steps; reads_ok && step != 0u; --step) {
+            ax -= 2u * sizeof(RootBoxPair);
+            ay -= 2u * sizeof(RootBoxPair);
+            az -= 2u * sizeof(RootBoxPair);
+            mine = roots_shifted_in_box<V, 2>(mine, ax, ay, az, rf);
+          }
+        } else {
+#pragma unroll 1
+          for (uint32_t first = 0; reads_ok && first < whole; first += 4u) {
+            const uint32_t k = roots_kept_box4<V, !FLAT>(block, ax, ay, az, rf);
+            mine |= static_cast<unsigned long long>(k) << first;
+            block += 2u * sizeof(RootBoxPair);
+            ax += 2u * sizeof(RootBoxPair);
+            ay += 2u * sizeof(RootBoxPair);
+            az += 2u * sizeof(RootBoxPair);
+          }
+#if RTC_CULL_HALF_STEP
+          if (reads_ok && whole < nc) mine |= static_cast<unsigned long long>(roots_kept_box<V, !FLAT>(block, ax, ay, az, rf)) << whole;
+#endif
+        }
       }
     } else {
       for (uint32_t i = 4u * member; i < nc; i += 4u * stride) {
 #ifdef RTC_PROFILE
         if (!RTC_IN_BOUNDS(RTC_OOB_ROOTS, ((base + i) >> 1) + ((BOX && !(i + 2u < nc)) ? 1u : 2u) <= RTC_AVAIL(BOX ? 2 : 1))) continue;
 #endif
-        unsigned long long k;
+        Mask k;
         if constexpr (BOX) {
           const char* const p0 = reinterpret_cast<const char*>(cull.box + ((base + i) >> 1));
           const char* const p1 = p0 + sizeof(RootBoxPair);
@@ -1602,13 +1691,19 @@ __device__ __forceinline__ void trace(const DevScene& S, const RootRec* __restri
         mine |= k << i;
       }
     }
-    if (nc < 64u) mine &= (1ull << nc) - 1ull;  // (the padding is never kept; a NaN ray must not reach past the table either)
+    if constexpr (R32) {
+      mine &= below32(nc);
+    } else {
+      if (nc < 64u) mine &= (1ull << nc) - 1ull;  // (the padding is never kept; a NaN ray must not reach past the table either)
+    }
     if (nc < n) {  // the block's planes: kept as they are (what the bound of a plane, none, always said)
-      unsigned long long planes = (n < 64u ? (1ull << n) - 1ull : ~0ull) & ~((1ull << nc) - 1ull);
+      Mask planes;
+      if constexpr (R32) planes = below32(n) & ~below32(nc);  // (bits [nc, n), n up to 32)
+      else planes = (n < 64u ? (1ull << n) - 1ull : ~0ull) & ~((1ull << nc) - 1ull);
       if (stride != 1u) {  // (a cooperative trace: root r is lane ((r / 4) % stride)'s, as in the loop above)
-        unsigned long long own = 0xFull << (4u * member);
+        Mask own = Mask{0xFu} << (4u * member);
         if (stride == 4u) own |= own << 16;
-        own |= own << 32;
+        if constexpr (!R32) own |= own << 32;
         planes &= own;
       }
       mine |= planes;
@@ -1619,11 +1714,15 @@ __device__ __forceinline__ void trace(const DevScene& S, const RootRec* __restri
     // the cube code in almost every step (some lane holds one of each); kind by kind it runs each test's code only as
     // often as the lane with the most survivors of that kind needs it, and the compiler drops what a kind does not use
     // (a plane needs one row of the inverse).  Visiting order is free: the reductions do not depend on it.
-    auto range = [&](uint32_t lo, uint32_t hi) -> unsigned long long {  // bits of roots [lo, hi) that fall into this block
-      const uint32_t a = max(lo, base) - base, b = min(max(hi, base), base + 64u) - base;
-      const unsigned long long below_b = b >= 64u ? ~0ull : (1ull << b) - 1ull;
-      const unsigned long long below_a = a >= 64u ? ~0ull : (1ull << a) - 1ull;
-      return below_b & ~below_a;
+    auto range = [&](uint32_t lo, uint32_t hi) -> Mask {  // bits of roots [lo, hi) that fall into this block
+      if constexpr (R32) {
+        return below32(hi) & ~below32(lo);
+      } else {
+        const uint32_t a = max(lo, base) - base, b = min(max(hi, base), base + 64u) - base;
+        const unsigned long long below_b = b >= 64u ? ~0ull : (1ull << b) - 1ull;
+        const unsigned long long below_a = a >= 64u ? ~0ull : (1ull << a) - 1ull;
+        return below_b & ~below_a;
+      }
     };
 #if defined(RTC_PROFILE) && !defined(RTC_PROFILE_LITE)
     uint32_t cube_tests = 0u, cube_neg = 0u, cube_pred = 0u;  // this lane's exact cube tests of the block; those with tmax < 0; those cube_entirely_behind names
@@ -1688,10 +1787,10 @@ __device__ __forceinline__ void trace(const DevScene& S, const RootRec* __restri
         leaf_entries<SIMPLE>(KIND, cy, nullptr, lr, [&](double t, double u, double v) { vis.entry(leaf, shadow, material, t, u, v); });
       }
     };
-    auto leaves_of_kind = [&](auto kind_tag, unsigned long long m) {
-      while (m != 0ull && !vis.done()) {
-        const uint32_t bit = static_cast<uint32_t>(__builtin_ctzll(m));
-        m &= m - 1ull;
+    auto leaves_of_kind = [&](auto kind_tag, Mask m) {
+      while (m != 0u && !vis.done()) {
+        const uint32_t bit = static_cast<uint32_t>(R32 ? __builtin_ctz(static_cast<uint32_t>(m)) : __builtin_ctzll(m));
+        m &= m - Mask{1u};
         if constexpr (V::kBehindOnly) RTC_AUX_ADD(4, 1);  // (diagnostic builds: wave steps of the containers pass's exact tests)
         leaf_of_kind(kind_tag, base + bit);
       }
@@ -2978,6 +3077,13 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
   // (specular_skip: the point-light branch of the five simple kernels; every other kernel keeps its instructions.  What was
   // counted and measured: profiles/specular_skip/)
   constexpr bool kSpecularSkip = SIMPLE && RTC_SPECULAR_SKIP;
+  // (roots32: a three-wave simple kernel's world has at most RTC_LDS3_ROOTS = 32 roots, rtc_scene_create's simple3_ok: the
+  // closest-hit and shadow traces of rtc_render_kernel_simple3_b run one block of the root loop with a 32-bit survivor
+  // mask.  Not its containers pass - a ninth of cover's traces; with it the hit point went to scratch memory for the whole
+  // shading block, 512 -> 679 MB written per cover frame, and two thirds of the gain with it - and not the kernel that culls
+  // by spheres: fresnel + 2.8 %, reflection_and_refraction + 2.1 % with the 32-bit mask alone (six more spilled VGPRs).
+  // Every other kernel keeps its instructions.  profiles/roots32/)
+  constexpr int ROOTS = (SIMPLE && WAVES == 3 && BOX && RTC_ROOTS32) ? 32 : 64;
   constexpr int LDS_LEVELS = (FLAT || !LDS) ? 2 : 1;  // (what fits beside the tables at WAVES work-groups per CU)
   __shared__ Quad2 lds_pend[4][LDS_LEVELS][4][64];
   // The colour a lane has accumulated for its pixel: touched once per iteration and when the pixel is finished, live
@@ -3551,7 +3657,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
     RTC_COUNT(0);
     {
       RTC_HIST_BEGIN();
-      trace<CSG, WORLD, HitVisitor, TRAV, BOX, MOTION>(S, recs, cull, ray, hv, it_overflow, trav_stack, member, stride, mo.disp, tm);
+      trace<CSG, WORLD, HitVisitor, TRAV, BOX, MOTION, ROOTS>(S, recs, cull, ray, hv, it_overflow, trav_stack, member, stride, mo.disp, tm);
       RTC_HIST_END(0);
     }
     RTC_STAMP(2);
@@ -3648,7 +3754,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
       RTC_AUX_ADD(7, 1);  // (diagnostic builds: the passes of the wave, counted by its first active lane - RTC_COUNT's are lane 0's)
       {
         RTC_HIST_BEGIN();
-        trace<CSG, WORLD, BehindVisitor, TRAV, BOX, MOTION>(S, recs, cull, ray, bv, it_overflow, trav_stack, member, stride, mo.disp, tm);
+        trace<CSG, WORLD, BehindVisitor, TRAV, BOX, MOTION, 64>(S, recs, cull, ray, bv, it_overflow, trav_stack, member, stride, mo.disp, tm);
         RTC_HIST_END(2);
       }
         RTC_STAMP(6);
@@ -3856,7 +3962,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
           ShadowVisitor sv;
           sv.distance = occl_radius;
           Ray sray{ovx, ovy, ovz, od.x, od.y, od.z};
-          trace<CSG, WORLD, ShadowVisitor, TRAV, BOX, MOTION>(S, recs, cull, sray, sv, it_overflow, trav_stack, member, stride, mo.disp, tm);
+          trace<CSG, WORLD, ShadowVisitor, TRAV, BOX, MOTION, ROOTS>(S, recs, cull, sray, sv, it_overflow, trav_stack, member, stride, mo.disp, tm);
           clear += sv.shadowed ? 0u : 1u;
         }
         if (clear != occl.samples) occl_ka = occl_ka * (static_cast<double>(clear) / static_cast<double>(occl.samples));
@@ -4014,7 +4120,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
                   sv.distance = distance;
                   RTC_LIGHT_VISITOR_SET(sv);
                   Ray sray{ovx, ovy, ovz, lvx, lvy, lvz};
-                  trace<CSG, WORLD, RTC_LIGHT_VISITOR, TRAV, BOX, MOTION>(S, recs, cull, sray, sv, it_overflow, trav_stack, member, stride, mo.disp, tm);
+                  trace<CSG, WORLD, RTC_LIGHT_VISITOR, TRAV, BOX, MOTION, ROOTS>(S, recs, cull, sray, sv, it_overflow, trav_stack, member, stride, mo.disp, tm);
                   RTC_LIT_ADD(sv);
                 }
               const double samples = static_cast<double>(n_samples);
@@ -4068,7 +4174,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
           RTC_COUNT(2);
           {
             RTC_HIST_BEGIN();
-            trace<CSG, WORLD, RTC_LIGHT_VISITOR, TRAV, BOX, MOTION>(S, recs, cull, sray, sv, it_overflow, trav_stack, s_member, s_stride, mo.disp, tm);
+            trace<CSG, WORLD, RTC_LIGHT_VISITOR, TRAV, BOX, MOTION, ROOTS>(S, recs, cull, sray, sv, it_overflow, trav_stack, s_member, s_stride, mo.disp, tm);
             RTC_HIST_END(1);
           }
                 RTC_STAMP(4);
