@@ -729,6 +729,60 @@ typedef struct rtc_media {
  */
 int rtc_scene_set_media(rtc_scene *scene, const rtc_media *media);
 
+/* ---- the environment: a sky behind the world and suns that light it ---- */
+/*
+ * The sky.  Applied to every ray of the colorAt tree whose closest-hit trace finds nothing, after the media step above - W,
+ * the ray's weight per channel, is already multiplied by the miss transmittance -, in place of the reference's black
+ * (world.zig:119).  (dx, dy, dz) is the ray's direction, c runs over r, g, b:
+ *   len = sqrt((dx*dx + dy*dy) + dz*dz)            (RTC_ENV_SPHERE)
+ *   len = max(|dx|, max(|dy|, |dz|))               (RTC_ENV_CUBE: where the direction meets the unit cube)
+ *   p   = (dx / len, dy / len, dz / len)
+ *   E.c = pattern == RTC_ENV_NO_PATTERN ? rgb.c : pattern_at(pattern, p).c * rgb.c
+ *   acc.c = acc.c + W.c * E.c
+ * pattern_at is the evaluation a material's pattern gets (Pattern.patternAt): p is taken as an object-space point and the
+ * pattern's own inverse transform is applied to it, so a pattern transform turns the sky.  Every pattern kind is a sky.  A
+ * spherical texture map does not depend on len; a cubic one wants RTC_ENV_CUBE.  A texture map of mapping RTC_TEX_MESH is
+ * evaluated with no hit triangle (tri == RTC_NO_LEAF): the row of zeros.  A sky of colour zero without a pattern adds
+ * nothing and the step is not run.  A miss stays a miss: primary and secondary are those of the handle without an
+ * environment.  A miss in fog or inside an absorbing material has W == 0 and adds +0: a sky is not seen through an infinite
+ * fog.  Occlusion rays and shadow rays do not see the sky.
+ *
+ * The suns.  sun_direction is the way the light TRAVELS, any length > 0; the host normalises once,
+ *   a = direction / sqrt((x*x + y*y) + z*z),   lv = (-a.x, -a.y, -a.z),
+ * and a row keeps lv and sun_rgb.  At every hit, after the loop over World.lights (world.zig:89-96) and in table order, a
+ * sun is a point light in everything but its geometry: point_to_light = lv, distance = +infinity.  shadow_calls grows by
+ * one per sun and hit.  With shadow_matters (the material's diffuse or specular is not zero) and light_dot_normal >= 0 the
+ * shadow ray is traced from over_point along lv and counted in shadow_traced: every entry with et >= 0 on a casts_shadow
+ * leaf counts, however far away, and the rows of rtc_scene_set_shadow_filters multiply as they do for any light.
+ * Material.lighting adds ambient + diffuse + specular with sun_rgb as the intensity - the ambient term with the occlusion
+ * step's ka, the normal the bumped shading normal.  Spot cones do not apply.  The fog does not dim a sun's shadow ray.
+ * Suns do not count towards the light limit of the kernels that keep their tables in LDS.
+ */
+#define RTC_ENV_NO_PATTERN 0xFFFFFFFFu
+#define RTC_ENV_SPHERE 0u
+#define RTC_ENV_CUBE 1u
+#define RTC_ENV_MAX_SUNS 16u
+typedef struct rtc_environment {
+  double rgb[3];               /* the sky's colour; with a pattern, the factor on the pattern's colour */
+  uint32_t pattern;            /* a row of the handle's pat_* tables, or RTC_ENV_NO_PATTERN */
+  uint32_t projection;         /* RTC_ENV_SPHERE / RTC_ENV_CUBE */
+  uint32_t n_suns;             /* <= RTC_ENV_MAX_SUNS */
+  const double *sun_direction; /* [n_suns][3] the way the light TRAVELS, any length > 0 */
+  const double *sun_rgb;       /* [n_suns][3] intensity */
+} rtc_environment;
+
+/*
+ * This handle's environment for every render entry point.  Validated on the host before any HIP call and before anything
+ * changes: RTC_ERR_INVALID_ARGUMENT for a value that is not finite, a negative rgb or sun_rgb, a pattern that is
+ * >= n_patterns and not RTC_ENV_NO_PATTERN, a projection other than 0 or 1, n_suns > RTC_ENV_MAX_SUNS, n_suns > 0 with a
+ * NULL table, a direction of zero or non-finite magnitude; the previous table stays in force.  NULL, or rgb all zero with no
+ * pattern and no suns, is no environment and gives the handle its previous kernels back.  A clone starts with its source's
+ * environment; rtc_render's band clones follow.  A handle with an environment renders with the environment kernels
+ * (rtc_render_kernel_env, _env_bigworld).  librtc_multi renders without it.  rtc_scene_desc, rtc_camera, rtc_stats and
+ * RTC_ABI_VERSION are as they were.
+ */
+int rtc_scene_set_environment(rtc_scene *scene, const rtc_environment *environment);
+
 /* ---- adaptive sampling: progressive passes only for tiles still noisy ---- */
 #define RTC_ADAPTIVE_MAX_TILE 1024u
 

@@ -43,7 +43,8 @@ extern "C" {
  * kernels'), "shadow_filter_kernels" (!= 0: the shadow-filter kernels even on a handle without a filter, every filter row
  * zero, so that their images can be held to the handle's ordinary kernels'), "media_kernels" (!= 0: the media kernels even
  * on a handle without media, every absorption row and the fog density zero, so that their images can be held to the
- * handle's ordinary kernels').
+ * handle's ordinary kernels'), "environment_kernels" (!= 0: the environment kernels even on a handle without an environment,
+ * no sky and no sun, so that their images can be held to the handle's ordinary kernels').
  * RTC_ERR_INVALID_ARGUMENT for a name the library does not know.
  * (The library reads no environment variables.)
  */

@@ -25,7 +25,8 @@
  *                        rtch_scene_gloss, through rtc_scene_set_gloss; its materials' occlusion radii,
  *                        rtch_scene_occlusion, through rtc_scene_set_occlusion; its materials' shadow filters,
  *                        rtch_scene_shadow_filters, through rtc_scene_set_shadow_filters; its materials' absorption
- *                        and its atmosphere, rtch_scene_media, through rtc_scene_set_media)
+ *                        and its atmosphere, rtch_scene_media, through rtc_scene_set_media; its environment,
+ *                        rtch_scene_environment, through rtc_scene_set_environment)
  *
  * Every function that returns int returns 0 on success; otherwise rtch_last_error()
  * holds "<ZigStyleErrorName>: detail" (thread-local).
@@ -113,6 +114,13 @@ int rtch_scene_shadow_filters(void *handle, double *rgb, int *present, uint32_t 
  * a material of the file has the key or the file has an atmosphere.  Pass them to rtc_scene_set_media.  rtch_scene_render
  * applies them. */
 int rtch_scene_media(void *handle, double *absorption, double *fog, int *present, uint32_t n);
+/* The scene's "environment" (DESIGN.md section 24): {"color": [r, g, b], "pattern": {...}, "projection": "sphere" | "cube",
+ * "suns": [{"direction": [x, y, z], "intensity": [r, g, b]}, ...]}, every key optional - color defaults to (1, 1, 1) with a
+ * pattern and (0, 0, 0) without, projection to "sphere" -, as rtc_scene_set_environment takes it: *out's rgb, pattern (a row
+ * of the description's pat_* tables - the environment's rows follow every material's -, or RTC_ENV_NO_PATTERN), projection
+ * and n_suns; the suns' rows, as the file has them, go to sun_direction and sun_rgb (room for 3 * RTC_ENV_MAX_SUNS doubles
+ * each), which *out then points to.  *present: 1 when the file has the key.  rtch_scene_render applies it. */
+int rtch_scene_environment(void *handle, rtc_environment *out, double *sun_direction, double *sun_rgb, int *present);
 int rtch_scene_camera(void *handle, uint32_t width, uint32_t height, rtc_camera *out);
 int rtch_camera_rotate(void *handle, double angle);
 int rtch_camera_move(void *handle, double distance);

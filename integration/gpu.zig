@@ -89,6 +89,18 @@ pub extern fn rtc_canvas_unregister(canvas: *anyopaque) c_int; // ... and drop t
 pub extern fn rtc_rgba8_device(d_canvas: [*]const f64, n_pixels: usize, d_rgba: [*]u32, hip_stream: ?*anyopaque) c_int;
 pub extern fn rtc_scene_synchronize(scene: *RtcScene) c_int;
 pub extern fn rtc_get_stats(scene: *RtcScene, out: *RtcStats) c_int;
+// The environment (rtc.h, rtc_scene_set_environment): a sky behind the world - a colour, with `pattern` a row of the pat_*
+// tables the factor on that pattern's colour at a missed ray's direction - and suns, directional lights.
+pub const RTC_ENV_NO_PATTERN: u32 = 0xFFFFFFFF;
+pub const RtcEnvironment = extern struct {
+    rgb: [3]f64,
+    pattern: u32,
+    projection: u32, // 0: the unit sphere, 1: the unit cube
+    n_suns: u32,
+    sun_direction: ?[*]const f64, // [n_suns][3] the way the light travels
+    sun_rgb: ?[*]const f64, // [n_suns][3]
+};
+pub extern fn rtc_scene_set_environment(scene: *RtcScene, environment: ?*const RtcEnvironment) c_int; // null: no environment
 pub extern fn rtc_grow_csg_lists(scene: *RtcScene) c_int; // after an asynchronous frame whose stats.overflow != 0 on a csg scene: longer lists, render again
 pub extern fn rtc_scatter_tile_list_device(d_tiles: [*]const f64, d_tile_list: [*]const u32, n_tiles: u32, tile_w: u32, tile_h: u32,
                                            hsize: u32, vsize: u32, canvas: [*]f64, hip_stream: ?*anyopaque) c_int; // a rank's tiles straight into a (registered host) canvas

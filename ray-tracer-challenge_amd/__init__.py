@@ -221,7 +221,8 @@ BUMP_NONE, BUMP_NOISE, BUMP_RIPPLES = 0, 1, 2  # RTC_BUMP_*
 RTC_SPHERE, RTC_PLANE, RTC_CUBE, RTC_CYLINDER, RTC_TRIANGLE, RTC_SMOOTH_TRIANGLE, RTC_CONE, RTC_TORUS = range(8)
 # the options that select a kernel family on a handle that does not need it (set_option; tests and tools/time_scenes.py)
 KERNEL_OPTIONS = ("sampling_kernels", "motion_kernels", "spot_kernels", "bump_kernels", "torus_kernels", "meshuv_kernels", "gloss_kernels",
-                  "occlusion_kernels", "shadow_filter_kernels", "media_kernels")
+                  "occlusion_kernels", "shadow_filter_kernels", "media_kernels", "environment_kernels")
+ENV_NO_PATTERN, ENV_SPHERE, ENV_CUBE, ENV_MAX_SUNS = 0xFFFFFFFF, 0, 1, 16  # RTC_ENV_*
 NO_MEDIUM = 0xFFFFFFFF  # RTC_NO_MEDIUM: a ray in the atmosphere
 # texture mappings (rtc.h); RTC_TEX_MESH: (u, v) from the hit triangle's texture row
 RTC_TEX_SPHERICAL, RTC_TEX_PLANAR, RTC_TEX_CYLINDRICAL, RTC_TEX_CUBIC, RTC_TEX_MESH = range(5)
@@ -331,6 +332,31 @@ def media_struct(media):
     return m, a
 
 
+class Environment(C.Structure):
+    """struct rtc_environment (include/rtc.h): the sky - a colour, with a pattern row the factor on that pattern's colour at a
+    missed ray's direction - and the suns, directional lights: the way each one's light travels and its intensity."""
+
+    _fields_ = [("rgb", C.c_double * 3), ("pattern", C.c_uint32), ("projection", C.c_uint32), ("n_suns", C.c_uint32),
+                ("sun_direction", C.POINTER(C.c_double)), ("sun_rgb", C.POINTER(C.c_double))]
+
+
+def environment_struct(env):
+    """(Environment, the arrays it points into) of a dict of "rgb" ((0, 0, 0)), "pattern" (ENV_NO_PATTERN), "projection"
+    (ENV_SPHERE), "sun_direction" and "sun_rgb" ((n, 3) each; none: no suns) (GpuScene.set_environment); the arrays must
+    outlive the struct's use."""
+    rgb = [float(x) for x in env.get("rgb", (0.0, 0.0, 0.0))]
+    if len(rgb) != 3:
+        raise ValueError(f"environment: a colour of {len(rgb)} values, 3 expected")
+    d = np.ascontiguousarray(env.get("sun_direction", np.zeros((0, 3))), dtype=np.float64).reshape(-1, 3)
+    c = np.ascontiguousarray(env.get("sun_rgb", np.zeros((0, 3))), dtype=np.float64).reshape(-1, 3)
+    if d.shape != c.shape:
+        raise ValueError(f"environment: {d.shape[0]} sun directions and {c.shape[0]} intensities")
+    n = d.shape[0]
+    e = Environment((C.c_double * 3)(*rgb), int(env.get("pattern", ENV_NO_PATTERN)), int(env.get("projection", ENV_SPHERE)), n,
+                    d.ctypes.data_as(C.POINTER(C.c_double)) if n else None, c.ctypes.data_as(C.POINTER(C.c_double)) if n else None)
+    return e, (d, c)
+
+
 class Bump(C.Structure):
     """struct rtc_bump (include/rtc.h): a bump per material row (kind BUMP_NONE: the material as it is)."""
 
@@ -372,14 +398,14 @@ RTC_SYMBOLS = ["rtc_scene_create", "rtc_scene_clone", "rtc_scene_destroy", "rtc_
                "rtc_scene_set_sample_pass", "rtc_scene_accumulate_device", "rtc_scene_set_motion",
                "rtc_scene_adaptive_begin_device", "rtc_scene_adaptive_accumulate_device", "rtc_scene_adaptive_step", "rtc_render_adaptive",
                "rtc_scene_set_spots", "rtc_scene_set_bumps", "rtc_scene_set_mesh_uvs", "rtc_scene_set_gloss",
-               "rtc_scene_set_occlusion", "rtc_scene_set_shadow_filters", "rtc_scene_set_media"]
+               "rtc_scene_set_occlusion", "rtc_scene_set_shadow_filters", "rtc_scene_set_media", "rtc_scene_set_environment"]
 # (... and include/rtc_diag.h: diagnostics and tuning, for the tests, bench.py and tools/)
 RTC_DIAG_SYMBOLS = ["rtc_set_option", "rtc_last_kernel_name", "rtc_get_schedule", "rtc_get_chunk_times", "rtc_diag_build_tables", "rtc_diag_root_boxes", "rtc_diag_root_spheres"]
 HOST_SYMBOLS = ["rtch_last_error", "rtch_scene_load", "rtch_scene_free", "rtch_scene_desc", "rtch_scene_camera",
                 "rtch_camera_rotate", "rtch_camera_move", "rtch_camera_make", "rtch_canvas_ppm", "rtch_canvas_rgba8", "rtch_scene_render", "rtch_set_loader_threads",
                 "rtch_scene_lights", "rtch_scene_sampling", "rtch_scene_passes", "rtch_scene_motion", "rtch_scene_adaptive",
                 "rtch_scene_spots", "rtch_scene_bumps", "rtch_scene_mesh_uvs", "rtch_scene_gloss", "rtch_scene_occlusion",
-                "rtch_scene_shadow_filters", "rtch_scene_media"]
+                "rtch_scene_shadow_filters", "rtch_scene_media", "rtch_scene_environment"]
 
 MULTI_SYMBOLS = ["rtc_multi_create", "rtc_multi_destroy", "rtc_multi_render", "rtc_multi_render_rgba8", "rtc_multi_render_device", "rtc_multi_render_rgba8_device",
                  "rtc_multi_synchronize", "rtc_multi_stream", "rtc_multi_get_stats", "rtc_multi_balance", "rtc_multi_last_error"]
@@ -446,6 +472,7 @@ def hip_lib():
         lib.rtc_scene_set_occlusion.argtypes = [C.c_void_p, C.POINTER(Occlusion)]
         lib.rtc_scene_set_shadow_filters.argtypes = [C.c_void_p, C.POINTER(ShadowFilters)]
         lib.rtc_scene_set_media.argtypes = [C.c_void_p, C.POINTER(Media)]
+        lib.rtc_scene_set_environment.argtypes = [C.c_void_p, C.POINTER(Environment)]
         lib.rtc_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.POINTER(Adaptive), C.c_void_p, C.c_void_p]
         lib.rtc_scene_destroy.argtypes = [C.c_void_p]
         lib.rtc_scene_destroy.restype = None
@@ -505,6 +532,7 @@ def host_lib():
         lib.rtch_scene_occlusion.argtypes = [C.c_void_p, _dp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.c_uint32]
         lib.rtch_scene_shadow_filters.argtypes = [C.c_void_p, _dp, C.POINTER(C.c_int), C.c_uint32]
         lib.rtch_scene_media.argtypes = [C.c_void_p, _dp, _dp, C.POINTER(C.c_int), C.c_uint32]
+        lib.rtch_scene_environment.argtypes = [C.c_void_p, C.POINTER(Environment), _dp, _dp, C.POINTER(C.c_int)]
         lib.rtch_scene_adaptive.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(Adaptive)]
         lib.rtch_scene_camera.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Camera)]
         lib.rtch_camera_rotate.argtypes = [C.c_void_p, C.c_double]
@@ -743,6 +771,20 @@ class HostScene:
         out = {"absorption": a, "fog_density": float(fog[0]), "fog_color": [float(x) for x in fog[1:]]}
         return out if present.value else None
 
+    def environment(self):
+        """The scene's "environment" (rtch_scene_environment): a dict of "rgb", "pattern" (a row of the description's pat_*
+        tables, or ENV_NO_PATTERN), "projection", "sun_direction" and "sun_rgb" ((n, 3) each, as the file has them) - what
+        GpuScene.set_environment takes -, or None when the file has no environment."""
+        e = Environment()
+        d, c = np.zeros((ENV_MAX_SUNS, 3)), np.zeros((ENV_MAX_SUNS, 3))
+        present = C.c_int()
+        _check_host(host_lib().rtch_scene_environment(self._h, C.byref(e), d.ctypes.data_as(_dp), c.ctypes.data_as(_dp), C.byref(present)))
+        if not present.value:
+            return None
+        n = int(e.n_suns)
+        return {"rgb": [float(x) for x in e.rgb], "pattern": int(e.pattern), "projection": int(e.projection),
+                "sun_direction": d[:n].copy(), "sun_rgb": c[:n].copy()}
+
     def adaptive(self):
         """The camera's "sampling": {"adaptive": ...} of the scene file (rtch_scene_adaptive): an Adaptive whose max_passes
         is "passes", or None when the file has none."""
@@ -895,6 +937,16 @@ class GpuScene:
             return
         m, _keep = media_struct(media)
         _check_hip(hip_lib().rtc_scene_set_media(self._s, C.byref(m)))
+
+    def set_environment(self, env):
+        """rtc_scene_set_environment: a dict of "rgb", "pattern", "projection", "sun_direction" and "sun_rgb"
+        (HostScene.environment()); None: no environment - as a sky of zero with no pattern and no suns, the handle's previous
+        kernels."""
+        if env is None:
+            _check_hip(hip_lib().rtc_scene_set_environment(self._s, None))
+            return
+        e, _keep = environment_struct(env)
+        _check_hip(hip_lib().rtc_scene_set_environment(self._s, C.byref(e)))
 
     def accumulate_device(self, accum, stream=None):
         """rtc_scene_accumulate_device: an Accum, enqueued on `stream` (None: the handle's own) after this handle's renders."""

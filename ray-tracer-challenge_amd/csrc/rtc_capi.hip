@@ -195,6 +195,20 @@ __global__ void rtc_render_kernel_media_bigworld(const DevScene S, const DevCame
                                                  const DevBumps bumps, const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl,
                                                  const DevShadowFilter sfilt, const DevMedia media);
 }
+// The environment kernels (rtc_scene_set_environment: a sky behind the world and suns that light it): the media kernels'
+// tables and fifth quarter, and the sky and the sun rows (DevEnvironment) as one more argument.
+extern "C" {
+__global__ void rtc_render_kernel_env(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                      double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                      const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                      const DevBumps bumps, const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl,
+                                      const DevShadowFilter sfilt, const DevMedia media, const DevEnvironment env);
+__global__ void rtc_render_kernel_env_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                               double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                               const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                               const DevBumps bumps, const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl,
+                                               const DevShadowFilter sfilt, const DevMedia media, const DevEnvironment env);
+}
 // Progressive rendering's accumulation (rtc_accum.hip): the grid's blocks for n pixels (the noise partials it writes, at
 // most) and the enqueue of its kernels.
 uint32_t rtcAccumBlocks(size_t n_pixels, bool wide);
@@ -412,7 +426,7 @@ bool tablesInLds(const rtc_scene* s) {
 // `spot`; the bump kernels those four and DevBumps: `bump` - the torus kernels take the same arguments and travel in `bump` too;
 // the meshuv kernels those five and DevMeshUvs: `meshuv`; the gloss kernels those six and DevGloss: `gloss`;
 // the occlusion kernels those seven and DevOcclusion: `occl`; the shadow-filter kernels those eight and DevShadowFilter: `sfilt`;
-// the media kernels those nine and DevMedia: `media`)
+// the media kernels those nine and DevMedia: `media`; the environment kernels those ten and DevEnvironment: `env`)
 struct KernelChoice {
   decltype(&rtc_render_kernel) fn;
   const char* name;
@@ -427,6 +441,7 @@ struct KernelChoice {
   decltype(&rtc_render_kernel_occl) occl = nullptr;
   decltype(&rtc_render_kernel_sfilter) sfilt = nullptr;
   decltype(&rtc_render_kernel_media) media = nullptr;
+  decltype(&rtc_render_kernel_env) env = nullptr;
   KernelChoice(decltype(&rtc_render_kernel) f, const char* n) : fn(f), name(n) {}
   KernelChoice(decltype(&rtc_render_kernel_area) a, const char* n) : fn(nullptr), name(n), area(a) {}
   KernelChoice(decltype(&rtc_render_kernel_ms) m, const char* n) : fn(nullptr), name(n), ms(m) {}
@@ -439,11 +454,12 @@ struct KernelChoice {
   KernelChoice(decltype(&rtc_render_kernel_occl) ok, const char* n) : fn(nullptr), name(n), occl(ok) {}
   KernelChoice(decltype(&rtc_render_kernel_sfilter) fk, const char* n) : fn(nullptr), name(n), sfilt(fk) {}
   KernelChoice(decltype(&rtc_render_kernel_media) mk, const char* n) : fn(nullptr), name(n), media(mk) {}
+  KernelChoice(decltype(&rtc_render_kernel_env) ek, const char* n) : fn(nullptr), name(n), env(ek) {}
   void launch(uint32_t blocks, hipStream_t stream, const rtc_scene* s, const DevScene& dev, const DevCamera& cam, const DevPixelMap& map,
               uint32_t max_depth, double* d_out, DevStats* st_now, DevStats* st_next) const {
     DevSampling smp = s->sampling;  // (the pass's area-light offset, P * N * S: N is the camera's whole image)
     smp.pixel_base = static_cast<unsigned long long>(smp.sample_base) * (static_cast<unsigned long long>(cam.hsize) * cam.vsize);
-    if (motion || spot || bump || meshuv || gloss || occl || sfilt || media) {
+    if (motion || spot || bump || meshuv || gloss || occl || sfilt || media || env) {
       // the handle's root tables with the moving roots' bounds (or the scene's, all displacements zero: the option), and
       // the scene's area rows (or zero rows: a point-only table); the spot kernels also the handle's spot rows (or zero
       // rows, every flag 0: the option)
@@ -459,7 +475,7 @@ struct KernelChoice {
         mo.disp = m->disp.p;
       }
       const DevAreaLights area = s->area_kernel ? s->area : DevAreaLights{s->tab->zero_rows.p, s->area.seed};
-      if (media) {  // (the handle's absorption rows and atmosphere, or zero rows and no fog: the option; and the shadow-filter kernels' tables)
+      if (media || env) {  // (the handle's absorption rows and atmosphere, or zero rows and no fog: the option; and the shadow-filter kernels' tables)
         const DevSpots sp{s->spots ? s->spots->row.p : s->tab->zero_rows.p};
         const DevBumps bp{s->bumps ? s->bumps->row.p : s->tab->zero_bump.p};
         const DevMeshUvs uv{s->mesh_uvs ? s->mesh_uvs->row.p : nullptr};
@@ -475,7 +491,22 @@ struct KernelChoice {
           me.fog_density = m->fog_density;
           for (int c = 0; c < 3; ++c) me.fog_color[c] = m->fog_color[c];
         }
-        hipLaunchKernelGGL(media, dim3(blocks), dim3(256), 0, stream, md, cam, map, max_depth, d_out, st_now, st_next, area, smp, mo, sp, bp, uv, gl, oc, sf, me);
+        if (env) {  // (the handle's sky and suns, or no sky and no sun: the option; and the media kernels' tables)
+          DevEnvironment ev{{0.0, 0.0, 0.0}, RTC_ENV_NO_PATTERN, RTC_ENV_SPHERE, 0u, 0u, s->tab->zero_rows.p};
+          if (const EnvironmentTables* e = s->environment.get()) {
+            for (int c = 0; c < 3; ++c) ev.rgb[c] = e->rgb[c];
+            ev.pattern = e->pattern;
+            ev.projection = e->projection;
+            ev.sky = e->sky ? 1u : 0u;
+            if (e->n_suns != 0u) {
+              ev.n_suns = e->n_suns;
+              ev.sun = e->sun.p;
+            }
+          }
+          hipLaunchKernelGGL(env, dim3(blocks), dim3(256), 0, stream, md, cam, map, max_depth, d_out, st_now, st_next, area, smp, mo, sp, bp, uv, gl, oc, sf, me, ev);
+        } else {
+          hipLaunchKernelGGL(media, dim3(blocks), dim3(256), 0, stream, md, cam, map, max_depth, d_out, st_now, st_next, area, smp, mo, sp, bp, uv, gl, oc, sf, me);
+        }
       } else if (sfilt) {  // (the handle's filter rows, or zero rows, every material opaque: the option; and the occlusion kernels' tables)
         const DevSpots sp{s->spots ? s->spots->row.p : s->tab->zero_rows.p};
         const DevBumps bp{s->bumps ? s->bumps->row.p : s->tab->zero_bump.p};
@@ -558,6 +589,9 @@ bool shadowFilterKernels(const rtc_scene* s) { return s->shadow_filters != nullp
 // The media kernels run when the handle has an absorbing row or a fog (rtc_scene_set_media keeps no other table) - whatever
 // else the handle holds: they are the shadow-filter walk - or, for tests, whenever option "media_kernels" is set.
 bool mediaKernels(const rtc_scene* s) { return s->media != nullptr || rtcOptions().media_kernels != 0.0; }
+// The environment kernels run when the handle has a sky or a sun (rtc_scene_set_environment keeps no other table) - whatever
+// else the handle holds: they are the media walk - or, for tests, whenever option "environment_kernels" is set.
+bool environmentKernels(const rtc_scene* s) { return s->environment != nullptr || rtcOptions().environment_kernels != 0.0; }
 #define RTC_KERNEL(k) KernelChoice{k, #k}
 // The general kernel at three waves per SIMD (rtc_render_kernel3): forced by option "waves3", else what the handle's
 // trial measured (KernelTune in launch()).
@@ -584,6 +618,7 @@ KernelChoice ldsKernel(const rtc_scene* s, const DevPixelMap& map) {
   return s->ext_kernel ? RTC_KERNEL(rtc_render_kernel_ext) : RTC_KERNEL(rtc_render_kernel);
 }
 KernelChoice renderKernel(const rtc_scene* s, const DevPixelMap& map) {
+  if (environmentKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_env) : RTC_KERNEL(rtc_render_kernel_env_bigworld);
   if (mediaKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_media) : RTC_KERNEL(rtc_render_kernel_media_bigworld);
   if (shadowFilterKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_sfilter) : RTC_KERNEL(rtc_render_kernel_sfilter_bigworld);
   if (occlusionKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_occl) : RTC_KERNEL(rtc_render_kernel_occl_bigworld);
@@ -605,6 +640,7 @@ KernelChoice renderKernel(const rtc_scene* s, const DevPixelMap& map) {
 
 // Work-groups of the launch's kernel that are resident at once, and the waves in them.
 uint32_t residentBlocksAlone(const rtc_scene* s, const DevPixelMap& map) {
+  if (environmentKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_env_lds : s->blocks_per_cu_env_big);
   if (mediaKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_media_lds : s->blocks_per_cu_media_big);
   if (shadowFilterKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_sfilt_lds : s->blocks_per_cu_sfilt_big);
   if (occlusionKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_occl_lds : s->blocks_per_cu_occl_big);
@@ -891,7 +927,7 @@ int ensureScratch(rtc_scene* s, DevPixelMap& map, uint32_t blocks, uint32_t max_
     HIP_TRY(hipMalloc(&s->d_ray_stack, need));
     s->ray_stack_capacity = need;
   }
-  if (mediaKernels(s)) {
+  if (mediaKernels(s) || environmentKernels(s)) {  // (the environment kernels are the media walk)
     // (the media kernels' fifth quarter of every pending ray, 16 bytes beside the record's 64: a quarter of the ray stack's
     // capacity holds a slot for every slot of it, whatever the launch's depth)
     const size_t need_x = s->ray_stack_capacity / 4u;
@@ -1031,7 +1067,7 @@ int launch(rtc_scene* s, const rtc_camera& cam, const DevPixelMap& map_in, uint3
   int trial_slot = -1;
   {
     rtc_scene::KernelTune& T = s->tune;
-    const bool eligible = !samplingKernels(s) && !motionKernels(s) && !spotKernels(s) && !bumpKernels(s) && !torusKernels(s) && !meshuvKernels(s) && !glossKernels(s) && !occlusionKernels(s) && !shadowFilterKernels(s) && !mediaKernels(s) &&  // (the sampling, motion, spot, bump, torus, meshuv, gloss, occlusion, shadow-filter and media kernels have no three-wave form)
+    const bool eligible = !samplingKernels(s) && !motionKernels(s) && !spotKernels(s) && !bumpKernels(s) && !torusKernels(s) && !meshuvKernels(s) && !glossKernels(s) && !occlusionKernels(s) && !shadowFilterKernels(s) && !mediaKernels(s) && !environmentKernels(s) &&  // (the sampling, motion, spot, bump, torus, meshuv, gloss, occlusion, shadow-filter, media and environment kernels have no three-wave form)
                           ((s->general3_ok && rtcOptions().waves3 < 0.0 && tablesInLds(s) &&
                             !(s->tab && s->tab->handles.load(std::memory_order_relaxed) > 1) &&
                             static_cast<double>(map.n_chunks) >= 4.0 * 4.0 * s->n_cus * s->blocks_per_cu_lds) ||
@@ -2427,6 +2463,10 @@ int uploadTables(const rtc_scene_desc& d, const SceneTraits& traits, const HostT
     s->blocks_per_cu_media_lds = static_cast<uint32_t>(std::max(nb, 1));
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_media_bigworld, 256, 0));
     s->blocks_per_cu_media_big = static_cast<uint32_t>(std::max(nb, 1));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_env, 256, 0));  // (the environment kernels: one pair for every world)
+    s->blocks_per_cu_env_lds = static_cast<uint32_t>(std::max(nb, 1));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_env_bigworld, 256, 0));
+    s->blocks_per_cu_env_big = static_cast<uint32_t>(std::max(nb, 1));
     if (const int v = static_cast<int>(rtcOptions().blocks_per_cu); v >= 1) {  // (tuning option)
       s->blocks_per_cu_lds = std::min<uint32_t>(s->blocks_per_cu_lds, v), s->blocks_per_cu_big = std::min<uint32_t>(s->blocks_per_cu_big, v);
       s->blocks_per_cu_ms_lds = std::min<uint32_t>(s->blocks_per_cu_ms_lds, v), s->blocks_per_cu_ms_big = std::min<uint32_t>(s->blocks_per_cu_ms_big, v);
@@ -2439,6 +2479,7 @@ int uploadTables(const rtc_scene_desc& d, const SceneTraits& traits, const HostT
       s->blocks_per_cu_occl_lds = std::min<uint32_t>(s->blocks_per_cu_occl_lds, v), s->blocks_per_cu_occl_big = std::min<uint32_t>(s->blocks_per_cu_occl_big, v);
       s->blocks_per_cu_sfilt_lds = std::min<uint32_t>(s->blocks_per_cu_sfilt_lds, v), s->blocks_per_cu_sfilt_big = std::min<uint32_t>(s->blocks_per_cu_sfilt_big, v);
       s->blocks_per_cu_media_lds = std::min<uint32_t>(s->blocks_per_cu_media_lds, v), s->blocks_per_cu_media_big = std::min<uint32_t>(s->blocks_per_cu_media_big, v);
+      s->blocks_per_cu_env_lds = std::min<uint32_t>(s->blocks_per_cu_env_lds, v), s->blocks_per_cu_env_big = std::min<uint32_t>(s->blocks_per_cu_env_big, v);
     }
   }
   DevScene& D = s->dev;
@@ -3158,6 +3199,64 @@ int rtc_scene_set_media(rtc_scene* s, const rtc_media* m) {
   return RTC_OK;
 }
 
+// ---- the environment
+// Validated on the host before any HIP call and before anything changes.  The suns' directions are normalised here, once:
+// a row keeps the unit vector towards the sun and the intensity.  NULL, or a sky of zero with no pattern and no suns, is no
+// environment: the handle's previous kernels.
+int rtc_scene_set_environment(rtc_scene* s, const rtc_environment* e) {
+  g_error.clear();
+  if (!s) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
+  bool sky = false;
+  std::vector<double> rows;
+  if (e) {
+    for (uint32_t c = 0; c < 3u; ++c) {
+      if (!std::isfinite(e->rgb[c])) return fail(RTC_ERR_INVALID_ARGUMENT, "environment: a colour that is not finite");
+      if (e->rgb[c] < 0.0) return fail(RTC_ERR_INVALID_ARGUMENT, "environment: colour %g is negative", e->rgb[c]);
+      sky = sky || e->rgb[c] != 0.0;
+    }
+    if (e->pattern != RTC_ENV_NO_PATTERN && e->pattern >= s->dev.n_patterns)
+      return fail(RTC_ERR_INVALID_ARGUMENT, "environment: pattern %u, the scene has %u", e->pattern, s->dev.n_patterns);
+    sky = sky || e->pattern != RTC_ENV_NO_PATTERN;
+    if (e->projection != RTC_ENV_SPHERE && e->projection != RTC_ENV_CUBE)
+      return fail(RTC_ERR_INVALID_ARGUMENT, "environment: projection %u", e->projection);
+    if (e->n_suns > RTC_ENV_MAX_SUNS) return fail(RTC_ERR_INVALID_ARGUMENT, "environment: %u suns, at most %u", e->n_suns, RTC_ENV_MAX_SUNS);
+    if (e->n_suns != 0u && (!e->sun_direction || !e->sun_rgb)) return fail(RTC_ERR_INVALID_ARGUMENT, "environment: suns without a table");
+    for (uint32_t i = 0; i < e->n_suns; ++i) {
+      const double* d = e->sun_direction + 3ull * i;
+      const double* c = e->sun_rgb + 3ull * i;
+      for (uint32_t k = 0; k < 3u; ++k) {
+        if (!std::isfinite(d[k]) || !std::isfinite(c[k])) return fail(RTC_ERR_INVALID_ARGUMENT, "environment: sun %u: a value that is not finite", i);
+        if (c[k] < 0.0) return fail(RTC_ERR_INVALID_ARGUMENT, "environment: sun %u: intensity %g is negative", i, c[k]);
+      }
+      const double len = std::sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+      if (!(std::isfinite(len) && len > 0.0)) return fail(RTC_ERR_INVALID_ARGUMENT, "environment: sun %u: a direction of zero or non-finite magnitude", i);
+      const double a[3] = {d[0] / len, d[1] / len, d[2] / len};
+      for (uint32_t k = 0; k < 3u; ++k) rows.push_back(-a[k]);  // point_to_light
+      for (uint32_t k = 0; k < 3u; ++k) rows.push_back(c[k]);
+    }
+  }
+  std::shared_ptr<const EnvironmentTables> tables;  // (no sky and no sun: none)
+  if (sky || !rows.empty()) {
+    auto t = std::make_shared<EnvironmentTables>();
+    for (int c = 0; c < 3; ++c) t->rgb[c] = e->rgb[c];
+    t->pattern = e->pattern;
+    t->projection = e->projection;
+    t->sky = sky;
+    t->n_suns = e->n_suns;
+    if (!rows.empty()) {
+      HIP_TRY(hipSetDevice(s->device));
+      HIP_TRY(t->sun.upload(rows));
+    }
+    tables = std::move(t);
+  }
+  // (the rows being replaced may still be read by a launch of this handle or of its band clones)
+  HIP_TRY(handleIdle(s));
+  for (rtc_scene* b : s->band) HIP_TRY(handleIdle(b));
+  s->environment = tables;
+  for (rtc_scene* b : s->band) b->environment = tables;  // (the band clones rtc_render renders a large frame with)
+  return RTC_OK;
+}
+
 // ---- adaptive sampling
 // The setting's own fields, and the image's tile count (T < 2^31)
 static int checkAdaptive(const rtc_adaptive* a, uint32_t hsize, uint32_t vsize, uint32_t* n_tiles) {
@@ -3389,6 +3488,9 @@ int rtc_scene_clone(const rtc_scene* src, rtc_scene** out) {
   s->media = src->media;  // (shared: read-only once made; the fifth-quarter buffer is the handle's own, made at its first launch)
   s->blocks_per_cu_media_lds = src->blocks_per_cu_media_lds;
   s->blocks_per_cu_media_big = src->blocks_per_cu_media_big;
+  s->environment = src->environment;  // (shared: read-only once made)
+  s->blocks_per_cu_env_lds = src->blocks_per_cu_env_lds;
+  s->blocks_per_cu_env_big = src->blocks_per_cu_env_big;
   s->simple_kernel = src->simple_kernel;
   s->flat_kernel = src->flat_kernel;
   s->simple3_ok = src->simple3_ok;
@@ -3810,7 +3912,8 @@ int rtc_set_option(const char* name, double value) {
                {"spot_kernels", &o.spot_kernels}, {"bump_kernels", &o.bump_kernels},
                {"torus_kernels", &o.torus_kernels}, {"meshuv_kernels", &o.meshuv_kernels},
                {"gloss_kernels", &o.gloss_kernels}, {"occlusion_kernels", &o.occlusion_kernels},
-               {"shadow_filter_kernels", &o.shadow_filter_kernels}, {"media_kernels", &o.media_kernels}};
+               {"shadow_filter_kernels", &o.shadow_filter_kernels}, {"media_kernels", &o.media_kernels},
+               {"environment_kernels", &o.environment_kernels}};
   for (const auto& e : table)
     if (std::strcmp(e.name, name) == 0) {
       e.slot->set(value);

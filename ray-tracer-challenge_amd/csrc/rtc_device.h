@@ -414,6 +414,27 @@ struct DevMedia {
   void* __restrict__ stack_ext;
 };
 
+// An environment (rtc_scene_set_environment): the extra argument of the environment kernels only.
+// The sky: `rgb`, the colour a missed ray adds - with a pattern, a row of the scene's pattern table, the factor on that
+// pattern's colour at the ray's direction; `sky`: 0 when the colour is zero and there is no pattern - the step is not run.
+// The suns: RTC_ENV_SUN_ROW doubles each, in table order - the unit vector TOWARDS the sun (the direction the light
+// travels, normalised and negated on the host) and the intensity.  Under the "environment_kernels" option on a handle
+// without an environment there is no sky and there are no suns.
+#ifndef RTC_ENV_NO_PATTERN
+#define RTC_ENV_NO_PATTERN 0xFFFFFFFFu  // (rtc.h's)
+#define RTC_ENV_SPHERE 0u
+#define RTC_ENV_CUBE 1u
+#endif
+#define RTC_ENV_SUN_ROW 6u
+struct DevEnvironment {
+  double rgb[3];
+  uint32_t pattern;     // a row of DevScene::pat, or RTC_ENV_NO_PATTERN
+  uint32_t projection;  // RTC_ENV_SPHERE / RTC_ENV_CUBE
+  uint32_t n_suns;
+  uint32_t sky;
+  const double* __restrict__ sun;  // [n_suns][RTC_ENV_SUN_ROW]
+};
+
 struct DevCamera {
   double half_width, half_height, pixel_size;
   double inv[12];  // rows 0..2 of Camera._inverse_transform

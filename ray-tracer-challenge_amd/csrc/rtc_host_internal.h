@@ -75,6 +75,7 @@ struct RtcOptions {
   RtcOption occlusion_kernels{0.0};    // != 0: the occlusion kernels even on a handle without a radius, every row zero (tests: against the handle's ordinary kernels)
   RtcOption shadow_filter_kernels{0.0};  // != 0: the shadow-filter kernels even on a handle without a filter, every row zero (tests: against the handle's ordinary kernels)
   RtcOption media_kernels{0.0};        // != 0: the media kernels even on a handle without media, every row and the density zero (tests: against the handle's ordinary kernels)
+  RtcOption environment_kernels{0.0};  // != 0: the environment kernels even on a handle without an environment, no sky and no sun (tests: against the handle's ordinary kernels)
   RtcOption build_threads{0.0};        // threads of rtc_scene_create's candidate-BVH build (one top-level group each); 0: as many as the host allows, up to 8
 };
 inline RtcOptions& rtcOptions() {
@@ -187,6 +188,15 @@ struct MediaTables {
   double fog_color[3] = {0.0, 0.0, 0.0};
 };
 
+// A handle's environment (rtc_scene_set_environment): DevEnvironment's sky and sun rows.  Read-only once made: a clone and
+// the band clones share it.
+struct EnvironmentTables {
+  double rgb[3] = {0.0, 0.0, 0.0};
+  uint32_t pattern = 0xFFFFFFFFu, projection = 0u, n_suns = 0u;
+  bool sky = false;     // a non-zero colour or a pattern: the miss step runs
+  DevBuf<double> sun;   // [n_suns][RTC_ENV_SUN_ROW]; empty without suns
+};
+
 // A handle's spot lights (rtc_scene_set_spots): DevSpots::row.  Read-only once made: a clone and the band clones share it.
 struct SpotTables {
   DevBuf<double> row;
@@ -251,6 +261,8 @@ struct rtc_scene {
   uint32_t blocks_per_cu_sfilt_lds = 1, blocks_per_cu_sfilt_big = 1;  // resident work-groups per CU of the shadow-filter kernels
   std::shared_ptr<const MediaTables> media;  // rtc_scene_set_media; null: no absorbing row and no fog (a clone starts with its source's)
   uint32_t blocks_per_cu_media_lds = 1, blocks_per_cu_media_big = 1;  // resident work-groups per CU of the media kernels
+  std::shared_ptr<const EnvironmentTables> environment;  // rtc_scene_set_environment; null: no sky and no sun (a clone starts with its source's)
+  uint32_t blocks_per_cu_env_lds = 1, blocks_per_cu_env_big = 1;  // resident work-groups per CU of the environment kernels
   bool simple3_ok = false;         // a simple world whose tables fit the three-waves-per-SIMD kernel's LDS (RTC_LDS3_*)
   void* d_csg_buf = nullptr;       // DevPixelMap::csg_buf, only for scenes with csg nodes
   size_t csg_buf_capacity = 0;     // bytes

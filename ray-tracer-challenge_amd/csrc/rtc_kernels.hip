@@ -2060,6 +2060,26 @@ struct FilterVisitor {
 };
 #endif
 
+// A sun's isShadowed (rtc.h's rtc_scene_set_environment): FilterVisitor without a far end.  The limit
+// is +infinity for every box rule - `tn > inf` is false, and no rule multiplies the limit by a zero or subtracts it from
+// itself -, and an entry counts on `et >= 0` alone, not on `et < distance`: a cube whose local direction is shorter than
+// the reference's 1e-5 on every axis answers with entries at -inf and +inf (cube.zig's check_axis), and the one at +inf
+// is an entry with et >= 0 however far away - `inf < inf` would drop it.  A NaN fails `et >= 0` as it does everywhere.
+// Compiled into the environment kernels' translation unit only.
+#ifdef RTC_ENV_TU
+struct SunVisitor : FilterVisitor {
+  __device__ __forceinline__ void entry(uint32_t, uint32_t casts_shadow, uint32_t material, double et, double, double) {
+    if (et >= 0.0 && casts_shadow) {
+      const double* __restrict__ f = filter + 3ull * material;
+      tr = tr * f[0];
+      tg = tg * f[1];
+      tb = tb * f[2];
+    }
+  }
+  __device__ __forceinline__ bool relevant(uint32_t, uint32_t casts_shadow, double et) const { return et >= 0.0 && casts_shadow; }
+};
+#endif
+
 // The containers walk of PreComputations.new (world.zig:229-255), as a reduction.
 // Entries before the hit in the sorted list are exactly those with t < 0.  A leaf with an
 // odd number of them is still in `containers` when the hit is reached, at the position of
@@ -2557,6 +2577,18 @@ __device__ __forceinline__ Rgb pattern_at(const DevScene& S, const DevPattern* _
   return {ca.r + (cb.r - ca.r) * fpart, ca.g + (cb.g - ca.g) * fpart, ca.b + (cb.b - ca.b) * fpart};
 }
 
+// (ENV) the environment unit evaluates patterns in a second place, at a missed ray's direction.
+// pattern_at is forced inline: a second call would put a second copy of the select-chain and mix code into kernels that
+// stand at 256 VGPRs.  The miss calls this out-of-line form instead; the hit keeps the inlined call every unit has (with
+// the hit's lookup out of line too, through generic pointers where it reads LDS, every hit paid for it: cover + 6 %,
+// teapot + 8 % on a handle without an environment).
+#ifdef RTC_ENV_TU
+__device__ __noinline__ Rgb pattern_at_shared(const DevScene& S, const DevPattern* pat, uint32_t idx, double ox, double oy,
+                                              double oz RTC_MESHUV_PARAM) {
+  return pattern_at<true>(S, pat, idx, ox, oy, oz RTC_MESHUV_ARG);
+}
+#endif
+
 // std.math.pow(f64, x, y) as Zig's standard library computes it (lib/std/math/pow.zig, a port of Go's
 // math.Pow; the reference calls it at material.zig:69 and world.zig:288): special cases, then
 // x^y = x^frac(y) * x^int(y), the integer power by binary exponentiation on the frexp mantissa with the
@@ -2980,9 +3012,13 @@ __device__ __noinline__ GlossDir occl_direction(unsigned long long h, uint32_t w
 // weight per channel, and is attenuated along its segment (Beer-Lambert absorption in a material, a uniform fog outside).
 // With SFILT and everything below it, compiled into the media kernels' translation unit only, under RTC_MEDIA_TU, which
 // implies RTC_SFILT_TU)
+// (ENV: an environment - DevEnvironment, the environment kernels' extra argument: a ray that misses adds the sky's colour at
+// its direction, and every hit is lit by the suns, directional lights whose shadow rays have no far end, in a second loop
+// after World.lights.  With MEDIA and everything below it, compiled into the environment kernels' translation unit only,
+// under RTC_ENV_TU, which implies RTC_MEDIA_TU)
 template <bool LDS, bool CSG, int WORLD = 0, int WAVES = 2, bool COOP = false, bool BOX = true, bool AREA = false, bool MS = false,
           bool MOTION = false, bool SPOT = false, bool BUMP = false, bool TORUS = false, bool MESHUV = false, bool GLOSS = false,
-          bool OCCL = false, bool SFILT = false, bool MEDIA = false>
+          bool OCCL = false, bool SFILT = false, bool MEDIA = false, bool ENV = false>
 __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& cam, const DevPixelMap& map,
                                             const uint32_t max_depth, double* __restrict__ out,
                                             DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
@@ -2991,7 +3027,8 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
                                             const DevBumps& bumps = DevBumps{}, const DevMeshUvs& muv = DevMeshUvs{},
                                             const DevGloss& gloss = DevGloss{}, const DevOcclusion& occl = DevOcclusion{},
                                             const DevShadowFilter& sfilt = DevShadowFilter{},
-                                            const DevMedia& media = DevMedia{}) {
+                                            const DevMedia& media = DevMedia{},
+                                            const DevEnvironment& env = DevEnvironment{}) {
   static_assert(!AREA || !COOP, "the area kernels run no cooperative iterations");
   static_assert(!MS || !COOP, "the sampling kernels run no cooperative iterations");
   static_assert(!MOTION || (MS && AREA && WORLD == 0), "the motion kernels are the general area-sampling walk");
@@ -3037,6 +3074,14 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
 #else
   static_assert(!MEDIA, "participating media are compiled in the media translation unit (rtc_media.hip) only");
   (void)media;
+#endif
+  static_assert(!ENV || MEDIA, "the environment kernels are the media walk");
+#ifdef RTC_ENV_TU
+  static_assert(ENV, "the environment translation unit compiles the environment kernels only");
+  static_assert(CSG, "the environment kernels evaluate every pattern kind");
+#else
+  static_assert(!ENV, "the environment is compiled in the environment translation unit (rtc_environment.hip) only");
+  (void)env;
 #endif
   RTC_PRIO_PHASE(RTC_PRIO_WORK);
 #ifndef RTC_PROFILE
@@ -3699,6 +3744,33 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
     }
     uint32_t kid_medium = RTC_NO_MEDIUM;  // the medium of a refracted child: the material that supplies n2, or none
 #endif
+#ifdef RTC_ENV_TU
+    // (ENV, rtc.h's rtc_scene_set_environment) the sky: a ray that found nothing adds its weight - after the media step, so
+    // with the miss transmittance in it - times the sky's colour at its direction.  The pattern is evaluated at the point
+    // where the direction meets the unit sphere or the unit cube, as at an object-space point, with no hit triangle.  A
+    // wave none of whose lanes missed, and every wave of a handle without a sky, branches around it.
+    if constexpr (ENV) {
+      const bool missed = hv.leaf == RTC_NO_LEAF;
+      if (env.sky != 0u && __any(missed)) {
+        if (missed) {
+          double e_r = env.rgb[0], e_g = env.rgb[1], e_b = env.rgb[2];
+          if (env.pattern != RTC_ENV_NO_PATTERN) {
+            const double len = env.projection == RTC_ENV_CUBE
+                                   ? __builtin_fmax(__builtin_fabs(ray.dx), __builtin_fmax(__builtin_fabs(ray.dy), __builtin_fabs(ray.dz)))
+                                   : __builtin_sqrt((ray.dx * ray.dx + ray.dy * ray.dy) + ray.dz * ray.dz);
+            const MeshUvHit mh{muv.row, RTC_NO_LEAF, 0.0, 0.0};
+            const Rgb c = pattern_at_shared(S, pats, env.pattern, ray.dx / len, ray.dy / len, ray.dz / len, mh);
+            e_r = c.r * e_r;
+            e_g = c.g * e_g;
+            e_b = c.b * e_b;
+          }
+          acc[0] = acc[0] + cur.weight * e_r;
+          acc[1] = acc[1] + cur.weight_g * e_g;
+          acc[2] = acc[2] + cur.weight_b * e_b;
+        }
+      }
+    }
+#endif
     if (hv.leaf == RTC_NO_LEAF) continue;  // black (world.zig:119)
 
     // ---- PreComputations.new (world.zig:212-227)
@@ -4242,6 +4314,72 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
         sg = sg + lg_;
         sb = sb + lb_;
       }
+#ifdef RTC_ENV_TU
+      // (ENV, rtc.h's rtc_scene_set_environment) the suns, after World.lights and in table order: a point light in
+      // everything but its geometry.  point_to_light is the row's unit vector whatever the point, the distance is
+      // infinite: every entry with et >= 0 on a casts_shadow leaf counts (SunVisitor: FilterVisitor with an infinite limit
+      // - not an any-hit walk, so no early-out that reasons about a segment's far end is compiled in; DESIGN.md section 24
+      // lists what was read).  No cone, no area row.  si is wave-uniform: the row is read through the constant address space at a
+      // readfirstlane index - scalar loads, as DevSpots' rows are -, and nothing of it is staged in LDS.
+      if constexpr (ENV) {
+        for (uint32_t si = 0u; si < env.n_suns; ++si) {
+          typedef const __attribute__((address_space(4))) double ConstRow;
+          ConstRow* U = (ConstRow*)env.sun + static_cast<size_t>(RTC_ENV_SUN_ROW) * __builtin_amdgcn_readfirstlane(si);
+          const double lvx = U[0], lvy = U[1], lvz = U[2];
+          const double ir = U[3], ig = U[4], ib = U[5];
+          it_shadow_calls++;
+          const double light_dot_normal = (lvx * hx + lvy * hy) + lvz * hz;
+          bool shadowed = false;
+          RTC_SF_DECL;
+          if (shadow_matters && light_dot_normal >= 0.0) {
+            it_shadow_traced++;
+            it_share++;
+            SunVisitor sv;
+            sv.distance = kInf;
+            RTC_LIGHT_VISITOR_SET(sv);
+            Ray sray{ovx, ovy, ovz, lvx, lvy, lvz};
+            trace<CSG, WORLD, SunVisitor, TRAV, BOX, MOTION, ROOTS>(S, recs, cull, sray, sv, it_overflow, trav_stack, member, stride, mo.disp, tm);
+            shadowed = RTC_LIGHT_BLOCKED(sv);
+            RTC_SF_TAKE(sv);
+          }
+          // Material.lighting (material.zig:40-74) with the sun's intensity
+          const double er = color.r * ir, eg = color.g * ig, eb = color.b * ib;  // effective_color
+          const double ka = RTC_KA(mat);
+          double lr_ = er * ka, lg_ = eg * ka, lb_ = eb * ka;
+          if (!shadowed) {
+            double dr = 0.0, dg = 0.0, db = 0.0, pr = 0.0, pg = 0.0, pb = 0.0;
+            if (light_dot_normal >= 0.0) {
+              const double kd = mat.diffuse * light_dot_normal;
+              dr = er * kd;
+              dg = eg * kd;
+              db = eb * kd;
+              const double two_dot = 2.0 * light_dot_normal;  // point_to_light.reflect(normal)
+              const double rx = lvx - hx * two_dot, ry = lvy - hy * two_dot, rz = lvz - hz * two_dot;
+              const double reflect_dot_eye = ((-rx) * ex + (-ry) * ey) + (-rz) * ez;
+              if (reflect_dot_eye > 0.0) {
+                const uint32_t n = mat.shininess_int;
+                // (specular_skip, as in the loop above: a material without a specular term keeps the zero itself)
+                bool ks_is_specular = false;
+                if (mat.specular == 0.0) ks_is_specular = n != 0u && reflect_dot_eye <= 1.0;
+                double ks = mat.specular;
+                if (!(kSpecularSkip && ks_is_specular))
+                  ks = mat.specular * (n != 0u && reflect_dot_eye < kInf ? pow_small_int(reflect_dot_eye, n)
+                                                                         : zig_pow(reflect_dot_eye, mat.shininess));
+                pr = ir * ks;
+                pg = ig * ks;
+                pb = ib * ks;
+              }
+            }
+            lr_ = (lr_ + RTC_SF(dr, r)) + RTC_SF(pr, r);
+            lg_ = (lg_ + RTC_SF(dg, g)) + RTC_SF(pg, g);
+            lb_ = (lb_ + RTC_SF(db, b)) + RTC_SF(pb, b);
+          }
+          sr = sr + lr_;
+          sg = sg + lg_;
+          sb = sb + lb_;
+        }
+      }
+#endif
       if constexpr (COOP) {
         if (deal_lights) {  // the other half's light (lane i <-> 7 - i pairs the halves), and what it counted
           sr = sr + group8_other<2>(sr);
@@ -4510,7 +4648,8 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
 // and the torus kernels, rtc_meshuv.hip with RTC_MESHUV_TU (and, with it, RTC_TORUS_TU) and the meshuv kernels, rtc_gloss.hip
 // with RTC_GLOSS_TU (and, with it, both of those) and the gloss kernels, rtc_occlusion.hip with RTC_OCCL_TU (and, with it, those
 // three) and the occlusion kernels, rtc_shadowfilter.hip with RTC_SFILT_TU (and, with it, those four) and the shadow-filter
-// kernels, rtc_media.hip with RTC_MEDIA_TU (and, with it, those five) and the media kernels.  rtc_kernels_ext.hip
+// kernels, rtc_media.hip with RTC_MEDIA_TU (and, with it, those five) and the media kernels, rtc_environment.hip with
+// RTC_ENV_TU (and, with it, those six) and the environment kernels.  rtc_kernels_ext.hip
 // includes it with RTC_EXT_TU defined: in the -DRTC_PROFILE diagnostic build, whose instrumented walk makes this unit's
 // compile about a third longer, it gets the csg / texture-map, flat and area-light kernels (rtc_render_kernel_ext to
 // rtc_render_kernel_area_bigworld below), so that neither unit takes the time of all of them.  The product build keeps
@@ -5383,6 +5522,31 @@ rtc_render_kernel_bump_bigworld(const DevScene S, const DevCamera cam, const Dev
                                                                             spots, bumps);
 }
 
+#elif defined(RTC_ENV_TU)
+
+// An environment (rtc_scene_set_environment): the media walk with a sky where a ray misses and the
+// suns' loop after World.lights, and the sky and the sun rows (DevEnvironment) as one more argument; one pair for every
+// world.  Every other kernel is compiled without it.
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_env(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                      double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                      const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots, const DevBumps bumps,
+                      const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl, const DevShadowFilter sfilt,
+                      const DevMedia media, const DevEnvironment env) {
+  render_body<true, true, 0, 2, false, true, true, true, true, true, true, true, true, true, true, true, true, true>(
+      S, cam, map, max_depth, out, stats, next_stats, area, smp, mo, spots, bumps, muv, gloss, occl, sfilt, media, env);
+}
+
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_env_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                               double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                               const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                               const DevBumps bumps, const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl,
+                               const DevShadowFilter sfilt, const DevMedia media, const DevEnvironment env) {
+  render_body<false, true, 0, 2, false, true, true, true, true, true, true, true, true, true, true, true, true, true>(
+      S, cam, map, max_depth, out, stats, next_stats, area, smp, mo, spots, bumps, muv, gloss, occl, sfilt, media, env);
+}
+
 #elif defined(RTC_MEDIA_TU)
 
 // Participating media (rtc_scene_set_media): the shadow-filter walk with a medium and a weight per
@@ -5526,4 +5690,4 @@ rtc_render_kernel_torus_bigworld(const DevScene S, const DevCamera cam, const De
                                                                                   smp, mo, spots, bumps);
 }
 
-#endif  // RTC_MOTION_TU / RTC_SPOT_TU / RTC_BUMP_TU / RTC_MEDIA_TU / RTC_SFILT_TU / RTC_OCCL_TU / RTC_GLOSS_TU / RTC_MESHUV_TU / RTC_TORUS_TU
+#endif  // RTC_MOTION_TU / RTC_SPOT_TU / RTC_BUMP_TU / RTC_ENV_TU / RTC_MEDIA_TU / RTC_SFILT_TU / RTC_OCCL_TU / RTC_GLOSS_TU / RTC_MESHUV_TU / RTC_TORUS_TU

@@ -253,7 +253,7 @@ struct Flattener {
 
 }  // namespace
 
-FlatScene flattenWorld(const World& world) {
+FlatScene flattenWorld(const World& world, const Pattern* environment_pattern) {
   Flattener f;
   for (const Shape& s : world.objects) {
     const uint32_t r = f.visit(s);
@@ -274,6 +274,8 @@ FlatScene flattenWorld(const World& world) {
     f.out.light_vsteps.push_back(l.vsteps);
     f.out.light_jitter.push_back(l.jitter ? 1u : 0u);
   }
+  // (last: every table is that of the world alone, and then the environment's rows)
+  if (environment_pattern) f.out.env_pattern = f.internPattern(*environment_pattern);
   return std::move(f.out);
 }
 

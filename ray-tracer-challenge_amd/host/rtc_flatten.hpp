@@ -34,6 +34,7 @@ struct FlatScene {
   bool shadow_filter_present = false;     // some material of the scene has the "shadow-filter" key
   std::vector<double> mat_absorption;  // [n_materials][3]: each row's "absorption" (rtch_scene_media; not part of rtc_scene_desc)
   bool absorption_present = false;     // some material of the scene has the "absorption" key
+  uint32_t env_pattern = 0xFFFFFFFFu;  // the environment's pattern row (rtch_scene_environment), or RTC_ENV_NO_PATTERN; not part of rtc_scene_desc
   std::vector<Bump> mat_bump;  // [n_materials]: each row's "normal-perturbation" (rtch_scene_bumps; not part of rtc_scene_desc)
   std::vector<uint8_t> pat_kind;
   std::vector<double> pat_inv, pat_rgb;
@@ -64,7 +65,9 @@ struct FlatScene {
   size_t nodeCount() const { return node_first.size(); }
 };
 
-FlatScene flattenWorld(const World& world);
+// (environment_pattern: the "environment"'s pattern, DESIGN.md section 24 - its rows, and the images it names, are interned
+// after every material's: the tables of the same file without the key, and then those rows; FlatScene::env_pattern)
+FlatScene flattenWorld(const World& world, const Pattern* environment_pattern = nullptr);
 rtc_camera flattenCamera(const Camera& camera);
 
 }  // namespace rtc

@@ -50,7 +50,7 @@ int rtch_scene_load(const char* scene_json, const char* data_dir, void** out) {
   return guarded([&] {
     auto hs = std::make_unique<HostScene>();
     hs->info = rtc::parseScene(scene_json, rtc::directoryLoader(data_dir ? data_dir : ""));
-    hs->flat = rtc::flattenWorld(hs->info.world);
+    hs->flat = rtc::flattenWorld(hs->info.world, hs->info.env_pattern ? &*hs->info.env_pattern : nullptr);
     hs->desc = hs->flat.desc();
     hs->lights = hs->flat.lights();
     *out = hs.release();
@@ -195,6 +195,29 @@ int rtch_scene_media(void* h, double* absorption, double* fog, int* present, uin
   });
 }
 
+// The scene's "environment"  as rtc_scene_set_environment takes it: `out`'s rgb, pattern - a row of
+// the description's pat_* tables, after every material's -, projection and n_suns; the suns' directions and intensities, as
+// the file has them, into sun_direction and sun_rgb (3 * RTC_ENV_MAX_SUNS doubles each), which `out` then points to;
+// *present: the file has the key.
+int rtch_scene_environment(void* h, rtc_environment* out, double* sun_direction, double* sun_rgb, int* present) {
+  return guarded([&] {
+    const HostScene* hs = static_cast<HostScene*>(h);
+    if (!out || !sun_direction || !sun_rgb) throw rtc::Error("InvalidArgument", "environment: null argument");
+    std::memset(out, 0, sizeof(*out));
+    for (int c = 0; c < 3; ++c) out->rgb[c] = hs->info.env_color[c];
+    out->pattern = hs->flat.env_pattern;
+    out->projection = hs->info.env_projection;
+    out->n_suns = static_cast<uint32_t>(hs->info.sun_direction.size() / 3u);
+    for (size_t i = 0; i < hs->info.sun_direction.size(); ++i) {
+      sun_direction[i] = hs->info.sun_direction[i];
+      sun_rgb[i] = hs->info.sun_intensity[i];
+    }
+    out->sun_direction = sun_direction;
+    out->sun_rgb = sun_rgb;
+    if (present) *present = hs->info.environment_present ? 1 : 0;
+  });
+}
+
 // The triangles' texture rows (RTC_TEX_MESH), in tri_* order, as rtc_scene_set_mesh_uvs takes them.
 int rtch_scene_mesh_uvs(void* h, double* uv, uint32_t n) {
   return guarded([&] {
@@ -329,6 +352,15 @@ int rtch_scene_render(void* h, uint32_t width, uint32_t height, uint32_t max_dep
         const rtc_media me{hs->desc.n_materials, hs->flat.mat_absorption.data(), hs->info.fog_density,
                            {hs->info.fog_color[0], hs->info.fog_color[1], hs->info.fog_color[2]}};
         st = rtc_scene_set_media(scene, &me);
+      }
+      if (st == RTC_OK && hs->info.environment_present) {  // (the environment; no sky and no sun: the handle as it is)
+        const rtc_environment ev{{hs->info.env_color[0], hs->info.env_color[1], hs->info.env_color[2]},
+                                 hs->flat.env_pattern,
+                                 hs->info.env_projection,
+                                 static_cast<uint32_t>(hs->info.sun_direction.size() / 3u),
+                                 hs->info.sun_direction.data(),
+                                 hs->info.sun_intensity.data()};
+        st = rtc_scene_set_environment(scene, &ev);
       }
       const rtc::CameraSampling& cs = hs->info.sampling;
       if (cs.adaptive && st == RTC_OK) {  // (adaptive sampling: each tile's mean after its own passes, section 15)

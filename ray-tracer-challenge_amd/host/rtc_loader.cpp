@@ -375,6 +375,18 @@ Pattern parsePattern(const Value& cfg, const FileLoader& load_file_data) {
   return pat;
 }
 
+// Whether a texture map of mapping "mesh" sits anywhere in a pattern: below a select, a mix or a perturb, or among a uv
+// pattern's sub-patterns (the environment's pattern, DESIGN.md section 24, has no triangle to read a texture row from).
+bool hasMeshMap(const Pattern& p) {
+  if (p.kind == PatternKind::TextureMap && p.texture_map) {
+    if (p.texture_map->mapping == TexMapping::Mesh) return true;
+    for (const UvPattern& uv : p.texture_map->faces)
+      for (const auto& sub : uv.sub)
+        if (sub && hasMeshMap(*sub)) return true;
+  }
+  return (p.a && hasMeshMap(*p.a)) || (p.b && hasMeshMap(*p.b));
+}
+
 // ---- scene.zig:407-430 ------------------------------------------------------------------
 const Value* presentField(const Value& obj, const char* k) {
   const Value* v = obj.find(k);
@@ -780,7 +792,7 @@ unsigned loaderThreads() {
 SceneInfo parseScene(const std::string& scene_json, const FileLoader& load_file_data) {
   const Value root = json::parse(scene_json);
   requireObject(root, "scene");
-  checkFields(root, {"shape-definitions", "camera", "lights", "objects", "atmosphere"}, "scene");
+  checkFields(root, {"shape-definitions", "camera", "lights", "objects", "atmosphere", "environment"}, "scene");
 
   Definitions definitions;
   if (const Value* defs = root.find("shape-definitions")) {
@@ -822,6 +834,57 @@ SceneInfo parseScene(const std::string& scene_json, const FileLoader& load_file_
       if (col.arr[i].type != Value::Number) throw Error("InvalidData", "atmosphere: color is three numbers >= 0");
       info.fog_color[i] = asFloat(col.arr[i], "atmosphere");
       if (!(std::isfinite(info.fog_color[i]) && info.fog_color[i] >= 0.0)) throw Error("InvalidData", "atmosphere: color is three finite numbers >= 0");
+    }
+  }
+  // "environment" (not in the reference): the sky behind the world and the suns that light it
+  if (const Value* env = root.find("environment")) {
+    requireObject(*env, "environment");
+    checkFields(*env, {"color", "pattern", "projection", "suns"}, "environment");
+    if (env->obj.empty()) throw Error("MissingField", "environment: one of color, pattern, projection, suns");
+    info.environment_present = true;
+    // (three finite numbers >= 0)
+    auto vec3 = [](const Value& v, const char* what, double out[3]) {
+      if (v.type != Value::Array) throw Error("InvalidData", std::string(what) + " is [x, y, z]");
+      if (v.arr.size() != 3) throw Error("LengthMismatch", std::string(what) + " is [x, y, z]");
+      for (int i = 0; i < 3; ++i) {
+        if (v.arr[i].type != Value::Number) throw Error("InvalidData", std::string(what) + " is three numbers");
+        out[i] = v.arr[i].num;
+        if (!std::isfinite(out[i])) throw Error("InvalidData", std::string(what) + " is three finite numbers");
+      }
+    };
+    auto colour = [&](const Value& v, const char* what, double out[3]) {
+      vec3(v, what, out);
+      for (int i = 0; i < 3; ++i)
+        if (!(out[i] >= 0.0)) throw Error("InvalidData", std::string(what) + " is three numbers >= 0");
+    };
+    if (const Value* p = env->find("pattern")) {
+      info.env_pattern = parsePattern(*p, load_file_data);
+      if (hasMeshMap(*info.env_pattern)) throw Error("InvalidData", "environment: a mesh texture map has no triangle to read");
+      info.env_color[0] = info.env_color[1] = info.env_color[2] = 1.0;
+    }
+    if (const Value* c = env->find("color")) colour(*c, "environment: color", info.env_color);
+    if (const Value* pr = env->find("projection")) {
+      if (pr->type != Value::String) throw Error("InvalidData", "environment: projection is \"sphere\" or \"cube\"");
+      if (pr->str == "cube") {
+        info.env_projection = RTC_ENV_CUBE;
+      } else if (pr->str != "sphere") {
+        throw Error("InvalidData", "environment: projection is \"sphere\" or \"cube\"");
+      }
+    }
+    if (const Value* suns = env->find("suns")) {
+      if (suns->type != Value::Array) throw Error("InvalidData", "environment: suns is a list");
+      if (suns->arr.size() > RTC_ENV_MAX_SUNS) throw Error("InvalidData", "environment: more than " + std::to_string(RTC_ENV_MAX_SUNS) + " suns");
+      for (const Value& sun : suns->arr) {
+        requireObject(sun, "sun");
+        checkFields(sun, {"direction", "intensity"}, "sun");
+        double d[3], c[3];
+        vec3(requireField(sun, "direction", "sun"), "sun: direction", d);
+        colour(requireField(sun, "intensity", "sun"), "sun: intensity", c);
+        const double len = std::sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+        if (!(std::isfinite(len) && len > 0.0)) throw Error("InvalidData", "sun: a direction of zero or non-finite magnitude");
+        info.sun_direction.insert(info.sun_direction.end(), d, d + 3);
+        info.sun_intensity.insert(info.sun_intensity.end(), c, c + 3);
+      }
     }
   }
   info.camera.saved_from = from;

@@ -54,6 +54,13 @@ struct SceneInfo {  // scene.zig:608-610
   bool atmosphere_present = false;
   double fog_density = 0.0;
   double fog_color[3] = {0.0, 0.0, 0.0};
+  // the scene's "environment" (section 24): rtc_environment's sky and suns; nothing without the key
+  bool environment_present = false;
+  double env_color[3] = {0.0, 0.0, 0.0};
+  std::optional<Pattern> env_pattern;
+  uint32_t env_projection = 0u;            // RTC_ENV_SPHERE / RTC_ENV_CUBE
+  std::vector<double> sun_direction;       // [suns][3], as the file has them
+  std::vector<double> sun_intensity;       // [suns][3]
 };
 
 // scene.zig:612-661.  Throws rtc::Error whose .name is the Zig error name

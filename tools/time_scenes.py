@@ -59,6 +59,11 @@ shadow-filter kernels without a filter.  With --passes the noise run has the sam
 world distance; --media fog=density,r,g,b: the atmosphere (rtc_scene_set_media); on a scene file with
 "absorption" entries or an "atmosphere" those are applied first; --media off applies none.  Option media_kernels=1 times the
 media kernels without media.  With --passes the noise run has the same table.
+--environment FILE: the "environment" of scene file FILE - its sky, whose pattern must be one the timed scene's tables hold at
+the same row, as the same file's is, and its suns (rtc_scene_set_environment) - instead of the timed
+scene file's own, which is applied otherwise; --environment off applies none.  Option environment_kernels=1 times the
+environment kernels without an environment.  With --passes the noise run has the same table.
+--data-dir DIR: where a scene named by its path finds the images and OBJ files it names (default: the scene's directory).
 --adaptive threshold[,min,tile]: adaptive sampling at up to --max-passes (64) passes, min passes 4 and
 16 x 16 tiles by default, with the --sampling of the frames: prints the rounds and tile-passes of a run against
 T * max_passes, its time (a second run, end to end on the host) against uniform progressive passes (render_device +
@@ -103,6 +108,8 @@ ap.add_argument("--occlusion", action="append", default=[])
 ap.add_argument("--occlusion-samples", type=int, default=0)
 ap.add_argument("--shadow-filter", action="append", default=[])
 ap.add_argument("--media", action="append", default=[])
+ap.add_argument("--environment", default="")
+ap.add_argument("--data-dir", default="")  # where a scene named by path finds its images and OBJ files (default: beside it)
 ap.add_argument("--torus", action="store_true")
 ap.add_argument("--meshuv", action="store_true")
 ap.add_argument("--mesh-as-planar", action="store_true")
@@ -184,6 +191,18 @@ def media_table(hs):
         else:
             media["absorption"][int(m)] = v
     return media
+
+
+def environment_table(hs):
+    """the scene file's environment, or that of the --environment file; None: no table (--environment off, or nothing to set)"""
+    if args.environment == "off":
+        return None
+    if args.environment:
+        env = rtc.HostScene.from_file(args.environment).environment()
+        if env is not None and env["pattern"] != rtc.ENV_NO_PATTERN and env["pattern"] >= hs.desc.n_patterns:
+            raise SystemExit("--environment: the file's sky pattern is no row of the timed scene's tables")
+        return env
+    return hs.environment()
 
 
 def light_table(hs, how):
@@ -324,7 +343,7 @@ stream = torch.cuda.Stream(); torch.cuda.set_stream(stream)
 out = []
 for name, w, h, depth in cases:
     # (a scene given by its path may name files beside it)
-    hs = (rtc.HostScene.from_file(name + ".json", os.path.dirname(name)) if os.path.exists(name + ".json")
+    hs = (rtc.HostScene.from_file(name + ".json", args.data_dir or os.path.dirname(name)) if os.path.exists(name + ".json")
           else rtc.HostScene.from_file(name + ".json")); cam = hs.camera(w, h)
     desc, keep = hs.desc, None
     if args.mesh_as_planar:
@@ -391,6 +410,9 @@ for name, w, h, depth in cases:
         media = media_table(hs)
         if media is not None:
             gpu.set_media(media)
+        environment = environment_table(hs)
+        if environment is not None:
+            gpu.set_environment(environment)
         for i in range(args.settle):
             gpu.render_device(cam, canvas.data_ptr(), depth, None, stream.cuda_stream)
         torch.cuda.synchronize()
@@ -415,7 +437,7 @@ for name, w, h, depth in cases:
     if delta is not None: line += f" maxdelta {delta:.2e}"
     if args.lights or args.spot or "spot_kernels=1" in args.option:
         line += f" shadow_traced {st['shadow_traced']} ns/shadow-ray {min(ts) * 1e6 / max(1, st['shadow_traced']):.3f}"
-    if args.sampling or args.option or args.passes >= 0 or args.motion or args.spot or args.bump or args.torus or args.meshuv or args.gloss or args.occlusion or args.shadow_filter or args.media:
+    if args.sampling or args.option or args.passes >= 0 or args.motion or args.spot or args.bump or args.torus or args.meshuv or args.gloss or args.occlusion or args.shadow_filter or args.media or args.environment:
         line += f" primary {st['primary']} ns/primary-ray {min(ts) * 1e6 / max(1, st['primary']):.3f}"
     if acc:
         ms, copy_ms, nbytes = min(a[0] for a in acc), min(a[1] for a in acc), acc[0][2]
@@ -431,6 +453,7 @@ for name, w, h, depth in cases:
         if occlusion_table(hs) is not None: gpu.set_occlusion(occlusion_table(hs))
         if shadow_filter_table(hs) is not None: gpu.set_shadow_filters(shadow_filter_table(hs))
         if media_table(hs) is not None: gpu.set_media(media_table(hs))
+        if environment_table(hs) is not None: gpu.set_environment(environment_table(hs))
         prog = rtc.Progressive(gpu, cam, depth)
         noise = {}
         for i in range(1, 65):
