@@ -783,6 +783,60 @@ typedef struct rtc_environment {
  */
 int rtc_scene_set_environment(rtc_scene *scene, const rtc_environment *environment);
 
+/* ---- the sky light: hemisphere rays that reach the sky light diffuse surfaces ---- */
+/*
+ * A handle has one sky light: a gain (finite, >= 0), samples (1 .. RTC_SKY_LIGHT_MAX_SAMPLES) and a seed.  The step runs at
+ * every hit, of a primary or a secondary ray, with material.diffuse != 0.0, gain > 0 and a handle whose environment has a sky
+ * (a colour that is not zero, or a pattern).  It runs once per hit, and its result is added after the suns' loop above
+ * (c runs over r, g, b):
+ *   L = (0.0, 0.0, 0.0)
+ *   for k = 0 .. samples - 1:
+ *     d   = the occlusion step's direction rule, unchanged (the first accepted of 32 triples, e = ng + u, d = e / m, the two
+ *           fall-backs to ng), with J drawn from this table's key (below)
+ *     T   = what a sun's shadow ray yields for origin over_point, direction d, distance = +infinity: (1, 1, 1) times the
+ *           row of rtc_scene_set_shadow_filters of every entry with et >= 0 on a casts_shadow leaf - a leaf without a filter
+ *           row, or a handle without a filter table, gives (0, 0, 0) at the first such entry -, under motion at the ray's
+ *           shutter time
+ *     if T != (0, 0, 0):
+ *       E   = the sky at d: the miss formula of the section above with (dx, dy, dz) = d (len, p = d / len, pattern or rgb)
+ *       L.c = L.c + T.c * E.c                                  in k's order
+ *   G.c = gain * (L.c / double(samples))
+ *   s.c = s.c + (color.c * material.diffuse) * G.c             after the last sun's  s = s + l
+ * ng is the geometric normal after its `inside` flip, as in the occlusion step, not the bumped shading normal; color is the
+ * pattern colour the lights' loop uses at that hit.  A cosine-weighted direction has density cos / pi, so the mean of T * E
+ * is the Lambertian irradiance estimate: no pi and no cosine appear.  A blocked sample adds nothing.  Only + - * / sqrt and
+ * comparisons are added, each correctly rounded, in the order written.
+ *
+ * The draws are the occlusion step's functions with a key of their own: J(axis) = rtc_gloss_jitter(h, (k << 17) | code, axis),
+ * h = rtc_gloss_sample_key(key, p, g), key = rtc_mix64(seed ^ 0x082EFA98EC4E6C89) - independent of the occlusion step's, new
+ * per camera sample and pass, independent of bands, tiles, clones, lanes and order.  Like gloss and occlusion, the term is
+ * always sampled.
+ *
+ * Counts: each such hit adds `samples` to shadow_calls and to shadow_traced; a hit with diffuse == 0.0 draws nothing and counts
+ * nothing; primary and secondary are those of the handle without the table.  The occlusion step and its ka, the miss step
+ * and the suns are as they were.  Sky-light rays are a third kind beside occlusion rays and shadow rays: they alone see the
+ * sky, where nothing blocks them; like a sun's shadow ray they are not dimmed by fog or absorption.  A hemisphere ray that
+ * hits something contributes nothing of that surface's light.
+ */
+#define RTC_SKY_LIGHT_MAX_SAMPLES 64u
+typedef struct rtc_sky_light {
+  double gain;      /* the factor on the gathered sky; finite, >= 0; 0: no sky light */
+  uint32_t samples; /* hemisphere rays per hit, 1 .. RTC_SKY_LIGHT_MAX_SAMPLES */
+  uint64_t seed;
+} rtc_sky_light;
+
+/*
+ * This handle's sky light for every render entry point.  Validated on the host before any HIP call and before anything
+ * changes: RTC_ERR_INVALID_ARGUMENT for a gain that is not finite or is negative, or samples outside
+ * 1 .. RTC_SKY_LIGHT_MAX_SAMPLES; the previous table stays in force.  NULL, or a gain of zero, is no sky light.  A clone
+ * starts with its source's table; rtc_render's band clones follow.  The order of this setter and rtc_scene_set_environment
+ * does not matter: which kernels run is decided at launch - the sky-light kernels (rtc_render_kernel_skyl, _skyl_bigworld)
+ * when the handle has a sky light and an environment with a sky; every other handle gets the kernels it got before.
+ * librtc_multi renders without it.  rtc_scene_desc, rtc_camera, rtc_stats, rtc_environment and RTC_ABI_VERSION are as they
+ * were.
+ */
+int rtc_scene_set_sky_light(rtc_scene *scene, const rtc_sky_light *sky_light);
+
 /* ---- adaptive sampling: progressive passes only for tiles still noisy ---- */
 #define RTC_ADAPTIVE_MAX_TILE 1024u
 

@@ -44,7 +44,9 @@ extern "C" {
  * zero, so that their images can be held to the handle's ordinary kernels'), "media_kernels" (!= 0: the media kernels even
  * on a handle without media, every absorption row and the fog density zero, so that their images can be held to the
  * handle's ordinary kernels'), "environment_kernels" (!= 0: the environment kernels even on a handle without an environment,
- * no sky and no sun, so that their images can be held to the handle's ordinary kernels').
+ * no sky and no sun, so that their images can be held to the handle's ordinary kernels'), "sky_light_kernels" (!= 0: the
+ * sky-light kernels even on a handle without a sky light, the gain zero, so that their images can be held to the handle's
+ * ordinary kernels').
  * RTC_ERR_INVALID_ARGUMENT for a name the library does not know.
  * (The library reads no environment variables.)
  */

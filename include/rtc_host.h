@@ -26,7 +26,8 @@
  *                        rtch_scene_occlusion, through rtc_scene_set_occlusion; its materials' shadow filters,
  *                        rtch_scene_shadow_filters, through rtc_scene_set_shadow_filters; its materials' absorption
  *                        and its atmosphere, rtch_scene_media, through rtc_scene_set_media; its environment,
- *                        rtch_scene_environment, through rtc_scene_set_environment)
+ *                        rtch_scene_environment, through rtc_scene_set_environment; its sky light,
+ *                        rtch_scene_sky_light, through rtc_scene_set_sky_light)
  *
  * Every function that returns int returns 0 on success; otherwise rtch_last_error()
  * holds "<ZigStyleErrorName>: detail" (thread-local).
@@ -121,6 +122,10 @@ int rtch_scene_media(void *handle, double *absorption, double *fog, int *present
  * and n_suns; the suns' rows, as the file has them, go to sun_direction and sun_rgb (room for 3 * RTC_ENV_MAX_SUNS doubles
  * each), which *out then points to.  *present: 1 when the file has the key.  rtch_scene_render applies it. */
 int rtch_scene_environment(void *handle, rtc_environment *out, double *sun_direction, double *sun_rgb, int *present);
+/* The environment's "light" (DESIGN.md section 25): g, or {"gain": g, "samples": n, "seed": s} - gain defaults to 1.0,
+ * samples to 1, seed to 0 -, as rtc_scene_set_sky_light takes it.  *present: 1 when the file has the key; without it *out is
+ * gain 0, samples 1, seed 0.  The key adds no table row.  rtch_scene_render applies it. */
+int rtch_scene_sky_light(void *handle, rtc_sky_light *out, int *present);
 int rtch_scene_camera(void *handle, uint32_t width, uint32_t height, rtc_camera *out);
 int rtch_camera_rotate(void *handle, double angle);
 int rtch_camera_move(void *handle, double distance);

@@ -101,6 +101,13 @@ pub const RtcEnvironment = extern struct {
     sun_rgb: ?[*]const f64, // [n_suns][3]
 };
 pub extern fn rtc_scene_set_environment(scene: *RtcScene, environment: ?*const RtcEnvironment) c_int; // null: no environment
+// The sky light (rtc.h, rtc_scene_set_sky_light): `samples` hemisphere rays per diffuse hit gather the environment's sky.
+pub const RtcSkyLight = extern struct {
+    gain: f64, // finite, >= 0; 0: no sky light
+    samples: u32, // 1 .. 64
+    seed: u64,
+};
+pub extern fn rtc_scene_set_sky_light(scene: *RtcScene, sky_light: ?*const RtcSkyLight) c_int; // null: no sky light
 pub extern fn rtc_grow_csg_lists(scene: *RtcScene) c_int; // after an asynchronous frame whose stats.overflow != 0 on a csg scene: longer lists, render again
 pub extern fn rtc_scatter_tile_list_device(d_tiles: [*]const f64, d_tile_list: [*]const u32, n_tiles: u32, tile_w: u32, tile_h: u32,
                                            hsize: u32, vsize: u32, canvas: [*]f64, hip_stream: ?*anyopaque) c_int; // a rank's tiles straight into a (registered host) canvas

@@ -221,7 +221,8 @@ BUMP_NONE, BUMP_NOISE, BUMP_RIPPLES = 0, 1, 2  # RTC_BUMP_*
 RTC_SPHERE, RTC_PLANE, RTC_CUBE, RTC_CYLINDER, RTC_TRIANGLE, RTC_SMOOTH_TRIANGLE, RTC_CONE, RTC_TORUS = range(8)
 # the options that select a kernel family on a handle that does not need it (set_option; tests and tools/time_scenes.py)
 KERNEL_OPTIONS = ("sampling_kernels", "motion_kernels", "spot_kernels", "bump_kernels", "torus_kernels", "meshuv_kernels", "gloss_kernels",
-                  "occlusion_kernels", "shadow_filter_kernels", "media_kernels", "environment_kernels")
+                  "occlusion_kernels", "shadow_filter_kernels", "media_kernels", "environment_kernels", "sky_light_kernels")
+SKY_LIGHT_MAX_SAMPLES = 64  # RTC_SKY_LIGHT_MAX_SAMPLES
 ENV_NO_PATTERN, ENV_SPHERE, ENV_CUBE, ENV_MAX_SUNS = 0xFFFFFFFF, 0, 1, 16  # RTC_ENV_*
 NO_MEDIUM = 0xFFFFFFFF  # RTC_NO_MEDIUM: a ray in the atmosphere
 # texture mappings (rtc.h); RTC_TEX_MESH: (u, v) from the hit triangle's texture row
@@ -357,6 +358,17 @@ def environment_struct(env):
     return e, (d, c)
 
 
+class SkyLight(C.Structure):
+    """struct rtc_sky_light (include/rtc.h): the factor on the sky that `samples` hemisphere rays gather at every diffuse hit."""
+
+    _fields_ = [("gain", C.c_double), ("samples", C.c_uint32), ("seed", C.c_uint64)]
+
+
+def sky_light_struct(light):
+    """SkyLight of a dict of "gain" (1.0), "samples" (1) and "seed" (0) (GpuScene.set_sky_light)"""
+    return SkyLight(float(light.get("gain", 1.0)), int(light.get("samples", 1)), int(light.get("seed", 0)))
+
+
 class Bump(C.Structure):
     """struct rtc_bump (include/rtc.h): a bump per material row (kind BUMP_NONE: the material as it is)."""
 
@@ -398,14 +410,15 @@ RTC_SYMBOLS = ["rtc_scene_create", "rtc_scene_clone", "rtc_scene_destroy", "rtc_
                "rtc_scene_set_sample_pass", "rtc_scene_accumulate_device", "rtc_scene_set_motion",
                "rtc_scene_adaptive_begin_device", "rtc_scene_adaptive_accumulate_device", "rtc_scene_adaptive_step", "rtc_render_adaptive",
                "rtc_scene_set_spots", "rtc_scene_set_bumps", "rtc_scene_set_mesh_uvs", "rtc_scene_set_gloss",
-               "rtc_scene_set_occlusion", "rtc_scene_set_shadow_filters", "rtc_scene_set_media", "rtc_scene_set_environment"]
+               "rtc_scene_set_occlusion", "rtc_scene_set_shadow_filters", "rtc_scene_set_media", "rtc_scene_set_environment",
+               "rtc_scene_set_sky_light"]
 # (... and include/rtc_diag.h: diagnostics and tuning, for the tests, bench.py and tools/)
 RTC_DIAG_SYMBOLS = ["rtc_set_option", "rtc_last_kernel_name", "rtc_get_schedule", "rtc_get_chunk_times", "rtc_diag_build_tables", "rtc_diag_root_boxes", "rtc_diag_root_spheres"]
 HOST_SYMBOLS = ["rtch_last_error", "rtch_scene_load", "rtch_scene_free", "rtch_scene_desc", "rtch_scene_camera",
                 "rtch_camera_rotate", "rtch_camera_move", "rtch_camera_make", "rtch_canvas_ppm", "rtch_canvas_rgba8", "rtch_scene_render", "rtch_set_loader_threads",
                 "rtch_scene_lights", "rtch_scene_sampling", "rtch_scene_passes", "rtch_scene_motion", "rtch_scene_adaptive",
                 "rtch_scene_spots", "rtch_scene_bumps", "rtch_scene_mesh_uvs", "rtch_scene_gloss", "rtch_scene_occlusion",
-                "rtch_scene_shadow_filters", "rtch_scene_media", "rtch_scene_environment"]
+                "rtch_scene_shadow_filters", "rtch_scene_media", "rtch_scene_environment", "rtch_scene_sky_light"]
 
 MULTI_SYMBOLS = ["rtc_multi_create", "rtc_multi_destroy", "rtc_multi_render", "rtc_multi_render_rgba8", "rtc_multi_render_device", "rtc_multi_render_rgba8_device",
                  "rtc_multi_synchronize", "rtc_multi_stream", "rtc_multi_get_stats", "rtc_multi_balance", "rtc_multi_last_error"]
@@ -473,6 +486,7 @@ def hip_lib():
         lib.rtc_scene_set_shadow_filters.argtypes = [C.c_void_p, C.POINTER(ShadowFilters)]
         lib.rtc_scene_set_media.argtypes = [C.c_void_p, C.POINTER(Media)]
         lib.rtc_scene_set_environment.argtypes = [C.c_void_p, C.POINTER(Environment)]
+        lib.rtc_scene_set_sky_light.argtypes = [C.c_void_p, C.POINTER(SkyLight)]
         lib.rtc_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.POINTER(Adaptive), C.c_void_p, C.c_void_p]
         lib.rtc_scene_destroy.argtypes = [C.c_void_p]
         lib.rtc_scene_destroy.restype = None
@@ -533,6 +547,7 @@ def host_lib():
         lib.rtch_scene_shadow_filters.argtypes = [C.c_void_p, _dp, C.POINTER(C.c_int), C.c_uint32]
         lib.rtch_scene_media.argtypes = [C.c_void_p, _dp, _dp, C.POINTER(C.c_int), C.c_uint32]
         lib.rtch_scene_environment.argtypes = [C.c_void_p, C.POINTER(Environment), _dp, _dp, C.POINTER(C.c_int)]
+        lib.rtch_scene_sky_light.argtypes = [C.c_void_p, C.POINTER(SkyLight), C.POINTER(C.c_int)]
         lib.rtch_scene_adaptive.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(Adaptive)]
         lib.rtch_scene_camera.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Camera)]
         lib.rtch_camera_rotate.argtypes = [C.c_void_p, C.c_double]
@@ -785,6 +800,16 @@ class HostScene:
         return {"rgb": [float(x) for x in e.rgb], "pattern": int(e.pattern), "projection": int(e.projection),
                 "sun_direction": d[:n].copy(), "sun_rgb": c[:n].copy()}
 
+    def sky_light(self):
+        """The environment's "light" (rtch_scene_sky_light): a dict of "gain", "samples" and "seed" - what
+        GpuScene.set_sky_light takes -, or None when the file has none."""
+        y = SkyLight()
+        present = C.c_int()
+        _check_host(host_lib().rtch_scene_sky_light(self._h, C.byref(y), C.byref(present)))
+        if not present.value:
+            return None
+        return {"gain": float(y.gain), "samples": int(y.samples), "seed": int(y.seed)}
+
     def adaptive(self):
         """The camera's "sampling": {"adaptive": ...} of the scene file (rtch_scene_adaptive): an Adaptive whose max_passes
         is "passes", or None when the file has none."""
@@ -947,6 +972,15 @@ class GpuScene:
             return
         e, _keep = environment_struct(env)
         _check_hip(hip_lib().rtc_scene_set_environment(self._s, C.byref(e)))
+
+    def set_sky_light(self, light):
+        """rtc_scene_set_sky_light: a dict of "gain", "samples" and "seed" (HostScene.sky_light()); None: no sky light - as a
+        gain of zero, the handle's previous kernels."""
+        if light is None:
+            _check_hip(hip_lib().rtc_scene_set_sky_light(self._s, None))
+            return
+        y = sky_light_struct(light)
+        _check_hip(hip_lib().rtc_scene_set_sky_light(self._s, C.byref(y)))
 
     def accumulate_device(self, accum, stream=None):
         """rtc_scene_accumulate_device: an Accum, enqueued on `stream` (None: the handle's own) after this handle's renders."""

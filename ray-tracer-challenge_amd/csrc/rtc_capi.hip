@@ -209,6 +209,22 @@ __global__ void rtc_render_kernel_env_bigworld(const DevScene S, const DevCamera
                                                const DevBumps bumps, const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl,
                                                const DevShadowFilter sfilt, const DevMedia media, const DevEnvironment env);
 }
+// The sky-light kernels (rtc_scene_set_sky_light: hemisphere rays that reach the sky light diffuse surfaces): the environment
+// kernels' tables and fifth quarter, and the gain, the sample count and the hash key (DevSkyLight) as one more argument.
+extern "C" {
+__global__ void rtc_render_kernel_skyl(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                       double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                       const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                       const DevBumps bumps, const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl,
+                                       const DevShadowFilter sfilt, const DevMedia media, const DevEnvironment env,
+                                       const DevSkyLight skyl);
+__global__ void rtc_render_kernel_skyl_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                                double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                                const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                                const DevBumps bumps, const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl,
+                                                const DevShadowFilter sfilt, const DevMedia media, const DevEnvironment env,
+                                                const DevSkyLight skyl);
+}
 // Progressive rendering's accumulation (rtc_accum.hip): the grid's blocks for n pixels (the noise partials it writes, at
 // most) and the enqueue of its kernels.
 uint32_t rtcAccumBlocks(size_t n_pixels, bool wide);
@@ -426,7 +442,7 @@ bool tablesInLds(const rtc_scene* s) {
 // `spot`; the bump kernels those four and DevBumps: `bump` - the torus kernels take the same arguments and travel in `bump` too;
 // the meshuv kernels those five and DevMeshUvs: `meshuv`; the gloss kernels those six and DevGloss: `gloss`;
 // the occlusion kernels those seven and DevOcclusion: `occl`; the shadow-filter kernels those eight and DevShadowFilter: `sfilt`;
-// the media kernels those nine and DevMedia: `media`; the environment kernels those ten and DevEnvironment: `env`)
+// the media kernels those nine and DevMedia: `media`; the environment kernels those ten and DevEnvironment: `env`; the sky-light kernels those eleven and DevSkyLight: `skyl`)
 struct KernelChoice {
   decltype(&rtc_render_kernel) fn;
   const char* name;
@@ -442,6 +458,7 @@ struct KernelChoice {
   decltype(&rtc_render_kernel_sfilter) sfilt = nullptr;
   decltype(&rtc_render_kernel_media) media = nullptr;
   decltype(&rtc_render_kernel_env) env = nullptr;
+  decltype(&rtc_render_kernel_skyl) skyl = nullptr;
   KernelChoice(decltype(&rtc_render_kernel) f, const char* n) : fn(f), name(n) {}
   KernelChoice(decltype(&rtc_render_kernel_area) a, const char* n) : fn(nullptr), name(n), area(a) {}
   KernelChoice(decltype(&rtc_render_kernel_ms) m, const char* n) : fn(nullptr), name(n), ms(m) {}
@@ -455,11 +472,12 @@ struct KernelChoice {
   KernelChoice(decltype(&rtc_render_kernel_sfilter) fk, const char* n) : fn(nullptr), name(n), sfilt(fk) {}
   KernelChoice(decltype(&rtc_render_kernel_media) mk, const char* n) : fn(nullptr), name(n), media(mk) {}
   KernelChoice(decltype(&rtc_render_kernel_env) ek, const char* n) : fn(nullptr), name(n), env(ek) {}
+  KernelChoice(decltype(&rtc_render_kernel_skyl) yk, const char* n) : fn(nullptr), name(n), skyl(yk) {}
   void launch(uint32_t blocks, hipStream_t stream, const rtc_scene* s, const DevScene& dev, const DevCamera& cam, const DevPixelMap& map,
               uint32_t max_depth, double* d_out, DevStats* st_now, DevStats* st_next) const {
     DevSampling smp = s->sampling;  // (the pass's area-light offset, P * N * S: N is the camera's whole image)
     smp.pixel_base = static_cast<unsigned long long>(smp.sample_base) * (static_cast<unsigned long long>(cam.hsize) * cam.vsize);
-    if (motion || spot || bump || meshuv || gloss || occl || sfilt || media || env) {
+    if (motion || spot || bump || meshuv || gloss || occl || sfilt || media || env || skyl) {
       // the handle's root tables with the moving roots' bounds (or the scene's, all displacements zero: the option), and
       // the scene's area rows (or zero rows: a point-only table); the spot kernels also the handle's spot rows (or zero
       // rows, every flag 0: the option)
@@ -475,7 +493,7 @@ struct KernelChoice {
         mo.disp = m->disp.p;
       }
       const DevAreaLights area = s->area_kernel ? s->area : DevAreaLights{s->tab->zero_rows.p, s->area.seed};
-      if (media || env) {  // (the handle's absorption rows and atmosphere, or zero rows and no fog: the option; and the shadow-filter kernels' tables)
+      if (media || env || skyl) {  // (the handle's absorption rows and atmosphere, or zero rows and no fog: the option; and the shadow-filter kernels' tables)
         const DevSpots sp{s->spots ? s->spots->row.p : s->tab->zero_rows.p};
         const DevBumps bp{s->bumps ? s->bumps->row.p : s->tab->zero_bump.p};
         const DevMeshUvs uv{s->mesh_uvs ? s->mesh_uvs->row.p : nullptr};
@@ -491,7 +509,7 @@ struct KernelChoice {
           me.fog_density = m->fog_density;
           for (int c = 0; c < 3; ++c) me.fog_color[c] = m->fog_color[c];
         }
-        if (env) {  // (the handle's sky and suns, or no sky and no sun: the option; and the media kernels' tables)
+        if (env || skyl) {  // (the handle's sky and suns, or no sky and no sun: the option; and the media kernels' tables)
           DevEnvironment ev{{0.0, 0.0, 0.0}, RTC_ENV_NO_PATTERN, RTC_ENV_SPHERE, 0u, 0u, s->tab->zero_rows.p};
           if (const EnvironmentTables* e = s->environment.get()) {
             for (int c = 0; c < 3; ++c) ev.rgb[c] = e->rgb[c];
@@ -503,7 +521,13 @@ struct KernelChoice {
               ev.sun = e->sun.p;
             }
           }
-          hipLaunchKernelGGL(env, dim3(blocks), dim3(256), 0, stream, md, cam, map, max_depth, d_out, st_now, st_next, area, smp, mo, sp, bp, uv, gl, oc, sf, me, ev);
+          if (skyl) {  // (the handle's sky light, or a gain of zero: the option; and the environment kernels' tables)
+            DevSkyLight sl{0.0, 0ull, 1u};
+            if (const SkyLightTable* y = s->sky_light.get()) sl = DevSkyLight{y->gain, y->key, y->samples};
+            hipLaunchKernelGGL(skyl, dim3(blocks), dim3(256), 0, stream, md, cam, map, max_depth, d_out, st_now, st_next, area, smp, mo, sp, bp, uv, gl, oc, sf, me, ev, sl);
+          } else {
+            hipLaunchKernelGGL(env, dim3(blocks), dim3(256), 0, stream, md, cam, map, max_depth, d_out, st_now, st_next, area, smp, mo, sp, bp, uv, gl, oc, sf, me, ev);
+          }
         } else {
           hipLaunchKernelGGL(media, dim3(blocks), dim3(256), 0, stream, md, cam, map, max_depth, d_out, st_now, st_next, area, smp, mo, sp, bp, uv, gl, oc, sf, me);
         }
@@ -592,6 +616,27 @@ bool mediaKernels(const rtc_scene* s) { return s->media != nullptr || rtcOptions
 // The environment kernels run when the handle has a sky or a sun (rtc_scene_set_environment keeps no other table) - whatever
 // else the handle holds: they are the media walk - or, for tests, whenever option "environment_kernels" is set.
 bool environmentKernels(const rtc_scene* s) { return s->environment != nullptr || rtcOptions().environment_kernels != 0.0; }
+// The sky-light kernels run when the handle has a sky light AND an environment with a sky - decided here, launch by launch,
+// so the order of the two setters does not matter, and a sky light without a sky keeps the kernels the handle had - whatever
+// else the handle holds: they are the environment walk - or, for tests, whenever option "sky_light_kernels" is set.
+bool skyLightKernels(const rtc_scene* s) {
+  return (s->sky_light != nullptr && s->environment != nullptr && s->environment->sky) || rtcOptions().sky_light_kernels != 0.0;
+}
+// Their resident work-groups per CU, asked for by the first launch that selects them and not at create: the query loads the
+// unit's code object, and a process none of whose handles has a sky light loads, allocates and runs what it did before the
+// unit existed.  A clone takes its source's answer.
+int skyLightOccupancy(rtc_scene* s) {
+  if (s->skyl_occupancy_known) return RTC_OK;
+  int nb = 0;
+  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_skyl, 256, 0));
+  s->blocks_per_cu_skyl_lds = static_cast<uint32_t>(std::max(nb, 1));
+  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_skyl_bigworld, 256, 0));
+  s->blocks_per_cu_skyl_big = static_cast<uint32_t>(std::max(nb, 1));
+  if (const int v = static_cast<int>(rtcOptions().blocks_per_cu); v >= 1)  // (tuning option)
+    s->blocks_per_cu_skyl_lds = std::min<uint32_t>(s->blocks_per_cu_skyl_lds, v), s->blocks_per_cu_skyl_big = std::min<uint32_t>(s->blocks_per_cu_skyl_big, v);
+  s->skyl_occupancy_known = true;
+  return RTC_OK;
+}
 #define RTC_KERNEL(k) KernelChoice{k, #k}
 // The general kernel at three waves per SIMD (rtc_render_kernel3): forced by option "waves3", else what the handle's
 // trial measured (KernelTune in launch()).
@@ -618,6 +663,7 @@ KernelChoice ldsKernel(const rtc_scene* s, const DevPixelMap& map) {
   return s->ext_kernel ? RTC_KERNEL(rtc_render_kernel_ext) : RTC_KERNEL(rtc_render_kernel);
 }
 KernelChoice renderKernel(const rtc_scene* s, const DevPixelMap& map) {
+  if (skyLightKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_skyl) : RTC_KERNEL(rtc_render_kernel_skyl_bigworld);
   if (environmentKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_env) : RTC_KERNEL(rtc_render_kernel_env_bigworld);
   if (mediaKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_media) : RTC_KERNEL(rtc_render_kernel_media_bigworld);
   if (shadowFilterKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_sfilter) : RTC_KERNEL(rtc_render_kernel_sfilter_bigworld);
@@ -640,6 +686,7 @@ KernelChoice renderKernel(const rtc_scene* s, const DevPixelMap& map) {
 
 // Work-groups of the launch's kernel that are resident at once, and the waves in them.
 uint32_t residentBlocksAlone(const rtc_scene* s, const DevPixelMap& map) {
+  if (skyLightKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_skyl_lds : s->blocks_per_cu_skyl_big);
   if (environmentKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_env_lds : s->blocks_per_cu_env_big);
   if (mediaKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_media_lds : s->blocks_per_cu_media_big);
   if (shadowFilterKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_sfilt_lds : s->blocks_per_cu_sfilt_big);
@@ -927,7 +974,7 @@ int ensureScratch(rtc_scene* s, DevPixelMap& map, uint32_t blocks, uint32_t max_
     HIP_TRY(hipMalloc(&s->d_ray_stack, need));
     s->ray_stack_capacity = need;
   }
-  if (mediaKernels(s) || environmentKernels(s)) {  // (the environment kernels are the media walk)
+  if (mediaKernels(s) || environmentKernels(s) || skyLightKernels(s)) {  // (the environment and sky-light kernels are the media walk)
     // (the media kernels' fifth quarter of every pending ray, 16 bytes beside the record's 64: a quarter of the ray stack's
     // capacity holds a slot for every slot of it, whatever the launch's depth)
     const size_t need_x = s->ray_stack_capacity / 4u;
@@ -1015,6 +1062,8 @@ int launch(rtc_scene* s, const rtc_camera& cam, const DevPixelMap& map_in, uint3
     return fail(RTC_ERR_INVALID_ARGUMENT, "max_depth %u exceeds the per-lane ray stack (%d)", max_depth, RTC_MAX_DEPTH);
   if (map.n_chunks == 0) return fail(RTC_ERR_INVALID_ARGUMENT, "nothing to render");
   HIP_TRY(hipSetDevice(s->device));
+  if (skyLightKernels(s))
+    if (const int st = skyLightOccupancy(s); st != RTC_OK) return st;
   // Launches on one handle share its counters, work counter, pending-ray stacks, csg lists and schedule buffers, and
   // launch N + 1 clears the counters of launch N + 2: they must run one after the other.  Stream order gives that on
   // one stream; when the caller changes streams (rtc_render_device on its own stream, then rtc_render on the handle's),
@@ -1067,7 +1116,7 @@ int launch(rtc_scene* s, const rtc_camera& cam, const DevPixelMap& map_in, uint3
   int trial_slot = -1;
   {
     rtc_scene::KernelTune& T = s->tune;
-    const bool eligible = !samplingKernels(s) && !motionKernels(s) && !spotKernels(s) && !bumpKernels(s) && !torusKernels(s) && !meshuvKernels(s) && !glossKernels(s) && !occlusionKernels(s) && !shadowFilterKernels(s) && !mediaKernels(s) && !environmentKernels(s) &&  // (the sampling, motion, spot, bump, torus, meshuv, gloss, occlusion, shadow-filter, media and environment kernels have no three-wave form)
+    const bool eligible = !samplingKernels(s) && !motionKernels(s) && !spotKernels(s) && !bumpKernels(s) && !torusKernels(s) && !meshuvKernels(s) && !glossKernels(s) && !occlusionKernels(s) && !shadowFilterKernels(s) && !mediaKernels(s) && !environmentKernels(s) && !skyLightKernels(s) &&  // (the sampling, motion, spot, bump, torus, meshuv, gloss, occlusion, shadow-filter, media, environment and sky-light kernels have no three-wave form)
                           ((s->general3_ok && rtcOptions().waves3 < 0.0 && tablesInLds(s) &&
                             !(s->tab && s->tab->handles.load(std::memory_order_relaxed) > 1) &&
                             static_cast<double>(map.n_chunks) >= 4.0 * 4.0 * s->n_cus * s->blocks_per_cu_lds) ||
@@ -3257,6 +3306,32 @@ int rtc_scene_set_environment(rtc_scene* s, const rtc_environment* e) {
   return RTC_OK;
 }
 
+// ---- the sky light
+// Validated on the host before any HIP call and before anything changes.  NULL, or a gain of zero, is no sky light.  Whether
+// the sky-light kernels run is decided at launch (skyLightKernels): the table alone, on a handle without a sky, changes nothing.
+int rtc_scene_set_sky_light(rtc_scene* s, const rtc_sky_light* y) {
+  g_error.clear();
+  if (!s) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
+  std::shared_ptr<const SkyLightTable> table;  // (no gain: none)
+  if (y) {
+    if (!std::isfinite(y->gain)) return fail(RTC_ERR_INVALID_ARGUMENT, "sky light: a gain that is not finite");
+    if (y->gain < 0.0) return fail(RTC_ERR_INVALID_ARGUMENT, "sky light: gain %g is negative", y->gain);
+    if (y->samples < 1u || y->samples > RTC_SKY_LIGHT_MAX_SAMPLES)
+      return fail(RTC_ERR_INVALID_ARGUMENT, "sky light: %u samples, 1 to %u", y->samples, RTC_SKY_LIGHT_MAX_SAMPLES);
+    if (y->gain != 0.0) {
+      auto t = std::make_shared<SkyLightTable>();
+      t->gain = y->gain;
+      t->samples = y->samples;
+      t->key = rtc_mix64(y->seed ^ RTC_SKY_LIGHT_SALT);
+      table = std::move(t);
+    }
+  }
+  // (a launch of this handle or of its band clones takes the values at its enqueue: nothing on the device is replaced)
+  s->sky_light = table;
+  for (rtc_scene* b : s->band) b->sky_light = table;  // (the band clones rtc_render renders a large frame with)
+  return RTC_OK;
+}
+
 // ---- adaptive sampling
 // The setting's own fields, and the image's tile count (T < 2^31)
 static int checkAdaptive(const rtc_adaptive* a, uint32_t hsize, uint32_t vsize, uint32_t* n_tiles) {
@@ -3491,6 +3566,10 @@ int rtc_scene_clone(const rtc_scene* src, rtc_scene** out) {
   s->environment = src->environment;  // (shared: read-only once made)
   s->blocks_per_cu_env_lds = src->blocks_per_cu_env_lds;
   s->blocks_per_cu_env_big = src->blocks_per_cu_env_big;
+  s->sky_light = src->sky_light;  // (shared: read-only once made)
+  s->blocks_per_cu_skyl_lds = src->blocks_per_cu_skyl_lds;
+  s->blocks_per_cu_skyl_big = src->blocks_per_cu_skyl_big;
+  s->skyl_occupancy_known = src->skyl_occupancy_known;
   s->simple_kernel = src->simple_kernel;
   s->flat_kernel = src->flat_kernel;
   s->simple3_ok = src->simple3_ok;
@@ -3913,7 +3992,7 @@ int rtc_set_option(const char* name, double value) {
                {"torus_kernels", &o.torus_kernels}, {"meshuv_kernels", &o.meshuv_kernels},
                {"gloss_kernels", &o.gloss_kernels}, {"occlusion_kernels", &o.occlusion_kernels},
                {"shadow_filter_kernels", &o.shadow_filter_kernels}, {"media_kernels", &o.media_kernels},
-               {"environment_kernels", &o.environment_kernels}};
+               {"environment_kernels", &o.environment_kernels}, {"sky_light_kernels", &o.sky_light_kernels}};
   for (const auto& e : table)
     if (std::strcmp(e.name, name) == 0) {
       e.slot->set(value);

@@ -435,6 +435,17 @@ struct DevEnvironment {
   const double* __restrict__ sun;  // [n_suns][RTC_ENV_SUN_ROW]
 };
 
+// A sky light (rtc_scene_set_sky_light): the extra argument of the sky-light kernels only.  `gain`:
+// the factor on the gathered sky (0: the step is not run - a handle without a table, or the "sky_light_kernels" option);
+// `samples`: hemisphere rays per hit, 1 .. RTC_SKY_LIGHT_MAX_SAMPLES; key = rtc_mix64(seed ^ RTC_SKY_LIGHT_SALT); the draws
+// are rtc_gloss_sample_key's and rtc_gloss_jitter's at the occlusion step's word, (k << RTC_OCCLUSION_SAMPLE_SHIFT) | code.
+#define RTC_SKY_LIGHT_SALT 0x082EFA98EC4E6C89ull
+struct DevSkyLight {
+  double gain;
+  unsigned long long key;
+  uint32_t samples;
+};
+
 struct DevCamera {
   double half_width, half_height, pixel_size;
   double inv[12];  // rows 0..2 of Camera._inverse_transform

@@ -76,6 +76,7 @@ struct RtcOptions {
   RtcOption shadow_filter_kernels{0.0};  // != 0: the shadow-filter kernels even on a handle without a filter, every row zero (tests: against the handle's ordinary kernels)
   RtcOption media_kernels{0.0};        // != 0: the media kernels even on a handle without media, every row and the density zero (tests: against the handle's ordinary kernels)
   RtcOption environment_kernels{0.0};  // != 0: the environment kernels even on a handle without an environment, no sky and no sun (tests: against the handle's ordinary kernels)
+  RtcOption sky_light_kernels{0.0};    // != 0: the sky-light kernels even on a handle without a sky light, the gain zero (tests: against the handle's ordinary kernels)
   RtcOption build_threads{0.0};        // threads of rtc_scene_create's candidate-BVH build (one top-level group each); 0: as many as the host allows, up to 8
 };
 inline RtcOptions& rtcOptions() {
@@ -197,6 +198,14 @@ struct EnvironmentTables {
   DevBuf<double> sun;   // [n_suns][RTC_ENV_SUN_ROW]; empty without suns
 };
 
+// A handle's sky light (rtc_scene_set_sky_light): DevSkyLight's values; nothing on the device.  Read-only once made: a clone
+// and the band clones share it.
+struct SkyLightTable {
+  double gain = 0.0;
+  uint32_t samples = 1u;
+  unsigned long long key = 0ull;  // rtc_mix64(seed ^ RTC_SKY_LIGHT_SALT)
+};
+
 // A handle's spot lights (rtc_scene_set_spots): DevSpots::row.  Read-only once made: a clone and the band clones share it.
 struct SpotTables {
   DevBuf<double> row;
@@ -263,6 +272,9 @@ struct rtc_scene {
   uint32_t blocks_per_cu_media_lds = 1, blocks_per_cu_media_big = 1;  // resident work-groups per CU of the media kernels
   std::shared_ptr<const EnvironmentTables> environment;  // rtc_scene_set_environment; null: no sky and no sun (a clone starts with its source's)
   uint32_t blocks_per_cu_env_lds = 1, blocks_per_cu_env_big = 1;  // resident work-groups per CU of the environment kernels
+  std::shared_ptr<const SkyLightTable> sky_light;  // rtc_scene_set_sky_light; null: no gain (a clone starts with its source's)
+  uint32_t blocks_per_cu_skyl_lds = 1, blocks_per_cu_skyl_big = 1;  // resident work-groups per CU of the sky-light kernels ...
+  bool skyl_occupancy_known = false;  // ... asked for by the first launch that selects them (skyLightOccupancy), not at create
   bool simple3_ok = false;         // a simple world whose tables fit the three-waves-per-SIMD kernel's LDS (RTC_LDS3_*)
   void* d_csg_buf = nullptr;       // DevPixelMap::csg_buf, only for scenes with csg nodes
   size_t csg_buf_capacity = 0;     // bytes

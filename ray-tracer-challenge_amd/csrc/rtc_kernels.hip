@@ -3016,9 +3016,13 @@ __device__ __noinline__ GlossDir occl_direction(unsigned long long h, uint32_t w
 // its direction, and every hit is lit by the suns, directional lights whose shadow rays have no far end, in a second loop
 // after World.lights.  With MEDIA and everything below it, compiled into the environment kernels' translation unit only,
 // under RTC_ENV_TU, which implies RTC_MEDIA_TU)
+// (SKYL: a sky light - DevSkyLight, the sky-light kernels' extra argument: every hit of a material with a diffuse term gathers
+// the sky through cosine-weighted hemisphere rays that are walked as a sun's shadow ray is, and the mean is added after the
+// suns' loop.  With ENV and everything below it, compiled into the sky-light kernels' translation unit only, under
+// RTC_SKYL_TU, which implies RTC_ENV_TU)
 template <bool LDS, bool CSG, int WORLD = 0, int WAVES = 2, bool COOP = false, bool BOX = true, bool AREA = false, bool MS = false,
           bool MOTION = false, bool SPOT = false, bool BUMP = false, bool TORUS = false, bool MESHUV = false, bool GLOSS = false,
-          bool OCCL = false, bool SFILT = false, bool MEDIA = false, bool ENV = false>
+          bool OCCL = false, bool SFILT = false, bool MEDIA = false, bool ENV = false, bool SKYL = false>
 __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& cam, const DevPixelMap& map,
                                             const uint32_t max_depth, double* __restrict__ out,
                                             DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
@@ -3028,7 +3032,8 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
                                             const DevGloss& gloss = DevGloss{}, const DevOcclusion& occl = DevOcclusion{},
                                             const DevShadowFilter& sfilt = DevShadowFilter{},
                                             const DevMedia& media = DevMedia{},
-                                            const DevEnvironment& env = DevEnvironment{}) {
+                                            const DevEnvironment& env = DevEnvironment{},
+                                            const DevSkyLight& skyl = DevSkyLight{}) {
   static_assert(!AREA || !COOP, "the area kernels run no cooperative iterations");
   static_assert(!MS || !COOP, "the sampling kernels run no cooperative iterations");
   static_assert(!MOTION || (MS && AREA && WORLD == 0), "the motion kernels are the general area-sampling walk");
@@ -3082,6 +3087,13 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
 #else
   static_assert(!ENV, "the environment is compiled in the environment translation unit (rtc_environment.hip) only");
   (void)env;
+#endif
+  static_assert(!SKYL || ENV, "the sky-light kernels are the environment walk");
+#ifdef RTC_SKYL_TU
+  static_assert(SKYL, "the sky-light translation unit compiles the sky-light kernels only");
+#else
+  static_assert(!SKYL, "the sky light is compiled in the sky-light translation unit (rtc_skylight.hip) only");
+  (void)skyl;
 #endif
   RTC_PRIO_PHASE(RTC_PRIO_WORK);
 #ifndef RTC_PROFILE
@@ -4321,6 +4333,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
       // - not an any-hit walk, so no early-out that reasons about a segment's far end is compiled in; DESIGN.md section 24
       // lists what was read).  No cone, no area row.  si is wave-uniform: the row is read through the constant address space at a
       // readfirstlane index - scalar loads, as DevSpots' rows are -, and nothing of it is staged in LDS.
+#ifndef RTC_SKYL_TU
       if constexpr (ENV) {
         for (uint32_t si = 0u; si < env.n_suns; ++si) {
           typedef const __attribute__((address_space(4))) double ConstRow;
@@ -4379,6 +4392,120 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
           sb = sb + lb_;
         }
       }
+#else
+      // (SKYL, rtc.h's rtc_scene_set_sky_light) in the sky-light unit the suns' loop goes on after the last sun for the sky
+      // light's samples, so that both kinds of ray without a far end share ONE inlined walk: a second call site of
+      // trace<SunVisitor> made the flag alone cost cover + 27 % and teapot + 19 %.  Whether an iteration
+      // is a sun's or a sample's is wave-uniform; a sun's part is the loop's of the environment unit, statement for statement.
+      // A sample, at a hit of a material with a diffuse term: a direction of the geometric normal's hemisphere - the
+      // occlusion step's rule and word, from this table's key: nx, ny, nz is ng after its inside flip, not the bumped hx,
+      // hy, hz -, walked from over_point as a sun's shadow ray is, so the filter rows multiply and the early-outs are the ones
+      // section 24 read; a direction that is not blocked looks the sky up as a miss does, through the out-of-line
+      // pattern_at_shared.  Across the walk live L and the sample's hash; the mean is added after the last iteration: after
+      // the last sun's term.
+      if constexpr (SKYL) {
+        const uint32_t n_sky = (skyl.gain > 0.0 && env.sky != 0u) ? skyl.samples : 0u;  // (wave-uniform)
+        const bool sky_lane = n_sky != 0u && mat.diffuse != 0.0;
+        unsigned long long skyl_h = 0ull;
+        if (sky_lane) {
+          uint32_t kpx, kpy;
+          map_pixel(map, out_index, kpx, kpy);
+          skyl_h = rtc_gloss_sample_key(skyl.key, static_cast<unsigned long long>(kpy) * cam.hsize + kpx,
+                                        static_cast<unsigned long long>(smp.sample_base) + (*samp_word & RTC_SAMPLE_MASK));
+        }
+        double l_r = 0.0, l_g = 0.0, l_b = 0.0;
+        const uint32_t n_rays = env.n_suns + n_sky;
+        for (uint32_t si = 0u; si < n_rays; ++si) {
+          const bool is_sun = si < env.n_suns;
+          double lvx = 0.0, lvy = 0.0, lvz = 0.0, ir = 0.0, ig = 0.0, ib = 0.0, light_dot_normal = 0.0;
+          bool walk = false;
+          if (is_sun) {
+            typedef const __attribute__((address_space(4))) double ConstRow;
+            ConstRow* U = (ConstRow*)env.sun + static_cast<size_t>(RTC_ENV_SUN_ROW) * __builtin_amdgcn_readfirstlane(si);
+            lvx = U[0], lvy = U[1], lvz = U[2];
+            ir = U[3], ig = U[4], ib = U[5];
+            it_shadow_calls++;
+            light_dot_normal = (lvx * hx + lvy * hy) + lvz * hz;
+            walk = shadow_matters && light_dot_normal >= 0.0;
+          } else if (sky_lane) {
+            const GlossDir sd = occl_direction(skyl_h, ((si - env.n_suns) << RTC_OCCLUSION_SAMPLE_SHIFT) | cur.code, nx, ny, nz);
+            lvx = sd.x, lvy = sd.y, lvz = sd.z;
+            it_shadow_calls++;
+            walk = true;
+          }
+          bool shadowed = false;
+          RTC_SF_DECL;
+          if (walk) {
+            it_shadow_traced++;
+            it_share++;
+            SunVisitor sv;
+            sv.distance = kInf;
+            RTC_LIGHT_VISITOR_SET(sv);
+            Ray sray{ovx, ovy, ovz, lvx, lvy, lvz};
+            trace<CSG, WORLD, SunVisitor, TRAV, BOX, MOTION, ROOTS>(S, recs, cull, sray, sv, it_overflow, trav_stack, member, stride, mo.disp, tm);
+            shadowed = RTC_LIGHT_BLOCKED(sv);
+            RTC_SF_TAKE(sv);
+          }
+          if (is_sun) {
+            // Material.lighting (material.zig:40-74) with the sun's intensity
+            const double er = color.r * ir, eg = color.g * ig, eb = color.b * ib;  // effective_color
+            const double ka = RTC_KA(mat);
+            double lr_ = er * ka, lg_ = eg * ka, lb_ = eb * ka;
+            if (!shadowed) {
+              double dr = 0.0, dg = 0.0, db = 0.0, pr = 0.0, pg = 0.0, pb = 0.0;
+              if (light_dot_normal >= 0.0) {
+                const double kd = mat.diffuse * light_dot_normal;
+                dr = er * kd;
+                dg = eg * kd;
+                db = eb * kd;
+                const double two_dot = 2.0 * light_dot_normal;  // point_to_light.reflect(normal)
+                const double rx = lvx - hx * two_dot, ry = lvy - hy * two_dot, rz = lvz - hz * two_dot;
+                const double reflect_dot_eye = ((-rx) * ex + (-ry) * ey) + (-rz) * ez;
+                if (reflect_dot_eye > 0.0) {
+                  const uint32_t n = mat.shininess_int;
+                  bool ks_is_specular = false;
+                  if (mat.specular == 0.0) ks_is_specular = n != 0u && reflect_dot_eye <= 1.0;
+                  double ks = mat.specular;
+                  if (!(kSpecularSkip && ks_is_specular))
+                    ks = mat.specular * (n != 0u && reflect_dot_eye < kInf ? pow_small_int(reflect_dot_eye, n)
+                                                                           : zig_pow(reflect_dot_eye, mat.shininess));
+                  pr = ir * ks;
+                  pg = ig * ks;
+                  pb = ib * ks;
+                }
+              }
+              lr_ = (lr_ + RTC_SF(dr, r)) + RTC_SF(pr, r);
+              lg_ = (lg_ + RTC_SF(dg, g)) + RTC_SF(pg, g);
+              lb_ = (lb_ + RTC_SF(db, b)) + RTC_SF(pb, b);
+            }
+            sr = sr + lr_;
+            sg = sg + lg_;
+            sb = sb + lb_;
+          } else if (walk && !shadowed) {
+            double e_r = env.rgb[0], e_g = env.rgb[1], e_b = env.rgb[2];
+            if (env.pattern != RTC_ENV_NO_PATTERN) {
+              const double len = env.projection == RTC_ENV_CUBE
+                                     ? __builtin_fmax(__builtin_fabs(lvx), __builtin_fmax(__builtin_fabs(lvy), __builtin_fabs(lvz)))
+                                     : __builtin_sqrt((lvx * lvx + lvy * lvy) + lvz * lvz);
+              const MeshUvHit sky_mh{muv.row, RTC_NO_LEAF, 0.0, 0.0};
+              const Rgb c = pattern_at_shared(S, pats, env.pattern, lvx / len, lvy / len, lvz / len, sky_mh);
+              e_r = c.r * e_r;
+              e_g = c.g * e_g;
+              e_b = c.b * e_b;
+            }
+            l_r = l_r + RTC_SF(e_r, r);
+            l_g = l_g + RTC_SF(e_g, g);
+            l_b = l_b + RTC_SF(e_b, b);
+          }
+        }
+        if (sky_lane) {
+          const double n_mean = static_cast<double>(skyl.samples);
+          sr = sr + (color.r * mat.diffuse) * (skyl.gain * (l_r / n_mean));
+          sg = sg + (color.g * mat.diffuse) * (skyl.gain * (l_g / n_mean));
+          sb = sb + (color.b * mat.diffuse) * (skyl.gain * (l_b / n_mean));
+        }
+      }
+#endif
 #endif
       if constexpr (COOP) {
         if (deal_lights) {  // the other half's light (lane i <-> 7 - i pairs the halves), and what it counted
@@ -4649,7 +4776,8 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
 // with RTC_GLOSS_TU (and, with it, both of those) and the gloss kernels, rtc_occlusion.hip with RTC_OCCL_TU (and, with it, those
 // three) and the occlusion kernels, rtc_shadowfilter.hip with RTC_SFILT_TU (and, with it, those four) and the shadow-filter
 // kernels, rtc_media.hip with RTC_MEDIA_TU (and, with it, those five) and the media kernels, rtc_environment.hip with
-// RTC_ENV_TU (and, with it, those six) and the environment kernels.  rtc_kernels_ext.hip
+// RTC_ENV_TU (and, with it, those six) and the environment kernels, rtc_skylight.hip with RTC_SKYL_TU (and, with it, those
+// seven) and the sky-light kernels.  rtc_kernels_ext.hip
 // includes it with RTC_EXT_TU defined: in the -DRTC_PROFILE diagnostic build, whose instrumented walk makes this unit's
 // compile about a third longer, it gets the csg / texture-map, flat and area-light kernels (rtc_render_kernel_ext to
 // rtc_render_kernel_area_bigworld below), so that neither unit takes the time of all of them.  The product build keeps
@@ -5522,6 +5650,31 @@ rtc_render_kernel_bump_bigworld(const DevScene S, const DevCamera cam, const Dev
                                                                             spots, bumps);
 }
 
+#elif defined(RTC_SKYL_TU)
+
+// A sky light (rtc_scene_set_sky_light): the environment walk with the hemisphere rays that gather the
+// sky at every diffuse hit, and the gain, the sample count and the hash key (DevSkyLight) as one more argument; one pair for
+// every world.  Every other kernel is compiled without it.
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_skyl(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                       double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                       const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots, const DevBumps bumps,
+                       const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl, const DevShadowFilter sfilt,
+                       const DevMedia media, const DevEnvironment env, const DevSkyLight skyl) {
+  render_body<true, true, 0, 2, false, true, true, true, true, true, true, true, true, true, true, true, true, true, true>(
+      S, cam, map, max_depth, out, stats, next_stats, area, smp, mo, spots, bumps, muv, gloss, occl, sfilt, media, env, skyl);
+}
+
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_skyl_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                const DevBumps bumps, const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl,
+                                const DevShadowFilter sfilt, const DevMedia media, const DevEnvironment env, const DevSkyLight skyl) {
+  render_body<false, true, 0, 2, false, true, true, true, true, true, true, true, true, true, true, true, true, true, true>(
+      S, cam, map, max_depth, out, stats, next_stats, area, smp, mo, spots, bumps, muv, gloss, occl, sfilt, media, env, skyl);
+}
+
 #elif defined(RTC_ENV_TU)
 
 // An environment (rtc_scene_set_environment): the media walk with a sky where a ray misses and the
@@ -5690,4 +5843,4 @@ rtc_render_kernel_torus_bigworld(const DevScene S, const DevCamera cam, const De
                                                                                   smp, mo, spots, bumps);
 }
 
-#endif  // RTC_MOTION_TU / RTC_SPOT_TU / RTC_BUMP_TU / RTC_ENV_TU / RTC_MEDIA_TU / RTC_SFILT_TU / RTC_OCCL_TU / RTC_GLOSS_TU / RTC_MESHUV_TU / RTC_TORUS_TU
+#endif  // RTC_MOTION_TU / RTC_SPOT_TU / RTC_BUMP_TU / RTC_SKYL_TU / RTC_ENV_TU / RTC_MEDIA_TU / RTC_SFILT_TU / RTC_OCCL_TU / RTC_GLOSS_TU / RTC_MESHUV_TU / RTC_TORUS_TU

@@ -218,6 +218,19 @@ int rtch_scene_environment(void* h, rtc_environment* out, double* sun_direction,
   });
 }
 
+// The environment's "light"  as rtc_scene_set_sky_light takes it; *present: the file has the key.
+int rtch_scene_sky_light(void* h, rtc_sky_light* out, int* present) {
+  return guarded([&] {
+    const HostScene* hs = static_cast<HostScene*>(h);
+    if (!out) throw rtc::Error("InvalidArgument", "sky light: null argument");
+    std::memset(out, 0, sizeof(*out));
+    out->gain = hs->info.sky_light_gain;
+    out->samples = hs->info.sky_light_samples;
+    out->seed = hs->info.sky_light_seed;
+    if (present) *present = hs->info.sky_light_present ? 1 : 0;
+  });
+}
+
 // The triangles' texture rows (RTC_TEX_MESH), in tri_* order, as rtc_scene_set_mesh_uvs takes them.
 int rtch_scene_mesh_uvs(void* h, double* uv, uint32_t n) {
   return guarded([&] {
@@ -361,6 +374,10 @@ int rtch_scene_render(void* h, uint32_t width, uint32_t height, uint32_t max_dep
                                  hs->info.sun_direction.data(),
                                  hs->info.sun_intensity.data()};
         st = rtc_scene_set_environment(scene, &ev);
+      }
+      if (st == RTC_OK && hs->info.sky_light_present) {  // (the sky light; a gain of zero: the handle as it is)
+        const rtc_sky_light sl{hs->info.sky_light_gain, hs->info.sky_light_samples, hs->info.sky_light_seed};
+        st = rtc_scene_set_sky_light(scene, &sl);
       }
       const rtc::CameraSampling& cs = hs->info.sampling;
       if (cs.adaptive && st == RTC_OK) {  // (adaptive sampling: each tile's mean after its own passes, section 15)

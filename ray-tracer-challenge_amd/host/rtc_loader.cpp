@@ -839,8 +839,8 @@ SceneInfo parseScene(const std::string& scene_json, const FileLoader& load_file_
   // "environment" (not in the reference): the sky behind the world and the suns that light it
   if (const Value* env = root.find("environment")) {
     requireObject(*env, "environment");
-    checkFields(*env, {"color", "pattern", "projection", "suns"}, "environment");
-    if (env->obj.empty()) throw Error("MissingField", "environment: one of color, pattern, projection, suns");
+    checkFields(*env, {"color", "pattern", "projection", "suns", "light"}, "environment");
+    if (env->obj.empty()) throw Error("MissingField", "environment: one of color, pattern, projection, suns, light");
     info.environment_present = true;
     // (three finite numbers >= 0)
     auto vec3 = [](const Value& v, const char* what, double out[3]) {
@@ -885,6 +885,33 @@ SceneInfo parseScene(const std::string& scene_json, const FileLoader& load_file_
         info.sun_direction.insert(info.sun_direction.end(), d, d + 3);
         info.sun_intensity.insert(info.sun_intensity.end(), c, c + 3);
       }
+    }
+    // "light" (DESIGN.md section 25): the sky lights diffuse surfaces - a gain, or {"gain", "samples", "seed"}; no table row
+    if (const Value* light = env->find("light")) {
+      auto gainOf = [](const Value& v) {
+        if (v.type != Value::Number) throw Error("InvalidData", "environment: light: gain is a number");
+        if (!(std::isfinite(v.num) && v.num >= 0.0)) throw Error("InvalidData", "environment: light: gain is a finite number >= 0");
+        return v.num;
+      };
+      // (a whole number in [lo, hi])
+      auto wholeOf = [](const Value& v, const std::string& what, double lo, double hi) {
+        if (v.type != Value::Number || !(v.num >= lo && v.num <= hi) || v.num != std::floor(v.num))
+          throw Error("InvalidData", std::string("environment: light: ") + what);
+        return v.num;
+      };
+      info.sky_light_present = true;
+      info.sky_light_gain = 1.0;
+      if (light->type == Value::Object) {
+        checkFields(*light, {"gain", "samples", "seed"}, "light");
+        if (const Value* g = light->find("gain")) info.sky_light_gain = gainOf(*g);
+        if (const Value* n = light->find("samples"))
+          info.sky_light_samples = static_cast<uint32_t>(wholeOf(*n, "samples is a whole number from 1 to " + std::to_string(RTC_SKY_LIGHT_MAX_SAMPLES), 1.0, RTC_SKY_LIGHT_MAX_SAMPLES));
+        if (const Value* sd = light->find("seed")) info.sky_light_seed = static_cast<uint64_t>(wholeOf(*sd, "seed is a whole number from 0 to 2^53", 0.0, 0x1p53));
+      } else {
+        info.sky_light_gain = gainOf(*light);
+      }
+      const bool has_sky = info.env_pattern.has_value() || info.env_color[0] != 0.0 || info.env_color[1] != 0.0 || info.env_color[2] != 0.0;
+      if (!has_sky) throw Error("InvalidData", "environment: light in an environment that has no sky (no pattern and a colour of zero)");
     }
   }
   info.camera.saved_from = from;

@@ -61,6 +61,11 @@ struct SceneInfo {  // scene.zig:608-610
   uint32_t env_projection = 0u;            // RTC_ENV_SPHERE / RTC_ENV_CUBE
   std::vector<double> sun_direction;       // [suns][3], as the file has them
   std::vector<double> sun_intensity;       // [suns][3]
+  // the environment's "light" (section 25): rtc_sky_light's values; gain 0 without the key
+  bool sky_light_present = false;
+  double sky_light_gain = 0.0;
+  uint32_t sky_light_samples = 1u;
+  uint64_t sky_light_seed = 0u;
 };
 
 // scene.zig:612-661.  Throws rtc::Error whose .name is the Zig error name

@@ -63,6 +63,10 @@ media kernels without media.  With --passes the noise run has the same table.
 the same row, as the same file's is, and its suns (rtc_scene_set_environment) - instead of the timed
 scene file's own, which is applied otherwise; --environment off applies none.  Option environment_kernels=1 times the
 environment kernels without an environment.  With --passes the noise run has the same table.
+--sky-light GAIN[:SAMPLES]: a sky light of that gain and 1 (or SAMPLES) hemisphere rays per diffuse hit (rtc_scene_set_sky_light;
+DESIGN.md section 25) instead of the scene file's own "light", which is applied otherwise; it lights only a scene whose
+environment has a sky; --sky-light off applies none.  Option sky_light_kernels=1 times the sky-light kernels without a sky light.
+With --passes the noise run has the same table.
 --data-dir DIR: where a scene named by its path finds the images and OBJ files it names (default: the scene's directory).
 --adaptive threshold[,min,tile]: adaptive sampling at up to --max-passes (64) passes, min passes 4 and
 16 x 16 tiles by default, with the --sampling of the frames: prints the rounds and tile-passes of a run against
@@ -109,6 +113,7 @@ ap.add_argument("--occlusion-samples", type=int, default=0)
 ap.add_argument("--shadow-filter", action="append", default=[])
 ap.add_argument("--media", action="append", default=[])
 ap.add_argument("--environment", default="")
+ap.add_argument("--sky-light", default="")
 ap.add_argument("--data-dir", default="")  # where a scene named by path finds its images and OBJ files (default: beside it)
 ap.add_argument("--torus", action="store_true")
 ap.add_argument("--meshuv", action="store_true")
@@ -203,6 +208,16 @@ def environment_table(hs):
             raise SystemExit("--environment: the file's sky pattern is no row of the timed scene's tables")
         return env
     return hs.environment()
+
+
+def sky_light_table(hs):
+    """the scene file's sky light, or --sky-light's; None: no table (--sky-light off, or nothing to set)"""
+    if args.sky_light == "off":
+        return None
+    if args.sky_light:
+        gain, _, samples = args.sky_light.partition(":")
+        return {"gain": float(gain), "samples": int(samples or 1), "seed": 0}
+    return hs.sky_light()
 
 
 def light_table(hs, how):
@@ -413,6 +428,9 @@ for name, w, h, depth in cases:
         environment = environment_table(hs)
         if environment is not None:
             gpu.set_environment(environment)
+        sky_light = sky_light_table(hs)
+        if sky_light is not None:
+            gpu.set_sky_light(sky_light)
         for i in range(args.settle):
             gpu.render_device(cam, canvas.data_ptr(), depth, None, stream.cuda_stream)
         torch.cuda.synchronize()
@@ -437,7 +455,7 @@ for name, w, h, depth in cases:
     if delta is not None: line += f" maxdelta {delta:.2e}"
     if args.lights or args.spot or "spot_kernels=1" in args.option:
         line += f" shadow_traced {st['shadow_traced']} ns/shadow-ray {min(ts) * 1e6 / max(1, st['shadow_traced']):.3f}"
-    if args.sampling or args.option or args.passes >= 0 or args.motion or args.spot or args.bump or args.torus or args.meshuv or args.gloss or args.occlusion or args.shadow_filter or args.media or args.environment:
+    if args.sampling or args.option or args.passes >= 0 or args.motion or args.spot or args.bump or args.torus or args.meshuv or args.gloss or args.occlusion or args.shadow_filter or args.media or args.environment or args.sky_light:
         line += f" primary {st['primary']} ns/primary-ray {min(ts) * 1e6 / max(1, st['primary']):.3f}"
     if acc:
         ms, copy_ms, nbytes = min(a[0] for a in acc), min(a[1] for a in acc), acc[0][2]
@@ -454,6 +472,7 @@ for name, w, h, depth in cases:
         if shadow_filter_table(hs) is not None: gpu.set_shadow_filters(shadow_filter_table(hs))
         if media_table(hs) is not None: gpu.set_media(media_table(hs))
         if environment_table(hs) is not None: gpu.set_environment(environment_table(hs))
+        if sky_light_table(hs) is not None: gpu.set_sky_light(sky_light_table(hs))
         prog = rtc.Progressive(gpu, cam, depth)
         noise = {}
         for i in range(1, 65):
