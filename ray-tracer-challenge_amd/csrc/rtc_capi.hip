@@ -437,207 +437,198 @@ bool tablesInLds(const rtc_scene* s) {
          s->dev.n_patterns <= RTC_LDS_PATTERNS && s->dev.n_lights <= RTC_LDS_LIGHTS;
 }
 
-// (the area kernels take one more argument, DevAreaLights: `area` instead of `fn`; the sampling kernels DevSampling:
-// `ms`, and both: `area_ms`; the motion kernels both and DevMotion: `motion`; the spot kernels those three and DevSpots:
-// `spot`; the bump kernels those four and DevBumps: `bump` - the torus kernels take the same arguments and travel in `bump` too;
-// the meshuv kernels those five and DevMeshUvs: `meshuv`; the gloss kernels those six and DevGloss: `gloss`;
-// the occlusion kernels those seven and DevOcclusion: `occl`; the shadow-filter kernels those eight and DevShadowFilter: `sfilt`;
-// the media kernels those nine and DevMedia: `media`; the environment kernels those ten and DevEnvironment: `env`; the sky-light kernels those eleven and DevSkyLight: `skyl`)
+// The launch family of the handle's next launch (Family, rtc_host_internal.h): the highest one whose condition holds.
+// Decided launch by launch: an option takes effect on the next launch of an existing handle and goes away when it is
+// cleared, and a clone or a band clone, which holds its source's tables and flags, selects what its source does.
+Family family(const rtc_scene* s) {
+  const RtcOptions& o = rtcOptions();
+  // The sky-light kernels run when the handle has a sky light AND an environment with a sky - decided here, launch by launch,
+  // so the order of the two setters does not matter, and a sky light without a sky keeps the kernels the handle had - whatever
+  // else the handle holds: they are the environment walk - or, for tests, whenever option "sky_light_kernels" is set.
+  if ((s->sky_light != nullptr && s->environment != nullptr && s->environment->sky) || o.sky_light_kernels != 0.0) return Family::SKYL;
+  // The environment kernels run when the handle has a sky or a sun (rtc_scene_set_environment keeps no other table) - whatever
+  // else the handle holds: they are the media walk - or, for tests, whenever option "environment_kernels" is set.
+  if (s->environment != nullptr || o.environment_kernels != 0.0) return Family::ENV;
+  // The media kernels run when the handle has an absorbing row or a fog (rtc_scene_set_media keeps no other table) - whatever
+  // else the handle holds: they are the shadow-filter walk - or, for tests, whenever option "media_kernels" is set.
+  if (s->media != nullptr || o.media_kernels != 0.0) return Family::MEDIA;
+  // The shadow-filter kernels run when a row of the handle's filter table is non-zero (rtc_scene_set_shadow_filters keeps no
+  // other table) - whatever else the handle holds: they are the occlusion walk - or, for tests, whenever option
+  // "shadow_filter_kernels" is set.
+  if (s->shadow_filters != nullptr || o.shadow_filter_kernels != 0.0) return Family::SFILT;
+  // The occlusion kernels run when a row of the handle's radius table is non-zero (rtc_scene_set_occlusion keeps no other
+  // table) - whatever else the handle holds: they are the gloss walk - or, for tests, whenever option "occlusion_kernels" is set.
+  if (s->occlusion != nullptr || o.occlusion_kernels != 0.0) return Family::OCCL;
+  // The gloss kernels run when a row of the handle's roughness table is non-zero (rtc_scene_set_gloss keeps no other table)
+  // - whatever else the handle holds: they are the meshuv walk - or, for tests, whenever option "gloss_kernels" is set.
+  if (s->gloss != nullptr || o.gloss_kernels != 0.0) return Family::GLOSS;
+  // The meshuv kernels run when a texture map of the handle's scene has mapping RTC_TEX_MESH - whatever else the handle
+  // holds, tori included: no other kernel knows mapping 4 - or, for tests, whenever option "meshuv_kernels" is set.
+  if (s->has_mesh_map || o.meshuv_kernels != 0.0) return Family::MESHUV;
+  // The torus kernels run when a leaf of the handle's world is a torus - whatever the sampling, the pass, the motion, the
+  // cones and the bumps: no other kernel knows kind 7 - or, for tests, whenever option "torus_kernels" is set.
+  if (s->has_torus || o.torus_kernels != 0.0) return Family::TORUS;
+  // The bump kernels run when a material of the handle has a bump - whatever the sampling, the pass, the motion and the
+  // cones - or, for tests, whenever option "bump_kernels" is set.
+  if (s->bumps != nullptr || o.bump_kernels != 0.0) return Family::BUMP;
+  // The spot kernels run when a light of the handle has a cone - whatever the sampling, the pass and the motion - or, for
+  // tests, whenever option "spot_kernels" is set.
+  if (s->spots != nullptr || o.spot_kernels != 0.0) return Family::SPOT;
+  // The motion kernels run when a displacement of the handle is not zero - whatever the sampling and the pass: the image
+  // depends on the shutter time - or, for tests, whenever option "motion_kernels" is set.
+  if (s->motion != nullptr || o.motion_kernels != 0.0) return Family::MOTION;
+  // The sampling kernels run when the handle's sampling is not the default (one centred ray per pixel, no lens), or its
+  // sample pass is not 0 - or, for tests, whenever option "sampling_kernels" is set.  Otherwise the kernels run exactly as before.
+  if (s->sampling_on || s->sample_pass != 0u || o.sampling_kernels != 0.0) return Family::MS;
+  return Family::BASE;  // (the world's own kernel: ldsKernel / the big-world kernel, or an area world's pair)
+}
+
+// What a launch runs: the family, whether the tables are in LDS (else the family's _bigworld kernel), the kernel's name
+// (static storage: rtc_last_kernel_name) and, for the BASE family of a world without area lights, the kernel itself - every
+// other kernel is named in forFamilyKernel.
 struct KernelChoice {
+  Family family;
+  bool lds;
   decltype(&rtc_render_kernel) fn;
   const char* name;
-  decltype(&rtc_render_kernel_area) area = nullptr;
-  decltype(&rtc_render_kernel_ms) ms = nullptr;
-  decltype(&rtc_render_kernel_area_ms) area_ms = nullptr;
-  decltype(&rtc_render_kernel_motion) motion = nullptr;
-  decltype(&rtc_render_kernel_spot) spot = nullptr;
-  decltype(&rtc_render_kernel_bump) bump = nullptr;
-  decltype(&rtc_render_kernel_meshuv) meshuv = nullptr;
-  decltype(&rtc_render_kernel_gloss) gloss = nullptr;
-  decltype(&rtc_render_kernel_occl) occl = nullptr;
-  decltype(&rtc_render_kernel_sfilter) sfilt = nullptr;
-  decltype(&rtc_render_kernel_media) media = nullptr;
-  decltype(&rtc_render_kernel_env) env = nullptr;
-  decltype(&rtc_render_kernel_skyl) skyl = nullptr;
-  KernelChoice(decltype(&rtc_render_kernel) f, const char* n) : fn(f), name(n) {}
-  KernelChoice(decltype(&rtc_render_kernel_area) a, const char* n) : fn(nullptr), name(n), area(a) {}
-  KernelChoice(decltype(&rtc_render_kernel_ms) m, const char* n) : fn(nullptr), name(n), ms(m) {}
-  KernelChoice(decltype(&rtc_render_kernel_area_ms) am, const char* n) : fn(nullptr), name(n), area_ms(am) {}
-  KernelChoice(decltype(&rtc_render_kernel_motion) mo, const char* n) : fn(nullptr), name(n), motion(mo) {}
-  KernelChoice(decltype(&rtc_render_kernel_spot) sk, const char* n) : fn(nullptr), name(n), spot(sk) {}
-  KernelChoice(decltype(&rtc_render_kernel_bump) bk, const char* n) : fn(nullptr), name(n), bump(bk) {}
-  KernelChoice(decltype(&rtc_render_kernel_meshuv) uk, const char* n) : fn(nullptr), name(n), meshuv(uk) {}
-  KernelChoice(decltype(&rtc_render_kernel_gloss) gk, const char* n) : fn(nullptr), name(n), gloss(gk) {}
-  KernelChoice(decltype(&rtc_render_kernel_occl) ok, const char* n) : fn(nullptr), name(n), occl(ok) {}
-  KernelChoice(decltype(&rtc_render_kernel_sfilter) fk, const char* n) : fn(nullptr), name(n), sfilt(fk) {}
-  KernelChoice(decltype(&rtc_render_kernel_media) mk, const char* n) : fn(nullptr), name(n), media(mk) {}
-  KernelChoice(decltype(&rtc_render_kernel_env) ek, const char* n) : fn(nullptr), name(n), env(ek) {}
-  KernelChoice(decltype(&rtc_render_kernel_skyl) yk, const char* n) : fn(nullptr), name(n), skyl(yk) {}
-  void launch(uint32_t blocks, hipStream_t stream, const rtc_scene* s, const DevScene& dev, const DevCamera& cam, const DevPixelMap& map,
-              uint32_t max_depth, double* d_out, DevStats* st_now, DevStats* st_next) const {
-    DevSampling smp = s->sampling;  // (the pass's area-light offset, P * N * S: N is the camera's whole image)
-    smp.pixel_base = static_cast<unsigned long long>(smp.sample_base) * (static_cast<unsigned long long>(cam.hsize) * cam.vsize);
-    if (motion || spot || bump || meshuv || gloss || occl || sfilt || media || env || skyl) {
-      // the handle's root tables with the moving roots' bounds (or the scene's, all displacements zero: the option), and
-      // the scene's area rows (or zero rows: a point-only table); the spot kernels also the handle's spot rows (or zero
-      // rows, every flag 0: the option)
-      DevScene md = dev;
-      DevMotion mo{s->tab->zero_disp.p};
-      smp.key = rtc_mix64(s->sampling_desc.seed ^ 0x243F6A8885A308D3ull);  // (the time's hash: also under the default sampling)
-      if (const MotionTables* m = s->motion.get()) {
-        md.root_recs = m->root_recs.p;
-        md.root_cull = m->root_cull.p;
-        md.root_box = m->root_box.p;
-        md.cull_cmax = m->cull_cmax;
-        md.cull_bmax = m->cull_bmax;
-        mo.disp = m->disp.p;
-      }
-      const DevAreaLights area = s->area_kernel ? s->area : DevAreaLights{s->tab->zero_rows.p, s->area.seed};
-      if (media || env || skyl) {  // (the handle's absorption rows and atmosphere, or zero rows and no fog: the option; and the shadow-filter kernels' tables)
-        const DevSpots sp{s->spots ? s->spots->row.p : s->tab->zero_rows.p};
-        const DevBumps bp{s->bumps ? s->bumps->row.p : s->tab->zero_bump.p};
-        const DevMeshUvs uv{s->mesh_uvs ? s->mesh_uvs->row.p : nullptr};
-        const DevGloss gl{s->gloss ? s->gloss->row.p : s->tab->zero_bump.p, s->gloss ? s->gloss->key : 0ull};
-        const DevOcclusion oc{s->occlusion ? s->occlusion->row.p : s->tab->zero_bump.p, s->occlusion ? s->occlusion->key : 0ull,
-                              s->occlusion ? s->occlusion->samples : 1u};
-        const DevShadowFilter sf{s->shadow_filters ? s->shadow_filters->row.p : s->tab->zero_bump.p};
-        // (three doubles per material, 3 <= RTC_BUMP_ROW: the zero bump rows serve as zero absorption rows; the fifth
-        // quarter of the pending rays in memory: ensureScratch sized it with the ray stack)
-        DevMedia me{s->tab->zero_bump.p, 0.0, {0.0, 0.0, 0.0}, s->d_media_stack};
-        if (const MediaTables* m = s->media.get()) {
-          me.absorption = m->row.p;
-          me.fog_density = m->fog_density;
-          for (int c = 0; c < 3; ++c) me.fog_color[c] = m->fog_color[c];
-        }
-        if (env || skyl) {  // (the handle's sky and suns, or no sky and no sun: the option; and the media kernels' tables)
-          DevEnvironment ev{{0.0, 0.0, 0.0}, RTC_ENV_NO_PATTERN, RTC_ENV_SPHERE, 0u, 0u, s->tab->zero_rows.p};
-          if (const EnvironmentTables* e = s->environment.get()) {
-            for (int c = 0; c < 3; ++c) ev.rgb[c] = e->rgb[c];
-            ev.pattern = e->pattern;
-            ev.projection = e->projection;
-            ev.sky = e->sky ? 1u : 0u;
-            if (e->n_suns != 0u) {
-              ev.n_suns = e->n_suns;
-              ev.sun = e->sun.p;
-            }
-          }
-          if (skyl) {  // (the handle's sky light, or a gain of zero: the option; and the environment kernels' tables)
-            DevSkyLight sl{0.0, 0ull, 1u};
-            if (const SkyLightTable* y = s->sky_light.get()) sl = DevSkyLight{y->gain, y->key, y->samples};
-            hipLaunchKernelGGL(skyl, dim3(blocks), dim3(256), 0, stream, md, cam, map, max_depth, d_out, st_now, st_next, area, smp, mo, sp, bp, uv, gl, oc, sf, me, ev, sl);
-          } else {
-            hipLaunchKernelGGL(env, dim3(blocks), dim3(256), 0, stream, md, cam, map, max_depth, d_out, st_now, st_next, area, smp, mo, sp, bp, uv, gl, oc, sf, me, ev);
-          }
-        } else {
-          hipLaunchKernelGGL(media, dim3(blocks), dim3(256), 0, stream, md, cam, map, max_depth, d_out, st_now, st_next, area, smp, mo, sp, bp, uv, gl, oc, sf, me);
-        }
-      } else if (sfilt) {  // (the handle's filter rows, or zero rows, every material opaque: the option; and the occlusion kernels' tables)
-        const DevSpots sp{s->spots ? s->spots->row.p : s->tab->zero_rows.p};
-        const DevBumps bp{s->bumps ? s->bumps->row.p : s->tab->zero_bump.p};
-        const DevMeshUvs uv{s->mesh_uvs ? s->mesh_uvs->row.p : nullptr};
-        const DevGloss gl{s->gloss ? s->gloss->row.p : s->tab->zero_bump.p, s->gloss ? s->gloss->key : 0ull};
-        const DevOcclusion oc{s->occlusion ? s->occlusion->row.p : s->tab->zero_bump.p, s->occlusion ? s->occlusion->key : 0ull,
-                              s->occlusion ? s->occlusion->samples : 1u};
-        // (three doubles per material, 3 <= RTC_BUMP_ROW: the zero bump rows serve as zero filter rows)
-        const DevShadowFilter sf{s->shadow_filters ? s->shadow_filters->row.p : s->tab->zero_bump.p};
-        hipLaunchKernelGGL(sfilt, dim3(blocks), dim3(256), 0, stream, md, cam, map, max_depth, d_out, st_now, st_next, area, smp, mo, sp, bp, uv, gl, oc, sf);
-      } else if (occl) {  // (the handle's radius rows, or zero rows, no material occluded: the option; and the gloss kernels' tables)
-        const DevSpots sp{s->spots ? s->spots->row.p : s->tab->zero_rows.p};
-        const DevBumps bp{s->bumps ? s->bumps->row.p : s->tab->zero_bump.p};
-        const DevMeshUvs uv{s->mesh_uvs ? s->mesh_uvs->row.p : nullptr};
-        const DevGloss gl{s->gloss ? s->gloss->row.p : s->tab->zero_bump.p, s->gloss ? s->gloss->key : 0ull};
-        // (one double per material: the zero bump rows serve as zero radius rows)
-        const DevOcclusion oc{s->occlusion ? s->occlusion->row.p : s->tab->zero_bump.p, s->occlusion ? s->occlusion->key : 0ull,
-                              s->occlusion ? s->occlusion->samples : 1u};
-        hipLaunchKernelGGL(occl, dim3(blocks), dim3(256), 0, stream, md, cam, map, max_depth, d_out, st_now, st_next, area, smp, mo, sp, bp, uv, gl, oc);
-      } else if (gloss) {  // (the handle's roughness rows, or zero rows, every material smooth: the option)
-        const DevSpots sp{s->spots ? s->spots->row.p : s->tab->zero_rows.p};
-        const DevBumps bp{s->bumps ? s->bumps->row.p : s->tab->zero_bump.p};
-        const DevMeshUvs uv{s->mesh_uvs ? s->mesh_uvs->row.p : nullptr};
-        // (RTC_GLOSS_ROW <= RTC_BUMP_ROW: the zero bump rows serve as zero roughness rows)
-        const DevGloss gl{s->gloss ? s->gloss->row.p : s->tab->zero_bump.p, s->gloss ? s->gloss->key : 0ull};
-        hipLaunchKernelGGL(gloss, dim3(blocks), dim3(256), 0, stream, md, cam, map, max_depth, d_out, st_now, st_next, area, smp, mo, sp, bp, uv, gl);
-      } else if (meshuv) {  // (the handle's texture rows, or none: every row six zeros)
-        const DevSpots sp{s->spots ? s->spots->row.p : s->tab->zero_rows.p};
-        const DevBumps bp{s->bumps ? s->bumps->row.p : s->tab->zero_bump.p};
-        const DevMeshUvs uv{s->mesh_uvs ? s->mesh_uvs->row.p : nullptr};
-        hipLaunchKernelGGL(meshuv, dim3(blocks), dim3(256), 0, stream, md, cam, map, max_depth, d_out, st_now, st_next, area, smp, mo, sp, bp, uv);
-      } else if (bump) {  // (the handle's bump rows, or zero rows, every kind none: the option)
-        const DevSpots sp{s->spots ? s->spots->row.p : s->tab->zero_rows.p};
-        const DevBumps bp{s->bumps ? s->bumps->row.p : s->tab->zero_bump.p};
-        hipLaunchKernelGGL(bump, dim3(blocks), dim3(256), 0, stream, md, cam, map, max_depth, d_out, st_now, st_next, area, smp, mo, sp, bp);
-      } else if (spot) {
-        const DevSpots sp{s->spots ? s->spots->row.p : s->tab->zero_rows.p};
-        hipLaunchKernelGGL(spot, dim3(blocks), dim3(256), 0, stream, md, cam, map, max_depth, d_out, st_now, st_next, area, smp, mo, sp);
-      } else {
-        hipLaunchKernelGGL(motion, dim3(blocks), dim3(256), 0, stream, md, cam, map, max_depth, d_out, st_now, st_next, area, smp, mo);
-      }
-    } else if (area_ms)
-      hipLaunchKernelGGL(area_ms, dim3(blocks), dim3(256), 0, stream, dev, cam, map, max_depth, d_out, st_now, st_next, s->area, smp);
-    else if (ms)
-      hipLaunchKernelGGL(ms, dim3(blocks), dim3(256), 0, stream, dev, cam, map, max_depth, d_out, st_now, st_next, smp);
-    else if (area)
-      hipLaunchKernelGGL(area, dim3(blocks), dim3(256), 0, stream, dev, cam, map, max_depth, d_out, st_now, st_next, s->area);
-    else
-      hipLaunchKernelGGL(fn, dim3(blocks), dim3(256), 0, stream, dev, cam, map, max_depth, d_out, st_now, st_next);
-  }
 };
-// The sampling kernels run when the handle's sampling is not the default (one centred ray per pixel, no lens), or its
-// sample pass is not 0 - or, for tests, whenever option "sampling_kernels" is set.  Otherwise the kernels run exactly as before.
-bool samplingKernels(const rtc_scene* s) { return s->sampling_on || s->sample_pass != 0u || rtcOptions().sampling_kernels != 0.0; }
-// The motion kernels run when a displacement of the handle is not zero - whatever the sampling and the pass: the image
-// depends on the shutter time - or, for tests, whenever option "motion_kernels" is set.
-bool motionKernels(const rtc_scene* s) { return s->motion != nullptr || rtcOptions().motion_kernels != 0.0; }
-// The spot kernels run when a light of the handle has a cone - whatever the sampling, the pass and the motion - or, for
-// tests, whenever option "spot_kernels" is set.
-bool spotKernels(const rtc_scene* s) { return s->spots != nullptr || rtcOptions().spot_kernels != 0.0; }
-// The bump kernels run when a material of the handle has a bump - whatever the sampling, the pass, the motion and the
-// cones - or, for tests, whenever option "bump_kernels" is set.
-bool bumpKernels(const rtc_scene* s) { return s->bumps != nullptr || rtcOptions().bump_kernels != 0.0; }
-// The torus kernels run when a leaf of the handle's world is a torus - whatever the sampling, the pass, the motion, the
-// cones and the bumps: no other kernel knows kind 7 - or, for tests, whenever option "torus_kernels" is set.
-bool torusKernels(const rtc_scene* s) { return s->has_torus || rtcOptions().torus_kernels != 0.0; }
-// The meshuv kernels run when a texture map of the handle's scene has mapping RTC_TEX_MESH - whatever else the handle
-// holds, tori included: no other kernel knows mapping 4 - or, for tests, whenever option "meshuv_kernels" is set.
-bool meshuvKernels(const rtc_scene* s) { return s->has_mesh_map || rtcOptions().meshuv_kernels != 0.0; }
-// The gloss kernels run when a row of the handle's roughness table is non-zero (rtc_scene_set_gloss keeps no other table)
-// - whatever else the handle holds: they are the meshuv walk - or, for tests, whenever option "gloss_kernels" is set.
-bool glossKernels(const rtc_scene* s) { return s->gloss != nullptr || rtcOptions().gloss_kernels != 0.0; }
-// The occlusion kernels run when a row of the handle's radius table is non-zero (rtc_scene_set_occlusion keeps no other
-// table) - whatever else the handle holds: they are the gloss walk - or, for tests, whenever option "occlusion_kernels" is set.
-bool occlusionKernels(const rtc_scene* s) { return s->occlusion != nullptr || rtcOptions().occlusion_kernels != 0.0; }
-// The shadow-filter kernels run when a row of the handle's filter table is non-zero (rtc_scene_set_shadow_filters keeps no
-// other table) - whatever else the handle holds: they are the occlusion walk - or, for tests, whenever option
-// "shadow_filter_kernels" is set.
-bool shadowFilterKernels(const rtc_scene* s) { return s->shadow_filters != nullptr || rtcOptions().shadow_filter_kernels != 0.0; }
-// The media kernels run when the handle has an absorbing row or a fog (rtc_scene_set_media keeps no other table) - whatever
-// else the handle holds: they are the shadow-filter walk - or, for tests, whenever option "media_kernels" is set.
-bool mediaKernels(const rtc_scene* s) { return s->media != nullptr || rtcOptions().media_kernels != 0.0; }
-// The environment kernels run when the handle has a sky or a sun (rtc_scene_set_environment keeps no other table) - whatever
-// else the handle holds: they are the media walk - or, for tests, whenever option "environment_kernels" is set.
-bool environmentKernels(const rtc_scene* s) { return s->environment != nullptr || rtcOptions().environment_kernels != 0.0; }
-// The sky-light kernels run when the handle has a sky light AND an environment with a sky - decided here, launch by launch,
-// so the order of the two setters does not matter, and a sky light without a sky keeps the kernels the handle had - whatever
-// else the handle holds: they are the environment walk - or, for tests, whenever option "sky_light_kernels" is set.
-bool skyLightKernels(const rtc_scene* s) {
-  return (s->sky_light != nullptr && s->environment != nullptr && s->environment->sky) || rtcOptions().sky_light_kernels != 0.0;
+
+// Everything a family's kernel can take behind the seven arguments all of them share; a family passes the prefix its
+// signature takes (forFamilyKernel).
+struct LaunchArgs {
+  DevScene scene;
+  DevAreaLights area;
+  DevSampling smp;
+  DevMotion mo;
+  DevSpots spots;
+  DevBumps bumps;
+  DevMeshUvs muv;
+  DevGloss gloss;
+  DevOcclusion occl;
+  DevShadowFilter sfilt;
+  DevMedia media;
+  DevEnvironment env;
+  DevSkyLight skyl;
+};
+// ... from the handle, for a launch of family `f` with the scene `dev` (the handle's, or its copy for an empty dispatch).
+LaunchArgs launchArgs(const rtc_scene* s, Family f, const DevScene& dev, const DevCamera& cam) {
+  LaunchArgs a{};
+  a.scene = dev;
+  a.area = s->area;
+  a.smp = s->sampling;  // (the pass's area-light offset, P * N * S: N is the camera's whole image)
+  a.smp.pixel_base = static_cast<unsigned long long>(a.smp.sample_base) * (static_cast<unsigned long long>(cam.hsize) * cam.vsize);
+  if (f < Family::MOTION) return a;  // (BASE and MS: the caller's scene, the handle's area rows and its own sampling key)
+  // From the motion kernels up: the handle's root tables with the moving roots' bounds (or the scene's, all displacements
+  // zero: the option), and the scene's area rows (or zero rows: a point-only table); then every table the handle has, or
+  // what stands for none - under a family's option, and under every family above the table's own
+  a.smp.key = rtc_mix64(s->sampling_desc.seed ^ 0x243F6A8885A308D3ull);  // (the time's hash: also under the default sampling)
+  a.mo = DevMotion{s->tab->zero_disp.p};
+  if (const MotionTables* m = s->motion.get()) {
+    a.scene.root_recs = m->root_recs.p;
+    a.scene.root_cull = m->root_cull.p;
+    a.scene.root_box = m->root_box.p;
+    a.scene.cull_cmax = m->cull_cmax;
+    a.scene.cull_bmax = m->cull_bmax;
+    a.mo.disp = m->disp.p;
+  }
+  if (!s->area_kernel) a.area = DevAreaLights{s->tab->zero_rows.p, s->area.seed};
+  // (zero rows, every flag 0: no cone)
+  a.spots = DevSpots{s->spots ? s->spots->row.p : s->tab->zero_rows.p};
+  // (zero rows, every kind none: no bump)
+  a.bumps = DevBumps{s->bumps ? s->bumps->row.p : s->tab->zero_bump.p};
+  // (none: every row six zeros)
+  a.muv = DevMeshUvs{s->mesh_uvs ? s->mesh_uvs->row.p : nullptr};
+  // (RTC_GLOSS_ROW <= RTC_BUMP_ROW: the zero bump rows serve as zero roughness rows, every material smooth)
+  a.gloss = DevGloss{s->gloss ? s->gloss->row.p : s->tab->zero_bump.p, s->gloss ? s->gloss->key : 0ull};
+  // (one double per material: the zero bump rows serve as zero radius rows, no material occluded)
+  a.occl = DevOcclusion{s->occlusion ? s->occlusion->row.p : s->tab->zero_bump.p, s->occlusion ? s->occlusion->key : 0ull,
+                        s->occlusion ? s->occlusion->samples : 1u};
+  // (three doubles per material, 3 <= RTC_BUMP_ROW: the zero bump rows serve as zero filter rows, every material opaque)
+  a.sfilt = DevShadowFilter{s->shadow_filters ? s->shadow_filters->row.p : s->tab->zero_bump.p};
+  // (three doubles per material, 3 <= RTC_BUMP_ROW: the zero bump rows serve as zero absorption rows, and no fog; the fifth
+  // quarter of the pending rays in memory: ensureScratch sized it with the ray stack)
+  a.media = DevMedia{s->tab->zero_bump.p, 0.0, {0.0, 0.0, 0.0}, s->d_media_stack};
+  if (const MediaTables* m = s->media.get()) {
+    a.media.absorption = m->row.p;
+    a.media.fog_density = m->fog_density;
+    for (int c = 0; c < 3; ++c) a.media.fog_color[c] = m->fog_color[c];
+  }
+  // (the handle's sky and suns, or no sky and no sun)
+  a.env = DevEnvironment{{0.0, 0.0, 0.0}, RTC_ENV_NO_PATTERN, RTC_ENV_SPHERE, 0u, 0u, s->tab->zero_rows.p};
+  if (const EnvironmentTables* e = s->environment.get()) {
+    for (int c = 0; c < 3; ++c) a.env.rgb[c] = e->rgb[c];
+    a.env.pattern = e->pattern;
+    a.env.projection = e->projection;
+    a.env.sky = e->sky ? 1u : 0u;
+    if (e->n_suns != 0u) {
+      a.env.n_suns = e->n_suns;
+      a.env.sun = e->sun.p;
+    }
+  }
+  // (the handle's sky light, or a gain of zero)
+  const SkyLightTable* y = s->sky_light.get();
+  a.skyl = DevSkyLight{y ? y->gain : 0.0, y ? y->key : 0ull, y ? y->samples : 1u};
+  return a;
 }
-// Their resident work-groups per CU, asked for by the first launch that selects them and not at create: the query loads the
-// unit's code object, and a process none of whose handles has a sky light loads, allocates and runs what it did before the
-// unit existed.  A clone takes its source's answer.
-int skyLightOccupancy(rtc_scene* s) {
-  if (s->skyl_occupancy_known) return RTC_OK;
+
+// Every family's kernel pair, named once: `use(kernel, name, the arguments behind the shared seven...)` is called for the
+// kernel of `c` - by the launch (launchRender), by the occupancy query (familyOccupancy) and for the name (renderKernel).
+// The area kernels take DevAreaLights; the sampling kernels DevSampling, and an area world's both; the motion kernels both and
+// DevMotion; every family above takes the arguments of the one below and one more - the torus kernels the bump kernels'.
+#define RTC_KERNEL_PAIR(k, ...) return c.lds ? use(k, #k, __VA_ARGS__) : use(k##_bigworld, #k "_bigworld", __VA_ARGS__)
+template <typename Use>
+hipError_t forFamilyKernel(const rtc_scene* s, const KernelChoice& c, const LaunchArgs& a, Use&& use) {
+  switch (c.family) {
+    case Family::BASE:
+      if (s->area_kernel) RTC_KERNEL_PAIR(rtc_render_kernel_area, a.area);
+      return use(c.fn, c.name);  // (renderKernel's choice among the world's own kernels)
+    case Family::MS:
+      if (s->area_kernel) RTC_KERNEL_PAIR(rtc_render_kernel_area_ms, a.area, a.smp);
+      RTC_KERNEL_PAIR(rtc_render_kernel_ms, a.smp);
+    case Family::MOTION: RTC_KERNEL_PAIR(rtc_render_kernel_motion, a.area, a.smp, a.mo);
+    case Family::SPOT: RTC_KERNEL_PAIR(rtc_render_kernel_spot, a.area, a.smp, a.mo, a.spots);
+    case Family::BUMP: RTC_KERNEL_PAIR(rtc_render_kernel_bump, a.area, a.smp, a.mo, a.spots, a.bumps);
+    case Family::TORUS: RTC_KERNEL_PAIR(rtc_render_kernel_torus, a.area, a.smp, a.mo, a.spots, a.bumps);
+    case Family::MESHUV: RTC_KERNEL_PAIR(rtc_render_kernel_meshuv, a.area, a.smp, a.mo, a.spots, a.bumps, a.muv);
+    case Family::GLOSS: RTC_KERNEL_PAIR(rtc_render_kernel_gloss, a.area, a.smp, a.mo, a.spots, a.bumps, a.muv, a.gloss);
+    case Family::OCCL: RTC_KERNEL_PAIR(rtc_render_kernel_occl, a.area, a.smp, a.mo, a.spots, a.bumps, a.muv, a.gloss, a.occl);
+    case Family::SFILT: RTC_KERNEL_PAIR(rtc_render_kernel_sfilter, a.area, a.smp, a.mo, a.spots, a.bumps, a.muv, a.gloss, a.occl, a.sfilt);
+    case Family::MEDIA: RTC_KERNEL_PAIR(rtc_render_kernel_media, a.area, a.smp, a.mo, a.spots, a.bumps, a.muv, a.gloss, a.occl, a.sfilt, a.media);
+    case Family::ENV: RTC_KERNEL_PAIR(rtc_render_kernel_env, a.area, a.smp, a.mo, a.spots, a.bumps, a.muv, a.gloss, a.occl, a.sfilt, a.media, a.env);
+    case Family::SKYL: RTC_KERNEL_PAIR(rtc_render_kernel_skyl, a.area, a.smp, a.mo, a.spots, a.bumps, a.muv, a.gloss, a.occl, a.sfilt, a.media, a.env, a.skyl);
+  }
+  return hipErrorInvalidValue;  // (no such family)
+}
+#undef RTC_KERNEL_PAIR
+
+// One kernel's resident work-groups per CU: at least one.
+template <typename K>
+hipError_t residentPerCu(K kernel, uint32_t& blocks) {
   int nb = 0;
-  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_skyl, 256, 0));
-  s->blocks_per_cu_skyl_lds = static_cast<uint32_t>(std::max(nb, 1));
-  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_skyl_bigworld, 256, 0));
-  s->blocks_per_cu_skyl_big = static_cast<uint32_t>(std::max(nb, 1));
-  if (const int v = static_cast<int>(rtcOptions().blocks_per_cu); v >= 1)  // (tuning option)
-    s->blocks_per_cu_skyl_lds = std::min<uint32_t>(s->blocks_per_cu_skyl_lds, v), s->blocks_per_cu_skyl_big = std::min<uint32_t>(s->blocks_per_cu_skyl_big, v);
-  s->skyl_occupancy_known = true;
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, 256, 0);
+  if (e == hipSuccess) blocks = static_cast<uint32_t>(std::max(nb, 1));
+  return e;
+}
+uint32_t cappedBlocks(uint32_t blocks) {  // (tuning option)
+  const int v = static_cast<int>(rtcOptions().blocks_per_cu);
+  return v >= 1 ? std::min<uint32_t>(blocks, v) : blocks;
+}
+// A family's pair, asked once: at create, or - a lazy family - by the first launch that selects it (launch(), after
+// hipSetDevice).  Not for the BASE family of a world without area lights: create asks for that world's own kernels.
+int familyOccupancy(rtc_scene* s, Family f) {
+  bool& known = s->occupancy.known[static_cast<uint32_t>(f)];
+  if (known) return RTC_OK;
+  for (const bool lds : {true, false}) {
+    uint32_t& blocks = s->occupancy.at(f, lds);
+    HIP_TRY(forFamilyKernel(s, KernelChoice{f, lds, nullptr, nullptr}, LaunchArgs{},
+                            [&blocks](auto kernel, const char*, const auto&...) { return residentPerCu(kernel, blocks); }));
+    blocks = cappedBlocks(blocks);
+  }
+  known = true;
   return RTC_OK;
 }
-#define RTC_KERNEL(k) KernelChoice{k, #k}
+
+#define RTC_KERNEL(k, lds) KernelChoice{Family::BASE, lds, k, #k}
 // The general kernel at three waves per SIMD (rtc_render_kernel3): forced by option "waves3", else what the handle's
 // trial measured (KernelTune in launch()).
 bool usesGeneral3(const rtc_scene* s) {
@@ -653,54 +644,60 @@ bool usesGeneral3(const rtc_scene* s) {
 }
 KernelChoice ldsKernel(const rtc_scene* s, const DevPixelMap& map) {
   // (a simple world that is mostly cubes: the kernels whose root loop rejects by world boxes - trace() in rtc_kernels.hip)
-  if (usesSimple3(s, map)) return s->box_cull ? RTC_KERNEL(rtc_render_kernel_simple3_b) : RTC_KERNEL(rtc_render_kernel_simple3);
+  if (usesSimple3(s, map)) return s->box_cull ? RTC_KERNEL(rtc_render_kernel_simple3_b, true) : RTC_KERNEL(rtc_render_kernel_simple3, true);
 #if RTC_BVH8
-  if (usesGeneral3(s)) return RTC_KERNEL(rtc_render_kernel3);
+  if (usesGeneral3(s)) return RTC_KERNEL(rtc_render_kernel3, true);
 #endif
   if (s->simple_kernel)
-    return s->ext_kernel ? RTC_KERNEL(rtc_render_kernel_simple_ext) : (s->box_cull ? RTC_KERNEL(rtc_render_kernel_simple_b) : RTC_KERNEL(rtc_render_kernel_simple));
-  if (s->flat_kernel) return s->ext_kernel ? RTC_KERNEL(rtc_render_kernel_flat_ext) : RTC_KERNEL(rtc_render_kernel_flat);
-  return s->ext_kernel ? RTC_KERNEL(rtc_render_kernel_ext) : RTC_KERNEL(rtc_render_kernel);
+    return s->ext_kernel ? RTC_KERNEL(rtc_render_kernel_simple_ext, true) : (s->box_cull ? RTC_KERNEL(rtc_render_kernel_simple_b, true) : RTC_KERNEL(rtc_render_kernel_simple, true));
+  if (s->flat_kernel) return s->ext_kernel ? RTC_KERNEL(rtc_render_kernel_flat_ext, true) : RTC_KERNEL(rtc_render_kernel_flat, true);
+  return s->ext_kernel ? RTC_KERNEL(rtc_render_kernel_ext, true) : RTC_KERNEL(rtc_render_kernel, true);
 }
+// The kernel of the handle's next launch of `map`: the family and the place of the tables, decided here once for the launch,
+// its name, and the BASE family's choice among the world's own kernels.
 KernelChoice renderKernel(const rtc_scene* s, const DevPixelMap& map) {
-  if (skyLightKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_skyl) : RTC_KERNEL(rtc_render_kernel_skyl_bigworld);
-  if (environmentKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_env) : RTC_KERNEL(rtc_render_kernel_env_bigworld);
-  if (mediaKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_media) : RTC_KERNEL(rtc_render_kernel_media_bigworld);
-  if (shadowFilterKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_sfilter) : RTC_KERNEL(rtc_render_kernel_sfilter_bigworld);
-  if (occlusionKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_occl) : RTC_KERNEL(rtc_render_kernel_occl_bigworld);
-  if (glossKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_gloss) : RTC_KERNEL(rtc_render_kernel_gloss_bigworld);
-  if (meshuvKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_meshuv) : RTC_KERNEL(rtc_render_kernel_meshuv_bigworld);
-  if (torusKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_torus) : RTC_KERNEL(rtc_render_kernel_torus_bigworld);
-  if (bumpKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_bump) : RTC_KERNEL(rtc_render_kernel_bump_bigworld);
-  if (spotKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_spot) : RTC_KERNEL(rtc_render_kernel_spot_bigworld);
-  if (motionKernels(s)) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_motion) : RTC_KERNEL(rtc_render_kernel_motion_bigworld);
-  if (samplingKernels(s)) {
-    if (s->area_kernel) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_area_ms) : RTC_KERNEL(rtc_render_kernel_area_ms_bigworld);
-    return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_ms) : RTC_KERNEL(rtc_render_kernel_ms_bigworld);
+  KernelChoice c{family(s), tablesInLds(s), nullptr, nullptr};
+  if (c.family == Family::BASE && !s->area_kernel) {
+    if (c.lds) return ldsKernel(s, map);
+    return s->ext_kernel ? RTC_KERNEL(rtc_render_kernel_bigworld_ext, false) : RTC_KERNEL(rtc_render_kernel_bigworld, false);
   }
-  if (s->area_kernel) return tablesInLds(s) ? RTC_KERNEL(rtc_render_kernel_area) : RTC_KERNEL(rtc_render_kernel_area_bigworld);
-  if (tablesInLds(s)) return ldsKernel(s, map);
-  return s->ext_kernel ? RTC_KERNEL(rtc_render_kernel_bigworld_ext) : RTC_KERNEL(rtc_render_kernel_bigworld);
+  const char* name = "";
+  (void)forFamilyKernel(s, c, LaunchArgs{}, [&name](auto, const char* n, const auto&...) {
+    name = n;
+    return hipSuccess;
+  });
+  c.name = name;
+  return c;
 }
 #undef RTC_KERNEL
 
+// The launch stays type-checked: a kernel and arguments that do not fit its signature do not compile.
+template <typename... X>
+void launchTyped(void (*kernel)(DevScene, DevCamera, DevPixelMap, uint32_t, double*, DevStats*, DevStats*, X...), uint32_t blocks,
+                 hipStream_t stream, const DevScene& dev, const DevCamera& cam, const DevPixelMap& map, uint32_t max_depth, double* d_out,
+                 DevStats* st_now, DevStats* st_next, const X&... x) {
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, stream, dev, cam, map, max_depth, d_out, st_now, st_next, x...);
+}
+// The kernel `c` on `blocks` work-groups, with the handle's arguments for its family (`dev`: the handle's scene, or its copy
+// for an empty dispatch).
+void launchRender(const rtc_scene* s, const KernelChoice& c, uint32_t blocks, hipStream_t stream, const DevScene& dev, const DevCamera& cam,
+                  const DevPixelMap& map, uint32_t max_depth, double* d_out, DevStats* st_now, DevStats* st_next) {
+  const LaunchArgs a = launchArgs(s, c.family, dev, cam);
+  (void)forFamilyKernel(s, c, a, [&](auto kernel, const char*, const auto&... x) {
+    launchTyped(kernel, blocks, stream, a.scene, cam, map, max_depth, d_out, st_now, st_next, x...);
+    return hipSuccess;
+  });
+}
+
 // Work-groups of the launch's kernel that are resident at once, and the waves in them.
 uint32_t residentBlocksAlone(const rtc_scene* s, const DevPixelMap& map) {
-  if (skyLightKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_skyl_lds : s->blocks_per_cu_skyl_big);
-  if (environmentKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_env_lds : s->blocks_per_cu_env_big);
-  if (mediaKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_media_lds : s->blocks_per_cu_media_big);
-  if (shadowFilterKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_sfilt_lds : s->blocks_per_cu_sfilt_big);
-  if (occlusionKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_occl_lds : s->blocks_per_cu_occl_big);
-  if (glossKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_gloss_lds : s->blocks_per_cu_gloss_big);
-  if (meshuvKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_meshuv_lds : s->blocks_per_cu_meshuv_big);
-  if (torusKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_torus_lds : s->blocks_per_cu_torus_big);
-  if (bumpKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_bump_lds : s->blocks_per_cu_bump_big);
-  if (spotKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_spot_lds : s->blocks_per_cu_spot_big);
-  if (motionKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_motion_lds : s->blocks_per_cu_motion_big);
-  if (samplingKernels(s)) return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_ms_lds : s->blocks_per_cu_ms_big);
-  if (usesSimple3(s, map)) return s->n_cus * s->blocks_per_cu_simple3;
-  if (tablesInLds(s) && usesGeneral3(s)) return s->n_cus * s->blocks_per_cu_general3;
-  return s->n_cus * (tablesInLds(s) ? s->blocks_per_cu_lds : s->blocks_per_cu_big);
+  const Family f = family(s);
+  const bool lds = tablesInLds(s);
+  if (f == Family::BASE) {  // (the world's own kernels: a three-wave form has its own answer)
+    if (usesSimple3(s, map)) return s->n_cus * s->blocks_per_cu_simple3;
+    if (lds && usesGeneral3(s)) return s->n_cus * s->blocks_per_cu_general3;
+  }
+  return s->n_cus * s->occupancy.at(f, lds);
 }
 // With frames in flight (a scene with several handles) a launch gets no more waves than one per three chunks: a rank's
 // share of a split frame - 4 050 chunks of cover at 8 ranks - spread over all 3 072 wave slots leaves every lane with a
@@ -974,7 +971,7 @@ int ensureScratch(rtc_scene* s, DevPixelMap& map, uint32_t blocks, uint32_t max_
     HIP_TRY(hipMalloc(&s->d_ray_stack, need));
     s->ray_stack_capacity = need;
   }
-  if (mediaKernels(s) || environmentKernels(s) || skyLightKernels(s)) {  // (the environment and sky-light kernels are the media walk)
+  if (family(s) >= Family::MEDIA) {  // (the environment and sky-light kernels are the media walk)
     // (the media kernels' fifth quarter of every pending ray, 16 bytes beside the record's 64: a quarter of the ray stack's
     // capacity holds a slot for every slot of it, whatever the launch's depth)
     const size_t need_x = s->ray_stack_capacity / 4u;
@@ -1050,7 +1047,7 @@ int enqueueRender(rtc_scene* s, const rtc_camera& cam, DevPixelMap& map, uint32_
   // hands part of its ray tree to a neighbour (render_body step 2a).
   const KernelChoice kernel = renderKernel(s, map);
   s->last_kernel = kernel.name;
-  kernel.launch(blocks, stream, s, s->dev, devCamera(cam), map, max_depth, d_out, st_now, st_next);
+  launchRender(s, kernel, blocks, stream, s->dev, devCamera(cam), map, max_depth, d_out, st_now, st_next);
   HIP_TRY(hipGetLastError());
   return RTC_OK;
 }
@@ -1062,8 +1059,7 @@ int launch(rtc_scene* s, const rtc_camera& cam, const DevPixelMap& map_in, uint3
     return fail(RTC_ERR_INVALID_ARGUMENT, "max_depth %u exceeds the per-lane ray stack (%d)", max_depth, RTC_MAX_DEPTH);
   if (map.n_chunks == 0) return fail(RTC_ERR_INVALID_ARGUMENT, "nothing to render");
   HIP_TRY(hipSetDevice(s->device));
-  if (skyLightKernels(s))
-    if (const int st = skyLightOccupancy(s); st != RTC_OK) return st;
+  if (const int st = familyOccupancy(s, family(s)); st != RTC_OK) return st;  // (a lazy family's first launch; else known since create)
   // Launches on one handle share its counters, work counter, pending-ray stacks, csg lists and schedule buffers, and
   // launch N + 1 clears the counters of launch N + 2: they must run one after the other.  Stream order gives that on
   // one stream; when the caller changes streams (rtc_render_device on its own stream, then rtc_render on the handle's),
@@ -1098,8 +1094,8 @@ int launch(rtc_scene* s, const rtc_camera& cam, const DevPixelMap& map_in, uint3
     const KernelChoice kernel = renderKernel(s, map);
     DevScene dev = s->dev;
     dev.csg_buf = nullptr;
-    kernel.launch(residentBlocks(s, map), stream, s, dev, devCamera(cam), idle, max_depth, d_out, s->d_stats + s->stats_parity,
-                  s->d_stats + (s->stats_parity ^ 1u));
+    launchRender(s, kernel, residentBlocks(s, map), stream, dev, devCamera(cam), idle, max_depth, d_out, s->d_stats + s->stats_parity,
+                 s->d_stats + (s->stats_parity ^ 1u));
     HIP_TRY(hipGetLastError());
   }
   s->trial_live = false;  // (set again below if this launch is a frame of a running trial)
@@ -1116,10 +1112,10 @@ int launch(rtc_scene* s, const rtc_camera& cam, const DevPixelMap& map_in, uint3
   int trial_slot = -1;
   {
     rtc_scene::KernelTune& T = s->tune;
-    const bool eligible = !samplingKernels(s) && !motionKernels(s) && !spotKernels(s) && !bumpKernels(s) && !torusKernels(s) && !meshuvKernels(s) && !glossKernels(s) && !occlusionKernels(s) && !shadowFilterKernels(s) && !mediaKernels(s) && !environmentKernels(s) && !skyLightKernels(s) &&  // (the sampling, motion, spot, bump, torus, meshuv, gloss, occlusion, shadow-filter, media, environment and sky-light kernels have no three-wave form)
+    const bool eligible = family(s) == Family::BASE &&  // (no other family has a three-wave form)
                           ((s->general3_ok && rtcOptions().waves3 < 0.0 && tablesInLds(s) &&
                             !(s->tab && s->tab->handles.load(std::memory_order_relaxed) > 1) &&
-                            static_cast<double>(map.n_chunks) >= 4.0 * 4.0 * s->n_cus * s->blocks_per_cu_lds) ||
+                            static_cast<double>(map.n_chunks) >= 4.0 * 4.0 * s->n_cus * s->occupancy.at(Family::BASE, true)) ||
                            simple3Trial(s, map));  // (a simple world's launch of a size where neither of its kernels always wins)
     if (eligible && T.key != s->cost_key) {  // another pixel map: a trial of its own (the last choice stands until it ends)
       T.key = s->cost_key;
@@ -2449,87 +2445,21 @@ int uploadTables(const rtc_scene_desc& d, const SceneTraits& traits, const HostT
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, s->device));
     s->n_cus = static_cast<uint32_t>(prop.multiProcessorCount);
-    int nb = 0;
-    DevPixelMap no_map{};  // (n_chunks 0: the kernel of a small launch)
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &nb, ldsKernel(s, no_map).fn, 256, 0));
-    s->blocks_per_cu_lds = static_cast<uint32_t>(std::max(nb, 1));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_simple3, 256, 0));
-    s->blocks_per_cu_simple3 = static_cast<uint32_t>(std::max(nb, 1));
+    // The world's own kernels: the kernel of a small launch (n_chunks 0) where the tables fit, the three-wave forms, the
+    // big-world kernel.
+    const DevPixelMap no_map{};
+    HIP_TRY(residentPerCu(ldsKernel(s, no_map).fn, s->occupancy.at(Family::BASE, true)));
+    HIP_TRY(residentPerCu(rtc_render_kernel_simple3, s->blocks_per_cu_simple3));
 #if RTC_BVH8
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel3, 256, 0));
-    s->blocks_per_cu_general3 = static_cast<uint32_t>(std::max(nb, 1));
+    HIP_TRY(residentPerCu(rtc_render_kernel3, s->blocks_per_cu_general3));
 #endif
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &nb, ext_kernel ? rtc_render_kernel_bigworld_ext : rtc_render_kernel_bigworld, 256, 0));
-    s->blocks_per_cu_big = static_cast<uint32_t>(std::max(nb, 1));
-    if (s->area_kernel) {
-      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_area, 256, 0));
-      s->blocks_per_cu_lds = static_cast<uint32_t>(std::max(nb, 1));
-      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_area_bigworld, 256, 0));
-      s->blocks_per_cu_big = static_cast<uint32_t>(std::max(nb, 1));
-    }
-    // (the sampling kernels of this world, whichever setting a handle of it takes later)
-    if (s->area_kernel) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_area_ms, 256, 0));
-    else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_ms, 256, 0));
-    s->blocks_per_cu_ms_lds = static_cast<uint32_t>(std::max(nb, 1));
-    if (s->area_kernel) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_area_ms_bigworld, 256, 0));
-    else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_ms_bigworld, 256, 0));
-    s->blocks_per_cu_ms_big = static_cast<uint32_t>(std::max(nb, 1));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_motion, 256, 0));  // (the motion kernels: one pair for every world)
-    s->blocks_per_cu_motion_lds = static_cast<uint32_t>(std::max(nb, 1));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_motion_bigworld, 256, 0));
-    s->blocks_per_cu_motion_big = static_cast<uint32_t>(std::max(nb, 1));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_spot, 256, 0));  // (the spot kernels: one pair for every world)
-    s->blocks_per_cu_spot_lds = static_cast<uint32_t>(std::max(nb, 1));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_spot_bigworld, 256, 0));
-    s->blocks_per_cu_spot_big = static_cast<uint32_t>(std::max(nb, 1));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_bump, 256, 0));  // (the bump kernels: one pair for every world)
-    s->blocks_per_cu_bump_lds = static_cast<uint32_t>(std::max(nb, 1));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_bump_bigworld, 256, 0));
-    s->blocks_per_cu_bump_big = static_cast<uint32_t>(std::max(nb, 1));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_torus, 256, 0));  // (the torus kernels: one pair for every world)
-    s->blocks_per_cu_torus_lds = static_cast<uint32_t>(std::max(nb, 1));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_torus_bigworld, 256, 0));
-    s->blocks_per_cu_torus_big = static_cast<uint32_t>(std::max(nb, 1));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_meshuv, 256, 0));  // (the meshuv kernels: one pair for every world)
-    s->blocks_per_cu_meshuv_lds = static_cast<uint32_t>(std::max(nb, 1));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_meshuv_bigworld, 256, 0));
-    s->blocks_per_cu_meshuv_big = static_cast<uint32_t>(std::max(nb, 1));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_gloss, 256, 0));  // (the gloss kernels: one pair for every world)
-    s->blocks_per_cu_gloss_lds = static_cast<uint32_t>(std::max(nb, 1));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_gloss_bigworld, 256, 0));
-    s->blocks_per_cu_gloss_big = static_cast<uint32_t>(std::max(nb, 1));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_occl, 256, 0));  // (the occlusion kernels: one pair for every world)
-    s->blocks_per_cu_occl_lds = static_cast<uint32_t>(std::max(nb, 1));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_occl_bigworld, 256, 0));
-    s->blocks_per_cu_occl_big = static_cast<uint32_t>(std::max(nb, 1));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_sfilter, 256, 0));  // (the shadow-filter kernels: one pair for every world)
-    s->blocks_per_cu_sfilt_lds = static_cast<uint32_t>(std::max(nb, 1));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_sfilter_bigworld, 256, 0));
-    s->blocks_per_cu_sfilt_big = static_cast<uint32_t>(std::max(nb, 1));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_media, 256, 0));  // (the media kernels: one pair for every world)
-    s->blocks_per_cu_media_lds = static_cast<uint32_t>(std::max(nb, 1));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_media_bigworld, 256, 0));
-    s->blocks_per_cu_media_big = static_cast<uint32_t>(std::max(nb, 1));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_env, 256, 0));  // (the environment kernels: one pair for every world)
-    s->blocks_per_cu_env_lds = static_cast<uint32_t>(std::max(nb, 1));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtc_render_kernel_env_bigworld, 256, 0));
-    s->blocks_per_cu_env_big = static_cast<uint32_t>(std::max(nb, 1));
-    if (const int v = static_cast<int>(rtcOptions().blocks_per_cu); v >= 1) {  // (tuning option)
-      s->blocks_per_cu_lds = std::min<uint32_t>(s->blocks_per_cu_lds, v), s->blocks_per_cu_big = std::min<uint32_t>(s->blocks_per_cu_big, v);
-      s->blocks_per_cu_ms_lds = std::min<uint32_t>(s->blocks_per_cu_ms_lds, v), s->blocks_per_cu_ms_big = std::min<uint32_t>(s->blocks_per_cu_ms_big, v);
-      s->blocks_per_cu_motion_lds = std::min<uint32_t>(s->blocks_per_cu_motion_lds, v), s->blocks_per_cu_motion_big = std::min<uint32_t>(s->blocks_per_cu_motion_big, v);
-      s->blocks_per_cu_spot_lds = std::min<uint32_t>(s->blocks_per_cu_spot_lds, v), s->blocks_per_cu_spot_big = std::min<uint32_t>(s->blocks_per_cu_spot_big, v);
-      s->blocks_per_cu_bump_lds = std::min<uint32_t>(s->blocks_per_cu_bump_lds, v), s->blocks_per_cu_bump_big = std::min<uint32_t>(s->blocks_per_cu_bump_big, v);
-      s->blocks_per_cu_torus_lds = std::min<uint32_t>(s->blocks_per_cu_torus_lds, v), s->blocks_per_cu_torus_big = std::min<uint32_t>(s->blocks_per_cu_torus_big, v);
-      s->blocks_per_cu_meshuv_lds = std::min<uint32_t>(s->blocks_per_cu_meshuv_lds, v), s->blocks_per_cu_meshuv_big = std::min<uint32_t>(s->blocks_per_cu_meshuv_big, v);
-      s->blocks_per_cu_gloss_lds = std::min<uint32_t>(s->blocks_per_cu_gloss_lds, v), s->blocks_per_cu_gloss_big = std::min<uint32_t>(s->blocks_per_cu_gloss_big, v);
-      s->blocks_per_cu_occl_lds = std::min<uint32_t>(s->blocks_per_cu_occl_lds, v), s->blocks_per_cu_occl_big = std::min<uint32_t>(s->blocks_per_cu_occl_big, v);
-      s->blocks_per_cu_sfilt_lds = std::min<uint32_t>(s->blocks_per_cu_sfilt_lds, v), s->blocks_per_cu_sfilt_big = std::min<uint32_t>(s->blocks_per_cu_sfilt_big, v);
-      s->blocks_per_cu_media_lds = std::min<uint32_t>(s->blocks_per_cu_media_lds, v), s->blocks_per_cu_media_big = std::min<uint32_t>(s->blocks_per_cu_media_big, v);
-      s->blocks_per_cu_env_lds = std::min<uint32_t>(s->blocks_per_cu_env_lds, v), s->blocks_per_cu_env_big = std::min<uint32_t>(s->blocks_per_cu_env_big, v);
-    }
+    HIP_TRY(residentPerCu(ext_kernel ? rtc_render_kernel_bigworld_ext : rtc_render_kernel_bigworld, s->occupancy.at(Family::BASE, false)));
+    for (const bool lds : {true, false}) s->occupancy.at(Family::BASE, lds) = cappedBlocks(s->occupancy.at(Family::BASE, lds));
+    s->occupancy.known[static_cast<uint32_t>(Family::BASE)] = !s->area_kernel;  // (an area world: its area pair instead, asked for below)
+    // Every family's pair of this world, whichever setting a handle of it takes later - but a lazy family's.
+    for (uint32_t f = 0; f < RTC_FAMILIES; ++f)
+      if (!familyIsLazy(static_cast<Family>(f)))
+        if (const int st = familyOccupancy(s, static_cast<Family>(f)); st != RTC_OK) return st;
   }
   DevScene& D = s->dev;
   D.root_recs = s->tab->root_recs.p;
@@ -2588,6 +2518,20 @@ int uploadTables(const rtc_scene_desc& d, const SceneTraits& traits, const HostT
   D.n_root_spheres = T.n_root_kind[0];
   D.n_root_planes = T.n_root_kind[1];
   D.n_root_cubes = T.n_root_kind[2];
+  return RTC_OK;
+}
+
+// The table setters' common tail, behind their validation and their upload: the handle and its band clones (the handles
+// rtc_render renders a large frame with) get the new tables - null: none - once nothing reads the old ones.  `on_device`
+// false: the tables hold values a launch takes at its enqueue, nothing on the device is replaced and nothing is waited for.
+template <typename T>
+int replaceTables(rtc_scene* s, std::shared_ptr<const T> rtc_scene::*slot, const std::shared_ptr<const T>& tables, bool on_device = true) {
+  if (on_device) {  // (the tables being replaced may still be read by a launch of this handle or of its band clones)
+    HIP_TRY(handleIdle(s));
+    for (rtc_scene* b : s->band) HIP_TRY(handleIdle(b));
+  }
+  s->*slot = tables;
+  for (rtc_scene* b : s->band) b->*slot = tables;
   return RTC_OK;
 }
 
@@ -2927,12 +2871,7 @@ int rtc_scene_set_motion(rtc_scene* s, const rtc_motion* motion) {
   if (moving) {
     if (const int st = makeMotionTables(s, motion->displacement, tables); st != RTC_OK) return st;
   }
-  // (the tables being replaced may still be read by a launch of this handle or of its band clones)
-  HIP_TRY(handleIdle(s));
-  for (rtc_scene* b : s->band) HIP_TRY(handleIdle(b));
-  s->motion = tables;
-  for (rtc_scene* b : s->band) b->motion = tables;  // (the band clones rtc_render renders a large frame with)
-  return RTC_OK;
+  return replaceTables(s, &rtc_scene::motion, tables);
 }
 
 // ---- spot lights
@@ -2984,12 +2923,7 @@ int rtc_scene_set_spots(rtc_scene* s, const rtc_spot* spots) {
     HIP_TRY(t->row.upload(rows));
     tables = std::move(t);
   }
-  // (the rows being replaced may still be read by a launch of this handle or of its band clones)
-  HIP_TRY(handleIdle(s));
-  for (rtc_scene* b : s->band) HIP_TRY(handleIdle(b));
-  s->spots = tables;
-  for (rtc_scene* b : s->band) b->spots = tables;  // (the band clones rtc_render renders a large frame with)
-  return RTC_OK;
+  return replaceTables(s, &rtc_scene::spots, tables);
 }
 
 // ---- normal perturbation
@@ -3046,12 +2980,7 @@ int rtc_scene_set_bumps(rtc_scene* s, const rtc_bump* bumps) {
     HIP_TRY(t->row.upload(rows));
     tables = std::move(t);
   }
-  // (the rows being replaced may still be read by a launch of this handle or of its band clones)
-  HIP_TRY(handleIdle(s));
-  for (rtc_scene* b : s->band) HIP_TRY(handleIdle(b));
-  s->bumps = tables;
-  for (rtc_scene* b : s->band) b->bumps = tables;  // (the band clones rtc_render renders a large frame with)
-  return RTC_OK;
+  return replaceTables(s, &rtc_scene::bumps, tables);
 }
 
 // ---- mesh texture coordinates
@@ -3075,12 +3004,7 @@ int rtc_scene_set_mesh_uvs(rtc_scene* s, const rtc_mesh_uvs* uvs) {
       tables = std::move(t);
     }
   }
-  // (the rows being replaced may still be read by a launch of this handle or of its band clones)
-  HIP_TRY(handleIdle(s));
-  for (rtc_scene* b : s->band) HIP_TRY(handleIdle(b));
-  s->mesh_uvs = tables;
-  for (rtc_scene* b : s->band) b->mesh_uvs = tables;  // (the band clones rtc_render renders a large frame with)
-  return RTC_OK;
+  return replaceTables(s, &rtc_scene::mesh_uvs, tables);
 }
 
 // ---- glossy reflection and refraction
@@ -3115,12 +3039,7 @@ int rtc_scene_set_gloss(rtc_scene* s, const rtc_gloss* gloss) {
     t->key = rtc_mix64(gloss->seed ^ RTC_GLOSS_SALT);
     tables = std::move(t);
   }
-  // (the rows being replaced may still be read by a launch of this handle or of its band clones)
-  HIP_TRY(handleIdle(s));
-  for (rtc_scene* b : s->band) HIP_TRY(handleIdle(b));
-  s->gloss = tables;
-  for (rtc_scene* b : s->band) b->gloss = tables;  // (the band clones rtc_render renders a large frame with)
-  return RTC_OK;
+  return replaceTables(s, &rtc_scene::gloss, tables);
 }
 
 // ---- ambient occlusion
@@ -3155,12 +3074,7 @@ int rtc_scene_set_occlusion(rtc_scene* s, const rtc_occlusion* occlusion) {
     t->samples = occlusion->samples;
     tables = std::move(t);
   }
-  // (the rows being replaced may still be read by a launch of this handle or of its band clones)
-  HIP_TRY(handleIdle(s));
-  for (rtc_scene* b : s->band) HIP_TRY(handleIdle(b));
-  s->occlusion = tables;
-  for (rtc_scene* b : s->band) b->occlusion = tables;  // (the band clones rtc_render renders a large frame with)
-  return RTC_OK;
+  return replaceTables(s, &rtc_scene::occlusion, tables);
 }
 
 // ---- shadow filters
@@ -3192,12 +3106,7 @@ int rtc_scene_set_shadow_filters(rtc_scene* s, const rtc_shadow_filters* f) {
     HIP_TRY(t->row.upload(rows));
     tables = std::move(t);
   }
-  // (the rows being replaced may still be read by a launch of this handle or of its band clones)
-  HIP_TRY(handleIdle(s));
-  for (rtc_scene* b : s->band) HIP_TRY(handleIdle(b));
-  s->shadow_filters = tables;
-  for (rtc_scene* b : s->band) b->shadow_filters = tables;  // (the band clones rtc_render renders a large frame with)
-  return RTC_OK;
+  return replaceTables(s, &rtc_scene::shadow_filters, tables);
 }
 
 // ---- participating media
@@ -3240,12 +3149,7 @@ int rtc_scene_set_media(rtc_scene* s, const rtc_media* m) {
     for (int c = 0; c < 3; ++c) t->fog_color[c] = m->fog_color[c];
     tables = std::move(t);
   }
-  // (the rows being replaced may still be read by a launch of this handle or of its band clones)
-  HIP_TRY(handleIdle(s));
-  for (rtc_scene* b : s->band) HIP_TRY(handleIdle(b));
-  s->media = tables;
-  for (rtc_scene* b : s->band) b->media = tables;  // (the band clones rtc_render renders a large frame with)
-  return RTC_OK;
+  return replaceTables(s, &rtc_scene::media, tables);
 }
 
 // ---- the environment
@@ -3298,17 +3202,12 @@ int rtc_scene_set_environment(rtc_scene* s, const rtc_environment* e) {
     }
     tables = std::move(t);
   }
-  // (the rows being replaced may still be read by a launch of this handle or of its band clones)
-  HIP_TRY(handleIdle(s));
-  for (rtc_scene* b : s->band) HIP_TRY(handleIdle(b));
-  s->environment = tables;
-  for (rtc_scene* b : s->band) b->environment = tables;  // (the band clones rtc_render renders a large frame with)
-  return RTC_OK;
+  return replaceTables(s, &rtc_scene::environment, tables);
 }
 
 // ---- the sky light
 // Validated on the host before any HIP call and before anything changes.  NULL, or a gain of zero, is no sky light.  Whether
-// the sky-light kernels run is decided at launch (skyLightKernels): the table alone, on a handle without a sky, changes nothing.
+// the sky-light kernels run is decided at launch (family()): the table alone, on a handle without a sky, changes nothing.
 int rtc_scene_set_sky_light(rtc_scene* s, const rtc_sky_light* y) {
   g_error.clear();
   if (!s) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
@@ -3327,9 +3226,7 @@ int rtc_scene_set_sky_light(rtc_scene* s, const rtc_sky_light* y) {
     }
   }
   // (a launch of this handle or of its band clones takes the values at its enqueue: nothing on the device is replaced)
-  s->sky_light = table;
-  for (rtc_scene* b : s->band) b->sky_light = table;  // (the band clones rtc_render renders a large frame with)
-  return RTC_OK;
+  return replaceTables(s, &rtc_scene::sky_light, table, false);
 }
 
 // ---- adaptive sampling
@@ -3532,52 +3429,26 @@ int rtc_scene_clone(const rtc_scene* src, rtc_scene** out) {
   s->area = src->area;  // (the rows the scene's device copy holds, and the source's seed)
   s->sample_pass = src->sample_pass;
   applySampling(s, src->sampling_desc);
-  s->blocks_per_cu_ms_lds = src->blocks_per_cu_ms_lds;
-  s->blocks_per_cu_ms_big = src->blocks_per_cu_ms_big;
   s->motion = src->motion;  // (shared: read-only once made)
-  s->blocks_per_cu_motion_lds = src->blocks_per_cu_motion_lds;
-  s->blocks_per_cu_motion_big = src->blocks_per_cu_motion_big;
   s->spots = src->spots;  // (shared: read-only once made)
-  s->blocks_per_cu_spot_lds = src->blocks_per_cu_spot_lds;
-  s->blocks_per_cu_spot_big = src->blocks_per_cu_spot_big;
   s->bumps = src->bumps;  // (shared: read-only once made)
-  s->blocks_per_cu_bump_lds = src->blocks_per_cu_bump_lds;
-  s->blocks_per_cu_bump_big = src->blocks_per_cu_bump_big;
   s->has_torus = src->has_torus;
-  s->blocks_per_cu_torus_lds = src->blocks_per_cu_torus_lds;
-  s->blocks_per_cu_torus_big = src->blocks_per_cu_torus_big;
   s->has_mesh_map = src->has_mesh_map;
   s->n_tris = src->n_tris;
   s->mesh_uvs = src->mesh_uvs;  // (shared: read-only once made)
-  s->blocks_per_cu_meshuv_lds = src->blocks_per_cu_meshuv_lds;
-  s->blocks_per_cu_meshuv_big = src->blocks_per_cu_meshuv_big;
   s->gloss = src->gloss;  // (shared: read-only once made)
-  s->blocks_per_cu_gloss_lds = src->blocks_per_cu_gloss_lds;
-  s->blocks_per_cu_gloss_big = src->blocks_per_cu_gloss_big;
   s->occlusion = src->occlusion;  // (shared: read-only once made)
-  s->blocks_per_cu_occl_lds = src->blocks_per_cu_occl_lds;
-  s->blocks_per_cu_occl_big = src->blocks_per_cu_occl_big;
   s->shadow_filters = src->shadow_filters;  // (shared: read-only once made)
-  s->blocks_per_cu_sfilt_lds = src->blocks_per_cu_sfilt_lds;
-  s->blocks_per_cu_sfilt_big = src->blocks_per_cu_sfilt_big;
   s->media = src->media;  // (shared: read-only once made; the fifth-quarter buffer is the handle's own, made at its first launch)
-  s->blocks_per_cu_media_lds = src->blocks_per_cu_media_lds;
-  s->blocks_per_cu_media_big = src->blocks_per_cu_media_big;
   s->environment = src->environment;  // (shared: read-only once made)
-  s->blocks_per_cu_env_lds = src->blocks_per_cu_env_lds;
-  s->blocks_per_cu_env_big = src->blocks_per_cu_env_big;
   s->sky_light = src->sky_light;  // (shared: read-only once made)
-  s->blocks_per_cu_skyl_lds = src->blocks_per_cu_skyl_lds;
-  s->blocks_per_cu_skyl_big = src->blocks_per_cu_skyl_big;
-  s->skyl_occupancy_known = src->skyl_occupancy_known;
   s->simple_kernel = src->simple_kernel;
   s->flat_kernel = src->flat_kernel;
   s->simple3_ok = src->simple3_ok;
   s->box_cull = src->box_cull;
   s->max_trav_stack = src->max_trav_stack;
   s->n_cus = src->n_cus;
-  s->blocks_per_cu_lds = src->blocks_per_cu_lds;
-  s->blocks_per_cu_big = src->blocks_per_cu_big;
+  s->occupancy = src->occupancy;  // (every family's answers, and which have been asked for: a lazy family's too)
   s->blocks_per_cu_simple3 = src->blocks_per_cu_simple3;
   s->general3_ok = src->general3_ok;
   s->blocks_per_cu_general3 = src->blocks_per_cu_general3;

@@ -224,6 +224,28 @@ struct MotionTables {
 
 constexpr uint32_t RTC_MAX_HOST_BANDS = 4;
 
+// The render kernels' launch families, lowest priority first: a launch runs the highest family whose condition holds
+// (family() in rtc_capi.hip, which also names every family's kernel pair and its arguments - forFamilyKernel).  Each takes
+// the arguments of the one below and, but for TORUS, one more.
+enum class Family : uint32_t { BASE, MS, MOTION, SPOT, BUMP, TORUS, MESHUV, GLOSS, OCCL, SFILT, MEDIA, ENV, SKYL };
+constexpr uint32_t RTC_FAMILIES = 13;
+// A family whose occupancy is asked for by the first launch that selects it and not at create: the query loads the unit's
+// code object, and a process none of whose handles has a sky light loads, allocates and runs what it did before the unit
+// existed.
+constexpr bool familyIsLazy(Family f) { return f == Family::SKYL; }
+
+// Resident work-groups per CU of every family's kernels, [family][tables in LDS ? 0 : 1], and whether they have been asked
+// for (at create, or for a lazy family at its first launch).  A clone takes its source's.
+struct FamilyOccupancy {
+  uint32_t blocks_per_cu[RTC_FAMILIES][2];
+  bool known[RTC_FAMILIES] = {};
+  FamilyOccupancy() {
+    for (auto& pair : blocks_per_cu) pair[0] = pair[1] = 1;  // (until asked for: one work-group, as every answer is at least)
+  }
+  uint32_t& at(Family f, bool lds) { return blocks_per_cu[static_cast<uint32_t>(f)][lds ? 0 : 1]; }
+  uint32_t at(Family f, bool lds) const { return blocks_per_cu[static_cast<uint32_t>(f)][lds ? 0 : 1]; }
+};
+
 struct rtc_scene {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -249,32 +271,19 @@ struct rtc_scene {
   double* d_adaptive_frame = nullptr;  // rtc_scene_adaptive_step's compact tile frame, and its size in doubles
   size_t adaptive_frame_capacity = 0;
   std::vector<uint32_t> h_adaptive_list;  // ... and the active list it read back
-  uint32_t blocks_per_cu_ms_lds = 1, blocks_per_cu_ms_big = 1;  // resident work-groups of the world's sampling kernels
   std::shared_ptr<const MotionTables> motion;  // rtc_scene_set_motion; null: static (a clone starts with its source's)
-  uint32_t blocks_per_cu_motion_lds = 1, blocks_per_cu_motion_big = 1;  // ... and of the motion kernels
   std::shared_ptr<const SpotTables> spots;  // rtc_scene_set_spots; null: no cones (a clone starts with its source's)
-  uint32_t blocks_per_cu_spot_lds = 1, blocks_per_cu_spot_big = 1;  // ... and of the spot kernels
   std::shared_ptr<const BumpTables> bumps;  // rtc_scene_set_bumps; null: no bumps (a clone starts with its source's)
-  uint32_t blocks_per_cu_bump_lds = 1, blocks_per_cu_bump_big = 1;  // ... and of the bump kernels
   bool has_torus = false;          // a leaf of the world is a torus (RTC_TORUS): the torus kernels
-  uint32_t blocks_per_cu_torus_lds = 1, blocks_per_cu_torus_big = 1;  // resident work-groups per CU of the torus kernels
   bool has_mesh_map = false;       // a texture map of the scene has mapping RTC_TEX_MESH: the meshuv kernels
   uint32_t n_tris = 0;             // the description's n_tris: what rtc_scene_set_mesh_uvs' table must have
   std::shared_ptr<const MeshUvTables> mesh_uvs;  // rtc_scene_set_mesh_uvs; null: every row six zeros (a clone starts with its source's)
-  uint32_t blocks_per_cu_meshuv_lds = 1, blocks_per_cu_meshuv_big = 1;  // resident work-groups per CU of the meshuv kernels
   std::shared_ptr<const GlossTables> gloss;  // rtc_scene_set_gloss; null: no rough row (a clone starts with its source's)
-  uint32_t blocks_per_cu_gloss_lds = 1, blocks_per_cu_gloss_big = 1;  // resident work-groups per CU of the gloss kernels
   std::shared_ptr<const OcclusionTables> occlusion;  // rtc_scene_set_occlusion; null: no row with a radius (a clone starts with its source's)
-  uint32_t blocks_per_cu_occl_lds = 1, blocks_per_cu_occl_big = 1;  // resident work-groups per CU of the occlusion kernels
   std::shared_ptr<const ShadowFilterTables> shadow_filters;  // rtc_scene_set_shadow_filters; null: no non-zero row (a clone starts with its source's)
-  uint32_t blocks_per_cu_sfilt_lds = 1, blocks_per_cu_sfilt_big = 1;  // resident work-groups per CU of the shadow-filter kernels
   std::shared_ptr<const MediaTables> media;  // rtc_scene_set_media; null: no absorbing row and no fog (a clone starts with its source's)
-  uint32_t blocks_per_cu_media_lds = 1, blocks_per_cu_media_big = 1;  // resident work-groups per CU of the media kernels
   std::shared_ptr<const EnvironmentTables> environment;  // rtc_scene_set_environment; null: no sky and no sun (a clone starts with its source's)
-  uint32_t blocks_per_cu_env_lds = 1, blocks_per_cu_env_big = 1;  // resident work-groups per CU of the environment kernels
   std::shared_ptr<const SkyLightTable> sky_light;  // rtc_scene_set_sky_light; null: no gain (a clone starts with its source's)
-  uint32_t blocks_per_cu_skyl_lds = 1, blocks_per_cu_skyl_big = 1;  // resident work-groups per CU of the sky-light kernels ...
-  bool skyl_occupancy_known = false;  // ... asked for by the first launch that selects them (skyLightOccupancy), not at create
   bool simple3_ok = false;         // a simple world whose tables fit the three-waves-per-SIMD kernel's LDS (RTC_LDS3_*)
   void* d_csg_buf = nullptr;       // DevPixelMap::csg_buf, only for scenes with csg nodes
   size_t csg_buf_capacity = 0;     // bytes
@@ -302,7 +311,8 @@ struct rtc_scene {
     std::vector<uint32_t> key;     // the pixel map the trial belongs to
   } tune;
   bool kernel_warm = false;        // the handle's first launch has sent the render kernel ahead once with no work (launch())
-  uint32_t n_cus = 0, blocks_per_cu_lds = 1, blocks_per_cu_big = 1, blocks_per_cu_simple3 = 1;
+  uint32_t n_cus = 0, blocks_per_cu_simple3 = 1;
+  FamilyOccupancy occupancy;       // resident work-groups per CU of every family's kernels (BASE: the world's own kernel, two waves per SIMD)
   // ---- the schedule (DevPixelMap::order): two device buffers, used alternately.  d_sched[sched_cur] is what the next
   // launch runs; a measuring launch is followed by the packer's launches, which pack the other buffer from what the
   // launch measured (the first launch of a pixel map: from rtc_estimate_kernel's guesses), and the buffers swap - no host
