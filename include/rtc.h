@@ -837,6 +837,64 @@ typedef struct rtc_sky_light {
  */
 int rtc_scene_set_sky_light(rtc_scene *scene, const rtc_sky_light *sky_light);
 
+/* ---- indirect light: diffuse bounce rays and emissive materials ---- */
+/*
+ * A handle has one indirect table: a gain (finite, >= 0), bounces (0 .. RTC_MAX_DEPTH = 16), a seed and, optionally, an
+ * emission row of three finite doubles >= 0 per material (NULL: no material emits).  c runs over r, g, b.
+ *
+ * Emission.  At every hit, of a primary or a secondary ray,
+ *   s.c = s.c + emission[material].c          after the last light's, sun's and sky-light term, before the ray's weight
+ * It needs no gain and no bounces.
+ *
+ * The diffuse child.  Every ray carries d, the number of diffuse bounces on its lineage; the primary ray has d = 0, a
+ * reflected or refracted child its parent's d.  A hit forms the child when gain > 0, material.diffuse != 0.0,
+ * cur.remaining > 0 and d < bounces:
+ *   origin    = over_point
+ *   direction = the occlusion step's direction rule, unchanged (the first accepted of 32 triples, e = ng + u, d = e / m, the
+ *               two fall-backs to ng) about ng, the geometric normal after its `inside` flip - not the bumped normal, not
+ *               the mirror direction -, with J(axis) = rtc_gloss_jitter(h, (d << 17) | cur.code, axis),
+ *               h = rtc_gloss_sample_key(key', p, g), key = rtc_mix64(seed ^ 0x452821E638D01377)
+ *   remaining = cur.remaining - 1;  d + 1;  the parent's medium;  path code 2 * cur.code (the reflected child's)
+ *   weight.c  = cur.weight.c * ((color.c * material.diffuse) * gain)
+ * cur.weight is the weight after the media step, color the pattern colour the lights' loop uses at that hit.  A
+ * cosine-weighted direction has density cos / pi, so, as for the sky light, no pi and no cosine appear.  The child is an
+ * ordinary ray: traced, shaded, fogged and absorbed like any other, it forms children like any other and counts one
+ * `secondary`.  The pixel gets the sum of weight.c * s.c over every ray of its tree, as before.
+ *
+ * No sky counted twice.  Where the sky-light step ran at the parent hit (the sky light's gain > 0 and the environment has a
+ * sky), the miss step of the ray that was formed as a diffuse child adds no sky (the media step's fog term stays).  A miss
+ * of its reflected or refracted descendants adds the sky as before.
+ *
+ * Decorrelation.  At a ray with d > 0 the gloss, occlusion, sky-light and indirect draws use
+ *   key' = key ^ ((uint64_t)d * RTC_INDIRECT_DECORR)
+ * in place of their table's key; with d == 0 this is the key itself, and every draw of a handle without the table keeps its
+ * bits.  Two rays of one pixel's tree that share both path code and d share their draws: that correlates the two branches
+ * and does not bias the mean, because along one lineage the codes differ.
+ *
+ * Counts: primary as before; secondary grows by one per child; shadow_calls and shadow_traced grow by what the child's own
+ * hits count.  Only + - * / sqrt and comparisons are added, each correctly rounded, in the order written.
+ */
+#define RTC_INDIRECT_DECORR 0xBE5466CF34E90C6Dull /* odd */
+typedef struct rtc_indirect {
+  double gain;            /* the factor on a diffuse child's weight; finite, >= 0; 0: no child */
+  uint32_t bounces;       /* the most diffuse bounces on one lineage, 0 .. RTC_MAX_DEPTH; 0: no child */
+  uint64_t seed;
+  const double *emission; /* [n_materials][3], finite, >= 0; NULL: no material emits */
+  uint32_t n_materials;   /* with emission: the scene's material count */
+} rtc_indirect;
+
+/*
+ * This handle's indirect light for every render entry point.  Validated on the host before any HIP call and before anything
+ * changes: RTC_ERR_INVALID_ARGUMENT for a gain that is not finite or is negative, bounces above RTC_MAX_DEPTH, a non-NULL
+ * emission whose n_materials is not the scene's, or an emission entry that is not finite or is negative; the previous table
+ * stays in force.  NULL is no table.  The rows are copied.  A clone starts with its source's table; rtc_render's band clones
+ * follow.  The order of this setter and the others does not matter: which kernels run is decided at launch - the indirect
+ * kernels (rtc_render_kernel_indir, _indir_bigworld) when the table has gain > 0 and bounces > 0 or an emission entry that
+ * is not zero; every other handle gets the kernels it got before.  librtc_multi renders without it.  rtc_scene_desc,
+ * rtc_camera, rtc_stats and RTC_ABI_VERSION are as they were.
+ */
+int rtc_scene_set_indirect(rtc_scene *scene, const rtc_indirect *indirect);
+
 /* ---- adaptive sampling: progressive passes only for tiles still noisy ---- */
 #define RTC_ADAPTIVE_MAX_TILE 1024u
 

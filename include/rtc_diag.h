@@ -46,7 +46,8 @@ extern "C" {
  * handle's ordinary kernels'), "environment_kernels" (!= 0: the environment kernels even on a handle without an environment,
  * no sky and no sun, so that their images can be held to the handle's ordinary kernels'), "sky_light_kernels" (!= 0: the
  * sky-light kernels even on a handle without a sky light, the gain zero, so that their images can be held to the handle's
- * ordinary kernels').
+ * ordinary kernels'), "indirect_kernels" (!= 0: the indirect kernels even on a handle without an indirect table, the gain
+ * zero and no emission, so that their images can be held to the handle's ordinary kernels').
  * RTC_ERR_INVALID_ARGUMENT for a name the library does not know.
  * (The library reads no environment variables.)
  */

@@ -27,7 +27,8 @@
  *                        rtch_scene_shadow_filters, through rtc_scene_set_shadow_filters; its materials' absorption
  *                        and its atmosphere, rtch_scene_media, through rtc_scene_set_media; its environment,
  *                        rtch_scene_environment, through rtc_scene_set_environment; its sky light,
- *                        rtch_scene_sky_light, through rtc_scene_set_sky_light)
+ *                        rtch_scene_sky_light, through rtc_scene_set_sky_light; its indirect light,
+ *                        rtch_scene_indirect, through rtc_scene_set_indirect)
  *
  * Every function that returns int returns 0 on success; otherwise rtch_last_error()
  * holds "<ZigStyleErrorName>: detail" (thread-local).
@@ -126,6 +127,12 @@ int rtch_scene_environment(void *handle, rtc_environment *out, double *sun_direc
  * samples to 1, seed to 0 -, as rtc_scene_set_sky_light takes it.  *present: 1 when the file has the key; without it *out is
  * gain 0, samples 1, seed 0.  The key adds no table row.  rtch_scene_render applies it. */
 int rtch_scene_sky_light(void *handle, rtc_sky_light *out, int *present);
+/* The scene's "indirect" (DESIGN.md section 27): g, or {"gain": g, "bounces": n, "seed": s} - gain defaults to 1.0, bounces
+ * to 1, seed to 0 -, and the materials' "emission" (e, or [r, g, b]) in mat_* order, as rtc_scene_set_indirect takes them:
+ * `emission` has room for 3 * n doubles, n the description's n_materials, and *out points to it.  *present: 1 when the file
+ * has either key; without "indirect" *out is gain 0, bounces 0, seed 0.  Neither key adds a table row.  rtch_scene_render
+ * applies them. */
+int rtch_scene_indirect(void *handle, rtc_indirect *out, double *emission, int *present, uint32_t n);
 int rtch_scene_camera(void *handle, uint32_t width, uint32_t height, rtc_camera *out);
 int rtch_camera_rotate(void *handle, double angle);
 int rtch_camera_move(void *handle, double distance);

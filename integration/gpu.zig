@@ -108,6 +108,16 @@ pub const RtcSkyLight = extern struct {
     seed: u64,
 };
 pub extern fn rtc_scene_set_sky_light(scene: *RtcScene, sky_light: ?*const RtcSkyLight) c_int; // null: no sky light
+// Indirect light (rtc.h, rtc_scene_set_indirect): a diffuse child ray per diffuse hit, up to `bounces` on one lineage, and
+// what each material emits by itself.
+pub const RtcIndirect = extern struct {
+    gain: f64, // finite, >= 0; 0: no child
+    bounces: u32, // 0 .. 16
+    seed: u64,
+    emission: ?[*]const f64, // [n_materials][3], finite, >= 0; null: no material emits
+    n_materials: u32, // with emission: the scene's material count
+};
+pub extern fn rtc_scene_set_indirect(scene: *RtcScene, indirect: ?*const RtcIndirect) c_int; // null: no table
 pub extern fn rtc_grow_csg_lists(scene: *RtcScene) c_int; // after an asynchronous frame whose stats.overflow != 0 on a csg scene: longer lists, render again
 pub extern fn rtc_scatter_tile_list_device(d_tiles: [*]const f64, d_tile_list: [*]const u32, n_tiles: u32, tile_w: u32, tile_h: u32,
                                            hsize: u32, vsize: u32, canvas: [*]f64, hip_stream: ?*anyopaque) c_int; // a rank's tiles straight into a (registered host) canvas

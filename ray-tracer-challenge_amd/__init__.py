@@ -221,7 +221,8 @@ BUMP_NONE, BUMP_NOISE, BUMP_RIPPLES = 0, 1, 2  # RTC_BUMP_*
 RTC_SPHERE, RTC_PLANE, RTC_CUBE, RTC_CYLINDER, RTC_TRIANGLE, RTC_SMOOTH_TRIANGLE, RTC_CONE, RTC_TORUS = range(8)
 # the options that select a kernel family on a handle that does not need it (set_option; tests and tools/time_scenes.py)
 KERNEL_OPTIONS = ("sampling_kernels", "motion_kernels", "spot_kernels", "bump_kernels", "torus_kernels", "meshuv_kernels", "gloss_kernels",
-                  "occlusion_kernels", "shadow_filter_kernels", "media_kernels", "environment_kernels", "sky_light_kernels")
+                  "occlusion_kernels", "shadow_filter_kernels", "media_kernels", "environment_kernels", "sky_light_kernels",
+                  "indirect_kernels")
 SKY_LIGHT_MAX_SAMPLES = 64  # RTC_SKY_LIGHT_MAX_SAMPLES
 ENV_NO_PATTERN, ENV_SPHERE, ENV_CUBE, ENV_MAX_SUNS = 0xFFFFFFFF, 0, 1, 16  # RTC_ENV_*
 NO_MEDIUM = 0xFFFFFFFF  # RTC_NO_MEDIUM: a ray in the atmosphere
@@ -369,6 +370,29 @@ def sky_light_struct(light):
     return SkyLight(float(light.get("gain", 1.0)), int(light.get("samples", 1)), int(light.get("seed", 0)))
 
 
+class Indirect(C.Structure):
+    """struct rtc_indirect (include/rtc.h): the factor on a diffuse child's weight, the most diffuse bounces on one lineage,
+    the draws' seed, and three doubles per material row that the material emits by itself (NULL: none)."""
+
+    _fields_ = [("gain", C.c_double), ("bounces", C.c_uint32), ("seed", C.c_uint64), ("emission", C.POINTER(C.c_double)),
+                ("n_materials", C.c_uint32)]
+
+
+def indirect_struct(indirect):
+    """(Indirect, the array it points into) of a dict of "gain" (1.0), "bounces" (1), "seed" (0) and "emission" ((n, 3);
+    None: no rows) (GpuScene.set_indirect); the array must outlive the struct's use."""
+    e = indirect.get("emission")
+    n = 0
+    if e is not None:
+        e = np.ascontiguousarray(e, dtype=np.float64)
+        if e.ndim != 2 or e.shape[1] != 3:
+            raise ValueError(f"indirect: an emission array of shape {e.shape}, (n, 3) expected")
+        n = e.shape[0]
+    d = Indirect(float(indirect.get("gain", 1.0)), int(indirect.get("bounces", 1)), int(indirect.get("seed", 0)),
+                 e.ctypes.data_as(C.POINTER(C.c_double)) if e is not None else None, int(indirect.get("n_materials", n)))
+    return d, e
+
+
 class Bump(C.Structure):
     """struct rtc_bump (include/rtc.h): a bump per material row (kind BUMP_NONE: the material as it is)."""
 
@@ -411,14 +435,15 @@ RTC_SYMBOLS = ["rtc_scene_create", "rtc_scene_clone", "rtc_scene_destroy", "rtc_
                "rtc_scene_adaptive_begin_device", "rtc_scene_adaptive_accumulate_device", "rtc_scene_adaptive_step", "rtc_render_adaptive",
                "rtc_scene_set_spots", "rtc_scene_set_bumps", "rtc_scene_set_mesh_uvs", "rtc_scene_set_gloss",
                "rtc_scene_set_occlusion", "rtc_scene_set_shadow_filters", "rtc_scene_set_media", "rtc_scene_set_environment",
-               "rtc_scene_set_sky_light"]
+               "rtc_scene_set_sky_light", "rtc_scene_set_indirect"]
 # (... and include/rtc_diag.h: diagnostics and tuning, for the tests, bench.py and tools/)
 RTC_DIAG_SYMBOLS = ["rtc_set_option", "rtc_last_kernel_name", "rtc_get_schedule", "rtc_get_chunk_times", "rtc_diag_build_tables", "rtc_diag_root_boxes", "rtc_diag_root_spheres"]
 HOST_SYMBOLS = ["rtch_last_error", "rtch_scene_load", "rtch_scene_free", "rtch_scene_desc", "rtch_scene_camera",
                 "rtch_camera_rotate", "rtch_camera_move", "rtch_camera_make", "rtch_canvas_ppm", "rtch_canvas_rgba8", "rtch_scene_render", "rtch_set_loader_threads",
                 "rtch_scene_lights", "rtch_scene_sampling", "rtch_scene_passes", "rtch_scene_motion", "rtch_scene_adaptive",
                 "rtch_scene_spots", "rtch_scene_bumps", "rtch_scene_mesh_uvs", "rtch_scene_gloss", "rtch_scene_occlusion",
-                "rtch_scene_shadow_filters", "rtch_scene_media", "rtch_scene_environment", "rtch_scene_sky_light"]
+                "rtch_scene_shadow_filters", "rtch_scene_media", "rtch_scene_environment", "rtch_scene_sky_light",
+                "rtch_scene_indirect"]
 
 MULTI_SYMBOLS = ["rtc_multi_create", "rtc_multi_destroy", "rtc_multi_render", "rtc_multi_render_rgba8", "rtc_multi_render_device", "rtc_multi_render_rgba8_device",
                  "rtc_multi_synchronize", "rtc_multi_stream", "rtc_multi_get_stats", "rtc_multi_balance", "rtc_multi_last_error"]
@@ -487,6 +512,7 @@ def hip_lib():
         lib.rtc_scene_set_media.argtypes = [C.c_void_p, C.POINTER(Media)]
         lib.rtc_scene_set_environment.argtypes = [C.c_void_p, C.POINTER(Environment)]
         lib.rtc_scene_set_sky_light.argtypes = [C.c_void_p, C.POINTER(SkyLight)]
+        lib.rtc_scene_set_indirect.argtypes = [C.c_void_p, C.POINTER(Indirect)]
         lib.rtc_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.POINTER(Adaptive), C.c_void_p, C.c_void_p]
         lib.rtc_scene_destroy.argtypes = [C.c_void_p]
         lib.rtc_scene_destroy.restype = None
@@ -548,6 +574,7 @@ def host_lib():
         lib.rtch_scene_media.argtypes = [C.c_void_p, _dp, _dp, C.POINTER(C.c_int), C.c_uint32]
         lib.rtch_scene_environment.argtypes = [C.c_void_p, C.POINTER(Environment), _dp, _dp, C.POINTER(C.c_int)]
         lib.rtch_scene_sky_light.argtypes = [C.c_void_p, C.POINTER(SkyLight), C.POINTER(C.c_int)]
+        lib.rtch_scene_indirect.argtypes = [C.c_void_p, C.POINTER(Indirect), _dp, C.POINTER(C.c_int), C.c_uint32]
         lib.rtch_scene_adaptive.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(Adaptive)]
         lib.rtch_scene_camera.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Camera)]
         lib.rtch_camera_rotate.argtypes = [C.c_void_p, C.c_double]
@@ -810,6 +837,17 @@ class HostScene:
             return None
         return {"gain": float(y.gain), "samples": int(y.samples), "seed": int(y.seed)}
 
+    def indirect(self):
+        """The scene's "indirect" and the materials' "emission" rows, in mat_* order (rtch_scene_indirect): a dict of "gain",
+        "bounces", "seed" and "emission" (n, 3) - what GpuScene.set_indirect takes -, or None when the file has neither key."""
+        n = self.desc.n_materials
+        d, e = Indirect(), np.zeros((n, 3))
+        present = C.c_int()
+        _check_host(host_lib().rtch_scene_indirect(self._h, C.byref(d), e.ctypes.data_as(_dp), C.byref(present), n))
+        if not present.value:
+            return None
+        return {"gain": float(d.gain), "bounces": int(d.bounces), "seed": int(d.seed), "emission": e}
+
     def adaptive(self):
         """The camera's "sampling": {"adaptive": ...} of the scene file (rtch_scene_adaptive): an Adaptive whose max_passes
         is "passes", or None when the file has none."""
@@ -981,6 +1019,16 @@ class GpuScene:
             return
         y = sky_light_struct(light)
         _check_hip(hip_lib().rtc_scene_set_sky_light(self._s, C.byref(y)))
+
+    def set_indirect(self, indirect):
+        """rtc_scene_set_indirect: a dict of "gain", "bounces", "seed" and "emission" ((n_materials, 3) or None)
+        (HostScene.indirect()); None: no table - as a table that forms no child and emits nothing, the handle's previous
+        kernels."""
+        if indirect is None:
+            _check_hip(hip_lib().rtc_scene_set_indirect(self._s, None))
+            return
+        d, _keep = indirect_struct(indirect)
+        _check_hip(hip_lib().rtc_scene_set_indirect(self._s, C.byref(d)))
 
     def accumulate_device(self, accum, stream=None):
         """rtc_scene_accumulate_device: an Accum, enqueued on `stream` (None: the handle's own) after this handle's renders."""

@@ -225,6 +225,22 @@ __global__ void rtc_render_kernel_skyl_bigworld(const DevScene S, const DevCamer
                                                 const DevShadowFilter sfilt, const DevMedia media, const DevEnvironment env,
                                                 const DevSkyLight skyl);
 }
+// The indirect kernels (rtc_scene_set_indirect: diffuse bounce rays and emissive materials): the sky-light kernels' tables and
+// fifth quarter, and the gain, the hash key, the bounce limit and the emission rows (DevIndirect) as one more argument.
+extern "C" {
+__global__ void rtc_render_kernel_indir(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                        double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                        const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                        const DevBumps bumps, const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl,
+                                        const DevShadowFilter sfilt, const DevMedia media, const DevEnvironment env,
+                                        const DevSkyLight skyl, const DevIndirect indir);
+__global__ void rtc_render_kernel_indir_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                                 double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                                 const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                                 const DevBumps bumps, const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl,
+                                                 const DevShadowFilter sfilt, const DevMedia media, const DevEnvironment env,
+                                                 const DevSkyLight skyl, const DevIndirect indir);
+}
 // Progressive rendering's accumulation (rtc_accum.hip): the grid's blocks for n pixels (the noise partials it writes, at
 // most) and the enqueue of its kernels.
 uint32_t rtcAccumBlocks(size_t n_pixels, bool wide);
@@ -442,6 +458,10 @@ bool tablesInLds(const rtc_scene* s) {
 // cleared, and a clone or a band clone, which holds its source's tables and flags, selects what its source does.
 Family family(const rtc_scene* s) {
   const RtcOptions& o = rtcOptions();
+  // The indirect kernels run when the handle's indirect table can form a diffuse child (gain > 0 and bounces > 0) or holds an
+  // emission entry that is not zero (rtc_scene_set_indirect keeps no other table) - whatever else the handle holds: they are
+  // the sky-light walk - or, for tests, whenever option "indirect_kernels" is set.
+  if (s->indirect != nullptr || o.indirect_kernels != 0.0) return Family::INDIR;
   // The sky-light kernels run when the handle has a sky light AND an environment with a sky - decided here, launch by launch,
   // so the order of the two setters does not matter, and a sky light without a sky keeps the kernels the handle had - whatever
   // else the handle holds: they are the environment walk - or, for tests, whenever option "sky_light_kernels" is set.
@@ -509,6 +529,7 @@ struct LaunchArgs {
   DevMedia media;
   DevEnvironment env;
   DevSkyLight skyl;
+  DevIndirect indir;
 };
 // ... from the handle, for a launch of family `f` with the scene `dev` (the handle's, or its copy for an empty dispatch).
 LaunchArgs launchArgs(const rtc_scene* s, Family f, const DevScene& dev, const DevCamera& cam) {
@@ -568,6 +589,9 @@ LaunchArgs launchArgs(const rtc_scene* s, Family f, const DevScene& dev, const D
   // (the handle's sky light, or a gain of zero)
   const SkyLightTable* y = s->sky_light.get();
   a.skyl = DevSkyLight{y ? y->gain : 0.0, y ? y->key : 0ull, y ? y->samples : 1u};
+  // (the handle's indirect light, or a gain of zero and no emission rows)
+  a.indir = DevIndirect{0.0, 0ull, nullptr, 0u};
+  if (const IndirectTables* t = s->indirect.get()) a.indir = DevIndirect{t->gain, t->key, t->emits ? t->emission.p : nullptr, t->bounces};
   return a;
 }
 
@@ -596,6 +620,7 @@ hipError_t forFamilyKernel(const rtc_scene* s, const KernelChoice& c, const Laun
     case Family::MEDIA: RTC_KERNEL_PAIR(rtc_render_kernel_media, a.area, a.smp, a.mo, a.spots, a.bumps, a.muv, a.gloss, a.occl, a.sfilt, a.media);
     case Family::ENV: RTC_KERNEL_PAIR(rtc_render_kernel_env, a.area, a.smp, a.mo, a.spots, a.bumps, a.muv, a.gloss, a.occl, a.sfilt, a.media, a.env);
     case Family::SKYL: RTC_KERNEL_PAIR(rtc_render_kernel_skyl, a.area, a.smp, a.mo, a.spots, a.bumps, a.muv, a.gloss, a.occl, a.sfilt, a.media, a.env, a.skyl);
+    case Family::INDIR: RTC_KERNEL_PAIR(rtc_render_kernel_indir, a.area, a.smp, a.mo, a.spots, a.bumps, a.muv, a.gloss, a.occl, a.sfilt, a.media, a.env, a.skyl, a.indir);
   }
   return hipErrorInvalidValue;  // (no such family)
 }
@@ -961,8 +986,17 @@ int packNextSchedule(rtc_scene* s, const rtc_camera& cam, const DevPixelMap& map
 
 // Per-launch scratch in HBM, grown on demand: the lanes' pending-ray stacks ([wave][level][lane], 64 B each) and,
 // for scenes with csg, the lanes' intersection lists.
+// The levels of a lane's pending-ray stack.  A hit forms at most two children, one of which continues in registers: a
+// depth-first walk holds at most one waiting ray per level of the tree, and max_depth + 2 is what every family had.  A hit of
+// the indirect kernels may form three and pushes at most two; every ray on the stack waits at a tree level 1 .. max_depth
+// and a level's hit is shaded once per walk down, so at most 2 * max_depth wait at once: 2 * max_depth + 2 levels.
+uint32_t rayStackLevels(const rtc_scene* s, uint32_t max_depth) {
+  return family(s) == Family::INDIR ? 2u * max_depth + 2u : max_depth + 2u;
+}
+
 int ensureScratch(rtc_scene* s, DevPixelMap& map, uint32_t blocks, uint32_t max_depth) {
-  const size_t need = static_cast<size_t>(blocks) * 4u * (max_depth + 2u) * 64u * 64u;
+  const uint32_t levels = rayStackLevels(s, max_depth);
+  const size_t need = static_cast<size_t>(blocks) * 4u * levels * 64u * 64u;
   if (need > s->ray_stack_capacity) {
     HIP_TRY(handleIdle(s));  // (the last launch may still be using the old buffer)
     if (s->d_ray_stack) (void)hipFree(s->d_ray_stack);
@@ -985,7 +1019,7 @@ int ensureScratch(rtc_scene* s, DevPixelMap& map, uint32_t blocks, uint32_t max_
     }
   }
   map.ray_stack = static_cast<PendingRec*>(s->d_ray_stack);
-  map.ray_stack_levels = max_depth + 2u;
+  map.ray_stack_levels = levels;
 #ifdef RTC_PROFILE
   map.ray_stack_waves = static_cast<uint32_t>(s->ray_stack_capacity / (static_cast<size_t>(map.ray_stack_levels) * 64u * 64u));
 #endif
@@ -3229,6 +3263,51 @@ int rtc_scene_set_sky_light(rtc_scene* s, const rtc_sky_light* y) {
   return replaceTables(s, &rtc_scene::sky_light, table, false);
 }
 
+// ---- indirect light
+// Validated on the host before any HIP call and before anything changes: first the table's own values - so that they are
+// checked whatever the handle -, then its material count against the handle's.  NULL is no table; a table that can form no
+// child (a gain or a bounce limit of zero) and whose emission is NULL or all zeros is none either: the handle's previous
+// kernels.
+int rtc_scene_set_indirect(rtc_scene* s, const rtc_indirect* d) {
+  g_error.clear();
+  if (!s) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
+  bool emits = false, bounce = false;
+  std::vector<double> rows;
+  if (d) {
+    if (!std::isfinite(d->gain)) return fail(RTC_ERR_INVALID_ARGUMENT, "indirect: a gain that is not finite");
+    if (d->gain < 0.0) return fail(RTC_ERR_INVALID_ARGUMENT, "indirect: gain %g is negative", d->gain);
+    if (d->bounces > static_cast<uint32_t>(RTC_MAX_DEPTH))
+      return fail(RTC_ERR_INVALID_ARGUMENT, "indirect: %u bounces, at most %d", d->bounces, RTC_MAX_DEPTH);
+    if (d->emission) {
+      const uint32_t n = d->n_materials;
+      for (uint32_t i = 0; i < n; ++i)
+        for (uint32_t c = 0; c < 3u; ++c) {
+          const double v = d->emission[3ull * i + c];
+          if (!std::isfinite(v)) return fail(RTC_ERR_INVALID_ARGUMENT, "indirect: material %u: an emission that is not finite", i);
+          if (v < 0.0) return fail(RTC_ERR_INVALID_ARGUMENT, "indirect: material %u: emission %g is negative", i, v);
+          emits = emits || v != 0.0;
+        }
+      if (n != s->dev.n_materials) return fail(RTC_ERR_INVALID_ARGUMENT, "indirect: n_materials %u, the scene has %u", n, s->dev.n_materials);
+      if (emits) rows.assign(d->emission, d->emission + 3ull * n);
+    }
+    bounce = d->gain > 0.0 && d->bounces > 0u;
+  }
+  std::shared_ptr<const IndirectTables> tables;  // (no child and no emission: none)
+  if (bounce || emits) {
+    auto t = std::make_shared<IndirectTables>();
+    t->gain = d->gain;
+    t->bounces = d->bounces;
+    t->key = rtc_mix64(d->seed ^ RTC_INDIRECT_SALT);
+    t->emits = emits;
+    if (emits) {
+      HIP_TRY(hipSetDevice(s->device));
+      HIP_TRY(t->emission.upload(rows));
+    }
+    tables = std::move(t);
+  }
+  return replaceTables(s, &rtc_scene::indirect, tables);
+}
+
 // ---- adaptive sampling
 // The setting's own fields, and the image's tile count (T < 2^31)
 static int checkAdaptive(const rtc_adaptive* a, uint32_t hsize, uint32_t vsize, uint32_t* n_tiles) {
@@ -3442,6 +3521,7 @@ int rtc_scene_clone(const rtc_scene* src, rtc_scene** out) {
   s->media = src->media;  // (shared: read-only once made; the fifth-quarter buffer is the handle's own, made at its first launch)
   s->environment = src->environment;  // (shared: read-only once made)
   s->sky_light = src->sky_light;  // (shared: read-only once made)
+  s->indirect = src->indirect;    // (shared: read-only once made)
   s->simple_kernel = src->simple_kernel;
   s->flat_kernel = src->flat_kernel;
   s->simple3_ok = src->simple3_ok;
@@ -3863,7 +3943,8 @@ int rtc_set_option(const char* name, double value) {
                {"torus_kernels", &o.torus_kernels}, {"meshuv_kernels", &o.meshuv_kernels},
                {"gloss_kernels", &o.gloss_kernels}, {"occlusion_kernels", &o.occlusion_kernels},
                {"shadow_filter_kernels", &o.shadow_filter_kernels}, {"media_kernels", &o.media_kernels},
-               {"environment_kernels", &o.environment_kernels}, {"sky_light_kernels", &o.sky_light_kernels}};
+               {"environment_kernels", &o.environment_kernels}, {"sky_light_kernels", &o.sky_light_kernels},
+               {"indirect_kernels", &o.indirect_kernels}};
   for (const auto& e : table)
     if (std::strcmp(e.name, name) == 0) {
       e.slot->set(value);

@@ -446,6 +446,21 @@ struct DevSkyLight {
   uint32_t samples;
 };
 
+// Indirect light (rtc_scene_set_indirect): the extra argument of the indirect kernels only.  `gain`: the
+// factor on a diffuse child's weight (0: no child is formed - a handle without a table, or the "indirect_kernels" option);
+// `bounces`: the most diffuse bounces on one lineage, 0 .. RTC_MAX_DEPTH; key = rtc_mix64(seed ^ RTC_INDIRECT_SALT); the
+// child's draws are rtc_gloss_sample_key's and rtc_gloss_jitter's at word (d << RTC_OCCLUSION_SAMPLE_SHIFT) | code.
+// `emission`: [n_materials][3], or null: no material emits.  At a ray with d diffuse bounces on its lineage the gloss,
+// occlusion, sky-light and indirect keys are key ^ (d * RTC_INDIRECT_DECORR).
+#define RTC_INDIRECT_SALT 0x452821E638D01377ull
+#define RTC_INDIRECT_DECORR 0xBE5466CF34E90C6Dull /* rtc.h's, token for token */
+struct DevIndirect {
+  double gain;
+  unsigned long long key;
+  const double* __restrict__ emission;
+  uint32_t bounces;
+};
+
 struct DevCamera {
   double half_width, half_height, pixel_size;
   double inv[12];  // rows 0..2 of Camera._inverse_transform

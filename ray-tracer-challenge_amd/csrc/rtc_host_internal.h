@@ -77,6 +77,7 @@ struct RtcOptions {
   RtcOption media_kernels{0.0};        // != 0: the media kernels even on a handle without media, every row and the density zero (tests: against the handle's ordinary kernels)
   RtcOption environment_kernels{0.0};  // != 0: the environment kernels even on a handle without an environment, no sky and no sun (tests: against the handle's ordinary kernels)
   RtcOption sky_light_kernels{0.0};    // != 0: the sky-light kernels even on a handle without a sky light, the gain zero (tests: against the handle's ordinary kernels)
+  RtcOption indirect_kernels{0.0};     // != 0: the indirect kernels even on a handle without an indirect table, the gain zero and no emission (tests: against the handle's ordinary kernels)
   RtcOption build_threads{0.0};        // threads of rtc_scene_create's candidate-BVH build (one top-level group each); 0: as many as the host allows, up to 8
 };
 inline RtcOptions& rtcOptions() {
@@ -206,6 +207,16 @@ struct SkyLightTable {
   unsigned long long key = 0ull;  // rtc_mix64(seed ^ RTC_SKY_LIGHT_SALT)
 };
 
+// A handle's indirect light (rtc_scene_set_indirect): DevIndirect's values, and the emission rows on the device (empty:
+// no material emits).  Read-only once made: a clone and the band clones share it.
+struct IndirectTables {
+  double gain = 0.0;
+  uint32_t bounces = 0u;
+  unsigned long long key = 0ull;  // rtc_mix64(seed ^ RTC_INDIRECT_SALT)
+  DevBuf<double> emission;        // [n_materials][3]; empty without rows
+  bool emits = false;             // an emission entry is not zero
+};
+
 // A handle's spot lights (rtc_scene_set_spots): DevSpots::row.  Read-only once made: a clone and the band clones share it.
 struct SpotTables {
   DevBuf<double> row;
@@ -227,12 +238,12 @@ constexpr uint32_t RTC_MAX_HOST_BANDS = 4;
 // The render kernels' launch families, lowest priority first: a launch runs the highest family whose condition holds
 // (family() in rtc_capi.hip, which also names every family's kernel pair and its arguments - forFamilyKernel).  Each takes
 // the arguments of the one below and, but for TORUS, one more.
-enum class Family : uint32_t { BASE, MS, MOTION, SPOT, BUMP, TORUS, MESHUV, GLOSS, OCCL, SFILT, MEDIA, ENV, SKYL };
-constexpr uint32_t RTC_FAMILIES = 13;
+enum class Family : uint32_t { BASE, MS, MOTION, SPOT, BUMP, TORUS, MESHUV, GLOSS, OCCL, SFILT, MEDIA, ENV, SKYL, INDIR };
+constexpr uint32_t RTC_FAMILIES = 14;
 // A family whose occupancy is asked for by the first launch that selects it and not at create: the query loads the unit's
-// code object, and a process none of whose handles has a sky light loads, allocates and runs what it did before the unit
-// existed.
-constexpr bool familyIsLazy(Family f) { return f == Family::SKYL; }
+// code object, and a process none of whose handles has a sky light - or an indirect table - loads, allocates and runs what
+// it did before the unit existed.
+constexpr bool familyIsLazy(Family f) { return f == Family::SKYL || f == Family::INDIR; }
 
 // Resident work-groups per CU of every family's kernels, [family][tables in LDS ? 0 : 1], and whether they have been asked
 // for (at create, or for a lazy family at its first launch).  A clone takes its source's.
@@ -284,6 +295,7 @@ struct rtc_scene {
   std::shared_ptr<const MediaTables> media;  // rtc_scene_set_media; null: no absorbing row and no fog (a clone starts with its source's)
   std::shared_ptr<const EnvironmentTables> environment;  // rtc_scene_set_environment; null: no sky and no sun (a clone starts with its source's)
   std::shared_ptr<const SkyLightTable> sky_light;  // rtc_scene_set_sky_light; null: no gain (a clone starts with its source's)
+  std::shared_ptr<const IndirectTables> indirect;  // rtc_scene_set_indirect; null: no child and no emission (a clone starts with its source's)
   bool simple3_ok = false;         // a simple world whose tables fit the three-waves-per-SIMD kernel's LDS (RTC_LDS3_*)
   void* d_csg_buf = nullptr;       // DevPixelMap::csg_buf, only for scenes with csg nodes
   size_t csg_buf_capacity = 0;     // bytes

@@ -2710,8 +2710,30 @@ struct Pending {
   double weight_g, weight_b;
   uint32_t medium;
 #endif
+#ifdef RTC_INDIR_TU
+  // (INDIRECT) the ray's lineage: d, the diffuse bounces on it (bits 0-4: at most RTC_MAX_DEPTH), and
+  // RTC_LIN_DIFFUSE where the ray itself was formed as a diffuse child.  It rides in the seven spare bits of the 24-bit code
+  // field, above the path code's 17: the record and its fifth quarter stay.  Compiled into the indirect kernels' unit only.
+  uint32_t lin;
+#endif
 };
-#ifdef RTC_MEDIA_TU
+#ifdef RTC_INDIR_TU
+static_assert(RTC_MAX_DEPTH < 32, "a Pending's lineage has five bits for its diffuse bounces");
+static_assert(RTC_MAX_DEPTH + 1 <= 17, "the path code stays below 2^17: the lineage rides above it");
+#define RTC_LIN_D 31u
+#define RTC_LIN_DIFFUSE 32u
+#define RTC_PENDING_TAIL(p)                                                                                           \
+  (static_cast<unsigned long long>((p).remaining) | (static_cast<unsigned long long>((p).code | ((p).lin << 17)) << 8) | \
+   (static_cast<unsigned long long>((p).medium) << 32))
+#define RTC_PENDING_REMAINING(word) (static_cast<uint32_t>(word) & 0xFFu)
+#define RTC_PENDING_CODE(p, word)                                                                                  \
+  (p).code = (static_cast<uint32_t>(word) >> 8) & 0x1FFFFu, (p).lin = (static_cast<uint32_t>(word) >> 25) & 0x7Fu, \
+  (p).medium = static_cast<uint32_t>((word) >> 32)
+#define RTC_SET_CODE(p, c) (p).code = (c)
+#define RTC_SET_LIN(p, v) (p).lin = (v)
+// (the draws of a ray with d diffuse bounces on its lineage: key ^ (d * RTC_INDIRECT_DECORR); d == 0: the key itself)
+#define RTC_DKEY(k) ((k) ^ (static_cast<unsigned long long>(cur.lin & RTC_LIN_D) * RTC_INDIRECT_DECORR))
+#elif defined(RTC_MEDIA_TU)
 static_assert(RTC_MAX_DEPTH < 256, "a Pending's `remaining` has eight bits beside the path code and the medium");
 #define RTC_PENDING_TAIL(p) \
   (static_cast<unsigned long long>((p).remaining) | (static_cast<unsigned long long>((p).code) << 8) | (static_cast<unsigned long long>((p).medium) << 32))
@@ -2728,6 +2750,10 @@ static_assert(RTC_MAX_DEPTH < 256, "a Pending's `remaining` has eight bits besid
 #define RTC_PENDING_REMAINING(word) static_cast<uint32_t>(word)
 #define RTC_PENDING_CODE(p, word)
 #define RTC_SET_CODE(p, c)
+#endif
+#ifndef RTC_INDIR_TU
+#define RTC_SET_LIN(p, v) (void)0
+#define RTC_DKEY(k) (k)
 #endif
 // (MEDIA) what the media unit adds where a ray is made, weighted or moved; nothing in every other unit
 #ifdef RTC_MEDIA_TU
@@ -3020,9 +3046,13 @@ __device__ __noinline__ GlossDir occl_direction(unsigned long long h, uint32_t w
 // the sky through cosine-weighted hemisphere rays that are walked as a sun's shadow ray is, and the mean is added after the
 // suns' loop.  With ENV and everything below it, compiled into the sky-light kernels' translation unit only, under
 // RTC_SKYL_TU, which implies RTC_ENV_TU)
+// (INDIRECT: indirect light - DevIndirect, the indirect kernels' extra argument: every hit adds its material's emission row, and
+// a hit of a material with a diffuse term forms a third child, a cosine-weighted direction of the geometric normal's
+// hemisphere by occl_direction, which the main loop traces like every other Pending.  With SKYL and everything below it,
+// compiled into the indirect kernels' translation unit only, under RTC_INDIR_TU, which implies RTC_SKYL_TU)
 template <bool LDS, bool CSG, int WORLD = 0, int WAVES = 2, bool COOP = false, bool BOX = true, bool AREA = false, bool MS = false,
           bool MOTION = false, bool SPOT = false, bool BUMP = false, bool TORUS = false, bool MESHUV = false, bool GLOSS = false,
-          bool OCCL = false, bool SFILT = false, bool MEDIA = false, bool ENV = false, bool SKYL = false>
+          bool OCCL = false, bool SFILT = false, bool MEDIA = false, bool ENV = false, bool SKYL = false, bool INDIRECT = false>
 __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& cam, const DevPixelMap& map,
                                             const uint32_t max_depth, double* __restrict__ out,
                                             DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
@@ -3033,7 +3063,8 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
                                             const DevShadowFilter& sfilt = DevShadowFilter{},
                                             const DevMedia& media = DevMedia{},
                                             const DevEnvironment& env = DevEnvironment{},
-                                            const DevSkyLight& skyl = DevSkyLight{}) {
+                                            const DevSkyLight& skyl = DevSkyLight{},
+                                            const DevIndirect& indir = DevIndirect{}) {
   static_assert(!AREA || !COOP, "the area kernels run no cooperative iterations");
   static_assert(!MS || !COOP, "the sampling kernels run no cooperative iterations");
   static_assert(!MOTION || (MS && AREA && WORLD == 0), "the motion kernels are the general area-sampling walk");
@@ -3094,6 +3125,14 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
 #else
   static_assert(!SKYL, "the sky light is compiled in the sky-light translation unit (rtc_skylight.hip) only");
   (void)skyl;
+#endif
+  static_assert(!INDIRECT || SKYL, "the indirect kernels are the sky-light walk");
+  static_assert(!INDIRECT || !COOP, "a cooperative iteration's Yield holds two children: a hit of the indirect kernels may form three");
+#ifdef RTC_INDIR_TU
+  static_assert(INDIRECT, "the indirect translation unit compiles the indirect kernels only: its Pending carries the lineage");
+#else
+  static_assert(!INDIRECT, "indirect light is compiled in the indirect translation unit (rtc_indirect.hip) only");
+  (void)indir;
 #endif
   RTC_PRIO_PHASE(RTC_PRIO_WORK);
 #ifndef RTC_PROFILE
@@ -3292,6 +3331,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
   cur.weight = 0.0;
   cur.remaining = 0u;
   RTC_SET_CODE(cur, 0u);
+  RTC_SET_LIN(cur, 0u);
   RTC_MEDIA_START(cur, 0.0);
   // The lane's pending refraction siblings: a deque.  The lane itself pops the newest entry (depth
   // first); an idle neighbour may take the OLDEST one (the largest sub-tree) through the mailbox.
@@ -3602,6 +3642,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
         RTC_MEDIA_START(cur, smp.weight);  // (MEDIA: the camera stands in the atmosphere)
         cur.remaining = max_depth;
         RTC_SET_CODE(cur, 1u);  // (GLOSS) the primary ray
+        RTC_SET_LIN(cur, 0u);   // (INDIRECT) no diffuse bounce yet
         have_cur = true;
         has_pixel = true;
         n_primary++;
@@ -3632,6 +3673,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
       RTC_MEDIA_START(cur, 1.0);
       cur.remaining = max_depth;
       RTC_SET_CODE(cur, 1u);  // (GLOSS) the primary ray
+      RTC_SET_LIN(cur, 0u);   // (INDIRECT) no diffuse bounce yet
       have_cur = true;
       has_pixel = true;
       shared = false;
@@ -3764,7 +3806,14 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
     if constexpr (ENV) {
       const bool missed = hv.leaf == RTC_NO_LEAF;
       if (env.sky != 0u && __any(missed)) {
+#ifdef RTC_INDIR_TU
+        // (INDIRECT) where the sky-light step ran at its parent's hit, a diffuse child's own miss adds no sky: the step
+        // counted it.  Only the ray formed as a diffuse child; its reflected and refracted descendants add the sky as before.
+        const bool sky_counted = INDIRECT && (cur.lin & RTC_LIN_DIFFUSE) != 0u && skyl.gain > 0.0;
+        if (missed && !sky_counted) {
+#else
         if (missed) {
+#endif
           double e_r = env.rgb[0], e_g = env.rgb[1], e_b = env.rgb[2];
           if (env.pattern != RTC_ENV_NO_PATTERN) {
             const double len = env.projection == RTC_ENV_CUBE
@@ -4035,7 +4084,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
         uint32_t opx, opy;
         map_pixel(map, out_index, opx, opy);
         const unsigned long long occl_h = rtc_gloss_sample_key(
-            occl.key, static_cast<unsigned long long>(opy) * cam.hsize + opx,
+            RTC_DKEY(occl.key), static_cast<unsigned long long>(opy) * cam.hsize + opx,
             static_cast<unsigned long long>(smp.sample_base) + (*samp_word & RTC_SAMPLE_MASK));
         uint32_t clear = 0u;
         for (uint32_t k = 0u; k < occl.samples; ++k) {
@@ -4055,6 +4104,9 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
 #endif
     // ---- World.shadeHit, lights loop (world.zig:89-96)
     double sr = 0.0, sg = 0.0, sb = 0.0;
+#ifdef RTC_INDIR_TU
+    double ind_r = 0.0, ind_g = 0.0, ind_b = 0.0;  // (INDIRECT) colour * diffuse of this hit, for the diffuse child's weight
+#endif
     {
       const DevMaterial& mat = mats[mat_index];
       // Pattern.patternAtShape (pattern.zig:128-131) looks the colour up at over_point in object space - but a world all of
@@ -4410,7 +4462,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
         if (sky_lane) {
           uint32_t kpx, kpy;
           map_pixel(map, out_index, kpx, kpy);
-          skyl_h = rtc_gloss_sample_key(skyl.key, static_cast<unsigned long long>(kpy) * cam.hsize + kpx,
+          skyl_h = rtc_gloss_sample_key(RTC_DKEY(skyl.key), static_cast<unsigned long long>(kpy) * cam.hsize + kpx,
                                         static_cast<unsigned long long>(smp.sample_base) + (*samp_word & RTC_SAMPLE_MASK));
         }
         double l_r = 0.0, l_g = 0.0, l_b = 0.0;
@@ -4507,6 +4559,21 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
       }
 #endif
 #endif
+#ifdef RTC_INDIR_TU
+      // (INDIRECT, rtc.h's rtc_scene_set_indirect) the material's emission row, after the last light's, sun's and sky-light
+      // term and before the ray's weight; a handle without rows has a null pointer (wave-uniform)
+      if constexpr (INDIRECT) {
+        if (indir.emission != nullptr) {
+          const double* __restrict__ EM = indir.emission + 3ull * mat_index;
+          sr = sr + EM[0];
+          sg = sg + EM[1];
+          sb = sb + EM[2];
+        }
+        ind_r = color.r * mat.diffuse;
+        ind_g = color.g * mat.diffuse;
+        ind_b = color.b * mat.diffuse;
+      }
+#endif
       if constexpr (COOP) {
         if (deal_lights) {  // the other half's light (lane i <-> 7 - i pairs the halves), and what it counted
           sr = sr + group8_other<2>(sr);
@@ -4534,7 +4601,13 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
     const DevMaterial& mat = mats[mat_index];
     const bool do_reflect = !(mat.reflective == 0.0);
     const bool transparent = !(mat.transparency == 0.0);
+#ifdef RTC_INDIR_TU
+    // (INDIRECT) the diffuse child's conditions; cur.remaining > 0 holds here
+    const bool do_diffuse = INDIRECT && indir.gain > 0.0 && mat.diffuse != 0.0 && (cur.lin & RTC_LIN_D) < indir.bounces;
+    if (!do_reflect && !transparent && !do_diffuse) continue;
+#else
     if (!do_reflect && !transparent) continue;
+#endif
 
     const double cos_i = (ex * hx + ey * hy) + ez * hz;  // eyev.dot(normal)
     double w_reflect = mat.reflective, w_refract = mat.transparency;
@@ -4585,7 +4658,44 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
         uint32_t px, py;
         map_pixel(map, out_index, px, py);
         const unsigned long long p = static_cast<unsigned long long>(py) * cam.hsize + px;
-        gloss_h = rtc_gloss_sample_key(gloss.key, p, static_cast<unsigned long long>(smp.sample_base) + (*samp_word & RTC_SAMPLE_MASK));
+        gloss_h = rtc_gloss_sample_key(RTC_DKEY(gloss.key), p, static_cast<unsigned long long>(smp.sample_base) + (*samp_word & RTC_SAMPLE_MASK));
+      }
+    }
+#endif
+#ifdef RTC_INDIR_TU
+    // (INDIRECT) the diffuse child: from over_point along a direction of ng's hemisphere - the occlusion step's rule, from
+    // this table's key at word (d << shift) | code -, in its parent's medium, with the reflected child's path code.  It is
+    // formed first and, where a reflected or refracted child follows, waits on the stack below the refraction: a hit pushes
+    // at most two (ensureScratch sizes the indirect family's stack by that).  Alone it continues in registers.
+    if constexpr (INDIRECT) {
+      if (do_diffuse) {
+        uint32_t ipx, ipy;
+        map_pixel(map, out_index, ipx, ipy);
+        const unsigned long long ind_h = rtc_gloss_sample_key(RTC_DKEY(indir.key), static_cast<unsigned long long>(ipy) * cam.hsize + ipx,
+                                                              static_cast<unsigned long long>(smp.sample_base) + (*samp_word & RTC_SAMPLE_MASK));
+        const uint32_t d = cur.lin & RTC_LIN_D;
+        const GlossDir dd = occl_direction(ind_h, (d << RTC_OCCLUSION_SAMPLE_SHIFT) | cur.code, nx, ny, nz);
+        Pending q;
+        q.ray = {ovx, ovy, ovz, dd.x, dd.y, dd.z};
+        q.weight = cur.weight * (ind_r * indir.gain);
+        q.weight_g = cur.weight_g * (ind_g * indir.gain);
+        q.weight_b = cur.weight_b * (ind_b * indir.gain);
+        q.medium = cur.medium;
+        q.remaining = cur.remaining - 1u;
+        q.code = 2u * cur.code;
+        q.lin = (d + 1u) | RTC_LIN_DIFFUSE;
+        it_secondary++;
+        if (do_reflect || do_refract) {
+          if (sp < stack_cap) {
+            RTC_MEDIA_PUSH_EXTRA(sp, q);
+            push_level(sp++, q);
+          } else {
+            overflow = CSG ? (overflow | 1u) : 1u;
+          }
+        } else {
+          cur = q;
+          have_cur = true;
+        }
       }
     }
 #endif
@@ -4595,6 +4705,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
       child.weight = cur.weight * w_reflect;
       RTC_MEDIA_KID(child, cur, w_reflect, cur.medium);  // (MEDIA: a reflected child stays in its parent's medium)
       RTC_SET_CODE(child, 2u * cur.code);
+      RTC_SET_LIN(child, cur.lin & RTC_LIN_D);  // (INDIRECT: its parent's d; not a diffuse child)
 #ifdef RTC_GLOSS_TU
       if (rough_r > 0.0) {
         const GlossDir g = gloss_scatter(gloss_h, child.code, rough_r, child.ray.dx, child.ray.dy, child.ray.dz, nx, ny, nz, false);
@@ -4615,6 +4726,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
       RTC_MEDIA_KID(p, cur, w_refract, kid_medium);
       p.remaining = cur.remaining - 1u;
       RTC_SET_CODE(p, 2u * cur.code + 1u);
+      RTC_SET_LIN(p, cur.lin & RTC_LIN_D);
 #ifdef RTC_GLOSS_TU
       if (rough_t > 0.0) {
         const GlossDir g = gloss_scatter(gloss_h, p.code, rough_t, p.ray.dx, p.ray.dy, p.ray.dz, nx, ny, nz, true);
@@ -4777,7 +4889,8 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
 // three) and the occlusion kernels, rtc_shadowfilter.hip with RTC_SFILT_TU (and, with it, those four) and the shadow-filter
 // kernels, rtc_media.hip with RTC_MEDIA_TU (and, with it, those five) and the media kernels, rtc_environment.hip with
 // RTC_ENV_TU (and, with it, those six) and the environment kernels, rtc_skylight.hip with RTC_SKYL_TU (and, with it, those
-// seven) and the sky-light kernels.  rtc_kernels_ext.hip
+// seven) and the sky-light kernels, rtc_indirect.hip with RTC_INDIR_TU (and, with it, those eight) and the indirect kernels.
+// rtc_kernels_ext.hip
 // includes it with RTC_EXT_TU defined: in the -DRTC_PROFILE diagnostic build, whose instrumented walk makes this unit's
 // compile about a third longer, it gets the csg / texture-map, flat and area-light kernels (rtc_render_kernel_ext to
 // rtc_render_kernel_area_bigworld below), so that neither unit takes the time of all of them.  The product build keeps
@@ -5650,6 +5763,32 @@ rtc_render_kernel_bump_bigworld(const DevScene S, const DevCamera cam, const Dev
                                                                             spots, bumps);
 }
 
+#elif defined(RTC_INDIR_TU)
+
+// Indirect light (rtc_scene_set_indirect): the sky-light walk with the emission rows and the diffuse
+// child, and the gain, the hash key, the bounce limit and the emission rows (DevIndirect) as one more argument; one pair for
+// every world.  Every other kernel is compiled without it.
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_indir(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                        double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                        const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots, const DevBumps bumps,
+                        const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl, const DevShadowFilter sfilt,
+                        const DevMedia media, const DevEnvironment env, const DevSkyLight skyl, const DevIndirect indir) {
+  render_body<true, true, 0, 2, false, true, true, true, true, true, true, true, true, true, true, true, true, true, true, true>(
+      S, cam, map, max_depth, out, stats, next_stats, area, smp, mo, spots, bumps, muv, gloss, occl, sfilt, media, env, skyl, indir);
+}
+
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_indir_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                 double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                 const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                 const DevBumps bumps, const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl,
+                                 const DevShadowFilter sfilt, const DevMedia media, const DevEnvironment env, const DevSkyLight skyl,
+                                 const DevIndirect indir) {
+  render_body<false, true, 0, 2, false, true, true, true, true, true, true, true, true, true, true, true, true, true, true, true>(
+      S, cam, map, max_depth, out, stats, next_stats, area, smp, mo, spots, bumps, muv, gloss, occl, sfilt, media, env, skyl, indir);
+}
+
 #elif defined(RTC_SKYL_TU)
 
 // A sky light (rtc_scene_set_sky_light): the environment walk with the hemisphere rays that gather the
@@ -5843,4 +5982,4 @@ rtc_render_kernel_torus_bigworld(const DevScene S, const DevCamera cam, const De
                                                                                   smp, mo, spots, bumps);
 }
 
-#endif  // RTC_MOTION_TU / RTC_SPOT_TU / RTC_BUMP_TU / RTC_SKYL_TU / RTC_ENV_TU / RTC_MEDIA_TU / RTC_SFILT_TU / RTC_OCCL_TU / RTC_GLOSS_TU / RTC_MESHUV_TU / RTC_TORUS_TU
+#endif  // RTC_MOTION_TU / RTC_SPOT_TU / RTC_BUMP_TU / RTC_INDIR_TU / RTC_SKYL_TU / RTC_ENV_TU / RTC_MEDIA_TU / RTC_SFILT_TU / RTC_OCCL_TU / RTC_GLOSS_TU / RTC_MESHUV_TU / RTC_TORUS_TU

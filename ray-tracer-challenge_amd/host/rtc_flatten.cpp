@@ -147,6 +147,13 @@ struct Flattener {
       const double absn[5] = {-3.0, m.absorption.r, m.absorption.g, m.absorption.b, -3.0};
       appendBits(key, absn, 5);
     }
+    // (likewise a material with an "emission": a row of its own only when a value is non-zero)
+    out.emission_present = out.emission_present || m.emission.present;
+    if (m.emission.r != 0.0 || m.emission.g != 0.0 || m.emission.b != 0.0) {
+      // (a tag of its own before the values: an emission never shares a key with an absorption of the same bits)
+      const double emit[5] = {-4.0, m.emission.r, m.emission.g, m.emission.b, -4.0};
+      appendBits(key, emit, 5);
+    }
     auto it = material_ids.find(key);
     if (it != material_ids.end()) return it->second;
     const uint32_t id = static_cast<uint32_t>(out.mat_pattern.size());
@@ -162,6 +169,9 @@ struct Flattener {
     out.mat_absorption.push_back(m.absorption.r);
     out.mat_absorption.push_back(m.absorption.g);
     out.mat_absorption.push_back(m.absorption.b);
+    out.mat_emission.push_back(m.emission.r);
+    out.mat_emission.push_back(m.emission.g);
+    out.mat_emission.push_back(m.emission.b);
     material_ids.emplace(std::move(key), id);
     return id;
   }

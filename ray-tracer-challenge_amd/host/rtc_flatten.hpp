@@ -34,6 +34,8 @@ struct FlatScene {
   bool shadow_filter_present = false;     // some material of the scene has the "shadow-filter" key
   std::vector<double> mat_absorption;  // [n_materials][3]: each row's "absorption" (rtch_scene_media; not part of rtc_scene_desc)
   bool absorption_present = false;     // some material of the scene has the "absorption" key
+  std::vector<double> mat_emission;    // [n_materials][3]: each row's "emission" (rtch_scene_indirect; not part of rtc_scene_desc)
+  bool emission_present = false;       // some material of the scene has the "emission" key
   uint32_t env_pattern = 0xFFFFFFFFu;  // the environment's pattern row (rtch_scene_environment), or RTC_ENV_NO_PATTERN; not part of rtc_scene_desc
   std::vector<Bump> mat_bump;  // [n_materials]: each row's "normal-perturbation" (rtch_scene_bumps; not part of rtc_scene_desc)
   std::vector<uint8_t> pat_kind;

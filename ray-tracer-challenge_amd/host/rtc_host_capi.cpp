@@ -231,6 +231,26 @@ int rtch_scene_sky_light(void* h, rtc_sky_light* out, int* present) {
   });
 }
 
+// The scene's "indirect" and the materials' "emission" rows, in mat_* order, three doubles each, as
+// rtc_scene_set_indirect takes them; *out points to `emission`.  *present: the file has either key.
+int rtch_scene_indirect(void* h, rtc_indirect* out, double* emission, int* present, uint32_t n) {
+  return guarded([&] {
+    const HostScene* hs = static_cast<HostScene*>(h);
+    if (!out) throw rtc::Error("InvalidArgument", "indirect: null argument");
+    if (n != hs->desc.n_materials)
+      throw rtc::Error("InvalidArgument", "indirect: room for " + std::to_string(n) + " materials, the scene has " + std::to_string(hs->desc.n_materials));
+    if (n != 0u && !emission) throw rtc::Error("InvalidArgument", "indirect: null argument");
+    for (size_t i = 0; i < 3u * static_cast<size_t>(n); ++i) emission[i] = hs->flat.mat_emission[i];  // (mat_* order)
+    std::memset(out, 0, sizeof(*out));
+    out->gain = hs->info.indirect_gain;
+    out->bounces = hs->info.indirect_bounces;
+    out->seed = hs->info.indirect_seed;
+    out->emission = emission;
+    out->n_materials = n;
+    if (present) *present = (hs->info.indirect_present || hs->flat.emission_present) ? 1 : 0;
+  });
+}
+
 // The triangles' texture rows (RTC_TEX_MESH), in tri_* order, as rtc_scene_set_mesh_uvs takes them.
 int rtch_scene_mesh_uvs(void* h, double* uv, uint32_t n) {
   return guarded([&] {
@@ -378,6 +398,11 @@ int rtch_scene_render(void* h, uint32_t width, uint32_t height, uint32_t max_dep
       if (st == RTC_OK && hs->info.sky_light_present) {  // (the sky light; a gain of zero: the handle as it is)
         const rtc_sky_light sl{hs->info.sky_light_gain, hs->info.sky_light_samples, hs->info.sky_light_seed};
         st = rtc_scene_set_sky_light(scene, &sl);
+      }
+      if (st == RTC_OK && (hs->info.indirect_present || hs->flat.emission_present)) {  // (indirect light; nothing to form or emit: the handle as it is)
+        const rtc_indirect in{hs->info.indirect_gain, hs->info.indirect_bounces, hs->info.indirect_seed, hs->flat.mat_emission.data(),
+                              hs->desc.n_materials};
+        st = rtc_scene_set_indirect(scene, &in);
       }
       const rtc::CameraSampling& cs = hs->info.sampling;
       if (cs.adaptive && st == RTC_OK) {  // (adaptive sampling: each tile's mean after its own passes, section 15)

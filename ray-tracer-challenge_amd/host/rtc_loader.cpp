@@ -547,10 +547,32 @@ Absorption parseAbsorption(const Value& cfg) {
   return a;
 }
 
+// A material's "emission" (not in the reference): a number e - (e, e, e) - or [r, g, b]; each value
+// finite and >= 0.
+Emission parseEmission(const Value& cfg) {
+  auto one = [](const Value& v) {
+    if (v.type != Value::Number) throw Error("InvalidData", "emission: a number >= 0 or [r, g, b]");
+    const double x = asFloat(v, "emission");
+    if (!(std::isfinite(x) && x >= 0.0)) throw Error("InvalidData", "emission: a finite number >= 0");
+    return x == 0.0 ? 0.0 : x;  // (-0.0 is stored as 0.0)
+  };
+  Emission e;
+  e.present = true;
+  if (cfg.type == Value::Array) {
+    if (cfg.arr.size() != 3) throw Error("LengthMismatch", "emission: [r, g, b]");
+    e.r = one(cfg.arr[0]);
+    e.g = one(cfg.arr[1]);
+    e.b = one(cfg.arr[2]);
+  } else {
+    e.r = e.g = e.b = one(cfg);
+  }
+  return e;
+}
+
 Material parseMaterial(const Value& cfg, const std::optional<Material>& inherited, const FileLoader& load_file_data) {
   requireObject(cfg, "material");
   checkFields(cfg, {"pattern", "ambient", "diffuse", "specular", "shininess", "reflective", "transparency",
-                    "refractive-index", "normal-perturbation", "roughness", "ambient-occlusion", "shadow-filter", "absorption"}, "material");
+                    "refractive-index", "normal-perturbation", "roughness", "ambient-occlusion", "shadow-filter", "absorption", "emission"}, "material");
   Material mat = inherited ? *inherited : Material{};
   auto present = [&](const char* k) -> const Value* {
     const Value* v = cfg.find(k);
@@ -569,6 +591,7 @@ Material parseMaterial(const Value& cfg, const std::optional<Material>& inherite
   if (auto* v = present("ambient-occlusion")) mat.occlusion = parseOcclusion(*v);
   if (auto* v = present("shadow-filter")) mat.shadow_filter = parseShadowFilter(*v);
   if (auto* v = present("absorption")) mat.absorption = parseAbsorption(*v);
+  if (auto* v = present("emission")) mat.emission = parseEmission(*v);
   if (mat.shadow_filter.from_transparency) {  // (`true`, the material's own or an inherited one: this material's transparency)
     const double t = mat.transparency;
     if (!(std::isfinite(t) && t >= 0.0 && t <= 1.0)) throw Error("InvalidData", "shadow-filter: true needs a transparency in [0, 1]");
@@ -792,7 +815,7 @@ unsigned loaderThreads() {
 SceneInfo parseScene(const std::string& scene_json, const FileLoader& load_file_data) {
   const Value root = json::parse(scene_json);
   requireObject(root, "scene");
-  checkFields(root, {"shape-definitions", "camera", "lights", "objects", "atmosphere", "environment"}, "scene");
+  checkFields(root, {"shape-definitions", "camera", "lights", "objects", "atmosphere", "environment", "indirect"}, "scene");
 
   Definitions definitions;
   if (const Value* defs = root.find("shape-definitions")) {
@@ -912,6 +935,32 @@ SceneInfo parseScene(const std::string& scene_json, const FileLoader& load_file_
       }
       const bool has_sky = info.env_pattern.has_value() || info.env_color[0] != 0.0 || info.env_color[1] != 0.0 || info.env_color[2] != 0.0;
       if (!has_sky) throw Error("InvalidData", "environment: light in an environment that has no sky (no pattern and a colour of zero)");
+    }
+  }
+  // "indirect" (not in the reference): diffuse bounce rays - a gain, or {"gain", "bounces", "seed"};
+  // no table row
+  if (const Value* ind = root.find("indirect")) {
+    auto gainOf = [](const Value& v) {
+      if (v.type != Value::Number) throw Error("InvalidData", "indirect: gain is a number");
+      if (!(std::isfinite(v.num) && v.num >= 0.0)) throw Error("InvalidData", "indirect: gain is a finite number >= 0");
+      return v.num;
+    };
+    // (a whole number in [lo, hi])
+    auto wholeOf = [](const Value& v, const std::string& what, double lo, double hi) {
+      if (v.type != Value::Number || !(v.num >= lo && v.num <= hi) || v.num != std::floor(v.num))
+        throw Error("InvalidData", std::string("indirect: ") + what);
+      return v.num;
+    };
+    info.indirect_present = true;
+    info.indirect_gain = 1.0;
+    info.indirect_bounces = 1u;
+    if (ind->type == Value::Object) {
+      checkFields(*ind, {"gain", "bounces", "seed"}, "indirect");
+      if (const Value* g = ind->find("gain")) info.indirect_gain = gainOf(*g);
+      if (const Value* n = ind->find("bounces")) info.indirect_bounces = static_cast<uint32_t>(wholeOf(*n, "bounces is a whole number from 0 to 16", 0.0, 16.0));
+      if (const Value* sd = ind->find("seed")) info.indirect_seed = static_cast<uint64_t>(wholeOf(*sd, "seed is a whole number from 0 to 2^53", 0.0, 0x1p53));
+    } else {
+      info.indirect_gain = gainOf(*ind);
     }
   }
   info.camera.saved_from = from;

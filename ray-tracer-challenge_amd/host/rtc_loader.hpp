@@ -66,6 +66,11 @@ struct SceneInfo {  // scene.zig:608-610
   double sky_light_gain = 0.0;
   uint32_t sky_light_samples = 1u;
   uint64_t sky_light_seed = 0u;
+  // the scene's "indirect" (section 27): rtc_indirect's values; gain 0 and bounces 0 without the key
+  bool indirect_present = false;
+  double indirect_gain = 0.0;
+  uint32_t indirect_bounces = 0u;
+  uint64_t indirect_seed = 0u;
 };
 
 // scene.zig:612-661.  Throws rtc::Error whose .name is the Zig error name

@@ -125,6 +125,14 @@ struct Absorption {
   bool present = false;
 };
 
+// A material's "emission" (not in the reference), as rtc_scene_set_indirect takes it: what the
+// material adds to every hit's colour by itself, each >= 0; (0, 0, 0): the material as it is.  `present`: the material, or
+// one it inherits from, has the key.
+struct Emission {
+  double r = 0.0, g = 0.0, b = 0.0;
+  bool present = false;
+};
+
 struct Material {  // material.zig:18-25
   Pattern pattern = Pattern::solid({1.0, 1.0, 1.0});
   double ambient = 0.1, diffuse = 0.9, specular = 0.9, shininess = 200.0;
@@ -134,6 +142,7 @@ struct Material {  // material.zig:18-25
   Occlusion occlusion;  // (0 in every scene of the reference)
   ShadowFilter shadow_filter;  // (0, 0, 0 in every scene of the reference)
   Absorption absorption;  // (0, 0, 0 in every scene of the reference)
+  Emission emission;  // (0, 0, 0 in every scene of the reference)
 };
 
 struct Light {  // light.zig:14-15
