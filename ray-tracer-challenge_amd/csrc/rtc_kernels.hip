@@ -167,6 +167,9 @@ __device__ __forceinline__ bool rtc_in_bounds(uint32_t kind, bool ok) {
 #ifndef RTC_CONTAINERS_SOLIDS
 #define RTC_CONTAINERS_SOLIDS 1      // simple worlds: the containers pass drops a solid whose bound lies behind the origin and a plane whose entry cannot be negative (trace(), kSolids)
 #endif
+#ifndef RTC_SHARED_NORMALIZE
+#define RTC_SHARED_NORMALIZE 1       // rtc_render_kernel_simple, _simple_b and _simple3_b divide a vector's three components by its magnitude with one refined reciprocal where a whole wave's operands allow it (shared_normalize; render_body, kSharedNormalize)
+#endif
 // Wave priority by phase of the iteration (s_setprio, round 5; profiles/r05/wave_priority.md).  The three waves of a SIMD
 // are at different places of the same loop; which of them issues when more than one could is the arbiter's choice, and
 // with equal priorities it serves them alike.  Here a wave says what it is doing: fetching work (RTC_PRIO_DEAL: popping its
@@ -285,6 +288,32 @@ __device__ __forceinline__ double refined_rcp(double d) {
 __device__ __forceinline__ double quotient(double x, double d, double r) {
   const double q = x * r;
   return __builtin_fma(__builtin_fma(-d, q, x), r, q);
+}
+
+// Three quotients by one positive divisor, as Tuple.normalized needs them (tuple.zig:109-116: x / m, y / m, z / m with m
+// the vector's magnitude, sqrt((x*x + y*y) + z*z), and m != 0 tested first).  The compiler expands the three divisions
+// one by one, three v_rcp_f64 and 33 instructions; here the m-only part of the expansion is computed once, as above.
+// Operand range - shared_normalize_ok() - in which neither v_div_scale rescales and v_div_fixup passes the result through
+// except for the sign of a zero: m a normal number in [2^-200, 2^201) (its biased exponent within 1023 +- 200: an infinity
+// or a NaN fails, and with it every vector that has an infinite or NaN component or a square that overflows), every
+// numerator zero or at least 2^-801 in magnitude (v_frexp_exp yields 0 for a zero and less than -1022 for a denormal).
+// No numerator exceeds m by more than a rounding, m being the magnitude: a quotient's exponent lies in [-1002, 1], far
+// inside the hardware's conditions (numerator exponent above -969, quotient normal and below 2^768).
+// v_div_fixup is also what gives a zero quotient its sign, and a cube's world normal does carry -0 components (a zero
+// times a negative matrix entry): m > 0, so the numerator's sign IS the quotient's - copied on (v_bfi_b32), a no-op for
+// every non-zero numerator.
+// Checked against the plain divisions on 2^28 vectors, inside and outside the range: tests/hip/shared_normalize_check.hip,
+// which carries a copy of these two functions - a change to one is a change to both.
+__device__ __forceinline__ bool shared_normalize_ok(double x, double y, double z, double m) {
+  const int lowest = min(min(__builtin_amdgcn_frexp_exp(x), __builtin_amdgcn_frexp_exp(y)), __builtin_amdgcn_frexp_exp(z));
+  const uint32_t m_exponent = static_cast<uint32_t>(__builtin_bit_cast(uint64_t, m) >> 52);  // (a sign bit set: out of the band)
+  return (lowest >= -800) & (m_exponent - (1023u - 200u) <= 400u);
+}
+__device__ __forceinline__ void shared_normalize(double& x, double& y, double& z, double m) {
+  const double rcp = refined_rcp(m);
+  x = __builtin_copysign(quotient(x, m, rcp), x);
+  y = __builtin_copysign(quotient(y, m, rcp), y);
+  z = __builtin_copysign(quotient(z, m, rcp), z);
 }
 
 // Cube.localIntersect's three checkAxis calls (cube.zig:24-47) for the unit cube.  The numerators are -1 - o and 1 - o:
@@ -3173,6 +3202,14 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
   // (specular_skip: the point-light branch of the five simple kernels; every other kernel keeps its instructions.  What was
   // counted and measured: profiles/specular_skip/)
   constexpr bool kSpecularSkip = SIMPLE && RTC_SPECULAR_SKIP;
+  // (shared_normalize: the world normal, the point-light vector and the camera ray's direction of the simple kernels are
+  // divided by their magnitude with one refined reciprocal - shared_normalize() - where the operands of every lane of the
+  // wave that divides lie in shared_normalize_ok()'s range; otherwise the whole wave takes the plain divisions.  Decided
+  // for the wave: a branch, not a select between two forms both computed.  Three of the five simple kernels keep it:
+  // rtc_render_kernel_simple3 loses with it (fresnel + 3.2 %, six more spilled VGPRs) and rtc_render_kernel_simple_ext
+  // gains nothing (skybox_demo, twelve more spilled VGPRs); they and every other kernel keep their instructions.
+  // What was measured: profiles/normalize/)
+  constexpr bool kSharedNormalize = SIMPLE && !CSG && (BOX || WAVES == 2) && RTC_SHARED_NORMALIZE;
   // (roots32: a three-wave simple kernel's world has at most RTC_LDS3_ROOTS = 32 roots, rtc_scene_create's simple3_ok: the
   // closest-hit and shadow traces of rtc_render_kernel_simple3_b run one block of the root loop with a 32-bit survivor
   // mask.  Not its containers pass - a ninth of cover's traces; with it the hit point went to scratch memory for the whole
@@ -3662,9 +3699,13 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
       double dx = pix_x - cur.ray.ox, dy = pix_y - cur.ray.oy, dz = pix_z - cur.ray.oz;
       const double mag = __builtin_sqrt((dx * dx + dy * dy) + dz * dz);  // Tuple.normalized, tuple.zig:109-116
       if (mag != 0.0) {
-        dx = dx / mag;
-        dy = dy / mag;
-        dz = dz / mag;
+        if (kSharedNormalize && __ballot(!shared_normalize_ok(dx, dy, dz, mag)) == 0ull) {
+          shared_normalize(dx, dy, dz, mag);
+        } else {
+          dx = dx / mag;
+          dy = dy / mag;
+          dz = dz / mag;
+        }
       }
       cur.ray.dx = dx;
       cur.ray.dy = dy;
@@ -4014,9 +4055,13 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
     {
       const double mag = __builtin_sqrt((nx * nx + ny * ny) + nz * nz);
       if (mag != 0.0) {
-        nx = nx / mag;
-        ny = ny / mag;
-        nz = nz / mag;
+        if (kSharedNormalize && __ballot(!shared_normalize_ok(nx, ny, nz, mag)) == 0ull) {
+          shared_normalize(nx, ny, nz, mag);
+        } else {
+          nx = nx / mag;
+          ny = ny / mag;
+          nz = nz / mag;
+        }
       }
     }
     const bool inside = ((nx * ex + ny * ey) + nz * ez) < 0.0;  // world.zig:218-221
@@ -4278,9 +4323,13 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
         const double distance = __builtin_sqrt((vx * vx + vy * vy) + vz * vz);
         double lvx = vx, lvy = vy, lvz = vz;
         if (distance != 0.0) {
-          lvx = vx / distance;
-          lvy = vy / distance;
-          lvz = vz / distance;
+          if (kSharedNormalize && __ballot(!shared_normalize_ok(vx, vy, vz, distance)) == 0ull) {
+            shared_normalize(lvx, lvy, lvz, distance);
+          } else {
+            lvx = vx / distance;
+            lvy = vy / distance;
+            lvz = vz / distance;
+          }
         }
         // With light_dot_normal < 0 (light behind the surface) lighting() returns `ambient` shadowed
         // or not (material.zig:62-73): that shadow ray cannot change the result either.
