@@ -29,6 +29,9 @@ extern "C" {
  * groups' candidate BVHs with, one top-level group each; 0 = the library's choice, at most 16; the tables do not depend
  * on it), "box_cull" (read at create: a world of top-level spheres / planes / cubes runs the kernels whose root loop
  * rejects by world boxes - 1 - or by bounding spheres - 0; < 0: boxes if it has more cubes than spheres),
+ * "containers_own_root" (read at create; 1: a root that is alone - rtc_diag_root_flags - is marked so in the handle's
+ * tables and a hit on it takes n1 and n2 from its own entries; 0: no root is marked and every such hit makes the
+ * containers pass, so that the two can be held to each other),
  * "sampling_kernels" (!= 0: the camera-sampling kernels even with the default sampling - one centred ray per pixel -, so
  * that their one-sample images can be held to the other kernels'), "motion_kernels" (!= 0: the motion kernels even on a
  * static handle, with every displacement zero, so that their images can be held to the sampling kernels'), "spot_kernels"
@@ -93,6 +96,16 @@ int rtc_diag_root_boxes(const rtc_scene_desc *desc, float *boxes, uint32_t *worl
  * squared (no finite bound: +inf), `*cmax` = the largest |centre| of a bounded root (the scale of the kernel's rounding
  * margin).  `spheres` may be NULL (then only *n_roots and *cmax). */
 int rtc_diag_root_spheres(const rtc_scene_desc *desc, float *spheres, uint32_t capacity, uint32_t *n_roots, float *cmax);
+
+/* Diagnostic (tests/test_own_root_cpu.py): the `kind_flags` word of every root record as rtc_scene_create builds it,
+ * without a device, in the table order of rtc_diag_root_boxes (its `world_index`): the leaf kind in bits 0-7, casts a
+ * shadow 0x100, a closed cylinder or cone 0x200, a room 0x400, alone 0x800 (RTC_ROOT_ALONE_FLAG: a top-level sphere or
+ * cube of a world of spheres, planes and cubes that no other root can share a containers list with),
+ * a csg 0x4000, a group 0x8000.  Option "containers_own_root" is not applied: at 0 a handle's tables are left without
+ * bit 0x800, at create.  (rtc_diag_build_tables digests the tables before that bit is set.)  `flags` may be NULL (then
+ * only *n_roots). */
+#define RTC_ROOT_ALONE_FLAG 0x800u
+int rtc_diag_root_flags(const rtc_scene_desc *desc, uint32_t *flags, uint32_t capacity, uint32_t *n_roots);
 
 #ifdef __cplusplus
 }

@@ -437,7 +437,8 @@ RTC_SYMBOLS = ["rtc_scene_create", "rtc_scene_clone", "rtc_scene_destroy", "rtc_
                "rtc_scene_set_occlusion", "rtc_scene_set_shadow_filters", "rtc_scene_set_media", "rtc_scene_set_environment",
                "rtc_scene_set_sky_light", "rtc_scene_set_indirect"]
 # (... and include/rtc_diag.h: diagnostics and tuning, for the tests, bench.py and tools/)
-RTC_DIAG_SYMBOLS = ["rtc_set_option", "rtc_last_kernel_name", "rtc_get_schedule", "rtc_get_chunk_times", "rtc_diag_build_tables", "rtc_diag_root_boxes", "rtc_diag_root_spheres"]
+RTC_DIAG_SYMBOLS = ["rtc_set_option", "rtc_last_kernel_name", "rtc_get_schedule", "rtc_get_chunk_times", "rtc_diag_build_tables", "rtc_diag_root_boxes", "rtc_diag_root_spheres",
+                    "rtc_diag_root_flags"]
 HOST_SYMBOLS = ["rtch_last_error", "rtch_scene_load", "rtch_scene_free", "rtch_scene_desc", "rtch_scene_camera",
                 "rtch_camera_rotate", "rtch_camera_move", "rtch_camera_make", "rtch_canvas_ppm", "rtch_canvas_rgba8", "rtch_scene_render", "rtch_set_loader_threads",
                 "rtch_scene_lights", "rtch_scene_sampling", "rtch_scene_passes", "rtch_scene_motion", "rtch_scene_adaptive",
@@ -1310,6 +1311,21 @@ def root_spheres(desc):
     spheres = np.zeros((n.value, 4), dtype=np.float32)
     _check_hip(lib.rtc_diag_root_spheres(C.byref(desc), spheres.ctypes.data_as(f32p), n.value, C.byref(n), C.byref(cmax)))
     return spheres, float(cmax.value)
+
+
+ROOT_ALONE = 0x800  # RTC_ROOT_ALONE_FLAG (rtc_diag.h)
+
+
+def root_flags(desc):
+    """rtc_diag_root_flags: the kind_flags word [n] u32 of every root record - in root_boxes' table order - of a scene
+    description, as rtc_scene_create builds them - no device needed.  Bit ROOT_ALONE: DESIGN.md section 5."""
+    lib = hip_lib()
+    n = C.c_uint32(0)
+    lib.rtc_diag_root_flags.argtypes = [C.c_void_p, _u32p, C.c_uint32, _u32p]
+    _check_hip(lib.rtc_diag_root_flags(C.byref(desc), None, 0, C.byref(n)))
+    flags = np.zeros(n.value, dtype=np.uint32)
+    _check_hip(lib.rtc_diag_root_flags(C.byref(desc), flags.ctypes.data_as(_u32p), n.value, C.byref(n)))
+    return flags
 
 
 def set_option(name, value):

@@ -1516,6 +1516,89 @@ int validateScene(const rtc_scene_desc& d, SceneTraits& traits) {
   return RTC_OK;
 }
 
+// RTC_ROOT_ALONE (rtc_device.h): in a simple world - top-level spheres, planes and cubes within the LDS
+// tables, what uploadTables gives the simple kernels - a sphere or cube H is alone when
+//   1. every other root's material has a refractive index of exactly 1.0,
+//   2. H's world box and every other bounded root's are apart on some axis by more than 1e-6 of the larger box's diagonal,
+//   3. H's world box, grown by its margin, lies wholly on one side of every plane root (all eight corners: an affine
+//      function takes its extremes there).  The margin of a sphere is 1e-6 of its box's diagonal.  A cube's is 0.05 x its
+//      largest half-extent (the lengths of its transform's columns), and every half-extent must be at most 1e3: the
+//      reference's parallel rule (cube.zig:28-35) lets the segment between a cube's entries leave it along an ignored axis
+//      by up to 1e-5 x that half-extent x the segment's length, which the size limit holds under 0.041 x the largest.
+// Then no other root can be open around a point of H that a ray through H passes before its origin, and whatever else
+// is open has the ior of "nothing open": a hit on H takes n1 and n2 from H's own entries (render_body, kOwnRoot).
+// Plain double arithmetic on leafWorldBox and the stored inverses: the flag only ever sends a wave the short way where
+// the long way provably gives the same bits.  Table order; the flag of every root of any other world stays clear.
+// A step of its own behind buildTables - createScene makes it unless option "containers_own_root" is 0, and so does
+// rtc_diag_root_flags -: the tables buildTables leaves, which rtc_diag_build_tables digests and tests pin per committed
+// scene, are what they were.
+void markAloneRoots(const rtc_scene_desc& d, HostTables& T) {
+  if (d.n_nodes != 0 || d.n_roots > RTC_LDS_ROOTS || d.n_materials > RTC_LDS_MATERIALS || d.n_patterns > RTC_LDS_PATTERNS ||
+      d.n_lights > RTC_LDS_LIGHTS)
+    return;
+  for (uint32_t i = 0; i < d.n_roots; ++i)
+    if ((d.roots[i] & RTC_CHILD_NODE_BIT) || d.leaf_kind[d.roots[i]] > RTC_CUBE) return;
+  const uint32_t n = d.n_roots;
+  std::vector<uint32_t> leaf(n);
+  std::vector<Aabb> box(n);
+  std::vector<double> diag(n, 0.0);
+  uint32_t not_one = 0, last_not_one = 0;  // roots whose ior is not exactly 1.0, and the last of them
+  for (uint32_t i = 0; i < n; ++i) {
+    leaf[i] = d.roots[T.root_order[i]];
+    if (d.leaf_kind[leaf[i]] != RTC_PLANE) {
+      box[i] = leafWorldBox(d, leaf[i]);
+      if (box[i].finite()) {
+        const double dx = box[i].hi[0] - box[i].lo[0], dy = box[i].hi[1] - box[i].lo[1], dz = box[i].hi[2] - box[i].lo[2];
+        diag[i] = std::sqrt(dx * dx + dy * dy + dz * dz);
+      }
+    }
+    if (!(d.mat_params[static_cast<size_t>(RTC_MAT_STRIDE) * d.leaf_material[leaf[i]] + 6u] == 1.0)) {
+      ++not_one;
+      last_not_one = i;
+    }
+  }
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint8_t kind = d.leaf_kind[leaf[i]];
+    if (kind == RTC_PLANE || !box[i].finite() || !std::isfinite(diag[i])) continue;
+    if (not_one > 1u || (not_one == 1u && last_not_one != i)) continue;  // (1)
+    double margin = 1e-6 * diag[i];
+    if (kind == RTC_CUBE) {
+      double M[12], s_max = 0.0;
+      if (!forwardOf(d.xf_inv + 16ull * d.leaf_xform[leaf[i]], M)) continue;
+      for (int c = 0; c < 3; ++c) s_max = std::fmax(s_max, std::sqrt(M[c] * M[c] + M[4 + c] * M[4 + c] + M[8 + c] * M[8 + c]));
+      if (!(s_max <= 1e3)) continue;
+      margin = 0.05 * s_max;
+    }
+    bool alone = true;
+    for (uint32_t j = 0; j < n && alone; ++j) {
+      if (j == i) continue;
+      if (d.leaf_kind[leaf[j]] != RTC_PLANE) {  // (2)
+        if (!box[j].finite() || !std::isfinite(diag[j])) {
+          alone = false;
+          break;
+        }
+        const double gap = 1e-6 * std::fmax(diag[i], diag[j]);
+        bool apart = false;
+        for (int k = 0; k < 3; ++k) apart = apart || box[i].lo[k] - box[j].hi[k] > gap || box[j].lo[k] - box[i].hi[k] > gap;
+        alone = apart;
+      } else {  // (3)
+        const double* row = d.xf_inv + 16ull * d.leaf_xform[leaf[j]] + 4;  // the plane's object-space y of a world point
+        int above = 0, below = 0;
+        for (int c = 0; c < 8; ++c) {
+          const double x = (c & 1) ? box[i].hi[0] + margin : box[i].lo[0] - margin;
+          const double y = (c & 2) ? box[i].hi[1] + margin : box[i].lo[1] - margin;
+          const double z = (c & 4) ? box[i].hi[2] + margin : box[i].lo[2] - margin;
+          const double oy = ((row[0] * x + row[1] * y) + row[2] * z) + row[3];
+          above += oy > 0.0;
+          below += oy < 0.0;
+        }
+        alone = above == 8 || below == 8;
+      }
+    }
+    if (alone) T.root_recs[i].kind_flags |= RTC_ROOT_ALONE;
+  }
+}
+
 // One record, one bounding sphere and one cost weight (for the first frame's schedule) per World.objects entry.
 void buildRootTables(const rtc_scene_desc& d, const std::vector<uint32_t>& dfs_of, const std::vector<uint32_t>& bvh_root_of,
                      HostTables& T) {
@@ -2597,6 +2680,7 @@ static int createScene(const rtc_scene_desc& d, std::vector<double>* area, std::
   HostTables tables;
   if (extent) tables.light_extent = std::move(*extent);
   if (const int st = buildTables(d, traits, tables); st != RTC_OK) return st;
+  if (rtcOptions().containers_own_root != 0.0) markAloneRoots(d, tables);  // (the kernels read the flags, never the option)
   if (area) tables.area = std::move(*area);
   int n_dev = 0;
   if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0)
@@ -2825,6 +2909,9 @@ static int makeMotionTables(const rtc_scene* s, const double* world_disp, std::s
   std::vector<RootBoxPair> box = tab.h_root_box;
   m->cull_cmax = s->dev.cull_cmax;
   m->cull_bmax = s->dev.cull_bmax;
+  // (a root that moves sweeps a box markAloneRoots did not see: these tables exist only when some displacement is non-zero,
+  // and then no root of them is alone)
+  for (RootRec& R : recs) R.kind_flags &= ~RTC_ROOT_ALONE;
   for (uint32_t i = 0; i < n; ++i) {
     const double* D = world_disp + 3ull * tab.h_root_order[i];
     if (D[0] == 0.0 && D[1] == 0.0 && D[2] == 0.0) continue;
@@ -3905,6 +3992,20 @@ int rtc_diag_root_boxes(const rtc_scene_desc* desc, float* boxes, uint32_t* worl
   return RTC_OK;
 }
 
+int rtc_diag_root_flags(const rtc_scene_desc* desc, uint32_t* flags, uint32_t capacity, uint32_t* n_roots) {
+  g_error.clear();
+  if (!desc || !n_roots) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
+  SceneTraits traits;
+  if (const int st = validateScene(*desc, traits); st != RTC_OK) return st;
+  HostTables tables;
+  if (const int st = buildTables(*desc, traits, tables); st != RTC_OK) return st;
+  markAloneRoots(*desc, tables);
+  *n_roots = desc->n_roots;
+  if (capacity < desc->n_roots) return flags ? fail(RTC_ERR_INVALID_ARGUMENT, "%u roots, room for %u", desc->n_roots, capacity) : RTC_OK;
+  for (uint32_t i = 0; flags && i < desc->n_roots; ++i) flags[i] = tables.root_recs[i].kind_flags;
+  return RTC_OK;
+}
+
 int rtc_diag_root_spheres(const rtc_scene_desc* desc, float* spheres, uint32_t capacity, uint32_t* n_roots, float* cmax) {
   g_error.clear();
   if (!desc || !n_roots) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
@@ -3938,6 +4039,7 @@ int rtc_set_option(const char* name, double value) {
                {"bvh_check", &o.bvh_check}, {"host_bands", &o.host_bands}, {"waves3", &o.waves3},
                {"measure_every", &o.measure_every}, {"sched_mix", &o.sched_mix},
                {"inflight_chunks_per_wave", &o.inflight_chunks_per_wave}, {"build_threads", &o.build_threads}, {"box_cull", &o.box_cull},
+               {"containers_own_root", &o.containers_own_root},
                {"sampling_kernels", &o.sampling_kernels}, {"motion_kernels", &o.motion_kernels},
                {"spot_kernels", &o.spot_kernels}, {"bump_kernels", &o.bump_kernels},
                {"torus_kernels", &o.torus_kernels}, {"meshuv_kernels", &o.meshuv_kernels},

@@ -65,6 +65,7 @@ struct RtcOptions {
   RtcOption measure_every{1.0};        // a moving view is measured (and its schedule re-packed) every this many frames (see updateSchedule)
   RtcOption host_bands{0.0};           // bands rtc_render cuts a frame into (copy of band i under the render of band i + 1); 0: by size
   RtcOption box_cull{-1.0};            // a simple world's kernels reject roots by world boxes (1) or bounding spheres (0); < 0: boxes if it has more cubes than spheres
+  RtcOption containers_own_root{1.0};  // read at create: 0 leaves every root without RTC_ROOT_ALONE, so that every wave of a simple kernel makes the containers pass (tests: against a handle with the flags)
   RtcOption sampling_kernels{0.0};     // != 0: the sampling kernels even with the default sampling (tests: one sample against the other kernels)
   RtcOption motion_kernels{0.0};       // != 0: the motion kernels even on a static handle, all displacements zero (tests: against the _ms kernels)
   RtcOption spot_kernels{0.0};         // != 0: the spot kernels even on a handle without cones, every flag zero (tests: against the motion kernels)

@@ -167,6 +167,9 @@ __device__ __forceinline__ bool rtc_in_bounds(uint32_t kind, bool ok) {
 #ifndef RTC_CONTAINERS_SOLIDS
 #define RTC_CONTAINERS_SOLIDS 1      // simple worlds: the containers pass drops a solid whose bound lies behind the origin and a plane whose entry cannot be negative (trace(), kSolids)
 #endif
+#ifndef RTC_CONTAINERS_OWN_ROOT
+#define RTC_CONTAINERS_OWN_ROOT 1    // rtc_render_kernel_simple_b and _simple3_b: a wave all of whose transparent hits lie on roots that are alone (RTC_ROOT_ALONE) takes n1 / n2 from each hit root's own two entries instead of the whole containers pass (render_body, kOwnRoot; trace(), OWN)
+#endif
 #ifndef RTC_SHARED_NORMALIZE
 #define RTC_SHARED_NORMALIZE 1       // rtc_render_kernel_simple, _simple_b and _simple3_b divide a vector's three components by its magnitude with one refined reciprocal where a whole wave's operands allow it (shared_normalize; render_body, kSharedNormalize)
 #endif
@@ -1599,11 +1602,12 @@ __device__ __forceinline__ void motion_root(V&, uint32_t) {}
 // and block).  32 (RTC_ROOTS32; a three-wave simple kernel, whose worlds rtc_scene_create holds to RTC_LDS3_ROOTS): one
 // block at base 0 and a 32-bit mask - no block loop, half the mask and bit-scan instructions, and a box form of phase 1
 // that shifts its survivor bits into that one register (roots_shifted_in_box).  Which traces take it: render_body, ROOTS.
-template <bool CSG, int WORLD, class V, int TRAV = RTC_LDS_TRAV, bool BOX = true, bool MOTION = false, int MAX_ROOTS = 64>
+template <bool CSG, int WORLD, class V, int TRAV = RTC_LDS_TRAV, bool BOX = true, bool MOTION = false, int MAX_ROOTS = 64, bool OWN = false>
 __device__ __forceinline__ void trace(const DevScene& S, const RootRec* __restrict__ recs,
                                       const CullTables& cull, const Ray& ray, V& vis, unsigned& overflow,
                                       uint32_t* lds_stack, const uint32_t member = 0u, const uint32_t stride = 1u,
-                                      const double* __restrict__ disp = nullptr, const double tm = 0.0) {
+                                      const double* __restrict__ disp = nullptr, const double tm = 0.0,
+                                      const bool own_pass = false, const uint32_t own_root = 0u) {
   constexpr bool SIMPLE = WORLD == 2, FLAT = WORLD >= 1;
   constexpr bool R32 = MAX_ROOTS == 32;
   static_assert(MAX_ROOTS == 64 || (R32 && SIMPLE && RTC_LDS3_ROOTS == 32), "the 32-root form is the three-wave simple kernels'");
@@ -1627,10 +1631,16 @@ __device__ __forceinline__ void trace(const DevScene& S, const RootRec* __restri
   constexpr bool kSolids = SIMPLE && RTC_CONTAINERS_SOLIDS && V::kBehindOnly;
   const auto rf = [&]() {
     if constexpr (BOX) {
+      if constexpr (OWN) {
+        if (own_pass) return RayB{};  // (no phase 1: no ray set-up)
+      }
       RayB b = ray_box(ray, S, vis);
       if constexpr (kSolids) b.t_lo = -1.0002e-4f;
       return b;
     } else {
+      if constexpr (OWN) {
+        if (own_pass) return RayF{};
+      }
       return ray_f32(ray, S.cull_cmax);
     }
   }();
@@ -1645,6 +1655,10 @@ __device__ __forceinline__ void trace(const DevScene& S, const RootRec* __restri
     Mask mine = 0u;
     RTC_PRIO_PHASE(BOX ? RTC_PRIO_CULL : RTC_PRIO_CULL_SPHERES);
     // the tables are padded with entries no ray keeps: the spheres to a multiple of four roots (r2 = -inf), the boxes to eight (lo > hi)
+    if (OWN && own_pass) {  // (the lane's survivors are its hit root, whatever lane of a group it is)
+      const uint32_t rel = own_root - base;
+      if (rel < 64u) mine = Mask{1u} << rel;
+    } else {
     if (BOX && FLAT && stride == 1u) {
       // (the kernels of worlds without groups, but for their cooperative iterations: four roots - two records - per step
       // off three per-lane addresses that move from step to step.  The kernels that walk groups have few top-level
@@ -1737,6 +1751,7 @@ __device__ __forceinline__ void trace(const DevScene& S, const RootRec* __restri
       }
       mine |= planes;
     }
+    }  // (not an own_pass)
     RTC_PRIO_PHASE(RTC_PRIO_WORK);
     // Phase 2, one kind at a time.  The table is sorted [spheres][cubes][everything else][planes] (rtc_scene_create), so
     // a kind is a range of bits.  A wave that walks its lanes' survivors in table order runs the plane, the sphere AND
@@ -1829,7 +1844,7 @@ __device__ __forceinline__ void trace(const DevScene& S, const RootRec* __restri
     // scenes 1-2 % and their worlds have few top-level objects.)
     if constexpr (FLAT) {
       const uint32_t k1 = S.n_root_spheres, k2 = k1 + S.n_root_cubes;
-      if (stride == 1u) {
+      if (stride == 1u || (OWN && own_pass)) {
         // Every lane holds every plane of the block (phase 1 has no say about them): the loop over them is the WAVE's -
         // one record address for all lanes, no per-lane bit scan, no integer multiply for a per-lane record address
         // (reflection_and_refraction runs six plane tests in every one of its 45 M traces).
@@ -1838,7 +1853,7 @@ __device__ __forceinline__ void trace(const DevScene& S, const RootRec* __restri
         // rendered a dozen pixels off the oracle, with fewer shadow rays, in one-lane traces only: the compiled loop did
         // not do what the source says.  Started at `base` with the bounded roots skipped, or with the planes taken from
         // `mine` as a cooperative trace takes them, it was exact; so is this form.  tests/test_table_limits_gpu.py, bounded63-*)
-        const uint32_t p1 = base + n;
+        const uint32_t p1 = (OWN && own_pass) ? base + nc : base + n;  // (own_pass: the hit root is a sphere or a cube - an empty loop, whatever the stride)
         for (uint32_t root = base + nc; root < p1; ++root) {
           if (__all(vis.done())) break;
           if constexpr (V::kBehindOnly) RTC_AUX_ADD(4, 1);
@@ -1913,7 +1928,7 @@ __device__ __forceinline__ void trace(const DevScene& S, const RootRec* __restri
     }  // while (mine)
   }
   if constexpr (FLAT) {
-    if (stride > 1u) vis.merge_group(stride);  // (a cooperative trace: every lane of the group leaves with the group's result)
+    if (stride > 1u && !(OWN && own_pass)) vis.merge_group(stride);  // (a cooperative trace: every lane of the group leaves with the group's result)
   }
 }
 
@@ -3217,6 +3232,18 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
   // by spheres: fresnel + 2.8 %, reflection_and_refraction + 2.1 % with the 32-bit mask alone (six more spilled VGPRs).
   // Every other kernel keeps its instructions.  profiles/roots32/)
   constexpr int ROOTS = (SIMPLE && WAVES == 3 && BOX && RTC_ROOTS32) ? 32 : 64;
+  // (own_root: rtc_scene_create marks a top-level sphere or cube of a simple world RTC_ROOT_ALONE when every other root's
+  // refractive index is exactly 1 and no other root - box against box, box against plane - can be open around a point of
+  // it.  For a hit on such a root the containers walk's n1 and n2 follow from that root's own two entries: every other
+  // open leaf has ior 1, which is what "no open leaf" gives as well, and none can have its last negative entry later than
+  // the hit root's.  In a wave whose transparent hits ALL lie on such roots the containers trace keeps of each lane's roots
+  // the hit root alone - no ray set-up, no phase 1, no plane step, no other cube's step (trace(), OWN); one lane on any
+  // other root and the whole wave makes the pass as before.  rtc_render_kernel_simple_b and _simple3_b, the simple kernels
+  // that cull by boxes: rtc_render_kernel_simple3 lost with it on worlds that never take it (fresnel + 6.4 %,
+  // reflection_and_refraction + 3.8 %: 126 spilled VGPRs for 118) and rtc_render_kernel_simple 1.7 % on fresnel; they,
+  // rtc_render_kernel_simple_ext and every other kernel keep their instructions.  The argument and its limits: DESIGN.md
+  // section 5; what was counted and measured, the form with a second copy of the tests among it: profiles/own_root/)
+  constexpr bool kOwnRoot = SIMPLE && !CSG && BOX && RTC_CONTAINERS_OWN_ROOT;
   constexpr int LDS_LEVELS = (FLAT || !LDS) ? 2 : 1;  // (what fits beside the tables at WAVES work-groups per CU)
   __shared__ Quad2 lds_pend[4][LDS_LEVELS][4][64];
   // The colour a lane has accumulated for its pixel: touched once per iteration and when the pixel is finished, live
@@ -3879,6 +3906,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
     // the hit Shape: its record sits in the (LDS) root table when it is a top-level object,
     // otherwise it is a leaf inside a group and comes from the leaf tables in memory
     uint32_t kind, geom, mat_index;
+    [[maybe_unused]] bool hit_alone = false;  // (kOwnRoot) the hit root carries RTC_ROOT_ALONE
     // The hit shape's inverse.  The kernels that walk BVHs are at their register limit with values in scratch memory:
     // there the matrix is READ WHERE IT IS USED (three times: the local point, the normal, the pattern point) from where
     // it lives - the root record in LDS or the transform table - instead of sitting in 24 VGPRs from the hit to the
@@ -3897,6 +3925,7 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
         M = R.inv;
       }
       kind = R.kind_flags & 0xFFu;
+      if constexpr (kOwnRoot) hit_alone = (R.kind_flags & RTC_ROOT_ALONE) != 0u;
       geom = R.geom;
       mat_index = R.material;
       hcy.ymin = R.ymin;
@@ -3925,10 +3954,18 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
       bv.hit_leaf = hv.leaf;
       bv.hit_t = t;
       RTC_COUNT(4);
-      RTC_AUX_ADD(7, 1);  // (diagnostic builds: the passes of the wave, counted by its first active lane - RTC_COUNT's are lane 0's)
+      // (kOwnRoot) decided for the wave, among the lanes that are here: every hit root alone, and the trace below keeps of
+      // each lane's roots the hit root only - no ray set-up, no phase 1, no plane step (trace(), OWN).  In a cooperative
+      // iteration the lanes of a group hold the same ray and the same hit: each tests that root itself and leaves with the
+      // whole result, nothing is merged (merge_group adds hit_dups across a group's lanes, which is right only where every
+      // root was tested by one of them).  One lane on any other root and the whole wave makes the pass as before.
+      bool own_root = false;
+      if constexpr (kOwnRoot) own_root = !__any(!hit_alone);
+      if (!own_root) RTC_AUX_ADD(7, 1);  // (diagnostic builds: the passes the wave makes in full, counted by its first active lane - RTC_COUNT's are lane 0's)
       {
         RTC_HIST_BEGIN();
-        trace<CSG, WORLD, BehindVisitor, TRAV, BOX, MOTION, 64>(S, recs, cull, ray, bv, it_overflow, trav_stack, member, stride, mo.disp, tm);
+        trace<CSG, WORLD, BehindVisitor, TRAV, BOX, MOTION, 64, kOwnRoot>(S, recs, cull, ray, bv, it_overflow, trav_stack, member, stride, mo.disp, tm,
+                                                                          own_root, kOwnRoot ? hv.root : 0u);
         RTC_HIST_END(2);
       }
         RTC_STAMP(6);
