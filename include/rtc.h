@@ -895,6 +895,80 @@ typedef struct rtc_indirect {
  */
 int rtc_scene_set_indirect(rtc_scene *scene, const rtc_indirect *indirect);
 
+/* ---- emitter sampling: emissive surfaces sampled directly at diffuse hits ---- */
+/*
+ * A handle has one emitter table: samples (1 .. RTC_EMITTER_MAX_SAMPLES) and a seed.  The list of emitters is not passed in:
+ * it is derived from the handle's own tables, in doubles, whenever rtc_scene_set_emitters, rtc_scene_set_indirect or
+ * rtc_scene_set_shadow_filters runs.  c runs over r, g, b.
+ *
+ * Emitters.  A leaf is an emitter when its material's emission row E of the indirect table is not (0, 0, 0); it is a triangle,
+ * a smooth triangle or a cube; no node above it is a csg node; its casts_shadow is set; and its material's shadow-filter row,
+ * if the handle has a filter table, is (0, 0, 0) - a shadow ray towards a cube's far face must be stopped by its near face.
+ * Leaves are taken in depth-first order (roots[] / children[]).  With I the leaf's inverse (xf_inv, rows 0 .. 2: A its
+ * 3 x 3 part, b its last column), the forward map is
+ *   c00 = a11 a22 - a12 a21   c01 = a12 a20 - a10 a22   c02 = a10 a21 - a11 a20
+ *   c10 = a02 a21 - a01 a22   c11 = a00 a22 - a02 a20   c12 = a01 a20 - a00 a21
+ *   c20 = a01 a12 - a02 a11   c21 = a02 a10 - a00 a12   c22 = a00 a11 - a01 a10
+ *   det = (a00 c00 + a01 c01) + a02 c02;   L[i][j] = c[j][i] / det;   t_i = -((L[i][0] b0 + L[i][1] b1) + L[i][2] b2)
+ *   point(p)_i = ((L[i][0] px + L[i][1] py) + L[i][2] pz) + t_i;   vector(v)_i = (L[i][0] vx + L[i][1] vy) + L[i][2] vz
+ * A triangle is one entry: origin = point(p1), eu = vector(e1), ev = vector(e2), half = 1.  A cube is six, its faces in the
+ * order +x, -x, +y, -y, +z, -z: for the face of axis a and sign s, with b = (a + 1) mod 3 and c = (a + 2) mod 3,
+ * origin = point(o), o_a = s, o_b = o_c = -1;  eu = vector(2 e_b);  ev = vector(2 e_c);  half = 0.  For every entry
+ *   m = eu x ev (each component x1 y2 - x2 y1 in the cross product's cyclic order);  len = sqrt((mx mx + my my) + mz mz)
+ *   n = m / len;   A = len, and len / 2 where half = 1;   w = A * ((E.r + E.g) + E.b)
+ * An entry whose w is not finite or not above zero is left out.  cdf[k] = cdf[k - 1] + w_k in list order (cdf[-1] = 0); W is
+ * the last; every entry stores q = W / ((E.r + E.g) + E.b).  More than RTC_MAX_EMITTERS entries: RTC_ERR_UNSUPPORTED.
+ * Spheres, cylinders, cones, tori, planes and the leaves of a csg are not listed: they light what a bounce ray finds.
+ *
+ * Where a sample is drawn.  At a hit that forms the diffuse child of rtc_scene_set_indirect - gain > 0, material.diffuse !=
+ * 0.0, cur.remaining > 0, d < bounces - when the list is not empty.  After the sky-light step, for j = 0 .. samples - 1:
+ *   J(axis) = rtc_gloss_jitter(h, (j << 17) | cur.code, axis),  h = rtc_gloss_sample_key(key', p, g),
+ *   key = rtc_mix64(seed ^ 0xC0AC29B7C97C50DD), key' as the indirect table's decorrelation has it
+ *   u0 = J(0);  k = the first entry with cdf[k] > u0 * W, the last entry where there is none
+ *   u = J(1), v = J(2);  where half = 1 and u + v > 1.0:  u = 1.0 - u, v = 1.0 - v
+ *   Y_i = (origin_i + u * eu_i) + v * ev_i
+ *   v = Y - over_point;  r2 = (vx vx + vy vy) + vz vz;  r = sqrt(r2);  w = v / r
+ *   cos_x = (ng.x wx + ng.y wy) + ng.z wz     ng: the geometric normal after its `inside` flip, not the bumped normal
+ *   cos_e = |(n.x wx + n.y wy) + n.z wz|      an emitter emits on both sides, as a hit on either side adds its row
+ *   where cos_x <= 0, cos_e == 0 or r <= 2e-4 the sample is zero, no walk is made and nothing is counted;
+ *   otherwise one shadow walk from over_point along w: the product F of the shadow-filter rows of every entry with
+ *   0 <= t < r - 1e-4 on a casts_shadow leaf (all zero: blocked, the sample is zero); it counts one shadow_calls and one
+ *   shadow_traced
+ *   term.c = (((E.c * q) * ((cos_x * cos_e) / (RTC_PI * r2))) * F.c),  with media times T.c, the transmittance of
+ *   rtc_scene_set_media for a segment of length r in the current ray's medium (sigma.c == 0: the term as it is; else
+ *   times exp(-(sigma.c * r))); the fog's own colour does not enter
+ *   sum.c = sum.c + term.c
+ * and then, before the emission row,
+ *   s.c = s.c + (color.c * material.diffuse) * (gain * (sum.c / samples))
+ *
+ * Nothing counted twice.  The ray that was formed as a diffuse child adds no emission row at a hit on a leaf of the list:
+ * its parent's samples counted that light.  Its reflected and refracted descendants, and every other ray, add emission as
+ * before.  The image's expectation is the one without the table.
+ *
+ * Only + - * / sqrt, exp (media) and comparisons are added, each correctly rounded, in the order written.
+ */
+#define RTC_PI 3.14159265358979323846
+#define RTC_MAX_EMITTERS 4096u
+#define RTC_EMITTER_MAX_SAMPLES 16u
+typedef struct rtc_emitters {
+  uint32_t samples; /* samples per hit, 1 .. RTC_EMITTER_MAX_SAMPLES; their mean is taken */
+  uint64_t seed;
+} rtc_emitters;
+
+/*
+ * This handle's emitter sampling for every render entry point.  Validated on the host before any HIP call and before anything
+ * changes: RTC_ERR_INVALID_ARGUMENT for samples outside 1 .. RTC_EMITTER_MAX_SAMPLES; RTC_ERR_UNSUPPORTED for a list of more
+ * than RTC_MAX_EMITTERS entries and for a listed leaf below a root that rtc_scene_set_motion moves - rtc_scene_set_motion,
+ * rtc_scene_set_indirect and rtc_scene_set_shadow_filters refuse in the same way what would make the list of a handle with
+ * the table too long or move one of its leaves, whichever call comes second; the previous state stays in force.  NULL is no
+ * table.  A clone starts with its source's table; rtc_render's band clones follow.  The order of this setter and the
+ * others does not matter: the list is derived again whenever one of the three runs, and which kernels run is decided at
+ * launch - the emitter kernels (rtc_render_kernel_emit, _emit_bigworld) when the derived list is not empty; every other
+ * handle gets the kernels it got before.  librtc_multi renders without it.  rtc_scene_desc, rtc_camera, rtc_stats and
+ * RTC_ABI_VERSION are as they were.
+ */
+int rtc_scene_set_emitters(rtc_scene *scene, const rtc_emitters *emitters);
+
 /* ---- adaptive sampling: progressive passes only for tiles still noisy ---- */
 #define RTC_ADAPTIVE_MAX_TILE 1024u
 

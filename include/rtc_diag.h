@@ -50,7 +50,9 @@ extern "C" {
  * no sky and no sun, so that their images can be held to the handle's ordinary kernels'), "sky_light_kernels" (!= 0: the
  * sky-light kernels even on a handle without a sky light, the gain zero, so that their images can be held to the handle's
  * ordinary kernels'), "indirect_kernels" (!= 0: the indirect kernels even on a handle without an indirect table, the gain
- * zero and no emission, so that their images can be held to the handle's ordinary kernels').
+ * zero and no emission, so that their images can be held to the handle's ordinary kernels'), "emitter_kernels" (!= 0: the
+ * emitter kernels even on a handle without an emitter list, the count zero, so that their images can be held to the handle's
+ * ordinary kernels').
  * RTC_ERR_INVALID_ARGUMENT for a name the library does not know.
  * (The library reads no environment variables.)
  */
@@ -82,6 +84,17 @@ int rtc_get_chunk_times(rtc_scene *scene, const rtc_camera *cam, uint32_t *estim
  * bounding spheres, reference-tree parents), `*build_ms` = the wall time of the table build.  Either may be NULL.  What
  * "build_threads" must not change. */
 int rtc_diag_build_tables(const rtc_scene_desc *desc, uint64_t *digest, double *build_ms);
+
+/* Diagnostic (tests/test_emitters_cpu.py): the emitter list rtc_scene_set_emitters derives (rtc.h) for
+ * a description, an emission table `emission` ([n_materials][3], as rtc_indirect's; NULL: no material emits) and a filter
+ * table `filter` ([n_materials][3], as rtc_shadow_filters'; NULL: no table), without a device: `rows[18 k ...]` = origin,
+ * eu, ev, the unit normal, the emission, W / (E.r + E.g + E.b), 1.0 for a triangle, the depth-first leaf; `cdf[k]` the
+ * running sum of the weights; `*count` the entries.  Either array may be NULL (then only *count).
+ * RTC_ERR_UNSUPPORTED for more than RTC_MAX_EMITTERS entries. */
+int rtc_diag_emitters(const rtc_scene_desc *desc, const double *emission, const double *filter, uint32_t capacity, double *rows,
+                      double *cdf, uint32_t *count);
+/* Diagnostic: the entry the kernels' search picks for the draw u0 from a CDF of `count` >= 1 entries, W = cdf[count - 1]. */
+int rtc_diag_emitter_pick(const double *cdf, uint32_t count, double u0, uint32_t *entry);
 
 /* Diagnostic (tests/test_root_boxes_cpu.py): the FP32 world boxes phase 1 of the render kernels' root loop tests
  * (DESIGN.md section 3), as rtc_scene_create builds them, without a device: per table position i (the tables are sorted

@@ -28,7 +28,8 @@
  *                        and its atmosphere, rtch_scene_media, through rtc_scene_set_media; its environment,
  *                        rtch_scene_environment, through rtc_scene_set_environment; its sky light,
  *                        rtch_scene_sky_light, through rtc_scene_set_sky_light; its indirect light,
- *                        rtch_scene_indirect, through rtc_scene_set_indirect)
+ *                        rtch_scene_indirect, through rtc_scene_set_indirect; its emitter sampling,
+ *                        rtch_scene_emitters, through rtc_scene_set_emitters)
  *
  * Every function that returns int returns 0 on success; otherwise rtch_last_error()
  * holds "<ZigStyleErrorName>: detail" (thread-local).
@@ -133,6 +134,10 @@ int rtch_scene_sky_light(void *handle, rtc_sky_light *out, int *present);
  * has either key; without "indirect" *out is gain 0, bounces 0, seed 0.  Neither key adds a table row.  rtch_scene_render
  * applies them. */
 int rtch_scene_indirect(void *handle, rtc_indirect *out, double *emission, int *present, uint32_t n);
+/* The "emitters" key inside the scene's "indirect" (DESIGN.md section 28): true, n, or {"samples": n, "seed": s} - samples
+ * defaults to 1, seed to 0 -, as rtc_scene_set_emitters takes it.  *present: 1 when the file has the key and it is not false;
+ * without it *out is samples 1, seed 0.  The key adds no table row.  rtch_scene_render applies it, after the indirect table. */
+int rtch_scene_emitters(void *handle, rtc_emitters *out, int *present);
 int rtch_scene_camera(void *handle, uint32_t width, uint32_t height, rtc_camera *out);
 int rtch_camera_rotate(void *handle, double angle);
 int rtch_camera_move(void *handle, double distance);

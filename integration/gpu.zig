@@ -118,6 +118,13 @@ pub const RtcIndirect = extern struct {
     n_materials: u32, // with emission: the scene's material count
 };
 pub extern fn rtc_scene_set_indirect(scene: *RtcScene, indirect: ?*const RtcIndirect) c_int; // null: no table
+// Emitter sampling (rtc.h, rtc_scene_set_emitters): every hit that forms a diffuse child also samples the handle's emissive
+// triangles and cubes directly; the list is derived from the handle's own tables.
+pub const RtcEmitters = extern struct {
+    samples: u32, // 1 .. 16
+    seed: u64,
+};
+pub extern fn rtc_scene_set_emitters(scene: *RtcScene, emitters: ?*const RtcEmitters) c_int; // null: no table
 pub extern fn rtc_grow_csg_lists(scene: *RtcScene) c_int; // after an asynchronous frame whose stats.overflow != 0 on a csg scene: longer lists, render again
 pub extern fn rtc_scatter_tile_list_device(d_tiles: [*]const f64, d_tile_list: [*]const u32, n_tiles: u32, tile_w: u32, tile_h: u32,
                                            hsize: u32, vsize: u32, canvas: [*]f64, hip_stream: ?*anyopaque) c_int; // a rank's tiles straight into a (registered host) canvas

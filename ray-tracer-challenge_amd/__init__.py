@@ -222,7 +222,8 @@ RTC_SPHERE, RTC_PLANE, RTC_CUBE, RTC_CYLINDER, RTC_TRIANGLE, RTC_SMOOTH_TRIANGLE
 # the options that select a kernel family on a handle that does not need it (set_option; tests and tools/time_scenes.py)
 KERNEL_OPTIONS = ("sampling_kernels", "motion_kernels", "spot_kernels", "bump_kernels", "torus_kernels", "meshuv_kernels", "gloss_kernels",
                   "occlusion_kernels", "shadow_filter_kernels", "media_kernels", "environment_kernels", "sky_light_kernels",
-                  "indirect_kernels")
+                  "indirect_kernels", "emitter_kernels")
+MAX_EMITTERS, EMITTER_MAX_SAMPLES, EMITTER_ROW = 4096, 16, 18  # RTC_MAX_EMITTERS, RTC_EMITTER_MAX_SAMPLES; rtc_diag_emitters' row
 SKY_LIGHT_MAX_SAMPLES = 64  # RTC_SKY_LIGHT_MAX_SAMPLES
 ENV_NO_PATTERN, ENV_SPHERE, ENV_CUBE, ENV_MAX_SUNS = 0xFFFFFFFF, 0, 1, 16  # RTC_ENV_*
 NO_MEDIUM = 0xFFFFFFFF  # RTC_NO_MEDIUM: a ray in the atmosphere
@@ -393,6 +394,41 @@ def indirect_struct(indirect):
     return d, e
 
 
+class Emitters(C.Structure):
+    """struct rtc_emitters (include/rtc.h): the samples per hit towards the handle's emissive surfaces and the draws' seed."""
+
+    _fields_ = [("samples", C.c_uint32), ("seed", C.c_uint64)]
+
+
+def emitters_struct(emitters):
+    """Emitters of a dict of "samples" (1) and "seed" (0) (GpuScene.set_emitters)"""
+    return Emitters(int(emitters.get("samples", 1)), int(emitters.get("seed", 0)))
+
+
+def diag_emitters(desc, emission, filters=None):
+    """rtc_diag_emitters: (rows (n, EMITTER_ROW), cdf (n,)) - the emitter list rtc_scene_set_emitters derives for a SceneDesc,
+    an emission table (n_materials, 3) or None and a filter table (n_materials, 3) or None; no device is needed."""
+    e = None if emission is None else np.ascontiguousarray(emission, dtype=np.float64)
+    f = None if filters is None else np.ascontiguousarray(filters, dtype=np.float64)
+    ep = e.ctypes.data_as(_dp) if e is not None else None
+    fp = f.ctypes.data_as(_dp) if f is not None else None
+    n = C.c_uint32()
+    _check_hip(hip_lib().rtc_diag_emitters(C.byref(desc), ep, fp, 0, None, None, C.byref(n)))
+    rows, cdf = np.zeros((n.value, EMITTER_ROW)), np.zeros(n.value)
+    _check_hip(hip_lib().rtc_diag_emitters(C.byref(desc), ep, fp, n.value, rows.ctypes.data_as(_dp), cdf.ctypes.data_as(_dp), C.byref(n)))
+    return rows, cdf
+
+
+def diag_emitter_pick(cdf, u0):
+    """rtc_diag_emitter_pick: the entry the kernels' binary search picks for the draw u0 from the CDF"""
+    cdf = np.ascontiguousarray(cdf, dtype=np.float64)
+    k = C.c_uint32()
+    lib = hip_lib()
+    lib.rtc_diag_emitter_pick.argtypes = [_dp, C.c_uint32, C.c_double, C.POINTER(C.c_uint32)]
+    _check_hip(lib.rtc_diag_emitter_pick(cdf.ctypes.data_as(_dp), len(cdf), float(u0), C.byref(k)))
+    return int(k.value)
+
+
 class Bump(C.Structure):
     """struct rtc_bump (include/rtc.h): a bump per material row (kind BUMP_NONE: the material as it is)."""
 
@@ -435,16 +471,16 @@ RTC_SYMBOLS = ["rtc_scene_create", "rtc_scene_clone", "rtc_scene_destroy", "rtc_
                "rtc_scene_adaptive_begin_device", "rtc_scene_adaptive_accumulate_device", "rtc_scene_adaptive_step", "rtc_render_adaptive",
                "rtc_scene_set_spots", "rtc_scene_set_bumps", "rtc_scene_set_mesh_uvs", "rtc_scene_set_gloss",
                "rtc_scene_set_occlusion", "rtc_scene_set_shadow_filters", "rtc_scene_set_media", "rtc_scene_set_environment",
-               "rtc_scene_set_sky_light", "rtc_scene_set_indirect"]
+               "rtc_scene_set_sky_light", "rtc_scene_set_indirect", "rtc_scene_set_emitters"]
 # (... and include/rtc_diag.h: diagnostics and tuning, for the tests, bench.py and tools/)
-RTC_DIAG_SYMBOLS = ["rtc_set_option", "rtc_last_kernel_name", "rtc_get_schedule", "rtc_get_chunk_times", "rtc_diag_build_tables", "rtc_diag_root_boxes", "rtc_diag_root_spheres",
+RTC_DIAG_SYMBOLS = ["rtc_set_option", "rtc_last_kernel_name", "rtc_get_schedule", "rtc_get_chunk_times", "rtc_diag_build_tables", "rtc_diag_root_boxes", "rtc_diag_root_spheres", "rtc_diag_emitters", "rtc_diag_emitter_pick",
                     "rtc_diag_root_flags"]
 HOST_SYMBOLS = ["rtch_last_error", "rtch_scene_load", "rtch_scene_free", "rtch_scene_desc", "rtch_scene_camera",
                 "rtch_camera_rotate", "rtch_camera_move", "rtch_camera_make", "rtch_canvas_ppm", "rtch_canvas_rgba8", "rtch_scene_render", "rtch_set_loader_threads",
                 "rtch_scene_lights", "rtch_scene_sampling", "rtch_scene_passes", "rtch_scene_motion", "rtch_scene_adaptive",
                 "rtch_scene_spots", "rtch_scene_bumps", "rtch_scene_mesh_uvs", "rtch_scene_gloss", "rtch_scene_occlusion",
                 "rtch_scene_shadow_filters", "rtch_scene_media", "rtch_scene_environment", "rtch_scene_sky_light",
-                "rtch_scene_indirect"]
+                "rtch_scene_indirect", "rtch_scene_emitters"]
 
 MULTI_SYMBOLS = ["rtc_multi_create", "rtc_multi_destroy", "rtc_multi_render", "rtc_multi_render_rgba8", "rtc_multi_render_device", "rtc_multi_render_rgba8_device",
                  "rtc_multi_synchronize", "rtc_multi_stream", "rtc_multi_get_stats", "rtc_multi_balance", "rtc_multi_last_error"]
@@ -514,6 +550,8 @@ def hip_lib():
         lib.rtc_scene_set_environment.argtypes = [C.c_void_p, C.POINTER(Environment)]
         lib.rtc_scene_set_sky_light.argtypes = [C.c_void_p, C.POINTER(SkyLight)]
         lib.rtc_scene_set_indirect.argtypes = [C.c_void_p, C.POINTER(Indirect)]
+        lib.rtc_scene_set_emitters.argtypes = [C.c_void_p, C.POINTER(Emitters)]
+        lib.rtc_diag_emitters.argtypes = [C.POINTER(SceneDesc), _dp, _dp, C.c_uint32, _dp, _dp, C.POINTER(C.c_uint32)]
         lib.rtc_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.POINTER(Adaptive), C.c_void_p, C.c_void_p]
         lib.rtc_scene_destroy.argtypes = [C.c_void_p]
         lib.rtc_scene_destroy.restype = None
@@ -576,6 +614,7 @@ def host_lib():
         lib.rtch_scene_environment.argtypes = [C.c_void_p, C.POINTER(Environment), _dp, _dp, C.POINTER(C.c_int)]
         lib.rtch_scene_sky_light.argtypes = [C.c_void_p, C.POINTER(SkyLight), C.POINTER(C.c_int)]
         lib.rtch_scene_indirect.argtypes = [C.c_void_p, C.POINTER(Indirect), _dp, C.POINTER(C.c_int), C.c_uint32]
+        lib.rtch_scene_emitters.argtypes = [C.c_void_p, C.POINTER(Emitters), C.POINTER(C.c_int)]
         lib.rtch_scene_adaptive.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(Adaptive)]
         lib.rtch_scene_camera.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Camera)]
         lib.rtch_camera_rotate.argtypes = [C.c_void_p, C.c_double]
@@ -849,6 +888,16 @@ class HostScene:
             return None
         return {"gain": float(d.gain), "bounces": int(d.bounces), "seed": int(d.seed), "emission": e}
 
+    def emitters(self):
+        """The "emitters" key of the scene's "indirect" (rtch_scene_emitters): a dict of "samples" and "seed" - what
+        GpuScene.set_emitters takes -, or None when the file has no such key."""
+        e = Emitters()
+        present = C.c_int()
+        _check_host(host_lib().rtch_scene_emitters(self._h, C.byref(e), C.byref(present)))
+        if not present.value:
+            return None
+        return {"samples": int(e.samples), "seed": int(e.seed)}
+
     def adaptive(self):
         """The camera's "sampling": {"adaptive": ...} of the scene file (rtch_scene_adaptive): an Adaptive whose max_passes
         is "passes", or None when the file has none."""
@@ -1030,6 +1079,15 @@ class GpuScene:
             return
         d, _keep = indirect_struct(indirect)
         _check_hip(hip_lib().rtc_scene_set_indirect(self._s, C.byref(d)))
+
+    def set_emitters(self, emitters):
+        """rtc_scene_set_emitters: a dict of "samples" and "seed" (HostScene.emitters()); None: no table - the handle's previous
+        kernels.  The list of emitters is derived from the handle's indirect and shadow-filter tables, whenever either is set."""
+        if emitters is None:
+            _check_hip(hip_lib().rtc_scene_set_emitters(self._s, None))
+            return
+        e = emitters_struct(emitters)
+        _check_hip(hip_lib().rtc_scene_set_emitters(self._s, C.byref(e)))
 
     def accumulate_device(self, accum, stream=None):
         """rtc_scene_accumulate_device: an Accum, enqueued on `stream` (None: the handle's own) after this handle's renders."""

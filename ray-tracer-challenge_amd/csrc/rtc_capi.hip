@@ -241,6 +241,23 @@ __global__ void rtc_render_kernel_indir_bigworld(const DevScene S, const DevCame
                                                  const DevShadowFilter sfilt, const DevMedia media, const DevEnvironment env,
                                                  const DevSkyLight skyl, const DevIndirect indir);
 }
+// The emitter kernels (rtc_scene_set_emitters: emissive surfaces sampled directly at diffuse hits): the indirect kernels'
+// tables and stack, and the emitter rows, their CDF, the leaf bits, the hash key and the counts (DevEmitters) as one more
+// argument.
+extern "C" {
+__global__ void rtc_render_kernel_emit(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                       double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                       const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                       const DevBumps bumps, const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl,
+                                       const DevShadowFilter sfilt, const DevMedia media, const DevEnvironment env,
+                                       const DevSkyLight skyl, const DevIndirect indir, const DevEmitters emit);
+__global__ void rtc_render_kernel_emit_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                                double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                                const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                                const DevBumps bumps, const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl,
+                                                const DevShadowFilter sfilt, const DevMedia media, const DevEnvironment env,
+                                                const DevSkyLight skyl, const DevIndirect indir, const DevEmitters emit);
+}
 // Progressive rendering's accumulation (rtc_accum.hip): the grid's blocks for n pixels (the noise partials it writes, at
 // most) and the enqueue of its kernels.
 uint32_t rtcAccumBlocks(size_t n_pixels, bool wide);
@@ -458,6 +475,11 @@ bool tablesInLds(const rtc_scene* s) {
 // cleared, and a clone or a band clone, which holds its source's tables and flags, selects what its source does.
 Family family(const rtc_scene* s) {
   const RtcOptions& o = rtcOptions();
+  // The emitter kernels run when the list derived for the handle's emitter table is not empty (rtc_scene_set_emitters; the
+  // list is derived again by rtc_scene_set_indirect and rtc_scene_set_shadow_filters, so the order of the setters does not
+  // matter) - whatever else the handle holds: they are the indirect walk - or, for tests, whenever option "emitter_kernels"
+  // is set.
+  if ((s->emitters != nullptr && s->emitters->count != 0u) || o.emitter_kernels != 0.0) return kFamilyEmit;
   // The indirect kernels run when the handle's indirect table can form a diffuse child (gain > 0 and bounces > 0) or holds an
   // emission entry that is not zero (rtc_scene_set_indirect keeps no other table) - whatever else the handle holds: they are
   // the sky-light walk - or, for tests, whenever option "indirect_kernels" is set.
@@ -530,6 +552,7 @@ struct LaunchArgs {
   DevEnvironment env;
   DevSkyLight skyl;
   DevIndirect indir;
+  DevEmitters emit;
 };
 // ... from the handle, for a launch of family `f` with the scene `dev` (the handle's, or its copy for an empty dispatch).
 LaunchArgs launchArgs(const rtc_scene* s, Family f, const DevScene& dev, const DevCamera& cam) {
@@ -592,6 +615,10 @@ LaunchArgs launchArgs(const rtc_scene* s, Family f, const DevScene& dev, const D
   // (the handle's indirect light, or a gain of zero and no emission rows)
   a.indir = DevIndirect{0.0, 0ull, nullptr, 0u};
   if (const IndirectTables* t = s->indirect.get()) a.indir = DevIndirect{t->gain, t->key, t->emits ? t->emission.p : nullptr, t->bounces};
+  // (the handle's emitter list, or a count of zero: no sample and nothing suppressed)
+  a.emit = DevEmitters{nullptr, nullptr, nullptr, 0ull, 0.0, 0u, 1u};
+  if (const EmitterTables* t = s->emitters.get())
+    if (t->count != 0u) a.emit = DevEmitters{t->row.p, t->cdf.p, t->leaf_bits.p, t->key, t->total, t->count, t->samples};
   return a;
 }
 
@@ -621,6 +648,7 @@ hipError_t forFamilyKernel(const rtc_scene* s, const KernelChoice& c, const Laun
     case Family::ENV: RTC_KERNEL_PAIR(rtc_render_kernel_env, a.area, a.smp, a.mo, a.spots, a.bumps, a.muv, a.gloss, a.occl, a.sfilt, a.media, a.env);
     case Family::SKYL: RTC_KERNEL_PAIR(rtc_render_kernel_skyl, a.area, a.smp, a.mo, a.spots, a.bumps, a.muv, a.gloss, a.occl, a.sfilt, a.media, a.env, a.skyl);
     case Family::INDIR: RTC_KERNEL_PAIR(rtc_render_kernel_indir, a.area, a.smp, a.mo, a.spots, a.bumps, a.muv, a.gloss, a.occl, a.sfilt, a.media, a.env, a.skyl, a.indir);
+    case kFamilyEmit: RTC_KERNEL_PAIR(rtc_render_kernel_emit, a.area, a.smp, a.mo, a.spots, a.bumps, a.muv, a.gloss, a.occl, a.sfilt, a.media, a.env, a.skyl, a.indir, a.emit);
   }
   return hipErrorInvalidValue;  // (no such family)
 }
@@ -991,7 +1019,8 @@ int packNextSchedule(rtc_scene* s, const rtc_camera& cam, const DevPixelMap& map
 // the indirect kernels may form three and pushes at most two; every ray on the stack waits at a tree level 1 .. max_depth
 // and a level's hit is shaded once per walk down, so at most 2 * max_depth wait at once: 2 * max_depth + 2 levels.
 uint32_t rayStackLevels(const rtc_scene* s, uint32_t max_depth) {
-  return family(s) == Family::INDIR ? 2u * max_depth + 2u : max_depth + 2u;
+  const Family f = family(s);  // (the emitter kernels are the indirect walk: the same children)
+  return (f == Family::INDIR || f == kFamilyEmit) ? 2u * max_depth + 2u : max_depth + 2u;
 }
 
 int ensureScratch(rtc_scene* s, DevPixelMap& map, uint32_t blocks, uint32_t max_depth) {
@@ -2386,6 +2415,115 @@ hipError_t ensureOwnStream(rtc_scene* s) {
   return s->stream != nullptr ? hipSuccess : hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
 }
 
+// ---- emitter sampling: the list, on the host
+// Per depth-first leaf: whether a csg node lies above it, and the World.objects index of its root.
+void emitterLeafTables(const rtc_scene_desc& d, const HostTables& T, std::vector<uint8_t>& leaf_csg, std::vector<uint32_t>& leaf_root) {
+  leaf_csg.assign(T.n_live, 0u);
+  leaf_root.assign(T.n_live, 0u);
+  for (uint32_t i = 0; i < d.n_roots; ++i) {
+    const uint32_t r = T.roots[i];
+    if (!(r & RTC_CHILD_NODE_BIT)) {
+      if (r < T.n_live) leaf_root[r] = i;
+      continue;
+    }
+    const uint2 range = T.node_range[r & ~RTC_CHILD_NODE_BIT];
+    for (uint32_t l = range.x; l < range.x + range.y && l < T.n_live; ++l) leaf_root[l] = i;
+  }
+  for (uint32_t n = 0; n < d.n_nodes; ++n) {
+    if ((T.node_info[n] & 3u) == RTC_CSG_NONE) continue;
+    const uint2 range = T.node_range[n];
+    for (uint32_t l = range.x; l < range.x + range.y && l < T.n_live; ++l) leaf_csg[l] = 1u;
+  }
+}
+
+// The emitter list (rtc.h's rtc_scene_set_emitters, operation for operation): rows of RTC_EMITTER_ROW doubles, the running
+// CDF and each entry's leaf.  `emission` / `filter`: [n_materials][3] or null (no material emits / no filter table).
+struct EmitterList {
+  std::vector<double> row, cdf;
+  std::vector<uint32_t> leaf;
+  double total = 0.0;
+};
+// (false: more than RTC_MAX_EMITTERS entries)
+bool deriveEmitterList(const std::vector<uint4>& leaf_meta, const std::vector<double>& xf, const std::vector<double>& tri,
+                       const std::vector<uint8_t>& leaf_csg, const double* emission, const double* filter, EmitterList& out) {
+  out = EmitterList{};
+  if (!emission) return true;
+  for (uint32_t l = 0; l < leaf_meta.size(); ++l) {
+    const uint4 m = leaf_meta[l];
+    const uint32_t kind = m.x & 0xFFu;
+    if (kind != RTC_CUBE && kind != RTC_TRIANGLE && kind != RTC_SMOOTH_TRIANGLE) continue;
+    if ((m.x & 0x100u) == 0u || leaf_csg[l]) continue;
+    const double* E = emission + 3ull * m.z;
+    if (E[0] == 0.0 && E[1] == 0.0 && E[2] == 0.0) continue;
+    if (filter) {
+      const double* f = filter + 3ull * m.z;
+      if (f[0] != 0.0 || f[1] != 0.0 || f[2] != 0.0) continue;
+    }
+    // the forward map of the leaf's inverse: cofactors over the determinant, and the translation
+    const double* I = xf.data() + 12ull * m.y;
+    const double a00 = I[0], a01 = I[1], a02 = I[2], b0 = I[3];
+    const double a10 = I[4], a11 = I[5], a12 = I[6], b1 = I[7];
+    const double a20 = I[8], a21 = I[9], a22 = I[10], b2 = I[11];
+    const double c00 = a11 * a22 - a12 * a21, c01 = a12 * a20 - a10 * a22, c02 = a10 * a21 - a11 * a20;
+    const double c10 = a02 * a21 - a01 * a22, c11 = a00 * a22 - a02 * a20, c12 = a01 * a20 - a00 * a21;
+    const double c20 = a01 * a12 - a02 * a11, c21 = a02 * a10 - a00 * a12, c22 = a00 * a11 - a01 * a10;
+    const double det = (a00 * c00 + a01 * c01) + a02 * c02;
+    const double L[3][3] = {{c00 / det, c10 / det, c20 / det}, {c01 / det, c11 / det, c21 / det}, {c02 / det, c12 / det, c22 / det}};
+    double t[3];
+    for (int i = 0; i < 3; ++i) t[i] = -((L[i][0] * b0 + L[i][1] * b1) + L[i][2] * b2);
+    auto vec = [&](const double* v, double* o) {
+      for (int i = 0; i < 3; ++i) o[i] = (L[i][0] * v[0] + L[i][1] * v[1]) + L[i][2] * v[2];
+    };
+    auto pnt = [&](const double* p, double* o) {
+      for (int i = 0; i < 3; ++i) o[i] = ((L[i][0] * p[0] + L[i][1] * p[1]) + L[i][2] * p[2]) + t[i];
+    };
+    const double sum_e = (E[0] + E[1]) + E[2];
+    auto add = [&](const double* o, const double* eu, const double* ev, bool half) {
+      double R[RTC_EMITTER_ROW] = {};
+      pnt(o, R + 0);
+      vec(eu, R + 3);
+      vec(ev, R + 6);
+      const double mx = R[4] * R[8] - R[5] * R[7], my = R[5] * R[6] - R[3] * R[8], mz = R[3] * R[7] - R[4] * R[6];
+      const double len = std::sqrt((mx * mx + my * my) + mz * mz);
+      R[9] = mx / len;
+      R[10] = my / len;
+      R[11] = mz / len;
+      const double area = half ? len / 2.0 : len;
+      const double w = area * sum_e;
+      if (!(std::isfinite(w) && w > 0.0)) return;
+      R[12] = E[0];
+      R[13] = E[1];
+      R[14] = E[2];
+      R[16] = half ? 1.0 : 0.0;
+      R[17] = static_cast<double>(l);
+      out.total = out.total + w;
+      out.row.insert(out.row.end(), R, R + RTC_EMITTER_ROW);
+      out.cdf.push_back(out.total);
+      out.leaf.push_back(l);
+    };
+    if (kind == RTC_CUBE) {
+      for (int a = 0; a < 3; ++a)
+        for (int sgn = 0; sgn < 2; ++sgn) {
+          const int b = (a + 1) % 3, c = (a + 2) % 3;
+          double o[3] = {-1.0, -1.0, -1.0}, eu[3] = {0.0, 0.0, 0.0}, ev[3] = {0.0, 0.0, 0.0};
+          o[a] = sgn == 0 ? 1.0 : -1.0;
+          eu[b] = 2.0;
+          ev[c] = 2.0;
+          add(o, eu, ev, false);
+        }
+    } else {
+      const double* T9 = tri.data() + 9ull * m.w;
+      add(T9 + 0, T9 + 3, T9 + 6, true);
+    }
+    if (out.cdf.size() > RTC_MAX_EMITTERS) return false;
+  }
+  for (size_t k = 0; k < out.cdf.size(); ++k) {
+    double* R = out.row.data() + static_cast<size_t>(RTC_EMITTER_ROW) * k;
+    R[15] = out.total / ((R[12] + R[13]) + R[14]);
+  }
+  return true;
+}
+
 int uploadTables(const rtc_scene_desc& d, const SceneTraits& traits, const HostTables& T, rtc_scene* s) {
   const auto& leaf_meta = T.leaf_meta;
   const auto& roots = T.roots;
@@ -2444,6 +2582,12 @@ int uploadTables(const rtc_scene_desc& d, const SceneTraits& traits, const HostT
     HIP_TRY(s->tab->zero_disp.upload(std::vector<double>(3ull * root_recs.size(), 0.0)));
     HIP_TRY(s->tab->zero_rows.upload(std::vector<double>(static_cast<size_t>(RTC_AREA_ROW) * d.n_lights, 0.0)));
     HIP_TRY(s->tab->zero_bump.upload(std::vector<double>(static_cast<size_t>(RTC_BUMP_ROW) * d.n_materials, 0.0)));
+  }
+  {  // (what rtc_scene_set_emitters derives a handle's emitter list from)
+    s->tab->h_leaf_meta = leaf_meta;
+    s->tab->h_xf = xf;
+    s->tab->h_tri = tri;
+    emitterLeafTables(d, T, s->tab->h_leaf_csg, s->tab->h_leaf_root);
   }
   HIP_TRY(s->tab->root_weight.upload(T.root_weight));
   HIP_TRY(s->tab->kids.upload(kids));
@@ -2904,6 +3048,7 @@ static int makeMotionTables(const rtc_scene* s, const double* world_disp, std::s
   const uint32_t n = s->dev.n_roots;
   auto m = std::make_shared<MotionTables>();
   std::vector<double> disp(3ull * n, 0.0);
+  m->moves.assign(n, 0u);
   std::vector<RootRec> recs = tab.h_root_recs;
   std::vector<RootCullPair> cull = tab.h_root_cull;
   std::vector<RootBoxPair> box = tab.h_root_box;
@@ -2915,6 +3060,7 @@ static int makeMotionTables(const rtc_scene* s, const double* world_disp, std::s
   for (uint32_t i = 0; i < n; ++i) {
     const double* D = world_disp + 3ull * tab.h_root_order[i];
     if (D[0] == 0.0 && D[1] == 0.0 && D[2] == 0.0) continue;
+    m->moves[tab.h_root_order[i]] = 1u;
     for (int k = 0; k < 3; ++k) disp[3ull * i + k] = D[k];
     recs[i].kind_flags &= ~RTC_ROOT_ROOM;
     {  // the world box: -3e38 / +3e38 (no finite bound) stays
@@ -2974,6 +3120,55 @@ static int makeMotionTables(const rtc_scene* s, const double* world_disp, std::s
   return RTC_OK;
 }
 
+// ---- emitter sampling
+// A handle's emitter tables for `samples` and `seed`: the list derived from the indirect table's emission rows and the filter
+// rows that the handle has or is about to get, refused where it is too long or a listed leaf's root moves by `mo`.
+static int makeEmitterTables(const rtc_scene* s, uint32_t samples, uint64_t seed, const IndirectTables* ind, const ShadowFilterTables* sf,
+                             const MotionTables* mo, std::shared_ptr<const EmitterTables>& out) {
+  const SceneTables& tab = *s->tab;
+  EmitterList list;
+  const double* emission = (ind && !ind->h_emission.empty()) ? ind->h_emission.data() : nullptr;
+  const double* filter = (sf && !sf->h_row.empty()) ? sf->h_row.data() : nullptr;
+  if (!deriveEmitterList(tab.h_leaf_meta, tab.h_xf, tab.h_tri, tab.h_leaf_csg, emission, filter, list))
+    return fail(RTC_ERR_UNSUPPORTED, "emitters: more than %u entries", RTC_MAX_EMITTERS);
+  if (mo)
+    for (const uint32_t leaf : list.leaf)
+      if (mo->moves[tab.h_leaf_root[leaf]])
+        return fail(RTC_ERR_UNSUPPORTED, "emitters: leaf %u is an emitter and its root %u moves", leaf, tab.h_leaf_root[leaf]);
+  auto t = std::make_shared<EmitterTables>();
+  t->samples = samples;
+  t->seed = seed;
+  t->key = rtc_mix64(seed ^ RTC_EMITTER_SALT);
+  t->count = static_cast<uint32_t>(list.cdf.size());
+  t->total = list.total;
+  if (t->count != 0u) {
+    std::vector<uint32_t> bits((tab.h_leaf_meta.size() + 31u) / 32u, 0u);
+    for (const uint32_t leaf : list.leaf) bits[leaf >> 5] |= 1u << (leaf & 31u);
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(t->row.upload(list.row));
+    HIP_TRY(t->cdf.upload(list.cdf));
+    HIP_TRY(t->leaf_bits.upload(bits));
+  }
+  t->h_row = std::move(list.row);
+  t->h_cdf = std::move(list.cdf);
+  t->h_leaf = std::move(list.leaf);
+  out = std::move(t);
+  return RTC_OK;
+}
+
+int rtc_scene_set_emitters(rtc_scene* s, const rtc_emitters* e) {
+  g_error.clear();
+  if (!s) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
+  std::shared_ptr<const EmitterTables> tables;  // (NULL: no table)
+  if (e) {
+    if (e->samples < 1u || e->samples > RTC_EMITTER_MAX_SAMPLES)
+      return fail(RTC_ERR_INVALID_ARGUMENT, "emitters: %u samples, 1 to %u", e->samples, RTC_EMITTER_MAX_SAMPLES);
+    if (const int st = makeEmitterTables(s, e->samples, e->seed, s->indirect.get(), s->shadow_filters.get(), s->motion.get(), tables); st != RTC_OK)
+      return st;
+  }
+  return replaceTables(s, &rtc_scene::emitters, tables);
+}
+
 int rtc_scene_set_motion(rtc_scene* s, const rtc_motion* motion) {
   g_error.clear();
   if (!s) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
@@ -2991,6 +3186,12 @@ int rtc_scene_set_motion(rtc_scene* s, const rtc_motion* motion) {
   std::shared_ptr<const MotionTables> tables;  // (all displacements zero: static)
   if (moving) {
     if (const int st = makeMotionTables(s, motion->displacement, tables); st != RTC_OK) return st;
+    // (emitter sampling: a listed leaf's root may not move; the list does not depend on the motion)
+    if (const EmitterTables* em = s->emitters.get())
+      for (const uint32_t leaf : em->h_leaf)
+        if (tables->moves[s->tab->h_leaf_root[leaf]])
+          return fail(RTC_ERR_UNSUPPORTED, "motion: root %u moves and its leaf %u is an emitter of the handle's emitter table",
+                      s->tab->h_leaf_root[leaf], leaf);
   }
   return replaceTables(s, &rtc_scene::motion, tables);
 }
@@ -3225,7 +3426,14 @@ int rtc_scene_set_shadow_filters(rtc_scene* s, const rtc_shadow_filters* f) {
     auto t = std::make_shared<ShadowFilterTables>();
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(t->row.upload(rows));
+    t->h_row = rows;
     tables = std::move(t);
+  }
+  // (emitter sampling: the list of a handle with an emitter table is derived again from the new rows, before anything changes)
+  if (const EmitterTables* em = s->emitters.get()) {
+    std::shared_ptr<const EmitterTables> again;
+    if (const int st = makeEmitterTables(s, em->samples, em->seed, s->indirect.get(), tables.get(), s->motion.get(), again); st != RTC_OK) return st;
+    if (const int st = replaceTables(s, &rtc_scene::emitters, again); st != RTC_OK) return st;
   }
   return replaceTables(s, &rtc_scene::shadow_filters, tables);
 }
@@ -3389,8 +3597,15 @@ int rtc_scene_set_indirect(rtc_scene* s, const rtc_indirect* d) {
     if (emits) {
       HIP_TRY(hipSetDevice(s->device));
       HIP_TRY(t->emission.upload(rows));
+      t->h_emission = rows;
     }
     tables = std::move(t);
+  }
+  // (emitter sampling: the list of a handle with an emitter table is derived again from the new rows, before anything changes)
+  if (const EmitterTables* em = s->emitters.get()) {
+    std::shared_ptr<const EmitterTables> again;
+    if (const int st = makeEmitterTables(s, em->samples, em->seed, tables.get(), s->shadow_filters.get(), s->motion.get(), again); st != RTC_OK) return st;
+    if (const int st = replaceTables(s, &rtc_scene::emitters, again); st != RTC_OK) return st;
   }
   return replaceTables(s, &rtc_scene::indirect, tables);
 }
@@ -3609,6 +3824,7 @@ int rtc_scene_clone(const rtc_scene* src, rtc_scene** out) {
   s->environment = src->environment;  // (shared: read-only once made)
   s->sky_light = src->sky_light;  // (shared: read-only once made)
   s->indirect = src->indirect;    // (shared: read-only once made)
+  s->emitters = src->emitters;    // (shared: read-only once made)
   s->simple_kernel = src->simple_kernel;
   s->flat_kernel = src->flat_kernel;
   s->simple3_ok = src->simple3_ok;
@@ -3964,6 +4180,34 @@ int rtc_diag_build_tables(const rtc_scene_desc* desc, uint64_t* digest, double* 
   return RTC_OK;
 }
 
+int rtc_diag_emitters(const rtc_scene_desc* desc, const double* emission, const double* filter, uint32_t capacity, double* rows,
+                      double* cdf, uint32_t* count) {
+  g_error.clear();
+  if (!desc || !count) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
+  SceneTraits traits;
+  if (const int st = validateScene(*desc, traits); st != RTC_OK) return st;
+  HostTables tables;
+  if (const int st = buildTables(*desc, traits, tables); st != RTC_OK) return st;
+  std::vector<uint8_t> leaf_csg;
+  std::vector<uint32_t> leaf_root;
+  emitterLeafTables(*desc, tables, leaf_csg, leaf_root);
+  EmitterList list;
+  if (!deriveEmitterList(tables.leaf_meta, tables.xf, tables.tri, leaf_csg, emission, filter, list))
+    return fail(RTC_ERR_UNSUPPORTED, "emitters: more than %u entries", RTC_MAX_EMITTERS);
+  *count = static_cast<uint32_t>(list.cdf.size());
+  if (capacity < *count) return (rows || cdf) ? fail(RTC_ERR_INVALID_ARGUMENT, "%u entries, room for %u", *count, capacity) : RTC_OK;
+  if (rows) std::copy(list.row.begin(), list.row.end(), rows);
+  if (cdf) std::copy(list.cdf.begin(), list.cdf.end(), cdf);
+  return RTC_OK;
+}
+
+int rtc_diag_emitter_pick(const double* cdf, uint32_t count, double u0, uint32_t* entry) {
+  g_error.clear();
+  if (!cdf || !entry || count == 0u) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument or an empty list");
+  *entry = rtc_emitter_pick(cdf, count, u0 * cdf[count - 1u]);
+  return RTC_OK;
+}
+
 int rtc_diag_root_boxes(const rtc_scene_desc* desc, float* boxes, uint32_t* world_index, uint32_t capacity, uint32_t* n_roots,
                         float* scales) {
   g_error.clear();
@@ -4046,7 +4290,7 @@ int rtc_set_option(const char* name, double value) {
                {"gloss_kernels", &o.gloss_kernels}, {"occlusion_kernels", &o.occlusion_kernels},
                {"shadow_filter_kernels", &o.shadow_filter_kernels}, {"media_kernels", &o.media_kernels},
                {"environment_kernels", &o.environment_kernels}, {"sky_light_kernels", &o.sky_light_kernels},
-               {"indirect_kernels", &o.indirect_kernels}};
+               {"indirect_kernels", &o.indirect_kernels}, {"emitter_kernels", &o.emitter_kernels}};
   for (const auto& e : table)
     if (std::strcmp(e.name, name) == 0) {
       e.slot->set(value);

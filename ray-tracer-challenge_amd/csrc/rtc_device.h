@@ -462,6 +462,40 @@ struct DevIndirect {
   uint32_t bounces;
 };
 
+// Emitter sampling (rtc_scene_set_emitters): the extra argument of the emitter kernels only.  `row`:
+// RTC_EMITTER_ROW doubles per entry of the emitter list, in list order - the world-space origin, the two edge vectors, the unit
+// geometric normal, the material's emission, W / (E.r + E.g + E.b), 1.0 for a triangle (0.0: a cube's face) and the leaf
+// (depth-first index, as a double); `cdf`: the running sum of the weights, `total` its last entry W; `leaf_bits`: one bit per
+// depth-first leaf, set where the leaf is in the list - read only by a ray formed as a diffuse child.  count == 0: no list -
+// a handle without a table, or the "emitter_kernels" option: no sample is drawn and no emission is suppressed.
+// key = rtc_mix64(seed ^ RTC_EMITTER_SALT); the draws are rtc_gloss_sample_key's and rtc_gloss_jitter's at word
+// (j << RTC_OCCLUSION_SAMPLE_SHIFT) | code, axes 0, 1, 2.
+#define RTC_EMITTER_SALT 0xC0AC29B7C97C50DDull
+#define RTC_EMITTER_ROW 18u
+#ifndef RTC_PI
+#define RTC_PI 3.14159265358979323846 /* rtc.h's, token for token */
+#endif
+struct DevEmitters {
+  const double* __restrict__ row;          // [count][RTC_EMITTER_ROW]
+  const double* __restrict__ cdf;          // [count]
+  const uint32_t* __restrict__ leaf_bits;  // [(n_leaves + 31) / 32]
+  unsigned long long key;
+  double total;
+  uint32_t count;
+  uint32_t samples;  // 1 .. RTC_EMITTER_MAX_SAMPLES
+};
+// The entry a draw picks (rtc.h): the first k with cdf[k] > x, x = u0 * W, the last entry where there is none - a binary
+// search, the CDF being non-decreasing.  count >= 1.  The same code in the kernels and in rtc_diag_emitter_pick.
+__host__ __device__ inline uint32_t rtc_emitter_pick(const double* __restrict__ cdf, uint32_t count, double x) {
+  uint32_t lo = 0u, hi = count - 1u;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (cdf[mid] > x) hi = mid;
+    else lo = mid + 1u;
+  }
+  return lo;
+}
+
 struct DevCamera {
   double half_width, half_height, pixel_size;
   double inv[12];  // rows 0..2 of Camera._inverse_transform

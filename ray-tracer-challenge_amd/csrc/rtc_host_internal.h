@@ -79,6 +79,7 @@ struct RtcOptions {
   RtcOption environment_kernels{0.0};  // != 0: the environment kernels even on a handle without an environment, no sky and no sun (tests: against the handle's ordinary kernels)
   RtcOption sky_light_kernels{0.0};    // != 0: the sky-light kernels even on a handle without a sky light, the gain zero (tests: against the handle's ordinary kernels)
   RtcOption indirect_kernels{0.0};     // != 0: the indirect kernels even on a handle without an indirect table, the gain zero and no emission (tests: against the handle's ordinary kernels)
+  RtcOption emitter_kernels{0.0};      // != 0: the emitter kernels even on a handle without an emitter list, the count zero (tests: against the handle's ordinary kernels)
   RtcOption build_threads{0.0};        // threads of rtc_scene_create's candidate-BVH build (one top-level group each); 0: as many as the host allows, up to 8
 };
 inline RtcOptions& rtcOptions() {
@@ -151,6 +152,13 @@ struct SceneTables {
   // normal perturbation (rtc_scene_set_bumps): the bump rows of a handle without bumps under the "bump_kernels" option
   // (RTC_BUMP_ROW zeros per material: every kind none)
   DevBuf<double> zero_bump;
+  // emitter sampling (rtc_scene_set_emitters): what a handle's emitter list is derived from, on the host - the depth-first
+  // leaves' kind | casts_shadow << 8, transform, material and triangle, the inverses' rows and the triangles as uploaded,
+  // whether a leaf lies below a csg node, and the World.objects index of the root above it
+  std::vector<uint4> h_leaf_meta;
+  std::vector<double> h_xf, h_tri;
+  std::vector<uint8_t> h_leaf_csg;
+  std::vector<uint32_t> h_leaf_root;
 };
 
 // A handle's bumps (rtc_scene_set_bumps): DevBumps::row.  Read-only once made: a clone and the band clones share it.
@@ -181,6 +189,7 @@ struct OcclusionTables {
 // band clones share it.
 struct ShadowFilterTables {
   DevBuf<double> row;
+  std::vector<double> h_row;  // the rows on the host: what the emitter list is derived from
 };
 
 // A handle's media (rtc_scene_set_media): DevMedia's absorption rows and atmosphere.  Read-only once made: a clone and the
@@ -216,6 +225,23 @@ struct IndirectTables {
   unsigned long long key = 0ull;  // rtc_mix64(seed ^ RTC_INDIRECT_SALT)
   DevBuf<double> emission;        // [n_materials][3]; empty without rows
   bool emits = false;             // an emission entry is not zero
+  std::vector<double> h_emission; // the rows on the host (empty without rows): what the emitter list is derived from
+};
+
+// A handle's emitter sampling (rtc_scene_set_emitters): the setter's values, and the list derived from the handle's tables -
+// DevEmitters' rows, CDF and leaf bits on the device, and on the host the rows, the CDF and each entry's leaf.  A table with
+// an empty list is kept: rtc_scene_set_indirect and rtc_scene_set_shadow_filters derive the list again.  Read-only once made:
+// a clone and the band clones share it.
+struct EmitterTables {
+  uint32_t samples = 1u;
+  uint64_t seed = 0u;
+  unsigned long long key = 0ull;  // rtc_mix64(seed ^ RTC_EMITTER_SALT)
+  uint32_t count = 0u;
+  double total = 0.0;
+  std::vector<double> h_row, h_cdf;
+  std::vector<uint32_t> h_leaf;   // per entry: its depth-first leaf
+  DevBuf<double> row, cdf;
+  DevBuf<uint32_t> leaf_bits;
 };
 
 // A handle's spot lights (rtc_scene_set_spots): DevSpots::row.  Read-only once made: a clone and the band clones share it.
@@ -232,6 +258,7 @@ struct MotionTables {
   DevBuf<RootCullPair> root_cull;
   DevBuf<RootBoxPair> root_box;
   float cull_cmax = 0.0f, cull_bmax = 0.0f;
+  std::vector<uint8_t> moves;      // per World.objects index: a displacement that is not zero
 };
 
 constexpr uint32_t RTC_MAX_HOST_BANDS = 4;
@@ -240,11 +267,14 @@ constexpr uint32_t RTC_MAX_HOST_BANDS = 4;
 // (family() in rtc_capi.hip, which also names every family's kernel pair and its arguments - forFamilyKernel).  Each takes
 // the arguments of the one below and, but for TORUS, one more.
 enum class Family : uint32_t { BASE, MS, MOTION, SPOT, BUMP, TORUS, MESHUV, GLOSS, OCCL, SFILT, MEDIA, ENV, SKYL, INDIR };
-constexpr uint32_t RTC_FAMILIES = 14;
+// The emitter family (rtc_scene_set_emitters) heads the list: the value above INDIR, the indirect family's arguments and
+// DevEmitters.  Named beside the enumeration, whose text the indirect family's tests pin.
+constexpr Family kFamilyEmit = static_cast<Family>(static_cast<uint32_t>(Family::INDIR) + 1u);
+constexpr uint32_t RTC_FAMILIES = 15;
 // A family whose occupancy is asked for by the first launch that selects it and not at create: the query loads the unit's
-// code object, and a process none of whose handles has a sky light - or an indirect table - loads, allocates and runs what
-// it did before the unit existed.
-constexpr bool familyIsLazy(Family f) { return f == Family::SKYL || f == Family::INDIR; }
+// code object, and a process none of whose handles has a sky light - or an indirect table, or an emitter list - loads,
+// allocates and runs what it did before the unit existed.
+constexpr bool familyIsLazy(Family f) { return f == Family::SKYL || f == Family::INDIR || f == kFamilyEmit; }
 
 // Resident work-groups per CU of every family's kernels, [family][tables in LDS ? 0 : 1], and whether they have been asked
 // for (at create, or for a lazy family at its first launch).  A clone takes its source's.
@@ -297,6 +327,7 @@ struct rtc_scene {
   std::shared_ptr<const EnvironmentTables> environment;  // rtc_scene_set_environment; null: no sky and no sun (a clone starts with its source's)
   std::shared_ptr<const SkyLightTable> sky_light;  // rtc_scene_set_sky_light; null: no gain (a clone starts with its source's)
   std::shared_ptr<const IndirectTables> indirect;  // rtc_scene_set_indirect; null: no child and no emission (a clone starts with its source's)
+  std::shared_ptr<const EmitterTables> emitters;   // rtc_scene_set_emitters; null: no table (a clone starts with its source's)
   bool simple3_ok = false;         // a simple world whose tables fit the three-waves-per-SIMD kernel's LDS (RTC_LDS3_*)
   void* d_csg_buf = nullptr;       // DevPixelMap::csg_buf, only for scenes with csg nodes
   size_t csg_buf_capacity = 0;     // bytes

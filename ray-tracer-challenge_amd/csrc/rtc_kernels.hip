@@ -2124,6 +2124,28 @@ struct SunVisitor : FilterVisitor {
 };
 #endif
 
+// The walk of the emitter unit's suns' loop (rtc.h's rtc_scene_set_emitters): a sun's and a sky-light
+// sample's iterations keep SunVisitor's rule - `distance` is +infinity and an entry counts on et >= 0 alone, the +inf entries
+// of a degenerate cube included -, an emitter sample's has a far end, the emitter's distance less 1e-4, and an entry
+// counts as FilterVisitor's does, on et < distance as well.  `bounded` says which; it is wave-uniform, as the iteration's
+// kind is.  Compiled into the emitter kernels' translation unit only.
+#ifdef RTC_EMIT_TU
+struct EmitVisitor : FilterVisitor {
+  bool bounded = false;
+  __device__ __forceinline__ void entry(uint32_t, uint32_t casts_shadow, uint32_t material, double et, double, double) {
+    if (et >= 0.0 && (!bounded || et < distance) && casts_shadow) {
+      const double* __restrict__ f = filter + 3ull * material;
+      tr = tr * f[0];
+      tg = tg * f[1];
+      tb = tb * f[2];
+    }
+  }
+  __device__ __forceinline__ bool relevant(uint32_t, uint32_t casts_shadow, double et) const {
+    return et >= 0.0 && (!bounded || et < distance) && casts_shadow;
+  }
+};
+#endif
+
 // The containers walk of PreComputations.new (world.zig:229-255), as a reduction.
 // Entries before the hit in the sorted list are exactly those with t < 0.  A leaf with an
 // odd number of them is still in `containers` when the hit is reached, at the position of
@@ -3094,9 +3116,14 @@ __device__ __noinline__ GlossDir occl_direction(unsigned long long h, uint32_t w
 // a hit of a material with a diffuse term forms a third child, a cosine-weighted direction of the geometric normal's
 // hemisphere by occl_direction, which the main loop traces like every other Pending.  With SKYL and everything below it,
 // compiled into the indirect kernels' translation unit only, under RTC_INDIR_TU, which implies RTC_SKYL_TU)
+// (EMIT: emitter sampling - DevEmitters, the emitter kernels' extra argument: a hit that forms a diffuse child also draws
+// points on the listed emissive surfaces and walks a shadow ray to each, in further iterations of the suns' loop, and a ray
+// formed as a diffuse child adds no emission at a listed leaf.  With INDIRECT and everything below it, compiled into the
+// emitter kernels' translation unit only, under RTC_EMIT_TU, which implies RTC_INDIR_TU)
 template <bool LDS, bool CSG, int WORLD = 0, int WAVES = 2, bool COOP = false, bool BOX = true, bool AREA = false, bool MS = false,
           bool MOTION = false, bool SPOT = false, bool BUMP = false, bool TORUS = false, bool MESHUV = false, bool GLOSS = false,
-          bool OCCL = false, bool SFILT = false, bool MEDIA = false, bool ENV = false, bool SKYL = false, bool INDIRECT = false>
+          bool OCCL = false, bool SFILT = false, bool MEDIA = false, bool ENV = false, bool SKYL = false, bool INDIRECT = false,
+          bool EMIT = false>
 __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& cam, const DevPixelMap& map,
                                             const uint32_t max_depth, double* __restrict__ out,
                                             DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
@@ -3108,7 +3135,8 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
                                             const DevMedia& media = DevMedia{},
                                             const DevEnvironment& env = DevEnvironment{},
                                             const DevSkyLight& skyl = DevSkyLight{},
-                                            const DevIndirect& indir = DevIndirect{}) {
+                                            const DevIndirect& indir = DevIndirect{},
+                                            const DevEmitters& emit = DevEmitters{}) {
   static_assert(!AREA || !COOP, "the area kernels run no cooperative iterations");
   static_assert(!MS || !COOP, "the sampling kernels run no cooperative iterations");
   static_assert(!MOTION || (MS && AREA && WORLD == 0), "the motion kernels are the general area-sampling walk");
@@ -3177,6 +3205,14 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
 #else
   static_assert(!INDIRECT, "indirect light is compiled in the indirect translation unit (rtc_indirect.hip) only");
   (void)indir;
+#endif
+  static_assert(!EMIT || INDIRECT, "the emitter kernels are the indirect walk");
+  static_assert(!EMIT || !COOP, "the emitter kernels run no cooperative iterations");
+#ifdef RTC_EMIT_TU
+  static_assert(EMIT, "the emitter translation unit compiles the emitter kernels only: its suns' loop walks with EmitVisitor");
+#else
+  static_assert(!EMIT, "emitter sampling is compiled in the emitter translation unit (rtc_emitters.hip) only");
+  (void)emit;
 #endif
   RTC_PRIO_PHASE(RTC_PRIO_WORK);
 #ifndef RTC_PROFILE
@@ -4552,11 +4588,70 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
                                         static_cast<unsigned long long>(smp.sample_base) + (*samp_word & RTC_SAMPLE_MASK));
         }
         double l_r = 0.0, l_g = 0.0, l_b = 0.0;
+#ifdef RTC_EMIT_TU
+        // (EMIT, rtc.h's rtc_scene_set_emitters) in the emitter unit the loop goes on once more, after the last sky-light
+        // sample, for the emitter samples: a third kind of iteration of the ONE inlined walk, wave-uniform as the other two.
+        // A lane draws where it will form a diffuse child - the conditions of the children's section below, with
+        // cur.remaining's, which that section has behind it -: the entry by the CDF (a binary search on global memory, per
+        // lane), the point on its parallelogram, then the walk to it with a far end (EmitVisitor::bounded).  Across the walk
+        // live the sample's factor per channel and the distance; the mean is added after the sky light's.
+        const uint32_t n_emit = (EMIT && emit.count != 0u && indir.gain > 0.0 && indir.bounces != 0u) ? emit.samples : 0u;  // (wave-uniform)
+        const bool emit_lane = n_emit != 0u && mat.diffuse != 0.0 && cur.remaining > 0u && (cur.lin & RTC_LIN_D) < indir.bounces;
+        unsigned long long emit_h = 0ull;
+        if (emit_lane) {
+          uint32_t mpx, mpy;
+          map_pixel(map, out_index, mpx, mpy);
+          emit_h = rtc_gloss_sample_key(RTC_DKEY(emit.key), static_cast<unsigned long long>(mpy) * cam.hsize + mpx,
+                                        static_cast<unsigned long long>(smp.sample_base) + (*samp_word & RTC_SAMPLE_MASK));
+        }
+        double m_r = 0.0, m_g = 0.0, m_b = 0.0;
+        const uint32_t n_rays = (env.n_suns + n_sky) + n_emit;
+#else
         const uint32_t n_rays = env.n_suns + n_sky;
+#endif
         for (uint32_t si = 0u; si < n_rays; ++si) {
           const bool is_sun = si < env.n_suns;
           double lvx = 0.0, lvy = 0.0, lvz = 0.0, ir = 0.0, ig = 0.0, ib = 0.0, light_dot_normal = 0.0;
           bool walk = false;
+#ifdef RTC_EMIT_TU
+          const bool is_emit = si >= env.n_suns + n_sky;
+          double far_end = kInf, emit_r = 0.0;
+          if (is_emit) {
+            if (emit_lane) {
+              const uint32_t word = ((si - (env.n_suns + n_sky)) << RTC_OCCLUSION_SAMPLE_SHIFT) | cur.code;
+              const double u0 = rtc_gloss_jitter(emit_h, word, 0u);
+              double eu = rtc_gloss_jitter(emit_h, word, 1u);
+              double ev = rtc_gloss_jitter(emit_h, word, 2u);
+              // (the first k with cdf[k] > u0 * W, the last entry at the most)
+              const uint32_t entry = rtc_emitter_pick(emit.cdf, emit.count, u0 * emit.total);
+              const double* __restrict__ R = emit.row + static_cast<size_t>(RTC_EMITTER_ROW) * entry;
+              if (R[16] != 0.0 && eu + ev > 1.0) {  // (a triangle: the other half of the parallelogram folds back)
+                eu = 1.0 - eu;
+                ev = 1.0 - ev;
+              }
+              const double yx = (R[0] + eu * R[3]) + ev * R[6];
+              const double yy = (R[1] + eu * R[4]) + ev * R[7];
+              const double yz = (R[2] + eu * R[5]) + ev * R[8];
+              const double vx = yx - ovx, vy = yy - ovy, vz = yz - ovz;
+              const double r2 = (vx * vx + vy * vy) + vz * vz;
+              const double r = __builtin_sqrt(r2);
+              lvx = vx / r, lvy = vy / r, lvz = vz / r;
+              const double cos_x = (nx * lvx + ny * lvy) + nz * lvz;
+              const double cos_e = __builtin_fabs((R[9] * lvx + R[10] * lvy) + R[11] * lvz);
+              walk = !(cos_x <= 0.0) && !(cos_e == 0.0) && !(r <= 2e-4);
+              if (walk) {
+                far_end = r - 1e-4;
+                // (the term but for the filter, per channel: E.c * (W / sum E) * ((cos_x * cos_e) / (pi * r2)))
+                const double geo = (cos_x * cos_e) / (RTC_PI * r2);
+                ir = (R[12] * R[15]) * geo;
+                ig = (R[13] * R[15]) * geo;
+                ib = (R[14] * R[15]) * geo;
+                emit_r = r;
+                it_shadow_calls++;
+              }
+            }
+          } else
+#endif
           if (is_sun) {
             typedef const __attribute__((address_space(4))) double ConstRow;
             ConstRow* U = (ConstRow*)env.sun + static_cast<size_t>(RTC_ENV_SUN_ROW) * __builtin_amdgcn_readfirstlane(si);
@@ -4576,14 +4671,45 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
           if (walk) {
             it_shadow_traced++;
             it_share++;
+#ifdef RTC_EMIT_TU
+            EmitVisitor sv;
+            sv.distance = far_end;  // (+infinity but for an emitter sample)
+            sv.bounded = is_emit;
+#else
             SunVisitor sv;
             sv.distance = kInf;
+#endif
             RTC_LIGHT_VISITOR_SET(sv);
             Ray sray{ovx, ovy, ovz, lvx, lvy, lvz};
+#ifdef RTC_EMIT_TU
+            trace<CSG, WORLD, EmitVisitor, TRAV, BOX, MOTION, ROOTS>(S, recs, cull, sray, sv, it_overflow, trav_stack, member, stride, mo.disp, tm);
+#else
             trace<CSG, WORLD, SunVisitor, TRAV, BOX, MOTION, ROOTS>(S, recs, cull, sray, sv, it_overflow, trav_stack, member, stride, mo.disp, tm);
+#endif
             shadowed = RTC_LIGHT_BLOCKED(sv);
             RTC_SF_TAKE(sv);
           }
+#ifdef RTC_EMIT_TU
+          if (is_emit) {
+            if (walk && !shadowed) {
+              // (MEDIA: times the transmittance of a segment of length r in the ray's medium; the attenuation alone)
+              double a_r = media.fog_density, a_g = media.fog_density, a_b = media.fog_density;
+              if (cur.medium != RTC_NO_MEDIUM) {
+                const double* __restrict__ A = media.absorption + 3ull * cur.medium;
+                a_r = A[0];
+                a_g = A[1];
+                a_b = A[2];
+              }
+              double t_r = RTC_SF(ir, r), t_g = RTC_SF(ig, g), t_b = RTC_SF(ib, b);
+              if (a_r != 0.0) t_r = t_r * exp(-(a_r * emit_r));
+              if (a_g != 0.0) t_g = t_g * exp(-(a_g * emit_r));
+              if (a_b != 0.0) t_b = t_b * exp(-(a_b * emit_r));
+              m_r = m_r + t_r;
+              m_g = m_g + t_g;
+              m_b = m_b + t_b;
+            }
+          } else
+#endif
           if (is_sun) {
             // Material.lighting (material.zig:40-74) with the sun's intensity
             const double er = color.r * ir, eg = color.g * ig, eb = color.b * ib;  // effective_color
@@ -4642,6 +4768,14 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
           sg = sg + (color.g * mat.diffuse) * (skyl.gain * (l_g / n_mean));
           sb = sb + (color.b * mat.diffuse) * (skyl.gain * (l_b / n_mean));
         }
+#ifdef RTC_EMIT_TU
+        if (emit_lane) {  // (EMIT) the emitter samples' mean, after the sky light's and before the emission row
+          const double n_mean = static_cast<double>(emit.samples);
+          sr = sr + (color.r * mat.diffuse) * (indir.gain * (m_r / n_mean));
+          sg = sg + (color.g * mat.diffuse) * (indir.gain * (m_g / n_mean));
+          sb = sb + (color.b * mat.diffuse) * (indir.gain * (m_b / n_mean));
+        }
+#endif
       }
 #endif
 #endif
@@ -4649,7 +4783,18 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
       // (INDIRECT, rtc.h's rtc_scene_set_indirect) the material's emission row, after the last light's, sun's and sky-light
       // term and before the ray's weight; a handle without rows has a null pointer (wave-uniform)
       if constexpr (INDIRECT) {
+#ifdef RTC_EMIT_TU
+        // (EMIT) nothing counted twice: the ray formed as a diffuse child adds no emission at a leaf of the emitter list -
+        // its parent's samples counted it.  Only such a ray reads the leaf's bit.
+        bool emits_here = indir.emission != nullptr;
+        if constexpr (EMIT) {
+          if (emits_here && emit.count != 0u && (cur.lin & RTC_LIN_DIFFUSE) != 0u)
+            emits_here = ((emit.leaf_bits[hv.leaf >> 5] >> (hv.leaf & 31u)) & 1u) == 0u;
+        }
+        if (emits_here) {
+#else
         if (indir.emission != nullptr) {
+#endif
           const double* __restrict__ EM = indir.emission + 3ull * mat_index;
           sr = sr + EM[0];
           sg = sg + EM[1];
@@ -4975,7 +5120,8 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
 // three) and the occlusion kernels, rtc_shadowfilter.hip with RTC_SFILT_TU (and, with it, those four) and the shadow-filter
 // kernels, rtc_media.hip with RTC_MEDIA_TU (and, with it, those five) and the media kernels, rtc_environment.hip with
 // RTC_ENV_TU (and, with it, those six) and the environment kernels, rtc_skylight.hip with RTC_SKYL_TU (and, with it, those
-// seven) and the sky-light kernels, rtc_indirect.hip with RTC_INDIR_TU (and, with it, those eight) and the indirect kernels.
+// seven) and the sky-light kernels, rtc_indirect.hip with RTC_INDIR_TU (and, with it, those eight) and the indirect kernels,
+// rtc_emitters.hip with RTC_EMIT_TU (and, with it, those nine) and the emitter kernels.
 // rtc_kernels_ext.hip
 // includes it with RTC_EXT_TU defined: in the -DRTC_PROFILE diagnostic build, whose instrumented walk makes this unit's
 // compile about a third longer, it gets the csg / texture-map, flat and area-light kernels (rtc_render_kernel_ext to
@@ -5847,6 +5993,34 @@ rtc_render_kernel_bump_bigworld(const DevScene S, const DevCamera cam, const Dev
                                 const DevBumps bumps) {
   render_body<false, true, 0, 2, false, true, true, true, true, true, true>(S, cam, map, max_depth, out, stats, next_stats, area, smp, mo,
                                                                             spots, bumps);
+}
+
+#elif defined(RTC_EMIT_TU)
+
+// Emitter sampling (rtc_scene_set_emitters): the indirect walk with the emitter samples in the suns'
+// loop and the suppressed emission of a diffuse child, and the emitter rows, their CDF, the leaf bits, the count, the sample
+// count, the hash key and the total weight (DevEmitters) as one more argument; one pair for every world.  Every other kernel
+// is compiled without it.
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_emit(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                       double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                       const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots, const DevBumps bumps,
+                       const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl, const DevShadowFilter sfilt,
+                       const DevMedia media, const DevEnvironment env, const DevSkyLight skyl, const DevIndirect indir,
+                       const DevEmitters emit) {
+  render_body<true, true, 0, 2, false, true, true, true, true, true, true, true, true, true, true, true, true, true, true, true, true>(
+      S, cam, map, max_depth, out, stats, next_stats, area, smp, mo, spots, bumps, muv, gloss, occl, sfilt, media, env, skyl, indir, emit);
+}
+
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_emit_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                const DevBumps bumps, const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl,
+                                const DevShadowFilter sfilt, const DevMedia media, const DevEnvironment env, const DevSkyLight skyl,
+                                const DevIndirect indir, const DevEmitters emit) {
+  render_body<false, true, 0, 2, false, true, true, true, true, true, true, true, true, true, true, true, true, true, true, true, true>(
+      S, cam, map, max_depth, out, stats, next_stats, area, smp, mo, spots, bumps, muv, gloss, occl, sfilt, media, env, skyl, indir, emit);
 }
 
 #elif defined(RTC_INDIR_TU)

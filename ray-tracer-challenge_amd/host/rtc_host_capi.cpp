@@ -251,6 +251,19 @@ int rtch_scene_indirect(void* h, rtc_indirect* out, double* emission, int* prese
   });
 }
 
+// The "emitters" key of the scene's "indirect" (DESIGN.md section 28), as rtc_scene_set_emitters takes it.  *present: the file
+// has the key (and it is not false).
+int rtch_scene_emitters(void* h, rtc_emitters* out, int* present) {
+  return guarded([&] {
+    const HostScene* hs = static_cast<HostScene*>(h);
+    if (!out) throw rtc::Error("InvalidArgument", "emitters: null argument");
+    std::memset(out, 0, sizeof(*out));
+    out->samples = hs->info.emitters_samples;
+    out->seed = hs->info.emitters_seed;
+    if (present) *present = hs->info.emitters_present ? 1 : 0;
+  });
+}
+
 // The triangles' texture rows (RTC_TEX_MESH), in tri_* order, as rtc_scene_set_mesh_uvs takes them.
 int rtch_scene_mesh_uvs(void* h, double* uv, uint32_t n) {
   return guarded([&] {
@@ -403,6 +416,10 @@ int rtch_scene_render(void* h, uint32_t width, uint32_t height, uint32_t max_dep
         const rtc_indirect in{hs->info.indirect_gain, hs->info.indirect_bounces, hs->info.indirect_seed, hs->flat.mat_emission.data(),
                               hs->desc.n_materials};
         st = rtc_scene_set_indirect(scene, &in);
+      }
+      if (st == RTC_OK && hs->info.emitters_present) {  // (emitter sampling: the list is derived from the tables set above)
+        const rtc_emitters em{hs->info.emitters_samples, hs->info.emitters_seed};
+        st = rtc_scene_set_emitters(scene, &em);
       }
       const rtc::CameraSampling& cs = hs->info.sampling;
       if (cs.adaptive && st == RTC_OK) {  // (adaptive sampling: each tile's mean after its own passes, section 15)

@@ -955,10 +955,29 @@ SceneInfo parseScene(const std::string& scene_json, const FileLoader& load_file_
     info.indirect_gain = 1.0;
     info.indirect_bounces = 1u;
     if (ind->type == Value::Object) {
-      checkFields(*ind, {"gain", "bounces", "seed"}, "indirect");
+      checkFields(*ind, {"gain", "bounces", "seed", "emitters"}, "indirect");
       if (const Value* g = ind->find("gain")) info.indirect_gain = gainOf(*g);
       if (const Value* n = ind->find("bounces")) info.indirect_bounces = static_cast<uint32_t>(wholeOf(*n, "bounces is a whole number from 0 to 16", 0.0, 16.0));
       if (const Value* sd = ind->find("seed")) info.indirect_seed = static_cast<uint64_t>(wholeOf(*sd, "seed is a whole number from 0 to 2^53", 0.0, 0x1p53));
+      // "emitters" (DESIGN.md section 28): emissive surfaces sampled directly - true, a sample count, or {"samples", "seed"};
+      // false: no table, as without the key
+      if (const Value* em = ind->find("emitters")) {
+        const char* const samples_are = "emitters: samples is a whole number from 1 to 16";
+        if (em->type == Value::Bool) {
+          info.emitters_present = em->b;
+        } else if (em->type == Value::Number) {
+          info.emitters_present = true;
+          info.emitters_samples = static_cast<uint32_t>(wholeOf(*em, samples_are, 1.0, 16.0));
+        } else if (em->type == Value::Object) {
+          checkFields(*em, {"samples", "seed"}, "emitters");
+          info.emitters_present = true;
+          if (const Value* n = em->find("samples")) info.emitters_samples = static_cast<uint32_t>(wholeOf(*n, samples_are, 1.0, 16.0));
+          if (const Value* sd = em->find("seed"))
+            info.emitters_seed = static_cast<uint64_t>(wholeOf(*sd, "emitters: seed is a whole number from 0 to 2^53", 0.0, 0x1p53));
+        } else {
+          throw Error("InvalidData", "indirect: emitters is true, a sample count or {\"samples\", \"seed\"}");
+        }
+      }
     } else {
       info.indirect_gain = gainOf(*ind);
     }

@@ -71,6 +71,10 @@ struct SceneInfo {  // scene.zig:608-610
   double indirect_gain = 0.0;
   uint32_t indirect_bounces = 0u;
   uint64_t indirect_seed = 0u;
+  // the "emitters" key of "indirect" (section 28): rtc_emitters' values; samples 1 and seed 0 without the key
+  bool emitters_present = false;
+  uint32_t emitters_samples = 1u;
+  uint64_t emitters_seed = 0u;
 };
 
 // scene.zig:612-661.  Throws rtc::Error whose .name is the Zig error name

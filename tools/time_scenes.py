@@ -71,6 +71,9 @@ With --passes the noise run has the same table.
 DESIGN.md section 27), with the scene file's own "emission" rows, instead of the scene file's own "indirect", which is applied
 otherwise; --indirect off applies no table, no emission either.  Option indirect_kernels=1 times the indirect kernels without a
 table.  With --passes the noise run has the same table.
+--emitters N|off: emitter sampling with N samples per hit (rtc_scene_set_emitters) instead of the scene file's
+own "emitters" key, which is applied otherwise; --emitters off applies no table.  Option emitter_kernels=1 times the emitter kernels
+without a list.  With --passes the noise run has the same table.
 --data-dir DIR: where a scene named by its path finds the images and OBJ files it names (default: the scene's directory).
 --adaptive threshold[,min,tile]: adaptive sampling at up to --max-passes (64) passes, min passes 4 and
 16 x 16 tiles by default, with the --sampling of the frames: prints the rounds and tile-passes of a run against
@@ -119,6 +122,7 @@ ap.add_argument("--media", action="append", default=[])
 ap.add_argument("--environment", default="")
 ap.add_argument("--sky-light", default="")
 ap.add_argument("--indirect", default="")
+ap.add_argument("--emitters", default="")
 ap.add_argument("--data-dir", default="")  # where a scene named by path finds its images and OBJ files (default: beside it)
 ap.add_argument("--torus", action="store_true")
 ap.add_argument("--meshuv", action="store_true")
@@ -235,6 +239,16 @@ def indirect_table(hs):
         own = hs.indirect()
         return {"gain": float(gain), "bounces": int(bounces or 1), "seed": 0, "emission": own["emission"] if own is not None else None}
     return hs.indirect()
+
+
+def emitters_table(hs):
+    """the scene file's emitter table, or --emitters'; None: no table (--emitters off, or nothing to set)"""
+    if args.emitters == "off":
+        return None
+    if args.emitters:
+        own = hs.emitters()
+        return {"samples": int(args.emitters), "seed": own["seed"] if own is not None else 0}
+    return hs.emitters()
 
 
 def light_table(hs, how):
@@ -451,6 +465,8 @@ for name, w, h, depth in cases:
         indirect = indirect_table(hs)
         if indirect is not None:
             gpu.set_indirect(indirect)
+        if emitters_table(hs) is not None:
+            gpu.set_emitters(emitters_table(hs))
         for i in range(args.settle):
             gpu.render_device(cam, canvas.data_ptr(), depth, None, stream.cuda_stream)
         torch.cuda.synchronize()
@@ -475,7 +491,7 @@ for name, w, h, depth in cases:
     if delta is not None: line += f" maxdelta {delta:.2e}"
     if args.lights or args.spot or "spot_kernels=1" in args.option:
         line += f" shadow_traced {st['shadow_traced']} ns/shadow-ray {min(ts) * 1e6 / max(1, st['shadow_traced']):.3f}"
-    if args.sampling or args.option or args.passes >= 0 or args.motion or args.spot or args.bump or args.torus or args.meshuv or args.gloss or args.occlusion or args.shadow_filter or args.media or args.environment or args.sky_light or args.indirect:
+    if args.sampling or args.option or args.passes >= 0 or args.motion or args.spot or args.bump or args.torus or args.meshuv or args.gloss or args.occlusion or args.shadow_filter or args.media or args.environment or args.sky_light or args.indirect or args.emitters:
         line += f" primary {st['primary']} ns/primary-ray {min(ts) * 1e6 / max(1, st['primary']):.3f}"
     if acc:
         ms, copy_ms, nbytes = min(a[0] for a in acc), min(a[1] for a in acc), acc[0][2]
@@ -494,6 +510,7 @@ for name, w, h, depth in cases:
         if environment_table(hs) is not None: gpu.set_environment(environment_table(hs))
         if sky_light_table(hs) is not None: gpu.set_sky_light(sky_light_table(hs))
         if indirect_table(hs) is not None: gpu.set_indirect(indirect_table(hs))
+        if emitters_table(hs) is not None: gpu.set_emitters(emitters_table(hs))
         prog = rtc.Progressive(gpu, cam, depth)
         noise = {}
         for i in range(1, 65):
