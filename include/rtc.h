@@ -1039,6 +1039,75 @@ int rtc_render_adaptive(rtc_scene *scene, const rtc_camera *cam, uint32_t max_de
                         double *rgb_out, uint32_t *tile_passes_out);
 /* (Every adaptive entry point checks all its arguments before the device is touched: RTC_ERR_INVALID_ARGUMENT, with
  * nothing changed, otherwise.) */
+
+/* ---- denoising: variance-guided non-local means over an accumulated image ---- */
+#define RTC_DENOISE_MAX_RADIUS 10u
+#define RTC_DENOISE_MAX_PATCH 3u
+#define RTC_DENOISE_EPS 1e-10
+/*
+ * An image-space filter guided only by what the accumulation already holds: the mean u ([vsize][hsize][3]) and the sum of
+ * squares s ([vsize][hsize], rtc_accum's or rtc_adaptive_state's sumsq), from which every pixel has an estimate of its own
+ * variance.  It is the variance-cancelling non-local means of Rousselle, Knaus and Zwicker (2012) on a single buffer.  No
+ * render kernel is involved and no scene is needed.  Every operation is an IEEE double operation in the order written (no
+ * fused multiply-add); max(0, x) is x > 0 ? x : 0 and min(x, y) is y < x ? y : x (so a NaN is dropped by max and kept
+ * from x by min).
+ *
+ * P(x, y) is `passes`, or with tile_passes tile_passes[(y / tile_h) * ceil(hsize / tile_w) + x / tile_w] (the tiles of an
+ * adaptive run, numbered as there).  k2 = strength * strength and c3 = 3.0 * cancel.  A pixel's variance is
+ *     v(x, y) = P < 2 ? 0.0 : max(0, s - P * ((u.r * u.r + u.g * u.g) + u.b * u.b)) / (3.0 * ((P - 1.0) * P))
+ * - the quantity under rtc_accum's noise sum, formed as there.  A pixel with P < 2 has variance 0.
+ *
+ * For a pixel p, W = 0 and A = (0, 0, 0); then for dy = -radius .. radius and, inside it, dx = -radius .. radius, both
+ * ascending, with q = p + (dx, dy) inside the image:
+ *     S = 0, n = 0
+ *     for oy = -patch .. patch, inside it ox = -patch .. patch, ascending, with a = p + (ox, oy) and b = q + (ox, oy)
+ *     both inside the image:
+ *         D.c = u.c(a) - u.c(b)
+ *         t   = ((D.r * D.r + D.g * D.g) + D.b * D.b) - c3 * (v(a) + min(v(a), v(b)))
+ *         S   = S + t / (RTC_DENOISE_EPS + k2 * (v(a) + v(b)));   n = n + 1
+ *     w = exp(-max(0, S / (3.0 * n)));   W = W + w;   A.c = A.c + w * u.c(q)
+ * and out.c(p) = A.c / W.  q = p always gives w = 1, so W >= 1; radius 0 returns the mean to the bit.  Where v(a) and v(b)
+ * are both 0 a term is the squared difference over RTC_DENOISE_EPS: such a patch matches only patches equal to it, so a
+ * tile that has taken one pass (P_t = 1) keeps its values unless another patch repeats them.  exp is the device library's:
+ * results agree with a host restatement to 1e-12 * max(1, |value|).  Non-finite inputs propagate.
+ *
+ * rgba, where given, is the clamp of out: the bits of rtc_rgba8_device(out).
+ */
+typedef struct rtc_denoise_setting {
+  uint32_t radius, patch; /* the search window is (2 radius + 1)^2 pixels, a patch (2 patch + 1)^2: at most the maxima above */
+  double strength, cancel; /* k > 0: larger smooths more; the share of the variance taken out of a distance, >= 0 */
+} rtc_denoise_setting;
+/* (the defaults the scene loader and the Python binding use: radius 7, patch 2, strength 0.45, cancel 1.0) */
+typedef struct rtc_denoise {
+  const double *mean;          /* [vsize][hsize][3], required                                            */
+  const double *sumsq;         /* [vsize][hsize], required: rtc_accum's / the adaptive state's           */
+  uint32_t hsize, vsize;       /* >= 1; hsize * vsize <= 2^40 as rtc_rgba8_device                        */
+  uint32_t passes;             /* the passes behind every pixel; read when tile_passes is NULL: >= 2     */
+  const uint32_t *tile_passes; /* or NULL; [T] device: an adaptive run's P_t, tiles numbered as there    */
+  uint32_t tile_w, tile_h;     /* with tile_passes: 1 .. RTC_ADAPTIVE_MAX_TILE                           */
+  rtc_denoise_setting setting;
+  double *out;                 /* [vsize][hsize][3], required, must not overlap mean                     */
+  uint32_t *rgba;              /* [vsize][hsize] or NULL: the clamp of out, rtc_rgba8_device's bits      */
+} rtc_denoise;
+/*
+ * Enqueues the filter on `hip_stream` (not NULL; every pointer a device pointer of that stream's device).  Asynchronous;
+ * the caller orders it after whatever wrote mean and sumsq.  RTC_ERR_INVALID_ARGUMENT before any HIP call, with nothing
+ * launched, for: a NULL among d, mean, sumsq, out and the stream; a size of 0 or above 2^40 pixels; radius or patch above
+ * its maximum; strength not finite or <= 0; cancel not finite or < 0; passes < 2 without tile_passes; a tile size outside
+ * 1 .. RTC_ADAPTIVE_MAX_TILE with tile_passes; out overlapping mean.
+ */
+int rtc_denoise_device(const rtc_denoise *d, void *hip_stream);
+/*
+ * A denoised render with buffers of its own.  Synchronous, on the handle's own stream.  Without `adaptive`: sample passes
+ * 0 .. passes - 1 (passes >= 2), each through rtc_scene_set_sample_pass, rtc_render_device and
+ * rtc_scene_accumulate_device, and the handle's own sample pass is put back afterwards whatever happens.  With `adaptive`:
+ * a run as rtc_render_adaptive's, with max_passes taken from the setting; `passes` is ignored.  Then rtc_denoise_device
+ * (`setting` NULL: the defaults above) over the mean, the sums of squares and the passes (the run's P_t).  rgb_out
+ * [vsize][hsize][3] (host) gets the filtered image, noisy_out (host, or NULL) the mean.  Every argument is checked before
+ * the device is touched.  librtc_multi renders without it.
+ */
+int rtc_render_denoised(rtc_scene *scene, const rtc_camera *cam, uint32_t max_depth, uint32_t passes,
+                        const rtc_adaptive *adaptive, const rtc_denoise_setting *setting, double *rgb_out, double *noisy_out);
 void rtc_scene_destroy(rtc_scene *scene);
 
 /*

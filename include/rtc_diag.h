@@ -52,7 +52,9 @@ extern "C" {
  * ordinary kernels'), "indirect_kernels" (!= 0: the indirect kernels even on a handle without an indirect table, the gain
  * zero and no emission, so that their images can be held to the handle's ordinary kernels'), "emitter_kernels" (!= 0: the
  * emitter kernels even on a handle without an emitter list, the count zero, so that their images can be held to the handle's
- * ordinary kernels').
+ * ordinary kernels'), "denoise_naive" (!= 0: rtc_denoise_device runs rtc_denoise_naive_kernel, the literal form of rtc.h's
+ * loops with one thread per pixel, in place of the tiled kernels, so that the two can be held to each other and timed
+ * against each other; the bits are the same).
  * RTC_ERR_INVALID_ARGUMENT for a name the library does not know.
  * (The library reads no environment variables.)
  */
@@ -119,6 +121,10 @@ int rtc_diag_root_spheres(const rtc_scene_desc *desc, float *spheres, uint32_t c
  * only *n_roots). */
 #define RTC_ROOT_ALONE_FLAG 0x800u
 int rtc_diag_root_flags(const rtc_scene_desc *desc, uint32_t *flags, uint32_t capacity, uint32_t *n_roots);
+
+/* Diagnostic (tests/test_denoise_gpu.py): the output tile of the tiled denoise kernels, so that tests
+ * can name image sizes relative to it.  No device needed. */
+int rtc_diag_denoise_tile(uint32_t *w, uint32_t *h);
 
 #ifdef __cplusplus
 }

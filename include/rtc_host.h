@@ -29,7 +29,8 @@
  *                        rtch_scene_environment, through rtc_scene_set_environment; its sky light,
  *                        rtch_scene_sky_light, through rtc_scene_set_sky_light; its indirect light,
  *                        rtch_scene_indirect, through rtc_scene_set_indirect; its emitter sampling,
- *                        rtch_scene_emitters, through rtc_scene_set_emitters)
+ *                        rtch_scene_emitters, through rtc_scene_set_emitters; its denoiser, rtch_scene_denoise,
+ *                        through rtc_render_denoised)
  *
  * Every function that returns int returns 0 on success; otherwise rtch_last_error()
  * holds "<ZigStyleErrorName>: detail" (thread-local).
@@ -71,6 +72,12 @@ int rtch_scene_passes(void *handle, uint32_t *out);
  * (adaptive sampling; min-passes 4 and tile 16 when absent, "passes" the maximum): *enabled = 1
  * and the setting, or *enabled = 0 when the file has none.  rtch_scene_render then renders through rtc_render_adaptive. */
 int rtch_scene_adaptive(void *handle, int *enabled, rtc_adaptive *out);
+/* The camera's "sampling": {"denoise": true | {"radius": R, "patch": F, "strength": k, "cancel": a}} of the scene file
+ * (the denoiser; radius 7, patch 2, strength 0.45, cancel 1.0 where absent; false is the same as no
+ * key): *enabled = 1 and the setting, or *enabled = 0 and the defaults when the file has none.  The file then has "passes"
+ * of 2 or more, or "adaptive".  rtch_scene_render then renders through rtc_render_denoised, with the file's adaptive
+ * setting when it has one. */
+int rtch_scene_denoise(void *handle, int *enabled, rtc_denoise_setting *out);
 /* The top-level objects' "motion" of the scene file (motion blur): out[3 r .. 3 r + 2] = the
  * displacement of root r over the shutter, (0, 0, 0) for a root without one; n must be the description's n_roots.  Pass
  * it to rtc_scene_set_motion.  rtch_scene_render applies it. */

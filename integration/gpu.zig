@@ -125,6 +125,38 @@ pub const RtcEmitters = extern struct {
     seed: u64,
 };
 pub extern fn rtc_scene_set_emitters(scene: *RtcScene, emitters: ?*const RtcEmitters) c_int; // null: no table
+// The denoiser (rtc.h, rtc_denoise_device): variance-guided non-local means over an accumulated image - the mean and the sums
+// of squares of rtc_scene_accumulate_device or of an adaptive run; no scene is needed.  rtc_render_denoised is the whole path:
+// passes (or an adaptive run, RtcAdaptive), the filter, both images to the host.
+pub const RtcAdaptive = extern struct {
+    tile_w: u32,
+    tile_h: u32,
+    min_passes: u32,
+    max_passes: u32,
+    threshold: f64,
+};
+pub const RtcDenoiseSetting = extern struct {
+    radius: u32 = 7, // 0 .. 10
+    patch: u32 = 2, // 0 .. 3
+    strength: f64 = 0.45, // above 0
+    cancel: f64 = 1.0, // 0 or more
+};
+pub const RtcDenoise = extern struct {
+    mean: [*]const f64, // [vsize][hsize][3], device
+    sumsq: [*]const f64, // [vsize][hsize], device
+    hsize: u32,
+    vsize: u32,
+    passes: u32, // behind every pixel, 2 or more; read when tile_passes is null
+    tile_passes: ?[*]const u32, // an adaptive run's passes per tile, device
+    tile_w: u32,
+    tile_h: u32,
+    setting: RtcDenoiseSetting,
+    out: [*]f64, // [vsize][hsize][3], device, must not overlap mean
+    rgba: ?[*]u32, // [vsize][hsize] or null: the clamp of out
+};
+pub extern fn rtc_denoise_device(d: *const RtcDenoise, hip_stream: *anyopaque) c_int; // asynchronous
+pub extern fn rtc_render_denoised(scene: *RtcScene, cam: *const RtcCamera, max_depth: u32, passes: u32, adaptive: ?*const RtcAdaptive,
+                                  setting: ?*const RtcDenoiseSetting, rgb_out: [*]f64, noisy_out: ?[*]f64) c_int; // synchronous
 pub extern fn rtc_grow_csg_lists(scene: *RtcScene) c_int; // after an asynchronous frame whose stats.overflow != 0 on a csg scene: longer lists, render again
 pub extern fn rtc_scatter_tile_list_device(d_tiles: [*]const f64, d_tile_list: [*]const u32, n_tiles: u32, tile_w: u32, tile_h: u32,
                                            hsize: u32, vsize: u32, canvas: [*]f64, hip_stream: ?*anyopaque) c_int; // a rank's tiles straight into a (registered host) canvas

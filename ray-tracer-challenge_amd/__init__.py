@@ -188,6 +188,34 @@ class AdaptiveState(C.Structure):
                 ("round", C.c_uint32)]
 
 
+DENOISE_MAX_RADIUS = 10   # RTC_DENOISE_MAX_RADIUS
+DENOISE_MAX_PATCH = 3     # RTC_DENOISE_MAX_PATCH
+DENOISE_EPS = 1e-10       # RTC_DENOISE_EPS
+
+
+class DenoiseSetting(C.Structure):
+    """struct rtc_denoise_setting (include/rtc.h): the denoiser's search radius, patch radius, strength and the share of the
+    variance it takes out of a distance.  make() fills the defaults the scene loader uses."""
+
+    _fields_ = [("radius", C.c_uint32), ("patch", C.c_uint32), ("strength", C.c_double), ("cancel", C.c_double)]
+
+    @classmethod
+    def make(cls, radius=7, patch=2, strength=0.45, cancel=1.0):
+        return cls(radius, patch, strength, cancel)
+
+    def to_dict(self):
+        return {"radius": self.radius, "patch": self.patch, "strength": self.strength, "cancel": self.cancel}
+
+
+class Denoise(C.Structure):
+    """struct rtc_denoise (include/rtc.h): one call of rtc_denoise_device; device pointers as integers, 0 for tile_passes
+    (then `passes` holds for every pixel) or for rgba when it is not wanted."""
+
+    _fields_ = [("mean", C.c_void_p), ("sumsq", C.c_void_p), ("hsize", C.c_uint32), ("vsize", C.c_uint32), ("passes", C.c_uint32),
+                ("tile_passes", C.c_void_p), ("tile_w", C.c_uint32), ("tile_h", C.c_uint32), ("setting", DenoiseSetting),
+                ("out", C.c_void_p), ("rgba", C.c_void_p)]
+
+
 class Motion(C.Structure):
     """struct rtc_motion (include/rtc.h): a world-space displacement over the shutter per World.objects entry."""
 
@@ -471,16 +499,17 @@ RTC_SYMBOLS = ["rtc_scene_create", "rtc_scene_clone", "rtc_scene_destroy", "rtc_
                "rtc_scene_adaptive_begin_device", "rtc_scene_adaptive_accumulate_device", "rtc_scene_adaptive_step", "rtc_render_adaptive",
                "rtc_scene_set_spots", "rtc_scene_set_bumps", "rtc_scene_set_mesh_uvs", "rtc_scene_set_gloss",
                "rtc_scene_set_occlusion", "rtc_scene_set_shadow_filters", "rtc_scene_set_media", "rtc_scene_set_environment",
-               "rtc_scene_set_sky_light", "rtc_scene_set_indirect", "rtc_scene_set_emitters"]
+               "rtc_scene_set_sky_light", "rtc_scene_set_indirect", "rtc_scene_set_emitters", "rtc_denoise_device",
+               "rtc_render_denoised"]
 # (... and include/rtc_diag.h: diagnostics and tuning, for the tests, bench.py and tools/)
 RTC_DIAG_SYMBOLS = ["rtc_set_option", "rtc_last_kernel_name", "rtc_get_schedule", "rtc_get_chunk_times", "rtc_diag_build_tables", "rtc_diag_root_boxes", "rtc_diag_root_spheres", "rtc_diag_emitters", "rtc_diag_emitter_pick",
-                    "rtc_diag_root_flags"]
+                    "rtc_diag_root_flags", "rtc_diag_denoise_tile"]
 HOST_SYMBOLS = ["rtch_last_error", "rtch_scene_load", "rtch_scene_free", "rtch_scene_desc", "rtch_scene_camera",
                 "rtch_camera_rotate", "rtch_camera_move", "rtch_camera_make", "rtch_canvas_ppm", "rtch_canvas_rgba8", "rtch_scene_render", "rtch_set_loader_threads",
                 "rtch_scene_lights", "rtch_scene_sampling", "rtch_scene_passes", "rtch_scene_motion", "rtch_scene_adaptive",
                 "rtch_scene_spots", "rtch_scene_bumps", "rtch_scene_mesh_uvs", "rtch_scene_gloss", "rtch_scene_occlusion",
                 "rtch_scene_shadow_filters", "rtch_scene_media", "rtch_scene_environment", "rtch_scene_sky_light",
-                "rtch_scene_indirect", "rtch_scene_emitters"]
+                "rtch_scene_indirect", "rtch_scene_emitters", "rtch_scene_denoise"]
 
 MULTI_SYMBOLS = ["rtc_multi_create", "rtc_multi_destroy", "rtc_multi_render", "rtc_multi_render_rgba8", "rtc_multi_render_device", "rtc_multi_render_rgba8_device",
                  "rtc_multi_synchronize", "rtc_multi_stream", "rtc_multi_get_stats", "rtc_multi_balance", "rtc_multi_last_error"]
@@ -553,6 +582,10 @@ def hip_lib():
         lib.rtc_scene_set_emitters.argtypes = [C.c_void_p, C.POINTER(Emitters)]
         lib.rtc_diag_emitters.argtypes = [C.POINTER(SceneDesc), _dp, _dp, C.c_uint32, _dp, _dp, C.POINTER(C.c_uint32)]
         lib.rtc_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.POINTER(Adaptive), C.c_void_p, C.c_void_p]
+        lib.rtc_denoise_device.argtypes = [C.POINTER(Denoise), C.c_void_p]
+        lib.rtc_render_denoised.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.POINTER(Adaptive),
+                                            C.POINTER(DenoiseSetting), C.c_void_p, C.c_void_p]
+        lib.rtc_diag_denoise_tile.argtypes = [_u32p, _u32p]
         lib.rtc_scene_destroy.argtypes = [C.c_void_p]
         lib.rtc_scene_destroy.restype = None
         lib.rtc_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32] + [C.c_uint32] * 4 + [C.c_void_p]
@@ -616,6 +649,7 @@ def host_lib():
         lib.rtch_scene_indirect.argtypes = [C.c_void_p, C.POINTER(Indirect), _dp, C.POINTER(C.c_int), C.c_uint32]
         lib.rtch_scene_emitters.argtypes = [C.c_void_p, C.POINTER(Emitters), C.POINTER(C.c_int)]
         lib.rtch_scene_adaptive.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(Adaptive)]
+        lib.rtch_scene_denoise.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(DenoiseSetting)]
         lib.rtch_scene_camera.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Camera)]
         lib.rtch_camera_rotate.argtypes = [C.c_void_p, C.c_double]
         lib.rtch_camera_move.argtypes = [C.c_void_p, C.c_double]
@@ -905,6 +939,13 @@ class HostScene:
         _check_host(host_lib().rtch_scene_adaptive(self._h, C.byref(on), C.byref(a)))
         return a if on.value else None
 
+    def denoise(self):
+        """The camera's "sampling": {"denoise": ...} of the scene file (rtch_scene_denoise): a DenoiseSetting, or None when
+        the file has no such key (or has it false)."""
+        on, d = C.c_int(), DenoiseSetting()
+        _check_host(host_lib().rtch_scene_denoise(self._h, C.byref(on), C.byref(d)))
+        return d if on.value else None
+
     def rotate_camera(self, angle):
         """Renderer.rotateCamera (lib.zig:166-178): orbit the camera around its target, about `up`."""
         _check_host(host_lib().rtch_camera_rotate(self._h, C.c_double(angle)))
@@ -1119,6 +1160,16 @@ class GpuScene:
                                                  passes.ctypes.data))
         return rgb, passes
 
+    def render_denoised(self, cam, passes, adaptive=None, setting=None, max_depth=REFERENCE_DEPTH):
+        """rtc_render_denoised: `passes` sample passes (or, with an Adaptive, a whole adaptive run) accumulated on the device
+        and filtered by the denoiser (setting: a DenoiseSetting; None: the defaults); returns (denoised, mean), both
+        [h][w][3] f64 host arrays.  The handle's own sample pass is left as it was."""
+        rgb = np.empty((cam.vsize, cam.hsize, 3), dtype=np.float64)
+        noisy = np.empty((cam.vsize, cam.hsize, 3), dtype=np.float64)
+        _check_hip(hip_lib().rtc_render_denoised(self._s, C.byref(cam), max_depth, passes, C.byref(adaptive) if adaptive is not None else None,
+                                                 C.byref(setting) if setting is not None else None, rgb.ctypes.data, noisy.ctypes.data))
+        return rgb, noisy
+
     def clone(self):
         """rtc_scene_clone: a handle of its own (stream, schedule, counters) on the same device copy of the scene - one
         per frame in flight."""
@@ -1260,6 +1311,13 @@ class Progressive:
         torch.cuda.current_stream().wait_stream(self.stream)
         return self._rgba.view(self.cam.vsize, self.cam.hsize, 1).view(torch.uint8)
 
+    def denoised(self, **setting):
+        """[h][w][3] f64 on the device: the denoiser (rtc_denoise_device) over the mean, the sums of squares and the passes
+        so far (two at least), on this object's stream after its last step; `setting`: DenoiseSetting.make's keywords."""
+        if self.sumsq is None:
+            raise ValueError("Progressive(noise=False) keeps no sums of squares: nothing to guide the denoiser")
+        return _denoised(self, self.passes, None, setting)
+
 
 class AdaptiveProgressive:
     """Adaptive sampling on the device: each step() is one round of rtc_scene_adaptive_step - the tiles still noisy take
@@ -1323,6 +1381,42 @@ class AdaptiveProgressive:
         """[T] int32 on the device: the passes each tile has taken."""
         self._wait()
         return self._tile_passes
+
+    def denoised(self, **setting):
+        """[h][w][3] f64 on the device: the denoiser (rtc_denoise_device) over the mean, the sums of squares and every
+        tile's passes, on this object's stream after its last round; `setting`: DenoiseSetting.make's keywords."""
+        return _denoised(self, 0, self._tile_passes, setting)
+
+
+def denoise_device(mean_ptr, sumsq_ptr, hsize, vsize, out_ptr, stream, passes=0, tile_passes_ptr=None, tile=(0, 0), setting=None,
+                   rgba_ptr=None):
+    """rtc_denoise_device: the denoiser over a device image [vsize][hsize][3] and its sums of squares, enqueued on `stream`
+    (a HIP stream, not None); `passes` behind every pixel, or tile_passes_ptr ([T] u32 on the device) with tile = (w, h);
+    setting: a DenoiseSetting (None: the defaults); rgba_ptr: where the clamp of the result goes, or None."""
+    d = Denoise(mean_ptr, sumsq_ptr, hsize, vsize, passes, tile_passes_ptr, tile[0], tile[1], setting if setting is not None else DenoiseSetting.make(),
+                out_ptr, rgba_ptr)
+    _check_hip(hip_lib().rtc_denoise_device(C.byref(d), stream))
+
+
+def denoise_tile():
+    """rtc_diag_denoise_tile: (w, h) of the tiled denoise kernels' output tile."""
+    w, h = C.c_uint32(), C.c_uint32()
+    _check_hip(hip_lib().rtc_diag_denoise_tile(C.byref(w), C.byref(h)))
+    return w.value, h.value
+
+
+def _denoised(prog, passes, tile_passes, setting):
+    """Progressive.denoised / AdaptiveProgressive.denoised: a new tensor, filled on prog.stream; the caller's current stream
+    is ordered after it."""
+    import torch
+    out = torch.empty_like(prog._mean)
+    prog.stream.wait_stream(torch.cuda.current_stream())   # (`out` was allocated on the current stream)
+    tile = (prog.adaptive.tile_w, prog.adaptive.tile_h) if tile_passes is not None else (0, 0)
+    denoise_device(prog._mean.data_ptr(), prog.sumsq.data_ptr(), prog.cam.hsize, prog.cam.vsize, out.data_ptr(), prog.stream.cuda_stream,
+                   passes=passes, tile_passes_ptr=tile_passes.data_ptr() if tile_passes is not None else None, tile=tile,
+                   setting=DenoiseSetting.make(**setting))
+    torch.cuda.current_stream().wait_stream(prog.stream)
+    return out
 
 
 def canvas_register(array):

@@ -270,6 +270,9 @@ hipError_t rtcAdaptiveAccumLaunch(const double* frame, const uint32_t* list, uin
                                   uint32_t tile_w, uint32_t tile_h, uint32_t min_passes, uint32_t max_passes, double threshold,
                                   double* sum, double* sumsq, double* mean, uint32_t* rgba, uint32_t* tile_passes, double* tile_noise,
                                   uint32_t* active, uint32_t* n_active, double* max_noise, hipStream_t stream);
+// The denoiser's kernels (rtc_denoise.hip): the enqueue of the tiled form or (naive) the literal one, and the tiled form's tile.
+hipError_t rtcDenoiseLaunch(const rtc_denoise* d, bool naive, hipStream_t stream);
+void rtcDenoiseTile(uint32_t* w, uint32_t* h);
 extern "C" __global__ void rtc_estimate_kernel(const DevScene S, const DevCamera cam, const DevPixelMap map,
                                                uint32_t* __restrict__ chunk_cost, uint32_t* __restrict__ chunk_time,
                                                DevChunkShape* __restrict__ chunk_shape, DevPackState* __restrict__ state
@@ -3742,6 +3745,43 @@ int rtc_scene_adaptive_step(rtc_scene* s, const rtc_camera* cam, uint32_t max_de
   return RTC_OK;
 }
 
+// A run's buffers in one allocation, carved at 16-byte boundaries: sum, sumsq, mean, tile_noise, tile_passes, active,
+// n_active.  Returns the bytes they take; base NULL: only that.
+static size_t carveAdaptive(char* base, size_t n_px, uint32_t n_tiles, rtc_adaptive_state* st) {
+  auto up16 = [](size_t b) { return (b + 15u) & ~static_cast<size_t>(15u); };
+  const size_t b_sum = up16(n_px * 3u * sizeof(double)), b_sq = up16(n_px * sizeof(double)), b_noise = up16(n_tiles * sizeof(double)),
+               b_u32 = up16(n_tiles * sizeof(uint32_t));
+  if (base) {
+    char* p = base;
+    st->sum = reinterpret_cast<double*>(p), p += b_sum;
+    st->sumsq = reinterpret_cast<double*>(p), p += b_sq;
+    st->mean = reinterpret_cast<double*>(p), p += b_sum;
+    st->tile_noise = reinterpret_cast<double*>(p), p += b_noise;
+    st->tile_passes = reinterpret_cast<uint32_t*>(p), p += b_u32;
+    st->active = reinterpret_cast<uint32_t*>(p), p += b_u32;
+    st->n_active = reinterpret_cast<uint32_t*>(p);
+  }
+  return 2u * b_sum + b_sq + b_noise + 2u * b_u32 + 16u;
+}
+
+// Frees a call's allocation once the handle is idle
+struct FreeWhenIdle {
+  rtc_scene* s;
+  char* p;
+  ~FreeWhenIdle() {
+    (void)handleIdle(s);
+    (void)hipFree(p);
+  }
+};
+
+// begin, then rounds until no tile is active, on the handle's own stream
+static int adaptiveRun(rtc_scene* s, const rtc_camera* cam, uint32_t max_depth, const rtc_adaptive* a, rtc_adaptive_state* st) {
+  if (const int e = rtc_scene_adaptive_begin_device(s, cam->hsize, cam->vsize, a, st, s->stream); e != RTC_OK) return e;
+  for (uint32_t n = 1; n != 0u;)
+    if (const int e = rtc_scene_adaptive_step(s, cam, max_depth, a, st, &n, s->stream); e != RTC_OK) return e;
+  return RTC_OK;
+}
+
 int rtc_render_adaptive(rtc_scene* s, const rtc_camera* cam, uint32_t max_depth, const rtc_adaptive* a, double* rgb_out,
                         uint32_t* tile_passes_out) {
   g_error.clear();
@@ -3752,36 +3792,103 @@ int rtc_render_adaptive(rtc_scene* s, const rtc_camera* cam, uint32_t max_depth,
   if (const int e = checkAdaptivePasses(a, s); e != RTC_OK) return e;
   HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(ensureOwnStream(s));
-  // one allocation, carved at 16-byte boundaries: sum, sumsq, mean, tile_noise, tile_passes, active, n_active
   const size_t n_px = static_cast<size_t>(cam->hsize) * cam->vsize;
-  auto up16 = [](size_t b) { return (b + 15u) & ~static_cast<size_t>(15u); };
-  const size_t b_sum = up16(n_px * 3u * sizeof(double)), b_sq = up16(n_px * sizeof(double)), b_noise = up16(n_tiles * sizeof(double)),
-               b_u32 = up16(n_tiles * sizeof(uint32_t));
   char* base = nullptr;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&base), 2u * b_sum + b_sq + b_noise + 2u * b_u32 + 16u));
-  struct Free {
-    rtc_scene* s;
-    char* p;
-    ~Free() {
-      (void)handleIdle(s);
-      (void)hipFree(p);
-    }
-  } release{s, base};
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&base), carveAdaptive(nullptr, n_px, n_tiles, nullptr)));
+  FreeWhenIdle release{s, base};
   rtc_adaptive_state st{};
-  char* p = base;
-  st.sum = reinterpret_cast<double*>(p), p += b_sum;
-  st.sumsq = reinterpret_cast<double*>(p), p += b_sq;
-  st.mean = reinterpret_cast<double*>(p), p += b_sum;
-  st.tile_noise = reinterpret_cast<double*>(p), p += b_noise;
-  st.tile_passes = reinterpret_cast<uint32_t*>(p), p += b_u32;
-  st.active = reinterpret_cast<uint32_t*>(p), p += b_u32;
-  st.n_active = reinterpret_cast<uint32_t*>(p);
-  if (const int e = rtc_scene_adaptive_begin_device(s, cam->hsize, cam->vsize, a, &st, s->stream); e != RTC_OK) return e;
-  for (uint32_t n = 1; n != 0u;)
-    if (const int e = rtc_scene_adaptive_step(s, cam, max_depth, a, &st, &n, s->stream); e != RTC_OK) return e;
+  carveAdaptive(base, n_px, n_tiles, &st);
+  if (const int e = adaptiveRun(s, cam, max_depth, a, &st); e != RTC_OK) return e;
   HIP_TRY(hipMemcpyAsync(rgb_out, st.mean, n_px * 3u * sizeof(double), hipMemcpyDeviceToHost, s->stream));
   if (tile_passes_out)
     HIP_TRY(hipMemcpyAsync(tile_passes_out, st.tile_passes, n_tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return RTC_OK;
+}
+
+// ---- the denoiser
+static int checkDenoiseSetting(const rtc_denoise_setting& v) {
+  if (v.radius > RTC_DENOISE_MAX_RADIUS || v.patch > RTC_DENOISE_MAX_PATCH)
+    return fail(RTC_ERR_INVALID_ARGUMENT, "denoise: radius %u, patch %u (at most %u and %u)", v.radius, v.patch, RTC_DENOISE_MAX_RADIUS,
+                RTC_DENOISE_MAX_PATCH);
+  if (!std::isfinite(v.strength) || v.strength <= 0.0) return fail(RTC_ERR_INVALID_ARGUMENT, "denoise: strength %g (finite, above 0)", v.strength);
+  if (!std::isfinite(v.cancel) || v.cancel < 0.0) return fail(RTC_ERR_INVALID_ARGUMENT, "denoise: cancel %g (finite, 0 or more)", v.cancel);
+  return RTC_OK;
+}
+
+int rtc_denoise_device(const rtc_denoise* d, void* hip_stream) {
+  g_error.clear();
+  if (!d || !d->mean || !d->sumsq || !d->out || !hip_stream) return fail(RTC_ERR_INVALID_ARGUMENT, "denoise: null argument");
+  const uint64_t n_px = static_cast<uint64_t>(d->hsize) * d->vsize;
+  if (n_px == 0u || n_px > (1ull << 40)) return fail(RTC_ERR_INVALID_ARGUMENT, "denoise: image %ux%u", d->hsize, d->vsize);
+  if (const int e = checkDenoiseSetting(d->setting); e != RTC_OK) return e;
+  if (!d->tile_passes && d->passes < 2u) return fail(RTC_ERR_INVALID_ARGUMENT, "denoise: passes %u (2 or more)", d->passes);
+  if (d->tile_passes && (d->tile_w == 0u || d->tile_h == 0u || d->tile_w > RTC_ADAPTIVE_MAX_TILE || d->tile_h > RTC_ADAPTIVE_MAX_TILE))
+    return fail(RTC_ERR_INVALID_ARGUMENT, "denoise: tile %ux%u (1 to %u)", d->tile_w, d->tile_h, RTC_ADAPTIVE_MAX_TILE);
+  const uintptr_t m = reinterpret_cast<uintptr_t>(d->mean), o = reinterpret_cast<uintptr_t>(d->out), bytes = n_px * 3u * sizeof(double);
+  if (m < o + bytes && o < m + bytes) return fail(RTC_ERR_INVALID_ARGUMENT, "denoise: out overlaps mean");
+  HIP_TRY(rtcDenoiseLaunch(d, rtcOptions().denoise_naive != 0.0, static_cast<hipStream_t>(hip_stream)));
+  return RTC_OK;
+}
+
+int rtc_diag_denoise_tile(uint32_t* w, uint32_t* h) {
+  g_error.clear();
+  if (!w || !h) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
+  rtcDenoiseTile(w, h);
+  return RTC_OK;
+}
+
+int rtc_render_denoised(rtc_scene* s, const rtc_camera* cam, uint32_t max_depth, uint32_t passes, const rtc_adaptive* adaptive,
+                        const rtc_denoise_setting* setting, double* rgb_out, double* noisy_out) {
+  g_error.clear();
+  if (!s || !rgb_out) return fail(RTC_ERR_INVALID_ARGUMENT, "denoise: null argument");
+  if (const int e = checkCamera(cam); e != RTC_OK) return e;
+  const rtc_denoise_setting v = setting ? *setting : rtc_denoise_setting{7u, 2u, 0.45, 1.0};
+  if (const int e = checkDenoiseSetting(v); e != RTC_OK) return e;
+  uint32_t n_tiles = 0;
+  if (adaptive) {
+    if (const int e = checkAdaptive(adaptive, cam->hsize, cam->vsize, &n_tiles); e != RTC_OK) return e;
+    if (const int e = checkAdaptivePasses(adaptive, s); e != RTC_OK) return e;
+  } else {
+    if (passes < 2u) return fail(RTC_ERR_INVALID_ARGUMENT, "denoise: passes %u (2 or more)", passes);
+    if (!passFits(passes - 1u, s->sampling.samples))
+      return fail(RTC_ERR_INVALID_ARGUMENT, "denoise: %u passes of %u samples exceed %u sample indices", passes, s->sampling.samples,
+                  RTC_SAMPLING_INDEX_LIMIT);
+  }
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(ensureOwnStream(s));
+  // one allocation: the filtered image, the pass just rendered, then the sums as an adaptive run has them
+  const size_t n_px = static_cast<size_t>(cam->hsize) * cam->vsize;
+  const size_t b_img = (n_px * 3u * sizeof(double) + 15u) & ~static_cast<size_t>(15u);
+  char* base = nullptr;
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&base), 2u * b_img + carveAdaptive(nullptr, n_px, n_tiles, nullptr)));
+  FreeWhenIdle release{s, base};
+  double* const d_out = reinterpret_cast<double*>(base);
+  double* const d_frame = reinterpret_cast<double*>(base + b_img);
+  rtc_adaptive_state st{};
+  carveAdaptive(base + 2u * b_img, n_px, n_tiles, &st);
+  rtc_denoise d{st.mean, st.sumsq, cam->hsize, cam->vsize, passes, nullptr, 0u, 0u, v, d_out, nullptr};
+  if (adaptive) {
+    if (const int e = adaptiveRun(s, cam, max_depth, adaptive, &st); e != RTC_OK) return e;
+    d.tile_passes = st.tile_passes, d.tile_w = adaptive->tile_w, d.tile_h = adaptive->tile_h;
+  } else {
+    // pass p at sample pass p; the handle's own pass is put back whatever happens
+    const uint32_t own_pass = s->sample_pass;
+    int rc = RTC_OK;
+    for (uint32_t p = 0; p < passes && rc == RTC_OK; ++p) {
+      rc = rtc_scene_set_sample_pass(s, p);
+      if (rc == RTC_OK) rc = rtc_render_device(s, cam, max_depth, 0, 0, cam->hsize, cam->vsize, d_frame, s->stream);
+      const rtc_accum acc{d_frame, n_px, p + 1u, st.sum, st.sumsq, st.mean, nullptr, nullptr};
+      if (rc == RTC_OK) rc = rtc_scene_accumulate_device(s, &acc, s->stream);
+    }
+    const std::string error = g_error;
+    (void)rtc_scene_set_sample_pass(s, own_pass);
+    g_error = error;
+    if (rc != RTC_OK) return rc;
+  }
+  if (const int e = rtc_denoise_device(&d, s->stream); e != RTC_OK) return e;
+  HIP_TRY(hipMemcpyAsync(rgb_out, d_out, n_px * 3u * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  if (noisy_out) HIP_TRY(hipMemcpyAsync(noisy_out, st.mean, n_px * 3u * sizeof(double), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   return RTC_OK;
 }
@@ -4290,7 +4397,8 @@ int rtc_set_option(const char* name, double value) {
                {"gloss_kernels", &o.gloss_kernels}, {"occlusion_kernels", &o.occlusion_kernels},
                {"shadow_filter_kernels", &o.shadow_filter_kernels}, {"media_kernels", &o.media_kernels},
                {"environment_kernels", &o.environment_kernels}, {"sky_light_kernels", &o.sky_light_kernels},
-               {"indirect_kernels", &o.indirect_kernels}, {"emitter_kernels", &o.emitter_kernels}};
+               {"indirect_kernels", &o.indirect_kernels}, {"emitter_kernels", &o.emitter_kernels},
+               {"denoise_naive", &o.denoise_naive}};
   for (const auto& e : table)
     if (std::strcmp(e.name, name) == 0) {
       e.slot->set(value);

@@ -85,6 +85,14 @@ int rtch_scene_adaptive(void* h, int* enabled, rtc_adaptive* out) {
   });
 }
 
+int rtch_scene_denoise(void* h, int* enabled, rtc_denoise_setting* out) {
+  return guarded([&] {
+    const rtc::CameraSampling& s = static_cast<HostScene*>(h)->info.sampling;
+    *enabled = s.denoise ? 1 : 0;
+    *out = rtc_denoise_setting{s.denoise_radius, s.denoise_patch, s.denoise_strength, s.denoise_cancel};
+  });
+}
+
 int rtch_scene_motion(void* h, double* out, uint32_t n) {
   return guarded([&] {
     const HostScene* hs = static_cast<HostScene*>(h);
@@ -340,7 +348,7 @@ int rtch_scene_render(void* h, uint32_t width, uint32_t height, uint32_t max_dep
     // number - the bits of rtc_scene_accumulate_device's mean)
     const uint32_t passes = hs->info.sampling.passes;
     const size_t n = 3ull * cam.hsize * cam.vsize;
-    std::vector<double> frame(passes > 1u ? n : 0u);
+    std::vector<double> frame(passes > 1u && !hs->info.sampling.denoise ? n : 0u);
     rtc_scene* scene = nullptr;
     // (a scene with area lights: its light table; point lights only: the description alone, as before)
     int st = hs->flat.has_area_light ? rtc_scene_create_with_lights(&hs->desc, &hs->lights, &scene) : rtc_scene_create(&hs->desc, &scene);
@@ -422,17 +430,22 @@ int rtch_scene_render(void* h, uint32_t width, uint32_t height, uint32_t max_dep
         st = rtc_scene_set_emitters(scene, &em);
       }
       const rtc::CameraSampling& cs = hs->info.sampling;
-      if (cs.adaptive && st == RTC_OK) {  // (adaptive sampling: each tile's mean after its own passes, section 15)
+      if (cs.denoise && st == RTC_OK) {  // (the denoiser over the accumulated passes, or over an adaptive run, section 29)
+        const rtc_adaptive a{cs.tile_w, cs.tile_h, cs.min_passes, cs.passes, cs.threshold};
+        const rtc_denoise_setting dn{cs.denoise_radius, cs.denoise_patch, cs.denoise_strength, cs.denoise_cancel};
+        st = rtc_render_denoised(scene, &cam, max_depth, passes, cs.adaptive ? &a : nullptr, &dn, rgb_out, nullptr);
+      } else if (cs.adaptive && st == RTC_OK) {  // (adaptive sampling: each tile's mean after its own passes, section 15)
         const rtc_adaptive a{cs.tile_w, cs.tile_h, cs.min_passes, cs.passes, cs.threshold};
         st = rtc_render_adaptive(scene, &cam, max_depth, &a, rgb_out, nullptr);
       }
-      for (uint32_t p = 0; p < passes && st == RTC_OK && !cs.adaptive; ++p) {
+      const bool on_host = !cs.adaptive && !cs.denoise;  // (the passes summed here)
+      for (uint32_t p = 0; p < passes && st == RTC_OK && on_host; ++p) {
         if (p > 0u) st = rtc_scene_set_sample_pass(scene, p);
         if (st == RTC_OK) st = rtc_render(scene, &cam, max_depth, 0, 0, cam.hsize, cam.vsize, p == 0u ? rgb_out : frame.data());
         if (st == RTC_OK && p > 0u)
           for (size_t i = 0; i < n; ++i) rgb_out[i] = rgb_out[i] + frame[i];
       }
-      if (st == RTC_OK && passes > 1u && !cs.adaptive)
+      if (st == RTC_OK && passes > 1u && on_host)
         for (size_t i = 0; i < n; ++i) rgb_out[i] = rgb_out[i] / static_cast<double>(passes);
       rtc_scene_destroy(scene);
     }

@@ -988,8 +988,8 @@ SceneInfo parseScene(const std::string& scene_json, const FileLoader& load_file_
   info.camera.setTransform(Matrix4::viewTransform(from, to, up));
   if (const Value* smp = cam.find("sampling")) {  // (not in the reference: anti-aliasing and focal blur, every key optional)
     requireObject(*smp, "sampling");
-    checkFields(*smp, {"grid", "jitter", "aperture", "focal-distance", "seed", "passes", "adaptive", "gloss-seed", "occlusion-samples",
-                       "occlusion-seed"}, "sampling");
+    checkFields(*smp, {"grid", "jitter", "aperture", "focal-distance", "seed", "passes", "adaptive", "denoise", "gloss-seed",
+                       "occlusion-samples", "occlusion-seed"}, "sampling");
     CameraSampling& s = info.sampling;
     if (const Value* v = smp->find("grid")) {
       const size_t g = asUsize(*v, "grid");
@@ -1049,6 +1049,32 @@ SceneInfo parseScene(const std::string& scene_json, const FileLoader& load_file_
         s.tile_w = static_cast<uint32_t>(wh[0]);
         s.tile_h = static_cast<uint32_t>(wh[1]);
       }
+    }
+    if (const Value* dn = smp->find("denoise")) {  // (the denoiser, DESIGN.md section 29: true, false or the setting's keys)
+      if (dn->type == Value::Object) {
+        checkFields(*dn, {"radius", "patch", "strength", "cancel"}, "sampling.denoise");
+        s.denoise = true;
+        auto wholeOf = [](const Value& v, const std::string& what, double hi) {
+          if (v.type != Value::Number || !(v.num >= 0.0 && v.num <= hi) || v.num != std::floor(v.num))
+            throw Error("InvalidData", "sampling.denoise: " + what + " is a whole number from 0 to " + std::to_string(static_cast<unsigned>(hi)));
+          return static_cast<uint32_t>(v.num);
+        };
+        auto realOf = [](const Value& v, const std::string& what, bool zero) {
+          if (v.type != Value::Number || !std::isfinite(v.num) || v.num < 0.0 || (!zero && v.num == 0.0))
+            throw Error("InvalidData", "sampling.denoise: " + what + (zero ? " is finite and at least 0" : " is finite and above 0"));
+          return v.num;
+        };
+        if (const Value* v = dn->find("radius")) s.denoise_radius = wholeOf(*v, "radius", RTC_DENOISE_MAX_RADIUS);
+        if (const Value* v = dn->find("patch")) s.denoise_patch = wholeOf(*v, "patch", RTC_DENOISE_MAX_PATCH);
+        if (const Value* v = dn->find("strength")) s.denoise_strength = realOf(*v, "strength", false);
+        if (const Value* v = dn->find("cancel")) s.denoise_cancel = realOf(*v, "cancel", true);
+      } else if (dn->type == Value::Bool) {
+        s.denoise = dn->b;
+      } else {
+        throw Error("InvalidData", "sampling: denoise is true, false or {\"radius\", \"patch\", \"strength\", \"cancel\"}");
+      }
+      if (s.denoise && !s.adaptive && s.passes < 2)
+        throw Error("InvalidData", "sampling: denoise needs passes of 2 or more, or adaptive");
     }
   }
 

@@ -31,6 +31,10 @@ struct CameraSampling {
   double threshold = 0.0;
   uint32_t min_passes = 4;
   uint32_t tile_w = 16, tile_h = 16;
+  // "denoise" (section 29): rtch_scene_render filters the accumulated image (rtc_render_denoised); rtc_denoise_setting's values
+  bool denoise = false;
+  uint32_t denoise_radius = 7, denoise_patch = 2;
+  double denoise_strength = 0.45, denoise_cancel = 1.0;
   uint64_t gloss_seed = 0;  // "gloss-seed" (section 20): rtc_gloss::seed of the materials' "roughness"
   uint32_t occlusion_samples = 1;  // "occlusion-samples" (section 21): rtc_occlusion::samples of the materials' "ambient-occlusion"
   uint64_t occlusion_seed = 0;     // "occlusion-seed": rtc_occlusion::seed

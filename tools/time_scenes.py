@@ -74,6 +74,10 @@ table.  With --passes the noise run has the same table.
 --emitters N|off: emitter sampling with N samples per hit (rtc_scene_set_emitters) instead of the scene file's
 own "emitters" key, which is applied otherwise; --emitters off applies no table.  Option emitter_kernels=1 times the emitter kernels
 without a list.  With --passes the noise run has the same table.
+--denoise [R:F:k]: the denoiser (rtc_denoise_device) at radius R, patch F and strength k (7:2:0.45 without
+a value) over the mean of 8 progressive passes of the timed handle: prints the time of one call in the tiled form and in the
+literal one (option denoise_naive), each taken twice, alternating, with device events around 20 launches after a warm-up, and
+the largest difference between the two results (0 is expected).  The frame time on the same line is one pass.
 --data-dir DIR: where a scene named by its path finds the images and OBJ files it names (default: the scene's directory).
 --adaptive threshold[,min,tile]: adaptive sampling at up to --max-passes (64) passes, min passes 4 and
 16 x 16 tiles by default, with the --sampling of the frames: prints the rounds and tile-passes of a run against
@@ -123,6 +127,7 @@ ap.add_argument("--environment", default="")
 ap.add_argument("--sky-light", default="")
 ap.add_argument("--indirect", default="")
 ap.add_argument("--emitters", default="")
+ap.add_argument("--denoise", nargs="?", const="7:2:0.45", default="")
 ap.add_argument("--data-dir", default="")  # where a scene named by path finds its images and OBJ files (default: beside it)
 ap.add_argument("--torus", action="store_true")
 ap.add_argument("--meshuv", action="store_true")
@@ -239,6 +244,35 @@ def indirect_table(hs):
         own = hs.indirect()
         return {"gain": float(gain), "bounces": int(bounces or 1), "seed": 0, "emission": own["emission"] if own is not None else None}
     return hs.indirect()
+
+
+def time_denoise(gpu, cam, depth):
+    """--denoise: both kernel forms on an 8-pass mean of the handle, each twice, alternating; ms per call"""
+    f = args.denoise.split(":")
+    setting = dict(radius=int(f[0]), patch=int(f[1]) if len(f) > 1 else 2, strength=float(f[2]) if len(f) > 2 else 0.45)
+    prog = rtc.Progressive(gpu, cam, depth)
+    for _ in range(8):
+        prog.step()
+    launches, results, ms = max(20, args.frames), {}, {"tiled": [], "naive": []}
+    for rep in range(2):
+        for form in ("tiled", "naive"):
+            rtc.set_option("denoise_naive", 1 if form == "naive" else 0)
+            results[form] = prog.denoised(**setting)   # (warm-up: the code object is loaded)
+            torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(prog.stream)
+            for _ in range(launches):
+                rtc.denoise_device(prog._mean.data_ptr(), prog.sumsq.data_ptr(), cam.hsize, cam.vsize, results[form].data_ptr(),
+                                   prog.stream.cuda_stream, passes=prog.passes, setting=rtc.DenoiseSetting.make(**setting))
+            b.record(prog.stream)
+            torch.cuda.synchronize()
+            ms[form].append(a.elapsed_time(b) / launches)
+    rtc.set_option("denoise_naive", 0)
+    gpu.set_sample_pass(0)
+    delta = float((results["tiled"] - results["naive"]).abs().max())
+    return (f" | denoise {setting['radius']}:{setting['patch']}:{setting['strength']} on 8 passes, {launches} launches: tiled "
+            + " ".join(f"{t:.4f}" for t in ms["tiled"]) + " ms, naive " + " ".join(f"{t:.4f}" for t in ms["naive"])
+            + f" ms ({min(ms['naive']) / min(ms['tiled']):.1f}x), max |tiled - naive| {delta:.1e}")
 
 
 def emitters_table(hs):
@@ -480,6 +514,8 @@ for name, w, h, depth in cases:
         if st["overflow"]: kernel += " OVERFLOW"
         if args.passes >= 0:
             acc.append(time_accumulate(gpu, canvas, w * h, args.passes + 1))
+        if args.denoise and rep == 0:
+            denoise_line = time_denoise(gpu, cam, depth)
         if args.check and rep == 0 and not args.sampling and args.passes < 0:
             import numpy as np, oracle_binding as ob
             step = max(1, h // 24)
@@ -518,6 +554,8 @@ for name, w, h, depth in cases:
             if i in (4, 16, 64): noise[i] = v
         line += " | noise " + " ".join(f"{k}:{v:.3e}" for k, v in noise.items())
         gpu.close()
+    if args.denoise:
+        line += denoise_line
     if args.adaptive:
         line += time_adaptive(hs, table, cam, depth)
     out.append(line)
