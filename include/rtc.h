@@ -1108,6 +1108,98 @@ int rtc_denoise_device(const rtc_denoise *d, void *hip_stream);
  */
 int rtc_render_denoised(rtc_scene *scene, const rtc_camera *cam, uint32_t max_depth, uint32_t passes,
                         const rtc_adaptive *adaptive, const rtc_denoise_setting *setting, double *rgb_out, double *noisy_out);
+
+/* ---- the film stage: exposure, bloom, tone curve, transfer and the 8-bit clamp over an image ---- */
+#define RTC_FILM_MAX_RADIUS 32u
+#define RTC_FILM_EPS 1e-10
+#define RTC_FILM_CURVE_LINEAR 0
+#define RTC_FILM_CURVE_REINHARD 1
+#define RTC_FILM_CURVE_ACES 2
+#define RTC_FILM_CURVE_HABLE 3
+#define RTC_FILM_TRANSFER_LINEAR 0
+#define RTC_FILM_TRANSFER_SRGB 1
+#define RTC_FILM_TRANSFER_GAMMA 2
+/*
+ * An image-space output stage, the last link of render -> accumulate -> (denoise) -> film -> RGBA8: it takes a scene-referred
+ * image `in` ([vsize][hsize][3], linear radiance, values above 1.0 expected) to display values.  No render kernel is involved
+ * and no scene is needed.  Every operation is an IEEE double operation in the order written (no fused multiply-add);
+ * max(0, x) is x > 0 ? x : 0.  Y(c) = (0.2126 * c.r + 0.7152 * c.g) + 0.0722 * c.b.  For a pixel p, with n = hsize * vsize:
+ *
+ * 1. Exposure E.  With auto_key == 0, E = exposure.  Otherwise E = (exposure * auto_key) / exp(T / n), where T is the sum
+ *    over all n pixels q of log(RTC_FILM_EPS + max(0, Y(in(q)))).  The order of that one sum is the implementation's: it
+ *    is a function of n alone, so the bits are the same on every run and every device, and it uses no floating-point atomics.
+ *    exp and log are the device library's.  E stays on the device: no host synchronisation happens inside the call.
+ * 2. The exposed image: x(p).c = E * in(p).c.
+ * 3. Bloom, only where bloom_radius >= 1 and bloom_intensity > 0, with R = bloom_radius:
+ *        y = Y(x(p));  w = max(0, y - bloom_threshold) / (y > RTC_FILM_EPS ? y : RTC_FILM_EPS);  b(p).c = x(p).c * w
+ *    The weights are formed on the host in doubles and handed to the kernels by value:
+ *        raw[i] = exp(-(double)(i * i) / (2.0 * sigma * sigma)) for i = 0 .. R
+ *        norm = raw[0], then norm = norm + 2.0 * raw[i] for i ascending;  g[i] = raw[i] / norm
+ *    Rows: H(x, y).c = the sum, from 0.0, over i = -R .. R ascending of g[|i|] * b(x + i, y).c; terms whose column lies
+ *    outside the image are left out.  Columns: B(x, y).c = the sum likewise over j of g[|j|] * H(x, y + j).c.  Light that
+ *    leaves the frame is lost: there is no renormalisation.  (An implementation may add +0.0 where a term is left out: only
+ *    the sign of a zero can differ, and no comparison here tells the two apart.)
+ * 4. Combine: c = x(p).c + bloom_intensity * B(p).c; without bloom c = x(p).c.
+ * 5. Curve, per channel.  LINEAR: t = c.  REINHARD: t = (c * (1.0 + c / (white * white))) / (1.0 + c).
+ *    ACES (Narkowicz's fit): t = (c * (2.51 * c + 0.03)) / (c * (2.43 * c + 0.59) + 0.14).
+ *    HABLE: f(v) = ((v * (0.15 * v + 0.05) + 0.004) / (v * (0.15 * v + 0.5) + 0.06)) - 0.02 / 0.3 and t = f(c) / f(white);
+ *    f(white) is formed on the host.
+ * 6. Transfer, per channel.  LINEAR: o = t.  SRGB: o = t <= 0.0031308 ? 12.92 * t : 1.055 * pow(t, 1.0 / 2.4) - 0.055.
+ *    GAMMA: o = t > 0 ? pow(t, 1.0 / gamma) : 0.0.
+ * 7. out(p).c = o; rgba(p), where wanted, is the clamp of out: the bits of rtc_rgba8_device(out).
+ *
+ * Non-finite inputs propagate (but GAMMA's t > 0 test takes a NaN to 0.0).  The setting {1, 0, no bloom, LINEAR, ., LINEAR, .}
+ * returns `in` to the bit.  With manual
+ * exposure and a LINEAR transfer no library function is involved: every kernel form and a host restatement give the same
+ * bits.  With pow, or with the automatic exposure, results agree with a host restatement to 1e-12 * max(1, |value|).
+ */
+typedef struct rtc_film_setting {
+  double exposure;        /* finite, > 0: a linear multiplier                                   */
+  double auto_key;        /* finite, >= 0; 0 is off: the log-average luminance is taken to it   */
+  uint32_t bloom_radius;  /* 0 .. RTC_FILM_MAX_RADIUS; 0 is no bloom                            */
+  double bloom_sigma;     /* finite, > 0 where bloom_radius > 0                                 */
+  double bloom_threshold; /* finite, >= 0                                                       */
+  double bloom_intensity; /* finite, >= 0; 0 is no bloom                                        */
+  uint32_t curve;         /* RTC_FILM_CURVE_*                                                   */
+  double white;           /* finite, > 0; read by REINHARD and HABLE                            */
+  uint32_t transfer;      /* RTC_FILM_TRANSFER_*                                                */
+  double gamma;           /* finite, > 0; read by GAMMA                                         */
+} rtc_film_setting;
+/* (the defaults the scene loader and the Python binding use: exposure 1, auto_key 0, no bloom, curve ACES, white 4.0,
+ * transfer SRGB, gamma 2.2; "bloom": true is radius 12, sigma 4.0, threshold 1.0, intensity 0.15) */
+typedef struct rtc_film {
+  const double *in;         /* [vsize][hsize][3], required                                                   */
+  uint32_t hsize, vsize;    /* >= 1; hsize * vsize <= 2^40 as rtc_rgba8_device                               */
+  rtc_film_setting setting;
+  void *scratch;            /* rtc_film_scratch_bytes() bytes of device memory; may be NULL where that is 0  */
+  double *out;              /* [vsize][hsize][3], required, must not overlap in                              */
+  uint32_t *rgba;           /* [vsize][hsize] or NULL: the clamp of out, rtc_rgba8_device's bits             */
+  double *scale_out;        /* device, or NULL: where E is written                                           */
+} rtc_film;
+/*
+ * The bytes `scratch` must hold for a size and a setting: H, the partials of T and E.  0 where the setting needs none
+ * (manual exposure without bloom); 0 with rtc_last_error set for a size or a setting the contract refuses.
+ */
+size_t rtc_film_scratch_bytes(uint32_t hsize, uint32_t vsize, const rtc_film_setting *s);
+/*
+ * Enqueues the film stage on `hip_stream` (not NULL; every pointer a device pointer of that stream's device).  Asynchronous;
+ * the caller orders it after whatever wrote `in`; it makes no allocation.  RTC_ERR_INVALID_ARGUMENT before any HIP call,
+ * with nothing launched, for: a NULL among f, in, out and the stream; a NULL scratch where bytes are needed; a size of 0 or
+ * above 2^40 pixels; every out-of-range or non-finite field above; an unknown curve or transfer; out overlapping in.
+ */
+int rtc_film_device(const rtc_film *f, void *hip_stream);
+/*
+ * A filmed render with buffers of its own: the whole path on the handle's own stream, synchronous.  The accumulation
+ * (passes >= 1) or the adaptive run is exactly rtc_render_denoised's, and the handle's own sample pass is put back
+ * afterwards whatever happens.  Then rtc_denoise_device where `denoise` is not NULL (it needs passes >= 2 or `adaptive`),
+ * then rtc_film_device (`film` NULL: the defaults above) over its result.  rgb_out [vsize][hsize][3] (host) gets the
+ * film's out, rgba_out ([vsize][hsize][4] bytes, host) its clamp, linear_out (host) the image the film read; each may be
+ * NULL, but not both rgb_out and rgba_out.  Every argument is checked before the device is touched.  librtc_multi renders
+ * without it.
+ */
+int rtc_render_filmed(rtc_scene *scene, const rtc_camera *cam, uint32_t max_depth, uint32_t passes, const rtc_adaptive *adaptive,
+                      const rtc_denoise_setting *denoise, const rtc_film_setting *film, double *rgb_out, uint8_t *rgba_out,
+                      double *linear_out);
 void rtc_scene_destroy(rtc_scene *scene);
 
 /*

@@ -54,7 +54,9 @@ extern "C" {
  * emitter kernels even on a handle without an emitter list, the count zero, so that their images can be held to the handle's
  * ordinary kernels'), "denoise_naive" (!= 0: rtc_denoise_device runs rtc_denoise_naive_kernel, the literal form of rtc.h's
  * loops with one thread per pixel, in place of the tiled kernels, so that the two can be held to each other and timed
- * against each other; the bits are the same).
+ * against each other; the bits are the same), "film_naive" (!= 0: a rtc_film_device that blooms runs rtc_film_naive_row_kernel
+ * and rtc_film_naive_resolve_kernel, the literal forms of rtc.h's loops with one thread per pixel and no LDS, in place of the
+ * tiled kernels, for the same two purposes; the bits are the same).
  * RTC_ERR_INVALID_ARGUMENT for a name the library does not know.
  * (The library reads no environment variables.)
  */
@@ -125,6 +127,11 @@ int rtc_diag_root_flags(const rtc_scene_desc *desc, uint32_t *flags, uint32_t ca
 /* Diagnostic (tests/test_denoise_gpu.py): the output tile of the tiled denoise kernels, so that tests
  * can name image sizes relative to it.  No device needed. */
 int rtc_diag_denoise_tile(uint32_t *w, uint32_t *h);
+
+/* Diagnostic (tests/test_film_gpu.py): the extents of the tiled film kernels' output tiles - the row
+ * kernel's width, the resolve kernel's width and height - so that tests can name image sizes relative to them.  No device
+ * needed. */
+int rtc_diag_film_tile(uint32_t *row_w, uint32_t *col_w, uint32_t *col_h);
 
 #ifdef __cplusplus
 }

@@ -30,7 +30,7 @@
  *                        rtch_scene_sky_light, through rtc_scene_set_sky_light; its indirect light,
  *                        rtch_scene_indirect, through rtc_scene_set_indirect; its emitter sampling,
  *                        rtch_scene_emitters, through rtc_scene_set_emitters; its denoiser, rtch_scene_denoise,
- *                        through rtc_render_denoised)
+ *                        through rtc_render_denoised; its film stage, rtch_scene_film, through rtc_render_filmed)
  *
  * Every function that returns int returns 0 on success; otherwise rtch_last_error()
  * holds "<ZigStyleErrorName>: detail" (thread-local).
@@ -78,6 +78,15 @@ int rtch_scene_adaptive(void *handle, int *enabled, rtc_adaptive *out);
  * of 2 or more, or "adaptive".  rtch_scene_render then renders through rtc_render_denoised, with the file's adaptive
  * setting when it has one. */
 int rtch_scene_denoise(void *handle, int *enabled, rtc_denoise_setting *out);
+/* The camera's "film": true | {"exposure": m | {"stops": s}, "auto-exposure": true | k, "bloom": true | {"radius": R,
+ * "sigma": s, "threshold": t, "intensity": i}, "tone-curve": "linear" | "reinhard" | "aces" | "hable", "white": w,
+ * "transfer": "linear" | "srgb" | {"gamma": g}} of the scene file (the film stage; exposure 1, no
+ * automatic exposure, no bloom, ACES, white 4, sRGB where absent; {"stops": s} is exp2(s), "auto-exposure": true the key 0.18,
+ * "bloom": true radius 12, sigma 4, threshold 1, intensity 0.15, and a bloom's sigma without a value its radius / 3; false is the
+ * same as no key): *enabled = 1 and the setting, or *enabled = 0 and the defaults when the file has none.  The key needs no
+ * "passes".  rtch_scene_render then renders through rtc_render_filmed, with the file's passes, adaptive and denoise settings,
+ * and its rgb_out is the film's out: display values, not radiance. */
+int rtch_scene_film(void *handle, int *enabled, rtc_film_setting *out);
 /* The top-level objects' "motion" of the scene file (motion blur): out[3 r .. 3 r + 2] = the
  * displacement of root r over the shutter, (0, 0, 0) for a root without one; n must be the description's n_roots.  Pass
  * it to rtc_scene_set_motion.  rtch_scene_render applies it. */

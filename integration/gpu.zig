@@ -157,6 +157,37 @@ pub const RtcDenoise = extern struct {
 pub extern fn rtc_denoise_device(d: *const RtcDenoise, hip_stream: *anyopaque) c_int; // asynchronous
 pub extern fn rtc_render_denoised(scene: *RtcScene, cam: *const RtcCamera, max_depth: u32, passes: u32, adaptive: ?*const RtcAdaptive,
                                   setting: ?*const RtcDenoiseSetting, rgb_out: [*]f64, noisy_out: ?[*]f64) c_int; // synchronous
+// The film stage (rtc.h, rtc_film_device): exposure (manual, or to a key from the image's log-average luminance), a Gaussian
+// bloom of what lies above a threshold, a tone curve, a transfer function and the 8-bit clamp over a scene-referred image on
+// the device; no scene is needed.  rtc_render_filmed is the whole path: passes (or an adaptive run), the denoiser where asked,
+// the film, the images to the host.
+pub const RtcFilmSetting = extern struct {
+    exposure: f64 = 1.0, // above 0: a linear multiplier
+    auto_key: f64 = 0.0, // 0: manual; else the log-average luminance is taken to it
+    bloom_radius: u32 = 0, // 0 .. 32; 0: no bloom
+    bloom_sigma: f64 = 4.0, // above 0 where the radius is
+    bloom_threshold: f64 = 1.0, // 0 or more
+    bloom_intensity: f64 = 0.0, // 0 or more; 0: no bloom
+    curve: u32 = 2, // 0 linear, 1 Reinhard, 2 ACES, 3 Hable
+    white: f64 = 4.0, // above 0: Reinhard's and Hable's white point
+    transfer: u32 = 1, // 0 linear, 1 sRGB, 2 gamma
+    gamma: f64 = 2.2, // above 0
+};
+pub const RtcFilm = extern struct {
+    in: [*]const f64, // [vsize][hsize][3], device
+    hsize: u32,
+    vsize: u32,
+    setting: RtcFilmSetting,
+    scratch: ?*anyopaque, // rtc_film_scratch_bytes() bytes, device; null where that is 0
+    out: [*]f64, // [vsize][hsize][3], device, must not overlap in
+    rgba: ?[*]u32, // [vsize][hsize] or null: the clamp of out
+    scale_out: ?*f64, // device, or null: where the exposure E is written
+};
+pub extern fn rtc_film_scratch_bytes(hsize: u32, vsize: u32, setting: *const RtcFilmSetting) usize; // 0: none needed, or (rtc_last_error set) refused
+pub extern fn rtc_film_device(f: *const RtcFilm, hip_stream: *anyopaque) c_int; // asynchronous
+pub extern fn rtc_render_filmed(scene: *RtcScene, cam: *const RtcCamera, max_depth: u32, passes: u32, adaptive: ?*const RtcAdaptive,
+                                denoise: ?*const RtcDenoiseSetting, film: ?*const RtcFilmSetting, rgb_out: ?[*]f64, rgba_out: ?[*]u8,
+                                linear_out: ?[*]f64) c_int; // synchronous
 pub extern fn rtc_grow_csg_lists(scene: *RtcScene) c_int; // after an asynchronous frame whose stats.overflow != 0 on a csg scene: longer lists, render again
 pub extern fn rtc_scatter_tile_list_device(d_tiles: [*]const f64, d_tile_list: [*]const u32, n_tiles: u32, tile_w: u32, tile_h: u32,
                                            hsize: u32, vsize: u32, canvas: [*]f64, hip_stream: ?*anyopaque) c_int; // a rank's tiles straight into a (registered host) canvas

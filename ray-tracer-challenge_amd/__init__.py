@@ -216,6 +216,41 @@ class Denoise(C.Structure):
                 ("out", C.c_void_p), ("rgba", C.c_void_p)]
 
 
+FILM_MAX_RADIUS = 32      # RTC_FILM_MAX_RADIUS
+FILM_EPS = 1e-10          # RTC_FILM_EPS
+FILM_CURVES = {"linear": 0, "reinhard": 1, "aces": 2, "hable": 3}     # RTC_FILM_CURVE_*
+FILM_TRANSFERS = {"linear": 0, "srgb": 1, "gamma": 2}                 # RTC_FILM_TRANSFER_*
+
+
+class FilmSetting(C.Structure):
+    """struct rtc_film_setting (include/rtc.h): the film stage's exposure, bloom, tone curve and transfer function.  make()
+    fills the defaults the scene loader uses; curve and transfer are numbers or the names of FILM_CURVES / FILM_TRANSFERS;
+    bloom=True is the loader's "bloom": true."""
+
+    _fields_ = [("exposure", C.c_double), ("auto_key", C.c_double), ("bloom_radius", C.c_uint32), ("bloom_sigma", C.c_double),
+                ("bloom_threshold", C.c_double), ("bloom_intensity", C.c_double), ("curve", C.c_uint32), ("white", C.c_double),
+                ("transfer", C.c_uint32), ("gamma", C.c_double)]
+
+    @classmethod
+    def make(cls, exposure=1.0, auto_key=0.0, bloom_radius=0, bloom_sigma=4.0, bloom_threshold=1.0, bloom_intensity=0.0, curve="aces",
+             white=4.0, transfer="srgb", gamma=2.2, bloom=False):
+        if bloom:
+            bloom_radius, bloom_sigma, bloom_threshold, bloom_intensity = 12, 4.0, 1.0, 0.15
+        return cls(exposure, auto_key, bloom_radius, bloom_sigma, bloom_threshold, bloom_intensity, FILM_CURVES.get(curve, curve), white,
+                   FILM_TRANSFERS.get(transfer, transfer), gamma)
+
+    def to_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class Film(C.Structure):
+    """struct rtc_film (include/rtc.h): one call of rtc_film_device; device pointers as integers, 0 for scratch where
+    film_scratch_bytes() is 0 and for rgba or scale_out when they are not wanted."""
+
+    _fields_ = [("in_", C.c_void_p), ("hsize", C.c_uint32), ("vsize", C.c_uint32), ("setting", FilmSetting), ("scratch", C.c_void_p),
+                ("out", C.c_void_p), ("rgba", C.c_void_p), ("scale_out", C.c_void_p)]
+
+
 class Motion(C.Structure):
     """struct rtc_motion (include/rtc.h): a world-space displacement over the shutter per World.objects entry."""
 
@@ -500,16 +535,16 @@ RTC_SYMBOLS = ["rtc_scene_create", "rtc_scene_clone", "rtc_scene_destroy", "rtc_
                "rtc_scene_set_spots", "rtc_scene_set_bumps", "rtc_scene_set_mesh_uvs", "rtc_scene_set_gloss",
                "rtc_scene_set_occlusion", "rtc_scene_set_shadow_filters", "rtc_scene_set_media", "rtc_scene_set_environment",
                "rtc_scene_set_sky_light", "rtc_scene_set_indirect", "rtc_scene_set_emitters", "rtc_denoise_device",
-               "rtc_render_denoised"]
+               "rtc_render_denoised", "rtc_film_scratch_bytes", "rtc_film_device", "rtc_render_filmed"]
 # (... and include/rtc_diag.h: diagnostics and tuning, for the tests, bench.py and tools/)
 RTC_DIAG_SYMBOLS = ["rtc_set_option", "rtc_last_kernel_name", "rtc_get_schedule", "rtc_get_chunk_times", "rtc_diag_build_tables", "rtc_diag_root_boxes", "rtc_diag_root_spheres", "rtc_diag_emitters", "rtc_diag_emitter_pick",
-                    "rtc_diag_root_flags", "rtc_diag_denoise_tile"]
+                    "rtc_diag_root_flags", "rtc_diag_denoise_tile", "rtc_diag_film_tile"]
 HOST_SYMBOLS = ["rtch_last_error", "rtch_scene_load", "rtch_scene_free", "rtch_scene_desc", "rtch_scene_camera",
                 "rtch_camera_rotate", "rtch_camera_move", "rtch_camera_make", "rtch_canvas_ppm", "rtch_canvas_rgba8", "rtch_scene_render", "rtch_set_loader_threads",
                 "rtch_scene_lights", "rtch_scene_sampling", "rtch_scene_passes", "rtch_scene_motion", "rtch_scene_adaptive",
                 "rtch_scene_spots", "rtch_scene_bumps", "rtch_scene_mesh_uvs", "rtch_scene_gloss", "rtch_scene_occlusion",
                 "rtch_scene_shadow_filters", "rtch_scene_media", "rtch_scene_environment", "rtch_scene_sky_light",
-                "rtch_scene_indirect", "rtch_scene_emitters", "rtch_scene_denoise"]
+                "rtch_scene_indirect", "rtch_scene_emitters", "rtch_scene_denoise", "rtch_scene_film"]
 
 MULTI_SYMBOLS = ["rtc_multi_create", "rtc_multi_destroy", "rtc_multi_render", "rtc_multi_render_rgba8", "rtc_multi_render_device", "rtc_multi_render_rgba8_device",
                  "rtc_multi_synchronize", "rtc_multi_stream", "rtc_multi_get_stats", "rtc_multi_balance", "rtc_multi_last_error"]
@@ -586,6 +621,12 @@ def hip_lib():
         lib.rtc_render_denoised.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.POINTER(Adaptive),
                                             C.POINTER(DenoiseSetting), C.c_void_p, C.c_void_p]
         lib.rtc_diag_denoise_tile.argtypes = [_u32p, _u32p]
+        lib.rtc_film_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(FilmSetting)]
+        lib.rtc_film_scratch_bytes.restype = C.c_size_t
+        lib.rtc_film_device.argtypes = [C.POINTER(Film), C.c_void_p]
+        lib.rtc_render_filmed.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.POINTER(Adaptive),
+                                          C.POINTER(DenoiseSetting), C.POINTER(FilmSetting), C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rtc_diag_film_tile.argtypes = [_u32p, _u32p, _u32p]
         lib.rtc_scene_destroy.argtypes = [C.c_void_p]
         lib.rtc_scene_destroy.restype = None
         lib.rtc_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32] + [C.c_uint32] * 4 + [C.c_void_p]
@@ -650,6 +691,7 @@ def host_lib():
         lib.rtch_scene_emitters.argtypes = [C.c_void_p, C.POINTER(Emitters), C.POINTER(C.c_int)]
         lib.rtch_scene_adaptive.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(Adaptive)]
         lib.rtch_scene_denoise.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(DenoiseSetting)]
+        lib.rtch_scene_film.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(FilmSetting)]
         lib.rtch_scene_camera.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Camera)]
         lib.rtch_camera_rotate.argtypes = [C.c_void_p, C.c_double]
         lib.rtch_camera_move.argtypes = [C.c_void_p, C.c_double]
@@ -946,6 +988,13 @@ class HostScene:
         _check_host(host_lib().rtch_scene_denoise(self._h, C.byref(on), C.byref(d)))
         return d if on.value else None
 
+    def film(self):
+        """The camera's "film" of the scene file (rtch_scene_film): a FilmSetting, or None when the file has no such key (or
+        has it false)."""
+        on, f = C.c_int(), FilmSetting()
+        _check_host(host_lib().rtch_scene_film(self._h, C.byref(on), C.byref(f)))
+        return f if on.value else None
+
     def rotate_camera(self, angle):
         """Renderer.rotateCamera (lib.zig:166-178): orbit the camera around its target, about `up`."""
         _check_host(host_lib().rtch_camera_rotate(self._h, C.c_double(angle)))
@@ -1170,6 +1219,19 @@ class GpuScene:
                                                  C.byref(setting) if setting is not None else None, rgb.ctypes.data, noisy.ctypes.data))
         return rgb, noisy
 
+    def render_filmed(self, cam, passes, adaptive=None, denoise=None, film=None, max_depth=REFERENCE_DEPTH):
+        """rtc_render_filmed: `passes` sample passes (or, with an Adaptive, a whole adaptive run) accumulated on the device,
+        filtered by the denoiser where `denoise` is a DenoiseSetting, and taken to display values by the film stage (film: a
+        FilmSetting; None: the defaults); returns (rgb [h][w][3] f64, rgba [h][w][4] u8, linear [h][w][3] f64: the image the
+        film read), host arrays.  The handle's own sample pass is left as it was."""
+        rgb = np.empty((cam.vsize, cam.hsize, 3), dtype=np.float64)
+        rgba = np.empty((cam.vsize, cam.hsize, 4), dtype=np.uint8)
+        linear = np.empty((cam.vsize, cam.hsize, 3), dtype=np.float64)
+        _check_hip(hip_lib().rtc_render_filmed(self._s, C.byref(cam), max_depth, passes, C.byref(adaptive) if adaptive is not None else None,
+                                               C.byref(denoise) if denoise is not None else None, C.byref(film) if film is not None else None,
+                                               rgb.ctypes.data, rgba.ctypes.data, linear.ctypes.data))
+        return rgb, rgba, linear
+
     def clone(self):
         """rtc_scene_clone: a handle of its own (stream, schedule, counters) on the same device copy of the scene - one
         per frame in flight."""
@@ -1318,6 +1380,12 @@ class Progressive:
             raise ValueError("Progressive(noise=False) keeps no sums of squares: nothing to guide the denoiser")
         return _denoised(self, self.passes, None, setting)
 
+    def filmed(self, denoise=None, **film):
+        """(out [h][w][3] f64, rgba [h][w][4] u8) on the device: the film stage (rtc_film_device) over the mean - or, where
+        `denoise` is a dict of DenoiseSetting.make's keywords, over denoised(**denoise) - on this object's stream after its
+        last step; `film`: FilmSetting.make's keywords."""
+        return _filmed(self, self.denoised(**denoise) if denoise is not None else self._mean, film)
+
 
 class AdaptiveProgressive:
     """Adaptive sampling on the device: each step() is one round of rtc_scene_adaptive_step - the tiles still noisy take
@@ -1387,6 +1455,12 @@ class AdaptiveProgressive:
         tile's passes, on this object's stream after its last round; `setting`: DenoiseSetting.make's keywords."""
         return _denoised(self, 0, self._tile_passes, setting)
 
+    def filmed(self, denoise=None, **film):
+        """(out [h][w][3] f64, rgba [h][w][4] u8) on the device: the film stage (rtc_film_device) over the mean - or, where
+        `denoise` is a dict of DenoiseSetting.make's keywords, over denoised(**denoise) - on this object's stream after its
+        last round; `film`: FilmSetting.make's keywords."""
+        return _filmed(self, self.denoised(**denoise) if denoise is not None else self._mean, film)
+
 
 def denoise_device(mean_ptr, sumsq_ptr, hsize, vsize, out_ptr, stream, passes=0, tile_passes_ptr=None, tile=(0, 0), setting=None,
                    rgba_ptr=None):
@@ -1417,6 +1491,49 @@ def _denoised(prog, passes, tile_passes, setting):
                    setting=DenoiseSetting.make(**setting))
     torch.cuda.current_stream().wait_stream(prog.stream)
     return out
+
+
+def film_scratch_bytes(hsize, vsize, setting=None):
+    """rtc_film_scratch_bytes: the bytes of device memory rtc_film_device needs beside its images for a size and a
+    FilmSetting (None: the defaults); 0 where it needs none.  A setting the contract refuses raises RtcError."""
+    lib = hip_lib()
+    n = lib.rtc_film_scratch_bytes(hsize, vsize, C.byref(setting if setting is not None else FilmSetting.make()))
+    if n == 0 and lib.rtc_last_error():
+        raise RtcError("InvalidArgument", lib.rtc_last_error().decode())
+    return n
+
+
+def film_device(in_ptr, hsize, vsize, out_ptr, stream, setting=None, scratch_ptr=None, rgba_ptr=None, scale_ptr=None):
+    """rtc_film_device: the film stage over a device image [vsize][hsize][3], enqueued on `stream` (a HIP stream, not None);
+    setting: a FilmSetting (None: the defaults); scratch_ptr: film_scratch_bytes() bytes on the device (None where that is
+    0); rgba_ptr: where the clamp of the result goes, or None; scale_ptr: where the exposure E goes (one f64), or None."""
+    f = Film(in_ptr, hsize, vsize, setting if setting is not None else FilmSetting.make(), scratch_ptr, out_ptr, rgba_ptr, scale_ptr)
+    _check_hip(hip_lib().rtc_film_device(C.byref(f), stream))
+
+
+def film_tile():
+    """rtc_diag_film_tile: (row_w, col_w, col_h) - the width of the tiled row kernel's tile, the width and the height of the
+    tiled resolve kernel's."""
+    a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    _check_hip(hip_lib().rtc_diag_film_tile(C.byref(a), C.byref(b), C.byref(c)))
+    return a.value, b.value, c.value
+
+
+def _filmed(prog, image, film):
+    """Progressive.filmed / AdaptiveProgressive.filmed: new tensors, filled on prog.stream; the caller's current stream is
+    ordered after it."""
+    import torch
+    setting = FilmSetting.make(**film)
+    h, w = prog.cam.vsize, prog.cam.hsize
+    out = torch.empty_like(image)
+    rgba = torch.empty((h, w), dtype=torch.int32, device=image.device)
+    n = film_scratch_bytes(w, h, setting)
+    scratch = torch.empty((n + 7) // 8, dtype=torch.float64, device=image.device) if n else None
+    prog.stream.wait_stream(torch.cuda.current_stream())   # (the tensors were allocated on the current stream)
+    film_device(image.data_ptr(), w, h, out.data_ptr(), prog.stream.cuda_stream, setting=setting,
+                scratch_ptr=scratch.data_ptr() if scratch is not None else None, rgba_ptr=rgba.data_ptr())
+    torch.cuda.current_stream().wait_stream(prog.stream)
+    return out, rgba.view(h, w, 1).view(torch.uint8)
 
 
 def canvas_register(array):

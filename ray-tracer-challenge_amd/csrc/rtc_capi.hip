@@ -273,6 +273,11 @@ hipError_t rtcAdaptiveAccumLaunch(const double* frame, const uint32_t* list, uin
 // The denoiser's kernels (rtc_denoise.hip): the enqueue of the tiled form or (naive) the literal one, and the tiled form's tile.
 hipError_t rtcDenoiseLaunch(const rtc_denoise* d, bool naive, hipStream_t stream);
 void rtcDenoiseTile(uint32_t* w, uint32_t* h);
+// The film stage's kernels (rtc_film.hip): the enqueue of the tiled forms or (naive) the literal ones, the scratch bytes of a
+// valid setting, and the tiled forms' tiles.
+hipError_t rtcFilmLaunch(const rtc_film* f, bool naive, hipStream_t stream);
+size_t rtcFilmScratchBytes(uint32_t hsize, uint32_t vsize, const rtc_film_setting* s);
+void rtcFilmTile(uint32_t* row_w, uint32_t* col_w, uint32_t* col_h);
 extern "C" __global__ void rtc_estimate_kernel(const DevScene S, const DevCamera cam, const DevPixelMap map,
                                                uint32_t* __restrict__ chunk_cost, uint32_t* __restrict__ chunk_time,
                                                DevChunkShape* __restrict__ chunk_shape, DevPackState* __restrict__ state
@@ -3838,6 +3843,41 @@ int rtc_diag_denoise_tile(uint32_t* w, uint32_t* h) {
   return RTC_OK;
 }
 
+// What rtc_render_denoised and rtc_render_filmed share.  The checks of a run: an adaptive setting, or `least` passes or more
+// whose samples fit the sample index.
+static int checkRun(const rtc_scene* s, const rtc_camera* cam, uint32_t passes, uint32_t least, const rtc_adaptive* adaptive,
+                    uint32_t* n_tiles, const char* who) {
+  if (adaptive) {
+    if (const int e = checkAdaptive(adaptive, cam->hsize, cam->vsize, n_tiles); e != RTC_OK) return e;
+    return checkAdaptivePasses(adaptive, s);
+  }
+  if (passes < least) return fail(RTC_ERR_INVALID_ARGUMENT, "%s: passes %u (%u or more)", who, passes, least);
+  if (!passFits(passes - 1u, s->sampling.samples))
+    return fail(RTC_ERR_INVALID_ARGUMENT, "%s: %u passes of %u samples exceed %u sample indices", who, passes, s->sampling.samples,
+                RTC_SAMPLING_INDEX_LIMIT);
+  return RTC_OK;
+}
+
+// The run itself on the handle's own stream, into st's sums and mean: an adaptive run, or pass p at sample pass p through
+// d_frame, the handle's own pass put back whatever happens.
+static int accumulatedRun(rtc_scene* s, const rtc_camera* cam, uint32_t max_depth, uint32_t passes, const rtc_adaptive* adaptive,
+                          double* d_frame, rtc_adaptive_state* st) {
+  if (adaptive) return adaptiveRun(s, cam, max_depth, adaptive, st);
+  const size_t n_px = static_cast<size_t>(cam->hsize) * cam->vsize;
+  const uint32_t own_pass = s->sample_pass;
+  int rc = RTC_OK;
+  for (uint32_t p = 0; p < passes && rc == RTC_OK; ++p) {
+    rc = rtc_scene_set_sample_pass(s, p);
+    if (rc == RTC_OK) rc = rtc_render_device(s, cam, max_depth, 0, 0, cam->hsize, cam->vsize, d_frame, s->stream);
+    const rtc_accum acc{d_frame, n_px, p + 1u, st->sum, st->sumsq, st->mean, nullptr, nullptr};
+    if (rc == RTC_OK) rc = rtc_scene_accumulate_device(s, &acc, s->stream);
+  }
+  const std::string error = g_error;
+  (void)rtc_scene_set_sample_pass(s, own_pass);
+  g_error = error;
+  return rc;
+}
+
 int rtc_render_denoised(rtc_scene* s, const rtc_camera* cam, uint32_t max_depth, uint32_t passes, const rtc_adaptive* adaptive,
                         const rtc_denoise_setting* setting, double* rgb_out, double* noisy_out) {
   g_error.clear();
@@ -3846,15 +3886,7 @@ int rtc_render_denoised(rtc_scene* s, const rtc_camera* cam, uint32_t max_depth,
   const rtc_denoise_setting v = setting ? *setting : rtc_denoise_setting{7u, 2u, 0.45, 1.0};
   if (const int e = checkDenoiseSetting(v); e != RTC_OK) return e;
   uint32_t n_tiles = 0;
-  if (adaptive) {
-    if (const int e = checkAdaptive(adaptive, cam->hsize, cam->vsize, &n_tiles); e != RTC_OK) return e;
-    if (const int e = checkAdaptivePasses(adaptive, s); e != RTC_OK) return e;
-  } else {
-    if (passes < 2u) return fail(RTC_ERR_INVALID_ARGUMENT, "denoise: passes %u (2 or more)", passes);
-    if (!passFits(passes - 1u, s->sampling.samples))
-      return fail(RTC_ERR_INVALID_ARGUMENT, "denoise: %u passes of %u samples exceed %u sample indices", passes, s->sampling.samples,
-                  RTC_SAMPLING_INDEX_LIMIT);
-  }
+  if (const int e = checkRun(s, cam, passes, 2u, adaptive, &n_tiles, "denoise"); e != RTC_OK) return e;
   HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(ensureOwnStream(s));
   // one allocation: the filtered image, the pass just rendered, then the sums as an adaptive run has them
@@ -3868,27 +3900,110 @@ int rtc_render_denoised(rtc_scene* s, const rtc_camera* cam, uint32_t max_depth,
   rtc_adaptive_state st{};
   carveAdaptive(base + 2u * b_img, n_px, n_tiles, &st);
   rtc_denoise d{st.mean, st.sumsq, cam->hsize, cam->vsize, passes, nullptr, 0u, 0u, v, d_out, nullptr};
-  if (adaptive) {
-    if (const int e = adaptiveRun(s, cam, max_depth, adaptive, &st); e != RTC_OK) return e;
-    d.tile_passes = st.tile_passes, d.tile_w = adaptive->tile_w, d.tile_h = adaptive->tile_h;
-  } else {
-    // pass p at sample pass p; the handle's own pass is put back whatever happens
-    const uint32_t own_pass = s->sample_pass;
-    int rc = RTC_OK;
-    for (uint32_t p = 0; p < passes && rc == RTC_OK; ++p) {
-      rc = rtc_scene_set_sample_pass(s, p);
-      if (rc == RTC_OK) rc = rtc_render_device(s, cam, max_depth, 0, 0, cam->hsize, cam->vsize, d_frame, s->stream);
-      const rtc_accum acc{d_frame, n_px, p + 1u, st.sum, st.sumsq, st.mean, nullptr, nullptr};
-      if (rc == RTC_OK) rc = rtc_scene_accumulate_device(s, &acc, s->stream);
-    }
-    const std::string error = g_error;
-    (void)rtc_scene_set_sample_pass(s, own_pass);
-    g_error = error;
-    if (rc != RTC_OK) return rc;
-  }
+  if (adaptive) d.tile_passes = st.tile_passes, d.tile_w = adaptive->tile_w, d.tile_h = adaptive->tile_h;
+  if (const int e = accumulatedRun(s, cam, max_depth, passes, adaptive, d_frame, &st); e != RTC_OK) return e;
   if (const int e = rtc_denoise_device(&d, s->stream); e != RTC_OK) return e;
   HIP_TRY(hipMemcpyAsync(rgb_out, d_out, n_px * 3u * sizeof(double), hipMemcpyDeviceToHost, s->stream));
   if (noisy_out) HIP_TRY(hipMemcpyAsync(noisy_out, st.mean, n_px * 3u * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return RTC_OK;
+}
+
+// ---- the film stage
+static const rtc_film_setting kFilmDefaults{1.0, 0.0, 0u, 4.0, 1.0, 0.0, RTC_FILM_CURVE_ACES, 4.0, RTC_FILM_TRANSFER_SRGB, 2.2};
+
+static int checkFilmSetting(const rtc_film_setting& v) {
+  auto bad = [](double x, bool zero) { return !std::isfinite(x) || x < 0.0 || (!zero && x == 0.0); };
+  if (bad(v.exposure, false)) return fail(RTC_ERR_INVALID_ARGUMENT, "film: exposure %g (finite, above 0)", v.exposure);
+  if (bad(v.auto_key, true)) return fail(RTC_ERR_INVALID_ARGUMENT, "film: auto_key %g (finite, 0 or more)", v.auto_key);
+  if (v.bloom_radius > RTC_FILM_MAX_RADIUS) return fail(RTC_ERR_INVALID_ARGUMENT, "film: bloom_radius %u (at most %u)", v.bloom_radius, RTC_FILM_MAX_RADIUS);
+  if (v.bloom_radius > 0u && bad(v.bloom_sigma, false)) return fail(RTC_ERR_INVALID_ARGUMENT, "film: bloom_sigma %g (finite, above 0)", v.bloom_sigma);
+  if (bad(v.bloom_threshold, true)) return fail(RTC_ERR_INVALID_ARGUMENT, "film: bloom_threshold %g (finite, 0 or more)", v.bloom_threshold);
+  if (bad(v.bloom_intensity, true)) return fail(RTC_ERR_INVALID_ARGUMENT, "film: bloom_intensity %g (finite, 0 or more)", v.bloom_intensity);
+  if (v.curve > RTC_FILM_CURVE_HABLE) return fail(RTC_ERR_INVALID_ARGUMENT, "film: curve %u unknown", v.curve);
+  if (bad(v.white, false)) return fail(RTC_ERR_INVALID_ARGUMENT, "film: white %g (finite, above 0)", v.white);
+  if (v.transfer > RTC_FILM_TRANSFER_GAMMA) return fail(RTC_ERR_INVALID_ARGUMENT, "film: transfer %u unknown", v.transfer);
+  if (bad(v.gamma, false)) return fail(RTC_ERR_INVALID_ARGUMENT, "film: gamma %g (finite, above 0)", v.gamma);
+  return RTC_OK;
+}
+
+static int checkFilmSize(uint32_t hsize, uint32_t vsize) {
+  const uint64_t n_px = static_cast<uint64_t>(hsize) * vsize;
+  if (n_px == 0u || n_px > (1ull << 40)) return fail(RTC_ERR_INVALID_ARGUMENT, "film: image %ux%u", hsize, vsize);
+  return RTC_OK;
+}
+
+size_t rtc_film_scratch_bytes(uint32_t hsize, uint32_t vsize, const rtc_film_setting* v) {
+  g_error.clear();
+  if (!v) return fail(RTC_ERR_INVALID_ARGUMENT, "film: null argument"), 0u;
+  if (checkFilmSize(hsize, vsize) != RTC_OK || checkFilmSetting(*v) != RTC_OK) return 0u;
+  return rtcFilmScratchBytes(hsize, vsize, v);
+}
+
+int rtc_film_device(const rtc_film* f, void* hip_stream) {
+  g_error.clear();
+  if (!f || !f->in || !f->out || !hip_stream) return fail(RTC_ERR_INVALID_ARGUMENT, "film: null argument");
+  if (const int e = checkFilmSize(f->hsize, f->vsize); e != RTC_OK) return e;
+  if (const int e = checkFilmSetting(f->setting); e != RTC_OK) return e;
+  if (!f->scratch && rtcFilmScratchBytes(f->hsize, f->vsize, &f->setting) != 0u)
+    return fail(RTC_ERR_INVALID_ARGUMENT, "film: null scratch where %zu bytes are needed", rtcFilmScratchBytes(f->hsize, f->vsize, &f->setting));
+  const uintptr_t i = reinterpret_cast<uintptr_t>(f->in), o = reinterpret_cast<uintptr_t>(f->out),
+                  bytes = static_cast<uintptr_t>(f->hsize) * f->vsize * 3u * sizeof(double);
+  if (i < o + bytes && o < i + bytes) return fail(RTC_ERR_INVALID_ARGUMENT, "film: out overlaps in");
+  HIP_TRY(rtcFilmLaunch(f, rtcOptions().film_naive != 0.0, static_cast<hipStream_t>(hip_stream)));
+  return RTC_OK;
+}
+
+int rtc_diag_film_tile(uint32_t* row_w, uint32_t* col_w, uint32_t* col_h) {
+  g_error.clear();
+  if (!row_w || !col_w || !col_h) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
+  rtcFilmTile(row_w, col_w, col_h);
+  return RTC_OK;
+}
+
+int rtc_render_filmed(rtc_scene* s, const rtc_camera* cam, uint32_t max_depth, uint32_t passes, const rtc_adaptive* adaptive,
+                      const rtc_denoise_setting* denoise, const rtc_film_setting* film, double* rgb_out, uint8_t* rgba_out,
+                      double* linear_out) {
+  g_error.clear();
+  if (!s || (!rgb_out && !rgba_out)) return fail(RTC_ERR_INVALID_ARGUMENT, "film: null argument");
+  if (const int e = checkCamera(cam); e != RTC_OK) return e;
+  if (denoise)
+    if (const int e = checkDenoiseSetting(*denoise); e != RTC_OK) return e;
+  const rtc_film_setting v = film ? *film : kFilmDefaults;
+  if (const int e = checkFilmSetting(v); e != RTC_OK) return e;
+  uint32_t n_tiles = 0;
+  if (const int e = checkRun(s, cam, passes, denoise ? 2u : 1u, adaptive, &n_tiles, "film"); e != RTC_OK) return e;
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(ensureOwnStream(s));
+  // one allocation: the film's out, the denoiser's, the pass just rendered, rgba, the film's scratch, then the sums as an
+  // adaptive run has them
+  auto up16 = [](size_t b) { return (b + 15u) & ~static_cast<size_t>(15u); };
+  const size_t n_px = static_cast<size_t>(cam->hsize) * cam->vsize;
+  const size_t b_img = up16(n_px * 3u * sizeof(double)), b_rgba = up16(n_px * sizeof(uint32_t));
+  const size_t b_scratch = up16(rtcFilmScratchBytes(cam->hsize, cam->vsize, &v));
+  char* base = nullptr;
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&base), 3u * b_img + b_rgba + b_scratch + carveAdaptive(nullptr, n_px, n_tiles, nullptr)));
+  FreeWhenIdle release{s, base};
+  double* const d_film = reinterpret_cast<double*>(base);
+  double* const d_denoised = reinterpret_cast<double*>(base + b_img);
+  double* const d_frame = reinterpret_cast<double*>(base + 2u * b_img);
+  uint32_t* const d_rgba = reinterpret_cast<uint32_t*>(base + 3u * b_img);
+  void* const d_scratch = b_scratch ? base + 3u * b_img + b_rgba : nullptr;
+  rtc_adaptive_state st{};
+  carveAdaptive(base + 3u * b_img + b_rgba + b_scratch, n_px, n_tiles, &st);
+  if (const int e = accumulatedRun(s, cam, max_depth, passes, adaptive, d_frame, &st); e != RTC_OK) return e;
+  const double* linear = st.mean;
+  if (denoise) {
+    rtc_denoise d{st.mean, st.sumsq, cam->hsize, cam->vsize, passes, nullptr, 0u, 0u, *denoise, d_denoised, nullptr};
+    if (adaptive) d.tile_passes = st.tile_passes, d.tile_w = adaptive->tile_w, d.tile_h = adaptive->tile_h;
+    if (const int e = rtc_denoise_device(&d, s->stream); e != RTC_OK) return e;
+    linear = d_denoised;
+  }
+  const rtc_film f{linear, cam->hsize, cam->vsize, v, d_scratch, d_film, rgba_out ? d_rgba : nullptr, nullptr};
+  if (const int e = rtc_film_device(&f, s->stream); e != RTC_OK) return e;
+  if (rgb_out) HIP_TRY(hipMemcpyAsync(rgb_out, d_film, n_px * 3u * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  if (rgba_out) HIP_TRY(hipMemcpyAsync(rgba_out, d_rgba, n_px * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+  if (linear_out) HIP_TRY(hipMemcpyAsync(linear_out, linear, n_px * 3u * sizeof(double), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   return RTC_OK;
 }
@@ -4398,7 +4513,7 @@ int rtc_set_option(const char* name, double value) {
                {"shadow_filter_kernels", &o.shadow_filter_kernels}, {"media_kernels", &o.media_kernels},
                {"environment_kernels", &o.environment_kernels}, {"sky_light_kernels", &o.sky_light_kernels},
                {"indirect_kernels", &o.indirect_kernels}, {"emitter_kernels", &o.emitter_kernels},
-               {"denoise_naive", &o.denoise_naive}};
+               {"denoise_naive", &o.denoise_naive}, {"film_naive", &o.film_naive}};
   for (const auto& e : table)
     if (std::strcmp(e.name, name) == 0) {
       e.slot->set(value);

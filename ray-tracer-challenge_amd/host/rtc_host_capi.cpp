@@ -93,6 +93,18 @@ int rtch_scene_denoise(void* h, int* enabled, rtc_denoise_setting* out) {
   });
 }
 
+static rtc_film_setting filmSetting(const rtc::CameraFilm& f) {
+  return rtc_film_setting{f.exposure, f.auto_key, f.bloom_radius, f.bloom_sigma, f.bloom_threshold, f.bloom_intensity, f.curve, f.white, f.transfer, f.gamma};
+}
+
+int rtch_scene_film(void* h, int* enabled, rtc_film_setting* out) {
+  return guarded([&] {
+    const rtc::CameraFilm& f = static_cast<HostScene*>(h)->info.film;
+    *enabled = f.enabled ? 1 : 0;
+    *out = filmSetting(f);
+  });
+}
+
 int rtch_scene_motion(void* h, double* out, uint32_t n) {
   return guarded([&] {
     const HostScene* hs = static_cast<HostScene*>(h);
@@ -348,7 +360,7 @@ int rtch_scene_render(void* h, uint32_t width, uint32_t height, uint32_t max_dep
     // number - the bits of rtc_scene_accumulate_device's mean)
     const uint32_t passes = hs->info.sampling.passes;
     const size_t n = 3ull * cam.hsize * cam.vsize;
-    std::vector<double> frame(passes > 1u && !hs->info.sampling.denoise ? n : 0u);
+    std::vector<double> frame(passes > 1u && !hs->info.sampling.denoise && !hs->info.film.enabled ? n : 0u);
     rtc_scene* scene = nullptr;
     // (a scene with area lights: its light table; point lights only: the description alone, as before)
     int st = hs->flat.has_area_light ? rtc_scene_create_with_lights(&hs->desc, &hs->lights, &scene) : rtc_scene_create(&hs->desc, &scene);
@@ -430,7 +442,12 @@ int rtch_scene_render(void* h, uint32_t width, uint32_t height, uint32_t max_dep
         st = rtc_scene_set_emitters(scene, &em);
       }
       const rtc::CameraSampling& cs = hs->info.sampling;
-      if (cs.denoise && st == RTC_OK) {  // (the denoiser over the accumulated passes, or over an adaptive run, section 29)
+      if (hs->info.film.enabled && st == RTC_OK) {  // (the whole path on the device, the film stage last, section 30)
+        const rtc_adaptive a{cs.tile_w, cs.tile_h, cs.min_passes, cs.passes, cs.threshold};
+        const rtc_denoise_setting dn{cs.denoise_radius, cs.denoise_patch, cs.denoise_strength, cs.denoise_cancel};
+        const rtc_film_setting film = filmSetting(hs->info.film);
+        st = rtc_render_filmed(scene, &cam, max_depth, passes, cs.adaptive ? &a : nullptr, cs.denoise ? &dn : nullptr, &film, rgb_out, nullptr, nullptr);
+      } else if (cs.denoise && st == RTC_OK) {  // (the denoiser over the accumulated passes, or over an adaptive run, section 29)
         const rtc_adaptive a{cs.tile_w, cs.tile_h, cs.min_passes, cs.passes, cs.threshold};
         const rtc_denoise_setting dn{cs.denoise_radius, cs.denoise_patch, cs.denoise_strength, cs.denoise_cancel};
         st = rtc_render_denoised(scene, &cam, max_depth, passes, cs.adaptive ? &a : nullptr, &dn, rgb_out, nullptr);
@@ -438,7 +455,7 @@ int rtch_scene_render(void* h, uint32_t width, uint32_t height, uint32_t max_dep
         const rtc_adaptive a{cs.tile_w, cs.tile_h, cs.min_passes, cs.passes, cs.threshold};
         st = rtc_render_adaptive(scene, &cam, max_depth, &a, rgb_out, nullptr);
       }
-      const bool on_host = !cs.adaptive && !cs.denoise;  // (the passes summed here)
+      const bool on_host = !cs.adaptive && !cs.denoise && !hs->info.film.enabled;  // (the passes summed here)
       for (uint32_t p = 0; p < passes && st == RTC_OK && on_host; ++p) {
         if (p > 0u) st = rtc_scene_set_sample_pass(scene, p);
         if (st == RTC_OK) st = rtc_render(scene, &cam, max_depth, 0, 0, cam.hsize, cam.vsize, p == 0u ? rgb_out : frame.data());

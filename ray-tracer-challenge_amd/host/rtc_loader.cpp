@@ -829,7 +829,7 @@ SceneInfo parseScene(const std::string& scene_json, const FileLoader& load_file_
   }
 
   const Value& cam = requireObject(requireField(root, "camera", "scene"), "camera");
-  checkFields(cam, {"width", "height", "field-of-view", "from", "to", "up", "sampling"}, "camera");
+  checkFields(cam, {"width", "height", "field-of-view", "from", "to", "up", "sampling", "film"}, "camera");
   SceneInfo info;
   info.camera = Camera::create(asUsize(requireField(cam, "width", "camera"), "width"),
                                asUsize(requireField(cam, "height", "camera"), "height"),
@@ -1075,6 +1075,79 @@ SceneInfo parseScene(const std::string& scene_json, const FileLoader& load_file_
       }
       if (s.denoise && !s.adaptive && s.passes < 2)
         throw Error("InvalidData", "sampling: denoise needs passes of 2 or more, or adaptive");
+    }
+  }
+  if (const Value* fv = cam.find("film")) {  // (the film stage, DESIGN.md section 30: true, false or the setting's keys)
+    CameraFilm& f = info.film;
+    auto realOf = [](const Value& v, const std::string& what, bool zero) {
+      if (v.type != Value::Number || !std::isfinite(v.num) || v.num < 0.0 || (!zero && v.num == 0.0))
+        throw Error("InvalidData", "film: " + what + (zero ? " is finite and at least 0" : " is finite and above 0"));
+      return v.num;
+    };
+    if (fv->type == Value::Object) {
+      checkFields(*fv, {"exposure", "auto-exposure", "bloom", "tone-curve", "white", "transfer"}, "film");
+      f.enabled = true;
+      if (const Value* v = fv->find("exposure")) {
+        if (v->type == Value::Object) {
+          checkFields(*v, {"stops"}, "film.exposure");
+          const Value* stops = v->find("stops");
+          if (!stops || stops->type != Value::Number || !std::isfinite(stops->num)) throw Error("InvalidData", "film: exposure is {\"stops\": s}, s finite");
+          f.exposure = std::exp2(stops->num);
+          if (!std::isfinite(f.exposure) || f.exposure <= 0.0) throw Error("InvalidData", "film: exposure stops out of range");
+        } else {
+          f.exposure = realOf(*v, "exposure", false);
+        }
+      }
+      if (const Value* v = fv->find("auto-exposure")) {
+        if (v->type == Value::Bool) f.auto_key = v->b ? 0.18 : 0.0;
+        else f.auto_key = realOf(*v, "auto-exposure", true);
+      }
+      if (const Value* v = fv->find("bloom")) {
+        if (v->type == Value::Object) {
+          checkFields(*v, {"radius", "sigma", "threshold", "intensity"}, "film.bloom");
+          f.bloom_radius = 12u, f.bloom_threshold = 1.0, f.bloom_intensity = 0.15;
+          if (const Value* r = v->find("radius")) {
+            if (r->type != Value::Number || !(r->num >= 0.0 && r->num <= RTC_FILM_MAX_RADIUS) || r->num != std::floor(r->num))
+              throw Error("InvalidData", "film.bloom: radius is a whole number from 0 to " + std::to_string(RTC_FILM_MAX_RADIUS));
+            f.bloom_radius = static_cast<uint32_t>(r->num);
+          }
+          if (f.bloom_radius > 0u) f.bloom_sigma = f.bloom_radius / 3.0;
+          if (const Value* r = v->find("sigma")) f.bloom_sigma = realOf(*r, "bloom sigma", false);
+          if (const Value* r = v->find("threshold")) f.bloom_threshold = realOf(*r, "bloom threshold", true);
+          if (const Value* r = v->find("intensity")) f.bloom_intensity = realOf(*r, "bloom intensity", true);
+        } else if (v->type == Value::Bool) {
+          if (v->b) f.bloom_radius = 12u, f.bloom_sigma = 4.0, f.bloom_threshold = 1.0, f.bloom_intensity = 0.15;
+        } else {
+          throw Error("InvalidData", "film: bloom is true, false or {\"radius\", \"sigma\", \"threshold\", \"intensity\"}");
+        }
+      }
+      if (const Value* v = fv->find("tone-curve")) {
+        static const char* const names[] = {"linear", "reinhard", "aces", "hable"};
+        uint32_t c = 0;
+        while (c < 4u && !(v->type == Value::String && v->str == names[c])) ++c;
+        if (c == 4u) throw Error("InvalidData", "film: tone-curve is \"linear\", \"reinhard\", \"aces\" or \"hable\"");
+        f.curve = c;
+      }
+      if (const Value* v = fv->find("white")) f.white = realOf(*v, "white", false);
+      if (const Value* v = fv->find("transfer")) {
+        if (v->type == Value::String && v->str == "linear") {
+          f.transfer = RTC_FILM_TRANSFER_LINEAR;
+        } else if (v->type == Value::String && v->str == "srgb") {
+          f.transfer = RTC_FILM_TRANSFER_SRGB;
+        } else if (v->type == Value::Object) {
+          checkFields(*v, {"gamma"}, "film.transfer");
+          const Value* g = v->find("gamma");
+          if (!g) throw Error("InvalidData", "film: transfer is \"linear\", \"srgb\" or {\"gamma\": g}");
+          f.transfer = RTC_FILM_TRANSFER_GAMMA;
+          f.gamma = realOf(*g, "gamma", false);
+        } else {
+          throw Error("InvalidData", "film: transfer is \"linear\", \"srgb\" or {\"gamma\": g}");
+        }
+      }
+    } else if (fv->type == Value::Bool) {
+      f.enabled = fv->b;
+    } else {
+      throw Error("InvalidData", "camera: film is true, false or {\"exposure\", \"auto-exposure\", \"bloom\", \"tone-curve\", \"white\", \"transfer\"}");
     }
   }
 

@@ -40,6 +40,19 @@ struct CameraSampling {
   uint64_t occlusion_seed = 0;     // "occlusion-seed": rtc_occlusion::seed
 };
 
+// The camera's optional "film" (not in the reference): rtc_film_setting's values, as rtc_render_filmed
+// takes them.  Absent or false: no film stage, rtch_scene_render gives the linear image.
+struct CameraFilm {
+  bool enabled = false;
+  double exposure = 1.0, auto_key = 0.0;
+  uint32_t bloom_radius = 0;
+  double bloom_sigma = 4.0, bloom_threshold = 1.0, bloom_intensity = 0.0;
+  uint32_t curve = 2;  // RTC_FILM_CURVE_ACES
+  double white = 4.0;
+  uint32_t transfer = 1;  // RTC_FILM_TRANSFER_SRGB
+  double gamma = 2.2;
+};
+
 // A "spot-light" entry's cone (not in the reference), as rtc_scene_set_spots takes it: the axis as
 // given ("to" - position, or "direction"), and the cosines of the half-angles (std::cos).  cone 0: a light without one.
 struct SpotCone {
@@ -52,6 +65,7 @@ struct SceneInfo {  // scene.zig:608-610
   Camera camera;
   World world;
   CameraSampling sampling;
+  CameraFilm film;
   std::vector<double> motion;  // [objects][3]: each top-level object's optional "motion" (DESIGN.md section 14), else 0
   std::vector<SpotCone> spots;  // [lights]: a "spot-light" entry's cone (section 16); cone 0 for every other light
   // the scene's "atmosphere": {"density": d, "color": [r, g, b]} (section 23): rtc_media's fog; all zero without the key

@@ -78,6 +78,12 @@ without a list.  With --passes the noise run has the same table.
 a value) over the mean of 8 progressive passes of the timed handle: prints the time of one call in the tiled form and in the
 literal one (option denoise_naive), each taken twice, alternating, with device events around 20 launches after a warm-up, and
 the largest difference between the two results (0 is expected).  The frame time on the same line is one pass.
+--film [R[:curve[:transfer[:key]]],...]: the film stage (rtc_film_device) with a bloom of radius R (sigma R / 3,
+threshold 1, intensity 0.15; 0: no bloom, the point kernel), a tone curve (aces), a transfer (srgb) and an automatic exposure's key
+(0: manual) over the mean of 8 progressive passes of the timed handle; several settings are separated by commas (12 without a value).
+Prints the time of one call in the tiled form and in the literal one (option film_naive; the point kernel has one form, timed
+four times), each taken twice, alternating, with device events around 20 launches after a warm-up, and whether the two results
+have the same bits.  The frame time on the same line is one pass.
 --data-dir DIR: where a scene named by its path finds the images and OBJ files it names (default: the scene's directory).
 --adaptive threshold[,min,tile]: adaptive sampling at up to --max-passes (64) passes, min passes 4 and
 16 x 16 tiles by default, with the --sampling of the frames: prints the rounds and tile-passes of a run against
@@ -128,6 +134,7 @@ ap.add_argument("--sky-light", default="")
 ap.add_argument("--indirect", default="")
 ap.add_argument("--emitters", default="")
 ap.add_argument("--denoise", nargs="?", const="7:2:0.45", default="")
+ap.add_argument("--film", nargs="?", const="12", default="")
 ap.add_argument("--data-dir", default="")  # where a scene named by path finds its images and OBJ files (default: beside it)
 ap.add_argument("--torus", action="store_true")
 ap.add_argument("--meshuv", action="store_true")
@@ -273,6 +280,48 @@ def time_denoise(gpu, cam, depth):
     return (f" | denoise {setting['radius']}:{setting['patch']}:{setting['strength']} on 8 passes, {launches} launches: tiled "
             + " ".join(f"{t:.4f}" for t in ms["tiled"]) + " ms, naive " + " ".join(f"{t:.4f}" for t in ms["naive"])
             + f" ms ({min(ms['naive']) / min(ms['tiled']):.1f}x), max |tiled - naive| {delta:.1e}")
+
+
+def time_film(gpu, cam, depth):
+    """--film: both kernel forms on an 8-pass mean of the handle, each twice, alternating; ms per call"""
+    prog = rtc.Progressive(gpu, cam, depth)
+    for _ in range(8):
+        prog.step()
+    launches, text = max(20, args.frames), ""
+    for spec in args.film.split(","):
+        f = spec.split(":")
+        radius = int(f[0])
+        setting = rtc.FilmSetting.make(bloom_radius=radius, bloom_sigma=radius / 3.0 if radius else 4.0, bloom_intensity=0.15 if radius else 0.0,
+                                       curve=f[1] if len(f) > 1 else "aces", transfer=f[2] if len(f) > 2 else "srgb",
+                                       auto_key=float(f[3]) if len(f) > 3 else 0.0)
+        n = rtc.film_scratch_bytes(cam.hsize, cam.vsize, setting)
+        scratch = torch.empty(max(1, (n + 7) // 8), dtype=torch.float64, device="cuda")
+        rgba = torch.empty((cam.vsize, cam.hsize), dtype=torch.int32, device="cuda")
+        results, ms = {}, {"tiled": [], "naive": []}
+        torch.cuda.synchronize()
+        for rep in range(2):
+            for form in ("tiled", "naive"):
+                rtc.set_option("film_naive", 1 if form == "naive" else 0)
+                results[form] = torch.empty_like(prog._mean)
+                run = lambda: rtc.film_device(prog._mean.data_ptr(), cam.hsize, cam.vsize, results[form].data_ptr(), prog.stream.cuda_stream,
+                                              setting=setting, scratch_ptr=scratch.data_ptr() if n else None, rgba_ptr=rgba.data_ptr())
+                torch.cuda.synchronize()
+                run()   # (warm-up: the code object is loaded)
+                torch.cuda.synchronize()
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record(prog.stream)
+                for _ in range(launches):
+                    run()
+                b.record(prog.stream)
+                torch.cuda.synchronize()
+                ms[form].append(a.elapsed_time(b) / launches)
+        rtc.set_option("film_naive", 0)
+        same = bool((results["tiled"].view(torch.int64) == results["naive"].view(torch.int64)).all())
+        text += (f" | film {spec} on 8 passes, {launches} launches: " + ("tiled " if radius else "point ") + " ".join(f"{t:.4f}" for t in ms["tiled"])
+                 + (" ms, naive " if radius else " ms, again ") + " ".join(f"{t:.4f}" for t in ms["naive"])
+                 + f" ms ({min(ms['naive']) / min(ms['tiled']):.1f}x), same bits {same}")
+    gpu.set_sample_pass(0)
+    return text
 
 
 def emitters_table(hs):
@@ -516,6 +565,8 @@ for name, w, h, depth in cases:
             acc.append(time_accumulate(gpu, canvas, w * h, args.passes + 1))
         if args.denoise and rep == 0:
             denoise_line = time_denoise(gpu, cam, depth)
+        if args.film and rep == 0:
+            film_line = time_film(gpu, cam, depth)
         if args.check and rep == 0 and not args.sampling and args.passes < 0:
             import numpy as np, oracle_binding as ob
             step = max(1, h // 24)
@@ -556,6 +607,8 @@ for name, w, h, depth in cases:
         gpu.close()
     if args.denoise:
         line += denoise_line
+    if args.film:
+        line += film_line
     if args.adaptive:
         line += time_adaptive(hs, table, cam, depth)
     out.append(line)
