@@ -26,6 +26,7 @@
 #   tests/build/libemitters_oracle.so            test infrastructure only: the emitter-sampling checker (tests/cpp/emitters_oracle.cpp)
 #   tests/build/libdenoise_oracle.so             test infrastructure only: the denoiser's checker (tests/cpp/denoise_oracle.cpp)
 #   tests/build/libfilm_oracle.so                test infrastructure only: the film stage's checker (tests/cpp/film_oracle.cpp)
+#   tests/build/librobust_oracle.so              test infrastructure only: robust accumulation's checker (tests/cpp/robust_oracle.cpp)
 #   tests/build/meshuv_kat                       product unit tests: the OBJ parser's texture coordinates and ignored lines (tests/cpp/meshuv_kat_main.cpp)
 #
 # -ffp-contract=off everywhere: the reference's float mode is strict IEEE
@@ -58,7 +59,7 @@ checker: tests/build/libarea_oracle.so tests/build/libcamera_oracle.so tests/bui
          tests/build/libgloss_oracle.so tests/build/liboccl_oracle.so tests/build/libsfilter_oracle.so \
          tests/build/libmedia_oracle.so tests/build/libenvironment_oracle.so tests/build/libskylight_oracle.so \
          tests/build/libindirect_oracle.so tests/build/libemitters_oracle.so tests/build/libdenoise_oracle.so \
-         tests/build/libfilm_oracle.so
+         tests/build/libfilm_oracle.so tests/build/librobust_oracle.so
 tests/build/libarea_oracle.so: tests/cpp/area_oracle.cpp oracle/oracle_capi.cpp oracle/rtc_oracle.hpp oracle/rtc_oracle_scene.hpp include/rtc.h
 	mkdir -p tests/build
 	$(CXX) -std=c++17 -O3 -ffp-contract=off -fPIC -Wall -Wextra -pthread -shared -o $@ tests/cpp/area_oracle.cpp
@@ -134,6 +135,10 @@ tests/build/libdenoise_oracle.so: tests/cpp/denoise_oracle.cpp
 tests/build/libfilm_oracle.so: tests/cpp/film_oracle.cpp
 	mkdir -p tests/build
 	$(CXX) -std=c++17 -O2 -ffp-contract=off -fPIC -Wall -Wextra -pthread -shared -o $@ tests/cpp/film_oracle.cpp
+# (robust accumulation's checker, likewise)
+tests/build/librobust_oracle.so: tests/cpp/robust_oracle.cpp
+	mkdir -p tests/build
+	$(CXX) -std=c++17 -O2 -ffp-contract=off -fPIC -Wall -Wextra -pthread -shared -o $@ tests/cpp/robust_oracle.cpp
 # (the OBJ parser's `vt` lines at parser level, against the product's host library as rtc_host_kat is)
 tests/build/meshuv_kat: tests/cpp/meshuv_kat_main.cpp $(LIB)/librtc_host.so $(HOST_HDR)
 	mkdir -p tests/build
@@ -212,8 +217,8 @@ $(LIB)/rtc_kernels_ext.o: $(PKG)/csrc/rtc_kernels_ext.hip $(PKG)/csrc/rtc_kernel
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o $@ $< 2> $(LIB)/rtc_kernels_ext.remarks || (grep -v "remark:" $(LIB)/rtc_kernels_ext.remarks >&2; exit 1)
 	@grep -v "remark:\|remarks generated\|\^\|^ *[0-9]* |" $(LIB)/rtc_kernels_ext.remarks >&2 || true
 
-$(LIB)/kernel_resources.json: $(LIB)/rtc_kernels.o $(LIB)/rtc_kernels_ext.o $(LIB)/rtc_motion.o $(LIB)/rtc_spot.o $(LIB)/rtc_bump.o $(LIB)/rtc_torus.o $(LIB)/rtc_meshuv.o $(LIB)/rtc_gloss.o $(LIB)/rtc_occlusion.o $(LIB)/rtc_shadowfilter.o $(LIB)/rtc_media.o $(LIB)/rtc_environment.o $(LIB)/rtc_skylight.o $(LIB)/rtc_indirect.o $(LIB)/rtc_emitters.o $(LIB)/rtc_denoise.o $(LIB)/rtc_film.o tools/kernel_resources.py
-	cat $(LIB)/rtc_kernels.remarks $(LIB)/rtc_kernels_ext.remarks $(LIB)/rtc_motion.remarks $(LIB)/rtc_spot.remarks $(LIB)/rtc_bump.remarks $(LIB)/rtc_torus.remarks $(LIB)/rtc_meshuv.remarks $(LIB)/rtc_gloss.remarks $(LIB)/rtc_occlusion.remarks $(LIB)/rtc_shadowfilter.remarks $(LIB)/rtc_media.remarks $(LIB)/rtc_environment.remarks $(LIB)/rtc_skylight.remarks $(LIB)/rtc_indirect.remarks $(LIB)/rtc_emitters.remarks $(LIB)/rtc_denoise.remarks $(LIB)/rtc_film.remarks > $(LIB)/render_kernels.remarks
+$(LIB)/kernel_resources.json: $(LIB)/rtc_kernels.o $(LIB)/rtc_kernels_ext.o $(LIB)/rtc_motion.o $(LIB)/rtc_spot.o $(LIB)/rtc_bump.o $(LIB)/rtc_torus.o $(LIB)/rtc_meshuv.o $(LIB)/rtc_gloss.o $(LIB)/rtc_occlusion.o $(LIB)/rtc_shadowfilter.o $(LIB)/rtc_media.o $(LIB)/rtc_environment.o $(LIB)/rtc_skylight.o $(LIB)/rtc_indirect.o $(LIB)/rtc_emitters.o $(LIB)/rtc_denoise.o $(LIB)/rtc_film.o $(LIB)/rtc_robust.o tools/kernel_resources.py
+	cat $(LIB)/rtc_kernels.remarks $(LIB)/rtc_kernels_ext.remarks $(LIB)/rtc_motion.remarks $(LIB)/rtc_spot.remarks $(LIB)/rtc_bump.remarks $(LIB)/rtc_torus.remarks $(LIB)/rtc_meshuv.remarks $(LIB)/rtc_gloss.remarks $(LIB)/rtc_occlusion.remarks $(LIB)/rtc_shadowfilter.remarks $(LIB)/rtc_media.remarks $(LIB)/rtc_environment.remarks $(LIB)/rtc_skylight.remarks $(LIB)/rtc_indirect.remarks $(LIB)/rtc_emitters.remarks $(LIB)/rtc_denoise.remarks $(LIB)/rtc_film.remarks $(LIB)/rtc_robust.remarks > $(LIB)/render_kernels.remarks
 	python3 tools/kernel_resources.py --from-remarks $(LIB)/render_kernels.remarks --json $@
 
 $(LIB)/rtc_capi.o: $(PKG)/csrc/rtc_capi.hip $(wildcard $(PKG)/csrc/*.h) include/rtc.h | $(LIB)
@@ -237,7 +242,12 @@ $(LIB)/rtc_film.o: $(PKG)/csrc/rtc_film.hip include/rtc.h | $(LIB)
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o $@ $< 2> $(LIB)/rtc_film.remarks || (grep -v "remark:" $(LIB)/rtc_film.remarks >&2; exit 1)
 	@grep -v "remark:\|remarks generated\|\^\|^ *[0-9]* |" $(LIB)/rtc_film.remarks >&2 || true
 
-$(LIB)/librtc_hip.so: $(LIB)/rtc_kernels.o $(LIB)/rtc_kernels_ext.o $(LIB)/rtc_motion.o $(LIB)/rtc_spot.o $(LIB)/rtc_bump.o $(LIB)/rtc_torus.o $(LIB)/rtc_meshuv.o $(LIB)/rtc_gloss.o $(LIB)/rtc_occlusion.o $(LIB)/rtc_shadowfilter.o $(LIB)/rtc_media.o $(LIB)/rtc_environment.o $(LIB)/rtc_skylight.o $(LIB)/rtc_indirect.o $(LIB)/rtc_emitters.o $(LIB)/rtc_capi.o $(LIB)/rtc_accum.o $(LIB)/rtc_adaptive.o $(LIB)/rtc_denoise.o $(LIB)/rtc_film.o | $(LIB)/kernel_resources.json
+# (robust accumulation's resolve kernels: a translation unit of its own, likewise)
+$(LIB)/rtc_robust.o: $(PKG)/csrc/rtc_robust.hip include/rtc.h | $(LIB)
+	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o $@ $< 2> $(LIB)/rtc_robust.remarks || (grep -v "remark:" $(LIB)/rtc_robust.remarks >&2; exit 1)
+	@grep -v "remark:\|remarks generated\|\^\|^ *[0-9]* |" $(LIB)/rtc_robust.remarks >&2 || true
+
+$(LIB)/librtc_hip.so: $(LIB)/rtc_kernels.o $(LIB)/rtc_kernels_ext.o $(LIB)/rtc_motion.o $(LIB)/rtc_spot.o $(LIB)/rtc_bump.o $(LIB)/rtc_torus.o $(LIB)/rtc_meshuv.o $(LIB)/rtc_gloss.o $(LIB)/rtc_occlusion.o $(LIB)/rtc_shadowfilter.o $(LIB)/rtc_media.o $(LIB)/rtc_environment.o $(LIB)/rtc_skylight.o $(LIB)/rtc_indirect.o $(LIB)/rtc_emitters.o $(LIB)/rtc_capi.o $(LIB)/rtc_accum.o $(LIB)/rtc_adaptive.o $(LIB)/rtc_denoise.o $(LIB)/rtc_film.o $(LIB)/rtc_robust.o | $(LIB)/kernel_resources.json
 	$(HIPCC) --offload-arch=gfx950 -shared -fPIC -o $@ $^
 
 $(LIB)/librtc_multi.so: $(PKG)/csrc/rtc_multi.hip include/rtc_multi.h include/rtc.h $(LIB)/librtc_hip.so

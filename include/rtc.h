@@ -1200,6 +1200,87 @@ int rtc_film_device(const rtc_film *f, void *hip_stream);
 int rtc_render_filmed(rtc_scene *scene, const rtc_camera *cam, uint32_t max_depth, uint32_t passes, const rtc_adaptive *adaptive,
                       const rtc_denoise_setting *denoise, const rtc_film_setting *film, double *rgb_out, uint8_t *rgba_out,
                       double *linear_out);
+
+/* ---- robust accumulation: the Gini-weighted median of means over bucket sums ---- */
+#define RTC_ROBUST_MAX_BUCKETS 15u
+/*
+ * An estimator for the accumulation that tells a firefly - one pass that returns 40 where the others return 0.5 - from signal:
+ * the Gini-weighted median of means (GMoN) of Buisine, Delepoulle and Renaud (2021, "Firefly removal in Monte Carlo rendering
+ * with adaptive Median of meaNs"), taken on luminance so that a pixel keeps its hue.  The passes of a run go round-robin into
+ * M bucket sums; the resolve ranks the M bucket means of a pixel and keeps the central ones, more of them where the pixel is
+ * calm and fewer where it is not.  No render kernel is involved and the resolve needs no scene.  Every operation is an IEEE
+ * double operation in the order written (no fused multiply-add), and no library function is involved: every kernel form and
+ * a host restatement give the same bits.
+ *
+ * Bucket sums.  `sums` is [M][n][3] doubles on the device, M = setting.buckets.  Pass p (0-based) of a run goes to bucket
+ * p % M.  This needs no kernel of its own: it is rtc_scene_accumulate_device with sum = sums + (p % M) * n * 3,
+ * passes = p / M + 1 (so a bucket's first pass overwrites it) and sumsq, mean, rgba and noise all NULL.  After P >= M passes
+ * bucket j holds n_j = P / M + (j < P % M ? 1 : 0) frames.
+ *
+ * Resolve, per pixel, with h = (M - 1) / 2 and P = `passes`:
+ * 1. Bucket means and keys: m_j.c = sums[j].c / (double)n_j;  y_j = (0.2126 * m_j.r + 0.7152 * m_j.g) + 0.0722 * m_j.b;
+ *    k_j = (y_j - y_j == 0) ? (y_j > 0 ? y_j : 0.0) : +infinity.  A NaN or infinite bucket therefore sorts last.
+ * 2. Rank: rank_j = the number of i != j with k_i < k_j || (k_i == k_j && i < j) - a permutation of 0 .. M - 1; ties go
+ *    by bucket index.
+ * 3. The Gini coefficient of the keys; every sum runs over j ascending from 0.0:
+ *        T = sum k_j;   A = sum (double)(rank_j + 1) * k_j
+ *        G0 = (T > 0 && T < infinity) ? (2.0 * A) / ((double)M * T) - (double)(M + 1) / (double)M : (T > 0 ? 1.0 : 0.0)
+ *        g = gain * G0;   G = g > 0 ? (g < 1 ? g : 1.0) : 0.0
+ * 4. The kept half-width: c = min(h, (uint32_t)floor((1.0 - G) * (double)h + 0.5)) and k = 2 c + 1; bucket j is kept where
+ *    h - c <= rank_j <= h + c.
+ * 5. mean_out.c = (the sum over kept j ascending, from 0.0, of m_j.c) / (double)k;  rejected_out = M - k.
+ * 6. The variance of that mean, for the denoiser: cv = c > 1 ? c : 1 and kv = 2 cv + 1; D = the sum over j ascending with
+ *    h - cv <= rank_j <= h + cv, from 0.0, of ((d.r * d.r + d.g * d.g) + d.b * d.b) where d.c = m_j.c - mean_out.c;
+ *        v = D / (3.0 * ((double)(kv - 1) * (double)kv))
+ *        sumsq_out = P * ((u.r * u.r + u.g * u.g) + u.b * u.b) + (3.0 * ((P - 1.0) * P)) * v,   u = mean_out, P = (double)passes
+ *    - the sum of squares a P-pass accumulation with this mean and this variance of the mean would hold: rtc_denoise_device
+ *    called with mean_out, sumsq_out and passes = P recovers v up to rounding.
+ * 7. rgba, where wanted, is the clamp of mean_out: the bits of rtc_rgba8_device(mean_out).
+ *
+ * What follows: non-finite passes in fewer than half of the buckets do not reach mean_out (with gain >= 1: T is infinite,
+ * G0 is 1 and the median alone is kept).  With gain 0 every bucket is kept
+ * and, with P a multiple of M, the result is the plain mean up to rounding; with P not a multiple of M the bucket means have
+ * unequal weights and gain 0 is NOT the plain mean.  A large gain is the plain median of the bucket means.
+ */
+typedef struct rtc_robust_setting {
+  uint32_t buckets; /* M: odd, 3 .. RTC_ROBUST_MAX_BUCKETS                                  */
+  double gain;      /* finite, >= 0: 0 keeps every bucket, a large gain is the plain median */
+} rtc_robust_setting;
+/* (the defaults the scene loader and the Python binding use: buckets 5, gain 1.0) */
+typedef struct rtc_robust {
+  const double *sums;     /* [M][n][3], required: the bucket sums                                          */
+  size_t n_pixels;        /* n: 1 .. 2^40                                                                   */
+  uint32_t passes;        /* P >= M: the passes of the run, dealt to the buckets as above                   */
+  rtc_robust_setting setting;
+  double *mean_out;       /* [n][3], required, not inside sums                                              */
+  double *sumsq_out;      /* [n] or NULL, not inside sums: what rtc_denoise_device takes as sumsq           */
+  uint32_t *rejected_out; /* [n] or NULL: M - k, the buckets left out of a pixel                            */
+  uint32_t *rgba;         /* [n] or NULL: the clamp of mean_out, rtc_rgba8_device's bits                    */
+} rtc_robust;
+/*
+ * Enqueues the resolve on `hip_stream` (not NULL; every pointer a device pointer of that stream's device).  Asynchronous;
+ * the caller orders it after whatever wrote sums; it makes no allocation.  Every output is written once and not read back.
+ * RTC_ERR_INVALID_ARGUMENT before any HIP call, with nothing launched, for: a NULL among r, sums, mean_out and the stream;
+ * n_pixels of 0 or above 2^40; buckets even or outside 3 .. RTC_ROBUST_MAX_BUCKETS; passes < buckets; gain not finite or
+ * < 0; mean_out or sumsq_out lying inside sums.
+ */
+int rtc_robust_device(const rtc_robust *r, void *hip_stream);
+/*
+ * A robust render with buffers of its own: the whole path on the handle's own stream with one allocation, synchronous.
+ * Sample passes 0 .. passes - 1 (passes >= the buckets; there is no adaptive run: tiles at different pass counts would need
+ * buckets per tile) each go through rtc_scene_set_sample_pass, rtc_render_device, the ordinary
+ * rtc_scene_accumulate_device (sum, sumsq and mean, as rtc_render_denoised's) and a second rtc_scene_accumulate_device into
+ * the pass's bucket; the handle's own sample pass is put back afterwards whatever happens.  Then rtc_robust_device (`robust`
+ * NULL: the defaults above); then, where `denoise` is not NULL, rtc_denoise_device over mean_out, sumsq_out and passes; then,
+ * where `film` is not NULL, rtc_film_device over that - here NULL means NO film stage, unlike rtc_render_filmed, where it
+ * means the defaults.  rgb_out [vsize][hsize][3] (host) gets the last stage's image, rgba_out ([vsize][hsize][4] bytes, host)
+ * its clamp, robust_out (host) the robust mean, plain_out (host) the ordinary mean, rejected_out ([vsize][hsize] uint32_t,
+ * host) the map of rejected buckets; each may be NULL, but not both rgb_out and rgba_out.  Every argument is checked before
+ * the device is touched.  librtc_multi renders without it.
+ */
+int rtc_render_robust(rtc_scene *scene, const rtc_camera *cam, uint32_t max_depth, uint32_t passes,
+                      const rtc_robust_setting *robust, const rtc_denoise_setting *denoise, const rtc_film_setting *film,
+                      double *rgb_out, uint8_t *rgba_out, double *robust_out, double *plain_out, uint32_t *rejected_out);
 void rtc_scene_destroy(rtc_scene *scene);
 
 /*

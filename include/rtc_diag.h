@@ -56,7 +56,10 @@ extern "C" {
  * loops with one thread per pixel, in place of the tiled kernels, so that the two can be held to each other and timed
  * against each other; the bits are the same), "film_naive" (!= 0: a rtc_film_device that blooms runs rtc_film_naive_row_kernel
  * and rtc_film_naive_resolve_kernel, the literal forms of rtc.h's loops with one thread per pixel and no LDS, in place of the
- * tiled kernels, for the same two purposes; the bits are the same).
+ * tiled kernels, for the same two purposes; the bits are the same), "robust_naive" (!= 0: rtc_robust_device runs
+ * rtc_robust_naive_kernel, the literal form of rtc.h's loops with one thread per pixel, the bucket count a run-time value and
+ * every bucket mean formed again wherever it is used, in place of the register forms, for the same two purposes; the bits
+ * are the same).
  * RTC_ERR_INVALID_ARGUMENT for a name the library does not know.
  * (The library reads no environment variables.)
  */
@@ -132,6 +135,10 @@ int rtc_diag_denoise_tile(uint32_t *w, uint32_t *h);
  * kernel's width, the resolve kernel's width and height - so that tests can name image sizes relative to them.  No device
  * needed. */
 int rtc_diag_film_tile(uint32_t *row_w, uint32_t *col_w, uint32_t *col_h);
+
+/* Diagnostic (tests/test_robust_gpu.py): the cap of rtc_robust_device's grid in blocks and the threads of a block (DESIGN.md
+ * section 31), so that tests can name a pixel count above what one sweep of the grid covers.  No device needed. */
+int rtc_diag_robust_grid(uint32_t *max_blocks, uint32_t *block);
 
 #ifdef __cplusplus
 }

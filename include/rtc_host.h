@@ -30,7 +30,8 @@
  *                        rtch_scene_sky_light, through rtc_scene_set_sky_light; its indirect light,
  *                        rtch_scene_indirect, through rtc_scene_set_indirect; its emitter sampling,
  *                        rtch_scene_emitters, through rtc_scene_set_emitters; its denoiser, rtch_scene_denoise,
- *                        through rtc_render_denoised; its film stage, rtch_scene_film, through rtc_render_filmed)
+ *                        through rtc_render_denoised; its film stage, rtch_scene_film, through rtc_render_filmed;
+ *                        its robust accumulation, rtch_scene_robust, through rtc_render_robust)
  *
  * Every function that returns int returns 0 on success; otherwise rtch_last_error()
  * holds "<ZigStyleErrorName>: detail" (thread-local).
@@ -87,6 +88,11 @@ int rtch_scene_denoise(void *handle, int *enabled, rtc_denoise_setting *out);
  * "passes".  rtch_scene_render then renders through rtc_render_filmed, with the file's passes, adaptive and denoise settings,
  * and its rgb_out is the film's out: display values, not radiance. */
 int rtch_scene_film(void *handle, int *enabled, rtc_film_setting *out);
+/* The camera sampling's "robust": true | M | {"buckets": M, "gain": g} of the scene file (robust accumulation, DESIGN.md
+ * section 31; buckets 5 and gain 1.0 where absent; false is the same as no key): *enabled = 1 and the setting, or
+ * *enabled = 0 and the defaults when the file has none.  The key needs "passes" of M or more and does not go with "adaptive".
+ * rtch_scene_render then renders through rtc_render_robust, with the file's passes, denoise and film settings. */
+int rtch_scene_robust(void *handle, int *enabled, rtc_robust_setting *out);
 /* The top-level objects' "motion" of the scene file (motion blur): out[3 r .. 3 r + 2] = the
  * displacement of root r over the shutter, (0, 0, 0) for a root without one; n must be the description's n_roots.  Pass
  * it to rtc_scene_set_motion.  rtch_scene_render applies it. */

@@ -188,6 +188,39 @@ pub extern fn rtc_film_device(f: *const RtcFilm, hip_stream: *anyopaque) c_int; 
 pub extern fn rtc_render_filmed(scene: *RtcScene, cam: *const RtcCamera, max_depth: u32, passes: u32, adaptive: ?*const RtcAdaptive,
                                 denoise: ?*const RtcDenoiseSetting, film: ?*const RtcFilmSetting, rgb_out: ?[*]f64, rgba_out: ?[*]u8,
                                 linear_out: ?[*]f64) c_int; // synchronous
+// Robust accumulation (rtc.h, rtc_robust_device): the Gini-weighted median of means over M bucket sums on the device; no
+// scene is needed for the resolve.  Pass p of a run goes into bucket p % M through rtc_scene_accumulate_device with
+// sum = sums + (p % M) * n * 3, passes = p / M + 1 and every optional pointer null.  rtc_render_robust is the whole path:
+// passes into the ordinary sums and the buckets, the resolve, the denoiser and the film stage where asked, the images to the host.
+pub const RtcAccum = extern struct {
+    frame: [*]const f64, // [n][3], device: the pass just rendered
+    n_pixels: usize,
+    passes: u32, // passes in the sums after this call; 1 overwrites
+    sum: [*]f64, // [n][3], device
+    sumsq: ?[*]f64 = null, // [n] or null
+    mean: ?[*]f64 = null, // [n][3] or null
+    rgba: ?[*]u32 = null, // [n] or null
+    noise: ?*f64 = null, // one device double or null
+};
+pub const RtcRobustSetting = extern struct {
+    buckets: u32 = 5, // M: odd, 3 .. 15
+    gain: f64 = 1.0, // 0 or more: 0 keeps every bucket, a large gain is the plain median
+};
+pub const RtcRobust = extern struct {
+    sums: [*]const f64, // [M][n][3], device
+    n_pixels: usize,
+    passes: u32, // M or more
+    setting: RtcRobustSetting,
+    mean_out: [*]f64, // [n][3], device, not inside sums
+    sumsq_out: ?[*]f64, // [n] or null: what rtc_denoise_device takes as sumsq
+    rejected_out: ?[*]u32, // [n] or null: the buckets left out of a pixel
+    rgba: ?[*]u32, // [n] or null: the clamp of mean_out
+};
+pub extern fn rtc_scene_accumulate_device(scene: *RtcScene, accum: *const RtcAccum, hip_stream: ?*anyopaque) c_int; // asynchronous
+pub extern fn rtc_robust_device(r: *const RtcRobust, hip_stream: *anyopaque) c_int; // asynchronous
+pub extern fn rtc_render_robust(scene: *RtcScene, cam: *const RtcCamera, max_depth: u32, passes: u32, robust: ?*const RtcRobustSetting,
+                                denoise: ?*const RtcDenoiseSetting, film: ?*const RtcFilmSetting, rgb_out: ?[*]f64, rgba_out: ?[*]u8,
+                                robust_out: ?[*]f64, plain_out: ?[*]f64, rejected_out: ?[*]u32) c_int; // synchronous
 pub extern fn rtc_grow_csg_lists(scene: *RtcScene) c_int; // after an asynchronous frame whose stats.overflow != 0 on a csg scene: longer lists, render again
 pub extern fn rtc_scatter_tile_list_device(d_tiles: [*]const f64, d_tile_list: [*]const u32, n_tiles: u32, tile_w: u32, tile_h: u32,
                                            hsize: u32, vsize: u32, canvas: [*]f64, hip_stream: ?*anyopaque) c_int; // a rank's tiles straight into a (registered host) canvas

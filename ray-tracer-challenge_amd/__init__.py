@@ -251,6 +251,32 @@ class Film(C.Structure):
                 ("out", C.c_void_p), ("rgba", C.c_void_p), ("scale_out", C.c_void_p)]
 
 
+ROBUST_MAX_BUCKETS = 15   # RTC_ROBUST_MAX_BUCKETS
+
+
+class RobustSetting(C.Structure):
+    """struct rtc_robust_setting (include/rtc.h): robust accumulation's bucket count M (odd, 3 .. 15) and the gain on the
+    Gini coefficient (0 keeps every bucket, a large gain is the plain median).  make() fills the defaults the scene loader
+    uses."""
+
+    _fields_ = [("buckets", C.c_uint32), ("gain", C.c_double)]
+
+    @classmethod
+    def make(cls, buckets=5, gain=1.0):
+        return cls(buckets, gain)
+
+    def to_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class Robust(C.Structure):
+    """struct rtc_robust (include/rtc.h): one call of rtc_robust_device; device pointers as integers, 0 for sumsq_out,
+    rejected_out or rgba when they are not wanted."""
+
+    _fields_ = [("sums", C.c_void_p), ("n_pixels", C.c_size_t), ("passes", C.c_uint32), ("setting", RobustSetting),
+                ("mean_out", C.c_void_p), ("sumsq_out", C.c_void_p), ("rejected_out", C.c_void_p), ("rgba", C.c_void_p)]
+
+
 class Motion(C.Structure):
     """struct rtc_motion (include/rtc.h): a world-space displacement over the shutter per World.objects entry."""
 
@@ -535,16 +561,17 @@ RTC_SYMBOLS = ["rtc_scene_create", "rtc_scene_clone", "rtc_scene_destroy", "rtc_
                "rtc_scene_set_spots", "rtc_scene_set_bumps", "rtc_scene_set_mesh_uvs", "rtc_scene_set_gloss",
                "rtc_scene_set_occlusion", "rtc_scene_set_shadow_filters", "rtc_scene_set_media", "rtc_scene_set_environment",
                "rtc_scene_set_sky_light", "rtc_scene_set_indirect", "rtc_scene_set_emitters", "rtc_denoise_device",
-               "rtc_render_denoised", "rtc_film_scratch_bytes", "rtc_film_device", "rtc_render_filmed"]
+               "rtc_render_denoised", "rtc_film_scratch_bytes", "rtc_film_device", "rtc_render_filmed", "rtc_robust_device",
+               "rtc_render_robust"]
 # (... and include/rtc_diag.h: diagnostics and tuning, for the tests, bench.py and tools/)
 RTC_DIAG_SYMBOLS = ["rtc_set_option", "rtc_last_kernel_name", "rtc_get_schedule", "rtc_get_chunk_times", "rtc_diag_build_tables", "rtc_diag_root_boxes", "rtc_diag_root_spheres", "rtc_diag_emitters", "rtc_diag_emitter_pick",
-                    "rtc_diag_root_flags", "rtc_diag_denoise_tile", "rtc_diag_film_tile"]
+                    "rtc_diag_root_flags", "rtc_diag_denoise_tile", "rtc_diag_film_tile", "rtc_diag_robust_grid"]
 HOST_SYMBOLS = ["rtch_last_error", "rtch_scene_load", "rtch_scene_free", "rtch_scene_desc", "rtch_scene_camera",
                 "rtch_camera_rotate", "rtch_camera_move", "rtch_camera_make", "rtch_canvas_ppm", "rtch_canvas_rgba8", "rtch_scene_render", "rtch_set_loader_threads",
                 "rtch_scene_lights", "rtch_scene_sampling", "rtch_scene_passes", "rtch_scene_motion", "rtch_scene_adaptive",
                 "rtch_scene_spots", "rtch_scene_bumps", "rtch_scene_mesh_uvs", "rtch_scene_gloss", "rtch_scene_occlusion",
                 "rtch_scene_shadow_filters", "rtch_scene_media", "rtch_scene_environment", "rtch_scene_sky_light",
-                "rtch_scene_indirect", "rtch_scene_emitters", "rtch_scene_denoise", "rtch_scene_film"]
+                "rtch_scene_indirect", "rtch_scene_emitters", "rtch_scene_denoise", "rtch_scene_film", "rtch_scene_robust"]
 
 MULTI_SYMBOLS = ["rtc_multi_create", "rtc_multi_destroy", "rtc_multi_render", "rtc_multi_render_rgba8", "rtc_multi_render_device", "rtc_multi_render_rgba8_device",
                  "rtc_multi_synchronize", "rtc_multi_stream", "rtc_multi_get_stats", "rtc_multi_balance", "rtc_multi_last_error"]
@@ -627,6 +654,11 @@ def hip_lib():
         lib.rtc_render_filmed.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.POINTER(Adaptive),
                                           C.POINTER(DenoiseSetting), C.POINTER(FilmSetting), C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rtc_diag_film_tile.argtypes = [_u32p, _u32p, _u32p]
+        lib.rtc_robust_device.argtypes = [C.POINTER(Robust), C.c_void_p]
+        lib.rtc_render_robust.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.POINTER(RobustSetting),
+                                          C.POINTER(DenoiseSetting), C.POINTER(FilmSetting), C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]
+        lib.rtc_diag_robust_grid.argtypes = [_u32p, _u32p]
         lib.rtc_scene_destroy.argtypes = [C.c_void_p]
         lib.rtc_scene_destroy.restype = None
         lib.rtc_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32] + [C.c_uint32] * 4 + [C.c_void_p]
@@ -692,6 +724,7 @@ def host_lib():
         lib.rtch_scene_adaptive.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(Adaptive)]
         lib.rtch_scene_denoise.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(DenoiseSetting)]
         lib.rtch_scene_film.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(FilmSetting)]
+        lib.rtch_scene_robust.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(RobustSetting)]
         lib.rtch_scene_camera.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Camera)]
         lib.rtch_camera_rotate.argtypes = [C.c_void_p, C.c_double]
         lib.rtch_camera_move.argtypes = [C.c_void_p, C.c_double]
@@ -995,6 +1028,13 @@ class HostScene:
         _check_host(host_lib().rtch_scene_film(self._h, C.byref(on), C.byref(f)))
         return f if on.value else None
 
+    def robust(self):
+        """The camera sampling's "robust" of the scene file (rtch_scene_robust): a RobustSetting, or None when the file has
+        no such key (or has it false)."""
+        on, r = C.c_int(), RobustSetting()
+        _check_host(host_lib().rtch_scene_robust(self._h, C.byref(on), C.byref(r)))
+        return r if on.value else None
+
     def rotate_camera(self, angle):
         """Renderer.rotateCamera (lib.zig:166-178): orbit the camera around its target, about `up`."""
         _check_host(host_lib().rtch_camera_rotate(self._h, C.c_double(angle)))
@@ -1232,6 +1272,23 @@ class GpuScene:
                                                rgb.ctypes.data, rgba.ctypes.data, linear.ctypes.data))
         return rgb, rgba, linear
 
+    def render_robust(self, cam, passes, robust=None, denoise=None, film=None, max_depth=REFERENCE_DEPTH):
+        """rtc_render_robust: `passes` sample passes accumulated on the device, into the ordinary sums and round-robin into
+        bucket sums; the Gini-weighted median of means of the buckets (robust: a RobustSetting; None: the defaults), filtered
+        by the denoiser where `denoise` is a DenoiseSetting and taken to display values where `film` is a FilmSetting (None:
+        no film stage); returns (rgb [h][w][3] f64: the last stage's image, rgba [h][w][4] u8: its clamp, robust [h][w][3]
+        f64: the robust mean, plain [h][w][3] f64: the ordinary mean, rejected [h][w] u32: the buckets left out), host
+        arrays.  The handle's own sample pass is left as it was."""
+        shape = (cam.vsize, cam.hsize)
+        rgb, robust_mean, plain = (np.empty(shape + (3,), dtype=np.float64) for _ in range(3))
+        rgba = np.empty(shape + (4,), dtype=np.uint8)
+        rejected = np.empty(shape, dtype=np.uint32)
+        _check_hip(hip_lib().rtc_render_robust(self._s, C.byref(cam), max_depth, passes, C.byref(robust) if robust is not None else None,
+                                               C.byref(denoise) if denoise is not None else None, C.byref(film) if film is not None else None,
+                                               rgb.ctypes.data, rgba.ctypes.data, robust_mean.ctypes.data, plain.ctypes.data,
+                                               rejected.ctypes.data))
+        return rgb, rgba, robust_mean, plain, rejected
+
     def clone(self):
         """rtc_scene_clone: a handle of its own (stream, schedule, counters) on the same device copy of the scene - one
         per frame in flight."""
@@ -1328,11 +1385,17 @@ class Progressive:
     """Progressive rendering on the device: each step() renders the next sample pass of `gpu_scene` (rtc_scene_set_sample_pass)
     into a frame buffer and accumulates it (rtc_scene_accumulate_device) into running sums, the mean and its RGBA8 clamp,
     all torch tensors on the scene's device, on a torch stream of its own (`stream`).  The host decides when to stop, from
-    what step() returns; mean() and rgba8() order the caller's current stream after the last step."""
+    what step() returns; mean() and rgba8() order the caller's current stream after the last step.  With robust=M (odd,
+    3 .. 15) every step() also adds its pass to bucket `passes % M` of `buckets` ([M][h][w][3], a second
+    rtc_scene_accumulate_device), and robust(), denoised(robust=...) and filmed(robust=...) resolve them (rtc_robust_device)."""
 
-    def __init__(self, gpu_scene, cam, max_depth=REFERENCE_DEPTH, noise=True):
+    def __init__(self, gpu_scene, cam, max_depth=REFERENCE_DEPTH, noise=True, robust=None):
         import torch
         self.gpu, self.cam, self.max_depth, self.noise_on = gpu_scene, cam, max_depth, noise
+        if robust is not None and (robust % 2 == 0 or not 3 <= robust <= ROBUST_MAX_BUCKETS):
+            raise ValueError(f"Progressive(robust={robust}): an odd bucket count from 3 to {ROBUST_MAX_BUCKETS}")
+        self.robust_buckets = robust
+        self.buckets = torch.empty((robust, cam.vsize, cam.hsize, 3), dtype=torch.float64, device="cuda") if robust is not None else None
         shape, dev = (cam.vsize, cam.hsize), "cuda"
         self.frame = torch.empty(shape + (3,), dtype=torch.float64, device=dev)
         self.sum = torch.empty(shape + (3,), dtype=torch.float64, device=dev)
@@ -1355,6 +1418,10 @@ class Progressive:
                   self.sumsq.data_ptr() if self.sumsq is not None else None, self._mean.data_ptr(), self._rgba.data_ptr(),
                   self._noise.data_ptr() if want_noise else None)
         self.gpu.accumulate_device(a, stream)
+        if self.buckets is not None:   # (pass p into bucket p % M, its passes // M + 1-th frame)
+            m = self.robust_buckets
+            self.gpu.accumulate_device(Accum(self.frame.data_ptr(), self.cam.hsize * self.cam.vsize, self.passes // m + 1,
+                                             self.buckets[self.passes % m].data_ptr(), None, None, None, None), stream)
         self.passes = n
         if not want_noise:
             return None
@@ -1373,18 +1440,43 @@ class Progressive:
         torch.cuda.current_stream().wait_stream(self.stream)
         return self._rgba.view(self.cam.vsize, self.cam.hsize, 1).view(torch.uint8)
 
-    def denoised(self, **setting):
+    def robust(self, gain=1.0):
+        """(mean [h][w][3] f64, sumsq [h][w] f64, rejected [h][w] i32) on the device: the Gini-weighted median of means of the
+        buckets (rtc_robust_device) after the passes so far (M at least), the sum of squares the denoiser takes with it and
+        the buckets left out of each pixel, on this object's stream after its last step.  ValueError on an object built
+        without robust=."""
+        import torch
+        if self.buckets is None:
+            raise ValueError("Progressive built without robust=M keeps no bucket sums")
+        mean = torch.empty_like(self._mean)
+        sumsq = torch.empty((self.cam.vsize, self.cam.hsize), dtype=torch.float64, device=mean.device)
+        rejected = torch.empty((self.cam.vsize, self.cam.hsize), dtype=torch.int32, device=mean.device)
+        self.stream.wait_stream(torch.cuda.current_stream())   # (the tensors were allocated on the current stream)
+        robust_device(self.buckets.data_ptr(), self.cam.hsize * self.cam.vsize, self.passes, mean.data_ptr(), self.stream.cuda_stream,
+                      setting=RobustSetting.make(self.robust_buckets, gain), sumsq_ptr=sumsq.data_ptr(), rejected_ptr=rejected.data_ptr())
+        torch.cuda.current_stream().wait_stream(self.stream)
+        return mean, sumsq, rejected
+
+    def denoised(self, robust=None, **setting):
         """[h][w][3] f64 on the device: the denoiser (rtc_denoise_device) over the mean, the sums of squares and the passes
-        so far (two at least), on this object's stream after its last step; `setting`: DenoiseSetting.make's keywords."""
+        so far (two at least), on this object's stream after its last step; `setting`: DenoiseSetting.make's keywords.
+        Where `robust` is a dict of robust()'s keywords ({} for the defaults), over the robust mean and its sums of squares
+        instead."""
+        if robust is not None:
+            mean, sumsq, _ = self.robust(**robust)
+            return _denoised(self, self.passes, None, setting, mean, sumsq)
         if self.sumsq is None:
             raise ValueError("Progressive(noise=False) keeps no sums of squares: nothing to guide the denoiser")
         return _denoised(self, self.passes, None, setting)
 
-    def filmed(self, denoise=None, **film):
+    def filmed(self, denoise=None, robust=None, **film):
         """(out [h][w][3] f64, rgba [h][w][4] u8) on the device: the film stage (rtc_film_device) over the mean - or, where
         `denoise` is a dict of DenoiseSetting.make's keywords, over denoised(**denoise) - on this object's stream after its
-        last step; `film`: FilmSetting.make's keywords."""
-        return _filmed(self, self.denoised(**denoise) if denoise is not None else self._mean, film)
+        last step; `film`: FilmSetting.make's keywords.  Where `robust` is a dict of robust()'s keywords, the robust mean
+        takes the mean's place (under the denoiser too)."""
+        if denoise is not None:
+            return _filmed(self, self.denoised(robust=robust, **denoise), film)
+        return _filmed(self, self.robust(**robust)[0] if robust is not None else self._mean, film)
 
 
 class AdaptiveProgressive:
@@ -1479,18 +1571,34 @@ def denoise_tile():
     return w.value, h.value
 
 
-def _denoised(prog, passes, tile_passes, setting):
+def _denoised(prog, passes, tile_passes, setting, mean=None, sumsq=None):
     """Progressive.denoised / AdaptiveProgressive.denoised: a new tensor, filled on prog.stream; the caller's current stream
-    is ordered after it."""
+    is ordered after it.  mean, sumsq: the pair to filter in place of the object's own (the robust one)."""
     import torch
-    out = torch.empty_like(prog._mean)
+    mean, sumsq = mean if mean is not None else prog._mean, sumsq if sumsq is not None else prog.sumsq
+    out = torch.empty_like(mean)
     prog.stream.wait_stream(torch.cuda.current_stream())   # (`out` was allocated on the current stream)
     tile = (prog.adaptive.tile_w, prog.adaptive.tile_h) if tile_passes is not None else (0, 0)
-    denoise_device(prog._mean.data_ptr(), prog.sumsq.data_ptr(), prog.cam.hsize, prog.cam.vsize, out.data_ptr(), prog.stream.cuda_stream,
+    denoise_device(mean.data_ptr(), sumsq.data_ptr(), prog.cam.hsize, prog.cam.vsize, out.data_ptr(), prog.stream.cuda_stream,
                    passes=passes, tile_passes_ptr=tile_passes.data_ptr() if tile_passes is not None else None, tile=tile,
                    setting=DenoiseSetting.make(**setting))
     torch.cuda.current_stream().wait_stream(prog.stream)
     return out
+
+
+def robust_device(sums_ptr, n_pixels, passes, mean_ptr, stream, setting=None, sumsq_ptr=None, rejected_ptr=None, rgba_ptr=None):
+    """rtc_robust_device: the Gini-weighted median of means over bucket sums [M][n][3] on the device after `passes` passes
+    dealt round-robin, enqueued on `stream` (a HIP stream, not None); setting: a RobustSetting (None: the defaults);
+    mean_ptr: [n][3] f64; sumsq_ptr: [n] f64 for the denoiser, rejected_ptr: [n] u32, rgba_ptr: the clamp of the mean, or None."""
+    r = Robust(sums_ptr, n_pixels, passes, setting if setting is not None else RobustSetting.make(), mean_ptr, sumsq_ptr, rejected_ptr, rgba_ptr)
+    _check_hip(hip_lib().rtc_robust_device(C.byref(r), stream))
+
+
+def robust_grid():
+    """rtc_diag_robust_grid: (max_blocks, block) - the cap of rtc_robust_device's grid and the threads of a block."""
+    a, b = C.c_uint32(), C.c_uint32()
+    _check_hip(hip_lib().rtc_diag_robust_grid(C.byref(a), C.byref(b)))
+    return a.value, b.value
 
 
 def film_scratch_bytes(hsize, vsize, setting=None):

@@ -278,6 +278,10 @@ void rtcDenoiseTile(uint32_t* w, uint32_t* h);
 hipError_t rtcFilmLaunch(const rtc_film* f, bool naive, hipStream_t stream);
 size_t rtcFilmScratchBytes(uint32_t hsize, uint32_t vsize, const rtc_film_setting* s);
 void rtcFilmTile(uint32_t* row_w, uint32_t* col_w, uint32_t* col_h);
+// Robust accumulation's resolve kernels (rtc_robust.hip): the enqueue of the register forms or (naive) the literal one, and
+// the grid's cap and block.
+hipError_t rtcRobustLaunch(const rtc_robust* r, bool naive, hipStream_t stream);
+void rtcRobustGrid(uint32_t* max_blocks, uint32_t* block);
 extern "C" __global__ void rtc_estimate_kernel(const DevScene S, const DevCamera cam, const DevPixelMap map,
                                                uint32_t* __restrict__ chunk_cost, uint32_t* __restrict__ chunk_time,
                                                DevChunkShape* __restrict__ chunk_shape, DevPackState* __restrict__ state
@@ -4008,6 +4012,125 @@ int rtc_render_filmed(rtc_scene* s, const rtc_camera* cam, uint32_t max_depth, u
   return RTC_OK;
 }
 
+// ---- robust accumulation
+static const rtc_robust_setting kRobustDefaults{5u, 1.0};
+
+static int checkRobustSetting(const rtc_robust_setting& v) {
+  if (v.buckets % 2u == 0u || v.buckets < 3u || v.buckets > RTC_ROBUST_MAX_BUCKETS)
+    return fail(RTC_ERR_INVALID_ARGUMENT, "robust: buckets %u (odd, 3 to %u)", v.buckets, RTC_ROBUST_MAX_BUCKETS);
+  if (!std::isfinite(v.gain) || v.gain < 0.0) return fail(RTC_ERR_INVALID_ARGUMENT, "robust: gain %g (finite, 0 or more)", v.gain);
+  return RTC_OK;
+}
+
+int rtc_robust_device(const rtc_robust* r, void* hip_stream) {
+  g_error.clear();
+  if (!r || !r->sums || !r->mean_out || !hip_stream) return fail(RTC_ERR_INVALID_ARGUMENT, "robust: null argument");
+  if (r->n_pixels == 0u || r->n_pixels > (static_cast<size_t>(1) << 40)) return fail(RTC_ERR_INVALID_ARGUMENT, "robust: %zu pixels", r->n_pixels);
+  if (const int e = checkRobustSetting(r->setting); e != RTC_OK) return e;
+  if (r->passes < r->setting.buckets)
+    return fail(RTC_ERR_INVALID_ARGUMENT, "robust: passes %u (the %u buckets or more)", r->passes, r->setting.buckets);
+  const uintptr_t lo = reinterpret_cast<uintptr_t>(r->sums), b_img = static_cast<uintptr_t>(r->n_pixels) * 3u * sizeof(double),
+                  hi = lo + r->setting.buckets * b_img;
+  auto inside = [&](const void* p, uintptr_t bytes) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+    return p && a < hi && lo < a + bytes;
+  };
+  if (inside(r->mean_out, b_img)) return fail(RTC_ERR_INVALID_ARGUMENT, "robust: mean_out inside sums");
+  if (inside(r->sumsq_out, b_img / 3u)) return fail(RTC_ERR_INVALID_ARGUMENT, "robust: sumsq_out inside sums");
+  HIP_TRY(rtcRobustLaunch(r, rtcOptions().robust_naive != 0.0, static_cast<hipStream_t>(hip_stream)));
+  return RTC_OK;
+}
+
+int rtc_diag_robust_grid(uint32_t* max_blocks, uint32_t* block) {
+  g_error.clear();
+  if (!max_blocks || !block) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
+  rtcRobustGrid(max_blocks, block);
+  return RTC_OK;
+}
+
+// accumulatedRun's passes with a second accumulation each, into the pass's bucket of `sums` ([M][n][3]): pass p at sample
+// pass p through d_frame, the handle's own pass put back whatever happens.
+static int robustRun(rtc_scene* s, const rtc_camera* cam, uint32_t max_depth, uint32_t passes, uint32_t buckets, double* d_frame,
+                     rtc_adaptive_state* st, double* sums) {
+  const size_t n_px = static_cast<size_t>(cam->hsize) * cam->vsize;
+  const uint32_t own_pass = s->sample_pass;
+  int rc = RTC_OK;
+  for (uint32_t p = 0; p < passes && rc == RTC_OK; ++p) {
+    rc = rtc_scene_set_sample_pass(s, p);
+    if (rc == RTC_OK) rc = rtc_render_device(s, cam, max_depth, 0, 0, cam->hsize, cam->vsize, d_frame, s->stream);
+    const rtc_accum acc{d_frame, n_px, p + 1u, st->sum, st->sumsq, st->mean, nullptr, nullptr};
+    if (rc == RTC_OK) rc = rtc_scene_accumulate_device(s, &acc, s->stream);
+    const rtc_accum bucket{d_frame, n_px, p / buckets + 1u, sums + (p % buckets) * n_px * 3u, nullptr, nullptr, nullptr, nullptr};
+    if (rc == RTC_OK) rc = rtc_scene_accumulate_device(s, &bucket, s->stream);
+  }
+  const std::string error = g_error;
+  (void)rtc_scene_set_sample_pass(s, own_pass);
+  g_error = error;
+  return rc;
+}
+
+int rtc_render_robust(rtc_scene* s, const rtc_camera* cam, uint32_t max_depth, uint32_t passes, const rtc_robust_setting* robust,
+                      const rtc_denoise_setting* denoise, const rtc_film_setting* film, double* rgb_out, uint8_t* rgba_out,
+                      double* robust_out, double* plain_out, uint32_t* rejected_out) {
+  g_error.clear();
+  if (!s || (!rgb_out && !rgba_out)) return fail(RTC_ERR_INVALID_ARGUMENT, "robust: null argument");
+  if (const int e = checkCamera(cam); e != RTC_OK) return e;
+  const rtc_robust_setting v = robust ? *robust : kRobustDefaults;
+  if (const int e = checkRobustSetting(v); e != RTC_OK) return e;
+  if (denoise)
+    if (const int e = checkDenoiseSetting(*denoise); e != RTC_OK) return e;
+  if (film)
+    if (const int e = checkFilmSetting(*film); e != RTC_OK) return e;
+  uint32_t n_tiles = 0;
+  if (const int e = checkRun(s, cam, passes, v.buckets, nullptr, &n_tiles, "robust"); e != RTC_OK) return e;
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(ensureOwnStream(s));
+  // one allocation: the robust mean, the denoiser's out, the film's out, the pass just rendered, the robust sums of squares,
+  // the rejected map, rgba, the film's scratch, the bucket sums, then the sums as accumulatedRun has them
+  auto up16 = [](size_t b) { return (b + 15u) & ~static_cast<size_t>(15u); };
+  const size_t n_px = static_cast<size_t>(cam->hsize) * cam->vsize;
+  const size_t b_img = up16(n_px * 3u * sizeof(double)), b_sq = up16(n_px * sizeof(double)), b_u32 = up16(n_px * sizeof(uint32_t));
+  const size_t b_scratch = film ? up16(rtcFilmScratchBytes(cam->hsize, cam->vsize, film)) : 0u;
+  const size_t b_buckets = up16(v.buckets * n_px * 3u * sizeof(double));
+  char* base = nullptr;
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&base), 4u * b_img + b_sq + 2u * b_u32 + b_scratch + b_buckets + carveAdaptive(nullptr, n_px, 0u, nullptr)));
+  FreeWhenIdle release{s, base};
+  char* p = base;
+  double* const d_robust = reinterpret_cast<double*>(p);
+  double* const d_denoised = reinterpret_cast<double*>(p += b_img);
+  double* const d_film = reinterpret_cast<double*>(p += b_img);
+  double* const d_frame = reinterpret_cast<double*>(p += b_img);
+  double* const d_sq = reinterpret_cast<double*>(p += b_img);
+  uint32_t* const d_rejected = reinterpret_cast<uint32_t*>(p += b_sq);
+  uint32_t* const d_rgba = reinterpret_cast<uint32_t*>(p += b_u32);
+  void* const d_scratch = b_scratch ? (p + b_u32) : nullptr;
+  double* const d_buckets = reinterpret_cast<double*>(p += b_u32 + b_scratch);
+  rtc_adaptive_state st{};
+  carveAdaptive(p + b_buckets, n_px, 0u, &st);
+  if (const int e = robustRun(s, cam, max_depth, passes, v.buckets, d_frame, &st, d_buckets); e != RTC_OK) return e;
+  // (rgba comes from the last stage that runs)
+  const rtc_robust r{d_buckets, n_px, passes, v, d_robust, d_sq, d_rejected, rgba_out && !denoise && !film ? d_rgba : nullptr};
+  if (const int e = rtc_robust_device(&r, s->stream); e != RTC_OK) return e;
+  const double* last = d_robust;
+  if (denoise) {
+    const rtc_denoise d{d_robust, d_sq, cam->hsize, cam->vsize, passes, nullptr, 0u, 0u, *denoise, d_denoised, rgba_out && !film ? d_rgba : nullptr};
+    if (const int e = rtc_denoise_device(&d, s->stream); e != RTC_OK) return e;
+    last = d_denoised;
+  }
+  if (film) {
+    const rtc_film f{last, cam->hsize, cam->vsize, *film, d_scratch, d_film, rgba_out ? d_rgba : nullptr, nullptr};
+    if (const int e = rtc_film_device(&f, s->stream); e != RTC_OK) return e;
+    last = d_film;
+  }
+  if (rgb_out) HIP_TRY(hipMemcpyAsync(rgb_out, last, n_px * 3u * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  if (rgba_out) HIP_TRY(hipMemcpyAsync(rgba_out, d_rgba, n_px * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+  if (robust_out) HIP_TRY(hipMemcpyAsync(robust_out, d_robust, n_px * 3u * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  if (plain_out) HIP_TRY(hipMemcpyAsync(plain_out, st.mean, n_px * 3u * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  if (rejected_out) HIP_TRY(hipMemcpyAsync(rejected_out, d_rejected, n_px * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return RTC_OK;
+}
+
 int rtc_scene_clone(const rtc_scene* src, rtc_scene** out) {
   g_error.clear();
   if (!src || !out) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
@@ -4513,7 +4636,8 @@ int rtc_set_option(const char* name, double value) {
                {"shadow_filter_kernels", &o.shadow_filter_kernels}, {"media_kernels", &o.media_kernels},
                {"environment_kernels", &o.environment_kernels}, {"sky_light_kernels", &o.sky_light_kernels},
                {"indirect_kernels", &o.indirect_kernels}, {"emitter_kernels", &o.emitter_kernels},
-               {"denoise_naive", &o.denoise_naive}, {"film_naive", &o.film_naive}};
+               {"denoise_naive", &o.denoise_naive}, {"film_naive", &o.film_naive},
+               {"robust_naive", &o.robust_naive}};
   for (const auto& e : table)
     if (std::strcmp(e.name, name) == 0) {
       e.slot->set(value);

@@ -82,6 +82,7 @@ struct RtcOptions {
   RtcOption emitter_kernels{0.0};      // != 0: the emitter kernels even on a handle without an emitter list, the count zero (tests: against the handle's ordinary kernels)
   RtcOption denoise_naive{0.0};        // != 0: rtc_denoise_device runs the literal kernel, one thread per pixel (tests and timing: against the tiled one)
   RtcOption film_naive{0.0};           // != 0: a rtc_film_device that blooms runs the literal kernels, one thread per pixel (tests and timing: against the tiled ones)
+  RtcOption robust_naive{0.0};         // != 0: rtc_robust_device runs the literal kernel, one thread per pixel (tests and timing: against the register forms)
   RtcOption build_threads{0.0};        // threads of rtc_scene_create's candidate-BVH build (one top-level group each); 0: as many as the host allows, up to 8
 };
 inline RtcOptions& rtcOptions() {

@@ -93,6 +93,14 @@ int rtch_scene_denoise(void* h, int* enabled, rtc_denoise_setting* out) {
   });
 }
 
+int rtch_scene_robust(void* h, int* enabled, rtc_robust_setting* out) {
+  return guarded([&] {
+    const rtc::CameraSampling& s = static_cast<HostScene*>(h)->info.sampling;
+    *enabled = s.robust ? 1 : 0;
+    *out = rtc_robust_setting{s.robust_buckets, s.robust_gain};
+  });
+}
+
 static rtc_film_setting filmSetting(const rtc::CameraFilm& f) {
   return rtc_film_setting{f.exposure, f.auto_key, f.bloom_radius, f.bloom_sigma, f.bloom_threshold, f.bloom_intensity, f.curve, f.white, f.transfer, f.gamma};
 }
@@ -360,7 +368,7 @@ int rtch_scene_render(void* h, uint32_t width, uint32_t height, uint32_t max_dep
     // number - the bits of rtc_scene_accumulate_device's mean)
     const uint32_t passes = hs->info.sampling.passes;
     const size_t n = 3ull * cam.hsize * cam.vsize;
-    std::vector<double> frame(passes > 1u && !hs->info.sampling.denoise && !hs->info.film.enabled ? n : 0u);
+    std::vector<double> frame(passes > 1u && !hs->info.sampling.denoise && !hs->info.film.enabled && !hs->info.sampling.robust ? n : 0u);
     rtc_scene* scene = nullptr;
     // (a scene with area lights: its light table; point lights only: the description alone, as before)
     int st = hs->flat.has_area_light ? rtc_scene_create_with_lights(&hs->desc, &hs->lights, &scene) : rtc_scene_create(&hs->desc, &scene);
@@ -442,7 +450,13 @@ int rtch_scene_render(void* h, uint32_t width, uint32_t height, uint32_t max_dep
         st = rtc_scene_set_emitters(scene, &em);
       }
       const rtc::CameraSampling& cs = hs->info.sampling;
-      if (hs->info.film.enabled && st == RTC_OK) {  // (the whole path on the device, the film stage last, section 30)
+      if (cs.robust && st == RTC_OK) {  // (bucket sums and their resolve, then the file's denoiser and film stage, section 31)
+        const rtc_robust_setting rb{cs.robust_buckets, cs.robust_gain};
+        const rtc_denoise_setting dn{cs.denoise_radius, cs.denoise_patch, cs.denoise_strength, cs.denoise_cancel};
+        const rtc_film_setting film = filmSetting(hs->info.film);
+        st = rtc_render_robust(scene, &cam, max_depth, passes, &rb, cs.denoise ? &dn : nullptr, hs->info.film.enabled ? &film : nullptr,
+                               rgb_out, nullptr, nullptr, nullptr, nullptr);
+      } else if (hs->info.film.enabled && st == RTC_OK) {  // (the whole path on the device, the film stage last, section 30)
         const rtc_adaptive a{cs.tile_w, cs.tile_h, cs.min_passes, cs.passes, cs.threshold};
         const rtc_denoise_setting dn{cs.denoise_radius, cs.denoise_patch, cs.denoise_strength, cs.denoise_cancel};
         const rtc_film_setting film = filmSetting(hs->info.film);
@@ -455,7 +469,7 @@ int rtch_scene_render(void* h, uint32_t width, uint32_t height, uint32_t max_dep
         const rtc_adaptive a{cs.tile_w, cs.tile_h, cs.min_passes, cs.passes, cs.threshold};
         st = rtc_render_adaptive(scene, &cam, max_depth, &a, rgb_out, nullptr);
       }
-      const bool on_host = !cs.adaptive && !cs.denoise && !hs->info.film.enabled;  // (the passes summed here)
+      const bool on_host = !cs.adaptive && !cs.denoise && !hs->info.film.enabled && !cs.robust;  // (the passes summed here)
       for (uint32_t p = 0; p < passes && st == RTC_OK && on_host; ++p) {
         if (p > 0u) st = rtc_scene_set_sample_pass(scene, p);
         if (st == RTC_OK) st = rtc_render(scene, &cam, max_depth, 0, 0, cam.hsize, cam.vsize, p == 0u ? rgb_out : frame.data());

@@ -988,7 +988,7 @@ SceneInfo parseScene(const std::string& scene_json, const FileLoader& load_file_
   info.camera.setTransform(Matrix4::viewTransform(from, to, up));
   if (const Value* smp = cam.find("sampling")) {  // (not in the reference: anti-aliasing and focal blur, every key optional)
     requireObject(*smp, "sampling");
-    checkFields(*smp, {"grid", "jitter", "aperture", "focal-distance", "seed", "passes", "adaptive", "denoise", "gloss-seed",
+    checkFields(*smp, {"grid", "jitter", "aperture", "focal-distance", "seed", "passes", "adaptive", "denoise", "robust", "gloss-seed",
                        "occlusion-samples", "occlusion-seed"}, "sampling");
     CameraSampling& s = info.sampling;
     if (const Value* v = smp->find("grid")) {
@@ -1075,6 +1075,34 @@ SceneInfo parseScene(const std::string& scene_json, const FileLoader& load_file_
       }
       if (s.denoise && !s.adaptive && s.passes < 2)
         throw Error("InvalidData", "sampling: denoise needs passes of 2 or more, or adaptive");
+    }
+    if (const Value* rb = smp->find("robust")) {  // (robust accumulation, DESIGN.md section 31: true, false, M or the setting's keys)
+      auto bucketsOf = [](const Value& v) {
+        if (v.type != Value::Number || !(v.num >= 3.0 && v.num <= RTC_ROBUST_MAX_BUCKETS) || v.num != std::floor(v.num) ||
+            static_cast<uint32_t>(v.num) % 2u == 0u)
+          throw Error("InvalidData", "sampling.robust: buckets is an odd whole number from 3 to " + std::to_string(RTC_ROBUST_MAX_BUCKETS));
+        return static_cast<uint32_t>(v.num);
+      };
+      if (rb->type == Value::Object) {
+        checkFields(*rb, {"buckets", "gain"}, "sampling.robust");
+        s.robust = true;
+        if (const Value* v = rb->find("buckets")) s.robust_buckets = bucketsOf(*v);
+        if (const Value* v = rb->find("gain")) {
+          if (v->type != Value::Number || !std::isfinite(v->num) || v->num < 0.0)
+            throw Error("InvalidData", "sampling.robust: gain is finite and at least 0");
+          s.robust_gain = v->num;
+        }
+      } else if (rb->type == Value::Bool) {
+        s.robust = rb->b;
+      } else if (rb->type == Value::Number) {
+        s.robust = true;
+        s.robust_buckets = bucketsOf(*rb);
+      } else {
+        throw Error("InvalidData", "sampling: robust is true, false, a bucket count or {\"buckets\", \"gain\"}");
+      }
+      if (s.robust && s.adaptive) throw Error("InvalidData", "sampling: robust beside adaptive (buckets per tile are not kept)");
+      if (s.robust && s.passes < s.robust_buckets)
+        throw Error("InvalidData", "sampling: robust needs passes of its " + std::to_string(s.robust_buckets) + " buckets or more");
     }
   }
   if (const Value* fv = cam.find("film")) {  // (the film stage, DESIGN.md section 30: true, false or the setting's keys)

@@ -35,6 +35,10 @@ struct CameraSampling {
   bool denoise = false;
   uint32_t denoise_radius = 7, denoise_patch = 2;
   double denoise_strength = 0.45, denoise_cancel = 1.0;
+  // "robust" (section 31): rtch_scene_render resolves bucket sums (rtc_render_robust); rtc_robust_setting's values
+  bool robust = false;
+  uint32_t robust_buckets = 5;
+  double robust_gain = 1.0;
   uint64_t gloss_seed = 0;  // "gloss-seed" (section 20): rtc_gloss::seed of the materials' "roughness"
   uint32_t occlusion_samples = 1;  // "occlusion-samples" (section 21): rtc_occlusion::samples of the materials' "ambient-occlusion"
   uint64_t occlusion_seed = 0;     // "occlusion-seed": rtc_occlusion::seed

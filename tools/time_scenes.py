@@ -84,6 +84,11 @@ threshold 1, intensity 0.15; 0: no bloom, the point kernel), a tone curve (aces)
 Prints the time of one call in the tiled form and in the literal one (option film_naive; the point kernel has one form, timed
 four times), each taken twice, alternating, with device events around 20 launches after a warm-up, and whether the two results
 have the same bits.  The frame time on the same line is one pass.
+--robust [M[:gain],...]: robust accumulation's resolve (rtc_robust_device) with M buckets and a gain (1
+without one) over the bucket sums of 16 progressive passes of the timed handle; several settings are separated by commas (5
+without a value).  Prints the time of one call in the register form and in the literal one (option robust_naive), each taken
+twice, alternating, with device events around 20 launches after a warm-up, and whether the two results have the same bits.
+The frame time on the same line is one pass.
 --data-dir DIR: where a scene named by its path finds the images and OBJ files it names (default: the scene's directory).
 --adaptive threshold[,min,tile]: adaptive sampling at up to --max-passes (64) passes, min passes 4 and
 16 x 16 tiles by default, with the --sampling of the frames: prints the rounds and tile-passes of a run against
@@ -135,6 +140,7 @@ ap.add_argument("--indirect", default="")
 ap.add_argument("--emitters", default="")
 ap.add_argument("--denoise", nargs="?", const="7:2:0.45", default="")
 ap.add_argument("--film", nargs="?", const="12", default="")
+ap.add_argument("--robust", nargs="?", const="5", default="")
 ap.add_argument("--data-dir", default="")  # where a scene named by path finds its images and OBJ files (default: beside it)
 ap.add_argument("--torus", action="store_true")
 ap.add_argument("--meshuv", action="store_true")
@@ -320,6 +326,47 @@ def time_film(gpu, cam, depth):
         text += (f" | film {spec} on 8 passes, {launches} launches: " + ("tiled " if radius else "point ") + " ".join(f"{t:.4f}" for t in ms["tiled"])
                  + (" ms, naive " if radius else " ms, again ") + " ".join(f"{t:.4f}" for t in ms["naive"])
                  + f" ms ({min(ms['naive']) / min(ms['tiled']):.1f}x), same bits {same}")
+    gpu.set_sample_pass(0)
+    return text
+
+
+def time_robust(gpu, cam, depth):
+    """--robust: both kernel forms on the bucket sums of 16 passes of the handle, each twice, alternating; ms per call"""
+    text = ""
+    for spec in args.robust.split(","):
+        f = spec.split(":")
+        buckets, gain = int(f[0]), float(f[1]) if len(f) > 1 else 1.0
+        prog = rtc.Progressive(gpu, cam, depth, noise=False, robust=buckets)
+        for _ in range(max(16, buckets)):
+            prog.step()
+        launches, n = max(20, args.frames), cam.hsize * cam.vsize
+        setting = rtc.RobustSetting.make(buckets, gain)
+        sumsq = torch.empty((cam.vsize, cam.hsize), dtype=torch.float64, device="cuda")
+        rejected = torch.empty((cam.vsize, cam.hsize), dtype=torch.int32, device="cuda")
+        results, ms = {}, {"register": [], "naive": []}
+        torch.cuda.synchronize()
+        for rep in range(2):
+            for form in ("register", "naive"):
+                rtc.set_option("robust_naive", 1 if form == "naive" else 0)
+                results[form] = torch.empty_like(prog._mean)
+                run = lambda: rtc.robust_device(prog.buckets.data_ptr(), n, prog.passes, results[form].data_ptr(), prog.stream.cuda_stream,
+                                                setting=setting, sumsq_ptr=sumsq.data_ptr(), rejected_ptr=rejected.data_ptr())
+                torch.cuda.synchronize()
+                run()   # (warm-up: the code object is loaded)
+                torch.cuda.synchronize()
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record(prog.stream)
+                for _ in range(launches):
+                    run()
+                b.record(prog.stream)
+                torch.cuda.synchronize()
+                ms[form].append(a.elapsed_time(b) / launches)
+        rtc.set_option("robust_naive", 0)
+        same = bool((results["register"].view(torch.int64) == results["naive"].view(torch.int64)).all())
+        text += (f" | robust {spec} on {prog.passes} passes, {launches} launches: register " + " ".join(f"{t:.4f}" for t in ms["register"])
+                 + " ms, naive " + " ".join(f"{t:.4f}" for t in ms["naive"])
+                 + f" ms ({min(ms['naive']) / min(ms['register']):.1f}x), same bits {same}, rejected on {float((rejected > 0).float().mean()):.4f} of the pixels")
+        del prog
     gpu.set_sample_pass(0)
     return text
 
@@ -567,6 +614,8 @@ for name, w, h, depth in cases:
             denoise_line = time_denoise(gpu, cam, depth)
         if args.film and rep == 0:
             film_line = time_film(gpu, cam, depth)
+        if args.robust and rep == 0:
+            robust_line = time_robust(gpu, cam, depth)
         if args.check and rep == 0 and not args.sampling and args.passes < 0:
             import numpy as np, oracle_binding as ob
             step = max(1, h // 24)
@@ -609,6 +658,8 @@ for name, w, h, depth in cases:
         line += denoise_line
     if args.film:
         line += film_line
+    if args.robust:
+        line += robust_line
     if args.adaptive:
         line += time_adaptive(hs, table, cam, depth)
     out.append(line)
