@@ -24,6 +24,7 @@
 #   tests/build/libskylight_oracle.so            test infrastructure only: the sky-light checker (tests/cpp/skylight_oracle.cpp)
 #   tests/build/libindirect_oracle.so            test infrastructure only: the indirect-light checker (tests/cpp/indirect_oracle.cpp)
 #   tests/build/libemitters_oracle.so            test infrastructure only: the emitter-sampling checker (tests/cpp/emitters_oracle.cpp)
+#   tests/build/libmis_oracle.so                 test infrastructure only: the multiple-importance-sampling checker (tests/cpp/mis_oracle.cpp)
 #   tests/build/libdenoise_oracle.so             test infrastructure only: the denoiser's checker (tests/cpp/denoise_oracle.cpp)
 #   tests/build/libfilm_oracle.so                test infrastructure only: the film stage's checker (tests/cpp/film_oracle.cpp)
 #   tests/build/librobust_oracle.so              test infrastructure only: robust accumulation's checker (tests/cpp/robust_oracle.cpp)
@@ -58,7 +59,7 @@ checker: tests/build/libarea_oracle.so tests/build/libcamera_oracle.so tests/bui
          tests/build/libtorus_oracle.so tests/build/libtorus_bounds.so tests/build/libmeshuv_oracle.so tests/build/meshuv_kat \
          tests/build/libgloss_oracle.so tests/build/liboccl_oracle.so tests/build/libsfilter_oracle.so \
          tests/build/libmedia_oracle.so tests/build/libenvironment_oracle.so tests/build/libskylight_oracle.so \
-         tests/build/libindirect_oracle.so tests/build/libemitters_oracle.so tests/build/libdenoise_oracle.so \
+         tests/build/libindirect_oracle.so tests/build/libemitters_oracle.so tests/build/libmis_oracle.so tests/build/libdenoise_oracle.so \
          tests/build/libfilm_oracle.so tests/build/librobust_oracle.so
 tests/build/libarea_oracle.so: tests/cpp/area_oracle.cpp oracle/oracle_capi.cpp oracle/rtc_oracle.hpp oracle/rtc_oracle_scene.hpp include/rtc.h
 	mkdir -p tests/build
@@ -127,6 +128,10 @@ tests/build/libindirect_oracle.so: tests/cpp/indirect_oracle.cpp tests/cpp/skyli
 tests/build/libemitters_oracle.so: tests/cpp/emitters_oracle.cpp tests/cpp/indirect_oracle.cpp tests/cpp/skylight_oracle.cpp tests/cpp/environment_oracle.cpp tests/cpp/media_oracle.cpp tests/cpp/sfilter_oracle.cpp tests/cpp/occlusion_oracle.cpp tests/cpp/gloss_oracle.cpp tests/cpp/meshuv_oracle.cpp tests/cpp/torus_oracle.cpp tests/cpp/bump_oracle.cpp tests/cpp/spot_oracle.cpp tests/cpp/motion_oracle.cpp tests/cpp/camera_oracle.cpp tests/cpp/area_oracle.cpp oracle/oracle_capi.cpp oracle/rtc_oracle.hpp oracle/rtc_oracle_scene.hpp include/rtc.h
 	mkdir -p tests/build
 	$(CXX) -std=c++17 -O3 -ffp-contract=off -fPIC -Wall -Wextra -Wno-subobject-linkage -pthread -shared -o $@ tests/cpp/emitters_oracle.cpp
+# (the MIS checker includes the emitter-sampling checker, read-only)
+tests/build/libmis_oracle.so: tests/cpp/mis_oracle.cpp tests/cpp/emitters_oracle.cpp tests/cpp/indirect_oracle.cpp tests/cpp/skylight_oracle.cpp tests/cpp/environment_oracle.cpp tests/cpp/media_oracle.cpp tests/cpp/sfilter_oracle.cpp tests/cpp/occlusion_oracle.cpp tests/cpp/gloss_oracle.cpp tests/cpp/meshuv_oracle.cpp tests/cpp/torus_oracle.cpp tests/cpp/bump_oracle.cpp tests/cpp/spot_oracle.cpp tests/cpp/motion_oracle.cpp tests/cpp/camera_oracle.cpp tests/cpp/area_oracle.cpp oracle/oracle_capi.cpp oracle/rtc_oracle.hpp oracle/rtc_oracle_scene.hpp include/rtc.h
+	mkdir -p tests/build
+	$(CXX) -std=c++17 -O3 -ffp-contract=off -fPIC -Wall -Wextra -Wno-subobject-linkage -pthread -shared -o $@ tests/cpp/mis_oracle.cpp
 # (the denoiser's checker: include/rtc.h's contract as plain loops in doubles; it links nothing of the product)
 tests/build/libdenoise_oracle.so: tests/cpp/denoise_oracle.cpp
 	mkdir -p tests/build
@@ -153,7 +158,7 @@ $(LIB):
 
 # (the compiler's resource-usage remarks of the product build are kept: lib/kernel_resources.json - registers, spills,
 # scratch bytes per lane, LDS of every kernel - is what bench.py quotes as roofline.scratch_bytes_per_lane)
-# (the motion kernels, rtc_motion.hip, the spot kernels, rtc_spot.hip, the bump kernels, rtc_bump.hip, the torus kernels, rtc_torus.hip, the meshuv kernels, rtc_meshuv.hip, the gloss kernels, rtc_gloss.hip, the occlusion kernels, rtc_occlusion.hip, the shadow-filter kernels, rtc_shadowfilter.hip, the media kernels, rtc_media.hip, the environment kernels, rtc_environment.hip, the sky-light kernels, rtc_skylight.hip, the indirect kernels, rtc_indirect.hip, and the emitter kernels, rtc_emitters.hip, are render_body
+# (the motion kernels, rtc_motion.hip, the spot kernels, rtc_spot.hip, the bump kernels, rtc_bump.hip, the torus kernels, rtc_torus.hip, the meshuv kernels, rtc_meshuv.hip, the gloss kernels, rtc_gloss.hip, the occlusion kernels, rtc_occlusion.hip, the shadow-filter kernels, rtc_shadowfilter.hip, the media kernels, rtc_media.hip, the environment kernels, rtc_environment.hip, the sky-light kernels, rtc_skylight.hip, the indirect kernels, rtc_indirect.hip, the emitter kernels, rtc_emitters.hip, and the MIS kernels, rtc_mis.hip, are render_body
 # of rtc_kernels.hip in translation units of their own: the file of every other kernel compiles as before; the JSON holds the kernels of all)
 $(LIB)/rtc_kernels.o: $(PKG)/csrc/rtc_kernels.hip $(PKG)/csrc/rtc_device.h | $(LIB)
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o $@ $< 2> $(LIB)/rtc_kernels.remarks || (grep -v "remark:" $(LIB)/rtc_kernels.remarks >&2; exit 1)
@@ -211,14 +216,18 @@ $(LIB)/rtc_emitters.o: $(PKG)/csrc/rtc_emitters.hip $(PKG)/csrc/rtc_kernels.hip 
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o $@ $< 2> $(LIB)/rtc_emitters.remarks || (grep -v "remark:" $(LIB)/rtc_emitters.remarks >&2; exit 1)
 	@grep -v "remark:\|remarks generated\|\^\|^ *[0-9]* |" $(LIB)/rtc_emitters.remarks >&2 || true
 
+$(LIB)/rtc_mis.o: $(PKG)/csrc/rtc_mis.hip $(PKG)/csrc/rtc_kernels.hip $(PKG)/csrc/rtc_device.h | $(LIB)
+	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o $@ $< 2> $(LIB)/rtc_mis.remarks || (grep -v "remark:" $(LIB)/rtc_mis.remarks >&2; exit 1)
+	@grep -v "remark:\|remarks generated\|\^\|^ *[0-9]* |" $(LIB)/rtc_mis.remarks >&2 || true
+
 # (rtc_kernels_ext.hip: in the -DRTC_PROFILE diagnostic build the csg / texture-map, flat and area-light kernels, in a
 # unit of their own so that the instrumented render kernels do not compile in one; in the product build it holds none)
 $(LIB)/rtc_kernels_ext.o: $(PKG)/csrc/rtc_kernels_ext.hip $(PKG)/csrc/rtc_kernels.hip $(PKG)/csrc/rtc_device.h | $(LIB)
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o $@ $< 2> $(LIB)/rtc_kernels_ext.remarks || (grep -v "remark:" $(LIB)/rtc_kernels_ext.remarks >&2; exit 1)
 	@grep -v "remark:\|remarks generated\|\^\|^ *[0-9]* |" $(LIB)/rtc_kernels_ext.remarks >&2 || true
 
-$(LIB)/kernel_resources.json: $(LIB)/rtc_kernels.o $(LIB)/rtc_kernels_ext.o $(LIB)/rtc_motion.o $(LIB)/rtc_spot.o $(LIB)/rtc_bump.o $(LIB)/rtc_torus.o $(LIB)/rtc_meshuv.o $(LIB)/rtc_gloss.o $(LIB)/rtc_occlusion.o $(LIB)/rtc_shadowfilter.o $(LIB)/rtc_media.o $(LIB)/rtc_environment.o $(LIB)/rtc_skylight.o $(LIB)/rtc_indirect.o $(LIB)/rtc_emitters.o $(LIB)/rtc_denoise.o $(LIB)/rtc_film.o $(LIB)/rtc_robust.o tools/kernel_resources.py
-	cat $(LIB)/rtc_kernels.remarks $(LIB)/rtc_kernels_ext.remarks $(LIB)/rtc_motion.remarks $(LIB)/rtc_spot.remarks $(LIB)/rtc_bump.remarks $(LIB)/rtc_torus.remarks $(LIB)/rtc_meshuv.remarks $(LIB)/rtc_gloss.remarks $(LIB)/rtc_occlusion.remarks $(LIB)/rtc_shadowfilter.remarks $(LIB)/rtc_media.remarks $(LIB)/rtc_environment.remarks $(LIB)/rtc_skylight.remarks $(LIB)/rtc_indirect.remarks $(LIB)/rtc_emitters.remarks $(LIB)/rtc_denoise.remarks $(LIB)/rtc_film.remarks $(LIB)/rtc_robust.remarks > $(LIB)/render_kernels.remarks
+$(LIB)/kernel_resources.json: $(LIB)/rtc_kernels.o $(LIB)/rtc_kernels_ext.o $(LIB)/rtc_motion.o $(LIB)/rtc_spot.o $(LIB)/rtc_bump.o $(LIB)/rtc_torus.o $(LIB)/rtc_meshuv.o $(LIB)/rtc_gloss.o $(LIB)/rtc_occlusion.o $(LIB)/rtc_shadowfilter.o $(LIB)/rtc_media.o $(LIB)/rtc_environment.o $(LIB)/rtc_skylight.o $(LIB)/rtc_indirect.o $(LIB)/rtc_emitters.o $(LIB)/rtc_mis.o $(LIB)/rtc_denoise.o $(LIB)/rtc_film.o $(LIB)/rtc_robust.o tools/kernel_resources.py
+	cat $(LIB)/rtc_kernels.remarks $(LIB)/rtc_kernels_ext.remarks $(LIB)/rtc_motion.remarks $(LIB)/rtc_spot.remarks $(LIB)/rtc_bump.remarks $(LIB)/rtc_torus.remarks $(LIB)/rtc_meshuv.remarks $(LIB)/rtc_gloss.remarks $(LIB)/rtc_occlusion.remarks $(LIB)/rtc_shadowfilter.remarks $(LIB)/rtc_media.remarks $(LIB)/rtc_environment.remarks $(LIB)/rtc_skylight.remarks $(LIB)/rtc_indirect.remarks $(LIB)/rtc_emitters.remarks $(LIB)/rtc_mis.remarks $(LIB)/rtc_denoise.remarks $(LIB)/rtc_film.remarks $(LIB)/rtc_robust.remarks > $(LIB)/render_kernels.remarks
 	python3 tools/kernel_resources.py --from-remarks $(LIB)/render_kernels.remarks --json $@
 
 $(LIB)/rtc_capi.o: $(PKG)/csrc/rtc_capi.hip $(wildcard $(PKG)/csrc/*.h) include/rtc.h | $(LIB)
@@ -247,7 +256,7 @@ $(LIB)/rtc_robust.o: $(PKG)/csrc/rtc_robust.hip include/rtc.h | $(LIB)
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o $@ $< 2> $(LIB)/rtc_robust.remarks || (grep -v "remark:" $(LIB)/rtc_robust.remarks >&2; exit 1)
 	@grep -v "remark:\|remarks generated\|\^\|^ *[0-9]* |" $(LIB)/rtc_robust.remarks >&2 || true
 
-$(LIB)/librtc_hip.so: $(LIB)/rtc_kernels.o $(LIB)/rtc_kernels_ext.o $(LIB)/rtc_motion.o $(LIB)/rtc_spot.o $(LIB)/rtc_bump.o $(LIB)/rtc_torus.o $(LIB)/rtc_meshuv.o $(LIB)/rtc_gloss.o $(LIB)/rtc_occlusion.o $(LIB)/rtc_shadowfilter.o $(LIB)/rtc_media.o $(LIB)/rtc_environment.o $(LIB)/rtc_skylight.o $(LIB)/rtc_indirect.o $(LIB)/rtc_emitters.o $(LIB)/rtc_capi.o $(LIB)/rtc_accum.o $(LIB)/rtc_adaptive.o $(LIB)/rtc_denoise.o $(LIB)/rtc_film.o $(LIB)/rtc_robust.o | $(LIB)/kernel_resources.json
+$(LIB)/librtc_hip.so: $(LIB)/rtc_kernels.o $(LIB)/rtc_kernels_ext.o $(LIB)/rtc_motion.o $(LIB)/rtc_spot.o $(LIB)/rtc_bump.o $(LIB)/rtc_torus.o $(LIB)/rtc_meshuv.o $(LIB)/rtc_gloss.o $(LIB)/rtc_occlusion.o $(LIB)/rtc_shadowfilter.o $(LIB)/rtc_media.o $(LIB)/rtc_environment.o $(LIB)/rtc_skylight.o $(LIB)/rtc_indirect.o $(LIB)/rtc_emitters.o $(LIB)/rtc_mis.o $(LIB)/rtc_capi.o $(LIB)/rtc_accum.o $(LIB)/rtc_adaptive.o $(LIB)/rtc_denoise.o $(LIB)/rtc_film.o $(LIB)/rtc_robust.o | $(LIB)/kernel_resources.json
 	$(HIPCC) --offload-arch=gfx950 -shared -fPIC -o $@ $^
 
 $(LIB)/librtc_multi.so: $(PKG)/csrc/rtc_multi.hip include/rtc_multi.h include/rtc.h $(LIB)/librtc_hip.so

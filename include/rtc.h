@@ -969,6 +969,53 @@ typedef struct rtc_emitters {
  */
 int rtc_scene_set_emitters(rtc_scene *scene, const rtc_emitters *emitters);
 
+/* ---- multiple importance sampling of emitter samples and bounce rays ---- */
+/*
+ * At a hit that draws emitter samples two strategies find the light of a listed emitter: the `samples` emitter samples and
+ * the one cosine-weighted diffuse child.  With mode 0 they are combined by a switch - the samples take all of it, the child
+ * adds nothing where it meets a listed leaf (above).  With mode 1 each is weighted by the balance heuristic (Veach and Guibas
+ * 1995): the expectation stays, and what one pass returns is bounded.  Notation as above: n = samples as a double; q the
+ * entry's W / ((E.r + E.g) + E.b) - the area density of a point of any entry of that material is 1 / q -; for one direction
+ *   a = q * (cos_s * cos_e);   b = n * (RTC_PI * r2);   w_e = b / (b + a);   w_b = a / (b + a)
+ * with cos_s the cosine at the shaded point.  This is n / (n + rho) and rho / (n + rho) with rho = a / (RTC_PI * r2) =
+ * p_bounce / p_emitter in solid angle, in a form that divides by no vanishing r2 and forms no rho; the skip rules below keep
+ * r2 > 4e-8, so b > 0 and b + a > 0.  Both weights divide by the one sum b + a: w_e + w_b = 1 within a rounding of each.
+ *
+ * Emitter sample (mode 1, list not empty).  cos_s = cos_x, cos_e and r2 as in the sample step; the skip rules - cos_x <= 0,
+ * cos_e == 0, r <= 2e-4 -, the walk, the filters, the media factor and the counters are as they were;
+ *   term.c = ((((E.c * q) * ((cos_x * cos_e) / (RTC_PI * r2))) * w_e) * F.c),  with media times T.c as before.
+ *
+ * Diffuse child.  Where the child is formed, cos_b = (dir.x ng.x + dir.y ng.y) + dir.z ng.z, its direction against the normal
+ * it was drawn about; the value travels with the ray.  At that ray's hit - a ray that was formed as a diffuse child, not its
+ * descendants - on a leaf of the list (mode 1), at parameter t along dir:
+ *   the face: a triangle's, plain or smooth, is its one entry.  A cube's is the reference's rule for cube normals on the
+ *     object-space hit point lp = I * (origin + dir * t): m = max(|lp.x|, max(|lp.y|, |lp.z|)); the x faces where m == |lp.x|,
+ *     else the y faces where m == |lp.y|, else the z faces; of the pair, the negative face where that coordinate < 0.
+ *   n_face, q: the unit normal n and the q that the list stores for that face's entry - the flat geometric normal, not a
+ *     smooth triangle's interpolated one.  A face the list leaves out (w not finite or not above zero) is not sampled: w_b = 1.
+ *   cos_e' = |(n_face.x dir.x + n_face.y dir.y) + n_face.z dir.z|;   r2 = t * t;   cos_s = cos_b
+ *   where cos_b <= 0, cos_e' == 0 or t <= 2e-4 - where the sample step returns zero for this direction - w_b = 1
+ *   s.c = s.c + E.c * w_b                      in the place of the emission row
+ * Unlisted emissive leaves - spheres, cylinders, cones, tori, planes, csg leaves, filtered leaves - add their whole row, and
+ * every other ray - primary, reflected, refracted - adds emission as before.
+ *
+ * The bound.  With mode 1 the light one hit takes from listed emitters - the mean of its samples plus its child's weighted
+ * emission - is at most (n + 1) * max_c E.c, times color.c * material.diffuse * gain:  per sample
+ * E.c * q * (cos_x cos_e / (pi r2)) * w_e = E.c * rho * n / (n + rho) <= n * E.c, so the mean of n is at most n * E.c;  the
+ * child adds E.c * w_b <= E.c;  every filter and transmittance is <= 1.  With mode 0 there is no bound as r -> 0.
+ *
+ * Only + - * / and comparisons are added, each correctly rounded, in the order written, with no fused multiply-add.
+ */
+/*
+ * This handle's combination of emitter samples and diffuse children: 0 - the switch, the default: every render is what it was,
+ * bit for bit -, 1 - the balance heuristic.  Any other value: RTC_ERR_INVALID_ARGUMENT, refused before any HIP call, the
+ * previous mode stays.  The mode has an effect only while the derived emitter list is not empty, whatever the order of this
+ * setter, rtc_scene_set_emitters, rtc_scene_set_indirect and rtc_scene_set_shadow_filters; then the MIS kernels run
+ * (rtc_render_kernel_mis, _mis_bigworld).  A clone starts with its source's mode; rtc_render's band clones follow.
+ * librtc_multi renders without it.  rtc_scene_desc, rtc_camera, rtc_stats, rtc_emitters and RTC_ABI_VERSION are as they were.
+ */
+int rtc_scene_set_emitter_mis(rtc_scene *scene, uint32_t mode);
+
 /* ---- adaptive sampling: progressive passes only for tiles still noisy ---- */
 #define RTC_ADAPTIVE_MAX_TILE 1024u
 

@@ -52,7 +52,8 @@ extern "C" {
  * ordinary kernels'), "indirect_kernels" (!= 0: the indirect kernels even on a handle without an indirect table, the gain
  * zero and no emission, so that their images can be held to the handle's ordinary kernels'), "emitter_kernels" (!= 0: the
  * emitter kernels even on a handle without an emitter list, the count zero, so that their images can be held to the handle's
- * ordinary kernels'), "denoise_naive" (!= 0: rtc_denoise_device runs rtc_denoise_naive_kernel, the literal form of rtc.h's
+ * ordinary kernels'), "mis_kernels" (!= 0: the MIS kernels even on a handle whose MIS mode is 0 or whose emitter list is
+ * empty, the mode zero, so that their images can be held to the handle's ordinary kernels'), "denoise_naive" (!= 0: rtc_denoise_device runs rtc_denoise_naive_kernel, the literal form of rtc.h's
  * loops with one thread per pixel, in place of the tiled kernels, so that the two can be held to each other and timed
  * against each other; the bits are the same), "film_naive" (!= 0: a rtc_film_device that blooms runs rtc_film_naive_row_kernel
  * and rtc_film_naive_resolve_kernel, the literal forms of rtc.h's loops with one thread per pixel and no LDS, in place of the
@@ -102,6 +103,13 @@ int rtc_diag_emitters(const rtc_scene_desc *desc, const double *emission, const 
                       double *cdf, uint32_t *count);
 /* Diagnostic: the entry the kernels' search picks for the draw u0 from a CDF of `count` >= 1 entries, W = cdf[count - 1]. */
 int rtc_diag_emitter_pick(const double *cdf, uint32_t count, double u0, uint32_t *entry);
+/* Diagnostic (tests/test_mis_cpu.py): the two weights of rtc_scene_set_emitter_mis' balance heuristic (rtc.h, DESIGN.md section
+ * 32) for one direction, on the host with the kernels' own expression: `samples` = n (1 .. RTC_EMITTER_MAX_SAMPLES), `q` the
+ * entry's W / (E.r + E.g + E.b), `cos_s` the cosine at the shaded point (cos_x of a sample, cos_b of a child), `cos_e` the
+ * cosine at the emitter (its absolute value already taken), `r` the distance.  Where a skip rule holds - cos_s <= 0,
+ * cos_e == 0 or r <= 2e-4 - *w_e = 0 and *w_b = 1; else *w_e = b / (b + a) and *w_b = a / (b + a), a = q * (cos_s * cos_e),
+ * b = n * (RTC_PI * (r * r)).  RTC_ERR_INVALID_ARGUMENT for a NULL pointer or `samples` outside its range. */
+int rtc_diag_mis_weights(uint32_t samples, double q, double cos_s, double cos_e, double r, double *w_e, double *w_b);
 
 /* Diagnostic (tests/test_root_boxes_cpu.py): the FP32 world boxes phase 1 of the render kernels' root loop tests
  * (DESIGN.md section 3), as rtc_scene_create builds them, without a device: per table position i (the tables are sorted

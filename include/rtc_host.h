@@ -29,7 +29,8 @@
  *                        rtch_scene_environment, through rtc_scene_set_environment; its sky light,
  *                        rtch_scene_sky_light, through rtc_scene_set_sky_light; its indirect light,
  *                        rtch_scene_indirect, through rtc_scene_set_indirect; its emitter sampling,
- *                        rtch_scene_emitters, through rtc_scene_set_emitters; its denoiser, rtch_scene_denoise,
+ *                        rtch_scene_emitters, through rtc_scene_set_emitters, and its MIS mode, rtch_scene_emitter_mis,
+ *                        through rtc_scene_set_emitter_mis; its denoiser, rtch_scene_denoise,
  *                        through rtc_render_denoised; its film stage, rtch_scene_film, through rtc_render_filmed;
  *                        its robust accumulation, rtch_scene_robust, through rtc_render_robust)
  *
@@ -160,6 +161,10 @@ int rtch_scene_indirect(void *handle, rtc_indirect *out, double *emission, int *
  * defaults to 1, seed to 0 -, as rtc_scene_set_emitters takes it.  *present: 1 when the file has the key and it is not false;
  * without it *out is samples 1, seed 0.  The key adds no table row.  rtch_scene_render applies it, after the indirect table. */
 int rtch_scene_emitters(void *handle, rtc_emitters *out, int *present);
+/* The "mis" key inside the object form of the scene's "emitters" (DESIGN.md section 32): true | false, as
+ * rtc_scene_set_emitter_mis takes it - *mode is 1 where the file has the key and it is true, else 0 (false: as without the key).
+ * The key adds no table row.  rtch_scene_render applies it, after the emitter table. */
+int rtch_scene_emitter_mis(void *handle, uint32_t *mode);
 int rtch_scene_camera(void *handle, uint32_t width, uint32_t height, rtc_camera *out);
 int rtch_camera_rotate(void *handle, double angle);
 int rtch_camera_move(void *handle, double distance);

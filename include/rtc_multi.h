@@ -50,7 +50,8 @@ typedef struct rtc_multi rtc_multi; /* opaque: per frame slot n scene handles an
  * rtc_scene_set_media: it renders without media, no material absorbing and no fog; nor has rtc_scene_set_environment: it
  * renders without an environment, every miss black and no sun; nor has rtc_scene_set_sky_light: it renders without a sky
  * light; nor has rtc_scene_set_indirect: it renders without indirect light, no diffuse child and no emission; nor has
- * rtc_scene_set_emitters: it renders without emitter sampling. */
+ * rtc_scene_set_emitters: it renders without emitter sampling; nor has rtc_scene_set_emitter_mis, which acts on emitter samples
+ * alone. */
 int rtc_multi_create(const rtc_scene_desc *desc, uint32_t n_gpus, uint32_t flags, rtc_multi **out);
 void rtc_multi_destroy(rtc_multi *m);
 

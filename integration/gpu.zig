@@ -125,6 +125,9 @@ pub const RtcEmitters = extern struct {
     seed: u64,
 };
 pub extern fn rtc_scene_set_emitters(scene: *RtcScene, emitters: ?*const RtcEmitters) c_int; // null: no table
+// Multiple importance sampling (rtc.h, rtc_scene_set_emitter_mis): 0 - the emitter samples take all the light of listed
+// emitters, the default -, 1 - the samples and the diffuse child are weighted by the balance heuristic; anything else is refused.
+pub extern fn rtc_scene_set_emitter_mis(scene: *RtcScene, mode: u32) c_int;
 // The denoiser (rtc.h, rtc_denoise_device): variance-guided non-local means over an accumulated image - the mean and the sums
 // of squares of rtc_scene_accumulate_device or of an adaptive run; no scene is needed.  rtc_render_denoised is the whole path:
 // passes (or an adaptive run, RtcAdaptive), the filter, both images to the host.

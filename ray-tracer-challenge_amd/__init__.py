@@ -311,7 +311,7 @@ RTC_SPHERE, RTC_PLANE, RTC_CUBE, RTC_CYLINDER, RTC_TRIANGLE, RTC_SMOOTH_TRIANGLE
 # the options that select a kernel family on a handle that does not need it (set_option; tests and tools/time_scenes.py)
 KERNEL_OPTIONS = ("sampling_kernels", "motion_kernels", "spot_kernels", "bump_kernels", "torus_kernels", "meshuv_kernels", "gloss_kernels",
                   "occlusion_kernels", "shadow_filter_kernels", "media_kernels", "environment_kernels", "sky_light_kernels",
-                  "indirect_kernels", "emitter_kernels")
+                  "indirect_kernels", "emitter_kernels", "mis_kernels")
 MAX_EMITTERS, EMITTER_MAX_SAMPLES, EMITTER_ROW = 4096, 16, 18  # RTC_MAX_EMITTERS, RTC_EMITTER_MAX_SAMPLES; rtc_diag_emitters' row
 SKY_LIGHT_MAX_SAMPLES = 64  # RTC_SKY_LIGHT_MAX_SAMPLES
 ENV_NO_PATTERN, ENV_SPHERE, ENV_CUBE, ENV_MAX_SUNS = 0xFFFFFFFF, 0, 1, 16  # RTC_ENV_*
@@ -518,6 +518,17 @@ def diag_emitter_pick(cdf, u0):
     return int(k.value)
 
 
+def diag_mis_weights(samples, q, cos_s, cos_e, r):
+    """rtc_diag_mis_weights: (w_e, w_b), the balance heuristic's weights of rtc_scene_set_emitter_mis for one direction, by the
+    kernels' own expression: `samples` emitter samples per hit, the entry's q, the cosine at the shaded point, the cosine at
+    the emitter and the distance; (0, 1) where a skip rule of the sample step holds"""
+    w_e, w_b = C.c_double(), C.c_double()
+    lib = hip_lib()
+    lib.rtc_diag_mis_weights.argtypes = [C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_double, _dp, _dp]
+    _check_hip(lib.rtc_diag_mis_weights(int(samples), float(q), float(cos_s), float(cos_e), float(r), C.byref(w_e), C.byref(w_b)))
+    return float(w_e.value), float(w_b.value)
+
+
 class Bump(C.Structure):
     """struct rtc_bump (include/rtc.h): a bump per material row (kind BUMP_NONE: the material as it is)."""
 
@@ -560,18 +571,18 @@ RTC_SYMBOLS = ["rtc_scene_create", "rtc_scene_clone", "rtc_scene_destroy", "rtc_
                "rtc_scene_adaptive_begin_device", "rtc_scene_adaptive_accumulate_device", "rtc_scene_adaptive_step", "rtc_render_adaptive",
                "rtc_scene_set_spots", "rtc_scene_set_bumps", "rtc_scene_set_mesh_uvs", "rtc_scene_set_gloss",
                "rtc_scene_set_occlusion", "rtc_scene_set_shadow_filters", "rtc_scene_set_media", "rtc_scene_set_environment",
-               "rtc_scene_set_sky_light", "rtc_scene_set_indirect", "rtc_scene_set_emitters", "rtc_denoise_device",
+               "rtc_scene_set_sky_light", "rtc_scene_set_indirect", "rtc_scene_set_emitters", "rtc_scene_set_emitter_mis", "rtc_denoise_device",
                "rtc_render_denoised", "rtc_film_scratch_bytes", "rtc_film_device", "rtc_render_filmed", "rtc_robust_device",
                "rtc_render_robust"]
 # (... and include/rtc_diag.h: diagnostics and tuning, for the tests, bench.py and tools/)
-RTC_DIAG_SYMBOLS = ["rtc_set_option", "rtc_last_kernel_name", "rtc_get_schedule", "rtc_get_chunk_times", "rtc_diag_build_tables", "rtc_diag_root_boxes", "rtc_diag_root_spheres", "rtc_diag_emitters", "rtc_diag_emitter_pick",
+RTC_DIAG_SYMBOLS = ["rtc_set_option", "rtc_last_kernel_name", "rtc_get_schedule", "rtc_get_chunk_times", "rtc_diag_build_tables", "rtc_diag_root_boxes", "rtc_diag_root_spheres", "rtc_diag_emitters", "rtc_diag_emitter_pick", "rtc_diag_mis_weights",
                     "rtc_diag_root_flags", "rtc_diag_denoise_tile", "rtc_diag_film_tile", "rtc_diag_robust_grid"]
 HOST_SYMBOLS = ["rtch_last_error", "rtch_scene_load", "rtch_scene_free", "rtch_scene_desc", "rtch_scene_camera",
                 "rtch_camera_rotate", "rtch_camera_move", "rtch_camera_make", "rtch_canvas_ppm", "rtch_canvas_rgba8", "rtch_scene_render", "rtch_set_loader_threads",
                 "rtch_scene_lights", "rtch_scene_sampling", "rtch_scene_passes", "rtch_scene_motion", "rtch_scene_adaptive",
                 "rtch_scene_spots", "rtch_scene_bumps", "rtch_scene_mesh_uvs", "rtch_scene_gloss", "rtch_scene_occlusion",
                 "rtch_scene_shadow_filters", "rtch_scene_media", "rtch_scene_environment", "rtch_scene_sky_light",
-                "rtch_scene_indirect", "rtch_scene_emitters", "rtch_scene_denoise", "rtch_scene_film", "rtch_scene_robust"]
+                "rtch_scene_indirect", "rtch_scene_emitters", "rtch_scene_emitter_mis", "rtch_scene_denoise", "rtch_scene_film", "rtch_scene_robust"]
 
 MULTI_SYMBOLS = ["rtc_multi_create", "rtc_multi_destroy", "rtc_multi_render", "rtc_multi_render_rgba8", "rtc_multi_render_device", "rtc_multi_render_rgba8_device",
                  "rtc_multi_synchronize", "rtc_multi_stream", "rtc_multi_get_stats", "rtc_multi_balance", "rtc_multi_last_error"]
@@ -642,6 +653,7 @@ def hip_lib():
         lib.rtc_scene_set_sky_light.argtypes = [C.c_void_p, C.POINTER(SkyLight)]
         lib.rtc_scene_set_indirect.argtypes = [C.c_void_p, C.POINTER(Indirect)]
         lib.rtc_scene_set_emitters.argtypes = [C.c_void_p, C.POINTER(Emitters)]
+        lib.rtc_scene_set_emitter_mis.argtypes = [C.c_void_p, C.c_uint32]
         lib.rtc_diag_emitters.argtypes = [C.POINTER(SceneDesc), _dp, _dp, C.c_uint32, _dp, _dp, C.POINTER(C.c_uint32)]
         lib.rtc_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.POINTER(Adaptive), C.c_void_p, C.c_void_p]
         lib.rtc_denoise_device.argtypes = [C.POINTER(Denoise), C.c_void_p]
@@ -721,6 +733,7 @@ def host_lib():
         lib.rtch_scene_sky_light.argtypes = [C.c_void_p, C.POINTER(SkyLight), C.POINTER(C.c_int)]
         lib.rtch_scene_indirect.argtypes = [C.c_void_p, C.POINTER(Indirect), _dp, C.POINTER(C.c_int), C.c_uint32]
         lib.rtch_scene_emitters.argtypes = [C.c_void_p, C.POINTER(Emitters), C.POINTER(C.c_int)]
+        lib.rtch_scene_emitter_mis.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         lib.rtch_scene_adaptive.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(Adaptive)]
         lib.rtch_scene_denoise.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(DenoiseSetting)]
         lib.rtch_scene_film.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(FilmSetting)]
@@ -1007,6 +1020,13 @@ class HostScene:
             return None
         return {"samples": int(e.samples), "seed": int(e.seed)}
 
+    def emitter_mis(self):
+        """The "mis" key inside the scene's "emitters" (rtch_scene_emitter_mis): 1 where the file has it and it is true, else 0 -
+        what GpuScene.set_emitter_mis takes."""
+        mode = C.c_uint32()
+        _check_host(host_lib().rtch_scene_emitter_mis(self._h, C.byref(mode)))
+        return int(mode.value)
+
     def adaptive(self):
         """The camera's "sampling": {"adaptive": ...} of the scene file (rtch_scene_adaptive): an Adaptive whose max_passes
         is "passes", or None when the file has none."""
@@ -1218,6 +1238,12 @@ class GpuScene:
             return
         e = emitters_struct(emitters)
         _check_hip(hip_lib().rtc_scene_set_emitters(self._s, C.byref(e)))
+
+    def set_emitter_mis(self, mode):
+        """rtc_scene_set_emitter_mis: False / 0 - emitter samples and diffuse children combined by a switch, the default -,
+        True / 1 - weighted by the balance heuristic (HostScene.emitter_mis()).  It has an effect while the handle's derived
+        emitter list is not empty, whatever the order of the setters."""
+        _check_hip(hip_lib().rtc_scene_set_emitter_mis(self._s, int(mode)))
 
     def accumulate_device(self, accum, stream=None):
         """rtc_scene_accumulate_device: an Accum, enqueued on `stream` (None: the handle's own) after this handle's renders."""

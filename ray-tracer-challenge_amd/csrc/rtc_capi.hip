@@ -258,6 +258,22 @@ __global__ void rtc_render_kernel_emit_bigworld(const DevScene S, const DevCamer
                                                 const DevShadowFilter sfilt, const DevMedia media, const DevEnvironment env,
                                                 const DevSkyLight skyl, const DevIndirect indir, const DevEmitters emit);
 }
+// The MIS kernels (rtc_scene_set_emitter_mis: emitter samples and diffuse children weighted by the balance heuristic): the
+// emitter kernels' tables and stack, and the mode, the per-leaf entry words and the carry buffer (DevMis) as one more argument.
+extern "C" {
+__global__ void rtc_render_kernel_mis(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                      double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                      const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                      const DevBumps bumps, const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl,
+                                      const DevShadowFilter sfilt, const DevMedia media, const DevEnvironment env,
+                                      const DevSkyLight skyl, const DevIndirect indir, const DevEmitters emit, const DevMis mis);
+__global__ void rtc_render_kernel_mis_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                                               double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                                               const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                                               const DevBumps bumps, const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl,
+                                               const DevShadowFilter sfilt, const DevMedia media, const DevEnvironment env,
+                                               const DevSkyLight skyl, const DevIndirect indir, const DevEmitters emit, const DevMis mis);
+}
 // Progressive rendering's accumulation (rtc_accum.hip): the grid's blocks for n pixels (the noise partials it writes, at
 // most) and the enqueue of its kernels.
 uint32_t rtcAccumBlocks(size_t n_pixels, bool wide);
@@ -487,6 +503,10 @@ bool tablesInLds(const rtc_scene* s) {
 // cleared, and a clone or a band clone, which holds its source's tables and flags, selects what its source does.
 Family family(const rtc_scene* s) {
   const RtcOptions& o = rtcOptions();
+  // The MIS kernels run when the handle's MIS mode is not 0 (rtc_scene_set_emitter_mis) and its derived emitter list is not
+  // empty - the mode has no effect without a list, so the order of the setters does not matter - or, for tests, whenever option
+  // "mis_kernels" is set.
+  if ((s->emitter_mis != 0u && s->emitters != nullptr && s->emitters->count != 0u) || o.mis_kernels != 0.0) return kFamilyMis;
   // The emitter kernels run when the list derived for the handle's emitter table is not empty (rtc_scene_set_emitters; the
   // list is derived again by rtc_scene_set_indirect and rtc_scene_set_shadow_filters, so the order of the setters does not
   // matter) - whatever else the handle holds: they are the indirect walk - or, for tests, whenever option "emitter_kernels"
@@ -565,6 +585,7 @@ struct LaunchArgs {
   DevSkyLight skyl;
   DevIndirect indir;
   DevEmitters emit;
+  DevMis mis;
 };
 // ... from the handle, for a launch of family `f` with the scene `dev` (the handle's, or its copy for an empty dispatch).
 LaunchArgs launchArgs(const rtc_scene* s, Family f, const DevScene& dev, const DevCamera& cam) {
@@ -631,6 +652,11 @@ LaunchArgs launchArgs(const rtc_scene* s, Family f, const DevScene& dev, const D
   a.emit = DevEmitters{nullptr, nullptr, nullptr, 0ull, 0.0, 0u, 1u};
   if (const EmitterTables* t = s->emitters.get())
     if (t->count != 0u) a.emit = DevEmitters{t->row.p, t->cdf.p, t->leaf_bits.p, t->key, t->total, t->count, t->samples};
+  // (the handle's MIS mode where it has a list, else mode 0: the emitter kernels' image; the carry buffer: ensureScratch
+  // sized it with the ray stack)
+  a.mis = DevMis{nullptr, nullptr, 0u};
+  if (const EmitterTables* t = s->emitters.get())
+    if (t->count != 0u && s->emitter_mis != 0u) a.mis = DevMis{t->leaf_entry.p, static_cast<double*>(s->d_mis_carry), s->emitter_mis};
   return a;
 }
 
@@ -661,6 +687,7 @@ hipError_t forFamilyKernel(const rtc_scene* s, const KernelChoice& c, const Laun
     case Family::SKYL: RTC_KERNEL_PAIR(rtc_render_kernel_skyl, a.area, a.smp, a.mo, a.spots, a.bumps, a.muv, a.gloss, a.occl, a.sfilt, a.media, a.env, a.skyl);
     case Family::INDIR: RTC_KERNEL_PAIR(rtc_render_kernel_indir, a.area, a.smp, a.mo, a.spots, a.bumps, a.muv, a.gloss, a.occl, a.sfilt, a.media, a.env, a.skyl, a.indir);
     case kFamilyEmit: RTC_KERNEL_PAIR(rtc_render_kernel_emit, a.area, a.smp, a.mo, a.spots, a.bumps, a.muv, a.gloss, a.occl, a.sfilt, a.media, a.env, a.skyl, a.indir, a.emit);
+    case kFamilyMis: RTC_KERNEL_PAIR(rtc_render_kernel_mis, a.area, a.smp, a.mo, a.spots, a.bumps, a.muv, a.gloss, a.occl, a.sfilt, a.media, a.env, a.skyl, a.indir, a.emit, a.mis);
   }
   return hipErrorInvalidValue;  // (no such family)
 }
@@ -1031,8 +1058,8 @@ int packNextSchedule(rtc_scene* s, const rtc_camera& cam, const DevPixelMap& map
 // the indirect kernels may form three and pushes at most two; every ray on the stack waits at a tree level 1 .. max_depth
 // and a level's hit is shaded once per walk down, so at most 2 * max_depth wait at once: 2 * max_depth + 2 levels.
 uint32_t rayStackLevels(const rtc_scene* s, uint32_t max_depth) {
-  const Family f = family(s);  // (the emitter kernels are the indirect walk: the same children)
-  return (f == Family::INDIR || f == kFamilyEmit) ? 2u * max_depth + 2u : max_depth + 2u;
+  const Family f = family(s);  // (the emitter and MIS kernels are the indirect walk: the same children)
+  return (f == Family::INDIR || f == kFamilyEmit || f == kFamilyMis) ? 2u * max_depth + 2u : max_depth + 2u;
 }
 
 int ensureScratch(rtc_scene* s, DevPixelMap& map, uint32_t blocks, uint32_t max_depth) {
@@ -1057,6 +1084,19 @@ int ensureScratch(rtc_scene* s, DevPixelMap& map, uint32_t blocks, uint32_t max_
       s->media_stack_capacity = 0;
       HIP_TRY(hipMalloc(&s->d_media_stack, need_x));
       s->media_stack_capacity = need_x;
+    }
+  }
+  if (family(s) == kFamilyMis) {
+    // (the MIS kernels' cos_b of every pending diffuse child, 8 bytes beside the record's 64: an eighth of the ray stack's
+    // capacity holds a slot for every slot of it, whatever the launch's depth)
+    const size_t need_c = s->ray_stack_capacity / 8u;
+    if (need_c > s->mis_carry_capacity) {
+      HIP_TRY(handleIdle(s));  // (the last launch may still be using the old buffer)
+      if (s->d_mis_carry) (void)hipFree(s->d_mis_carry);
+      s->d_mis_carry = nullptr;
+      s->mis_carry_capacity = 0;
+      HIP_TRY(hipMalloc(&s->d_mis_carry, need_c));
+      s->mis_carry_capacity = need_c;
     }
   }
   map.ray_stack = static_cast<PendingRec*>(s->d_ray_stack);
@@ -2453,6 +2493,7 @@ void emitterLeafTables(const rtc_scene_desc& d, const HostTables& T, std::vector
 struct EmitterList {
   std::vector<double> row, cdf;
   std::vector<uint32_t> leaf;
+  std::vector<uint8_t> face;  // per entry: a cube's face 0 .. 5 (+x, -x, +y, -y, +z, -z), 0 for a triangle
   double total = 0.0;
 };
 // (false: more than RTC_MAX_EMITTERS entries)
@@ -2490,7 +2531,7 @@ bool deriveEmitterList(const std::vector<uint4>& leaf_meta, const std::vector<do
       for (int i = 0; i < 3; ++i) o[i] = ((L[i][0] * p[0] + L[i][1] * p[1]) + L[i][2] * p[2]) + t[i];
     };
     const double sum_e = (E[0] + E[1]) + E[2];
-    auto add = [&](const double* o, const double* eu, const double* ev, bool half) {
+    auto add = [&](const double* o, const double* eu, const double* ev, bool half, uint8_t face) {
       double R[RTC_EMITTER_ROW] = {};
       pnt(o, R + 0);
       vec(eu, R + 3);
@@ -2512,6 +2553,7 @@ bool deriveEmitterList(const std::vector<uint4>& leaf_meta, const std::vector<do
       out.row.insert(out.row.end(), R, R + RTC_EMITTER_ROW);
       out.cdf.push_back(out.total);
       out.leaf.push_back(l);
+      out.face.push_back(face);
     };
     if (kind == RTC_CUBE) {
       for (int a = 0; a < 3; ++a)
@@ -2521,11 +2563,11 @@ bool deriveEmitterList(const std::vector<uint4>& leaf_meta, const std::vector<do
           o[a] = sgn == 0 ? 1.0 : -1.0;
           eu[b] = 2.0;
           ev[c] = 2.0;
-          add(o, eu, ev, false);
+          add(o, eu, ev, false, static_cast<uint8_t>(2 * a + sgn));
         }
     } else {
       const double* T9 = tri.data() + 9ull * m.w;
-      add(T9 + 0, T9 + 3, T9 + 6, true);
+      add(T9 + 0, T9 + 3, T9 + 6, true, 0u);
     }
     if (out.cdf.size() > RTC_MAX_EMITTERS) return false;
   }
@@ -3156,7 +3198,16 @@ static int makeEmitterTables(const rtc_scene* s, uint32_t samples, uint64_t seed
   if (t->count != 0u) {
     std::vector<uint32_t> bits((tab.h_leaf_meta.size() + 31u) / 32u, 0u);
     for (const uint32_t leaf : list.leaf) bits[leaf >> 5] |= 1u << (leaf & 31u);
+    // (DevMis::leaf_entry: a leaf's entries are consecutive; the first one's index, and a bit per face that has an entry)
+    static_assert(RTC_MAX_EMITTERS <= 0xFFFFu, "an entry index fits below RTC_MIS_FACE_SHIFT");
+    std::vector<uint32_t> words(tab.h_leaf_meta.size(), 0u);
+    for (uint32_t k = 0; k < t->count; ++k) {
+      uint32_t& w = words[list.leaf[k]];
+      if (w == 0u) w = k;
+      w |= 1u << (RTC_MIS_FACE_SHIFT + list.face[k]);
+    }
     HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(t->leaf_entry.upload(words));
     HIP_TRY(t->row.upload(list.row));
     HIP_TRY(t->cdf.upload(list.cdf));
     HIP_TRY(t->leaf_bits.upload(bits));
@@ -3179,6 +3230,16 @@ int rtc_scene_set_emitters(rtc_scene* s, const rtc_emitters* e) {
       return st;
   }
   return replaceTables(s, &rtc_scene::emitters, tables);
+}
+
+int rtc_scene_set_emitter_mis(rtc_scene* s, uint32_t mode) {
+  g_error.clear();
+  if (mode > 1u) return fail(RTC_ERR_INVALID_ARGUMENT, "emitter mis: mode %u, 0 or 1", mode);
+  if (!s) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
+  // (a value a launch takes at its enqueue: nothing on the device is replaced and nothing is waited for)
+  s->emitter_mis = mode;
+  for (rtc_scene* b : s->band) b->emitter_mis = mode;
+  return RTC_OK;
 }
 
 int rtc_scene_set_motion(rtc_scene* s, const rtc_motion* motion) {
@@ -4170,6 +4231,7 @@ int rtc_scene_clone(const rtc_scene* src, rtc_scene** out) {
   s->sky_light = src->sky_light;  // (shared: read-only once made)
   s->indirect = src->indirect;    // (shared: read-only once made)
   s->emitters = src->emitters;    // (shared: read-only once made)
+  s->emitter_mis = src->emitter_mis;
   s->simple_kernel = src->simple_kernel;
   s->flat_kernel = src->flat_kernel;
   s->simple3_ok = src->simple3_ok;
@@ -4227,6 +4289,7 @@ void rtc_scene_destroy(rtc_scene* s) {
   if (s->launch_done) (void)hipEventDestroy(s->launch_done);
   if (s->d_ray_stack) (void)hipFree(s->d_ray_stack);
   if (s->d_media_stack) (void)hipFree(s->d_media_stack);
+  if (s->d_mis_carry) (void)hipFree(s->d_mis_carry);
   if (s->d_csg_buf) (void)hipFree(s->d_csg_buf);
   if (s->d_accum_partials) (void)hipFree(s->d_accum_partials);
   if (s->d_adaptive_frame) (void)hipFree(s->d_adaptive_frame);
@@ -4553,6 +4616,17 @@ int rtc_diag_emitter_pick(const double* cdf, uint32_t count, double u0, uint32_t
   return RTC_OK;
 }
 
+int rtc_diag_mis_weights(uint32_t samples, double q, double cos_s, double cos_e, double r, double* w_e, double* w_b) {
+  g_error.clear();
+  if (!w_e || !w_b) return fail(RTC_ERR_INVALID_ARGUMENT, "null argument");
+  if (samples < 1u || samples > RTC_EMITTER_MAX_SAMPLES)
+    return fail(RTC_ERR_INVALID_ARGUMENT, "mis weights: %u samples, 1 to %u", samples, RTC_EMITTER_MAX_SAMPLES);
+  *w_e = 0.0;  // (the skip rules: the sample is zero, the child keeps the whole row)
+  *w_b = 1.0;
+  if (!(cos_s <= 0.0) && !(cos_e == 0.0) && !(r <= 2e-4)) rtc_mis_weights(static_cast<double>(samples), q, cos_s, cos_e, r * r, *w_e, *w_b);
+  return RTC_OK;
+}
+
 int rtc_diag_root_boxes(const rtc_scene_desc* desc, float* boxes, uint32_t* world_index, uint32_t capacity, uint32_t* n_roots,
                         float* scales) {
   g_error.clear();
@@ -4636,6 +4710,7 @@ int rtc_set_option(const char* name, double value) {
                {"shadow_filter_kernels", &o.shadow_filter_kernels}, {"media_kernels", &o.media_kernels},
                {"environment_kernels", &o.environment_kernels}, {"sky_light_kernels", &o.sky_light_kernels},
                {"indirect_kernels", &o.indirect_kernels}, {"emitter_kernels", &o.emitter_kernels},
+               {"mis_kernels", &o.mis_kernels},
                {"denoise_naive", &o.denoise_naive}, {"film_naive", &o.film_naive},
                {"robust_naive", &o.robust_naive}};
   for (const auto& e : table)

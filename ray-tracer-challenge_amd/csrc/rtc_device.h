@@ -496,6 +496,32 @@ __host__ __device__ inline uint32_t rtc_emitter_pick(const double* __restrict__ 
   return lo;
 }
 
+// Multiple importance sampling of the emitter samples and the diffuse child (rtc_scene_set_emitter_mis):
+// the extra argument of the MIS kernels only.  `mode`: 0 - the emitter kernels' image -, 1 - the balance heuristic;
+// wave-uniform.  `leaf_entry`: one word per depth-first leaf, zero where the leaf is not in the emitter list, else the index
+// of the leaf's first entry (bits 0-15: at most RTC_MAX_EMITTERS) and, from bit 16, one bit per face that the list holds - a
+// cube's +x, -x, +y, -y, +z, -z, a triangle's bit 16 -: the entry of face f is first + popcount(mask & ((1 << f) - 1)),
+// and a face without a bit is not sampled.  Read only by a ray formed as a diffuse child, where the leaf bit is read.
+// `carry`: cos_b of every pending diffuse child, one double per slot of DevPixelMap::ray_stack ([wave][level][lane]), in
+// memory for the levels whose records live in LDS as well; null with mode 0.
+struct DevMis {
+  const uint32_t* __restrict__ leaf_entry;  // [n_leaves]
+  double* __restrict__ carry;
+  uint32_t mode;
+};
+#define RTC_MIS_FACE_SHIFT 16u
+// The two weights of one direction (rtc.h, operation for operation): a = q * (cos_s * cos_e), b = n * (RTC_PI * r2),
+// w_e = b / (b + a), w_b = a / (b + a) - the same sum under both, so that they add up to 1 within a rounding.  cos_s is the
+// cosine at the shaded point (cos_x of a sample, cos_b of a child); the callers apply the skip rules first, so b > 0.  The
+// same code in the kernels and in rtc_diag_mis_weights.
+__host__ __device__ inline void rtc_mis_weights(double n, double q, double cos_s, double cos_e, double r2, double& w_e, double& w_b) {
+  const double a = q * (cos_s * cos_e);
+  const double b = n * (RTC_PI * r2);
+  const double s = b + a;
+  w_e = b / s;
+  w_b = a / s;
+}
+
 struct DevCamera {
   double half_width, half_height, pixel_size;
   double inv[12];  // rows 0..2 of Camera._inverse_transform

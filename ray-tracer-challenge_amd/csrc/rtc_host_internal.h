@@ -79,6 +79,7 @@ struct RtcOptions {
   RtcOption environment_kernels{0.0};  // != 0: the environment kernels even on a handle without an environment, no sky and no sun (tests: against the handle's ordinary kernels)
   RtcOption sky_light_kernels{0.0};    // != 0: the sky-light kernels even on a handle without a sky light, the gain zero (tests: against the handle's ordinary kernels)
   RtcOption indirect_kernels{0.0};     // != 0: the indirect kernels even on a handle without an indirect table, the gain zero and no emission (tests: against the handle's ordinary kernels)
+  RtcOption mis_kernels{0.0};          // != 0: the MIS kernels even on a handle whose MIS mode is 0 or whose emitter list is empty, the mode zero (tests: against the handle's ordinary kernels)
   RtcOption emitter_kernels{0.0};      // != 0: the emitter kernels even on a handle without an emitter list, the count zero (tests: against the handle's ordinary kernels)
   RtcOption denoise_naive{0.0};        // != 0: rtc_denoise_device runs the literal kernel, one thread per pixel (tests and timing: against the tiled one)
   RtcOption film_naive{0.0};           // != 0: a rtc_film_device that blooms runs the literal kernels, one thread per pixel (tests and timing: against the tiled ones)
@@ -245,6 +246,7 @@ struct EmitterTables {
   std::vector<uint32_t> h_leaf;   // per entry: its depth-first leaf
   DevBuf<double> row, cdf;
   DevBuf<uint32_t> leaf_bits;
+  DevBuf<uint32_t> leaf_entry;    // DevMis::leaf_entry: per depth-first leaf, its first entry and its listed faces (rtc_scene_set_emitter_mis)
 };
 
 // A handle's spot lights (rtc_scene_set_spots): DevSpots::row.  Read-only once made: a clone and the band clones share it.
@@ -273,11 +275,13 @@ enum class Family : uint32_t { BASE, MS, MOTION, SPOT, BUMP, TORUS, MESHUV, GLOS
 // The emitter family (rtc_scene_set_emitters) heads the list: the value above INDIR, the indirect family's arguments and
 // DevEmitters.  Named beside the enumeration, whose text the indirect family's tests pin.
 constexpr Family kFamilyEmit = static_cast<Family>(static_cast<uint32_t>(Family::INDIR) + 1u);
-constexpr uint32_t RTC_FAMILIES = 15;
+// The MIS family (rtc_scene_set_emitter_mis) heads the list in its turn: the emitter family's arguments and DevMis.
+constexpr Family kFamilyMis = static_cast<Family>(static_cast<uint32_t>(kFamilyEmit) + 1u);
+constexpr uint32_t RTC_FAMILIES = 16;
 // A family whose occupancy is asked for by the first launch that selects it and not at create: the query loads the unit's
 // code object, and a process none of whose handles has a sky light - or an indirect table, or an emitter list - loads,
 // allocates and runs what it did before the unit existed.
-constexpr bool familyIsLazy(Family f) { return f == Family::SKYL || f == Family::INDIR || f == kFamilyEmit; }
+constexpr bool familyIsLazy(Family f) { return f == Family::SKYL || f == Family::INDIR || f == kFamilyEmit || f == kFamilyMis; }
 
 // Resident work-groups per CU of every family's kernels, [family][tables in LDS ? 0 : 1], and whether they have been asked
 // for (at create, or for a lazy family at its first launch).  A clone takes its source's.
@@ -402,6 +406,9 @@ struct rtc_scene {
   size_t ray_stack_capacity = 0;   // bytes
   void* d_media_stack = nullptr;   // DevMedia::stack_ext: the media kernels' fifth quarter of every pending ray (ensureScratch)
   size_t media_stack_capacity = 0; // bytes: a quarter of ray_stack_capacity, or 0 while no media kernel has run
+  uint32_t emitter_mis = 0;        // rtc_scene_set_emitter_mis: 0 the switch, 1 the balance heuristic (a clone starts with its source's)
+  void* d_mis_carry = nullptr;     // DevMis::carry: cos_b of every pending diffuse child of the MIS kernels (ensureScratch)
+  size_t mis_carry_capacity = 0;   // bytes: an eighth of ray_stack_capacity, or 0 while no MIS kernel has run
   // ---- host output of a large frame (rtc_render): rendered in horizontal bands one after the other, each copied to the
   // caller while the next renders.  A band is a pixel map of its own: the lower bands run on clones of this handle (made on
   // first use), which keep their band's schedule from frame to frame.

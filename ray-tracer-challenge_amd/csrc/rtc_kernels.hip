@@ -2782,6 +2782,13 @@ struct Pending {
   // field, above the path code's 17: the record and its fifth quarter stay.  Compiled into the indirect kernels' unit only.
   uint32_t lin;
 #endif
+#ifdef RTC_MIS_TU
+  // (MIS) cos_b of a ray formed as a diffuse child: the cosine between its direction and the normal it
+  // was drawn about.  The record's tail word is full and its fifth quarter holds two weights: while the ray waits the value
+  // lies in DevMis::carry, a slot of memory per stack level - the levels in LDS included, whose LDS does not grow
+  // (render_body's push_extra / load_extra).  Compiled into the MIS kernels' unit only.
+  double cosb;
+#endif
 };
 #ifdef RTC_INDIR_TU
 static_assert(RTC_MAX_DEPTH < 32, "a Pending's lineage has five bits for its diffuse bounces");
@@ -3120,10 +3127,14 @@ __device__ __noinline__ GlossDir occl_direction(unsigned long long h, uint32_t w
 // points on the listed emissive surfaces and walks a shadow ray to each, in further iterations of the suns' loop, and a ray
 // formed as a diffuse child adds no emission at a listed leaf.  With INDIRECT and everything below it, compiled into the
 // emitter kernels' translation unit only, under RTC_EMIT_TU, which implies RTC_INDIR_TU)
+// (MIS: multiple importance sampling - DevMis, the MIS kernels' extra argument: with mode 1 an emitter sample is weighted by
+// w_e and a ray formed as a diffuse child adds a listed leaf's emission times w_b, the balance heuristic's pair; the child
+// carries cos_b.  With EMIT and everything below it, compiled into the MIS kernels' translation unit only, under
+// RTC_MIS_TU, which implies RTC_EMIT_TU)
 template <bool LDS, bool CSG, int WORLD = 0, int WAVES = 2, bool COOP = false, bool BOX = true, bool AREA = false, bool MS = false,
           bool MOTION = false, bool SPOT = false, bool BUMP = false, bool TORUS = false, bool MESHUV = false, bool GLOSS = false,
           bool OCCL = false, bool SFILT = false, bool MEDIA = false, bool ENV = false, bool SKYL = false, bool INDIRECT = false,
-          bool EMIT = false>
+          bool EMIT = false, bool MIS = false>
 __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& cam, const DevPixelMap& map,
                                             const uint32_t max_depth, double* __restrict__ out,
                                             DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
@@ -3136,7 +3147,8 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
                                             const DevEnvironment& env = DevEnvironment{},
                                             const DevSkyLight& skyl = DevSkyLight{},
                                             const DevIndirect& indir = DevIndirect{},
-                                            const DevEmitters& emit = DevEmitters{}) {
+                                            const DevEmitters& emit = DevEmitters{},
+                                            const DevMis& mis = DevMis{}) {
   static_assert(!AREA || !COOP, "the area kernels run no cooperative iterations");
   static_assert(!MS || !COOP, "the sampling kernels run no cooperative iterations");
   static_assert(!MOTION || (MS && AREA && WORLD == 0), "the motion kernels are the general area-sampling walk");
@@ -3213,6 +3225,14 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
 #else
   static_assert(!EMIT, "emitter sampling is compiled in the emitter translation unit (rtc_emitters.hip) only");
   (void)emit;
+#endif
+  static_assert(!MIS || EMIT, "the MIS kernels are the emitter walk");
+  static_assert(!MIS || !COOP, "the MIS kernels run no cooperative iterations");
+#ifdef RTC_MIS_TU
+  static_assert(MIS, "the MIS translation unit compiles the MIS kernels only: its Pending carries cos_b");
+#else
+  static_assert(!MIS, "multiple importance sampling is compiled in the MIS translation unit (rtc_mis.hip) only");
+  (void)mis;
 #endif
   RTC_PRIO_PHASE(RTC_PRIO_WORK);
 #ifndef RTC_PROFILE
@@ -3433,6 +3453,9 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
   RTC_SET_CODE(cur, 0u);
   RTC_SET_LIN(cur, 0u);
   RTC_MEDIA_START(cur, 0.0);
+#ifdef RTC_MIS_TU
+  cur.cosb = 0.0;
+#endif
   // The lane's pending refraction siblings: a deque.  The lane itself pops the newest entry (depth
   // first); an idle neighbour may take the OLDEST one (the largest sub-tree) through the mailbox.
   // It lives in a buffer of its own rather than in scratch: scratch interleaves the lanes dword by dword,
@@ -3471,9 +3494,22 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
   Quad2* const pend_x_wave = &lds_pend_x[threadIdx.x >> 6][0][0];
   Quad2* const stack_x = static_cast<Quad2*>(media.stack_ext) +
       (static_cast<size_t>(blockIdx.x) * 4u + (threadIdx.x >> 6)) * map.ray_stack_levels * 64u + lane;
+#ifdef RTC_MIS_TU
+  // (MIS) cos_b of a waiting diffuse child: DevMis::carry, laid out as DevPixelMap::ray_stack is, 8 bytes a slot, in memory
+  // for every level - a sixth quarter in LDS would take the LDS form's second work-group per CU.
+  // Written and read only for a ray that carries RTC_LIN_DIFFUSE, with mode 1 (wave-uniform).
+  double* const carry = mis.carry + (static_cast<size_t>(blockIdx.x) * 4u + (threadIdx.x >> 6)) * map.ray_stack_levels * 64u + lane;
+#endif
   auto push_extra = [&](int level, const Pending& p) {
     Quad2 x;
     x.x = dbits(p.weight_g); x.y = dbits(p.weight_b);
+#ifdef RTC_MIS_TU
+    if constexpr (MIS) {
+      if (mis.mode != 0u && (p.lin & RTC_LIN_DIFFUSE) != 0u &&
+          RTC_IN_BOUNDS(RTC_OOB_PENDING, stack_ok && static_cast<uint32_t>(level) < map.ray_stack_levels))
+        carry[static_cast<size_t>(level) * 64u] = p.cosb;
+    }
+#endif
     if (level < LDS_LEVELS) {
       pend_x_wave[level * 64 + lane] = x;
     } else {
@@ -3495,6 +3531,14 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
     }
     p.weight_g = bitsd(x.x);
     p.weight_b = bitsd(x.y);
+#ifdef RTC_MIS_TU
+    if constexpr (MIS) {  // (after load_level: the lineage says whether the slot holds a value)
+      p.cosb = 0.0;
+      if (mis.mode != 0u && (p.lin & RTC_LIN_DIFFUSE) != 0u &&
+          RTC_IN_BOUNDS(RTC_OOB_PENDING, stack_ok && static_cast<uint32_t>(level) < map.ray_stack_levels && of_lane < 64u))
+        p.cosb = (carry + static_cast<size_t>(level) * 64u - lane)[of_lane];
+    }
+#endif
   };
 #endif
 
@@ -4646,6 +4690,19 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
                 ir = (R[12] * R[15]) * geo;
                 ig = (R[13] * R[15]) * geo;
                 ib = (R[14] * R[15]) * geo;
+#ifdef RTC_MIS_TU
+                // (MIS, mode 1) the balance heuristic's weight of the sample, w_e = n * pi * r2 / (n * pi * r2 + q * cos_x *
+                // cos_e): the term but for the filter, times w_e
+                if constexpr (MIS) {
+                  if (mis.mode != 0u) {
+                    double w_e, w_b;
+                    rtc_mis_weights(static_cast<double>(emit.samples), R[15], cos_x, cos_e, r2, w_e, w_b);
+                    ir = ir * w_e;
+                    ig = ig * w_e;
+                    ib = ib * w_e;
+                  }
+                }
+#endif
                 emit_r = r;
                 it_shadow_calls++;
               }
@@ -4787,18 +4844,74 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
         // (EMIT) nothing counted twice: the ray formed as a diffuse child adds no emission at a leaf of the emitter list -
         // its parent's samples counted it.  Only such a ray reads the leaf's bit.
         bool emits_here = indir.emission != nullptr;
+#ifdef RTC_MIS_TU
+        // (MIS, mode 1) the ray formed as a diffuse child adds a listed leaf's emission times w_b = a / (b + a), a = q *
+        // (cos_b * cos_e'), b = n * (pi * t * t): the direction's weight under the balance heuristic, whose other half its
+        // parent's samples took.  cos_e' is against the flat normal the list stores for the face hit - the leaf's word names
+        // its first entry and its faces; a cube's face is the reference's rule for cube normals on the object-space point,
+        // formed again here from the hit's own transform: nothing of it is live across the lights' loop.  (A listed leaf's
+        // root does not move: the point needs no displacement.)  A face the list leaves out, cos_b <= 0, cos_e' == 0 and
+        // t <= 2e-4 - where a sample would have been zero - keep the whole row.  Only such a ray reads the word and the row.
+        double mis_wb = 1.0;
+        if constexpr (MIS) {
+          if (mis.mode != 0u && emits_here && emit.count != 0u && (cur.lin & RTC_LIN_DIFFUSE) != 0u) {
+            const uint32_t lw = mis.leaf_entry[hv.leaf];
+            if (lw != 0u) {
+              const double* __restrict__ Mh;
+              uint32_t kh;
+              if (hv.root != RTC_NO_LEAF) {
+                const RootRec& Rh = recs[RTC_CHECK_INDEX(RTC_OOB_ROOTS, hv.root, RTC_AVAIL(0))];
+                Mh = Rh.inv;
+                kh = Rh.kind_flags & 0xFFu;
+              } else {
+                const uint4 meta = S.leaf_meta[hv.leaf];
+                Mh = S.xf + 12ull * meta.y;
+                kh = meta.x & 0xFFu;
+              }
+              uint32_t face = 0u;
+              if (kh == 2u) {  // cube.zig:81-97: the axis of the largest |coordinate|, x before y before z
+                const double fx = row_pt(Mh + 0, ptx, pty, ptz), fy = row_pt(Mh + 4, ptx, pty, ptz), fz = row_pt(Mh + 8, ptx, pty, ptz);
+                const double ax = __builtin_fabs(fx), ay = __builtin_fabs(fy), az = __builtin_fabs(fz);
+                const double maxc = zmax(ax, zmax(ay, az));
+                if (maxc == ax) face = fx < 0.0 ? 1u : 0u;
+                else if (maxc == ay) face = fy < 0.0 ? 3u : 2u;
+                else face = fz < 0.0 ? 5u : 4u;
+              }
+              const uint32_t mask = lw >> RTC_MIS_FACE_SHIFT;
+              if (((mask >> face) & 1u) != 0u) {
+                const uint32_t entry = (lw & 0xFFFFu) + static_cast<uint32_t>(__builtin_popcount(mask & ((1u << face) - 1u)));
+                const double* __restrict__ R = emit.row + static_cast<size_t>(RTC_EMITTER_ROW) * entry;
+                const double cos_e = __builtin_fabs((R[9] * ray.dx + R[10] * ray.dy) + R[11] * ray.dz);
+                if (!(cur.cosb <= 0.0) && !(cos_e == 0.0) && !(t <= 2e-4)) {
+                  double w_e;
+                  rtc_mis_weights(static_cast<double>(emit.samples), R[15], cur.cosb, cos_e, t * t, w_e, mis_wb);
+                }
+              }
+            }
+          }
+        }
+#endif
         if constexpr (EMIT) {
           if (emits_here && emit.count != 0u && (cur.lin & RTC_LIN_DIFFUSE) != 0u)
-            emits_here = ((emit.leaf_bits[hv.leaf >> 5] >> (hv.leaf & 31u)) & 1u) == 0u;
+#ifdef RTC_MIS_TU
+            if (!(MIS && mis.mode != 0u))  // (mode 0: the emitter kernels' rule)
+#endif
+            emits_here =((emit.leaf_bits[hv.leaf >> 5] >> (hv.leaf & 31u)) & 1u) == 0u;
         }
         if (emits_here) {
 #else
         if (indir.emission != nullptr) {
 #endif
           const double* __restrict__ EM = indir.emission + 3ull * mat_index;
+#ifdef RTC_MIS_TU
+          sr = sr + EM[0] * mis_wb;
+          sg = sg + EM[1] * mis_wb;
+          sb = sb + EM[2] * mis_wb;
+#else
           sr = sr + EM[0];
           sg = sg + EM[1];
           sb = sb + EM[2];
+#endif
         }
         ind_r = color.r * mat.diffuse;
         ind_g = color.g * mat.diffuse;
@@ -4915,6 +5028,9 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
         q.remaining = cur.remaining - 1u;
         q.code = 2u * cur.code;
         q.lin = (d + 1u) | RTC_LIN_DIFFUSE;
+#ifdef RTC_MIS_TU
+        q.cosb = (dd.x * nx + dd.y * ny) + dd.z * nz;  // (MIS) cos_b: the direction against the normal it was drawn about
+#endif
         it_secondary++;
         if (do_reflect || do_refract) {
           if (sp < stack_cap) {
@@ -4937,6 +5053,9 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
       RTC_MEDIA_KID(child, cur, w_reflect, cur.medium);  // (MEDIA: a reflected child stays in its parent's medium)
       RTC_SET_CODE(child, 2u * cur.code);
       RTC_SET_LIN(child, cur.lin & RTC_LIN_D);  // (INDIRECT: its parent's d; not a diffuse child)
+#ifdef RTC_MIS_TU
+      child.cosb = 0.0;
+#endif
 #ifdef RTC_GLOSS_TU
       if (rough_r > 0.0) {
         const GlossDir g = gloss_scatter(gloss_h, child.code, rough_r, child.ray.dx, child.ray.dy, child.ray.dz, nx, ny, nz, false);
@@ -4958,6 +5077,9 @@ __device__ __forceinline__ void render_body(const DevScene& S, const DevCamera& 
       p.remaining = cur.remaining - 1u;
       RTC_SET_CODE(p, 2u * cur.code + 1u);
       RTC_SET_LIN(p, cur.lin & RTC_LIN_D);
+#ifdef RTC_MIS_TU
+      p.cosb = 0.0;
+#endif
 #ifdef RTC_GLOSS_TU
       if (rough_t > 0.0) {
         const GlossDir g = gloss_scatter(gloss_h, p.code, rough_t, p.ray.dx, p.ray.dy, p.ray.dz, nx, ny, nz, true);
@@ -5993,6 +6115,34 @@ rtc_render_kernel_bump_bigworld(const DevScene S, const DevCamera cam, const Dev
                                 const DevBumps bumps) {
   render_body<false, true, 0, 2, false, true, true, true, true, true, true>(S, cam, map, max_depth, out, stats, next_stats, area, smp, mo,
                                                                             spots, bumps);
+}
+
+#elif defined(RTC_MIS_TU)
+
+// Multiple importance sampling (rtc_scene_set_emitter_mis): the emitter walk with the balance
+// heuristic's weights on the emitter samples and on the diffuse child's hit of a listed leaf, and the mode, the per-leaf entry
+// words and the carry buffer of cos_b (DevMis) as one more argument; one pair for every world.  Every other kernel is compiled
+// without it.
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_mis(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                      double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                      const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots, const DevBumps bumps,
+                      const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl, const DevShadowFilter sfilt,
+                      const DevMedia media, const DevEnvironment env, const DevSkyLight skyl, const DevIndirect indir,
+                      const DevEmitters emit, const DevMis mis) {
+  render_body<true, true, 0, 2, false, true, true, true, true, true, true, true, true, true, true, true, true, true, true, true, true, true>(
+      S, cam, map, max_depth, out, stats, next_stats, area, smp, mo, spots, bumps, muv, gloss, occl, sfilt, media, env, skyl, indir, emit, mis);
+}
+
+extern "C" __global__ void __launch_bounds__(256, RTC_LB2)
+rtc_render_kernel_mis_bigworld(const DevScene S, const DevCamera cam, const DevPixelMap map, const uint32_t max_depth,
+                               double* __restrict__ out, DevStats* __restrict__ stats, DevStats* __restrict__ next_stats,
+                               const DevAreaLights area, const DevSampling smp, const DevMotion mo, const DevSpots spots,
+                               const DevBumps bumps, const DevMeshUvs muv, const DevGloss gloss, const DevOcclusion occl,
+                               const DevShadowFilter sfilt, const DevMedia media, const DevEnvironment env, const DevSkyLight skyl,
+                               const DevIndirect indir, const DevEmitters emit, const DevMis mis) {
+  render_body<false, true, 0, 2, false, true, true, true, true, true, true, true, true, true, true, true, true, true, true, true, true, true>(
+      S, cam, map, max_depth, out, stats, next_stats, area, smp, mo, spots, bumps, muv, gloss, occl, sfilt, media, env, skyl, indir, emit, mis);
 }
 
 #elif defined(RTC_EMIT_TU)

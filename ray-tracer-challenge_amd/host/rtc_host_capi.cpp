@@ -292,6 +292,16 @@ int rtch_scene_emitters(void* h, rtc_emitters* out, int* present) {
   });
 }
 
+// The "mis" key inside the scene's "emitters" (DESIGN.md section 32), as rtc_scene_set_emitter_mis takes it: 1 where the file
+// has the key and it is true, else 0.
+int rtch_scene_emitter_mis(void* h, uint32_t* mode) {
+  return guarded([&] {
+    const HostScene* hs = static_cast<HostScene*>(h);
+    if (!mode) throw rtc::Error("InvalidArgument", "emitter mis: null argument");
+    *mode = (hs->info.emitters_present && hs->info.emitters_mis) ? 1u : 0u;
+  });
+}
+
 // The triangles' texture rows (RTC_TEX_MESH), in tri_* order, as rtc_scene_set_mesh_uvs takes them.
 int rtch_scene_mesh_uvs(void* h, double* uv, uint32_t n) {
   return guarded([&] {
@@ -448,6 +458,7 @@ int rtch_scene_render(void* h, uint32_t width, uint32_t height, uint32_t max_dep
       if (st == RTC_OK && hs->info.emitters_present) {  // (emitter sampling: the list is derived from the tables set above)
         const rtc_emitters em{hs->info.emitters_samples, hs->info.emitters_seed};
         st = rtc_scene_set_emitters(scene, &em);
+        if (st == RTC_OK) st = rtc_scene_set_emitter_mis(scene, hs->info.emitters_mis ? 1u : 0u);  // (after the emitter table)
       }
       const rtc::CameraSampling& cs = hs->info.sampling;
       if (cs.robust && st == RTC_OK) {  // (bucket sums and their resolve, then the file's denoiser and film stage, section 31)

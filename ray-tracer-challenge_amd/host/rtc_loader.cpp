@@ -969,13 +969,19 @@ SceneInfo parseScene(const std::string& scene_json, const FileLoader& load_file_
           info.emitters_present = true;
           info.emitters_samples = static_cast<uint32_t>(wholeOf(*em, samples_are, 1.0, 16.0));
         } else if (em->type == Value::Object) {
-          checkFields(*em, {"samples", "seed"}, "emitters");
+          checkFields(*em, {"samples", "seed", "mis"}, "emitters");
           info.emitters_present = true;
+          // "mis" (DESIGN.md section 32): the samples and the diffuse child weighted by the balance heuristic; false: as
+          // without the key
+          if (const Value* mi = em->find("mis")) {
+            if (mi->type != Value::Bool) throw Error("InvalidData", "emitters: mis is true or false");
+            info.emitters_mis = mi->b;
+          }
           if (const Value* n = em->find("samples")) info.emitters_samples = static_cast<uint32_t>(wholeOf(*n, samples_are, 1.0, 16.0));
           if (const Value* sd = em->find("seed"))
             info.emitters_seed = static_cast<uint64_t>(wholeOf(*sd, "emitters: seed is a whole number from 0 to 2^53", 0.0, 0x1p53));
         } else {
-          throw Error("InvalidData", "indirect: emitters is true, a sample count or {\"samples\", \"seed\"}");
+          throw Error("InvalidData", "indirect: emitters is true, a sample count or {\"samples\", \"seed\", \"mis\"}");
         }
       }
     } else {

@@ -97,6 +97,8 @@ struct SceneInfo {  // scene.zig:608-610
   bool emitters_present = false;
   uint32_t emitters_samples = 1u;
   uint64_t emitters_seed = 0u;
+  // the "mis" key inside the object form of "emitters" (section 32): rtc_scene_set_emitter_mis' mode 1; false without the key
+  bool emitters_mis = false;
 };
 
 // scene.zig:612-661.  Throws rtc::Error whose .name is the Zig error name

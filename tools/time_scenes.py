@@ -74,6 +74,9 @@ table.  With --passes the noise run has the same table.
 --emitters N|off: emitter sampling with N samples per hit (rtc_scene_set_emitters) instead of the scene file's
 own "emitters" key, which is applied otherwise; --emitters off applies no table.  Option emitter_kernels=1 times the emitter kernels
 without a list.  With --passes the noise run has the same table.
+--mis on|off: multiple importance sampling of the emitter samples and the diffuse child (rtc_scene_set_emitter_mis; DESIGN.md section
+32) instead of the scene file's own "mis" key, which is applied otherwise.  Option mis_kernels=1 times the MIS kernels with mode 0.
+With --passes the noise run has the same mode.
 --denoise [R:F:k]: the denoiser (rtc_denoise_device) at radius R, patch F and strength k (7:2:0.45 without
 a value) over the mean of 8 progressive passes of the timed handle: prints the time of one call in the tiled form and in the
 literal one (option denoise_naive), each taken twice, alternating, with device events around 20 launches after a warm-up, and
@@ -138,6 +141,7 @@ ap.add_argument("--environment", default="")
 ap.add_argument("--sky-light", default="")
 ap.add_argument("--indirect", default="")
 ap.add_argument("--emitters", default="")
+ap.add_argument("--mis", default="", choices=["", "on", "off"])
 ap.add_argument("--denoise", nargs="?", const="7:2:0.45", default="")
 ap.add_argument("--film", nargs="?", const="12", default="")
 ap.add_argument("--robust", nargs="?", const="5", default="")
@@ -381,6 +385,13 @@ def emitters_table(hs):
     return hs.emitters()
 
 
+def mis_mode(hs):
+    """the scene file's MIS mode, or --mis'"""
+    if args.mis:
+        return 1 if args.mis == "on" else 0
+    return hs.emitter_mis()
+
+
 def light_table(hs, how):
     """(None, or the LightDesc that --lights asks for)"""
     if not how:
@@ -597,6 +608,7 @@ for name, w, h, depth in cases:
             gpu.set_indirect(indirect)
         if emitters_table(hs) is not None:
             gpu.set_emitters(emitters_table(hs))
+        gpu.set_emitter_mis(mis_mode(hs))
         for i in range(args.settle):
             gpu.render_device(cam, canvas.data_ptr(), depth, None, stream.cuda_stream)
         torch.cuda.synchronize()
@@ -627,7 +639,7 @@ for name, w, h, depth in cases:
     if delta is not None: line += f" maxdelta {delta:.2e}"
     if args.lights or args.spot or "spot_kernels=1" in args.option:
         line += f" shadow_traced {st['shadow_traced']} ns/shadow-ray {min(ts) * 1e6 / max(1, st['shadow_traced']):.3f}"
-    if args.sampling or args.option or args.passes >= 0 or args.motion or args.spot or args.bump or args.torus or args.meshuv or args.gloss or args.occlusion or args.shadow_filter or args.media or args.environment or args.sky_light or args.indirect or args.emitters:
+    if args.sampling or args.option or args.passes >= 0 or args.motion or args.spot or args.bump or args.torus or args.meshuv or args.gloss or args.occlusion or args.shadow_filter or args.media or args.environment or args.sky_light or args.indirect or args.emitters or args.mis:
         line += f" primary {st['primary']} ns/primary-ray {min(ts) * 1e6 / max(1, st['primary']):.3f}"
     if acc:
         ms, copy_ms, nbytes = min(a[0] for a in acc), min(a[1] for a in acc), acc[0][2]
@@ -647,6 +659,7 @@ for name, w, h, depth in cases:
         if sky_light_table(hs) is not None: gpu.set_sky_light(sky_light_table(hs))
         if indirect_table(hs) is not None: gpu.set_indirect(indirect_table(hs))
         if emitters_table(hs) is not None: gpu.set_emitters(emitters_table(hs))
+        gpu.set_emitter_mis(mis_mode(hs))
         prog = rtc.Progressive(gpu, cam, depth)
         noise = {}
         for i in range(1, 65):
